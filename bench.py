@@ -2,6 +2,16 @@
 """Headline benchmark: pose-candidates x beams scored per second (BASELINE.json).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload auto|cfg2|cfg4]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line: the contract's fields,
+`roofline` / `roofline_hbm` (the timed launches' HIP events against the committed counters)
+and the result of the last step.  --full adds every side leg that takes runs of its own: the
+CPU baselines, the PCIe-inclusive host call, the particle filter, the cfg-1 / cfg-4 / cfg-5
+anchors, the node's default search, the C-ABI multi-device probe and, for N > 1, the whole
+lattice on one GPU, the in-grid share and the sharded particle step.  --dump-outputs DIR writes
+what the last timed step returned (float64 .npy, rank 0): `match_records` (the [N, 12] record
+table) and matchScan's `score`, `pose`, `covariance` and `best_index` (-1: no winner).
 
 A "step" is one pass of the hot path -- ScanMatcherNDT::matchScan's search (reference
 src/scan_matcher_ndt.cpp:103-143) -- over one lattice, inputs resident in HBM.
@@ -959,7 +969,13 @@ def main():
                          "gpurun_out/bench_detail.json when that directory exists); stdout carries the short line")
     ap.add_argument("--prewarm", type=float, default=PREWARM_SECONDS,
                     help="seconds of untimed launches before --warmup (profiler passes use 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side legs (CPU baselines, other workloads and sizes, the C-ABI probe)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.dump_outputs and args.host == "c":
+        ap.error("--dump-outputs writes the Python host's timed steps; --host c times the C probe")
 
     if args.print_source_hash:
         print(source_hash())
@@ -1151,10 +1167,12 @@ def main():
     best_score, best_index, acc = shard.combine_match_records(rec)
     result = m.finish_match(np.concatenate([[best_score, -1.0 if best_index is None else best_index], acc]))
     variant = m.last_variant()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, rec, result, best_index)
 
     # ---- N > 1: the same whole lattice on ONE GPU, measured by rank 0 in this job ----
     single = None
-    if world > 1 and rank == 0:
+    if world > 1 and rank == 0 and args.full:
         ms1 = []
         for i in range(4):
             torch.cuda.synchronize()
@@ -1171,7 +1189,7 @@ def main():
 
     # ---- cfg-5: sharded ParticleFilter::measure (N > 1 or forced collective) ----
     pf5 = None
-    if collective and not args.no_particles:
+    if collective and args.full and not args.no_particles:
         pf5 = particle_bench_sharded(ScanMatcherNDT, synth, shard, torch, dist, dev, dev_index, rank,
                                      world, backend, all_reduce, fence)
 
@@ -1227,14 +1245,14 @@ def main():
         if collective:
             line["rccl_world_size"] = dist.get_world_size() if backend == "nccl" else None
             line["collective_backend"] = backend
-        if cfg == 4:
+        if cfg == 4 and args.full:
             share = in_grid_share(np, synth, params, guess, pts, grid)
             line["config"]["in_grid_share_of_units"] = share
             line["value_in_grid_units"] = line["value"] * share
             if single is not None:
                 line["single_gpu_same_workload"] = single
                 line["speedup_vs_single_gpu_same_workload"] = single["ms_per_step"] / ms_per_step
-        if world == 1 and cfg == 2:
+        if world == 1 and cfg == 2 and args.full:
             # PCIe-inclusive figure (never `value`): the whole matchScan call with host
             # buffers in and out (subsample, tables, H2D, search, D2H of the 12-double record)
             m.set_stream(None)
@@ -1245,19 +1263,19 @@ def main():
                 e2e.append(time.perf_counter() - t0)
             line["host_call"] = {"ms": min(e2e) * 1e3, "value": total_units / min(e2e),
                                  "what": "ndt2d_matcher_match_scan, host buffers in/out"}
-        if world == 1 and cfg == 2 and not args.no_cpu_baseline:
+        if args.full and world == 1 and cfg == 2 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(synth.matcher_params(2), synth.map_scans(2),
                                                 *synth.query_scan(2)[:2])
-        elif cfg == 4:
+        elif args.full and cfg == 4:
             line["cpu_baseline"] = committed_cpu_baseline("cfg4_match")
             if pf5 is not None:
                 pf5["cpu_baseline"] = committed_cpu_baseline("cfg5_particles")
-        if world == 1 and not args.no_particles:
+        if world == 1 and args.full and not args.no_particles:
             m.set_stream(None)
             line["particle_filter"] = particle_bench_1gpu(ScanMatcherNDT, synth, torch, dev_index, pmc, n_cu)
         if pf5 is not None:
             line["particle_filter_cfg5" if world == 1 else "particle_filter"] = pf5
-        if world == 1 and cfg == 2 and not args.no_anchors:
+        if world == 1 and cfg == 2 and args.full and not args.no_anchors:
             # the single-GPU points of the two 8-GPU workloads (BASELINE.json configs[3], [4])
             m.set_stream(None)
             a4 = cfg4_single_gpu_bench(ScanMatcherNDT, synth, shard, np, torch, dev_index)
@@ -1275,12 +1293,12 @@ def main():
                     torch.cuda.synchronize)
                 a5["cpu_baseline"] = committed_cpu_baseline("cfg5_particles")
                 line["cfg5_single_gpu"] = a5
-        if world == 1 and not args.no_default_search:
+        if world == 1 and args.full and not args.no_default_search:
             line["default_search"] = default_search_bench(ScanMatcherNDT, synth, dev_index,
                                                           with_cpu=not args.no_cpu_baseline)
             line["cfg1_search"] = cfg1_search_bench(ScanMatcherNDT, synth, dev_index,
                                                     not args.no_cpu_baseline)
-        if not args.no_c_host:
+        if (args.full or args.host == "c") and not args.no_c_host:
             # ONE matcher over all N GPUs through the plain-C host (the unchanged node's
             # global_scan_matcher_->matchScan with the plugin's device_ids parameter); the other
             # ranks idle at the barrier below meanwhile
@@ -1502,6 +1520,16 @@ def c_host_multi_device(ids):
                    "dealing_overhead = the dealt call against the one-device call on workloads too small to matter; "
                    "host exchange at the top level, the RCCL exchange under `rccl`" % ids)
     return out
+
+
+def dump_outputs(where, rec, result, best_index):
+    """--dump-outputs: what the last timed step returned to its caller, as float64 arrays."""
+    import numpy as np
+    os.makedirs(where, exist_ok=True)
+    arrays = {"match_records": rec, "score": [result["score"]], "pose": result["pose"],
+              "covariance": result["covariance"], "best_index": [-1 if best_index is None else best_index]}
+    for name, a in arrays.items():
+        np.save(os.path.join(where, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def profile_shares():

@@ -10,8 +10,8 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/prof_$TAG
 rm -rf $O && mkdir -p $O
-BENCH="python3 $R/bench.py --steps 4 --warmup 2 --prewarm 0 --no-cpu-baseline --no-default-search --no-anchors --no-c-host"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 $R/bench.py --steps 200 --warmup 10 --no-cpu-baseline --no-default-search --no-anchors --no-c-host > $O/kt.log 2>&1
+BENCH="python3 $R/bench.py --full --steps 4 --warmup 2 --prewarm 0 --no-cpu-baseline --no-default-search --no-anchors --no-c-host"
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 $R/bench.py --full --steps 200 --warmup 10 --no-cpu-baseline --no-default-search --no-anchors --no-c-host > $O/kt.log 2>&1
 find $O/kt -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/kernel_stats.csv
 pass() {
   name=$1; shift
@@ -39,9 +39,9 @@ spass write WRITE_SIZE
 python3 $R/experiments/pmc_shares.py $O $(python3 $R/bench.py --print-source-hash) > $O/shares_summary.txt 2>> $O/pmc_to_json.err
 # the plain bench lines LAST, with this session's counters in place (bench.py reads profiles/r05_pmc.json)
 cp $O/pmc.json $R/profiles/r05_pmc.json
-python3 $R/bench.py > $O/bench.json 2> $O/bench.err
-python3 $R/bench.py --steps 20 --warmup 5 > $O/bench_driver_flags.json 2>> $O/bench.err
-NDT2D_BENCH_BACKEND=gloo python3 $R/bench.py --gpus 8 --steps 4 --warmup 2 > $O/bench_8ranks_one_gpu_gloo.json 2>> $O/bench.err
+python3 $R/bench.py --full > $O/bench.json 2> $O/bench.err
+python3 $R/bench.py --full --steps 20 --warmup 5 > $O/bench_driver_flags.json 2>> $O/bench.err
+NDT2D_BENCH_BACKEND=gloo python3 $R/bench.py --full --gpus 8 --steps 4 --warmup 2 > $O/bench_8ranks_one_gpu_gloo.json 2>> $O/bench.err
 # the multi-device matcher through the plain-C probe (dealing overhead, fan-out, cfg-5 sharded by default)
 bash $R/experiments/profile_multi_device_r05.sh > $O/multi_device.log 2>&1
 cp $R/gpurun_out/r05/multi_device/summary.json $O/multi_device_summary.json

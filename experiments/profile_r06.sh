@@ -10,8 +10,8 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/prof_$TAG
 rm -rf $O && mkdir -p $O
-BENCH="python3 $R/bench.py --steps 4 --warmup 2 --prewarm 0 --no-cpu-baseline --no-default-search --no-anchors --no-c-host"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 $R/bench.py --steps 200 --warmup 10 --no-cpu-baseline --no-default-search --no-anchors --no-c-host > $O/kt.log 2>&1
+BENCH="python3 $R/bench.py --full --steps 4 --warmup 2 --prewarm 0 --no-cpu-baseline --no-default-search --no-anchors --no-c-host"
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 $R/bench.py --full --steps 200 --warmup 10 --no-cpu-baseline --no-default-search --no-anchors --no-c-host > $O/kt.log 2>&1
 find $O/kt -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/kernel_stats.csv
 pass() {
   name=$1; shift
@@ -47,9 +47,9 @@ NDT2D_HIP_LIB=$R/experiments/bin/lane_paths.so python3 $R/experiments/lane_paths
 python3 $R/experiments/lane_path_mix.py $R/profiles/r06_lane_paths.json $R/profiles/r06_pmc.json > $R/profiles/r06_lane_path_mix.json 2> $O/lane_path_mix.err
 cp $R/profiles/r06_valu_mix.json $R/profiles/r06_lane_paths.json $R/profiles/r06_lane_path_mix.json $O/
 # the plain bench lines LAST: stdout = the short line the driver parses, --detail-file = the full record
-python3 $R/bench.py --detail-file $O/bench_detail.json > $O/bench.json 2> $O/bench.err
-python3 $R/bench.py --steps 20 --warmup 5 --detail-file $O/bench_driver_flags_detail.json > $O/bench_driver_flags.json 2>> $O/bench.err
-NDT2D_BENCH_BACKEND=gloo python3 $R/bench.py --gpus 8 --steps 4 --warmup 2 --detail-file $O/bench_8ranks_one_gpu_gloo_detail.json > $O/bench_8ranks_one_gpu_gloo.json 2>> $O/bench.err
+python3 $R/bench.py --full --detail-file $O/bench_detail.json > $O/bench.json 2> $O/bench.err
+python3 $R/bench.py --full --steps 20 --warmup 5 --detail-file $O/bench_driver_flags_detail.json > $O/bench_driver_flags.json 2>> $O/bench.err
+NDT2D_BENCH_BACKEND=gloo python3 $R/bench.py --full --gpus 8 --steps 4 --warmup 2 --detail-file $O/bench_8ranks_one_gpu_gloo_detail.json > $O/bench_8ranks_one_gpu_gloo.json 2>> $O/bench.err
 wc -c $O/bench.json $O/bench_driver_flags.json $O/bench_8ranks_one_gpu_gloo.json
 # the multi-device matcher through the plain-C probe (dealing overhead, fan-out, cfg-5 sharded by default)
 bash $R/experiments/profile_multi_device_r06.sh > $O/multi_device.log 2>&1

@@ -137,7 +137,7 @@ def test_rccl_single_rank_runs_the_production_collectives(tmp_path):
 
 
 def test_bench_with_eight_ranks_on_one_gpu_finds_the_cfg4_winner(tmp_path):
-    """Plain `python bench.py --gpus 8`: bench.py starts the driver's own launch command
+    """`python bench.py --gpus 8 --full`: bench.py starts the driver's own launch command
     (torch.distributed.run, 8 ranks) as a child process and relays rank 0's line; here
     the ranks share this box's one GPU and exchange through gloo
     (NDT2D_BENCH_BACKEND=gloo): BASELINE.json configs[3] strong-scaled over 8 round-robin
@@ -150,7 +150,7 @@ def test_bench_with_eight_ranks_on_one_gpu_finds_the_cfg4_winner(tmp_path):
     env.pop("WORLD_SIZE", None)
     detail8 = os.path.join(str(tmp_path), "detail8.json")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
-           "--detail-file", detail8]
+           "--full", "--detail-file", detail8]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1200, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     # stdout: ONE short line (the driver's contract); the full record is in the detail file
@@ -188,7 +188,7 @@ def test_bench_with_eight_ranks_on_one_gpu_finds_the_cfg4_winner(tmp_path):
     env1 = dict(env, NDT2D_BENCH_FORCE_COLLECTIVE="1")
     detail1 = os.path.join(str(tmp_path), "detail1.json")
     r1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cfg2", "--steps", "2",
-                         "--warmup", "1", "--no-cpu-baseline", "--no-default-search", "--no-anchors",
+                         "--warmup", "1", "--full", "--no-cpu-baseline", "--no-default-search", "--no-anchors",
                          "--detail-file", detail1],
                         capture_output=True, text=True, timeout=1200, env=env1, cwd=ROOT)
     assert r1.returncode == 0, r1.stderr[-3000:]
