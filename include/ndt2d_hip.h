@@ -147,7 +147,8 @@ int ndt2d_has_grid(ndt2d_handle h);
 
 /* Upload the beam endpoints of one scan, robot frame, already subsampled to
  * min(laser_max_beams, points.size()) points by the caller
- * (src/scan_matcher_ndt.cpp:95-96,110 / :165-166,171). */
+ * (src/scan_matcher_ndt.cpp:95-96,110 / :165-166,171).  Beams are taken as given: finite,
+ * within +-1e200 m (see "Points off the grid" at ndt2d_host_build_grid_ex). */
 int ndt2d_set_beams(ndt2d_handle h, const double * beams_xy, size_t n_beams);
 
 /* Upload the search lattice of matchScan.  dth[n_th] / dlin[n_lin] are the
@@ -710,7 +711,26 @@ int ndt2d_host_build_grid(double ndt_resolution, double range_max, const double 
  * reference's loop as it stands (src/ndt_model.cpp:132-152), instead of the four quarters of a
  * scan side by side (csrc/ndt2d_host.cpp HostNdt::add_scan) -- the two give the same bits, and
  * tests/test_host_logic.py holds them to it; NDT2D_BUILD_CLOSED_FORM takes the closed-form
- * eigenvalues (ndt2d_matcher_set_eigenvalue_form "closed"). */
+ * eigenvalues (ndt2d_matcher_set_eigenvalue_form "closed").
+ *
+ * Points off the grid.  Every index of the library -- the host build's two loops, the host
+ * single-pose scoring, the device build and every search and pose kernel -- takes a point as
+ * outside the grid when
+ *   !(x >= origin_x) || !(y >= origin_y) || !(fx < size_x) || !(fy < size_y),
+ * fx, fy the double quotients (x - origin) / cell_size, compared before any integer cast.  For a
+ * finite point less than 2^32 cells from the origin this is NDT::getIndex (reference
+ * src/ndt_model.cpp:203-218) exactly.  A NaN or infinite coordinate, or one 2^32 cells or more
+ * away, is outside: there the reference converts an out-of-range double to unsigned int, which is
+ * undefined, and this is the one place where the library departs from the literal reference.
+ * Such a point adds nothing to a cell and +0.0 to a likelihood (src/ndt_model.cpp:169), as any
+ * finite point off the grid does.  The device scorers send it to a sentinel record whose arithmetic
+ * would make a NaN or infinite beam NaN, so the matcher layer hands such beams on as finite far
+ * points: a beam with a coordinate outside +-1e200 m as (-1e300, -1e300) (csrc/ndt2d_host.cpp
+ * subsample_into), and for ndt2d_matcher_match_laser_scan, which converts and subsamples on the
+ * device, a kept infinite range as +-FLT_MAX (off_grid_ranges).  The device layer takes its beams as
+ * given: a caller of ndt2d_set_beams, ndt2d_set_search_beams or ndt2d_score_poses_beams(_launch)
+ * passes beams within +-1e200 m (or far finite stand-ins such as (-1e300, -1e300)); a NaN or
+ * infinite beam there scores NaN. */
 #define NDT2D_BUILD_SEQUENTIAL 1u
 #define NDT2D_BUILD_CLOSED_FORM 2u
 int ndt2d_host_build_grid_ex(double ndt_resolution, double range_max, const double * poses_xyt,

@@ -160,22 +160,27 @@ public:
     cell_size_ = cell_size;
     size_x_ = sx;
     size_y_ = sy;
+    fsize_x_ = static_cast<double>(sx);
+    fsize_y_ = static_cast<double>(sy);
     origin_x_ = origin_x;
     origin_y_ = origin_y;
   }
 
-  // NDT::getIndex, reference src/ndt_model.cpp:203-218
+  // NDT::getIndex, reference src/ndt_model.cpp:203-218, with the off-grid rule of
+  // include/ndt2d_hip.h: the four comparisons on the double quotients, before any integer cast
+  // (for f >= 0, trunc(f) < size <=> f < size; NaN, +-inf and points 2^32 cells away are outside)
   __attribute__((always_inline)) long index(double x, double y) const
   {
+    // (written with ordered compares only, `a < b`: a NaN falls through the first test and fails
+    // the second -- no extra branch on the unordered flag)
     if (x < origin_x_ || y < origin_y_) return -1;
     // (a power-of-two cell size: multiplying by its exact reciprocal is the correctly
     // rounded quotient, bit-identical to the reference's divide)
     const double fx = pow2_ ? (x - origin_x_) * inv_cell_size_ : (x - origin_x_) / cell_size_;
     const double fy = pow2_ ? (y - origin_y_) * inv_cell_size_ : (y - origin_y_) / cell_size_;
-    const unsigned int gx = static_cast<unsigned int>(static_cast<long long>(fx));
-    const unsigned int gy = static_cast<unsigned int>(static_cast<long long>(fy));
-    if (gx >= size_x_ || gy >= size_y_) return -1;
-    return static_cast<long>(gy * size_x_ + gx);
+    if (fx < fsize_x_ && fy < fsize_y_)
+      return static_cast<long>(static_cast<unsigned int>(fy) * size_x_ + static_cast<unsigned int>(fx));
+    return -1;
   }
 
   // NDT::addScan, reference src/ndt_model.cpp:132-152.
@@ -479,6 +484,7 @@ private:
   double cell_size_ = 0.0, inv_cell_size_ = 0.0;
   bool pow2_ = false;
   size_t size_x_ = 0, size_y_ = 0;
+  double fsize_x_ = 0.0, fsize_y_ = 0.0;   // (the sizes as index() compares them)
   double origin_x_ = 0.0, origin_y_ = 0.0;
   std::vector<HostCell> cells_;     // a pool: the first n_cells_ are the grid
   size_t n_cells_ = 0;
@@ -562,6 +568,47 @@ bool offsets_fit(double size, double res, size_t limit)
   return 2.0 * size / res <= static_cast<double>(limit) - 2.0;
 }
 
+// The off-grid rule (include/ndt2d_hip.h) for the beams the device scores.  A beam with a NaN or
+// infinite coordinate is off the grid for every pose, but the device scorers send a point off the
+// grid to a sentinel record (mean (1e300, 0), information -1) whose arithmetic turns it into exp(NaN);
+// and a beam near 1e300 lands near that mean and scores exp(-q^2) > 0.  A beam with a coordinate
+// outside +-1e200 m (off any grid a scan reaches) is therefore handed on as (-1e300, -1e300): 1.4e300
+// from every pose and at least 4e299 from the sentinel's mean -- exponent -inf, term +0.0, what the
+// reference adds for a point off the grid.  (The host scorers give it the same +0.0.)
+constexpr double kOffGridBeamBound = 1.0e200;
+constexpr double kOffGridBeam = -1.0e300;
+
+// The same rule for matchLaserScan, whose conversion and subsampling run on the device: a range the
+// conversion keeps (reference src/ndt_mapper.cpp:413,436 drop NaN and range > range_max only) and that is
+// infinite -- -inf, REP-117 "too close", or +inf under an infinite range_max -- converts to a point
+// with an infinite or NaN coordinate, which the device would score as NaN.  Such a range goes to the
+// device as +-FLT_MAX, which the conversion keeps as well: a finite point 3.4e38 m out, off the grid
+// and scored +0.0 like the original.  (Every other kept range converts to a finite point within
+// FLT_MAX of the laser; the laser and motion transforms are taken as finite.)  Returns the ranges to
+// upload: `ranges` itself unless one needed changing.  One pass over the ranges on the host.
+const float * off_grid_ranges(std::vector<float> & scratch, const float * ranges, size_t n_ranges,
+                              double range_max)
+{
+  size_t first = n_ranges;
+  for (size_t i = 0; i < n_ranges; ++i)
+  {
+    if (std::isinf(ranges[i]) && !(ranges[i] > range_max))
+    {
+      first = i;
+      break;
+    }
+  }
+  if (first == n_ranges) return ranges;
+  scratch.assign(ranges, ranges + n_ranges);
+  for (size_t i = first; i < n_ranges; ++i)
+  {
+    const float r = scratch[i];
+    const float f = std::copysign(FLT_MAX, r);
+    if (std::isinf(r) && !(r > range_max) && !(f > range_max)) scratch[i] = f;
+  }
+  return scratch.data();
+}
+
 // Subsampling of matchScan / scorePoints, reference src/scan_matcher_ndt.cpp:95-96,110.
 void subsample_into(std::vector<double> & out, const double * pts, size_t n_points,
                     size_t laser_max_beams)
@@ -570,11 +617,22 @@ void subsample_into(std::vector<double> & out, const double * pts, size_t n_poin
   out.resize(2 * use);
   if (use == 0) return;
   const double scan_step = static_cast<double>(n_points) / use;
+  // (the copy as it stands with one branch-free flag, and the far beams replaced in a second pass
+  // only when there are any)
+  bool far = false;
   for (size_t i = 0; i < use; ++i)
   {
     const size_t idx = static_cast<size_t>(i * scan_step);
-    out[2 * i] = pts[2 * idx];
-    out[2 * i + 1] = pts[2 * idx + 1];
+    const double x = pts[2 * idx], y = pts[2 * idx + 1];
+    out[2 * i] = x;
+    out[2 * i + 1] = y;
+    far |= !(std::fabs(x) <= kOffGridBeamBound) | !(std::fabs(y) <= kOffGridBeamBound);
+  }
+  if (!far) return;
+  for (size_t i = 0; i < use; ++i)
+  {
+    const bool near = std::fabs(out[2 * i]) <= kOffGridBeamBound && std::fabs(out[2 * i + 1]) <= kOffGridBeamBound;
+    if (!near) out[2 * i] = out[2 * i + 1] = kOffGridBeam;
   }
 }
 
@@ -646,6 +704,7 @@ struct ndt2d_matcher
   // skips the upload.  The matcher must be the only writer of its context's beams.
   bool beams_on_device = false;
   std::vector<double> scratch_beams, cos_th, sin_th;
+  std::vector<float> scratch_ranges;   // ranges with their kept infinities made finite (off_grid_ranges)
   // The mapper calls scoreScan(scan) and then matchScan(scan, ...) (reference
   // src/ndt_mapper.cpp:514-515, 552-553).  Once that pair has been seen, scoreScan queues the
   // scan's search behind its own kernel before it waits for the score (`ahead`): the search
@@ -2060,6 +2119,7 @@ int ndt2d_matcher_match_laser_scan(ndt2d_matcher * m, const double * scan_pose_x
   }
   discard_ahead(m);
   size_t n_points = 0, use = 0;
+  ranges = off_grid_ranges(m->scratch_ranges, ranges, n_ranges, scan->range_max);
   int rc = ndt2d_set_beams_from_ranges(m->dev, ranges, n_ranges, scan, m->laser_max_beams,
                                        &n_points, &use);
   if (rc != NDT2D_OK) return dev_fail(m, rc, "ndt2d_set_beams_from_ranges");

@@ -346,20 +346,23 @@ void orc_ndt_destroy(orc_ndt * ndt)
   free(ndt);
 }
 
-/* NDT::getIndex, src/ndt_model.cpp:203-218.  `unsigned int g = (double)`
- * truncates toward zero (x86-64: cvttsd2si to 64 bit, low 32 bits kept). */
+/* NDT::getIndex, src/ndt_model.cpp:203-218.  `unsigned int g = (double)` truncates toward
+ * zero.  The four comparisons are made on the double quotients, before any integer cast:
+ * for a finite point less than 2^32 cells from the origin this is the reference's index
+ * exactly (for f >= 0, trunc(f) < size <=> f < size); a NaN or infinite coordinate, or one
+ * 2^32 cells or more away, is outside the grid.  The reference's double -> unsigned int
+ * conversion is undefined there (include/ndt2d_hip.h, "Points off the grid"). */
 int orc_ndt_get_index(const orc_ndt * ndt, double x, double y)
 {
-  if (x < ndt->origin_x || y < ndt->origin_y)
+  const double fx = (x - ndt->origin_x) / ndt->cell_size;
+  const double fy = (y - ndt->origin_y) / ndt->cell_size;
+  if (!(x >= ndt->origin_x) || !(y >= ndt->origin_y) || !(fx < (double)ndt->size_x) ||
+      !(fy < (double)ndt->size_y))
   {
     return -1;
   }
-  unsigned int grid_x = (unsigned int)(long long)((x - ndt->origin_x) / ndt->cell_size);
-  unsigned int grid_y = (unsigned int)(long long)((y - ndt->origin_y) / ndt->cell_size);
-  if (grid_x >= ndt->size_x || grid_y >= ndt->size_y)
-  {
-    return -1;
-  }
+  unsigned int grid_x = (unsigned int)fx;
+  unsigned int grid_y = (unsigned int)fy;
   return (int)((grid_y * ndt->size_x) + grid_x);
 }
 

@@ -81,11 +81,15 @@ def test_edge_cases_follow_the_reference():
     edge = np.array([[-5.0, -5.0], [np.nextafter(-5.0, -10.0), 0.0], [5.0, 5.0], [5.25, 0.0], [0.0, 5.2499]])
     ident = (0.0, 0.0, 0.0)
     assert gpu.scorePoints(edge, ident) == ref.scorePoints(edge, ident)
-    # NaN beam: propagates as in the reference
-    nan_pts = pts.copy()
-    nan_pts[3, 0] = np.nan
-    a, b = gpu.scorePoints(nan_pts, ident), ref.scorePoints(nan_pts, ident)
-    assert (np.isnan(a) and np.isnan(b)) or a == b
+    # NaN beam: off the grid (include/ndt2d_hip.h), the oracle's finite score for the finite
+    # off-grid point (1e6, 1e6) in its place, bit for bit
+    for k in (0, 3):
+        nan_pts = pts.copy()
+        nan_pts[k, 0] = np.nan
+        far_pts = pts.copy()
+        far_pts[k] = (1e6, 1e6)
+        a, b = gpu.scorePoints(nan_pts, ident), ref.scorePoints(nan_pts, ident)
+        assert not np.isnan(b) and a == b == ref.scorePoints(far_pts, ident)
     # no NDT: 0.0
     empty = ScanMatcherNDT(0)
     empty.initialize("e", **synth.matcher_params(1, laser_max_beams=100))

@@ -133,6 +133,27 @@ def _random_scans(rng, n_scans, n_beams, spread, reach):
     return scans
 
 
+def _with_off_grid(scans, rng=None):
+    """(scans, substitute): off-grid points (tests/offgrid_cases.py) put first, last, about every
+    quarter boundary and in the n % 4 tail of every scan -- or, given rng, of a random half of the
+    scans at random ones of those places; in the substitute the finite (1e6, 1e6) in their place."""
+    import offgrid_cases as G
+    offg = [(x, y) for x, y, wrap in G.off_grid_points(0.25, 3.0) if wrap is None]
+    out, subs = [], []
+    for s, (pose, pts) in enumerate(scans):
+        pts = np.array(pts, dtype=np.float64, copy=True).reshape(-1, 2)
+        sub = pts.copy()
+        sl = G.slots(len(pts)) if len(pts) >= 16 else [0, len(pts) - 1][:len(pts) // 2]
+        if rng is not None:
+            sl = [k for k in sl if rng.random() < 0.5] if rng.random() < 0.5 else []
+        for i, k in enumerate(sl):
+            pts[k] = offg[(s + i) % len(offg)]
+            sub[k] = G.SUBSTITUTE
+        out.append((pose, pts))
+        subs.append((pose, sub))
+    return out, subs
+
+
 @pytest.mark.parametrize("cfg", [1, 3])
 def test_quarters_side_by_side_give_the_sequential_bits(cfg):
     """HostNdt::add_scan (csrc/ndt2d_host.cpp): four chains of Cell::addPoint in flight, the points
@@ -149,7 +170,9 @@ def test_quarters_side_by_side_give_the_sequential_bits(cfg):
 def test_quarters_that_share_cells_keep_the_order(seed):
     """Adversarial scans: ranges shorter than a cell (EVERY quarter lands in the robot's own cell
     and its neighbours), beams beyond the grid, beam counts that are no multiple of four, a
-    non-power-of-two cell size (true divide in getIndex), scans too short to be cut."""
+    non-power-of-two cell size (true divide in getIndex), scans too short to be cut -- and points off
+    the grid (NaN, +-inf, 1e300, DBL_MAX) first, last, about every quarter boundary and in the tail,
+    which must change what the finite off-grid point (1e6, 1e6) changes: nothing."""
     from ndt_2d_amd.scan_matcher import BUILD_SEQUENTIAL
     rng = np.random.default_rng(600 + seed)
     n_beams = [720, 719, 37, 33, 31, 1001, 64, 5, 360, 722, 90, 128][seed]
@@ -158,6 +181,7 @@ def test_quarters_that_share_cells_keep_the_order(seed):
     scans = _random_scans(rng, 7, n_beams, 0.6, reach)
     if seed == 9:
         scans[3] = (scans[3][0], scans[3][1][:0])           # an empty scan among the others
+    scans, subs = _with_off_grid(scans)
     a = host_build_grid(res, 3.0, scans)
     b = host_build_grid(res, 3.0, scans, BUILD_SEQUENTIAL)
     assert a[1:] == b[1:] and np.array_equal(a[0], b[0])
@@ -167,6 +191,9 @@ def test_quarters_that_share_cells_keep_the_order(seed):
     m.initialize(ndt_resolution=res, range_max=3.0)
     m.addScans(scans)
     assert np.array_equal(a[0], m.ndt.cells6())
+    m.reset()
+    m.addScans(subs)
+    assert np.array_equal(a[0].view(np.uint64), np.ascontiguousarray(m.ndt.cells6()).view(np.uint64))
 
 
 def test_builds_reuse_their_storage_across_geometries():
@@ -222,7 +249,8 @@ def test_a_lattice_that_would_not_end_is_an_error_code(size, res):
 
 def test_random_scan_sets_build_bit_for_bit_like_the_sequential_loop_and_the_oracle():
     """A slice of experiments/fuzz_host_build.py (142,850 cases without a difference in round 6): random
-    scan sets, ranges that make degenerate cells (NaN information) included -- compared as bits."""
+    scan sets, ranges that make degenerate cells (NaN information) included, off-grid points (NaN, +-inf,
+    1e300) in a random half of the scans -- compared as bits, and with the finite substitute's grid."""
     from ndt_2d_amd.scan_matcher import BUILD_SEQUENTIAL
     rng = np.random.default_rng(66)
     for _ in range(250):
@@ -240,6 +268,7 @@ def test_random_scan_sets_build_bit_for_bit_like_the_sequential_loop_and_the_ora
             r = [rng.uniform(0, reach, nb), np.full(nb, reach) * rng.uniform(0.99, 1.01, nb),
                  rng.choice([0.0, reach, reach * 0.5], nb)][int(rng.integers(0, 3))]
             scans.append((pose, np.stack([r * np.cos(ang), r * np.sin(ang)], axis=1)))
+        scans, subs = _with_off_grid(scans, rng)
         a = host_build_grid(res, rmax, scans)
         b = host_build_grid(res, rmax, scans, BUILD_SEQUENTIAL)
         m = O.ScanMatcherNDT()
@@ -249,3 +278,6 @@ def test_random_scan_sets_build_bit_for_bit_like_the_sequential_loop_and_the_ora
         assert a[1:] == b[1:]
         assert np.array_equal(a[0].view(np.uint64), b[0].view(np.uint64))
         assert np.array_equal(a[0].view(np.uint64), c.view(np.uint64))
+        m.reset()
+        m.addScans(subs)
+        assert np.array_equal(a[0].view(np.uint64), np.ascontiguousarray(m.ndt.cells6()).view(np.uint64))

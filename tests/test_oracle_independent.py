@@ -31,12 +31,12 @@ class NumpyNDT:
         self.info = np.zeros((n, 2, 2))
 
     def index(self, x, y):                                  # :203-218
-        if x < self.ox or y < self.oy:
+        # the off-grid rule (include/ndt2d_hip.h): compared as double quotients before the
+        # truncation, so NaN, +-inf and points 2^32 cells away are outside
+        fx, fy = (x - self.ox) / self.cell, (y - self.oy) / self.cell
+        if not (x >= self.ox and y >= self.oy and fx < self.sx and fy < self.sy):
             return -1
-        gx, gy = int((x - self.ox) / self.cell), int((y - self.oy) / self.cell)
-        if gx >= self.sx or gy >= self.sy:
-            return -1
-        return gy * self.sx + gx
+        return int(fy) * self.sx + int(fx)
 
     def add_scan(self, pose, pts):                          # :132-152
         c, s = math.cos(pose[2]), math.sin(pose[2])
@@ -71,11 +71,10 @@ class NumpyNDT:
 
     def likelihood(self, X, Y):
         """sum over the last axis of per-point likelihoods; X, Y: [..., n_points]"""
-        inside = (X >= self.ox) & (Y >= self.oy)
-        gx = ((X - self.ox) / self.cell).astype(np.int64)
-        gy = ((Y - self.oy) / self.cell).astype(np.int64)
-        inside &= (gx >= 0) & (gx < self.sx) & (gy >= 0) & (gy < self.sy)
-        idx = np.where(inside, gy * self.sx + gx, 0)
+        fx, fy = (X - self.ox) / self.cell, (Y - self.oy) / self.cell
+        inside = (X >= self.ox) & (Y >= self.oy) & (fx < self.sx) & (fy < self.sy)   # as index()
+        idx = np.where(inside, np.where(inside, fy, 0).astype(np.int64) * self.sx +
+                       np.where(inside, fx, 0).astype(np.int64), 0)
         ok = inside & (self.n[idx] >= 5)                    # :107 (n < 5 -> 0.0)
         q0 = X - self.mean[idx, 0]
         q1 = Y - self.mean[idx, 1]
