@@ -636,6 +636,12 @@ void subsample_into(std::vector<double> & out, const double * pts, size_t n_poin
   }
 }
 
+// Two scans' subsampled beams, bit for bit the same (and not none).
+bool same_beams(const std::vector<double> & a, const std::vector<double> & b)
+{
+  return !a.empty() && a.size() == b.size() && std::memcmp(a.data(), b.data(), a.size() * sizeof(double)) == 0;
+}
+
 // ROS angles::normalize_angle / shortest_angular_distance (unpinned dependency
 // of the reference, used by updateStatistics src/particle_filter.cpp:215).
 double normalize_angle(double a)
@@ -657,7 +663,7 @@ struct MatcherShard
   double * d_poses = nullptr;     // this device's particle range
   double * d_weights = nullptr;
   size_t poses_cap = 0;
-  uint64_t beams_epoch = ~0ull;   // ndt2d_matcher::beams_epoch of the beams ndt2d_set_beams put there
+  uint64_t beams_epoch = ~0ull;   // ndt2d_matcher::beams.epoch of the beams ndt2d_set_beams put there
 };
 
 struct ndt2d_matcher
@@ -677,7 +683,6 @@ struct ndt2d_matcher
   double multi_min_pose_units = 2.0e8;
   std::unique_ptr<ndt2d::DeviceWorkers> workers;   // one thread per device beyond the first
   std::vector<double> fanout_us;         // last dealt call: when each device's launch was queued
-  uint64_t beams_epoch = 0;              // counts the changes of `beams` (what the other devices hold: MatcherShard)
   double * pinned = nullptr;             // host block of the exchanges (layout: multi_pinned_*)
   std::string variant;                   // ndt2d_matcher_last_variant
   bool last_multi = false;
@@ -693,43 +698,64 @@ struct ndt2d_matcher
   bool have_ndt = false;          // `ndt_` is set (reference scan_matcher_ndt.hpp:102)
   int build_mode = 0;             // 0 auto, 1 host, 2 device
   int eigen_form = ndt2d::kEigenFormSchur;   // ndt2d_matcher_set_eigenvalue_form
-  // state of the last prepare_search (subsampled beams + visited offsets)
-  std::vector<double> beams, dth, dlin;
-  size_t n_use = 0;               // beams in use (the N of `best / N`, :148)
-  bool search_ready = false;
-  // `beams` is what the device context currently holds as its beams: a scoring call
-  // that arrives with the same points again (the unchanged ParticleFilter::measure
-  // calls scorePoints once per particle with one scan, src/particle_filter.cpp:81-87;
-  // the mapper calls scoreScan and matchScan on one scan, src/ndt_mapper.cpp:514-515)
-  // skips the upload.  The matcher must be the only writer of its context's beams.
-  bool beams_on_device = false;
-  std::vector<double> scratch_beams, cos_th, sin_th;
-  std::vector<float> scratch_ranges;   // ranges with their kept infinities made finite (off_grid_ranges)
+
+  // What the first device holds as its beams: a scoring call that arrives with the same points
+  // again (the unchanged ParticleFilter::measure calls scorePoints once per particle with one
+  // scan, src/particle_filter.cpp:81-87; the mapper calls scoreScan and matchScan on one scan,
+  // src/ndt_mapper.cpp:514-515) skips the upload.  The matcher must be the only writer of its
+  // context's beams.  Changed by adopt / sent / lost only.
+  struct DeviceBeams
+  {
+    std::vector<double> host;    // host copy of the subsampled beams (empty: a LaserScan the device converted)
+    std::vector<double> next;    // the subsampled beams of the call now arriving
+    bool on_device = false;      // the first device holds `host`
+    uint64_t epoch = 0;          // counts the changes of `host` (MatcherShard::beams_epoch is compared with it)
+    bool holds(const std::vector<double> & b) const { return on_device && same_beams(host, b); }
+    // b becomes the host copy, not yet on the device (b is left with the old one)
+    void adopt(std::vector<double> & b) { host.swap(b); ++epoch; on_device = false; }
+    void sent() { on_device = true; }    // the device received `host` (an upload, or a launch that carried it)
+    void lost() { on_device = false; }   // a call that may have replaced it failed
+  } beams;
+
+  // The prepared search: the visited offsets (set by initialize()), the per-theta cos/sin and
+  // the beams of the last prepare_search / match_laser_scan / search launched ahead.
+  struct PreparedSearch
+  {
+    std::vector<double> dth, dlin, cos_th, sin_th;
+    size_t n_use = 0;     // beams in use (the N of `best / N`, :148)
+    bool ready = false;   // the first device holds the tables (and the beams) of it
+  } search;
+
   // The mapper calls scoreScan(scan) and then matchScan(scan, ...) (reference
   // src/ndt_mapper.cpp:514-515, 552-553).  Once that pair has been seen, scoreScan queues the
-  // scan's search behind its own kernel before it waits for the score (`ahead`): the search
-  // then starts when the scoring kernel ends, not a host round trip later, and the matchScan
-  // that follows only collects it.  A call that is not that matchScan waits the search out,
-  // discards it, and scoreScan stops doing it until the pair is seen again.
-  bool pair_seen = false;         // the last matchScan was of the scan and pose of the scoreScan before it
-  bool score_scan_last = false;   // the previous device call was a scoreScan ...
-  double score_scan_pose[3] = {0.0, 0.0, 0.0};   // ... from this pose (its beams are `beams`)
-  bool ahead = false;             // a search launched by scoreScan has not been collected
-  double ahead_pose[3] = {0.0, 0.0, 0.0};
-  size_t ahead_n_th = 0;
-  uint64_t ahead_launch_id = 0, ahead_fetch_id = 0;   // ndt2d_match_status right after that launch
-  // One pose at a time (scorePoints, scoreScan): scored on the host from the host NDT when the
-  // scan is short (ndt2d_matcher_set_single_pose_path).  `scored` = the subsampled beams of the
-  // last scoreScan (the pair detection above compares the next matchScan's scan with it).
+  // scan's search behind its own kernel before it waits for the score: the search then starts
+  // when the scoring kernel ends, not a host round trip later, and the matchScan that follows
+  // only collects it.  A call that is not that matchScan waits the search out, discards it, and
+  // scoreScan stops doing it until the pair is seen again.  Changed by the *_ahead and
+  // note_*_scan functions only (and the switch).
+  struct SearchAhead
+  {
+    bool enabled = true;          // ndt2d_matcher_set_search_ahead
+    bool pair_seen = false;       // the last matchScan was of the scan and pose of the scoreScan before it
+    bool after_score_scan = false;   // the previous device call was a scoreScan ...
+    double score_scan_pose[3] = {0.0, 0.0, 0.0};   // ... from this pose ...
+    std::vector<double> scored;   // ... of these subsampled beams
+    bool pending = false;         // a search launched by scoreScan has not been collected
+    double pose[3] = {0.0, 0.0, 0.0};
+    size_t n_th = 0;
+    uint64_t launch_id = 0, fetch_id = 0;   // ndt2d_match_status right after that launch
+    uint64_t launched = 0, collected = 0;   // ndt2d_matcher_search_ahead_stats
+  } ahead;
+
+  std::vector<float> scratch_ranges;   // ranges with their kept infinities made finite (off_grid_ranges)
   // near-tie adjudication (ndt2d_matcher_set_adjudication)
   bool adjudicate = true;
   uint64_t adj_marked = 0, adj_changed = 0, adj_truncated = 0;
+  // One pose at a time (scorePoints, scoreScan): scored on the host from the host NDT when the
+  // scan is short (ndt2d_matcher_set_single_pose_path).
   bool single_pose_host = true;
   size_t single_pose_max_beams = 256;
   std::unique_ptr<HostNdt> fetched;  // host copy of a grid that was built on the device
-  std::vector<double> scored;
-  int ahead_enabled = 1;          // ndt2d_matcher_set_search_ahead
-  uint64_t ahead_launched = 0, ahead_collected = 0;
 };
 
 namespace
@@ -760,6 +786,15 @@ int dev_fail(ndt2d_matcher * m, int code, const char * what)
   return mfail(m, code, std::string(what) + ": " + ndt2d_last_error(m->dev));
 }
 
+// A search's result as the record {best_score, best_index or -1, k00,k01,k02,k11,k12,k22, u0,u1,u2, s};
+// a winner with another candidate within the near-tie tolerance is marked: index + 0.5.
+void record_from(const ndt2d_match_result & res, double * rec)
+{
+  rec[0] = res.best_score;
+  rec[1] = res.best_index == NDT2D_NO_INDEX ? -1.0 : static_cast<double>(res.best_index) + (res.near_tie ? 0.5 : 0.0);
+  for (int i = 0; i < 10; ++i) rec[2 + i] = res.acc[i];
+}
+
 // The visited offsets of the search and the per-theta cos/sin (reference
 // src/scan_matcher_ndt.cpp:103-107,117,119).  host_beams != nullptr: they are uploaded
 // together with the beams in one copy; nullptr: the beams are on the device already
@@ -769,88 +804,172 @@ int prepare_tables(ndt2d_matcher * m, const double * scan_pose_xyt, size_t use,
                    size_t * n_lin_out)
 {
   // (the visited offsets depend on the parameters only: computed by initialize())
-  const size_t n_th = m->dth.size(), n_lin = m->dlin.size();
+  const size_t n_th = m->search.dth.size(), n_lin = m->search.dlin.size();
   if (n_th_out != nullptr) *n_th_out = n_th;
   if (n_lin_out != nullptr) *n_lin_out = n_lin;
-  m->search_ready = false;
+  m->search.ready = false;
   if (use == 0 || n_th == 0 || n_lin == 0 || !m->have_ndt) return NDT2D_OK;  // nothing to upload
 
-  m->cos_th.resize(n_th);
-  m->sin_th.resize(n_th);
+  m->search.cos_th.resize(n_th);
+  m->search.sin_th.resize(n_th);
   for (size_t i = 0; i < n_th; ++i)
   {
     // reference src/scan_matcher_ndt.cpp:106-107
-    ndt2d_cos_sin(scan_pose_xyt[2] + m->dth[i], &m->cos_th[i], &m->sin_th[i]);
+    ndt2d_cos_sin(scan_pose_xyt[2] + m->search.dth[i], &m->search.cos_th[i], &m->search.sin_th[i]);
   }
   int rc;
   if (host_beams != nullptr || beams_cached)
   {
     rc = ndt2d_set_search_beams(m->dev, host_beams, use, scan_pose_xyt[0], scan_pose_xyt[1],
-                                m->dth.data(), m->cos_th.data(), m->sin_th.data(), n_th,
-                                m->dlin.data(), n_lin);
+                                m->search.dth.data(), m->search.cos_th.data(), m->search.sin_th.data(), n_th,
+                                m->search.dlin.data(), n_lin);
     if (rc != NDT2D_OK) return dev_fail(m, rc, "ndt2d_set_search_beams");
-    m->beams_on_device = true;
+    m->beams.sent();
   }
   else
   {
-    rc = ndt2d_set_search(m->dev, scan_pose_xyt[0], scan_pose_xyt[1], m->dth.data(),
-                          m->cos_th.data(), m->sin_th.data(), n_th, m->dlin.data(), n_lin);
+    rc = ndt2d_set_search(m->dev, scan_pose_xyt[0], scan_pose_xyt[1], m->search.dth.data(),
+                          m->search.cos_th.data(), m->search.sin_th.data(), n_th, m->search.dlin.data(), n_lin);
     if (rc != NDT2D_OK) return dev_fail(m, rc, "ndt2d_set_search");
   }
-  m->search_ready = true;
+  m->search.ready = true;
+  return NDT2D_OK;
+}
+
+// The host copy of the beams to the first device.
+int upload_beams(ndt2d_matcher * m)
+{
+  const int rc = ndt2d_set_beams(m->dev, m->beams.host.data(), m->beams.host.size() / 2);
+  if (rc != NDT2D_OK) return dev_fail(m, rc, "ndt2d_set_beams");
+  m->beams.sent();
   return NDT2D_OK;
 }
 
 // Subsample `points` (src/scan_matcher_ndt.cpp:165-166,171) and make them the device
 // context's beams -- unless they are exactly what it holds already.  *use_out = beams.
-// defer_upload: a changed scan is only noted (*pending_out = true; m->beams holds it):
-// the caller hands it to ndt2d_score_poses_beams, which uploads it or passes it along as
+// pending_out != nullptr: a changed scan is only adopted (*pending_out = true): the caller
+// hands m->beams.host to ndt2d_score_poses_beams, which uploads it or passes it along as
 // kernel arguments.
 int stage_beams(ndt2d_matcher * m, const double * points_xy, size_t n_points, size_t * use_out,
                 bool * pending_out = nullptr)
 {
   if (pending_out != nullptr) *pending_out = false;
-  subsample_into(m->scratch_beams, points_xy, n_points, m->laser_max_beams);
-  const size_t use = m->scratch_beams.size() / 2;
+  subsample_into(m->beams.next, points_xy, n_points, m->laser_max_beams);
+  const size_t use = m->beams.next.size() / 2;
   *use_out = use;
-  if (use == 0) return NDT2D_OK;
-  if (m->beams_on_device && m->beams.size() == m->scratch_beams.size() &&
-      std::memcmp(m->beams.data(), m->scratch_beams.data(), m->beams.size() * sizeof(double)) == 0)
-  {
-    return NDT2D_OK;   // same scan as the last call: the beams are there
-  }
-  m->search_ready = false;  // the device beams are replaced: a prepared search is void
-  m->beams_on_device = false;
-  if (pending_out != nullptr)
-  {
-    m->beams.swap(m->scratch_beams);
-    ++m->beams_epoch;
-    *pending_out = true;
-    return NDT2D_OK;
-  }
-  int rc = ndt2d_set_beams(m->dev, m->scratch_beams.data(), use);
-  if (rc != NDT2D_OK) return dev_fail(m, rc, "ndt2d_set_beams");
-  m->beams.swap(m->scratch_beams);
-  ++m->beams_epoch;
-  m->beams_on_device = true;
+  if (use == 0 || m->beams.holds(m->beams.next)) return NDT2D_OK;   // (same scan as the last call: the beams are there)
+  m->search.ready = false;  // the device beams are replaced: a prepared search is void
+  m->beams.adopt(m->beams.next);
+  if (pending_out == nullptr) return upload_beams(m);
+  *pending_out = true;
   return NDT2D_OK;
+}
+
+// Is the search launched ahead still the one pending on the context?  (A caller may have launched
+// or fetched on ndt2d_matcher_device(m) itself in between: then the record is not ours.)
+bool ahead_on_context(ndt2d_matcher * m)
+{
+  uint64_t launched = 0, fetched = 0;
+  return ndt2d_match_status(m->dev, &launched, &fetched) == NDT2D_OK && launched == m->ahead.launch_id &&
+         fetched == m->ahead.fetch_id;
 }
 
 // A search launched ahead that the call now arriving cannot use: wait it out (its record is
 // dropped), and do not launch ahead again until the scoreScan / matchScan pair reappears.
 void discard_ahead(ndt2d_matcher * m)
 {
-  m->score_scan_last = false;
-  if (!m->ahead) return;
-  uint64_t launched = 0, fetched = 0;
-  if (ndt2d_match_status(m->dev, &launched, &fetched) == NDT2D_OK && launched == m->ahead_launch_id &&
-      fetched == m->ahead_fetch_id)
+  m->ahead.after_score_scan = false;
+  if (!m->ahead.pending) return;
+  if (ahead_on_context(m))
   {
     ndt2d_match_result res;
     (void)ndt2d_match_fetch(m->dev, &res);
   }
-  m->ahead = false;
-  m->pair_seen = false;
+  m->ahead.pending = false;
+  m->ahead.pair_seen = false;
+}
+
+// ... and forget the pair even when nothing was pending (the lattice or the switch changed).
+void forget_ahead(ndt2d_matcher * m)
+{
+  discard_ahead(m);
+  m->ahead.pair_seen = false;
+}
+
+// scoreScan: the prepared search of its scan launched now, for the matchScan that follows to
+// collect.  (A search that cannot be launched is not scoreScan's failure: matchScan will say.)
+void launch_ahead(ndt2d_matcher * m, const double * scan_pose_xyt, size_t n_th, size_t use)
+{
+  if (!m->search.ready || ndt2d_match_launch(m->dev, 0, n_th, nullptr, nullptr) != NDT2D_OK) return;
+  ndt2d_matcher::SearchAhead & a = m->ahead;
+  a.pending = true;
+  (void)ndt2d_match_status(m->dev, &a.launch_id, &a.fetch_id);
+  ++a.launched;
+  std::memcpy(a.pose, scan_pose_xyt, sizeof(a.pose));
+  a.n_th = n_th;
+  m->search.n_use = use;
+}
+
+// matchScan: the search launched ahead, if it is this call's -- no per-candidate scores wanted,
+// the pose bitwise the same, the same subsampled beams, still the search pending on the context --
+// fetched into `record` (marked: record_from), *n_th_out = its theta steps.  Any other search
+// launched ahead is discarded (*n_th_out = 0).
+int collect_ahead(ndt2d_matcher * m, const double * scan_pose_xyt, const double * points_xy, size_t n_points,
+                  bool want_scores, double * record, size_t * n_th_out)
+{
+  ndt2d_matcher::SearchAhead & a = m->ahead;
+  *n_th_out = 0;
+  if (!a.pending) return NDT2D_OK;
+  bool hit = !want_scores && (n_points == 0 || points_xy != nullptr) &&
+             std::memcmp(a.pose, scan_pose_xyt, sizeof(a.pose)) == 0;
+  if (hit)
+  {
+    subsample_into(m->beams.next, points_xy, n_points, m->laser_max_beams);
+    hit = m->beams.holds(m->beams.next) && ahead_on_context(m);
+  }
+  if (!hit)
+  {
+    discard_ahead(m);
+    return NDT2D_OK;
+  }
+  a.pending = false;
+  a.after_score_scan = false;
+  ++a.collected;
+  *n_th_out = a.n_th;
+  ndt2d_match_result res;
+  const int rc = ndt2d_match_fetch(m->dev, &res);
+  if (rc != NDT2D_OK) return dev_fail(m, rc, "ndt2d_match_fetch");
+  record_from(res, record);
+  return NDT2D_OK;
+}
+
+// scoreScan of this pose and scan answered: the matchScan after it may be of the same.
+void note_score_scan(ndt2d_matcher * m, const double * scan_pose_xyt, const double * points_xy, size_t n_points)
+{
+  ndt2d_matcher::SearchAhead & a = m->ahead;
+  a.after_score_scan = true;
+  std::memcpy(a.score_scan_pose, scan_pose_xyt, sizeof(a.score_scan_pose));
+  subsample_into(a.scored, points_xy, n_points, m->laser_max_beams);
+}
+
+// matchScan (prepared: its search was prepared, m->beams.host holds its subsampled beams): the
+// pair is seen when it is of the scan and pose the scoreScan just before it scored.
+void note_match_scan(ndt2d_matcher * m, const double * scan_pose_xyt, bool prepared)
+{
+  ndt2d_matcher::SearchAhead & a = m->ahead;
+  if (prepared && a.after_score_scan && std::memcmp(a.score_scan_pose, scan_pose_xyt, sizeof(a.score_scan_pose)) == 0 &&
+      same_beams(m->beams.host, a.scored))
+  {
+    a.pair_seen = true;
+  }
+  a.after_score_scan = false;
+}
+
+// scorePoints / scoreScan: one pose of a short scan, scored on the host (ndt2d_matcher_set_single_pose_path)?
+bool single_pose_on_host(const ndt2d_matcher * m, const double * points_xy, size_t n_points)
+{
+  return m->single_pose_host && m->have_ndt && n_points > 0 && points_xy != nullptr && m->laser_max_beams > 0 &&
+         std::min(m->laser_max_beams, n_points) <= m->single_pose_max_beams;
 }
 
 // The host NDT the single-pose path and the near-tie adjudication score against: the one
@@ -916,7 +1035,7 @@ double host_score_points(const HostNdt & ndt, const double * points_xy, size_t n
 }
 
 // One candidate of matchScan's lattice as the reference scores it (src/scan_matcher_ndt.cpp:
-// 106-127): points_outer from the subsampled beams `beams` (m->beams) and cos/sin of
+// 106-127): points_outer from the subsampled beams (m->beams.host) and cos/sin of
 // scan_pose.theta + dth, points_inner = outer + (dx, dy), score = -(likelihoods summed in order).
 double host_score_candidate(const HostNdt & ndt, const double * beams_xy, size_t use, const double * scan_pose_xyt,
                             double costh, double sinth, double dx, double dy)
@@ -942,7 +1061,7 @@ int settle_near_tie(ndt2d_matcher * m, const double * scan_pose_xyt, size_t n_th
   if (!(record[1] >= 0.0) || record[1] == std::floor(record[1])) return NDT2D_OK;   // not marked
   record[1] = std::floor(record[1]);
   ++m->adj_marked;
-  if (!m->adjudicate || m->beams.size() != 2 * use || m->cos_th.size() != n_th) return NDT2D_OK;
+  if (!m->adjudicate || m->beams.host.size() != 2 * use || m->search.cos_th.size() != n_th) return NDT2D_OK;
   const HostNdt * ndt = host_ndt(m, false);
   if (ndt == nullptr) return NDT2D_OK;
   constexpr size_t kCap = 256;
@@ -975,8 +1094,8 @@ int settle_near_tie(ndt2d_matcher * m, const double * scan_pose_xyt, size_t n_th
   {
     const uint64_t ith = idx[k] / per_th, rem = idx[k] % per_th;
     if (ith >= n_th) continue;
-    const double score = host_score_candidate(*ndt, m->beams.data(), use, scan_pose_xyt, m->cos_th[ith], m->sin_th[ith],
-                                              m->dlin[rem / n_lin], m->dlin[rem % n_lin]);
+    const double score = host_score_candidate(*ndt, m->beams.host.data(), use, scan_pose_xyt, m->search.cos_th[ith],
+                                              m->search.sin_th[ith], m->search.dlin[rem / n_lin], m->search.dlin[rem % n_lin]);
     if (score < best_s)
     {
       best_s = score;
@@ -1010,10 +1129,15 @@ size_t pinned_rows_off(size_t n) { return n * n * kRec + n * kRec; }
 size_t pinned_sum_off(size_t n) { return n * n * kRec + 2 * n * kRec; }
 size_t pinned_doubles(size_t n) { return pinned_sum_off(n) + kStats; }
 
+std::string dev_msg_at(ndt2d_matcher * m, size_t r, const char * what)
+{
+  return std::string(what) + " (device " + std::to_string(m->device_ids[r]) + ", rank " + std::to_string(r) +
+         "): " + ndt2d_last_error(m->devs[r]);
+}
+
 int dev_fail_at(ndt2d_matcher * m, size_t r, int code, const char * what)
 {
-  return mfail(m, code, std::string(what) + " (device " + std::to_string(m->device_ids[r]) + ", rank " +
-                          std::to_string(r) + "): " + ndt2d_last_error(m->devs[r]));
+  return mfail(m, code, dev_msg_at(m, r, what));
 }
 
 // The exchange buffers every sharded call needs: made on the first one.
@@ -1159,16 +1283,19 @@ void drain_devices(ndt2d_matcher * m)
   }
 }
 
+// msg is made by the caller, before the devices are touched again.
+int give_up_dealt(ndt2d_matcher * m, int code, const std::string & msg)
+{
+  mfail(m, code, msg);
+  drain_devices(m);
+  return code;
+}
+
 int first_failure(ndt2d_matcher * m, const std::vector<RankStatus> & st)
 {
   for (size_t r = 0; r < st.size(); ++r)
   {
-    if (st[r].rc != NDT2D_OK)
-    {
-      const int rc = dev_fail_at(m, r, st[r].rc, st[r].what);   // (the message, before the devices are touched again)
-      drain_devices(m);
-      return rc;
-    }
+    if (st[r].rc != NDT2D_OK) return give_up_dealt(m, st[r].rc, dev_msg_at(m, r, st[r].what));
   }
   return NDT2D_OK;
 }
@@ -1219,13 +1346,14 @@ int multi_match(ndt2d_matcher * m, const double * scan_pose_xyt, size_t n_th, si
       s.what = "ndt2d_set_search_beams";
       if (beams_everywhere)
       {
-        s.rc = ndt2d_set_search(m->devs[r], scan_pose_xyt[0], scan_pose_xyt[1], m->dth.data(), m->cos_th.data(),
-                                m->sin_th.data(), n_th, m->dlin.data(), n_lin);
+        s.rc = ndt2d_set_search(m->devs[r], scan_pose_xyt[0], scan_pose_xyt[1], m->search.dth.data(),
+                                m->search.cos_th.data(), m->search.sin_th.data(), n_th, m->search.dlin.data(), n_lin);
       }
       else
       {
-        s.rc = ndt2d_set_search_beams(m->devs[r], m->beams.data(), use, scan_pose_xyt[0], scan_pose_xyt[1], m->dth.data(),
-                                      m->cos_th.data(), m->sin_th.data(), n_th, m->dlin.data(), n_lin);
+        s.rc = ndt2d_set_search_beams(m->devs[r], m->beams.host.data(), use, scan_pose_xyt[0], scan_pose_xyt[1],
+                                      m->search.dth.data(), m->search.cos_th.data(), m->search.sin_th.data(), n_th,
+                                      m->search.dlin.data(), n_lin);
       }
       sh.beams_epoch = ~0ull;   // (the device's beams now live in the search's upload)
       if (s.rc != NDT2D_OK) return;
@@ -1259,19 +1387,10 @@ int multi_match(ndt2d_matcher * m, const double * scan_pose_xyt, size_t n_th, si
     }
     std::string why;
     rc = ndt2d::exchange_all_reduce(m->exchange, tables.data(), n * kRec, streams.data(), &why);
-    if (rc != NDT2D_OK)
-    {
-      drain_devices(m);
-      return mfail(m, rc, why);
-    }
+    if (rc != NDT2D_OK) return give_up_dealt(m, rc, why);
     rc = ndt2d_copy_to_host_async(m->dev, rows, m->shards[0].d_table, n * kRec * sizeof(double));
     if (rc == NDT2D_OK) rc = ndt2d_synchronize(m->dev);
-    if (rc != NDT2D_OK)
-    {
-      const int frc = dev_fail_at(m, 0, rc, "ndt2d_copy_to_host_async");
-      drain_devices(m);
-      return frc;
-    }
+    if (rc != NDT2D_OK) return give_up_dealt(m, rc, dev_msg_at(m, 0, "ndt2d_copy_to_host_async"));
   }
   for (size_t r = 0; r < n; ++r)
   {
@@ -1281,19 +1400,8 @@ int multi_match(ndt2d_matcher * m, const double * scan_pose_xyt, size_t n_th, si
     // and the fetch only settles the context's state.)
     ndt2d_match_result res;
     rc = ndt2d_match_fetch(m->devs[r], &res);
-    if (rc != NDT2D_OK)
-    {
-      const int frc = dev_fail_at(m, r, rc, "ndt2d_match_fetch");
-      drain_devices(m);
-      return frc;
-    }
-    if (!rccl)
-    {
-      double * rec = rows + r * kRec;
-      rec[0] = res.best_score;
-      rec[1] = res.best_index == NDT2D_NO_INDEX ? -1.0 : static_cast<double>(res.best_index) + (res.near_tie ? 0.5 : 0.0);
-      for (int i = 0; i < 10; ++i) rec[2 + i] = res.acc[i];
-    }
+    if (rc != NDT2D_OK) return give_up_dealt(m, rc, dev_msg_at(m, r, "ndt2d_match_fetch"));
+    if (!rccl) record_from(res, rows + r * kRec);
   }
   if (all_scores != nullptr)
   {
@@ -1304,12 +1412,7 @@ int multi_match(ndt2d_matcher * m, const double * scan_pose_xyt, size_t n_th, si
       if (count[r] == 0) continue;
       tmp.resize(count[r] * per_th);
       rc = ndt2d_copy_to_host(m->devs[r], tmp.data(), m->shards[r].d_scores, tmp.size() * sizeof(double));
-      if (rc != NDT2D_OK)
-      {
-        const int frc = dev_fail_at(m, r, rc, "ndt2d_copy_to_host");
-        drain_devices(m);
-        return frc;
-      }
+      if (rc != NDT2D_OK) return give_up_dealt(m, rc, dev_msg_at(m, r, "ndt2d_copy_to_host"));
       for (size_t k = 0; k < count[r]; ++k)
       {
         std::memcpy(all_scores + (r + k * n) * per_th, tmp.data() + k * per_th, per_th * sizeof(double));
@@ -1318,6 +1421,22 @@ int multi_match(ndt2d_matcher * m, const double * scan_pose_xyt, size_t n_th, si
   }
   combine_records(rows, count, record_out);
   note_variant(m, true, rccl);
+  return NDT2D_OK;
+}
+
+// The prepared search run: dealt to all devices when it is large enough (multi_match, which
+// takes beams_everywhere and scores as it does), else on the first.  record: marked, record_from.
+int run_search(ndt2d_matcher * m, const double * scan_pose_xyt, size_t n_th, size_t n_lin, size_t use,
+               bool beams_everywhere, double * scores, double * record)
+{
+  if (multi_search_wanted(m, n_th, n_lin, use))
+  {
+    return multi_match(m, scan_pose_xyt, n_th, n_lin, use, beams_everywhere, scores, record);
+  }
+  ndt2d_match_result res;
+  const int rc = ndt2d_match(m->dev, 0, n_th, scores, &res);
+  if (rc != NDT2D_OK) return dev_fail(m, rc, "ndt2d_match");
+  record_from(res, record);
   return NDT2D_OK;
 }
 
@@ -1396,10 +1515,10 @@ int multi_score_poses(ndt2d_matcher * m, const double * poses_xyt, size_t n_pose
       give_up.store(true, std::memory_order_release);
       if (sync) (void)ndt2d_synchronize(m->devs[r]);   // nothing of this share stays in flight
     };
-    if (r > 0 && sh.beams_epoch != m->beams_epoch)
+    if (r > 0 && sh.beams_epoch != m->beams.epoch)
     {
-      if ((s.rc = ndt2d_set_beams(m->devs[r], m->beams.data(), use)) != NDT2D_OK) return fail("ndt2d_set_beams", true);
-      sh.beams_epoch = m->beams_epoch;
+      if ((s.rc = ndt2d_set_beams(m->devs[r], m->beams.host.data(), use)) != NDT2D_OK) return fail("ndt2d_set_beams", true);
+      sh.beams_epoch = m->beams.epoch;
     }
     s.rc = ndt2d_copy_to_device_async(m->devs[r], sh.d_poses, poses_xyt + 3 * begin[r], 3 * nr * sizeof(double));
     if (s.rc == NDT2D_OK && rccl)
@@ -1466,11 +1585,6 @@ int multi_score_poses(ndt2d_matcher * m, const double * poses_xyt, size_t n_pose
   }
 
   // RCCL exchange.  On any failure from here on every device is waited out before the error returns.
-  auto give_in = [&](int code, const std::string & msg) {
-    const int frc = mfail(m, code, msg);
-    drain_devices(m);
-    return frc;
-  };
   std::vector<double *> tables(n);
   std::vector<void *> streams(n);
   for (size_t r = 0; r < n; ++r)
@@ -1483,7 +1597,7 @@ int multi_score_poses(ndt2d_matcher * m, const double * poses_xyt, size_t n_pose
   // seven moment sums: [n, 8], every device its own row -- the ONE collective of the call
   // (until round 6 the devices' theta-variance parts went through a second one)
   rc = ndt2d::exchange_all_reduce(m->exchange, tables.data(), n * kStats, streams.data(), &why);
-  if (rc != NDT2D_OK) return give_in(rc, why);
+  if (rc != NDT2D_OK) return give_up_dealt(m, rc, why);
   // Behind it every device goes on by itself, on its own thread: the rows summed in device order
   // (the same bits everywhere), updateStatistics with them -- normalised weights, mean and
   // covariance, and the device's OWN part of the theta variance (:213-217) -- then the weights and
@@ -1572,8 +1686,8 @@ int ndt2d_matcher_create_multi(ndt2d_matcher ** out, const int * device_ids, int
     m->shards.resize(m->devs.size());
     m->dev = m->devs[0];
     m->workers.reset(new ndt2d::DeviceWorkers(m->devs.size()));
-    m->dth = search_offsets(m->angular_size, m->angular_res);
-    m->dlin = search_offsets(m->linear_size, m->linear_res);
+    m->search.dth = search_offsets(m->angular_size, m->angular_res);
+    m->search.dlin = search_offsets(m->linear_size, m->linear_res);
   }
   catch (const std::bad_alloc &)
   {
@@ -1718,8 +1832,7 @@ int ndt2d_matcher_initialize(ndt2d_matcher * m, double ndt_resolution,
     return mfail(m, NDT2D_ERR_INVALID, "search lattice: size / resolution must be finite, the resolution > 0, at most "
                                        "2^24 angular and 46,340 linear steps");
   }
-  discard_ahead(m);
-  m->pair_seen = false;
+  forget_ahead(m);
   m->resolution = ndt_resolution;
   m->angular_res = search_angular_resolution;
   m->angular_size = search_angular_size;
@@ -1727,9 +1840,9 @@ int ndt2d_matcher_initialize(ndt2d_matcher * m, double ndt_resolution,
   m->linear_size = search_linear_size;
   m->laser_max_beams = laser_max_beams;
   m->range_max = range_max;
-  m->dth = search_offsets(m->angular_size, m->angular_res);
-  m->dlin = search_offsets(m->linear_size, m->linear_res);
-  m->search_ready = false;
+  m->search.dth = search_offsets(m->angular_size, m->angular_res);
+  m->search.dlin = search_offsets(m->linear_size, m->linear_res);
+  m->search.ready = false;
   return NDT2D_OK;
   NDT2D_C_CATCH(m)
 }
@@ -1875,29 +1988,19 @@ int ndt2d_matcher_has_ndt(ndt2d_matcher * m) { return (m != nullptr && m->have_n
 
 static int prepare_search_impl(ndt2d_matcher * m, const double * scan_pose_xyt,
                                const double * points_xy, size_t n_points, size_t * n_th_out,
-                               size_t * n_lin_out, size_t * n_beams_out, bool * same_out)
+                               size_t * n_lin_out, size_t * n_beams_out)
 {
-  if (same_out != nullptr) *same_out = false;
   if (m == nullptr || scan_pose_xyt == nullptr) return NDT2D_ERR_INVALID;
   if (n_points > 0 && points_xy == nullptr) return mfail(m, NDT2D_ERR_INVALID, "null points");
-  subsample_into(m->scratch_beams, points_xy, n_points, m->laser_max_beams);
-  const size_t use = m->scratch_beams.size() / 2;
-  m->n_use = use;
+  subsample_into(m->beams.next, points_xy, n_points, m->laser_max_beams);
+  const size_t use = m->beams.next.size() / 2;
+  m->search.n_use = use;
   if (n_beams_out != nullptr) *n_beams_out = use;
-  m->search_ready = false;
   // the scan scoreScan was just called with (src/ndt_mapper.cpp:514-515)?  Then the
   // device holds these beams already and only the tables are new.
-  const bool same = m->beams_on_device && use > 0 && m->beams.size() == m->scratch_beams.size() &&
-                    std::memcmp(m->beams.data(), m->scratch_beams.data(),
-                                m->beams.size() * sizeof(double)) == 0;
-  if (same_out != nullptr) *same_out = same;
-  if (!same)
-  {
-    m->beams.swap(m->scratch_beams);
-    ++m->beams_epoch;
-    m->beams_on_device = false;
-  }
-  return prepare_tables(m, scan_pose_xyt, use, same ? nullptr : m->beams.data(), same, n_th_out,
+  const bool same = m->beams.holds(m->beams.next);
+  if (!same) m->beams.adopt(m->beams.next);
+  return prepare_tables(m, scan_pose_xyt, use, same ? nullptr : m->beams.host.data(), same, n_th_out,
                         n_lin_out);
 }
 
@@ -1907,8 +2010,7 @@ int ndt2d_matcher_prepare_search(ndt2d_matcher * m, const double * scan_pose_xyt
 {
   NDT2D_C_TRY
   if (m != nullptr) discard_ahead(m);
-  return prepare_search_impl(m, scan_pose_xyt, points_xy, n_points, n_th_out, n_lin_out, n_beams_out,
-                             nullptr);
+  return prepare_search_impl(m, scan_pose_xyt, points_xy, n_points, n_th_out, n_lin_out, n_beams_out);
   NDT2D_C_CATCH(m)
 }
 
@@ -1919,8 +2021,8 @@ int ndt2d_matcher_finish_match(ndt2d_matcher * m, const double * record, double 
   if (m == nullptr || record == nullptr || score_out == nullptr) return NDT2D_ERR_INVALID;
   // n_use is the N of the search prepared last (prepare_search / match_laser_scan);
   // scoring calls in between replace the device beams but leave it alone
-  const size_t use = m->n_use;
-  const size_t n_lin = m->dlin.size();
+  const size_t use = m->search.n_use;
+  const size_t n_lin = m->search.dlin.size();
   const double best_score = record[0];
   if (record[1] >= 0.0 && pose_inout != nullptr && n_lin > 0)
   {
@@ -1930,10 +2032,10 @@ int ndt2d_matcher_finish_match(ndt2d_matcher * m, const double * record, double 
     const uint64_t per_th = static_cast<uint64_t>(n_lin) * n_lin;
     const uint64_t ith = best_index / per_th;
     const uint64_t rem = best_index % per_th;
-    if (ith >= m->dth.size()) return mfail(m, NDT2D_ERR_INVALID, "finish_match: index out of range");
-    pose_inout[0] = m->dlin[rem / n_lin];
-    pose_inout[1] = m->dlin[rem % n_lin];
-    pose_inout[2] = m->dth[ith];
+    if (ith >= m->search.dth.size()) return mfail(m, NDT2D_ERR_INVALID, "finish_match: index out of range");
+    pose_inout[0] = m->search.dlin[rem / n_lin];
+    pose_inout[1] = m->search.dlin[rem % n_lin];
+    pose_inout[2] = m->search.dth[ith];
   }
   // :146 covariance = (1 / s) * k + (1 / (s * s) * u * u^T)
   if (covariance_out != nullptr)
@@ -1979,111 +2081,42 @@ int ndt2d_matcher_match_scan_ex(ndt2d_matcher * m, const double * scan_pose_xyt,
     return NDT2D_OK;
   }
   m->last_multi = false;
-  if (m->ahead)
-  {
-    // scoreScan launched a search ahead: is this the matchScan it was launched for -- the same
-    // pose, the same subsampled beams, no per-candidate scores wanted?
-    bool hit = all_scores == nullptr && (n_points == 0 || points_xy != nullptr) &&
-               std::memcmp(m->ahead_pose, scan_pose_xyt, sizeof(m->ahead_pose)) == 0;
-    if (hit)
-    {
-      subsample_into(m->scratch_beams, points_xy, n_points, m->laser_max_beams);
-      hit = m->scratch_beams.size() == m->beams.size() && !m->beams.empty() &&
-            std::memcmp(m->beams.data(), m->scratch_beams.data(), m->beams.size() * sizeof(double)) == 0;
-    }
-    if (hit)
-    {
-      // ... and still the search that is pending on the context?  (A caller may have launched or
-      // fetched on ndt2d_matcher_device(m) itself in between: then the record is not ours.)
-      uint64_t launched = 0, fetched = 0;
-      hit = ndt2d_match_status(m->dev, &launched, &fetched) == NDT2D_OK && launched == m->ahead_launch_id &&
-            fetched == m->ahead_fetch_id;
-    }
-    if (hit)
-    {
-      m->ahead = false;
-      ++m->ahead_collected;
-      m->score_scan_last = false;
-      const size_t n_lin_a = m->dlin.size();
-      if (n_candidates_out != nullptr) *n_candidates_out = m->ahead_n_th * n_lin_a * n_lin_a;
-      ndt2d_match_result res;
-      const int frc = ndt2d_match_fetch(m->dev, &res);
-      if (frc != NDT2D_OK) return dev_fail(m, frc, "ndt2d_match_fetch");
-      double rec[NDT2D_MATCH_RECORD_DOUBLES];
-      rec[0] = res.best_score;
-      rec[1] = res.best_index == NDT2D_NO_INDEX ? -1.0 : static_cast<double>(res.best_index) + (res.near_tie ? 0.5 : 0.0);
-      for (int i = 0; i < 10; ++i) rec[2 + i] = res.acc[i];
-      const int src = settle_near_tie(m, scan_pose_xyt, m->ahead_n_th, n_lin_a, m->n_use, rec);
-      if (src != NDT2D_OK) return src;
-      if (best_index_out != nullptr) *best_index_out = rec[1] < 0.0 ? NDT2D_NO_INDEX : static_cast<uint64_t>(rec[1]);
-      return ndt2d_matcher_finish_match(m, rec, pose_inout, covariance_out, score_out);
-    }
-    discard_ahead(m);
-  }
-  // (the pair: this matchScan is of the scan and pose the scoreScan just before it scored)
-  const bool after_score_scan =
-    m->score_scan_last && std::memcmp(m->score_scan_pose, scan_pose_xyt, sizeof(m->score_scan_pose)) == 0;
-  m->score_scan_last = false;
-  size_t n_th = 0, n_lin = 0, use = 0;
-  bool same_scan = false;
-  int rc = prepare_search_impl(m, scan_pose_xyt, points_xy, n_points, &n_th, &n_lin, &use, &same_scan);
-  if (rc != NDT2D_OK) return rc;
-  // (m->beams now holds this scan's subsampled beams, whether they were uploaded or found in place)
-  (void)same_scan;
-  if (after_score_scan && !m->beams.empty() && m->beams.size() == m->scored.size() &&
-      std::memcmp(m->beams.data(), m->scored.data(), m->beams.size() * sizeof(double)) == 0)
-  {
-    m->pair_seen = true;
-  }
-  const size_t n_cand = n_th * n_lin * n_lin;
-  if (n_candidates_out != nullptr) *n_candidates_out = n_cand;
-
   // record = {best_score, best_index or -1, k00,k01,k02,k11,k12,k22, u0,u1,u2, s}
   double record[NDT2D_MATCH_RECORD_DOUBLES] = {0, -1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  if (!m->search_ready)
+  size_t n_th = 0, n_lin = m->search.dlin.size(), use = m->search.n_use;
+  std::vector<double> tmp;
+  int rc = collect_ahead(m, scan_pose_xyt, points_xy, n_points, all_scores != nullptr, record, &n_th);
+  if (n_th > 0)
   {
-    // No points: every candidate scores -0.0 and none is < 0 (:127-128); no
-    // candidates: the loops do not run.  Either way k = u = s = 0.
-    if (all_scores != nullptr)
-    {
-      for (size_t i = 0; i < n_cand && i < all_scores_cap; ++i) all_scores[i] = -0.0;
-    }
+    // the search scoreScan launched ahead for this call
+    if (n_candidates_out != nullptr) *n_candidates_out = n_th * n_lin * n_lin;
+    if (rc != NDT2D_OK) return rc;
   }
   else
   {
-    std::vector<double> tmp;
-    double * scores_ptr = nullptr;
-    if (all_scores != nullptr)
+    rc = prepare_search_impl(m, scan_pose_xyt, points_xy, n_points, &n_th, &n_lin, &use);
+    note_match_scan(m, scan_pose_xyt, rc == NDT2D_OK);
+    if (rc != NDT2D_OK) return rc;
+    const size_t n_cand = n_th * n_lin * n_lin;
+    if (n_candidates_out != nullptr) *n_candidates_out = n_cand;
+    if (!m->search.ready)
     {
-      if (all_scores_cap >= n_cand)
-      {
-        scores_ptr = all_scores;
-      }
-      else
-      {
-        tmp.resize(n_cand);
-        scores_ptr = tmp.data();
-      }
+      // No points: every candidate scores -0.0 and none is < 0 (:127-128); no
+      // candidates: the loops do not run.  Either way k = u = s = 0.
+      for (size_t i = 0; all_scores != nullptr && i < n_cand && i < all_scores_cap; ++i) all_scores[i] = -0.0;
+      return ndt2d_matcher_finish_match(m, record, pose_inout, covariance_out, score_out);
     }
-    if (multi_search_wanted(m, n_th, n_lin, use))
+    double * scores_ptr = all_scores;
+    if (all_scores != nullptr && all_scores_cap < n_cand)
     {
-      // the lattice dealt to all devices of the matcher (ndt2d_matcher_create_multi)
-      rc = multi_match(m, scan_pose_xyt, n_th, n_lin, use, false, scores_ptr, record);
-      if (rc != NDT2D_OK) return rc;
+      tmp.resize(n_cand);
+      scores_ptr = tmp.data();
     }
-    else
-    {
-      ndt2d_match_result res;
-      rc = ndt2d_match(m->dev, 0, n_th, scores_ptr, &res);
-      if (rc != NDT2D_OK) return dev_fail(m, rc, "ndt2d_match");
-      record[0] = res.best_score;
-      record[1] = res.best_index == NDT2D_NO_INDEX ? -1.0 : static_cast<double>(res.best_index) + (res.near_tie ? 0.5 : 0.0);
-      for (int i = 0; i < 10; ++i) record[2 + i] = res.acc[i];
-    }
-    if ((rc = settle_near_tie(m, scan_pose_xyt, n_th, n_lin, use, record)) != NDT2D_OK) return rc;
-    if (!tmp.empty()) std::memcpy(all_scores, tmp.data(), all_scores_cap * sizeof(double));
-    if (best_index_out != nullptr) *best_index_out = record[1] < 0.0 ? NDT2D_NO_INDEX : static_cast<uint64_t>(record[1]);
+    if ((rc = run_search(m, scan_pose_xyt, n_th, n_lin, use, false, scores_ptr, record)) != NDT2D_OK) return rc;
   }
+  if ((rc = settle_near_tie(m, scan_pose_xyt, n_th, n_lin, use, record)) != NDT2D_OK) return rc;
+  if (!tmp.empty()) std::memcpy(all_scores, tmp.data(), all_scores_cap * sizeof(double));
+  if (best_index_out != nullptr) *best_index_out = record[1] < 0.0 ? NDT2D_NO_INDEX : static_cast<uint64_t>(record[1]);
   return ndt2d_matcher_finish_match(m, record, pose_inout, covariance_out, score_out);
   NDT2D_C_CATCH(m)
 }
@@ -2124,40 +2157,31 @@ int ndt2d_matcher_match_laser_scan(ndt2d_matcher * m, const double * scan_pose_x
                                        &n_points, &use);
   if (rc != NDT2D_OK) return dev_fail(m, rc, "ndt2d_set_beams_from_ranges");
   if (n_points_out != nullptr) *n_points_out = n_points;
-  m->beams.clear();
-  ++m->beams_epoch;
-  m->beams_on_device = false;   // the device holds beams the host has no copy of
-  m->n_use = use;
+  std::vector<double> none;
+  m->beams.adopt(none);   // the device holds beams the host has no copy of
+  m->search.n_use = use;
   size_t n_th = 0, n_lin = 0;
   rc = prepare_tables(m, scan_pose_xyt, use, nullptr, false, &n_th, &n_lin);
   if (rc != NDT2D_OK) return rc;
   double record[NDT2D_MATCH_RECORD_DOUBLES] = {0, -1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   m->last_multi = false;
-  if (m->search_ready && multi_search_wanted(m, n_th, n_lin, use))
+  if (m->search.ready)
   {
-    // every device converts the ranges itself (4 B/beam to each), then takes its theta steps
-    for (size_t r = 1; r < m->devs.size(); ++r)
+    if (multi_search_wanted(m, n_th, n_lin, use))
     {
-      size_t np = 0, nu = 0;
-      rc = ndt2d_set_beams_from_ranges(m->devs[r], ranges, n_ranges, scan, m->laser_max_beams, &np, &nu);
-      if (rc != NDT2D_OK) return dev_fail_at(m, r, rc, "ndt2d_set_beams_from_ranges");
-      if (np != n_points || nu != use) return mfail(m, NDT2D_ERR_HIP, "match_laser_scan: the devices disagree on the conversion");
+      // every device converts the ranges itself (4 B/beam to each), then takes its theta steps
+      for (size_t r = 1; r < m->devs.size(); ++r)
+      {
+        size_t np = 0, nu = 0;
+        rc = ndt2d_set_beams_from_ranges(m->devs[r], ranges, n_ranges, scan, m->laser_max_beams, &np, &nu);
+        if (rc != NDT2D_OK) return dev_fail_at(m, r, rc, "ndt2d_set_beams_from_ranges");
+        if (np != n_points || nu != use) return mfail(m, NDT2D_ERR_HIP, "match_laser_scan: the devices disagree on the conversion");
+      }
     }
-    rc = multi_match(m, scan_pose_xyt, n_th, n_lin, use, true, nullptr, record);
-    if (rc != NDT2D_OK) return rc;
+    if ((rc = run_search(m, scan_pose_xyt, n_th, n_lin, use, true, nullptr, record)) != NDT2D_OK) return rc;
     // (no host copy of the converted beams: a near-tie mark is counted, not settled)
     if (record[1] >= 0.0 && record[1] != std::floor(record[1])) ++m->adj_marked;
     if (record[1] >= 0.0) record[1] = std::floor(record[1]);
-  }
-  else if (m->search_ready)
-  {
-    ndt2d_match_result res;
-    rc = ndt2d_match(m->dev, 0, n_th, nullptr, &res);
-    if (rc != NDT2D_OK) return dev_fail(m, rc, "ndt2d_match");
-    record[0] = res.best_score;
-    record[1] = res.best_index == NDT2D_NO_INDEX ? -1.0 : static_cast<double>(res.best_index);
-    for (int i = 0; i < 10; ++i) record[2 + i] = res.acc[i];
-    if (res.near_tie) ++m->adj_marked;
   }
   return ndt2d_matcher_finish_match(m, record, pose_inout, covariance_out, score_out);
   NDT2D_C_CATCH(m)
@@ -2194,20 +2218,15 @@ int ndt2d_matcher_score_poses(ndt2d_matcher * m, const double * points_xy, size_
   if (multi_poses_wanted(m, n_poses, use))
   {
     // contiguous ranges of the batch on all devices of the matcher
-    if (pending)
-    {
-      rc = ndt2d_set_beams(m->dev, m->beams.data(), use);
-      if (rc != NDT2D_OK) return dev_fail(m, rc, "ndt2d_set_beams");
-      m->beams_on_device = true;
-    }
+    if (pending && (rc = upload_beams(m)) != NDT2D_OK) return rc;
     return multi_score_poses(m, poses_xyt, n_poses, use, scores_out, nullptr);
   }
   if (pending)
   {
     // a new scan: its beams go to the device with the scoring call itself
-    rc = ndt2d_score_poses_beams(m->dev, m->beams.data(), use, poses_xyt, n_poses, scores_out);
+    rc = ndt2d_score_poses_beams(m->dev, m->beams.host.data(), use, poses_xyt, n_poses, scores_out);
     if (rc != NDT2D_OK) return dev_fail(m, rc, "ndt2d_score_poses_beams");
-    m->beams_on_device = true;
+    m->beams.sent();
     return NDT2D_OK;
   }
   rc = ndt2d_score_poses(m->dev, poses_xyt, n_poses, scores_out, nullptr);
@@ -2235,8 +2254,7 @@ int ndt2d_matcher_score_points(ndt2d_matcher * m, const double * points_xy, size
 {
   NDT2D_C_TRY
   if (pose_xyt == nullptr || score_out == nullptr) return NDT2D_ERR_INVALID;
-  if (m != nullptr && m->single_pose_host && m->have_ndt && n_points > 0 && points_xy != nullptr &&
-      m->laser_max_beams > 0 && std::min(m->laser_max_beams, n_points) <= m->single_pose_max_beams)
+  if (m != nullptr && single_pose_on_host(m, points_xy, n_points))
   {
     // One pose of a short scan -- the unchanged ParticleFilter::measure calls this once per
     // particle (reference src/particle_filter.cpp:81-87): a kernel launch and a round trip over
@@ -2262,39 +2280,32 @@ int ndt2d_matcher_score_scan(ndt2d_matcher * m, const double * scan_pose_xyt,
   if (m == nullptr || scan_pose_xyt == nullptr || score_out == nullptr) return NDT2D_ERR_INVALID;
   discard_ahead(m);
   m->last_multi = false;
-  const bool ahead_wanted =
-    m->ahead_enabled && m->pair_seen && m->have_ndt && (n_points == 0 || points_xy != nullptr) && !m->dth.empty() &&
-    !m->dlin.empty() && !multi_search_wanted(m, m->dth.size(), m->dlin.size(), std::min(m->laser_max_beams, n_points));
-  if (m->single_pose_host && m->have_ndt && n_points > 0 && points_xy != nullptr && m->laser_max_beams > 0 &&
-      std::min(m->laser_max_beams, n_points) <= m->single_pose_max_beams)
+  const bool ahead_wanted = m->ahead.enabled && m->ahead.pair_seen && m->have_ndt &&
+                            (n_points == 0 || points_xy != nullptr) && !m->search.dth.empty() && !m->search.dlin.empty() &&
+                            !multi_search_wanted(m, m->search.dth.size(), m->search.dlin.size(),
+                                                 std::min(m->laser_max_beams, n_points));
+  if (single_pose_on_host(m, points_xy, n_points))
   {
     if (const HostNdt * ndt = host_ndt(m, true))
     {
       // The host scores the pose (see ndt2d_matcher_score_points) -- and when the matchScan of
-      // this scan is coming (`ahead`), its search is launched first and runs meanwhile.
-      subsample_into(m->scored, points_xy, n_points, m->laser_max_beams);
+      // this scan is coming (SearchAhead), its search is launched first and runs meanwhile.
       if (ahead_wanted)
       {
         size_t n_th = 0, n_lin = 0, use = 0;
-        if (prepare_search_impl(m, scan_pose_xyt, points_xy, n_points, &n_th, &n_lin, &use, nullptr) == NDT2D_OK &&
-            m->search_ready && ndt2d_match_launch(m->dev, 0, n_th, nullptr, nullptr) == NDT2D_OK)
+        if (prepare_search_impl(m, scan_pose_xyt, points_xy, n_points, &n_th, &n_lin, &use) == NDT2D_OK)
         {
-          m->ahead = true;
-          (void)ndt2d_match_status(m->dev, &m->ahead_launch_id, &m->ahead_fetch_id);
-          ++m->ahead_launched;
-          std::memcpy(m->ahead_pose, scan_pose_xyt, sizeof(m->ahead_pose));
-          m->ahead_n_th = n_th;
+          launch_ahead(m, scan_pose_xyt, n_th, use);
         }
       }
       *score_out = host_score_points(*ndt, points_xy, n_points, m->laser_max_beams, scan_pose_xyt);
-      m->score_scan_last = true;
-      std::memcpy(m->score_scan_pose, scan_pose_xyt, sizeof(m->score_scan_pose));
+      note_score_scan(m, scan_pose_xyt, points_xy, n_points);
       return NDT2D_OK;
     }
   }
   if (ahead_wanted)
   {
-    // The matchScan of this scan is coming (see `ahead`): its search goes onto the stream
+    // The matchScan of this scan is coming (SearchAhead): its search goes onto the stream
     // behind the scoring kernel, then the score is waited for.
     size_t use = 0;
     bool pending = false;
@@ -2302,43 +2313,31 @@ int ndt2d_matcher_score_scan(ndt2d_matcher * m, const double * scan_pose_xyt,
     if (rc != NDT2D_OK) return rc;
     if (use > 0)
     {
-      rc = ndt2d_score_poses_beams_launch(m->dev, pending ? m->beams.data() : nullptr, use, scan_pose_xyt, 1);
+      rc = ndt2d_score_poses_beams_launch(m->dev, pending ? m->beams.host.data() : nullptr, use, scan_pose_xyt, 1);
       if (rc == NDT2D_ERR_STATE && pending)
       {
         // more beams than travel as kernel arguments: one staged upload, then the launch on
         // the beams the device holds
-        rc = ndt2d_set_beams(m->dev, m->beams.data(), use);
-        if (rc != NDT2D_OK) return dev_fail(m, rc, "ndt2d_set_beams");
-        m->beams_on_device = true;
-        pending = false;
+        if ((rc = upload_beams(m)) != NDT2D_OK) return rc;
         rc = ndt2d_score_poses_beams_launch(m->dev, nullptr, use, scan_pose_xyt, 1);
       }
       if (rc == NDT2D_OK)
       {
-        m->beams_on_device = true;
+        m->beams.sent();
         size_t n_th = 0, n_lin = 0;
-        // (a search that cannot be launched ahead is not scoreScan's failure: matchScan will say)
-        if (prepare_tables(m, scan_pose_xyt, use, nullptr, true, &n_th, &n_lin) == NDT2D_OK && m->search_ready &&
-            ndt2d_match_launch(m->dev, 0, n_th, nullptr, nullptr) == NDT2D_OK)
+        if (prepare_tables(m, scan_pose_xyt, use, nullptr, true, &n_th, &n_lin) == NDT2D_OK)
         {
-          m->ahead = true;
-          (void)ndt2d_match_status(m->dev, &m->ahead_launch_id, &m->ahead_fetch_id);
-          ++m->ahead_launched;
-          std::memcpy(m->ahead_pose, scan_pose_xyt, sizeof(m->ahead_pose));
-          m->ahead_n_th = n_th;
-          m->n_use = use;
+          launch_ahead(m, scan_pose_xyt, n_th, use);
         }
         rc = ndt2d_score_fetch(m->dev, score_out);
         if (rc != NDT2D_OK)
         {
           const int frc = dev_fail(m, rc, "ndt2d_score_fetch");   // (the message, before anything else talks to the device)
           discard_ahead(m);
-          m->beams_on_device = false;
+          m->beams.lost();
           return frc;
         }
-        m->score_scan_last = true;
-        m->scored = m->beams;
-        std::memcpy(m->score_scan_pose, scan_pose_xyt, sizeof(m->score_scan_pose));
+        note_score_scan(m, scan_pose_xyt, points_xy, n_points);
         return NDT2D_OK;
       }
       if (rc != NDT2D_ERR_STATE) return dev_fail(m, rc, "ndt2d_score_poses_beams_launch");
@@ -2346,12 +2345,7 @@ int ndt2d_matcher_score_scan(ndt2d_matcher * m, const double * scan_pose_xyt,
     }
   }
   const int rc = ndt2d_matcher_score_poses(m, points_xy, n_points, scan_pose_xyt, 1, score_out);
-  if (rc == NDT2D_OK && m->have_ndt)
-  {
-    m->score_scan_last = true;
-    m->scored = m->beams;
-    std::memcpy(m->score_scan_pose, scan_pose_xyt, sizeof(m->score_scan_pose));
-  }
+  if (rc == NDT2D_OK && m->have_ndt) note_score_scan(m, scan_pose_xyt, points_xy, n_points);
   return rc;
   NDT2D_C_CATCH(m)
 }
@@ -2360,9 +2354,9 @@ int ndt2d_matcher_settle_near_tie(ndt2d_matcher * m, const double * scan_pose_xy
 {
   NDT2D_C_TRY
   if (m == nullptr || scan_pose_xyt == nullptr || record_inout == nullptr) return NDT2D_ERR_INVALID;
-  if (!m->search_ready) return mfail(m, NDT2D_ERR_STATE, "settle_near_tie: ndt2d_matcher_prepare_search first");
+  if (!m->search.ready) return mfail(m, NDT2D_ERR_STATE, "settle_near_tie: ndt2d_matcher_prepare_search first");
   discard_ahead(m);
-  return settle_near_tie(m, scan_pose_xyt, m->dth.size(), m->dlin.size(), m->n_use, record_inout);
+  return settle_near_tie(m, scan_pose_xyt, m->search.dth.size(), m->search.dlin.size(), m->search.n_use, record_inout);
   NDT2D_C_CATCH(m)
 }
 
@@ -2402,8 +2396,8 @@ int ndt2d_matcher_search_ahead_stats(ndt2d_matcher * m, uint64_t * launched, uin
 {
   NDT2D_C_TRY
   if (m == nullptr) return NDT2D_ERR_INVALID;
-  if (launched != nullptr) *launched = m->ahead_launched;
-  if (collected != nullptr) *collected = m->ahead_collected;
+  if (launched != nullptr) *launched = m->ahead.launched;
+  if (collected != nullptr) *collected = m->ahead.collected;
   return NDT2D_OK;
   NDT2D_C_CATCH(m)
 }
@@ -2412,9 +2406,8 @@ int ndt2d_matcher_set_search_ahead(ndt2d_matcher * m, int enabled)
 {
   NDT2D_C_TRY
   if (m == nullptr) return NDT2D_ERR_INVALID;
-  discard_ahead(m);
-  m->ahead_enabled = enabled != 0 ? 1 : 0;
-  m->pair_seen = false;
+  forget_ahead(m);
+  m->ahead.enabled = enabled != 0;
   return NDT2D_OK;
   NDT2D_C_CATCH(m)
 }
