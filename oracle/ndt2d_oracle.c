@@ -470,6 +470,38 @@ void orc_ndt_export_cells6(const orc_ndt * ndt, double * out)
   }
 }
 
+orc_ndt * orc_ndt_from_cells6(const double * cells6, size_t size_x, size_t size_y,
+                              double cell_size, double origin_x, double origin_y)
+{
+  orc_ndt * ndt = (orc_ndt *)calloc(1, sizeof(orc_ndt));
+  if (!ndt) return NULL;
+  ndt->cell_size = cell_size;
+  ndt->size_x = size_x;
+  ndt->size_y = size_y;
+  ndt->origin_x = origin_x;
+  ndt->origin_y = origin_y;
+  size_t ncell = size_x * size_y;
+  ndt->cells = (orc_cell *)calloc(ncell ? ncell : 1, sizeof(orc_cell));
+  if (!ndt->cells)
+  {
+    free(ndt);
+    return NULL;
+  }
+  for (size_t i = 0; i < ncell; ++i)
+  {
+    orc_cell * c = &ndt->cells[i];
+    c->mean[0] = cells6[6 * i + 0];
+    c->mean[1] = cells6[6 * i + 1];
+    c->information[0] = cells6[6 * i + 2];
+    c->information[1] = cells6[6 * i + 3];
+    c->information[2] = cells6[6 * i + 3];
+    c->information[3] = cells6[6 * i + 4];
+    c->n = cells6[6 * i + 5];
+    c->valid = c->n >= 5;
+  }
+  return ndt;
+}
+
 /* ------------------------------------------------------------------------- */
 /* ScanMatcherNDT                                                            */
 /* ------------------------------------------------------------------------- */
@@ -557,6 +589,16 @@ void orc_matcher_reset(orc_matcher * m)
 
 int orc_matcher_has_ndt(const orc_matcher * m) { return m->ndt != NULL; }
 const orc_ndt * orc_matcher_ndt(const orc_matcher * m) { return m->ndt; }
+
+/* The NDT is the only state addScans leaves in a matcher (the parameters of initialize stay as
+ * they are, m->resolution included: the grid's own cell_size is what every index uses), so
+ * replacing it is all there is to do.  m->ndt == NULL afterwards if memory ran out. */
+void orc_matcher_set_cells6(orc_matcher * m, const double * cells6, size_t size_x, size_t size_y,
+                            double cell_size, double origin_x, double origin_y)
+{
+  orc_ndt_destroy(m->ndt);
+  m->ndt = orc_ndt_from_cells6(cells6, size_x, size_y, cell_size, origin_x, origin_y);
+}
 
 size_t orc_search_offsets(double size, double res, double * out, size_t cap)
 {

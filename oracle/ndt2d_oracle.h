@@ -88,6 +88,12 @@ double orc_ndt_origin_y(const orc_ndt * ndt);
 const orc_cell * orc_ndt_cells(const orc_ndt * ndt);
 /* Pack every cell as {mean_x, mean_y, info00, info01, info11, n} (6 doubles). */
 void orc_ndt_export_cells6(const orc_ndt * ndt, double * out);
+/* The inverse: an NDT of size_x x size_y cells whose cells are the given records, taken as
+ * they are (information(1,0) = information(0,1) = info01; `valid` = n >= 5; the covariance and
+ * correlation of a cell stay zero: nothing that scores reads them).  Test infrastructure for
+ * grids whose records are the test vectors (tests/designed_grids.py).  NULL if memory runs out. */
+orc_ndt * orc_ndt_from_cells6(const double * cells6, size_t size_x, size_t size_y,
+                              double cell_size, double origin_x, double origin_y);
 
 /* The reference's `for (v = -size; v < size; v += res)` loop
  * (scan_matcher_ndt.cpp:103,117,119).  Writes at most cap values, returns the
@@ -151,6 +157,9 @@ double orc_matcher_score_scan(const orc_matcher * m, const double * scan_pose_xy
 void orc_matcher_reset(orc_matcher * m);                         /* :180-183 */
 int orc_matcher_has_ndt(const orc_matcher * m);
 const orc_ndt * orc_matcher_ndt(const orc_matcher * m);
+/* Install orc_ndt_from_cells6(...) as the matcher's NDT, in place of addScans. */
+void orc_matcher_set_cells6(orc_matcher * m, const double * cells6, size_t size_x, size_t size_y,
+                            double cell_size, double origin_x, double origin_y);
 
 /* ParticleFilter::measure, the per-particle loop (particle_filter.cpp:81-87):
  * weights[i] = scorePoints(points, particle_i).  The per-particle copy of the

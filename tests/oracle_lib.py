@@ -77,6 +77,8 @@ def lib():
     sig("orc_ndt_origin_y", d, [vp])
     sig("orc_ndt_cells", C.POINTER(OrcCell), [vp])
     sig("orc_ndt_export_cells6", None, [vp, _dp])
+    sig("orc_ndt_from_cells6", vp, [_dp, sz, sz, d, d, d])
+    sig("orc_matcher_set_cells6", None, [vp, _dp, sz, sz, d, d, d])
     sig("orc_search_offsets", sz, [d, d, _dp, sz])
     sig("orc_matcher_create", vp, [])
     sig("orc_matcher_destroy", None, [vp])
@@ -215,6 +217,17 @@ class NDT(_NDTView):
     def compute(self):
         lib().orc_ndt_compute(self.p)
 
+    @classmethod
+    def from_cells6(cls, cells6, size_x, size_y, cell_size, origin):
+        """The NDT whose cells ARE the given records (orc_ndt_export_cells6's inverse)."""
+        c6, cp = _arr(np.asarray(cells6, dtype=np.float64).reshape(-1, 6))
+        assert len(c6) == size_x * size_y, (len(c6), size_x, size_y)
+        self = cls.__new__(cls)
+        ptr = lib().orc_ndt_from_cells6(cp, size_x, size_y, cell_size, origin[0], origin[1])
+        assert ptr, "orc_ndt_from_cells6: out of memory"
+        _NDTView.__init__(self, ptr)
+        return self
+
 
 def search_offsets(size, res):
     n = lib().orc_search_offsets(size, res, None, 0)
@@ -258,6 +271,12 @@ class ScanMatcherNDT:
         lib().orc_matcher_add_scans(
             self.m, poses.ctypes.data_as(_dp), allpts.ctypes.data_as(_dp),
             offsets.ctypes.data_as(C.POINTER(C.c_size_t)), len(scans))
+
+    def setCells6(self, cells6, size_x, size_y, cell_size, origin):
+        """Install a grid given as its records, in place of addScans."""
+        c6, cp = _arr(np.asarray(cells6, dtype=np.float64).reshape(-1, 6))
+        assert len(c6) == size_x * size_y, (len(c6), size_x, size_y)
+        lib().orc_matcher_set_cells6(self.m, cp, size_x, size_y, cell_size, origin[0], origin[1])
 
     def reset(self):
         lib().orc_matcher_reset(self.m)
