@@ -341,6 +341,59 @@ int ndt2d_pf_update(ndt2d_handle h, double * h_poses_xyt, size_t n, double dx, d
                     double dth, const double * alphas5, const float * h_noise, uint64_t seed,
                     uint64_t step, double * h_weights, double * h_out);
 
+/* ---- ParticleFilter::resample on the device (particles stay in HBM) ----
+ *
+ * The KLD draw-and-stop loop (src/particle_filter.cpp:91-137) as kernels.  For every
+ * input the indices and the count are exactly what the host form ndt2d_kld_resample
+ * (section 3, the parity reference) returns for the same particles, weights, uniforms
+ * and parameters: the cumulative weights are summed in index order with one rounding
+ * per add, a draw is libstdc++'s upper_bound bisection, the leaf count after draw i is
+ * the number of distinct keys among draws 0..i, and the count kept is one more than the
+ * first i whose size passes the stop test.  A resampler is an object of its own beside
+ * the context: it owns its workspace (sized at creation) and a pinned word for the
+ * count, launches on the context's current stream (ndt2d_set_stream), and must be
+ * destroyed before ndt2d_destroy(h).  One launch may be in flight per resampler. */
+typedef struct ndt2d_resampler ndt2d_resampler;
+/* n_capacity: the most particles a launch may draw from (1 .. 2^32-1);
+ * max_particles_capacity: the largest max_particles of a launch (up to 2^30). */
+int ndt2d_resampler_create(ndt2d_handle h, size_t n_capacity, size_t max_particles_capacity,
+                           ndt2d_resampler ** out);
+int ndt2d_resampler_destroy(ndt2d_resampler * r);
+const char * ndt2d_resampler_last_error(ndt2d_resampler * r);
+/* The uniform stream a launch with d_uniforms == NULL uses, written to DEVICE
+ * d_out[n]: Philox4x32-10 with key = seed and counter (first_index + i, step), the
+ * convention of ndt2d_pf_noise_launch; u = ((w0 >> 5) * 2^26 + (w1 >> 6)) * 2^-53, in
+ * [0, 1) on the 2^-53 grid.  Asynchronous. */
+int ndt2d_resample_uniforms_launch(ndt2d_resampler * r, uint64_t seed, uint64_t step,
+                                   uint64_t first_index, size_t n, double * d_out);
+/* The loop and the copy of the kept particles on DEVICE pointers, asynchronous:
+ * d_particles_out[max_particles][3] and d_weights_out[max_particles] receive
+ * in[p_j] for j < count (weights as they are: updateStatistics renormalises),
+ * d_indices_out[max_particles] (or NULL) the p_j.  d_uniforms = [max_particles]
+ * values in [0, 1) or NULL (the Philox stream of (seed, step), index 0 onwards).
+ * leaf_size3 is a HOST pointer.  The outputs may not alias the inputs.  Refusals are
+ * those of ndt2d_kld_resample, plus sizes beyond the created capacities
+ * (NDT2D_ERR_INVALID); max_particles == 0 keeps nothing and is NDT2D_OK. */
+int ndt2d_resample_launch(ndt2d_resampler * r, const double * d_particles_xyt,
+                          const double * d_weights, size_t n, size_t min_particles,
+                          size_t max_particles, double kld_err, double kld_z,
+                          const double * leaf_size3, const double * d_uniforms, uint64_t seed,
+                          uint64_t step, double * d_particles_out, double * d_weights_out,
+                          uint32_t * d_indices_out);
+/* Waits for the launch and returns the count kept (the gather read it from device
+ * memory; no host round trip precedes it). */
+int ndt2d_resample_fetch(ndt2d_resampler * r, size_t * n_out);
+/* HIP events around the cumulative-weights kernel of each launch (the one serial
+ * part: one dependent FP64 add per particle) on / off, and the last one's time. */
+int ndt2d_resampler_set_timing(ndt2d_resampler * r, int enabled);
+int ndt2d_resampler_cdf_ms(ndt2d_resampler * r, float * ms);
+/* Host-pointer convenience with ndt2d_kld_resample's own arguments and a handle:
+ * upload, launch, fetch, indices back. */
+int ndt2d_pf_resample(ndt2d_handle h, const double * particles_xyt, const double * weights,
+                      size_t n, size_t min_particles, size_t max_particles, double kld_err,
+                      double kld_z, const double * leaf_size3, const double * uniforms,
+                      size_t n_uniforms, uint32_t * indices_out, size_t * n_out);
+
 /* ---- LaserScan -> Scan conversion on the device ----
  *
  * The loop of NdtMapper::laserCallback that turns a sensor_msgs/LaserScan into
@@ -687,8 +740,9 @@ int ndt2d_matcher_grid_cells6(ndt2d_matcher * m, double * cells6_out, size_t cap
  * loops): writes up to cap values, returns the count through *n_out. */
 int ndt2d_search_offsets(double size, double res, double * out, size_t cap, size_t * n_out);
 /* The draw-and-stop loop of ParticleFilter::resample (src/particle_filter.cpp:
- * 94-134), host code: KLD sampling is a sequential stopping rule and stays on the
- * CPU.  Draw i picks the particle whose cumulative weight
+ * 94-134), host code.  This is the host form and the parity reference of the
+ * device form (ndt2d_resample_launch, section 1), which returns the same indices and
+ * count for every input.  Draw i picks the particle whose cumulative weight
  * first exceeds uniforms[i] * sum(weights) (what std::discrete_distribution does
  * with its own generator, :94,110; the caller supplies the uniforms in [0, 1), so
  * any generator can drive it), inserts its KD-tree key

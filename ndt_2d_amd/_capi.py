@@ -112,6 +112,17 @@ SIGNATURES = {
     "ndt2d_pose_moments_launch": (C.c_int, [_vp, _vp, _sz, _vp, _vp]),
     "ndt2d_pf_update": (C.c_int, [_vp, _dp, _sz, _d, _d, _d, _dp, C.POINTER(C.c_float), _u64,
                                   _u64, _dp, _dp]),
+    "ndt2d_resampler_create": (C.c_int, [_vp, _sz, _sz, C.POINTER(_vp)]),
+    "ndt2d_resampler_destroy": (C.c_int, [_vp]),
+    "ndt2d_resampler_last_error": (C.c_char_p, [_vp]),
+    "ndt2d_resample_uniforms_launch": (C.c_int, [_vp, _u64, _u64, _u64, _sz, _vp]),
+    "ndt2d_resample_launch": (C.c_int, [_vp, _vp, _vp, _sz, _sz, _sz, _d, _d, _dp, _vp, _u64, _u64,
+                                        _vp, _vp, _vp]),
+    "ndt2d_resample_fetch": (C.c_int, [_vp, _szp]),
+    "ndt2d_resampler_set_timing": (C.c_int, [_vp, C.c_int]),
+    "ndt2d_resampler_cdf_ms": (C.c_int, [_vp, C.POINTER(C.c_float)]),
+    "ndt2d_pf_resample": (C.c_int, [_vp, _dp, _dp, _sz, _sz, _sz, _d, _d, _dp, _dp, _sz,
+                                    C.POINTER(_u32), _szp]),
     "ndt2d_convert_scan_launch": (C.c_int, [_vp, _vp, _sz, C.POINTER(LaserScan), _vp, _vp]),
     "ndt2d_convert_scan": (C.c_int, [_vp, C.POINTER(C.c_float), _sz, C.POINTER(LaserScan), _dp,
                                      _szp]),

@@ -5,10 +5,12 @@ include/ndt_2d/particle_filter.hpp:49-115, src/particle_filter.cpp) for the part
 of it that lies either side of the measurement hot path: `init`, `update`
 (MotionModel::sample), `measure` and `updateStatistics` all run as HIP kernels on
 one [n, 3] pose array that never leaves the device between calls.  `resample`
-(KLD sampling over the KD-tree leaf count, src/particle_filter.cpp:91-140) stays
-on the host, as SURVEY.md section 8(f) row N3 scopes it: it is a sequential
-stopping rule over weighted draws; only the gather of the chosen particles runs
-on the device.
+(KLD sampling over the KD-tree leaf count, src/particle_filter.cpp:91-140) has two
+forms that give the same particles bit for bit: the host form (the default, and the
+parity reference: particles and weights go to the host, the draw-and-stop loop runs
+there, the gather on the device) and, with resample_on="device", the same rule as
+kernels (csrc/resample/ndt2d_resample.hip), after which only the count kept comes
+back to the host.
 
 torch is used for device memory and the stream only.
 """
@@ -94,10 +96,21 @@ def kld_resample_native(particles, weights, min_particles, max_particles, kld_er
 class ParticleFilter:
     """ndt_2d::ParticleFilter over the MI355X kernels.  `matcher` supplies the device
     context (an ndt_2d_amd.ScanMatcherNDT); `seed` keys the Philox noise stream
-    that stands in for the reference's random_device-seeded mt19937."""
+    that stands in for the reference's random_device-seeded mt19937.
 
-    def __init__(self, min_particles, max_particles, motion_model, matcher, seed=0):
+    resample_on: "host" (default) runs the draw-and-stop loop of `resample` on the host;
+    "device" runs it as kernels on the same host-generated uniforms (bit for bit the
+    "host" run, only the count comes back); "device-philox" also draws the uniforms on
+    the device (Philox stream of (seed, step): nothing is uploaded, a different but
+    equally valid sequence of draws)."""
+
+    RESAMPLE_ON = ("host", "device", "device-philox")
+
+    def __init__(self, min_particles, max_particles, motion_model, matcher, seed=0,
+                 resample_on="host"):
         import torch
+        if resample_on not in self.RESAMPLE_ON:
+            raise ValueError("resample_on must be one of %s" % (self.RESAMPLE_ON,))
         if not torch.cuda.is_available():
             raise _capi.Ndt2dError(_capi.ERR_NO_DEVICE, "ParticleFilter",
                                    "no usable GPU; this library has no CPU fallback")
@@ -113,6 +126,12 @@ class ParticleFilter:
         self.seed = int(seed)
         self._step = 0
         self._host_rng = np.random.Generator(np.random.Philox(key=self.seed))
+        self.resample_on = resample_on
+        self._resampler = None
+        if resample_on != "host":
+            # the set holds min_particles at first and at most max(min, max) ever after
+            self._resampler = matcher.create_resampler(
+                max(self.min_particles, self.max_particles, 1), self.max_particles)
         with torch.cuda.stream(self._stream):
             # reference particle_filter.cpp:48-50
             self.particles = torch.zeros((self.min_particles, 3), dtype=torch.float64,
@@ -155,6 +174,9 @@ class ParticleFilter:
     def resample(self, kld_err, kld_z):
         """reference src/particle_filter.cpp:91-140"""
         torch = self._torch
+        if self._resampler is not None:
+            self._resample_on_device(kld_err, kld_z)
+            return
         self._stream.synchronize()
         pa = self.particles.cpu().numpy()
         w = self.weights.cpu().numpy()
@@ -165,6 +187,29 @@ class ParticleFilter:
             idx = torch.from_numpy(keep.astype(np.int64)).to(self.device)
             self.particles = self.particles.index_select(0, idx).contiguous()
             self.weights = self.weights.index_select(0, idx).contiguous()
+        self._update_statistics(have_moments=False)
+
+    def _resample_on_device(self, kld_err, kld_z):
+        torch = self._torch
+        m = self.max_particles
+        with torch.cuda.stream(self._stream):
+            d_u = None
+            step = 0
+            if self.resample_on == "device":
+                # the draws of the host form: the same generator, the same count of values
+                d_u = torch.from_numpy(self._host_rng.random(m)).to(self.device)
+            else:
+                step = self._next_step()
+            out_p = torch.empty((m, 3), dtype=torch.float64, device=self.device)
+            out_w = torch.empty((m,), dtype=torch.float64, device=self.device)
+            self._resampler.launch(self.particles.data_ptr(), self.weights.data_ptr(),
+                                   len(self.particles), self.min_particles, m, kld_err, kld_z,
+                                   out_p.data_ptr(), out_w.data_ptr(), None,
+                                   d_u.data_ptr() if d_u is not None else None, self.seed, step,
+                                   KD_LEAF)
+            n_keep = self._resampler.fetch()
+            self.particles = out_p[:n_keep]
+            self.weights = out_w[:n_keep]
         self._update_statistics(have_moments=False)
 
     def getMean(self):

@@ -144,6 +144,9 @@ class ScanMatcherNDT:
             state = getattr(self, "_pinned_state", None)
             if state is not None:
                 state["handle"] = None
+            # resamplers live on this context's device layer: they go first
+            for r in list(getattr(self, "_resamplers", ())):
+                r.close()
             self._L.ndt2d_matcher_destroy(self._m)
             self._m = None
 
@@ -466,6 +469,31 @@ class ScanMatcherNDT:
                                                           weights_ptr, stats_ptr),
                         "ndt2d_pose_moments_launch")
 
+    def create_resampler(self, n_capacity, max_particles_capacity):
+        """A Resampler (ParticleFilter::resample on the device) on this matcher's device
+        context: it draws from up to n_capacity particles, up to max_particles_capacity times."""
+        r = Resampler(self, n_capacity, max_particles_capacity)
+        if not hasattr(self, "_resamplers"):
+            self._resamplers = weakref.WeakSet()
+        self._resamplers.add(r)
+        return r
+
+    def pf_resample(self, particles, weights, min_particles, max_particles, kld_err, kld_z, uniforms,
+                    leaf=(0.5, 0.5, 0.2671)):
+        """ndt2d_pf_resample: kld_resample_native's arguments, computed on the device from host
+        arrays.  Returns the indices of the draws kept."""
+        pa = _f64(particles, (-1, 3))
+        w = _f64(weights)
+        u = _f64(uniforms)
+        lf = _f64(leaf, (3,))
+        out = np.empty(max(int(max_particles), 1), dtype=np.uint32)
+        n_out = C.c_size_t(0)
+        self._dev_check(self._L.ndt2d_pf_resample(
+            self.device_handle, dptr(pa), dptr(w), len(w), int(min_particles), int(max_particles),
+            float(kld_err), float(kld_z), dptr(lf), dptr(u), len(u),
+            out.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(n_out)), "ndt2d_pf_resample")
+        return out[:n_out.value].copy()
+
     def set_stream(self, stream_ptr):
         self._dev_check(self._L.ndt2d_set_stream(self.device_handle, stream_ptr),
                         "ndt2d_set_stream")
@@ -532,6 +560,75 @@ class ScanMatcherNDT:
         rc = self._L.ndt2d_set_variant(self.device_handle, name.encode())
         if rc != _capi.OK:
             raise Ndt2dError(rc, "ndt2d_set_variant")
+
+
+class Resampler:
+    """ndt2d_resampler: the KLD draw-and-stop loop of ParticleFilter::resample (reference
+    src/particle_filter.cpp:91-137) as kernels on DEVICE pointers.  Launches go to the stream
+    the matcher's device context is bound to; indices and count are those of the host form
+    (particle_filter.kld_resample_native) for the same inputs."""
+
+    def __init__(self, matcher, n_capacity, max_particles_capacity):
+        self._L = matcher._L
+        self._r = None
+        self._matcher = matcher   # the context must outlive the resampler
+        r = C.c_void_p()
+        matcher._dev_check(self._L.ndt2d_resampler_create(matcher.device_handle, int(n_capacity),
+                                                          int(max_particles_capacity), C.byref(r)),
+                           "ndt2d_resampler_create")
+        self._r = r
+        self.n_capacity = int(n_capacity)
+        self.max_particles_capacity = int(max_particles_capacity)
+
+    def close(self):
+        if getattr(self, "_r", None):
+            self._L.ndt2d_resampler_destroy(self._r)
+            self._r = None
+        self._matcher = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc, where):
+        if rc != _capi.OK:
+            msg = self._L.ndt2d_resampler_last_error(self._r)
+            raise Ndt2dError(rc, where, msg.decode() if msg else "")
+
+    def uniforms_launch(self, seed, step, first_index, n, out_ptr):
+        """The Philox uniform stream of (seed, step) for draws first_index .. first_index + n
+        into DEVICE double[n]: what launch() uses when uniforms_ptr is None."""
+        self._check(self._L.ndt2d_resample_uniforms_launch(self._r, seed, step, first_index, n,
+                                                           out_ptr),
+                    "ndt2d_resample_uniforms_launch")
+
+    def launch(self, particles_ptr, weights_ptr, n, min_particles, max_particles, kld_err, kld_z,
+               particles_out_ptr, weights_out_ptr, indices_out_ptr=None, uniforms_ptr=None, seed=0,
+               step=0, leaf=(0.5, 0.5, 0.2671)):
+        """Asynchronous: draws, stop rule and the gather of the kept particles; every pointer
+        is a DEVICE address.  fetch() returns the count kept."""
+        lf = _f64(leaf, (3,))
+        self._check(self._L.ndt2d_resample_launch(
+            self._r, particles_ptr, weights_ptr, int(n), int(min_particles), int(max_particles),
+            float(kld_err), float(kld_z), dptr(lf), uniforms_ptr, int(seed), int(step),
+            particles_out_ptr, weights_out_ptr, indices_out_ptr), "ndt2d_resample_launch")
+
+    def fetch(self):
+        n = C.c_size_t(0)
+        self._check(self._L.ndt2d_resample_fetch(self._r, C.byref(n)), "ndt2d_resample_fetch")
+        return n.value
+
+    def set_timing(self, enabled):
+        self._check(self._L.ndt2d_resampler_set_timing(self._r, 1 if enabled else 0),
+                    "ndt2d_resampler_set_timing")
+
+    def cdf_ms(self):
+        """Kernel time of the last launch's cumulative-weights chain (set_timing(True))."""
+        ms = C.c_float(0.0)
+        self._check(self._L.ndt2d_resampler_cdf_ms(self._r, C.byref(ms)), "ndt2d_resampler_cdf_ms")
+        return ms.value
 
 
 def pf_measure(matcher, particles, points, cov_prev=None):
