@@ -462,6 +462,86 @@ int ndt2d_occupancy_grid(ndt2d_handle h, double resolution, double occ_thresh,
                          double * bounds_inout, ndt2d_occupancy_info * info_out,
                          signed char * data_out, size_t data_capacity);
 
+/* ---- OccupancyGrid with resident scans and counts ----
+ *
+ * The same generator for a caller that publishes after every scan: the scans'
+ * points, the hit / empty counters and the int8 map stay on the device, so a
+ * publish after one more scan uploads that scan and its pose, traces its beams
+ * into the counters of the last publish and returns the cells that can have
+ * changed.  Counts are integers: the map is bit-identical to a full re-trace and
+ * to ndt2d_occupancy_grid.  An ndt2d_occupancy_map is an object of its own beside
+ * the context, one per generator: it holds min_x_ / max_x_ / min_y_ / max_y_ and
+ * num_scans_ (:37-43), works on the context's current stream (ndt2d_set_stream)
+ * and must be destroyed before ndt2d_destroy(h).  A scan's points never change
+ * once appended; a caller that drops or replaces scans calls ndt2d_occmap_reset.
+ *
+ * The rule of ndt2d_occmap_update(map, poses_xyt, n_scans, &result), which renders
+ * the first n_scans appended scans at the given poses:
+ *
+ * 1. n_scans below the count of the last update, or above the appended count, is
+ *    NDT2D_ERR_INVALID.  A caller that drops scans calls ndt2d_occmap_reset.
+ * 2. When n_scans differs from num_scans_, the bounds are extended by the scans
+ *    [num_scans_, n_scans) and re-rounded, with the host arithmetic of
+ *    ndt2d_occupancy_grid -- including the reference's quirk of re-rounding on
+ *    every change of count (:51-54,181-184).
+ * 3. Geometry comes from the bounds (:57-64).  Degenerate extents are refused as
+ *    ndt2d_occupancy_grid refuses them (the object keeps the state it had).
+ * 4. The mode depends on three conditions, all compared bit for bit: the counters
+ *    are valid, the geometry (origin_x, origin_y, width, height) equals the last
+ *    update's, and the poses of the scans already rendered equal the last
+ *    update's (-0.0 against 0.0 counts as changed).
+ *      all three hold and n_scans grew:          NDT2D_OCCMAP_INCREMENTAL, only the
+ *                                                new scans are traced and added;
+ *      all three hold and n_scans did not grow:  NDT2D_OCCMAP_UNCHANGED, nothing is
+ *                                                traced, the rectangle is empty;
+ *      any of the three fails:                   NDT2D_OCCMAP_FULL, the counters are
+ *                                                cleared and all scans re-traced from
+ *                                                the resident points (nothing but
+ *                                                poses is uploaded).
+ * 5. Whether a shifted origin reproduces the same cells is a question of rounding
+ *    in (p - origin) / resolution, and the rule does not try to answer it: any
+ *    geometry change means FULL.  That is what keeps the result exact.
+ * 6. FULL finalizes the whole map, INCREMENTAL the dirty rectangle only.
+ * 7. The dirty rectangle is the cell bounding box of the new scans' start and end
+ *    cells, clipped to the map (Bresenham never leaves that box; cell coordinates
+ *    are monotone in the map-frame coordinate, so it comes from the bounds
+ *    reduction of step 2 and the new poses, without a second read-back).  FULL
+ *    reports the whole map. */
+typedef struct ndt2d_occupancy_map ndt2d_occupancy_map;
+#define NDT2D_OCCMAP_FULL 0
+#define NDT2D_OCCMAP_INCREMENTAL 1
+#define NDT2D_OCCMAP_UNCHANGED 2
+typedef struct ndt2d_occmap_result
+{
+  ndt2d_occupancy_info info;
+  int mode;                  /* NDT2D_OCCMAP_* */
+  uint64_t beams_traced;     /* rays walked by this update */
+  uint32_t rect_x0, rect_y0, rect_w, rect_h;   /* cells that can differ from the last update */
+} ndt2d_occmap_result;
+/* resolution > 0 (NDT2D_ERR_INVALID otherwise). */
+int ndt2d_occmap_create(ndt2d_handle h, double resolution, double occ_thresh,
+                        ndt2d_occupancy_map ** out);
+int ndt2d_occmap_destroy(ndt2d_occupancy_map * map);
+const char * ndt2d_occmap_last_error(ndt2d_occupancy_map * map);
+/* points_xy[n_points][2] in the scan's own frame (HOST; uploaded once, here);
+ * n_points == 0 is allowed.  *scan_id_out (optional) = 0, 1, 2, ... */
+int ndt2d_occmap_append_scan(ndt2d_occupancy_map * map, const double * points_xy,
+                             size_t n_points, size_t * scan_id_out);
+int ndt2d_occmap_scan_count(ndt2d_occupancy_map * map, size_t * n_out);
+/* Forget scans, counters and bounds: a new generator (device memory is kept). */
+int ndt2d_occmap_reset(ndt2d_occupancy_map * map);
+/* poses_xyt[n_scans][3] (HOST).  See the rule above.  Returns when the bounds are
+ * known; the trace may still be running (ndt2d_occmap_read waits for it). */
+int ndt2d_occmap_update(ndt2d_occupancy_map * map, const double * poses_xyt, size_t n_scans,
+                        ndt2d_occmap_result * result);
+/* The rectangle [x0, x0 + w) x [y0, y0 + h) of the device map of the last update
+ * into HOST out[h][out_row_stride] (out_row_stride >= w).  A rectangle that leaves
+ * the map is NDT2D_ERR_INVALID; before the first update NDT2D_ERR_STATE. */
+int ndt2d_occmap_read(ndt2d_occupancy_map * map, uint32_t x0, uint32_t y0, uint32_t w,
+                      uint32_t h, signed char * out, size_t out_row_stride);
+/* bounds4_out = {min_x_, max_x_, min_y_, max_y_}, *num_scans_out = num_scans_. */
+int ndt2d_occmap_bounds(ndt2d_occupancy_map * map, double * bounds4_out, size_t * num_scans_out);
+
 /* ---- device memory for hosts without a GPU runtime of their own ----
  *
  * The *_launch entry points take device pointers.  A host that already manages

@@ -54,6 +54,18 @@ class OccupancyInfo(C.Structure):
                 ("origin_x", C.c_double), ("origin_y", C.c_double)]
 
 
+class OccmapResult(C.Structure):
+    """ndt2d_occmap_result"""
+    _fields_ = [("info", OccupancyInfo), ("mode", C.c_int), ("beams_traced", C.c_uint64),
+                ("rect_x0", C.c_uint32), ("rect_y0", C.c_uint32), ("rect_w", C.c_uint32),
+                ("rect_h", C.c_uint32)]
+
+
+OCCMAP_FULL = 0
+OCCMAP_INCREMENTAL = 1
+OCCMAP_UNCHANGED = 2
+
+
 class World(C.Structure):
     _fields_ = [("room_half", C.c_double), ("pillar_pitch", C.c_double),
                 ("pillar_half", C.c_double)]
@@ -131,6 +143,15 @@ SIGNATURES = {
     "ndt2d_scan_points": (_vp, [_vp, _szp]),
     "ndt2d_occupancy_grid": (C.c_int, [_vp, _d, _d, _dp, _dp, _szp, _sz, _sz, _dp,
                                        C.POINTER(OccupancyInfo), _vp, _sz]),
+    "ndt2d_occmap_create": (C.c_int, [_vp, _d, _d, C.POINTER(_vp)]),
+    "ndt2d_occmap_destroy": (C.c_int, [_vp]),
+    "ndt2d_occmap_last_error": (C.c_char_p, [_vp]),
+    "ndt2d_occmap_append_scan": (C.c_int, [_vp, _dp, _sz, _szp]),
+    "ndt2d_occmap_scan_count": (C.c_int, [_vp, _szp]),
+    "ndt2d_occmap_reset": (C.c_int, [_vp]),
+    "ndt2d_occmap_update": (C.c_int, [_vp, _dp, _sz, C.POINTER(OccmapResult)]),
+    "ndt2d_occmap_read": (C.c_int, [_vp, _u32, _u32, _u32, _u32, _vp, _sz]),
+    "ndt2d_occmap_bounds": (C.c_int, [_vp, _dp, _szp]),
     "ndt2d_device_alloc": (C.c_int, [_vp, _sz, C.POINTER(_vp)]),
     "ndt2d_device_free": (C.c_int, [_vp, _vp]),
     "ndt2d_copy_to_device": (C.c_int, [_vp, _vp, _vp, _sz]),

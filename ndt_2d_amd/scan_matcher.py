@@ -147,6 +147,8 @@ class ScanMatcherNDT:
             # resamplers live on this context's device layer: they go first
             for r in list(getattr(self, "_resamplers", ())):
                 r.close()
+            for o in list(getattr(self, "_occupancy_maps", ())):
+                o.close()
             self._L.ndt2d_matcher_destroy(self._m)
             self._m = None
 
