@@ -129,6 +129,69 @@ int ndt2d_grid_stage_commit(ndt2d_handle h, size_t n_listed, double cell_size, d
 int ndt2d_build_grid(ndt2d_handle h, double ndt_resolution, double range_max,
                      const double * poses_xyt, const double * points_xy, const size_t * offsets,
                      size_t n_scans);
+/* ---- the fused small-map build and resident scans (csrc/build_small/) ----
+ *
+ * ndt2d_build_grid for a mapper-size map -- at most ndt2d_build_small_max_points() points
+ * (16,384) on a grid of fewer than 65,535 cells -- with everything order-dependent in ONE
+ * workgroup: the points are keyed, sorted by cell and walked in the reference's order in a
+ * single launch that leaves the list of touched cells where ndt2d_grid_stage_begin / _commit
+ * take it, so the build is three launches and one small read-back instead of a dozen stream
+ * operations, and no host arithmetic.  Arguments, semantics and the grid (bit for bit) are
+ * those of ndt2d_build_grid; the call returns when the grid is installed.  A map beyond the
+ * limits: NDT2D_ERR_INVALID, ndt2d_build_small_last_error(h) names them, and the context is
+ * left without a grid.
+ *
+ * The build lives beside the context and reaches it through this boundary only, so
+ *  - its eigenvalue form is its own: ndt2d_build_small_set_eigenvalue_form(h, "eigen" |
+ *    "closed") (ndt2d_set_eigenvalue_form does not reach it; the matcher layer sets both);
+ *  - its messages are read with ndt2d_build_small_last_error(h);
+ *  - the device memory it keeps for h (found by the handle) is freed by
+ *    ndt2d_build_small_release(h), to be called before ndt2d_destroy(h) by a caller that used
+ *    ndt2d_build_grid_small or the form setter on h (the matcher layer does).
+ * ndt2d_build_grid_small_fits: 1 if a map of n_points points with these scan poses is within
+ * the limits, 0 otherwise (or on a bad argument); it needs no context. */
+int ndt2d_build_grid_small(ndt2d_handle h, double ndt_resolution, double range_max,
+                           const double * poses_xyt, const double * points_xy, const size_t * offsets,
+                           size_t n_scans);
+int ndt2d_build_grid_small_fits(double ndt_resolution, double range_max, const double * poses_xyt,
+                                size_t n_scans, size_t n_points);
+size_t ndt2d_build_small_max_points(void);
+int ndt2d_build_small_set_eigenvalue_form(ndt2d_handle h, const char * form);
+const char * ndt2d_build_small_last_error(ndt2d_handle h);
+int ndt2d_build_small_release(ndt2d_handle h);
+
+/* Resident scans.  The mapper rebuilds its local NDT before every scan match from the last ten
+ * scans (src/ndt_mapper.cpp:508-509) and the loop-closure thread does so for every candidate
+ * (:634-635): nine of ten scans were on the device the cycle before, only the poses are new.
+ * A scan store keeps the robot-frame points of the scans appended to it in device memory
+ * (ids count from 0 in append order) and builds a map from any of them in any order through
+ * the fused build above: per build only the poses and the {offset, count} table of the named
+ * scans are uploaded.  It is an object of its own beside the context: it launches on the
+ * context's current stream, installs the grid into that context, and must be destroyed before
+ * ndt2d_destroy(h).
+ *   append   copies n_points points (zero is allowed); the caller's buffer is free on return.
+ *            A store that holds capacity_scans scans, or too few free points: NDT2D_ERR_INVALID,
+ *            nothing is stored.
+ *   reset    forgets every scan (ids start from 0 again); the installed grid stays.
+ *   build    ScanMatcherNDT::addScans of the scans ids[0..n_scans) in that order with the poses
+ *            poses_xyt[3k..3k+2]: the grid ndt2d_build_grid gives for the same scans and poses.
+ *            An unknown id, a non-finite pose, a degenerate extent or a map beyond the fused
+ *            build's limits: NDT2D_ERR_INVALID before anything is launched; the installed grid
+ *            is left as it was.
+ *   set_eigenvalue_form   "eigen" (default) or "closed", as ndt2d_set_eigenvalue_form. */
+typedef struct ndt2d_scanstore ndt2d_scanstore;
+int ndt2d_scanstore_create(ndt2d_handle h, size_t capacity_points, size_t capacity_scans,
+                           ndt2d_scanstore ** out);
+int ndt2d_scanstore_destroy(ndt2d_scanstore * store);
+const char * ndt2d_scanstore_last_error(ndt2d_scanstore * store);
+int ndt2d_scanstore_set_eigenvalue_form(ndt2d_scanstore * store, const char * form);
+int ndt2d_scanstore_append(ndt2d_scanstore * store, const double * points_xy, size_t n_points,
+                           size_t * id_out);
+int ndt2d_scanstore_count(ndt2d_scanstore * store, size_t * n_scans_out);
+int ndt2d_scanstore_reset(ndt2d_scanstore * store);
+int ndt2d_scanstore_build(ndt2d_scanstore * store, const size_t * ids, const double * poses_xyt,
+                          size_t n_scans, double ndt_resolution, double range_max);
+
 /* How ndt2d_build_grid forms the eigenvalues of Cell::compute (src/ndt_model.cpp:84-85,
  * Eigen::EigenSolver<Eigen::Matrix2d>): "eigen" (default) = Eigen 3.4.0's RealSchur /
  * EigenSolver transcribed operation by operation for a 2 x 2 input (csrc/ndt2d_eigen2.h: the
@@ -706,8 +769,25 @@ int ndt2d_matcher_add_scans(ndt2d_matcher * m, const double * poses_xyt,
                             const double * points_xy, const size_t * offsets, size_t n_scans);
 /* Where addScans builds the NDT: "host" (C++ on the host, then upload), "device"
  * (ndt2d_build_grid) or "auto" (device from 73,728 map points up: ~100 scans of 720 beams).  Both give
- * bit-identical grids. */
+ * bit-identical grids.  "fused" (opt-in): ndt2d_build_grid_small when the map is within its
+ * limits, otherwise exactly what "auto" does; after a fused build there is no host NDT, as
+ * after a device build (scoreScan / scorePoints take the device single-pose path). */
 int ndt2d_matcher_set_build_mode(ndt2d_matcher * m, const char * mode);
+/* Resident scans (ndt2d_scanstore) at matcher level.  store_scan keeps a scan's points on every
+ * device of the matcher and returns its id (ids count from 0); add_scans_by_id is addScans of the
+ * stored scans ids[0..n_scans) in that order with the poses given -- every device builds its own
+ * copy through the fused build, as add_scans replicates builds -- and gives the grid add_scans
+ * gives for the same scans and poses.  A map beyond the fused build's limits, an unknown id or a
+ * non-finite pose: NDT2D_ERR_INVALID, the NDT in place stays.  drop_scans forgets every stored
+ * scan.  The stores hold up to 262,144 points and 4,096 scans per device. */
+int ndt2d_matcher_store_scan(ndt2d_matcher * m, const double * points_xy, size_t n_points, size_t * id_out);
+int ndt2d_matcher_add_scans_by_id(ndt2d_matcher * m, const double * poses_xyt, const size_t * ids,
+                                  size_t n_scans);
+int ndt2d_matcher_drop_scans(ndt2d_matcher * m);
+/* How the NDT in place was built: "build/fused-small-map" (the fused build: mode "fused" within
+ * its limits, add_scans_by_id), "build/device" (ndt2d_build_grid), "build/host", or "" without
+ * an NDT. */
+const char * ndt2d_matcher_last_build(ndt2d_matcher * m);
 /* ndt2d_set_eigenvalue_form for the host build and every device of the matcher. */
 int ndt2d_matcher_set_eigenvalue_form(ndt2d_matcher * m, const char * form);
 /* ScanMatcherNDT::matchScan (src/scan_matcher_ndt.cpp:76-149).  *score_out =

@@ -92,6 +92,20 @@ SIGNATURES = {
     "ndt2d_set_grid": (C.c_int, [_vp, _dp, _u32, _u32, _d, _d, _d]),
     "ndt2d_set_grid_sparse": (C.c_int, [_vp, C.POINTER(C.c_uint32), _dp, _sz, _u32, _u32, _d, _d, _d]),
     "ndt2d_build_grid": (C.c_int, [_vp, _d, _d, _dp, _dp, _szp, _sz]),
+    "ndt2d_build_grid_small": (C.c_int, [_vp, _d, _d, _dp, _dp, _szp, _sz]),
+    "ndt2d_build_grid_small_fits": (C.c_int, [_d, _d, _dp, _sz, _sz]),
+    "ndt2d_build_small_max_points": (_sz, []),
+    "ndt2d_build_small_set_eigenvalue_form": (C.c_int, [_vp, C.c_char_p]),
+    "ndt2d_build_small_last_error": (C.c_char_p, [_vp]),
+    "ndt2d_build_small_release": (C.c_int, [_vp]),
+    "ndt2d_scanstore_set_eigenvalue_form": (C.c_int, [_vp, C.c_char_p]),
+    "ndt2d_scanstore_create": (C.c_int, [_vp, _sz, _sz, C.POINTER(_vp)]),
+    "ndt2d_scanstore_destroy": (C.c_int, [_vp]),
+    "ndt2d_scanstore_last_error": (C.c_char_p, [_vp]),
+    "ndt2d_scanstore_append": (C.c_int, [_vp, _dp, _sz, _szp]),
+    "ndt2d_scanstore_count": (C.c_int, [_vp, _szp]),
+    "ndt2d_scanstore_reset": (C.c_int, [_vp]),
+    "ndt2d_scanstore_build": (C.c_int, [_vp, _szp, _dp, _sz, _d, _d]),
     "ndt2d_set_eigenvalue_form": (C.c_int, [_vp, C.c_char_p]),
     "ndt2d_get_grid": (C.c_int, [_vp, _dp, _sz, C.POINTER(_u32), C.POINTER(_u32), _dp, _dp, _dp]),
     "ndt2d_clear_grid": (C.c_int, [_vp]),
@@ -189,6 +203,10 @@ SIGNATURES = {
     "ndt2d_matcher_add_scans": (C.c_int, [_vp, _dp, _dp, _szp, _sz]),
     "ndt2d_matcher_set_eigenvalue_form": (C.c_int, [_vp, C.c_char_p]),
     "ndt2d_matcher_set_build_mode": (C.c_int, [_vp, C.c_char_p]),
+    "ndt2d_matcher_store_scan": (C.c_int, [_vp, _dp, _sz, _szp]),
+    "ndt2d_matcher_add_scans_by_id": (C.c_int, [_vp, _dp, _szp, _sz]),
+    "ndt2d_matcher_drop_scans": (C.c_int, [_vp]),
+    "ndt2d_matcher_last_build": (C.c_char_p, [_vp]),
     "ndt2d_matcher_match_scan": (C.c_int, [_vp, _dp, _dp, _sz, _dp, _dp, _dp]),
     "ndt2d_matcher_match_scan_ex": (C.c_int, [_vp, _dp, _dp, _sz, _dp, _dp, _dp, _dp, _sz,
                                              _szp, C.POINTER(C.c_uint64)]),

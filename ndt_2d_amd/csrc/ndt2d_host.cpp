@@ -696,7 +696,12 @@ struct ndt2d_matcher
   std::unique_ptr<HostNdt> ndt;   // host copy; empty when the NDT was built on the device
   std::unique_ptr<HostNdt> spare; // the storage of the NDT that reset() dropped, for the next build
   bool have_ndt = false;          // `ndt_` is set (reference scan_matcher_ndt.hpp:102)
-  int build_mode = 0;             // 0 auto, 1 host, 2 device
+  int build_mode = 0;             // 0 auto, 1 host, 2 device, 3 fused
+  std::vector<ndt2d_scanstore *> stores;   // resident scans, one store per device (made by the first store_scan)
+  // the NDT in place came from the fused build: one pose at a time is scored on the device (fetching
+  // the grid back for the host path would cost the cycle more than the build saved)
+  bool ndt_fused = false;
+  const char * last_build = "";   // ndt2d_matcher_last_build
   int eigen_form = ndt2d::kEigenFormSchur;   // ndt2d_matcher_set_eigenvalue_form
 
   // What the first device holds as its beams: a scoring call that arrives with the same points
@@ -779,6 +784,11 @@ int mfail(ndt2d_matcher * m, int code, const std::string & msg)
 {
   if (m != nullptr) m->err = msg;
   return code;
+}
+
+const char * eigen_form_name(const ndt2d_matcher * m)
+{
+  return m->eigen_form == ndt2d::kEigenFormClosed ? "closed" : "eigen";
 }
 
 int dev_fail(ndt2d_matcher * m, int code, const char * what)
@@ -968,7 +978,7 @@ void note_match_scan(ndt2d_matcher * m, const double * scan_pose_xyt, bool prepa
 // scorePoints / scoreScan: one pose of a short scan, scored on the host (ndt2d_matcher_set_single_pose_path)?
 bool single_pose_on_host(const ndt2d_matcher * m, const double * points_xy, size_t n_points)
 {
-  return m->single_pose_host && m->have_ndt && n_points > 0 && points_xy != nullptr && m->laser_max_beams > 0 &&
+  return m->single_pose_host && !m->ndt_fused && m->have_ndt && n_points > 0 && points_xy != nullptr && m->laser_max_beams > 0 &&
          std::min(m->laser_max_beams, n_points) <= m->single_pose_max_beams;
 }
 
@@ -1650,6 +1660,8 @@ void destroy_matcher(ndt2d_matcher * m)
     if (sh.d_poses != nullptr) ndt2d_device_free(m->devs[r], sh.d_poses);
     if (sh.d_weights != nullptr) ndt2d_device_free(m->devs[r], sh.d_weights);
   }
+  for (ndt2d_scanstore * st : m->stores) (void)ndt2d_scanstore_destroy(st);   // (before their contexts)
+  for (ndt2d_handle h : m->devs) (void)ndt2d_build_small_release(h);
   if (m->exchange != nullptr) ndt2d::exchange_destroy(m->exchange);
   if (m->pinned != nullptr && !m->devs.empty()) ndt2d_host_free(m->dev, m->pinned);
   for (ndt2d_handle h : m->devs) ndt2d_destroy(h);
@@ -1866,6 +1878,8 @@ int ndt2d_matcher_add_scans(ndt2d_matcher * m, const double * poses_xyt,
   }
   discard_ahead(m);
   m->fetched.reset();
+  m->ndt_fused = false;
+  m->last_build = "";
   static const double no_points[2] = {0.0, 0.0};
   if (points_xy == nullptr) points_xy = no_points;
   static const size_t no_offsets[1] = {0};
@@ -1879,24 +1893,44 @@ int ndt2d_matcher_add_scans(ndt2d_matcher * m, const double * poses_xyt,
   // and a synchronisation plus 3.4 ns per point, the host build 40 us plus 4.4 ns per point).
   constexpr size_t kDeviceBuildFromPoints = 73728;   // ~100 scans of 720 beams (32,768 until round 5)
   const size_t n_map_points = n_scans > 0 ? offsets[n_scans] : 0;
+  // "fused" (opt-in): the one-workgroup build for maps within its limits, otherwise as "auto"
+  const bool fused = n_scans > 0 && m->build_mode == 3 &&
+                     ndt2d_build_grid_small_fits(m->resolution, m->range_max, poses_xyt, n_scans, n_map_points) != 0;
   const bool on_device =
-    n_scans > 0 && (m->build_mode == 2 || (m->build_mode == 0 && n_map_points >= kDeviceBuildFromPoints));
+    n_scans > 0 && (fused || m->build_mode == 2 ||
+                    ((m->build_mode == 0 || m->build_mode == 3) && n_map_points >= kDeviceBuildFromPoints));
   if (on_device)
   {
     m->ndt.reset();
     // (every device of a multi-device matcher builds its own copy: the builds run side by side)
     for (size_t r = 0; r < m->devs.size(); ++r)
     {
-      const int rc = ndt2d_build_grid(m->devs[r], m->resolution, m->range_max, poses_xyt, points_xy, offsets,
-                                      n_scans);
+      int rc;
+      if (fused)
+      {
+        // (the fused build keeps its eigenvalue form beside the context: handed over with every build)
+        rc = ndt2d_build_small_set_eigenvalue_form(m->devs[r], eigen_form_name(m));
+        if (rc == NDT2D_OK)
+        {
+          rc = ndt2d_build_grid_small(m->devs[r], m->resolution, m->range_max, poses_xyt, points_xy, offsets, n_scans);
+        }
+      }
+      else
+      {
+        rc = ndt2d_build_grid(m->devs[r], m->resolution, m->range_max, poses_xyt, points_xy, offsets, n_scans);
+      }
       if (rc != NDT2D_OK)
       {
-        const int frc = dev_fail_at(m, r, rc, "ndt2d_build_grid");
+        const int frc = fused ? mfail(m, rc, "ndt2d_build_grid_small (rank " + std::to_string(r) + "): " +
+                                               ndt2d_build_small_last_error(m->devs[r]))
+                              : dev_fail_at(m, r, rc, "ndt2d_build_grid");
         for (ndt2d_handle h : m->devs) ndt2d_clear_grid(h);
         return frc;
       }
     }
     m->have_ndt = true;
+    m->ndt_fused = fused;
+    m->last_build = fused ? "build/fused-small-map" : "build/device";
     return NDT2D_OK;
   }
   if (m->ndt) m->spare = std::move(m->ndt);
@@ -1936,6 +1970,7 @@ int ndt2d_matcher_add_scans(ndt2d_matcher * m, const double * poses_xyt,
     }
   }
   m->have_ndt = true;
+  m->last_build = "build/host";
   return NDT2D_OK;
   NDT2D_C_CATCH(m)
 }
@@ -1961,7 +1996,105 @@ int ndt2d_matcher_set_build_mode(ndt2d_matcher * m, const char * mode)
   if (std::strcmp(mode, "auto") == 0) m->build_mode = 0;
   else if (std::strcmp(mode, "host") == 0) m->build_mode = 1;
   else if (std::strcmp(mode, "device") == 0) m->build_mode = 2;
+  else if (std::strcmp(mode, "fused") == 0) m->build_mode = 3;
   else return mfail(m, NDT2D_ERR_INVALID, "set_build_mode: unknown mode");
+  return NDT2D_OK;
+  NDT2D_C_CATCH(m)
+}
+
+// Resident scans: what one device's store holds (the mapper's rolling window is ten scans, a
+// loop closure's candidates a few dozen; 4 MB of points per device).
+static constexpr size_t kStorePoints = 262144, kStoreScans = 4096;
+
+int ndt2d_matcher_store_scan(ndt2d_matcher * m, const double * points_xy, size_t n_points, size_t * id_out)
+{
+  NDT2D_C_TRY
+  if (m == nullptr) return NDT2D_ERR_INVALID;
+  if (n_points > 0 && points_xy == nullptr) return mfail(m, NDT2D_ERR_INVALID, "store_scan: null points");
+  while (m->stores.size() < m->devs.size())
+  {
+    const size_t r = m->stores.size();
+    ndt2d_scanstore * st = nullptr;
+    const int rc = ndt2d_scanstore_create(m->devs[r], kStorePoints, kStoreScans, &st);
+    if (rc != NDT2D_OK) return dev_fail_at(m, r, rc, "ndt2d_scanstore_create");
+    m->stores.push_back(st);
+  }
+  size_t id = 0;
+  for (size_t r = 0; r < m->stores.size(); ++r)
+  {
+    size_t id_r = 0;
+    const int rc = ndt2d_scanstore_append(m->stores[r], points_xy, n_points, &id_r);
+    if (rc != NDT2D_OK)
+    {
+      const std::string why = ndt2d_scanstore_last_error(m->stores[r]);
+      // (a full store refuses on the first device, before any holds the scan; a copy that failed on a
+      // later one would leave the stores with different ids: they all start over)
+      if (r > 0) for (ndt2d_scanstore * st : m->stores) (void)ndt2d_scanstore_reset(st);
+      return mfail(m, rc, "store_scan (rank " + std::to_string(r) + "): " + why +
+                            (r > 0 ? "; every stored scan was dropped" : ""));
+    }
+    if (r == 0) id = id_r;
+  }
+  if (id_out != nullptr) *id_out = id;
+  return NDT2D_OK;
+  NDT2D_C_CATCH(m)
+}
+
+int ndt2d_matcher_add_scans_by_id(ndt2d_matcher * m, const double * poses_xyt, const size_t * ids, size_t n_scans)
+{
+  NDT2D_C_TRY
+  if (m == nullptr) return NDT2D_ERR_INVALID;
+  if (n_scans == 0 || poses_xyt == nullptr || ids == nullptr)
+  {
+    return mfail(m, NDT2D_ERR_INVALID, "add_scans_by_id: null input");
+  }
+  for (size_t k = 0; k < 3 * n_scans; ++k)
+  {
+    if (!std::isfinite(poses_xyt[k])) return mfail(m, NDT2D_ERR_INVALID, "add_scans_by_id: a scan pose is not finite");
+  }
+  if (m->stores.size() != m->devs.size()) return mfail(m, NDT2D_ERR_INVALID, "add_scans_by_id: unknown scan id (no scan is stored)");
+  discard_ahead(m);
+  // (every device builds its own copy from its own store, as add_scans replicates builds)
+  for (size_t r = 0; r < m->devs.size(); ++r)
+  {
+    int rc = ndt2d_scanstore_set_eigenvalue_form(m->stores[r], eigen_form_name(m));
+    if (rc == NDT2D_OK) rc = ndt2d_scanstore_build(m->stores[r], ids, poses_xyt, n_scans, m->resolution, m->range_max);
+    if (rc != NDT2D_OK)
+    {
+      const int frc = mfail(m, rc, "add_scans_by_id (rank " + std::to_string(r) + "): " +
+                                     ndt2d_scanstore_last_error(m->stores[r]));
+      // a refusal comes from the first store before anything is launched: the NDT in place stays
+      if (r == 0 && rc == NDT2D_ERR_INVALID) return frc;
+      m->ndt.reset();
+      m->fetched.reset();
+      m->have_ndt = false;
+      m->ndt_fused = false;
+      m->last_build = "";
+      for (ndt2d_handle h : m->devs) ndt2d_clear_grid(h);
+      return frc;
+    }
+    if (r == 0)
+    {
+      // the grid is replaced from here on: no host NDT, as after a device build
+      m->ndt.reset();
+      m->fetched.reset();
+      m->have_ndt = false;
+    }
+  }
+  m->have_ndt = true;
+  m->ndt_fused = true;
+  m->last_build = "build/fused-small-map";
+  return NDT2D_OK;
+  NDT2D_C_CATCH(m)
+}
+
+const char * ndt2d_matcher_last_build(ndt2d_matcher * m) { return (m != nullptr && m->have_ndt) ? m->last_build : ""; }
+
+int ndt2d_matcher_drop_scans(ndt2d_matcher * m)
+{
+  NDT2D_C_TRY
+  if (m == nullptr) return NDT2D_ERR_INVALID;
+  for (ndt2d_scanstore * st : m->stores) (void)ndt2d_scanstore_reset(st);
   return NDT2D_OK;
   NDT2D_C_CATCH(m)
 }
@@ -1974,6 +2107,7 @@ int ndt2d_matcher_reset(ndt2d_matcher * m)
   if (m->ndt) m->spare = std::move(m->ndt);   // `ndt_.reset()`; the storage serves the next addScans
   m->fetched.reset();
   m->have_ndt = false;
+  m->ndt_fused = false;
   int rc = NDT2D_OK;
   for (ndt2d_handle h : m->devs)
   {

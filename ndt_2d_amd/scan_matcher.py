@@ -349,8 +349,36 @@ class ScanMatcherNDT:
                     "set_single_pose_path")
 
     def set_build_mode(self, mode):
-        """Where addScans builds the NDT: "host", "device" or "auto" (bit-identical grids)."""
+        """Where addScans builds the NDT: "host", "device" or "auto" (bit-identical grids), or
+        "fused": the one-workgroup device build for maps of up to 16,384 points on fewer than
+        65,535 cells, otherwise what "auto" does."""
         self._check(self._L.ndt2d_matcher_set_build_mode(self._m, mode.encode()), "set_build_mode")
+
+    def storeScan(self, points):
+        """Keep a scan's robot-frame points on the device(s); returns its id (from 0, in order)."""
+        pts = _f64(points, (-1, 2))
+        out = C.c_size_t(0)
+        self._check(self._L.ndt2d_matcher_store_scan(self._m, dptr(pts), len(pts), C.byref(out)), "storeScan")
+        return out.value
+
+    def addScansById(self, poses, ids):
+        """addScans of the stored scans `ids`, in that order, with `poses[k]` for ids[k]: only the
+        poses and the id table travel.  Same grid as addScans of those scans and poses."""
+        ps = _f64(poses, (-1, 3))
+        idx = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        if len(ps) != len(idx):
+            raise ValueError("addScansById: %d poses for %d ids" % (len(ps), len(idx)))
+        self._check(self._L.ndt2d_matcher_add_scans_by_id(
+            self._m, dptr(ps), idx.ctypes.data_as(C.POINTER(C.c_size_t)), len(idx)), "addScansById")
+
+    def last_build(self):
+        """How the NDT in place was built: "build/fused-small-map", "build/device", "build/host" or ""."""
+        v = self._L.ndt2d_matcher_last_build(self._m)
+        return v.decode() if v else ""
+
+    def dropScans(self):
+        """Forget every stored scan; ids start from 0 again."""
+        self._check(self._L.ndt2d_matcher_drop_scans(self._m), "dropScans")
 
     def set_eigenvalue_form(self, form):
         """How Cell::compute's eigenvalues (src/ndt_model.cpp:84-85) are formed: "eigen" (default:
