@@ -192,6 +192,51 @@ int ndt2d_scanstore_reset(ndt2d_scanstore * store);
 int ndt2d_scanstore_build(ndt2d_scanstore * store, const size_t * ids, const double * poses_xyt,
                           size_t n_scans, double ndt_resolution, double range_max);
 
+/* ---- batched loop-closure match (csrc/closure/) ----
+ *
+ * The loop-closure thread matches every new scan against up to global_search_limit_ candidate
+ * maps, each built from one or two old scans: reset(), addScans(begin, end), matchScan(scan)
+ * per candidate (src/ndt_mapper.cpp:619-671).  ndt2d_closure_match does that for K candidates
+ * in one build launch (a workgroup of the fused small-map build per candidate map, which also
+ * writes the packed records and the cell -> record table the search reads), one search launch
+ * over (candidate map x lattice) and one reduction, and reads all K records back in one copy.
+ * An object of its own beside the context: it reads its scans from `store` (a store of the same
+ * context), launches on the context's current stream, installs nothing into the context, and
+ * must be destroyed before the store and before ndt2d_destroy(h).
+ *
+ *   create   max_candidates (1 .. 4,096): candidate maps of one launch; a call with more is
+ *            processed in chunks of that many inside the call.
+ *   match    candidate k is built from the stored scans ids[cand_offsets[k] .. cand_offsets[k + 1])
+ *            in that order with the poses poses_xyt[3 j ..] (flat, parallel to ids): the grid
+ *            ndt2d_scanstore_build gives for them with ndt_resolution / range_max.  The search
+ *            is the one ndt2d_set_search_beams + ndt2d_match_launch(0, n_th) would run on that
+ *            grid -- the same arguments: subsampled robot-frame beams, the scan pose, the
+ *            visited offsets, host-libm cos / sin per theta step -- and every candidate starts
+ *            from the same pose.  records_out[K][NDT2D_MATCH_RECORD_DOUBLES] receives
+ *            {best_score, best_index (-1: none; + 0.5: near tie), acc[10]} per candidate,
+ *            all_scores (optional) [K][n_th * n_lin * n_lin] every lattice candidate's raw score.
+ *            A raw score has the bits of the small-lattice search's (the mapping every
+ *            loop-closure-size lattice takes: ndt2d_set_variant); two calls give the same bits.
+ *            A candidate with an unknown id, a non-finite pose, no scans, a degenerate extent
+ *            or a map beyond the fused build's limits (ndt2d_build_grid_small_fits):
+ *            NDT2D_ERR_INVALID before anything is launched, the message names the candidate.
+ *            A candidate whose scans hold no points is a map without cells: every score 0.
+ *   set_timing / last_ms   HIP events around the build and the search launch of the last
+ *            (chunk of a) match, off by default. */
+typedef struct ndt2d_closure ndt2d_closure;
+int ndt2d_closure_create(ndt2d_handle h, ndt2d_scanstore * store, size_t max_candidates,
+                         ndt2d_closure ** out);
+int ndt2d_closure_destroy(ndt2d_closure * closure);
+const char * ndt2d_closure_last_error(ndt2d_closure * closure);
+int ndt2d_closure_match(ndt2d_closure * closure, size_t n_candidates, const size_t * cand_offsets,
+                        const size_t * ids, const double * poses_xyt, double ndt_resolution,
+                        double range_max, const double * beams_xy, size_t n_beams, double pose_x,
+                        double pose_y, const double * dth, const double * cos_th,
+                        const double * sin_th, size_t n_th, const double * dlin, size_t n_lin,
+                        double * records_out, double * all_scores);
+int ndt2d_closure_set_timing(ndt2d_closure * closure, int enabled);
+int ndt2d_closure_last_ms(ndt2d_closure * closure, float * build_ms, float * search_ms);
+
 /* How ndt2d_build_grid forms the eigenvalues of Cell::compute (src/ndt_model.cpp:84-85,
  * Eigen::EigenSolver<Eigen::Matrix2d>): "eigen" (default) = Eigen 3.4.0's RealSchur /
  * EigenSolver transcribed operation by operation for a 2 x 2 input (csrc/ndt2d_eigen2.h: the
@@ -806,6 +851,38 @@ int ndt2d_matcher_match_scan_ex(ndt2d_matcher * m, const double * scan_pose_xyt,
                                 double * score_out, double * all_scores,
                                 size_t all_scores_cap, size_t * n_candidates_out,
                                 uint64_t * best_index_out);
+/* The loop-closure thread's inner loop in one call (ndt2d_closure_match with the matcher's own
+ * parameters and stored scans, on the first device).  For candidate k of K the outputs are
+ * what this sequence gives on the same matcher:
+ *     ndt2d_matcher_reset; ndt2d_matcher_add_scans_by_id(poses_k, ids_k, n_k);
+ *     ndt2d_matcher_match_scan_ex(scan_pose, points, ...)
+ * with ids_k / poses_k = ids / poses_xyt[cand_offsets[k] .. cand_offsets[k + 1]) (flat arrays,
+ * poses three doubles an entry).  Every candidate starts from the same scan_pose.
+ *   poses_out[3 k ..]        written only when a lattice candidate of k scores below 0 (as
+ *                            match_scan's pose_inout): the caller pre-initialises it;
+ *   covariances_out[9 k ..]  row-major;  scores_out[k]  match_scan's return value;
+ *   best_index_out[k]        (optional) the winner's flat index, NDT2D_NO_INDEX if none;
+ *   all_scores               (optional) [K][lattice] raw scores, all_scores_cap doubles: only
+ *                            filled when it holds them all;  *n_lattice_out (optional) the
+ *                            lattice size n_th * n_lin * n_lin.
+ * A candidate map whose record comes back marked as a near tie is settled by running the three
+ * sequential calls for that candidate alone -- the existing adjudication, counted by
+ * ndt2d_matcher_adjudication_stats as any other.  A search launched ahead by score_scan is
+ * waited out and dropped first.  On return the matcher holds no NDT (has_ndt == 0), as after
+ * the reset() every iteration of the reference's loop begins with.  Refusals are those of
+ * ndt2d_closure_match (NDT2D_ERR_INVALID, the message names the candidate, nothing launched,
+ * the NDT in place stays). */
+int ndt2d_matcher_match_candidates(ndt2d_matcher * m, const double * scan_pose_xyt,
+                                   const double * points_xy, size_t n_points,
+                                   const size_t * cand_offsets, const size_t * ids,
+                                   const double * poses_xyt, size_t n_candidates,
+                                   double * poses_out, double * covariances_out,
+                                   double * scores_out, uint64_t * best_index_out,
+                                   double * all_scores, size_t all_scores_cap,
+                                   size_t * n_lattice_out);
+/* The batched call's closure object (made by the first match_candidates; NULL before), for
+ * ndt2d_closure_set_timing / _last_ms. */
+ndt2d_closure * ndt2d_matcher_closure(ndt2d_matcher * m);
 /* The two halves of matchScan, for sharded (multi-GPU) searches:
  * prepare_search subsamples the scan (:95-96,110), builds the offset and
  * cos/sin tables (:103-107,117,119) and uploads them -- after it,

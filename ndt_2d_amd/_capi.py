@@ -106,6 +106,13 @@ SIGNATURES = {
     "ndt2d_scanstore_count": (C.c_int, [_vp, _szp]),
     "ndt2d_scanstore_reset": (C.c_int, [_vp]),
     "ndt2d_scanstore_build": (C.c_int, [_vp, _szp, _dp, _sz, _d, _d]),
+    "ndt2d_closure_create": (C.c_int, [_vp, _vp, _sz, C.POINTER(_vp)]),
+    "ndt2d_closure_destroy": (C.c_int, [_vp]),
+    "ndt2d_closure_last_error": (C.c_char_p, [_vp]),
+    "ndt2d_closure_match": (C.c_int, [_vp, _sz, _szp, _szp, _dp, _d, _d, _dp, _sz, _d, _d, _dp, _dp, _dp, _sz,
+                                     _dp, _sz, _dp, _dp]),
+    "ndt2d_closure_set_timing": (C.c_int, [_vp, C.c_int]),
+    "ndt2d_closure_last_ms": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "ndt2d_set_eigenvalue_form": (C.c_int, [_vp, C.c_char_p]),
     "ndt2d_get_grid": (C.c_int, [_vp, _dp, _sz, C.POINTER(_u32), C.POINTER(_u32), _dp, _dp, _dp]),
     "ndt2d_clear_grid": (C.c_int, [_vp]),
@@ -210,6 +217,9 @@ SIGNATURES = {
     "ndt2d_matcher_match_scan": (C.c_int, [_vp, _dp, _dp, _sz, _dp, _dp, _dp]),
     "ndt2d_matcher_match_scan_ex": (C.c_int, [_vp, _dp, _dp, _sz, _dp, _dp, _dp, _dp, _sz,
                                              _szp, C.POINTER(C.c_uint64)]),
+    "ndt2d_matcher_match_candidates": (C.c_int, [_vp, _dp, _dp, _sz, _szp, _szp, _dp, _sz, _dp, _dp, _dp,
+                                                C.POINTER(C.c_uint64), _dp, _sz, _szp]),
+    "ndt2d_matcher_closure": (_vp, [_vp]),
     "ndt2d_matcher_match_laser_scan": (C.c_int, [_vp, _dp, C.POINTER(C.c_float), _sz,
                                                  C.POINTER(LaserScan), _dp, _dp, _dp, _szp]),
     "ndt2d_matcher_prepare_search": (C.c_int, [_vp, _dp, _dp, _sz, _szp, _szp, _szp]),

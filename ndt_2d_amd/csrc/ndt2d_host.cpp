@@ -698,6 +698,8 @@ struct ndt2d_matcher
   bool have_ndt = false;          // `ndt_` is set (reference scan_matcher_ndt.hpp:102)
   int build_mode = 0;             // 0 auto, 1 host, 2 device, 3 fused
   std::vector<ndt2d_scanstore *> stores;   // resident scans, one store per device (made by the first store_scan)
+  ndt2d_closure * closure = nullptr;       // batched loop-closure match on the first device (made by the first match_candidates)
+  std::vector<double> closure_records;     // its records, [K][NDT2D_MATCH_RECORD_DOUBLES]
   // the NDT in place came from the fused build: one pose at a time is scored on the device (fetching
   // the grid back for the host path would cost the cycle more than the build saved)
   bool ndt_fused = false;
@@ -1660,6 +1662,7 @@ void destroy_matcher(ndt2d_matcher * m)
     if (sh.d_poses != nullptr) ndt2d_device_free(m->devs[r], sh.d_poses);
     if (sh.d_weights != nullptr) ndt2d_device_free(m->devs[r], sh.d_weights);
   }
+  if (m->closure != nullptr) (void)ndt2d_closure_destroy(m->closure);         // (before its store)
   for (ndt2d_scanstore * st : m->stores) (void)ndt2d_scanstore_destroy(st);   // (before their contexts)
   for (ndt2d_handle h : m->devs) (void)ndt2d_build_small_release(h);
   if (m->exchange != nullptr) ndt2d::exchange_destroy(m->exchange);
@@ -2264,6 +2267,110 @@ int ndt2d_matcher_match_scan(ndt2d_matcher * m, const double * scan_pose_xyt,
                                      covariance_out, score_out, nullptr, 0, nullptr, nullptr);
   NDT2D_C_CATCH(m)
 }
+
+// Candidates the batched match launches at a time: the plugin's global_search_limit_ is a handful.
+static constexpr size_t kClosureSlots = 16;
+
+int ndt2d_matcher_match_candidates(ndt2d_matcher * m, const double * scan_pose_xyt, const double * points_xy,
+                                   size_t n_points, const size_t * cand_offsets, const size_t * ids,
+                                   const double * poses_xyt, size_t n_candidates, double * poses_out,
+                                   double * covariances_out, double * scores_out, uint64_t * best_index_out,
+                                   double * all_scores, size_t all_scores_cap, size_t * n_lattice_out)
+{
+  NDT2D_C_TRY
+  if (m == nullptr) return NDT2D_ERR_INVALID;
+  if (scan_pose_xyt == nullptr || scores_out == nullptr || (n_points > 0 && points_xy == nullptr) ||
+      (n_candidates > 0 && (cand_offsets == nullptr || ids == nullptr || poses_xyt == nullptr)))
+  {
+    return mfail(m, NDT2D_ERR_INVALID, "match_candidates: null input");
+  }
+  const size_t n_th = m->search.dth.size(), n_lin = m->search.dlin.size();
+  const size_t n_lattice = n_th * n_lin * n_lin;
+  if (n_lattice_out != nullptr) *n_lattice_out = n_lattice;
+  if (n_candidates == 0) return NDT2D_OK;
+  if (n_candidates > (1u << 20)) return mfail(m, NDT2D_ERR_INVALID, "match_candidates: too many candidates");
+  if (m->stores.size() != m->devs.size())
+  {
+    return mfail(m, NDT2D_ERR_INVALID, "match_candidates: candidate 0: unknown scan id (no scan is stored)");
+  }
+  discard_ahead(m);   // a search launched ahead by scoreScan is waited out and dropped
+  if (m->closure == nullptr)
+  {
+    const int rc = ndt2d_closure_create(m->dev, m->stores[0], kClosureSlots, &m->closure);
+    if (rc != NDT2D_OK) return dev_fail(m, rc, "ndt2d_closure_create");
+  }
+  double * scores_ptr = (all_scores != nullptr && all_scores_cap / n_candidates >= n_lattice && n_lattice > 0) ? all_scores : nullptr;
+
+  // the scan as matchScan takes it: subsampled beams (:95-96,110), cos / sin per theta step (:106-107)
+  subsample_into(m->beams.next, points_xy, n_points, m->laser_max_beams);
+  const size_t use = m->beams.next.size() / 2;
+  if (!m->beams.holds(m->beams.next)) m->beams.adopt(m->beams.next);   // (the host copy; the context's beams stay)
+  m->search.n_use = use;
+  m->search.ready = false;   // no search is prepared on the context
+  m->search.cos_th.resize(n_th);
+  m->search.sin_th.resize(n_th);
+  for (size_t i = 0; i < n_th; ++i)
+  {
+    ndt2d_cos_sin(scan_pose_xyt[2] + m->search.dth[i], &m->search.cos_th[i], &m->search.sin_th[i]);
+  }
+  m->closure_records.assign(n_candidates * NDT2D_MATCH_RECORD_DOUBLES, 0.0);
+  double * records = m->closure_records.data();
+  std::vector<char> sequential(n_candidates, 0);
+  if (use == 0 || n_lattice == 0)
+  {
+    // No points: every candidate scores -0.0 and none is < 0; no candidates: the loops do not run.
+    // What the sequential calls do with that is theirs to say.
+    std::fill(sequential.begin(), sequential.end(), 1);
+  }
+  else
+  {
+    int rc = ndt2d_scanstore_set_eigenvalue_form(m->stores[0], eigen_form_name(m));
+    if (rc == NDT2D_OK)
+    {
+      rc = ndt2d_closure_match(m->closure, n_candidates, cand_offsets, ids, poses_xyt, m->resolution, m->range_max,
+                               m->beams.host.data(), use, scan_pose_xyt[0], scan_pose_xyt[1], m->search.dth.data(),
+                               m->search.cos_th.data(), m->search.sin_th.data(), n_th, m->search.dlin.data(), n_lin,
+                               records, scores_ptr);
+    }
+    if (rc != NDT2D_OK) return mfail(m, rc, std::string("match_candidates: ") + ndt2d_closure_last_error(m->closure));
+    // a marked winner (index + 0.5): the candidate alone through the sequential calls, whose
+    // adjudication settles it
+    for (size_t k = 0; k < n_candidates; ++k)
+    {
+      const double bi = records[k * NDT2D_MATCH_RECORD_DOUBLES + 1];
+      sequential[k] = (bi >= 0.0 && bi != std::floor(bi)) ? 1 : 0;
+    }
+  }
+  int rc = NDT2D_OK;
+  for (size_t k = 0; k < n_candidates && rc == NDT2D_OK; ++k)
+  {
+    double * pose_k = poses_out != nullptr ? poses_out + 3 * k : nullptr;
+    double * cov_k = covariances_out != nullptr ? covariances_out + 9 * k : nullptr;
+    if (sequential[k])
+    {
+      const size_t j0 = cand_offsets[k], n_k = cand_offsets[k + 1] - cand_offsets[k];
+      rc = ndt2d_matcher_reset(m);
+      if (rc == NDT2D_OK) rc = ndt2d_matcher_add_scans_by_id(m, poses_xyt + 3 * j0, ids + j0, n_k);
+      if (rc == NDT2D_OK)
+      {
+        rc = ndt2d_matcher_match_scan_ex(m, scan_pose_xyt, points_xy, n_points, pose_k, cov_k, scores_out + k,
+                                         scores_ptr != nullptr ? scores_ptr + k * n_lattice : nullptr, n_lattice, nullptr,
+                                         best_index_out != nullptr ? best_index_out + k : nullptr);
+      }
+      if (rc != NDT2D_OK) m->err = "match_candidates: candidate " + std::to_string(k) + ": " + m->err;
+      continue;
+    }
+    const double * rec = records + k * NDT2D_MATCH_RECORD_DOUBLES;
+    if (best_index_out != nullptr) best_index_out[k] = rec[1] < 0.0 ? NDT2D_NO_INDEX : static_cast<uint64_t>(rec[1]);
+    rc = ndt2d_matcher_finish_match(m, rec, pose_k, cov_k, scores_out + k);
+  }
+  // `global_scan_matcher_->reset()` (src/ndt_mapper.cpp:634): no NDT is left in place
+  const int rrc = ndt2d_matcher_reset(m);
+  return rc != NDT2D_OK ? rc : rrc;
+  NDT2D_C_CATCH(m)
+}
+
+ndt2d_closure * ndt2d_matcher_closure(ndt2d_matcher * m) { return m != nullptr ? m->closure : nullptr; }
 
 int ndt2d_matcher_match_laser_scan(ndt2d_matcher * m, const double * scan_pose_xyt,
                                    const float * ranges, size_t n_ranges,

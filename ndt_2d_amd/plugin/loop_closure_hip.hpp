@@ -1,0 +1,159 @@
+// The loop-closure thread's inner loop (reference src/ndt_mapper.cpp:619-671) on the batched
+// match of libndt2d_hip.so: all candidate maps of a new scan in one call
+// (ndt2d_matcher_match_candidates, include/ndt2d_hip.h) instead of reset() / addScans() /
+// matchScan() per candidate.
+//
+// The node stores every scan on the matcher as it appends it to the graph (storeScan: the id is
+// the scan's index in graph_->scans) and then, per new scan, hands closeLoops() the candidates
+// findNearest returned.  The walk is the reference's: candidates in order, a candidate whose
+// scan is empty is skipped and does not count, every other one counts against
+// global_search_limit_, accepted when isfinite(score) && score < typical_matcher_response_.
+// An accept corrects the scan's pose, which every later candidate starts from: the remaining
+// candidates are matched again, in one batch, from the corrected pose.
+//
+// Plain arrays over the C-ABI, as the other mirrors in this directory: nothing of ROS or Eigen.
+#ifndef NDT_2D_HIP__LOOP_CLOSURE_HIP_HPP_
+#define NDT_2D_HIP__LOOP_CLOSURE_HIP_HPP_
+
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "ndt2d_hip.h"
+
+namespace ndt_2d_hip
+{
+
+// One accepted loop closure: what makeConstraint(candidate, scan, covariance) is given (:658).
+struct LoopClosure
+{
+  std::size_t candidate;     // index of the candidate scan in the graph
+  double score;
+  double correction[3];      // matchScan's pose output (dx, dy, dth)
+  double pose[3];            // the scan's pose after the correction (:652-655)
+  double covariance[9];      // row-major
+};
+
+class LoopClosureHip
+{
+public:
+  explicit LoopClosureHip(ndt2d_matcher * matcher) : m_(matcher) {}
+
+  // A scan appended to the graph: its points go to the device once.  Returns false on failure.
+  // The id the matcher hands out is the scan's index as long as every graph scan is stored in order.
+  bool storeScan(const double * points_xy, std::size_t n_points, std::size_t * id_out = nullptr)
+  {
+    std::size_t id = 0;
+    if (!ok(ndt2d_matcher_store_scan(m_, points_xy, n_points, &id))) return false;
+    if (id >= sizes_.size()) sizes_.resize(id + 1, 0);
+    sizes_[id] = n_points;
+    if (id_out != nullptr) *id_out = id;
+    return true;
+  }
+
+  // [begin_idx, end_idx) of src/ndt_mapper.cpp:628-631, quirk included: the candidate
+  // i == rolling yields only scan i - 1.
+  static void window(std::size_t i, std::size_t rolling, std::size_t * begin_idx, std::size_t * end_idx)
+  {
+    *begin_idx = (i > 0) ? i - 1 : i;
+    *end_idx = (i < rolling) ? i + 1 : i;
+  }
+
+  // The walk of :619-671 for one new scan.  scan_pose_inout[3]: scan->getPose() / setPose();
+  // candidates: findNearest's result; graph_poses_xyt[3 i ..]: the pose of graph scan i;
+  // limit: global_search_limit_ (0: the reference's unsigned counter never reaches zero -- all).
+  // Appends to closures_out; false when a device call fails (last_error()).
+  bool closeLoops(double * scan_pose_inout, const double * points_xy, std::size_t n_points,
+                  const std::vector<std::size_t> & candidates, const double * graph_poses_xyt,
+                  std::size_t rolling, double typical_response, std::size_t limit,
+                  std::vector<LoopClosure> & closures_out)
+  {
+    std::vector<std::size_t> todo;
+    for (std::size_t i : candidates)
+    {
+      if (i < sizes_.size() && sizes_[i] == 0) continue;   // `if (candidate->getPoints().empty()) continue;`
+      todo.push_back(i);
+      if (limit != 0 && todo.size() == limit) break;      // `if (--num_scans_to_check == 0) break;`
+    }
+    while (!todo.empty())
+    {
+      offsets_.assign(1, 0);
+      ids_.clear();
+      poses_.clear();
+      for (std::size_t i : todo)
+      {
+        std::size_t b = 0, e = 0;
+        window(i, rolling, &b, &e);
+        for (std::size_t j = b; j < e; ++j)
+        {
+          ids_.push_back(j);
+          poses_.insert(poses_.end(), graph_poses_xyt + 3 * j, graph_poses_xyt + 3 * j + 3);
+        }
+        offsets_.push_back(ids_.size());
+      }
+      const std::size_t K = todo.size();
+      corrections_.assign(3 * K, 0.0);
+      covariances_.assign(9 * K, 0.0);
+      scores_.assign(K, 0.0);
+      if (!ok(ndt2d_matcher_match_candidates(m_, scan_pose_inout, points_xy, n_points, offsets_.data(), ids_.data(),
+                                             poses_.data(), K, corrections_.data(), covariances_.data(),
+                                             scores_.data(), nullptr, nullptr, 0, nullptr)))
+      {
+        return false;
+      }
+      std::size_t accepted = K;
+      for (std::size_t k = 0; k < K; ++k)
+      {
+        if (std::isfinite(scores_[k]) && scores_[k] < typical_response)
+        {
+          accepted = k;
+          break;
+        }
+      }
+      if (accepted == K) break;
+      LoopClosure c;
+      c.candidate = todo[accepted];
+      c.score = scores_[accepted];
+      for (int d = 0; d < 3; ++d)
+      {
+        c.correction[d] = corrections_[3 * accepted + d];
+        // correction.x += scan->getPose().x; ... scan->setPose(correction);
+        scan_pose_inout[d] = c.correction[d] + scan_pose_inout[d];
+        c.pose[d] = scan_pose_inout[d];
+      }
+      for (int d = 0; d < 9; ++d) c.covariance[d] = covariances_[9 * accepted + d];
+      closures_out.push_back(c);
+      todo.erase(todo.begin(), todo.begin() + static_cast<std::ptrdiff_t>(accepted) + 1);
+    }
+    return true;
+  }
+
+  // Forget every stored scan (the graph was reloaded): ids start from 0 again.
+  bool dropScans()
+  {
+    sizes_.clear();
+    return ok(ndt2d_matcher_drop_scans(m_));
+  }
+
+  const std::string & last_error() const { return error_; }
+
+private:
+  bool ok(int rc)
+  {
+    if (rc == NDT2D_OK) return true;
+    error_ = std::string("ndt2d error ") + std::to_string(rc) + ": " + ndt2d_matcher_last_error(m_);
+    return false;
+  }
+
+  ndt2d_matcher * m_;
+  std::vector<std::size_t> sizes_;   // point count of stored scan `id`
+  std::vector<std::size_t> offsets_, ids_;
+  std::vector<double> poses_, corrections_, covariances_, scores_;
+  std::string error_;
+};
+
+}  // namespace ndt_2d_hip
+
+#endif  // NDT_2D_HIP__LOOP_CLOSURE_HIP_HPP_

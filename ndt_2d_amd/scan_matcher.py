@@ -371,6 +371,60 @@ class ScanMatcherNDT:
         self._check(self._L.ndt2d_matcher_add_scans_by_id(
             self._m, dptr(ps), idx.ctypes.data_as(C.POINTER(C.c_size_t)), len(idx)), "addScansById")
 
+    def matchCandidates(self, scan_pose, points, candidates, want_scores=False):
+        """The loop-closure thread's inner loop in one call: `candidates` is a list of candidate
+        maps, each a list of (stored scan id, pose_xyt).  Returns one dict per candidate, the
+        dict matchScan returns after reset() / addScansById(candidate): every candidate starts
+        from the same scan_pose, `pose` is (0, 0, 0) unless a lattice candidate scores below 0.
+        One build launch, one search launch and one read-back for all of them; the matcher holds
+        no NDT afterwards."""
+        sp = _f64(scan_pose, (3,))
+        pts = _f64(points, (-1, 2))
+        K = len(candidates)
+        offsets = np.zeros(K + 1, dtype=np.uint64)
+        offsets[1:] = np.cumsum([len(c) for c in candidates]) if K else []
+        flat = [entry for c in candidates for entry in c]
+        ids = np.ascontiguousarray([e[0] for e in flat], dtype=np.uint64).reshape(-1)
+        poses = _f64([e[1] for e in flat], (-1, 3)) if flat else np.zeros((0, 3))
+        poses_out = np.zeros((K, 3))
+        covs = np.full((K, 9), np.nan)
+        scores = np.zeros(K)
+        best = np.zeros(K, dtype=np.uint64)
+        n_lat = C.c_size_t(0)
+        all_scores, as_ptr, cap = None, None, 0
+        if want_scores:
+            p = self.params
+            n_th = len(search_offsets(p["search_angular_size"], p["search_angular_resolution"]))
+            n_lin = len(search_offsets(p["search_linear_size"], p["search_linear_resolution"]))
+            all_scores = np.zeros((K, n_th * n_lin * n_lin), dtype=np.float64)
+            as_ptr, cap = dptr(all_scores), all_scores.size
+        self._check(self._L.ndt2d_matcher_match_candidates(
+            self._m, dptr(sp), dptr(pts), len(pts), offsets.ctypes.data_as(C.POINTER(C.c_size_t)),
+            ids.ctypes.data_as(C.POINTER(C.c_size_t)), dptr(poses), K, dptr(poses_out), dptr(covs), dptr(scores),
+            best.ctypes.data_as(C.POINTER(C.c_uint64)), as_ptr, cap, C.byref(n_lat)), "matchCandidates")
+        return [dict(score=float(scores[k]), pose=poses_out[k].copy(), covariance=covs[k].reshape(3, 3).copy(),
+                     n_candidates=n_lat.value, best_index=int(best[k]),
+                     scores=all_scores[k] if want_scores else None) for k in range(K)]
+
+    def closure_set_timing(self, enabled):
+        """HIP events around the batched match's build and search launches on / off
+        (after the first matchCandidates: the closure object is made by it)."""
+        c = self._L.ndt2d_matcher_closure(self._m)
+        if not c:
+            raise Ndt2dError(_capi.ERR_STATE, "closure_set_timing", "no matchCandidates call yet")
+        rc = self._L.ndt2d_closure_set_timing(C.c_void_p(c), 1 if enabled else 0)
+        if rc != _capi.OK:
+            raise Ndt2dError(rc, "ndt2d_closure_set_timing")
+
+    def closure_last_ms(self):
+        """(build_ms, search_ms) of the last timed matchCandidates (its last chunk)."""
+        c = self._L.ndt2d_matcher_closure(self._m)
+        b, s = C.c_float(0.0), C.c_float(0.0)
+        rc = self._L.ndt2d_closure_last_ms(C.c_void_p(c), C.byref(b), C.byref(s)) if c else _capi.ERR_STATE
+        if rc != _capi.OK:
+            raise Ndt2dError(rc, "ndt2d_closure_last_ms")
+        return b.value, s.value
+
     def last_build(self):
         """How the NDT in place was built: "build/fused-small-map", "build/device", "build/host" or ""."""
         v = self._L.ndt2d_matcher_last_build(self._m)
@@ -709,3 +763,56 @@ def statistics_covariance(out, cov_prev):
     cov[1, 1] = out[6]
     cov[2, 2] += out[7]
     return cov
+
+
+def loop_closure_window(i, rolling):
+    """The scans a loop-closure candidate map is built from (reference src/ndt_mapper.cpp:
+    628-631): [begin_idx, end_idx) = "one additional scan on either side of candidate" as the
+    reference computes it -- the scan before `i` and `i` itself, only scan 0 for i == 0, and, its
+    quirk, only scan i - 1 for the candidate i == rolling (end_idx stays i there)."""
+    begin_idx = i - 1 if i > 0 else i
+    end_idx = i + 1 if i < rolling else i
+    return list(range(begin_idx, end_idx))
+
+
+def close_loops(matcher, scan_pose, points, candidate_indices, graph_poses, rolling, typical_response, limit,
+                scan_sizes=None):
+    """The loop-closure thread's walk over one new scan's candidates (reference
+    src/ndt_mapper.cpp:619-671) on the batched match.  candidate_indices: what findNearest
+    returned, in its order; graph_poses[i]: the pose of graph scan i, which is stored on the
+    matcher under id i; scan_sizes (optional): graph scan i's point count, to skip candidates
+    whose scan is empty (:625).  A skipped candidate does not count against `limit`, every
+    other one does (:670, `if (--num_scans_to_check == 0) break;` -- so limit == 0 never
+    reaches zero and checks them all, as the reference's unsigned counter does).
+
+    All remaining candidates are matched in one matchCandidates call from the scan's current
+    pose; the results are walked in order, and a candidate is accepted when
+    isfinite(score) and score < typical_response (:645).  An accept moves the scan's pose
+    (:652-655), which every later candidate of the reference's loop starts from: the rest is
+    matched again, in one batch, from the corrected pose.
+
+    Returns (pose, accepted): the scan's final pose and a list of dict(candidate, score,
+    correction, covariance, pose) in the order the constraints would be added."""
+    pose = np.array(scan_pose, dtype=np.float64).reshape(3).copy()
+    todo = []
+    for i in candidate_indices:
+        if scan_sizes is not None and scan_sizes[i] == 0:
+            continue                                   # `if (candidate->getPoints().empty()) continue;`
+        todo.append(int(i))
+        if limit and len(todo) == limit:               # `if (--num_scans_to_check == 0) break;`
+            break
+    accepted = []
+    while todo:
+        batch = [[(j, graph_poses[j]) for j in loop_closure_window(i, rolling)] for i in todo]
+        results = matcher.matchCandidates(pose, points, batch)
+        rest = []
+        for k, (i, res) in enumerate(zip(todo, results)):
+            if np.isfinite(res["score"]) and res["score"] < typical_response:
+                correction = np.array(res["pose"], dtype=np.float64)
+                pose = correction + pose               # correction.x += scan->getPose().x; ... (:652-654)
+                accepted.append(dict(candidate=i, score=res["score"], correction=correction,
+                                     covariance=res["covariance"], pose=pose.copy()))
+                rest = todo[k + 1:]
+                break
+        todo = rest
+    return pose, accepted
