@@ -1,0 +1,93 @@
+"""Batched match from K start poses against the K sequential matchScan calls (plugin defaults:
+80 x 21 x 21 lattice, 100 of 720 beams), on a 129 x 129 map and on the cfg-5 801 x 801 map.
+
+    python experiments/starts_batch_timing.py
+
+For K in {1, 8, 64, 512, 4096}: the median wall time of ScanMatcherNDT.matchStarts and of K
+matchScan calls (the same process, HIP events off; 20 repetitions after two warm-ups, 5 from
+K = 512 on), then -- events on -- the batched call's search and reduce launches
+(ndt2d_starts_last_ms; the last chunk of the call).  Start poses: the query's true pose first,
+the rest uniform over the room, every heading."""
+import math
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from ndt_2d_amd import ScanMatcherNDT, synth  # noqa: E402
+
+
+def median_us(fn, reps):
+    fn()
+    fn()
+    t = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        t.append(time.perf_counter() - t0)
+    return 1e6 * float(np.median(t))
+
+
+def fixture_map():
+    """The map of tests/test_gpu_match_starts.py: 45 scans of 360 beams, 129 x 129 cells."""
+    w = synth.world_of((12.0, 4.0, 0.25))
+    scans, index = [], 0
+    for iy in range(7):
+        for ix in range(7):
+            x, y = (ix - 3) * 3.0, (iy - 3) * 3.0
+            if not synth.pose_blocked(w, x, y):
+                scans.append(((x, y, 0.0), synth.scan(w, (x, y, 0.0), 9000 + index, n_beams=360)))
+            index += 1
+    true_pose = (2.2, -1.3, 0.4)
+    return "129 x 129", scans, 7.0, synth.scan(w, true_pose, 9100), true_pose, 12.0
+
+
+def cfg5_map():
+    c = synth.CONFIGS[5]
+    _, query, true_pose = synth.query_scan(5)
+    return "801 x 801 (cfg-5)", synth.map_scans(5), c["range_max"], query, tuple(true_pose), c["world"][0]
+
+
+def run(name, scans, range_max, query, true_pose, half):
+    m = ScanMatcherNDT(0)
+    m.initialize("starts-timing", range_max=range_max)      # the plugin's declared defaults
+    m.addScans(scans)
+    m.set_timing(False)
+    rng = np.random.default_rng(20261018)
+    print("map %s, %s" % (name, m.last_build()))
+    print("K     batched_us  sequential_us  ratio  search_ms  reduce_ms")
+    for K in (1, 8, 64, 512, 4096):
+        starts = np.empty((K, 3))
+        starts[:, 0:2] = rng.uniform(-half, half, size=(K, 2))
+        starts[:, 2] = rng.uniform(-math.pi, math.pi, size=K)
+        starts[0] = true_pose
+        reps = 20 if K < 512 else 5
+
+        def batched():
+            m.matchStarts(starts, query)
+
+        def sequential():
+            for s in starts:
+                m.matchScan(s, query)
+
+        batched()
+        m.starts_set_timing(False)
+        t_bat = median_us(batched, reps)
+        t_seq = median_us(sequential, reps)
+        m.starts_set_timing(True)
+        batched()
+        search_ms, reduce_ms = m.starts_last_ms()
+        m.starts_set_timing(False)
+        print("%-5d %10.1f %14.1f %6.2f %10.4f %10.4f" % (K, t_bat, t_seq, t_seq / t_bat, search_ms, reduce_ms), flush=True)
+
+
+def main():
+    run(*fixture_map())
+    run(*cfg5_map())
+
+
+if __name__ == "__main__":
+    main()

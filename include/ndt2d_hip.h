@@ -253,6 +253,59 @@ int ndt2d_get_grid(ndt2d_handle h, double * cells6_out, size_t capacity_cells, u
 int ndt2d_clear_grid(ndt2d_handle h);
 int ndt2d_has_grid(ndt2d_handle h);
 
+/* What a kernel outside the context needs of the installed grid (csrc/starts/): the geometry of
+ * NDT::getIndex and two device pointers -- cells_global[ncell + 1], one 64-byte line per cell
+ * {mean_x, mean_y, h00, h01, h11, occ, 0, 0} with h = -0.5 * information, and occ_bits, bit i =
+ * cell i can score (n >= 5); entry ncell of both stands for "off the grid".  Read-only, written
+ * by every install path; valid until the next install or clear.  NDT2D_ERR_NO_GRID without a
+ * grid. */
+typedef struct ndt2d_grid_view
+{
+  const double * cells_global;
+  const uint32_t * occ_bits;
+  uint32_t size_x, size_y, ncell;
+  int pow2;                 /* cell_size is a power of two: x * inv_cell_size == x / cell_size */
+  double cell_size, inv_cell_size;
+  double origin_x, origin_y;
+} ndt2d_grid_view;
+int ndt2d_grid_view_get(ndt2d_handle h, ndt2d_grid_view * out);
+
+/* ---- batched match from K start poses (csrc/starts/) ----
+ *
+ * One scan, the grid INSTALLED in the context, K start poses, the full matchScan lattice around
+ * each: what K calls of ndt2d_set_search_beams + ndt2d_match_launch(0, n_th) + ndt2d_match_fetch
+ * give, in one upload, one search launch over (theta step x start), one reduction and one
+ * read-back.  A node that loads a map and has no initial pose tries every graph node's pose under
+ * a few headings that way (relocalisation); a tracker keeps several hypotheses alive.
+ * An object of its own beside the context: it reads the grid installed at the time of the call
+ * (any install path, any size or origin), installs nothing, launches on the context's current
+ * stream, and must be destroyed before ndt2d_destroy(h).
+ *
+ *   create   max_starts (1 .. 4,096): starts of one launch; a call with more is processed in
+ *            chunks inside the call.  Chunking changes no bit.
+ *   match    starts_xyt[K][3]; beams_xy: the subsampled robot-frame beams; dth[n_th] / dlin[n_lin]:
+ *            the visited offsets (ndt2d_set_search).  cos / sin of theta_k + dth[i] come from the
+ *            host libm inside the call.  records_out[K][NDT2D_MATCH_RECORD_DOUBLES] receives
+ *            {best_score, best_index (-1: none; + 0.5: near tie), acc[10]} per start, all_scores
+ *            (optional) [K][n_th * n_lin * n_lin] every lattice candidate's raw score.  A raw
+ *            score has the bits of the small-lattice search's with its default plan; two calls
+ *            give the same bits.  Refused before anything is launched: a non-finite start
+ *            (NDT2D_ERR_INVALID, the message says "start k"), no grid (NDT2D_ERR_NO_GRID), a
+ *            lattice or beam count ndt2d_set_search / ndt2d_set_beams refuse (NDT2D_ERR_INVALID).
+ *            n_starts == 0: NDT2D_OK, nothing done.
+ *   set_timing / last_ms   HIP events around the search and the reduce launch of the last
+ *            (chunk of a) match, off by default. */
+typedef struct ndt2d_starts ndt2d_starts;
+int ndt2d_starts_create(ndt2d_handle h, size_t max_starts, ndt2d_starts ** out);
+int ndt2d_starts_destroy(ndt2d_starts * starts);
+const char * ndt2d_starts_last_error(ndt2d_starts * starts);
+int ndt2d_starts_match(ndt2d_starts * starts, const double * starts_xyt, size_t n_starts,
+                       const double * beams_xy, size_t n_beams, const double * dth, size_t n_th,
+                       const double * dlin, size_t n_lin, double * records_out,
+                       double * all_scores);
+int ndt2d_starts_set_timing(ndt2d_starts * starts, int enabled);
+int ndt2d_starts_last_ms(ndt2d_starts * starts, float * search_ms, float * reduce_ms);
+
 /* Upload the beam endpoints of one scan, robot frame, already subsampled to
  * min(laser_max_beams, points.size()) points by the caller
  * (src/scan_matcher_ndt.cpp:95-96,110 / :165-166,171).  Beams are taken as given: finite,
@@ -883,6 +936,27 @@ int ndt2d_matcher_match_candidates(ndt2d_matcher * m, const double * scan_pose_x
 /* The batched call's closure object (made by the first match_candidates; NULL before), for
  * ndt2d_closure_set_timing / _last_ms. */
 ndt2d_closure * ndt2d_matcher_closure(ndt2d_matcher * m);
+/* matchScan from K start poses against the NDT in place, in one call (ndt2d_starts_match with
+ * the matcher's own parameters, on the first device): relocalisation in a loaded map, several
+ * hypotheses of a tracker.  For start k the outputs are what
+ *     ndt2d_matcher_match_scan_ex(m, starts_xyt + 3 k, points, ...)
+ * gives on the same matcher, with match_candidates' conventions: poses_out[3 k ..] is written
+ * only when a lattice candidate of k scores below 0, best_index_out[k] is NDT2D_NO_INDEX without
+ * a winner, all_scores [K][lattice] is only filled when it holds them all, *n_lattice_out the
+ * lattice size (0 with no NDT in place: every score is then 0.0 and nothing else is written,
+ * src/scan_matcher_ndt.cpp:80).  A start whose record comes back marked as a near tie is settled
+ * by the sequential call for that start alone (ndt2d_matcher_adjudication_stats counts it); no
+ * points or an empty lattice go through the sequential call per start.  A search launched ahead
+ * by score_scan is waited out and dropped first.  The NDT stays in place.  A non-finite start:
+ * NDT2D_ERR_INVALID, "start k" in the message, nothing launched. */
+int ndt2d_matcher_match_starts(ndt2d_matcher * m, const double * starts_xyt, size_t n_starts,
+                               const double * points_xy, size_t n_points, double * poses_out,
+                               double * covariances_out, double * scores_out,
+                               uint64_t * best_index_out, double * all_scores,
+                               size_t all_scores_cap, size_t * n_lattice_out);
+/* The batched call's object (made by the first match_starts with an NDT in place; NULL before), for
+ * ndt2d_starts_set_timing / _last_ms. */
+ndt2d_starts * ndt2d_matcher_starts(ndt2d_matcher * m);
 /* The two halves of matchScan, for sharded (multi-GPU) searches:
  * prepare_search subsamples the scan (:95-96,110), builds the offset and
  * cos/sin tables (:103-107,117,119) and uploads them -- after it,

@@ -51,6 +51,7 @@
 #include "../build_small/ndt2d_build_small_fn.h"
 #include "ndt2d_guard.h"
 #include "ndt2d_hip.h"
+#include "ndt2d_walk_fn.h"
 
 namespace ndt2d
 {
@@ -61,11 +62,7 @@ namespace
 using namespace fused;
 
 constexpr uint32_t kNoRecord = 0xffffu;
-constexpr uint32_t kStageBeams = 1024;        // beams rotated into LDS at a time
-constexpr uint32_t kGroupBeams = 4;           // the small-lattice search's look-up group
-constexpr uint32_t kMaxSumChunks = 8;
-constexpr uint32_t kSearchMaxThreads = 1024;
-constexpr uint32_t kReduceThreads = 256;
+// (the lane's beam walk, the block records and the chunk plan: ndt2d_walk_fn.h, shared with ../starts/)
 
 // One candidate map of a launch.  Offsets are into the closure's device arrays.
 struct ClosureSlot
@@ -150,31 +147,21 @@ struct ClosureSearchArgs
   double * partials;         // [slot][n_th][kRecord]
 };
 
-// One beam of one lattice candidate: the term the reference adds (:127, NDT::likelihood).
-template <bool POW2>
-__device__ __forceinline__ void add_beam(const GridDesc & g, const uint16_t * lookup, const double * records,
-                                         double2 o, double dx, double dy, bool valid, double skip_below,
-                                         double & sum, bool & added)
+// A slot's map as the lane's walk reads it: the uint16 cell -> record table and the packed records.
+struct SlotMap
 {
-  const double px = o.x + dx;   // points_inner (:123-124)
-  const double py = o.y + dy;
-  const uint32_t cell = cell_index<POW2>(g, px, py);   // ncell: off the grid
-  const uint32_t rank = lookup[cell];
-  const bool has = valid & (rank != kNoRecord);
-  if (wave_any(has))
+  const uint16_t * lookup;
+  const double * records;
+  __device__ __forceinline__ bool find(uint32_t cell, uint32_t & rank) const
   {
-    const double2 * r = reinterpret_cast<const double2 *>(records + static_cast<size_t>(has ? rank : 0u) * 6);
-    const double2 m = r[0], h0 = r[1], h1 = r[2];
-    // (a lane without a record: exponent -inf, the reference's +0.0)
-    const double e = has ? record_exponent(m.x, m.y, h0.x, h0.y, h1.x, px, py) : -HUGE_VAL;
-    // !(e < bound) also keeps NaN exponents (degenerate cells) on the exact path
-    if (wave_any(!(e < skip_below)))
-    {
-      sum += exp_score(e);
-      added = true;
-    }
+    rank = lookup[cell];
+    return rank != kNoRecord;
   }
-}
+  __device__ __forceinline__ const double2 * record(uint32_t rank) const
+  {
+    return reinterpret_cast<const double2 *>(records + static_cast<size_t>(rank) * 6);
+  }
+};
 
 template <int C, bool POW2>
 __global__ void __launch_bounds__(kSearchMaxThreads) closure_search_kernel(const ClosureSearchArgs a)
@@ -182,16 +169,11 @@ __global__ void __launch_bounds__(kSearchMaxThreads) closure_search_kernel(const
   __shared__ double2 rows[kStageBeams];
   const uint32_t ith = blockIdx.x, slot = blockIdx.y;
   const uint32_t tid = threadIdx.x, n_threads = blockDim.x;
-  const uint32_t lane = tid & (kWave - 1), wave = tid >> 6, n_waves = n_threads >> 6;
   const ClosureSlot & s = a.slots[slot];
   const GridDesc g = s.grid;
-  const uint16_t * lookup = a.lookup + s.lookup_off;
-  const double * records = a.records + 6 * static_cast<size_t>(s.list_off);
+  const SlotMap map{a.lookup + s.lookup_off, a.records + 6 * static_cast<size_t>(s.list_off)};
   const double ct = a.cos_th[ith], st = a.sin_th[ith], dt = a.dth[ith];
   const uint32_t n_lin = a.n_lin, n_cand = n_lin * n_lin;
-  const uint32_t n_groups = (a.n_beams + kGroupBeams - 1) / kGroupBeams;
-  // groups of a piece: whole rounds of the C partial sums
-  constexpr uint32_t kPieceGroups = (kStageBeams / kGroupBeams / C) * C;
 
   double best_s = 0.0;       // `double best_score = 0;` (:83)
   double best_i = kNoIndex;
@@ -206,170 +188,27 @@ __global__ void __launch_bounds__(kSearchMaxThreads) closure_search_kernel(const
     const uint32_t cc = valid ? c : n_cand - 1u;
     const uint32_t ix = cc / n_lin, iy = cc - ix * n_lin;
     const double dx = a.dlin[ix], dy = a.dlin[iy];
-    double p[C], skip_below[C];
-#pragma unroll
-    for (int j = 0; j < C; ++j)
-    {
-      p[j] = 0.0;
-      skip_below[j] = negligible_below(0.0);
-    }
-    for (uint32_t g0 = 0; g0 < n_groups; g0 += kPieceGroups)
-    {
-      const uint32_t b0 = g0 * kGroupBeams;
-      const uint32_t b1 = min(a.n_beams, b0 + kPieceGroups * kGroupBeams);
-      __syncthreads();   // the piece before has been read
-      for (uint32_t b = b0 + tid; b < b1; b += n_threads)
-      {
-        const double2 q = reinterpret_cast<const double2 *>(a.beams_xy)[b];
-        // points_outer (:111-114)
-        rows[b - b0] = double2{q.x * ct - q.y * st + a.pose_x, q.x * st + q.y * ct + a.pose_y};
-      }
-      __syncthreads();
-      const uint32_t g1 = (b1 - b0 + kGroupBeams - 1) / kGroupBeams;   // groups of this piece
-      for (uint32_t gr = 0; gr < g1; gr += C)
-      {
-#pragma unroll
-        for (int j = 0; j < C; ++j)
-        {
-          const uint32_t first = (gr + j) * kGroupBeams;   // within the piece
-          if (first < b1 - b0)
-          {
-            bool added = false;
-#pragma unroll
-            for (uint32_t u = 0; u < kGroupBeams; ++u)
-            {
-              if (first + u < b1 - b0)
-              {
-                add_beam<POW2>(g, lookup, records, rows[first + u], dx, dy, valid, skip_below[j], p[j], added);
-              }
-            }
-            if (added) skip_below[j] = negligible_below(p[j]);
-          }
-        }
-      }
-    }
-    // ((p_0 + p_1) + p_2) + ... as the small-lattice search adds its waves' partial sums
-    double sum = p[0];
-#pragma unroll
-    for (int j = 1; j < C; ++j) sum += p[j];
+    const double sum = lane_walk<C, POW2>(g, map, rows, a.beams_xy, a.n_beams, ct, st, a.pose_x, a.pose_y, dx, dy, valid);
     if (valid)
     {
       const double score = -sum;  // (:127)
-      const uint64_t flat = static_cast<uint64_t>(ith) * n_cand + c;
-      double cs = 0.0, ci = kNoIndex;
-      if (score < 0.0)
-      {
-        cs = score;
-        ci = static_cast<double>(flat);
-      }
-      merge_best(cs, ci, best_s, best_i);
-      // k += x x^T score, u += x score, s += score (:137-140)
-      acc[0] += (dx * dx) * score;
-      acc[1] += (dx * dy) * score;
-      acc[2] += (dx * dt) * score;
-      acc[3] += (dy * dy) * score;
-      acc[4] += (dy * dt) * score;
-      acc[5] += (dt * dt) * score;
-      acc[6] += dx * score;
-      acc[7] += dy * score;
-      acc[8] += dt * score;
-      acc[9] += score;
+      lane_take(score, static_cast<uint64_t>(ith) * n_cand + c, dx, dy, dt, best_s, best_i, acc);
       if (a.scores != nullptr) a.scores[(static_cast<uint64_t>(slot) * a.n_th + ith) * n_cand + c] = score;
     }
   }
-
-  // the block's record: lanes over the DPP network, waves in wave order
-  wave_best_to_last_lane(best_s, best_i);
-#pragma unroll
-  for (int k = 0; k < 10; ++k) acc[k] = wave_sum_to_last_lane(acc[k]);
-  __syncthreads();   // the rows are free
-  double * scratch = reinterpret_cast<double *>(rows);
-  if (lane == kWave - 1)
-  {
-    scratch[wave * kRecord + 0] = best_s;
-    scratch[wave * kRecord + 1] = best_i;
-#pragma unroll
-    for (int k = 0; k < 10; ++k) scratch[wave * kRecord + 2 + k] = acc[k];
-  }
-  __syncthreads();
-  if (tid < static_cast<uint32_t>(kRecord))
-  {
-    double val;
-    if (tid < 2)
-    {
-      double s0 = scratch[0], i0 = scratch[1];
-      for (uint32_t w = 1; w < n_waves; ++w) merge_best(scratch[w * kRecord], scratch[w * kRecord + 1], s0, i0);
-      val = tid == 0 ? s0 : i0;
-    }
-    else
-    {
-      val = scratch[tid];
-      for (uint32_t w = 1; w < n_waves; ++w) val += scratch[w * kRecord + tid];
-    }
-    a.partials[(static_cast<size_t>(slot) * a.n_th + ith) * kRecord + tid] = val;
-  }
+  // the block's record (the rows are free behind block_record's first barrier)
+  block_record<false>(best_s, best_i, acc, reinterpret_cast<double *>(rows),
+                      a.partials + (static_cast<size_t>(slot) * a.n_th + ith) * kRecord);
 }
-static_assert(kStageBeams * sizeof(double2) >= (kSearchMaxThreads / 64) * kRecord * sizeof(double), "a record per wave");
 
 // partials[slot][n_th][kRecord] -> out[slot][kRecord]
 __global__ void __launch_bounds__(kReduceThreads) closure_reduce_kernel(const double * partials, uint32_t n_th,
                                                                          double * out)
 {
   __shared__ double scratch[(kReduceThreads / 64) * kRecord];
-  const uint32_t slot = blockIdx.x, tid = threadIdx.x;
-  const uint32_t lane = tid & (kWave - 1), wave = tid >> 6;
-  constexpr uint32_t n_waves = kReduceThreads / 64;
-  double bs = 0.0, bi = kNoIndex;
-  double acc[10];
-#pragma unroll
-  for (int k = 0; k < 10; ++k) acc[k] = 0.0;
-  for (uint32_t r = tid; r < n_th; r += kReduceThreads)
-  {
-    const double * p = partials + (static_cast<size_t>(slot) * n_th + r) * kRecord;
-    merge_best(p[0], p[1], bs, bi);
-#pragma unroll
-    for (int k = 0; k < 10; ++k) acc[k] += p[2 + k];
-  }
-  wave_best_to_last_lane(bs, bi);
-#pragma unroll
-  for (int k = 0; k < 10; ++k) acc[k] = wave_sum_to_last_lane(acc[k]);
-  if (lane == kWave - 1)
-  {
-    scratch[wave * kRecord + 0] = bs;
-    scratch[wave * kRecord + 1] = bi;
-#pragma unroll
-    for (int k = 0; k < 10; ++k) scratch[wave * kRecord + 2 + k] = acc[k];
-  }
-  __syncthreads();
-  if (tid < static_cast<uint32_t>(kRecord))
-  {
-    double val;
-    if (tid < 2)
-    {
-      double s0 = scratch[0], i0 = scratch[1];
-      for (uint32_t w = 1; w < n_waves; ++w) merge_best(scratch[w * kRecord], scratch[w * kRecord + 1], s0, i0);
-      val = tid == 0 ? s0 : (s0 < 0.0 ? i0 : -1.0);   // no candidate scored below 0: no index
-    }
-    else
-    {
-      val = scratch[tid];
-      for (uint32_t w = 1; w < n_waves; ++w) val += scratch[w * kRecord + tid];
-    }
-    out[static_cast<size_t>(slot) * kRecord + tid] = val;
-  }
-}
-
-// The partial sums of a candidate's score: the beam chunks of the small-lattice search's default
-// plan (ndt2d_match_small.hip small_plan: groups of four beams, chunks of five groups, at most
-// eight chunks), a function of the beam count alone.
-uint32_t sum_chunks(uint32_t n_beams)
-{
-  const uint32_t groups = (n_beams + kGroupBeams - 1) / kGroupBeams;
-  uint32_t best_c = (groups + 4) / 5;
-  if (best_c > kMaxSumChunks) best_c = kMaxSumChunks;
-  if (best_c < 1) best_c = 1;
-  const uint32_t chunk_groups = (groups + best_c - 1) / best_c;
-  return chunk_groups == 0 ? 1u : (groups + chunk_groups - 1) / chunk_groups;
+  const uint32_t slot = blockIdx.x;
+  reduce_slot_records(partials + static_cast<size_t>(slot) * n_th * kRecord, n_th, scratch,
+                      out + static_cast<size_t>(slot) * kRecord);
 }
 
 template <bool POW2>

@@ -700,6 +700,8 @@ struct ndt2d_matcher
   std::vector<ndt2d_scanstore *> stores;   // resident scans, one store per device (made by the first store_scan)
   ndt2d_closure * closure = nullptr;       // batched loop-closure match on the first device (made by the first match_candidates)
   std::vector<double> closure_records;     // its records, [K][NDT2D_MATCH_RECORD_DOUBLES]
+  ndt2d_starts * starts = nullptr;         // batched match from K start poses on the first device (made by the first match_starts)
+  std::vector<double> starts_records;      // its records, [K][NDT2D_MATCH_RECORD_DOUBLES]
   // the NDT in place came from the fused build: one pose at a time is scored on the device (fetching
   // the grid back for the host path would cost the cycle more than the build saved)
   bool ndt_fused = false;
@@ -1663,6 +1665,7 @@ void destroy_matcher(ndt2d_matcher * m)
     if (sh.d_weights != nullptr) ndt2d_device_free(m->devs[r], sh.d_weights);
   }
   if (m->closure != nullptr) (void)ndt2d_closure_destroy(m->closure);         // (before its store)
+  if (m->starts != nullptr) (void)ndt2d_starts_destroy(m->starts);            // (before its context)
   for (ndt2d_scanstore * st : m->stores) (void)ndt2d_scanstore_destroy(st);   // (before their contexts)
   for (ndt2d_handle h : m->devs) (void)ndt2d_build_small_release(h);
   if (m->exchange != nullptr) ndt2d::exchange_destroy(m->exchange);
@@ -2371,6 +2374,105 @@ int ndt2d_matcher_match_candidates(ndt2d_matcher * m, const double * scan_pose_x
 }
 
 ndt2d_closure * ndt2d_matcher_closure(ndt2d_matcher * m) { return m != nullptr ? m->closure : nullptr; }
+
+// Starts the batched match launches at a time: the object's limit (a relocalisation over every
+// graph node under a few headings is hundreds to a few thousand).
+static constexpr size_t kStartsSlots = 4096;
+
+int ndt2d_matcher_match_starts(ndt2d_matcher * m, const double * starts_xyt, size_t n_starts, const double * points_xy,
+                               size_t n_points, double * poses_out, double * covariances_out, double * scores_out,
+                               uint64_t * best_index_out, double * all_scores, size_t all_scores_cap,
+                               size_t * n_lattice_out)
+{
+  NDT2D_C_TRY
+  if (m == nullptr) return NDT2D_ERR_INVALID;
+  if (n_lattice_out != nullptr) *n_lattice_out = 0;
+  if (n_starts == 0) return NDT2D_OK;
+  if (starts_xyt == nullptr || scores_out == nullptr || (n_points > 0 && points_xy == nullptr))
+  {
+    return mfail(m, NDT2D_ERR_INVALID, "match_starts: null input");
+  }
+  if (n_starts > (1u << 20)) return mfail(m, NDT2D_ERR_INVALID, "match_starts: too many starts");
+  // `if (!ndt_) return 0.0;` (reference src/scan_matcher_ndt.cpp:80): outputs untouched
+  if (!m->have_ndt)
+  {
+    for (size_t k = 0; k < n_starts; ++k)
+    {
+      scores_out[k] = 0.0;
+      if (best_index_out != nullptr) best_index_out[k] = NDT2D_NO_INDEX;
+    }
+    return NDT2D_OK;
+  }
+  for (size_t k = 0; k < n_starts; ++k)
+  {
+    if (!std::isfinite(starts_xyt[3 * k]) || !std::isfinite(starts_xyt[3 * k + 1]) || !std::isfinite(starts_xyt[3 * k + 2]))
+    {
+      return mfail(m, NDT2D_ERR_INVALID, "match_starts: start " + std::to_string(k) + ": the pose is not finite");
+    }
+  }
+  const size_t n_th = m->search.dth.size(), n_lin = m->search.dlin.size();
+  const size_t n_lattice = n_th * n_lin * n_lin;
+  if (n_lattice_out != nullptr) *n_lattice_out = n_lattice;
+  discard_ahead(m);   // a search launched ahead by scoreScan is waited out and dropped
+  if (m->starts == nullptr)
+  {
+    const int rc = ndt2d_starts_create(m->dev, kStartsSlots, &m->starts);
+    if (rc != NDT2D_OK) return dev_fail(m, rc, "ndt2d_starts_create");
+  }
+  double * scores_ptr = (all_scores != nullptr && all_scores_cap / n_starts >= n_lattice && n_lattice > 0) ? all_scores : nullptr;
+
+  // the scan as matchScan takes it: subsampled beams (:95-96,110), once for every start
+  subsample_into(m->beams.next, points_xy, n_points, m->laser_max_beams);
+  const size_t use = m->beams.next.size() / 2;
+  if (!m->beams.holds(m->beams.next)) m->beams.adopt(m->beams.next);   // (the host copy; the context's beams stay)
+  m->search.n_use = use;
+  m->search.ready = false;   // no search is prepared on the context
+  m->starts_records.assign(n_starts * NDT2D_MATCH_RECORD_DOUBLES, 0.0);
+  double * records = m->starts_records.data();
+  std::vector<char> sequential(n_starts, 0);
+  if (use == 0 || n_lattice == 0)
+  {
+    // No points: every candidate scores -0.0 and none is < 0; no candidates: the loops do not run.
+    // What the sequential call does with that is its to say.
+    std::fill(sequential.begin(), sequential.end(), 1);
+  }
+  else
+  {
+    const int rc = ndt2d_starts_match(m->starts, starts_xyt, n_starts, m->beams.host.data(), use, m->search.dth.data(), n_th,
+                                      m->search.dlin.data(), n_lin, records, scores_ptr);
+    if (rc != NDT2D_OK) return mfail(m, rc, std::string("match_starts: ") + ndt2d_starts_last_error(m->starts));
+    m->last_multi = false;
+    // a marked winner (index + 0.5): the start alone through the sequential call, whose adjudication settles it
+    for (size_t k = 0; k < n_starts; ++k)
+    {
+      const double bi = records[k * NDT2D_MATCH_RECORD_DOUBLES + 1];
+      sequential[k] = (bi >= 0.0 && bi != std::floor(bi)) ? 1 : 0;
+    }
+  }
+  int rc = NDT2D_OK;
+  for (size_t k = 0; k < n_starts && rc == NDT2D_OK; ++k)
+  {
+    double * pose_k = poses_out != nullptr ? poses_out + 3 * k : nullptr;
+    double * cov_k = covariances_out != nullptr ? covariances_out + 9 * k : nullptr;
+    if (sequential[k])
+    {
+      rc = ndt2d_matcher_match_scan_ex(m, starts_xyt + 3 * k, points_xy, n_points, pose_k, cov_k, scores_out + k,
+                                       scores_ptr != nullptr ? scores_ptr + k * n_lattice : nullptr, n_lattice, nullptr,
+                                       best_index_out != nullptr ? best_index_out + k : nullptr);
+      if (rc != NDT2D_OK) m->err = "match_starts: start " + std::to_string(k) + ": " + m->err;
+      // (the sequential call prepared a search of its own; the records after it are finished with this N)
+      m->search.n_use = use;
+      continue;
+    }
+    const double * rec = records + k * NDT2D_MATCH_RECORD_DOUBLES;
+    if (best_index_out != nullptr) best_index_out[k] = rec[1] < 0.0 ? NDT2D_NO_INDEX : static_cast<uint64_t>(rec[1]);
+    rc = ndt2d_matcher_finish_match(m, rec, pose_k, cov_k, scores_out + k);
+  }
+  return rc;
+  NDT2D_C_CATCH(m)
+}
+
+ndt2d_starts * ndt2d_matcher_starts(ndt2d_matcher * m) { return m != nullptr ? m->starts : nullptr; }
 
 int ndt2d_matcher_match_laser_scan(ndt2d_matcher * m, const double * scan_pose_xyt,
                                    const float * ranges, size_t n_ranges,

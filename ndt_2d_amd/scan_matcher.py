@@ -425,6 +425,55 @@ class ScanMatcherNDT:
             raise Ndt2dError(rc, "ndt2d_closure_last_ms")
         return b.value, s.value
 
+    def matchStarts(self, start_poses, points, want_scores=False):
+        """matchScan of one scan from K start poses against the NDT in place, in one call (one
+        upload, one search launch over start x lattice, one read-back): relocalisation in a loaded
+        map, several hypotheses of a tracker.  Returns one dict per start, the dict
+        matchScan(start, points) returns: `pose` is (0, 0, 0) unless a lattice candidate scores
+        below 0, covariance is None when there is no NDT.  The NDT stays in place."""
+        sp = _f64(start_poses, (-1, 3))
+        pts = _f64(points, (-1, 2))
+        K = len(sp)
+        poses_out = np.zeros((K, 3))
+        covs = np.full((K, 9), np.nan)
+        scores = np.zeros(K)
+        best = np.full(K, _capi.NO_INDEX, dtype=np.uint64)
+        n_lat = C.c_size_t(0)
+        all_scores, as_ptr, cap = None, None, 0
+        if want_scores:
+            p = self.params
+            n_th = len(search_offsets(p["search_angular_size"], p["search_angular_resolution"]))
+            n_lin = len(search_offsets(p["search_linear_size"], p["search_linear_resolution"]))
+            all_scores = np.zeros((K, n_th * n_lin * n_lin), dtype=np.float64)
+            as_ptr, cap = dptr(all_scores), all_scores.size
+        self._check(self._L.ndt2d_matcher_match_starts(
+            self._m, dptr(sp), K, dptr(pts), len(pts), dptr(poses_out), dptr(covs), dptr(scores),
+            best.ctypes.data_as(C.POINTER(C.c_uint64)), as_ptr, cap, C.byref(n_lat)), "matchStarts")
+        has = bool(self._L.ndt2d_matcher_has_ndt(self._m))
+        return [dict(score=float(scores[k]), pose=poses_out[k].copy(),
+                     covariance=covs[k].reshape(3, 3).copy() if has else None,
+                     n_candidates=n_lat.value, best_index=int(best[k]),
+                     scores=all_scores[k] if want_scores else None) for k in range(K)]
+
+    def starts_set_timing(self, enabled):
+        """HIP events around the batched match's search and reduce launches on / off (after the
+        first matchStarts with an NDT in place: the object is made by it)."""
+        s = self._L.ndt2d_matcher_starts(self._m)
+        if not s:
+            raise Ndt2dError(_capi.ERR_STATE, "starts_set_timing", "no matchStarts call yet")
+        rc = self._L.ndt2d_starts_set_timing(C.c_void_p(s), 1 if enabled else 0)
+        if rc != _capi.OK:
+            raise Ndt2dError(rc, "ndt2d_starts_set_timing")
+
+    def starts_last_ms(self):
+        """(search_ms, reduce_ms) of the last timed matchStarts (its last chunk)."""
+        s = self._L.ndt2d_matcher_starts(self._m)
+        a, b = C.c_float(0.0), C.c_float(0.0)
+        rc = self._L.ndt2d_starts_last_ms(C.c_void_p(s), C.byref(a), C.byref(b)) if s else _capi.ERR_STATE
+        if rc != _capi.OK:
+            raise Ndt2dError(rc, "ndt2d_starts_last_ms")
+        return a.value, b.value
+
     def last_build(self):
         """How the NDT in place was built: "build/fused-small-map", "build/device", "build/host" or ""."""
         v = self._L.ndt2d_matcher_last_build(self._m)
@@ -816,3 +865,44 @@ def close_loops(matcher, scan_pose, points, candidate_indices, graph_poses, roll
                 break
         todo = rest
     return pose, accepted
+
+
+def heading_fan(poses, n_headings):
+    """Every pose under n_headings equally spaced headings, the first its own: pose k gives
+    (x, y, theta + 2 pi j / n_headings), j = 0 .. n_headings - 1, in that order.  Seeds for
+    relocalize() from graph nodes, whose stored heading says nothing about the robot's."""
+    ps = np.array(poses, dtype=np.float64).reshape(-1, 3)
+    n = int(n_headings)
+    if n < 1:
+        raise ValueError("heading_fan: n_headings must be at least 1")
+    out = np.repeat(ps, n, axis=0)
+    out[:, 2] += np.tile(np.arange(n) * (2.0 * np.pi / n), len(ps))
+    return out
+
+
+def relocalize(matcher, points, start_poses, accept_below=None):
+    """Where in the matcher's map was this scan taken?  One matchStarts call from every start
+    pose -- what a node that loaded its map does instead of refusing scans until somebody posts
+    `initialpose` (reference src/ndt_mapper.cpp:315-320).  Returns the starts ranked by score
+    (lower is better), ties in start order: a list of dict(start = index into start_poses,
+    correction = matchScan's pose output, pose = start pose + correction as the reference adds
+    it (:557-561), score, covariance).  Starts without a winner (no lattice candidate below 0)
+    follow those with one, non-finite scores come last.  accept_below: keep only
+    isfinite(score) and score < accept_below, the loop-closure rule (:645)."""
+    starts = np.array(start_poses, dtype=np.float64).reshape(-1, 3)
+    if len(starts) == 0:
+        return []
+    results = matcher.matchStarts(starts, points)
+    ranked = []
+    for k, res in enumerate(results):
+        score = float(res["score"])
+        if accept_below is not None and not (np.isfinite(score) and score < accept_below):
+            continue
+        correction = np.array(res["pose"], dtype=np.float64)
+        finite = bool(np.isfinite(score))
+        winner = res["best_index"] != _capi.NO_INDEX
+        key = (0 if finite else 1, 0 if winner else 1, score if finite else 0.0, k)
+        ranked.append((key, dict(start=k, correction=correction, pose=correction + starts[k], score=score,
+                                 covariance=res["covariance"])))
+    ranked.sort(key=lambda e: e[0])
+    return [entry for _, entry in ranked]
