@@ -306,6 +306,52 @@ int ndt2d_starts_match(ndt2d_starts * starts, const double * starts_xyt, size_t 
 int ndt2d_starts_set_timing(ndt2d_starts * starts, int enabled);
 int ndt2d_starts_last_ms(ndt2d_starts * starts, float * search_ms, float * reduce_ms);
 
+/* ---- batched scan tracking: K scans, each from its own pose (csrc/scans/) ----
+ *
+ * A job is a (scan, pose) pair; a call takes S scans and K jobs against the grid INSTALLED in the
+ * context: what K calls of ndt2d_set_search_beams + ndt2d_match_launch(0, n_th) +
+ * ndt2d_match_fetch give, each with its job's beams and pose, in one upload, the search launches
+ * over (theta step x job), one reduction and one read-back.  The reference's localisation branch
+ * (src/ndt_mapper.cpp:547-566) for many scans at once: a fleet of robots on one shared map, a
+ * recorded bag replayed against a loaded map, every scan of a graph matched again after an
+ * optimisation.  ndt2d_starts_match is the case S = 1.
+ * An object of its own beside the context, as ndt2d_starts: it reads the grid installed at the
+ * time of the call (any install path, any size or origin), installs nothing, launches on the
+ * context's current stream, and must be destroyed before ndt2d_destroy(h).
+ *
+ *   create   max_jobs (1 .. 4,096): jobs of one chunk; a call with more is processed in chunks
+ *            inside the call.  Chunking changes no bit.
+ *   match    jobs_xyt[K][3]; job_scan[K]: the scan of job k (several jobs may name one scan: its
+ *            beams travel once; a scan no job names is legal and is not uploaded), NULL: job k
+ *            uses scan k and n_scans must equal n_jobs.  beams_xy: the already subsampled
+ *            robot-frame beams of all scans, scan s = beams_xy[2 * beam_offsets[s] ..
+ *            2 * beam_offsets[s + 1]), beam_offsets[n_scans + 1] non-decreasing; beams are taken
+ *            as given ("Points off the grid" below).  dth[n_th] / dlin[n_lin]: the visited
+ *            offsets (ndt2d_set_search).  cos / sin of theta_k + dth[i] come from the host libm
+ *            inside the call.  records_out and all_scores (optional) have the layouts of
+ *            ndt2d_starts_match, by job in the caller's order.  The partial sums of a raw score
+ *            follow from the beam count of the job's scan, so a raw score has the bits of the
+ *            small-lattice search's with its default plan; the jobs of a chunk are searched with
+ *            one launch per number of partial sums present (one when every scan has the same
+ *            count, eight at most).  A job's bits do not depend on the other jobs.
+ *            Refused with NDT2D_ERR_INVALID before anything is launched: a non-finite job pose or
+ *            job_scan[k] >= n_scans (the message says "job k"), a scan with 0 or more than 2^20
+ *            beams or beam_offsets that decrease ("scan s"), a lattice ndt2d_set_search refuses,
+ *            job_scan == NULL with n_scans != n_jobs.  No grid: NDT2D_ERR_NO_GRID.
+ *            n_jobs == 0: NDT2D_OK, nothing done.
+ *   set_timing / last_ms   HIP events around the search launches and the reduce launch of the
+ *            last (chunk of a) match, off by default. */
+typedef struct ndt2d_scans ndt2d_scans;
+int ndt2d_scans_create(ndt2d_handle h, size_t max_jobs, ndt2d_scans ** out);
+int ndt2d_scans_destroy(ndt2d_scans * scans);
+const char * ndt2d_scans_last_error(ndt2d_scans * scans);
+int ndt2d_scans_match(ndt2d_scans * scans, const double * jobs_xyt, const uint32_t * job_scan,
+                      size_t n_jobs, const double * beams_xy, const size_t * beam_offsets,
+                      size_t n_scans, const double * dth, size_t n_th, const double * dlin,
+                      size_t n_lin, double * records_out, double * all_scores);
+int ndt2d_scans_set_timing(ndt2d_scans * scans, int enabled);
+int ndt2d_scans_last_ms(ndt2d_scans * scans, float * search_ms, float * reduce_ms);
+
 /* Upload the beam endpoints of one scan, robot frame, already subsampled to
  * min(laser_max_beams, points.size()) points by the caller
  * (src/scan_matcher_ndt.cpp:95-96,110 / :165-166,171).  Beams are taken as given: finite,
@@ -957,6 +1003,33 @@ int ndt2d_matcher_match_starts(ndt2d_matcher * m, const double * starts_xyt, siz
 /* The batched call's object (made by the first match_starts with an NDT in place; NULL before), for
  * ndt2d_starts_set_timing / _last_ms. */
 ndt2d_starts * ndt2d_matcher_starts(ndt2d_matcher * m);
+/* matchScan of K jobs -- (scan, pose) pairs -- against the NDT in place, in one call
+ * (ndt2d_scans_match with the matcher's own parameters, on the first device): the localisation
+ * branch (src/ndt_mapper.cpp:547-566) for a fleet on one map, a replayed bag, a graph's scans
+ * after an optimisation.  Scan s is points_xy[2 * point_offsets[s] .. 2 * point_offsets[s + 1]),
+ * point_offsets[n_scans + 1] non-decreasing; job_scan[k] names the scan of job k (NULL: job k
+ * uses scan k, n_scans == n_jobs).  Each scan a job names is subsampled once, as matchScan
+ * subsamples it.  For job k the outputs are what
+ *     ndt2d_matcher_match_scan_ex(m, jobs_xyt + 3 k, the points of scan job_scan[k], ...)
+ * gives on the same matcher, with match_starts' conventions: poses_out[3 k ..] is written only
+ * when a lattice candidate of k scores below 0, best_index_out[k] is NDT2D_NO_INDEX without a
+ * winner, all_scores [K][lattice] is only filled when it holds them all, *n_lattice_out the
+ * lattice size (0 with no NDT in place: every score is then 0.0 and nothing else is written,
+ * src/scan_matcher_ndt.cpp:80).  A job whose record comes back marked as a near tie is settled
+ * by the sequential call for that job alone (ndt2d_matcher_adjudication_stats counts it); jobs
+ * of a scan without points, or an empty lattice, go through the sequential call.  A search
+ * launched ahead by score_scan is waited out and dropped first.  The NDT stays in place.
+ * NDT2D_ERR_INVALID, nothing launched: a non-finite job pose or a scan index out of range
+ * ("job k" in the message), point_offsets that decrease ("scan s"), job_scan == NULL with
+ * n_scans != n_jobs. */
+int ndt2d_matcher_match_scans(ndt2d_matcher * m, const double * jobs_xyt, const uint32_t * job_scan,
+                              size_t n_jobs, const double * points_xy, const size_t * point_offsets,
+                              size_t n_scans, double * poses_out, double * covariances_out,
+                              double * scores_out, uint64_t * best_index_out, double * all_scores,
+                              size_t all_scores_cap, size_t * n_lattice_out);
+/* The batched call's object (made by the first match_scans with an NDT in place; NULL before), for
+ * ndt2d_scans_set_timing / _last_ms. */
+ndt2d_scans * ndt2d_matcher_scans(ndt2d_matcher * m);
 /* The two halves of matchScan, for sharded (multi-GPU) searches:
  * prepare_search subsamples the scan (:95-96,110), builds the offset and
  * cos/sin tables (:103-107,117,119) and uploads them -- after it,

@@ -120,6 +120,12 @@ SIGNATURES = {
     "ndt2d_starts_match": (C.c_int, [_vp, _dp, _sz, _dp, _sz, _dp, _sz, _dp, _sz, _dp, _dp]),
     "ndt2d_starts_set_timing": (C.c_int, [_vp, C.c_int]),
     "ndt2d_starts_last_ms": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "ndt2d_scans_create": (C.c_int, [_vp, _sz, C.POINTER(_vp)]),
+    "ndt2d_scans_destroy": (C.c_int, [_vp]),
+    "ndt2d_scans_last_error": (C.c_char_p, [_vp]),
+    "ndt2d_scans_match": (C.c_int, [_vp, _dp, C.POINTER(_u32), _sz, _dp, _szp, _sz, _dp, _sz, _dp, _sz, _dp, _dp]),
+    "ndt2d_scans_set_timing": (C.c_int, [_vp, C.c_int]),
+    "ndt2d_scans_last_ms": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "ndt2d_set_eigenvalue_form": (C.c_int, [_vp, C.c_char_p]),
     "ndt2d_get_grid": (C.c_int, [_vp, _dp, _sz, C.POINTER(_u32), C.POINTER(_u32), _dp, _dp, _dp]),
     "ndt2d_clear_grid": (C.c_int, [_vp]),
@@ -230,6 +236,9 @@ SIGNATURES = {
     "ndt2d_matcher_match_starts": (C.c_int, [_vp, _dp, _sz, _dp, _sz, _dp, _dp, _dp, C.POINTER(C.c_uint64), _dp, _sz,
                                              _szp]),
     "ndt2d_matcher_starts": (_vp, [_vp]),
+    "ndt2d_matcher_match_scans": (C.c_int, [_vp, _dp, C.POINTER(_u32), _sz, _dp, _szp, _sz, _dp, _dp, _dp,
+                                            C.POINTER(C.c_uint64), _dp, _sz, _szp]),
+    "ndt2d_matcher_scans": (_vp, [_vp]),
     "ndt2d_matcher_match_laser_scan": (C.c_int, [_vp, _dp, C.POINTER(C.c_float), _sz,
                                                  C.POINTER(LaserScan), _dp, _dp, _dp, _szp]),
     "ndt2d_matcher_prepare_search": (C.c_int, [_vp, _dp, _dp, _sz, _szp, _szp, _szp]),

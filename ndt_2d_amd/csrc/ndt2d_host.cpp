@@ -702,6 +702,8 @@ struct ndt2d_matcher
   std::vector<double> closure_records;     // its records, [K][NDT2D_MATCH_RECORD_DOUBLES]
   ndt2d_starts * starts = nullptr;         // batched match from K start poses on the first device (made by the first match_starts)
   std::vector<double> starts_records;      // its records, [K][NDT2D_MATCH_RECORD_DOUBLES]
+  ndt2d_scans * scans = nullptr;           // batched scan tracking on the first device (made by the first match_scans)
+  std::vector<double> scans_records;       // its records, [K][NDT2D_MATCH_RECORD_DOUBLES]
   // the NDT in place came from the fused build: one pose at a time is scored on the device (fetching
   // the grid back for the host path would cost the cycle more than the build saved)
   bool ndt_fused = false;
@@ -1666,6 +1668,7 @@ void destroy_matcher(ndt2d_matcher * m)
   }
   if (m->closure != nullptr) (void)ndt2d_closure_destroy(m->closure);         // (before its store)
   if (m->starts != nullptr) (void)ndt2d_starts_destroy(m->starts);            // (before its context)
+  if (m->scans != nullptr) (void)ndt2d_scans_destroy(m->scans);               // (before its context)
   for (ndt2d_scanstore * st : m->stores) (void)ndt2d_scanstore_destroy(st);   // (before their contexts)
   for (ndt2d_handle h : m->devs) (void)ndt2d_build_small_release(h);
   if (m->exchange != nullptr) ndt2d::exchange_destroy(m->exchange);
@@ -2473,6 +2476,172 @@ int ndt2d_matcher_match_starts(ndt2d_matcher * m, const double * starts_xyt, siz
 }
 
 ndt2d_starts * ndt2d_matcher_starts(ndt2d_matcher * m) { return m != nullptr ? m->starts : nullptr; }
+
+// Jobs the batched scan tracking launches at a time: the object's limit (a fleet is tens, a
+// replayed bag or a graph's scans hundreds to a few thousand).
+static constexpr size_t kScansSlots = 4096;
+
+int ndt2d_matcher_match_scans(ndt2d_matcher * m, const double * jobs_xyt, const uint32_t * job_scan, size_t n_jobs,
+                              const double * points_xy, const size_t * point_offsets, size_t n_scans, double * poses_out,
+                              double * covariances_out, double * scores_out, uint64_t * best_index_out,
+                              double * all_scores, size_t all_scores_cap, size_t * n_lattice_out)
+{
+  NDT2D_C_TRY
+  if (m == nullptr) return NDT2D_ERR_INVALID;
+  if (n_lattice_out != nullptr) *n_lattice_out = 0;
+  if (n_jobs == 0) return NDT2D_OK;
+  if (jobs_xyt == nullptr || scores_out == nullptr || point_offsets == nullptr)
+  {
+    return mfail(m, NDT2D_ERR_INVALID, "match_scans: null input");
+  }
+  if (n_jobs > (1u << 20) || n_scans > (1u << 20)) return mfail(m, NDT2D_ERR_INVALID, "match_scans: too many jobs or scans");
+  // `if (!ndt_) return 0.0;` (reference src/scan_matcher_ndt.cpp:80): outputs untouched
+  if (!m->have_ndt)
+  {
+    for (size_t k = 0; k < n_jobs; ++k)
+    {
+      scores_out[k] = 0.0;
+      if (best_index_out != nullptr) best_index_out[k] = NDT2D_NO_INDEX;
+    }
+    return NDT2D_OK;
+  }
+  if (job_scan == nullptr && n_scans != n_jobs)
+  {
+    return mfail(m, NDT2D_ERR_INVALID, "match_scans: no job_scan (job k uses scan k): n_scans must equal n_jobs");
+  }
+  for (size_t sc = 0; sc < n_scans; ++sc)
+  {
+    if (point_offsets[sc + 1] < point_offsets[sc])
+    {
+      return mfail(m, NDT2D_ERR_INVALID, "match_scans: scan " + std::to_string(sc) + ": point_offsets decrease");
+    }
+  }
+  if (n_scans > 0 && point_offsets[n_scans] > point_offsets[0] && points_xy == nullptr)
+  {
+    return mfail(m, NDT2D_ERR_INVALID, "match_scans: null input");
+  }
+  for (size_t k = 0; k < n_jobs; ++k)
+  {
+    if (!std::isfinite(jobs_xyt[3 * k]) || !std::isfinite(jobs_xyt[3 * k + 1]) || !std::isfinite(jobs_xyt[3 * k + 2]))
+    {
+      return mfail(m, NDT2D_ERR_INVALID, "match_scans: job " + std::to_string(k) + ": the pose is not finite");
+    }
+    if (job_scan != nullptr && job_scan[k] >= n_scans)
+    {
+      return mfail(m, NDT2D_ERR_INVALID, "match_scans: job " + std::to_string(k) + ": scan " + std::to_string(job_scan[k]) +
+                                             " of " + std::to_string(n_scans));
+    }
+  }
+  const size_t n_th = m->search.dth.size(), n_lin = m->search.dlin.size();
+  const size_t n_lattice = n_th * n_lin * n_lin;
+  if (n_lattice_out != nullptr) *n_lattice_out = n_lattice;
+  discard_ahead(m);   // a search launched ahead by scoreScan is waited out and dropped
+  if (m->scans == nullptr)
+  {
+    const int rc = ndt2d_scans_create(m->dev, kScansSlots, &m->scans);
+    if (rc != NDT2D_OK) return dev_fail(m, rc, "ndt2d_scans_create");
+  }
+  double * scores_ptr = (all_scores != nullptr && all_scores_cap / n_jobs >= n_lattice && n_lattice > 0) ? all_scores : nullptr;
+  const auto scan_of = [&](size_t k) { return job_scan != nullptr ? static_cast<size_t>(job_scan[k]) : k; };
+
+  // every scan a job names as matchScan takes it: subsampled beams (:95-96,110), once per scan.
+  // sent[s]: its index among the scans the batched call receives (a scan without points is not
+  // among them: its jobs go through the sequential call).
+  constexpr uint32_t kUnseen = ~0u, kEmpty = ~0u - 1u;
+  std::vector<uint32_t> sent(n_scans, kUnseen);
+  std::vector<double> beams, one;
+  std::vector<size_t> beam_offsets(1, 0);
+  std::vector<uint32_t> batch_job, batch_scan;   // the jobs of the batched call and their scans
+  for (size_t k = 0; k < n_jobs && n_lattice > 0; ++k)
+  {
+    const size_t sc = scan_of(k);
+    if (sent[sc] == kUnseen)
+    {
+      subsample_into(one, points_xy + 2 * point_offsets[sc], point_offsets[sc + 1] - point_offsets[sc], m->laser_max_beams);
+      if (one.empty())
+      {
+        sent[sc] = kEmpty;
+      }
+      else
+      {
+        sent[sc] = static_cast<uint32_t>(beam_offsets.size() - 1);
+        beams.insert(beams.end(), one.begin(), one.end());
+        beam_offsets.push_back(beams.size() / 2);
+      }
+    }
+    if (sent[sc] == kEmpty) continue;
+    batch_job.push_back(static_cast<uint32_t>(k));
+    batch_scan.push_back(sent[sc]);
+  }
+  m->search.ready = false;   // no search is prepared on the context
+  // No points: every candidate scores -0.0 and none is < 0; no candidates: the loops do not run.
+  // What the sequential call does with that is its to say.
+  std::vector<char> sequential(n_jobs, 1);
+  const size_t n_batch = batch_job.size();
+  m->scans_records.assign(n_batch * NDT2D_MATCH_RECORD_DOUBLES, 0.0);
+  std::vector<size_t> record_of(n_jobs, 0);
+  if (n_batch > 0)
+  {
+    // (all jobs in the batch: its scores are the caller's rows; else they are dealt out below)
+    std::vector<double> batch_scores, batch_xyt;
+    const double * xyt = jobs_xyt;
+    double * batch_scores_ptr = scores_ptr;
+    if (n_batch != n_jobs)
+    {
+      batch_xyt.resize(3 * n_batch);
+      for (size_t j = 0; j < n_batch; ++j) std::memcpy(&batch_xyt[3 * j], jobs_xyt + 3 * batch_job[j], 3 * sizeof(double));
+      xyt = batch_xyt.data();
+      if (scores_ptr != nullptr)
+      {
+        batch_scores.resize(n_batch * n_lattice);
+        batch_scores_ptr = batch_scores.data();
+      }
+    }
+    const int rc = ndt2d_scans_match(m->scans, xyt, batch_scan.data(), n_batch, beams.data(), beam_offsets.data(),
+                                     beam_offsets.size() - 1, m->search.dth.data(), n_th, m->search.dlin.data(), n_lin,
+                                     m->scans_records.data(), batch_scores_ptr);
+    if (rc != NDT2D_OK) return mfail(m, rc, std::string("match_scans: ") + ndt2d_scans_last_error(m->scans));
+    m->last_multi = false;
+    for (size_t j = 0; j < n_batch; ++j)
+    {
+      const size_t k = batch_job[j];
+      record_of[k] = j;
+      // a marked winner (index + 0.5): the job alone through the sequential call, whose adjudication settles it
+      const double bi = m->scans_records[j * NDT2D_MATCH_RECORD_DOUBLES + 1];
+      sequential[k] = (bi >= 0.0 && bi != std::floor(bi)) ? 1 : 0;
+      if (!batch_scores.empty() && !sequential[k])
+      {
+        std::memcpy(scores_ptr + k * n_lattice, &batch_scores[j * n_lattice], n_lattice * sizeof(double));
+      }
+    }
+  }
+  int rc = NDT2D_OK;
+  for (size_t k = 0; k < n_jobs && rc == NDT2D_OK; ++k)
+  {
+    double * pose_k = poses_out != nullptr ? poses_out + 3 * k : nullptr;
+    double * cov_k = covariances_out != nullptr ? covariances_out + 9 * k : nullptr;
+    const size_t sc = scan_of(k);
+    if (sequential[k])
+    {
+      rc = ndt2d_matcher_match_scan_ex(m, jobs_xyt + 3 * k, points_xy + 2 * point_offsets[sc],
+                                       point_offsets[sc + 1] - point_offsets[sc], pose_k, cov_k, scores_out + k,
+                                       scores_ptr != nullptr ? scores_ptr + k * n_lattice : nullptr, n_lattice, nullptr,
+                                       best_index_out != nullptr ? best_index_out + k : nullptr);
+      if (rc != NDT2D_OK) m->err = "match_scans: job " + std::to_string(k) + ": " + m->err;
+      continue;
+    }
+    const double * rec = m->scans_records.data() + record_of[k] * NDT2D_MATCH_RECORD_DOUBLES;
+    if (best_index_out != nullptr) best_index_out[k] = rec[1] < 0.0 ? NDT2D_NO_INDEX : static_cast<uint64_t>(rec[1]);
+    // the N of `best / N` (:148) is the job's own scan's
+    m->search.n_use = beam_offsets[sent[sc] + 1] - beam_offsets[sent[sc]];
+    m->search.ready = false;   // (a sequential call in between prepared a search of its own)
+    rc = ndt2d_matcher_finish_match(m, rec, pose_k, cov_k, scores_out + k);
+  }
+  return rc;
+  NDT2D_C_CATCH(m)
+}
+
+ndt2d_scans * ndt2d_matcher_scans(ndt2d_matcher * m) { return m != nullptr ? m->scans : nullptr; }
 
 int ndt2d_matcher_match_laser_scan(ndt2d_matcher * m, const double * scan_pose_xyt,
                                    const float * ranges, size_t n_ranges,

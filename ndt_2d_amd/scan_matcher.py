@@ -474,6 +474,72 @@ class ScanMatcherNDT:
             raise Ndt2dError(rc, "ndt2d_starts_last_ms")
         return a.value, b.value
 
+    def matchScans(self, jobs, scans, job_scan=None, want_scores=False):
+        """matchScan of K jobs -- (scan, pose) pairs -- against the NDT in place, in one call (one
+        upload, the search launches over job x lattice, one read-back): a fleet of robots on one
+        map, a recorded bag replayed against a loaded map, a graph's scans matched again after an
+        optimisation.  jobs: K poses; scans: a sequence of S point arrays; job_scan[k]: the scan
+        of job k (several jobs may share one), None: job k uses scan k.  Returns one dict per
+        job, the dict matchScan(jobs[k], scans[job_scan[k]]) returns: `pose` is (0, 0, 0) unless
+        a lattice candidate scores below 0, covariance is None when there is no NDT.  The NDT
+        stays in place."""
+        jp = _f64(jobs, (-1, 3))
+        K = len(jp)
+        arrays = [_f64(pts, (-1, 2)) for pts in scans]
+        offsets = np.zeros(len(arrays) + 1, dtype=np.uintp)
+        if arrays:
+            offsets[1:] = np.cumsum([len(a) for a in arrays])
+        pts = np.ascontiguousarray(np.concatenate(arrays) if arrays else np.zeros((0, 2)), dtype=np.float64)
+        js, js_ptr = None, None
+        if job_scan is not None:
+            js = np.ascontiguousarray(job_scan, dtype=np.int64).reshape(-1)
+            if len(js) != K:
+                raise ValueError("matchScans: job_scan must name one scan per job")
+            if np.any(js < 0) or np.any(js >= 2 ** 32):
+                raise ValueError("matchScans: job_scan must hold scan indices")
+            js = np.ascontiguousarray(js, dtype=np.uint32)
+            js_ptr = js.ctypes.data_as(C.POINTER(C.c_uint32))
+        poses_out = np.zeros((K, 3))
+        covs = np.full((K, 9), np.nan)
+        scores = np.zeros(K)
+        best = np.full(K, _capi.NO_INDEX, dtype=np.uint64)
+        n_lat = C.c_size_t(0)
+        all_scores, as_ptr, cap = None, None, 0
+        if want_scores:
+            p = self.params
+            n_th = len(search_offsets(p["search_angular_size"], p["search_angular_resolution"]))
+            n_lin = len(search_offsets(p["search_linear_size"], p["search_linear_resolution"]))
+            all_scores = np.zeros((K, n_th * n_lin * n_lin), dtype=np.float64)
+            as_ptr, cap = dptr(all_scores), all_scores.size
+        self._check(self._L.ndt2d_matcher_match_scans(
+            self._m, dptr(jp), js_ptr, K, dptr(pts), offsets.ctypes.data_as(C.POINTER(C.c_size_t)), len(arrays),
+            dptr(poses_out), dptr(covs), dptr(scores), best.ctypes.data_as(C.POINTER(C.c_uint64)), as_ptr, cap,
+            C.byref(n_lat)), "matchScans")
+        has = bool(self._L.ndt2d_matcher_has_ndt(self._m))
+        return [dict(score=float(scores[k]), pose=poses_out[k].copy(),
+                     covariance=covs[k].reshape(3, 3).copy() if has else None,
+                     n_candidates=n_lat.value, best_index=int(best[k]),
+                     scores=all_scores[k] if want_scores else None) for k in range(K)]
+
+    def scans_set_timing(self, enabled):
+        """HIP events around the batched scan tracking's search and reduce launches on / off (after
+        the first matchScans with an NDT in place: the object is made by it)."""
+        s = self._L.ndt2d_matcher_scans(self._m)
+        if not s:
+            raise Ndt2dError(_capi.ERR_STATE, "scans_set_timing", "no matchScans call yet")
+        rc = self._L.ndt2d_scans_set_timing(C.c_void_p(s), 1 if enabled else 0)
+        if rc != _capi.OK:
+            raise Ndt2dError(rc, "ndt2d_scans_set_timing")
+
+    def scans_last_ms(self):
+        """(search_ms, reduce_ms) of the last timed matchScans (its last chunk)."""
+        s = self._L.ndt2d_matcher_scans(self._m)
+        a, b = C.c_float(0.0), C.c_float(0.0)
+        rc = self._L.ndt2d_scans_last_ms(C.c_void_p(s), C.byref(a), C.byref(b)) if s else _capi.ERR_STATE
+        if rc != _capi.OK:
+            raise Ndt2dError(rc, "ndt2d_scans_last_ms")
+        return a.value, b.value
+
     def last_build(self):
         """How the NDT in place was built: "build/fused-small-map", "build/device", "build/host" or ""."""
         v = self._L.ndt2d_matcher_last_build(self._m)
@@ -906,3 +972,22 @@ def relocalize(matcher, points, start_poses, accept_below=None):
                                  covariance=res["covariance"])))
     ranked.sort(key=lambda e: e[0])
     return [entry for _, entry in ranked]
+
+
+def track_scans(matcher, jobs, scans, job_scan=None):
+    """Localisation by scan matching for many scans at once (reference src/ndt_mapper.cpp:547-566):
+    one matchScans call over the (scan, pose) jobs against the matcher's map.  Returns, in job
+    order, a list of dict(job = index into jobs, scan = index into scans, score, correction =
+    matchScan's pose output, pose = job pose + correction as the reference adds it (:557-561),
+    covariance).  A job without a winner (no lattice candidate below 0) keeps its pose."""
+    poses = np.array(jobs, dtype=np.float64).reshape(-1, 3)
+    if len(poses) == 0:
+        return []
+    which = np.arange(len(poses)) if job_scan is None else np.array(job_scan, dtype=np.int64).reshape(-1)
+    results = matcher.matchScans(poses, scans, job_scan=job_scan)
+    out = []
+    for k, res in enumerate(results):
+        correction = np.array(res["pose"], dtype=np.float64)
+        out.append(dict(job=k, scan=int(which[k]), score=float(res["score"]), correction=correction,
+                        pose=correction + poses[k], covariance=res["covariance"]))
+    return out
