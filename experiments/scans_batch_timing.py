@@ -1,7 +1,7 @@
 """Batched scan tracking against the K sequential matchScan calls (plugin defaults: 80 x 21 x 21
 lattice, 100 of 720 beams), on a 129 x 129 map and on the cfg-5 801 x 801 map (larger than LDS).
 
-    python experiments/scans_batch_timing.py
+    python experiments/scans_batch_timing.py [OUT.json]     # prints the table; writes profiles/scans_batch_timing.json or OUT.json
 
 For K in {1, 8, 64, 1024}: K distinct 720-beam scans, each matched from its own pose a few
 centimetres off where it was taken.  The median wall time of ScanMatcherNDT.matchScans and of K
@@ -105,7 +105,7 @@ def main():
     out = dict(experiment="scans_batch_timing", lattice="80 x 21 x 21", beams="100 of 720",
                note="median wall time of one matchScans call against K matchScan calls, same process and matcher",
                maps=[run(*fixture_map()), run(*cfg5_map())])
-    path = os.path.join(ROOT, "profiles", "scans_batch_timing.json")
+    path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "scans_batch_timing.json")
     with open(path, "w") as f:
         json.dump(out, f, indent=1)
         f.write("\n")

@@ -1,13 +1,14 @@
 """Batched match from K start poses against the K sequential matchScan calls (plugin defaults:
 80 x 21 x 21 lattice, 100 of 720 beams), on a 129 x 129 map and on the cfg-5 801 x 801 map.
 
-    python experiments/starts_batch_timing.py
+    python experiments/starts_batch_timing.py [OUT.json]     # prints the table; writes profiles/starts_batch_timing.json or OUT.json
 
 For K in {1, 8, 64, 512, 4096}: the median wall time of ScanMatcherNDT.matchStarts and of K
 matchScan calls (the same process, HIP events off; 20 repetitions after two warm-ups, 5 from
 K = 512 on), then -- events on -- the batched call's search and reduce launches
 (ndt2d_starts_last_ms; the last chunk of the call).  Start poses: the query's true pose first,
 the rest uniform over the room, every heading."""
+import json
 import math
 import os
 import sys
@@ -15,7 +16,8 @@ import time
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 
 from ndt_2d_amd import ScanMatcherNDT, synth  # noqa: E402
 
@@ -59,6 +61,7 @@ def run(name, scans, range_max, query, true_pose, half):
     rng = np.random.default_rng(20261018)
     print("map %s, %s" % (name, m.last_build()))
     print("K     batched_us  sequential_us  ratio  search_ms  reduce_ms")
+    rows = []
     for K in (1, 8, 64, 512, 4096):
         starts = np.empty((K, 3))
         starts[:, 0:2] = rng.uniform(-half, half, size=(K, 2))
@@ -82,11 +85,20 @@ def run(name, scans, range_max, query, true_pose, half):
         search_ms, reduce_ms = m.starts_last_ms()
         m.starts_set_timing(False)
         print("%-5d %10.1f %14.1f %6.2f %10.4f %10.4f" % (K, t_bat, t_seq, t_seq / t_bat, search_ms, reduce_ms), flush=True)
+        rows.append(dict(K=K, batched_us=t_bat, sequential_us=t_seq, repetitions=reps, search_ms=search_ms,
+                         reduce_ms=reduce_ms))
+    return dict(map=name, build=m.last_build(), rows=rows)
 
 
 def main():
-    run(*fixture_map())
-    run(*cfg5_map())
+    out = dict(experiment="starts_batch_timing", lattice="80 x 21 x 21", beams="100 of 720",
+               note="median wall time of one matchStarts call against K matchScan calls, same process and matcher",
+               maps=[run(*fixture_map()), run(*cfg5_map())])
+    path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "starts_batch_timing.json")
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print("wrote", path)
 
 
 if __name__ == "__main__":

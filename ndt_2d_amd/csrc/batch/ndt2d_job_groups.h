@@ -1,5 +1,5 @@
 // The jobs of one chunk of the batched scan tracking (scans/ndt2d_scans.hip) grouped by the number
-// C of partial sums their scan's beam count asks for (../closure/ndt2d_sum_chunks.h): C is a
+// C of partial sums their scan's beam count asks for (ndt2d_sum_chunks.h): C is a
 // template parameter of the lane's walk, so a chunk is searched with one launch per C present.
 // A group keeps its jobs in the caller's order (a stable counting sort), groups follow each other
 // by ascending C, and `position` maps a job back to its place in that launch order.  Records and
@@ -13,7 +13,7 @@
 
 #include <vector>
 
-#include "../closure/ndt2d_sum_chunks.h"
+#include "ndt2d_sum_chunks.h"
 
 namespace ndt2d
 {

@@ -1,4 +1,4 @@
-// The partial sums of a lattice candidate's score in the batched searches (closure/, starts/):
+// The partial sums of a lattice candidate's score in the batched searches (closure/, starts/, scans/):
 // the beam chunks of the small-lattice search's default plan (ndt2d_match_small.hip small_plan:
 // groups of four beams, chunks of five groups, at most eight chunks), a function of the beam
 // count alone.  Plain C++: host code and a stand-alone check include it without the HIP headers.

@@ -1,7 +1,8 @@
 // The lane of the batched searches (closure/ndt2d_closure.hip: one scan against K candidate maps;
-// starts/ndt2d_starts.hip: one scan from K start poses on the installed grid): a block per
-// (theta step, slot), a lane per (dx, dy).  What both kernels share lives here, so that a raw
-// score has the same bits whichever of them computes it:
+// starts/ndt2d_starts.hip: one scan from K start poses on the installed grid; scans/ndt2d_scans.hip:
+// K (scan, pose) jobs on the installed grid): a block per (theta step, slot), a lane per (dx, dy).
+// What the one search kernel (ndt2d_batch_search.h) is made of lives here, so that a raw score
+// has the same bits whichever of the three asks for it:
 //
 //   lane_walk      the block rotates the beams once for its theta step (points_outer,
 //                  src/scan_matcher_ndt.cpp:106-115) into LDS in pieces of kStageBeams; every lane

@@ -2274,6 +2274,39 @@ int ndt2d_matcher_match_scan(ndt2d_matcher * m, const double * scan_pose_xyt,
   NDT2D_C_CATCH(m)
 }
 
+// ---- what the three batched matches (candidates, starts, scans) share ----
+
+// `if (!ndt_) return 0.0;` (reference src/scan_matcher_ndt.cpp:80) for every slot: the other outputs untouched
+static void fill_no_ndt(size_t n, double * scores_out, uint64_t * best_index_out)
+{
+  for (size_t k = 0; k < n; ++k)
+  {
+    scores_out[k] = 0.0;
+    if (best_index_out != nullptr) best_index_out[k] = NDT2D_NO_INDEX;
+  }
+}
+
+// all_scores is filled only where it takes the lattice of every slot
+static double * scores_if_they_fit(double * all_scores, size_t all_scores_cap, size_t n_slots, size_t n_lattice)
+{
+  return (all_scores != nullptr && all_scores_cap / n_slots >= n_lattice && n_lattice > 0) ? all_scores : nullptr;
+}
+
+// A marked winner (index + 0.5): the slot goes alone through the sequential call, whose adjudication settles it.
+static bool marked_winner(const double * rec)
+{
+  const double bi = rec[1];
+  return bi >= 0.0 && bi != std::floor(bi);
+}
+
+// A slot's record -> its best index, pose, covariance and score.
+static int finish_slot(ndt2d_matcher * m, const double * rec, double * pose, double * covariance, double * score_out,
+                       uint64_t * best_index_out)
+{
+  if (best_index_out != nullptr) *best_index_out = rec[1] < 0.0 ? NDT2D_NO_INDEX : static_cast<uint64_t>(rec[1]);
+  return ndt2d_matcher_finish_match(m, rec, pose, covariance, score_out);
+}
+
 // Candidates the batched match launches at a time: the plugin's global_search_limit_ is a handful.
 static constexpr size_t kClosureSlots = 16;
 
@@ -2305,7 +2338,7 @@ int ndt2d_matcher_match_candidates(ndt2d_matcher * m, const double * scan_pose_x
     const int rc = ndt2d_closure_create(m->dev, m->stores[0], kClosureSlots, &m->closure);
     if (rc != NDT2D_OK) return dev_fail(m, rc, "ndt2d_closure_create");
   }
-  double * scores_ptr = (all_scores != nullptr && all_scores_cap / n_candidates >= n_lattice && n_lattice > 0) ? all_scores : nullptr;
+  double * scores_ptr = scores_if_they_fit(all_scores, all_scores_cap, n_candidates, n_lattice);
 
   // the scan as matchScan takes it: subsampled beams (:95-96,110), cos / sin per theta step (:106-107)
   subsample_into(m->beams.next, points_xy, n_points, m->laser_max_beams);
@@ -2339,13 +2372,7 @@ int ndt2d_matcher_match_candidates(ndt2d_matcher * m, const double * scan_pose_x
                                records, scores_ptr);
     }
     if (rc != NDT2D_OK) return mfail(m, rc, std::string("match_candidates: ") + ndt2d_closure_last_error(m->closure));
-    // a marked winner (index + 0.5): the candidate alone through the sequential calls, whose
-    // adjudication settles it
-    for (size_t k = 0; k < n_candidates; ++k)
-    {
-      const double bi = records[k * NDT2D_MATCH_RECORD_DOUBLES + 1];
-      sequential[k] = (bi >= 0.0 && bi != std::floor(bi)) ? 1 : 0;
-    }
+    for (size_t k = 0; k < n_candidates; ++k) sequential[k] = marked_winner(records + k * NDT2D_MATCH_RECORD_DOUBLES);
   }
   int rc = NDT2D_OK;
   for (size_t k = 0; k < n_candidates && rc == NDT2D_OK; ++k)
@@ -2366,9 +2393,8 @@ int ndt2d_matcher_match_candidates(ndt2d_matcher * m, const double * scan_pose_x
       if (rc != NDT2D_OK) m->err = "match_candidates: candidate " + std::to_string(k) + ": " + m->err;
       continue;
     }
-    const double * rec = records + k * NDT2D_MATCH_RECORD_DOUBLES;
-    if (best_index_out != nullptr) best_index_out[k] = rec[1] < 0.0 ? NDT2D_NO_INDEX : static_cast<uint64_t>(rec[1]);
-    rc = ndt2d_matcher_finish_match(m, rec, pose_k, cov_k, scores_out + k);
+    rc = finish_slot(m, records + k * NDT2D_MATCH_RECORD_DOUBLES, pose_k, cov_k, scores_out + k,
+                     best_index_out != nullptr ? best_index_out + k : nullptr);
   }
   // `global_scan_matcher_->reset()` (src/ndt_mapper.cpp:634): no NDT is left in place
   const int rrc = ndt2d_matcher_reset(m);
@@ -2396,14 +2422,9 @@ int ndt2d_matcher_match_starts(ndt2d_matcher * m, const double * starts_xyt, siz
     return mfail(m, NDT2D_ERR_INVALID, "match_starts: null input");
   }
   if (n_starts > (1u << 20)) return mfail(m, NDT2D_ERR_INVALID, "match_starts: too many starts");
-  // `if (!ndt_) return 0.0;` (reference src/scan_matcher_ndt.cpp:80): outputs untouched
   if (!m->have_ndt)
   {
-    for (size_t k = 0; k < n_starts; ++k)
-    {
-      scores_out[k] = 0.0;
-      if (best_index_out != nullptr) best_index_out[k] = NDT2D_NO_INDEX;
-    }
+    fill_no_ndt(n_starts, scores_out, best_index_out);
     return NDT2D_OK;
   }
   for (size_t k = 0; k < n_starts; ++k)
@@ -2422,7 +2443,7 @@ int ndt2d_matcher_match_starts(ndt2d_matcher * m, const double * starts_xyt, siz
     const int rc = ndt2d_starts_create(m->dev, kStartsSlots, &m->starts);
     if (rc != NDT2D_OK) return dev_fail(m, rc, "ndt2d_starts_create");
   }
-  double * scores_ptr = (all_scores != nullptr && all_scores_cap / n_starts >= n_lattice && n_lattice > 0) ? all_scores : nullptr;
+  double * scores_ptr = scores_if_they_fit(all_scores, all_scores_cap, n_starts, n_lattice);
 
   // the scan as matchScan takes it: subsampled beams (:95-96,110), once for every start
   subsample_into(m->beams.next, points_xy, n_points, m->laser_max_beams);
@@ -2445,12 +2466,7 @@ int ndt2d_matcher_match_starts(ndt2d_matcher * m, const double * starts_xyt, siz
                                       m->search.dlin.data(), n_lin, records, scores_ptr);
     if (rc != NDT2D_OK) return mfail(m, rc, std::string("match_starts: ") + ndt2d_starts_last_error(m->starts));
     m->last_multi = false;
-    // a marked winner (index + 0.5): the start alone through the sequential call, whose adjudication settles it
-    for (size_t k = 0; k < n_starts; ++k)
-    {
-      const double bi = records[k * NDT2D_MATCH_RECORD_DOUBLES + 1];
-      sequential[k] = (bi >= 0.0 && bi != std::floor(bi)) ? 1 : 0;
-    }
+    for (size_t k = 0; k < n_starts; ++k) sequential[k] = marked_winner(records + k * NDT2D_MATCH_RECORD_DOUBLES);
   }
   int rc = NDT2D_OK;
   for (size_t k = 0; k < n_starts && rc == NDT2D_OK; ++k)
@@ -2467,9 +2483,8 @@ int ndt2d_matcher_match_starts(ndt2d_matcher * m, const double * starts_xyt, siz
       m->search.n_use = use;
       continue;
     }
-    const double * rec = records + k * NDT2D_MATCH_RECORD_DOUBLES;
-    if (best_index_out != nullptr) best_index_out[k] = rec[1] < 0.0 ? NDT2D_NO_INDEX : static_cast<uint64_t>(rec[1]);
-    rc = ndt2d_matcher_finish_match(m, rec, pose_k, cov_k, scores_out + k);
+    rc = finish_slot(m, records + k * NDT2D_MATCH_RECORD_DOUBLES, pose_k, cov_k, scores_out + k,
+                     best_index_out != nullptr ? best_index_out + k : nullptr);
   }
   return rc;
   NDT2D_C_CATCH(m)
@@ -2495,14 +2510,9 @@ int ndt2d_matcher_match_scans(ndt2d_matcher * m, const double * jobs_xyt, const 
     return mfail(m, NDT2D_ERR_INVALID, "match_scans: null input");
   }
   if (n_jobs > (1u << 20) || n_scans > (1u << 20)) return mfail(m, NDT2D_ERR_INVALID, "match_scans: too many jobs or scans");
-  // `if (!ndt_) return 0.0;` (reference src/scan_matcher_ndt.cpp:80): outputs untouched
   if (!m->have_ndt)
   {
-    for (size_t k = 0; k < n_jobs; ++k)
-    {
-      scores_out[k] = 0.0;
-      if (best_index_out != nullptr) best_index_out[k] = NDT2D_NO_INDEX;
-    }
+    fill_no_ndt(n_jobs, scores_out, best_index_out);
     return NDT2D_OK;
   }
   if (job_scan == nullptr && n_scans != n_jobs)
@@ -2541,7 +2551,7 @@ int ndt2d_matcher_match_scans(ndt2d_matcher * m, const double * jobs_xyt, const 
     const int rc = ndt2d_scans_create(m->dev, kScansSlots, &m->scans);
     if (rc != NDT2D_OK) return dev_fail(m, rc, "ndt2d_scans_create");
   }
-  double * scores_ptr = (all_scores != nullptr && all_scores_cap / n_jobs >= n_lattice && n_lattice > 0) ? all_scores : nullptr;
+  double * scores_ptr = scores_if_they_fit(all_scores, all_scores_cap, n_jobs, n_lattice);
   const auto scan_of = [&](size_t k) { return job_scan != nullptr ? static_cast<size_t>(job_scan[k]) : k; };
 
   // every scan a job names as matchScan takes it: subsampled beams (:95-96,110), once per scan.
@@ -2606,9 +2616,7 @@ int ndt2d_matcher_match_scans(ndt2d_matcher * m, const double * jobs_xyt, const 
     {
       const size_t k = batch_job[j];
       record_of[k] = j;
-      // a marked winner (index + 0.5): the job alone through the sequential call, whose adjudication settles it
-      const double bi = m->scans_records[j * NDT2D_MATCH_RECORD_DOUBLES + 1];
-      sequential[k] = (bi >= 0.0 && bi != std::floor(bi)) ? 1 : 0;
+      sequential[k] = marked_winner(&m->scans_records[j * NDT2D_MATCH_RECORD_DOUBLES]);
       if (!batch_scores.empty() && !sequential[k])
       {
         std::memcpy(scores_ptr + k * n_lattice, &batch_scores[j * n_lattice], n_lattice * sizeof(double));
@@ -2630,12 +2638,11 @@ int ndt2d_matcher_match_scans(ndt2d_matcher * m, const double * jobs_xyt, const 
       if (rc != NDT2D_OK) m->err = "match_scans: job " + std::to_string(k) + ": " + m->err;
       continue;
     }
-    const double * rec = m->scans_records.data() + record_of[k] * NDT2D_MATCH_RECORD_DOUBLES;
-    if (best_index_out != nullptr) best_index_out[k] = rec[1] < 0.0 ? NDT2D_NO_INDEX : static_cast<uint64_t>(rec[1]);
     // the N of `best / N` (:148) is the job's own scan's
     m->search.n_use = beam_offsets[sent[sc] + 1] - beam_offsets[sent[sc]];
     m->search.ready = false;   // (a sequential call in between prepared a search of its own)
-    rc = ndt2d_matcher_finish_match(m, rec, pose_k, cov_k, scores_out + k);
+    rc = finish_slot(m, m->scans_records.data() + record_of[k] * NDT2D_MATCH_RECORD_DOUBLES, pose_k, cov_k, scores_out + k,
+                     best_index_out != nullptr ? best_index_out + k : nullptr);
   }
   return rc;
   NDT2D_C_CATCH(m)

@@ -1,6 +1,6 @@
 // The device layer's translation unit -- ../ndt2d_device.hip, included whole and unchanged -- plus
 // one read-only accessor to the grid installed in the context, for kernels that live beside the
-// context (ndt2d_starts.hip).  The context struct is private to ndt2d_device.hip and stays there;
+// context (../batch/ndt2d_batch_host.h installed_grid: starts/, scans/).  The context struct is private to ndt2d_device.hip and stays there;
 // the accessor has to be compiled with it to see it.  It is kept out of that file because the
 // committed profiles (profiles/r06_pmc.json, r06_valu_mix.json) carry the hash of the top-level
 // kernel sources they were taken with (bench.py source_hash): an accessor is no kernel edit and

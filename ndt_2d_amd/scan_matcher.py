@@ -46,6 +46,34 @@ def _pack_scans(scans):
     return poses, allpts, offsets
 
 
+class _BatchResults:
+    """What the three batched matches (matchCandidates, matchStarts, matchScans) write per slot --
+    pose, covariance, score, best index, optionally the lattice's raw scores -- and the list of
+    result dicts made of it.  `args`: the trailing arguments of the C call."""
+
+    def __init__(self, params, K, want_scores, best_fill=_capi.NO_INDEX):
+        self.K = K
+        self.poses = np.zeros((K, 3))
+        self.covs = np.full((K, 9), np.nan)
+        self.scores = np.zeros(K)
+        self.best = np.full(K, best_fill, dtype=np.uint64)
+        self.n_lat = C.c_size_t(0)
+        self.all_scores, as_ptr, cap = None, None, 0
+        if want_scores:
+            n_th = len(search_offsets(params["search_angular_size"], params["search_angular_resolution"]))
+            n_lin = len(search_offsets(params["search_linear_size"], params["search_linear_resolution"]))
+            self.all_scores = np.zeros((K, n_th * n_lin * n_lin), dtype=np.float64)
+            as_ptr, cap = dptr(self.all_scores), self.all_scores.size
+        self.args = (dptr(self.poses), dptr(self.covs), dptr(self.scores), self.best.ctypes.data_as(C.POINTER(C.c_uint64)),
+                     as_ptr, cap, C.byref(self.n_lat))
+
+    def dicts(self, has_ndt):
+        return [dict(score=float(self.scores[k]), pose=self.poses[k].copy(),
+                     covariance=self.covs[k].reshape(3, 3).copy() if has_ndt else None,
+                     n_candidates=self.n_lat.value, best_index=int(self.best[k]),
+                     scores=self.all_scores[k] if self.all_scores is not None else None) for k in range(self.K)]
+
+
 BUILD_SEQUENTIAL = 1      # include/ndt2d_hip.h NDT2D_BUILD_SEQUENTIAL
 BUILD_CLOSED_FORM = 2     # NDT2D_BUILD_CLOSED_FORM
 
@@ -386,44 +414,38 @@ class ScanMatcherNDT:
         flat = [entry for c in candidates for entry in c]
         ids = np.ascontiguousarray([e[0] for e in flat], dtype=np.uint64).reshape(-1)
         poses = _f64([e[1] for e in flat], (-1, 3)) if flat else np.zeros((0, 3))
-        poses_out = np.zeros((K, 3))
-        covs = np.full((K, 9), np.nan)
-        scores = np.zeros(K)
-        best = np.zeros(K, dtype=np.uint64)
-        n_lat = C.c_size_t(0)
-        all_scores, as_ptr, cap = None, None, 0
-        if want_scores:
-            p = self.params
-            n_th = len(search_offsets(p["search_angular_size"], p["search_angular_resolution"]))
-            n_lin = len(search_offsets(p["search_linear_size"], p["search_linear_resolution"]))
-            all_scores = np.zeros((K, n_th * n_lin * n_lin), dtype=np.float64)
-            as_ptr, cap = dptr(all_scores), all_scores.size
+        out = _BatchResults(self.params, K, want_scores, best_fill=0)
         self._check(self._L.ndt2d_matcher_match_candidates(
             self._m, dptr(sp), dptr(pts), len(pts), offsets.ctypes.data_as(C.POINTER(C.c_size_t)),
-            ids.ctypes.data_as(C.POINTER(C.c_size_t)), dptr(poses), K, dptr(poses_out), dptr(covs), dptr(scores),
-            best.ctypes.data_as(C.POINTER(C.c_uint64)), as_ptr, cap, C.byref(n_lat)), "matchCandidates")
-        return [dict(score=float(scores[k]), pose=poses_out[k].copy(), covariance=covs[k].reshape(3, 3).copy(),
-                     n_candidates=n_lat.value, best_index=int(best[k]),
-                     scores=all_scores[k] if want_scores else None) for k in range(K)]
+            ids.ctypes.data_as(C.POINTER(C.c_size_t)), dptr(poses), K, *out.args), "matchCandidates")
+        return out.dicts(has_ndt=True)
+
+    def _batch_set_timing(self, noun, call, enabled):
+        """ndt2d_<noun>_set_timing on the matcher's batched-match object, which `call` makes."""
+        obj = getattr(self._L, "ndt2d_matcher_" + noun)(self._m)
+        if not obj:
+            raise Ndt2dError(_capi.ERR_STATE, noun + "_set_timing", "no %s call yet" % call)
+        rc = getattr(self._L, "ndt2d_%s_set_timing" % noun)(C.c_void_p(obj), 1 if enabled else 0)
+        if rc != _capi.OK:
+            raise Ndt2dError(rc, "ndt2d_%s_set_timing" % noun)
+
+    def _batch_last_ms(self, noun):
+        """The two times of ndt2d_<noun>_last_ms on the matcher's batched-match object."""
+        obj = getattr(self._L, "ndt2d_matcher_" + noun)(self._m)
+        a, b = C.c_float(0.0), C.c_float(0.0)
+        rc = getattr(self._L, "ndt2d_%s_last_ms" % noun)(C.c_void_p(obj), C.byref(a), C.byref(b)) if obj else _capi.ERR_STATE
+        if rc != _capi.OK:
+            raise Ndt2dError(rc, "ndt2d_%s_last_ms" % noun)
+        return a.value, b.value
 
     def closure_set_timing(self, enabled):
         """HIP events around the batched match's build and search launches on / off
         (after the first matchCandidates: the closure object is made by it)."""
-        c = self._L.ndt2d_matcher_closure(self._m)
-        if not c:
-            raise Ndt2dError(_capi.ERR_STATE, "closure_set_timing", "no matchCandidates call yet")
-        rc = self._L.ndt2d_closure_set_timing(C.c_void_p(c), 1 if enabled else 0)
-        if rc != _capi.OK:
-            raise Ndt2dError(rc, "ndt2d_closure_set_timing")
+        self._batch_set_timing("closure", "matchCandidates", enabled)
 
     def closure_last_ms(self):
         """(build_ms, search_ms) of the last timed matchCandidates (its last chunk)."""
-        c = self._L.ndt2d_matcher_closure(self._m)
-        b, s = C.c_float(0.0), C.c_float(0.0)
-        rc = self._L.ndt2d_closure_last_ms(C.c_void_p(c), C.byref(b), C.byref(s)) if c else _capi.ERR_STATE
-        if rc != _capi.OK:
-            raise Ndt2dError(rc, "ndt2d_closure_last_ms")
-        return b.value, s.value
+        return self._batch_last_ms("closure")
 
     def matchStarts(self, start_poses, points, want_scores=False):
         """matchScan of one scan from K start poses against the NDT in place, in one call (one
@@ -434,45 +456,19 @@ class ScanMatcherNDT:
         sp = _f64(start_poses, (-1, 3))
         pts = _f64(points, (-1, 2))
         K = len(sp)
-        poses_out = np.zeros((K, 3))
-        covs = np.full((K, 9), np.nan)
-        scores = np.zeros(K)
-        best = np.full(K, _capi.NO_INDEX, dtype=np.uint64)
-        n_lat = C.c_size_t(0)
-        all_scores, as_ptr, cap = None, None, 0
-        if want_scores:
-            p = self.params
-            n_th = len(search_offsets(p["search_angular_size"], p["search_angular_resolution"]))
-            n_lin = len(search_offsets(p["search_linear_size"], p["search_linear_resolution"]))
-            all_scores = np.zeros((K, n_th * n_lin * n_lin), dtype=np.float64)
-            as_ptr, cap = dptr(all_scores), all_scores.size
+        out = _BatchResults(self.params, K, want_scores)
         self._check(self._L.ndt2d_matcher_match_starts(
-            self._m, dptr(sp), K, dptr(pts), len(pts), dptr(poses_out), dptr(covs), dptr(scores),
-            best.ctypes.data_as(C.POINTER(C.c_uint64)), as_ptr, cap, C.byref(n_lat)), "matchStarts")
-        has = bool(self._L.ndt2d_matcher_has_ndt(self._m))
-        return [dict(score=float(scores[k]), pose=poses_out[k].copy(),
-                     covariance=covs[k].reshape(3, 3).copy() if has else None,
-                     n_candidates=n_lat.value, best_index=int(best[k]),
-                     scores=all_scores[k] if want_scores else None) for k in range(K)]
+            self._m, dptr(sp), K, dptr(pts), len(pts), *out.args), "matchStarts")
+        return out.dicts(has_ndt=bool(self._L.ndt2d_matcher_has_ndt(self._m)))
 
     def starts_set_timing(self, enabled):
         """HIP events around the batched match's search and reduce launches on / off (after the
         first matchStarts with an NDT in place: the object is made by it)."""
-        s = self._L.ndt2d_matcher_starts(self._m)
-        if not s:
-            raise Ndt2dError(_capi.ERR_STATE, "starts_set_timing", "no matchStarts call yet")
-        rc = self._L.ndt2d_starts_set_timing(C.c_void_p(s), 1 if enabled else 0)
-        if rc != _capi.OK:
-            raise Ndt2dError(rc, "ndt2d_starts_set_timing")
+        self._batch_set_timing("starts", "matchStarts", enabled)
 
     def starts_last_ms(self):
         """(search_ms, reduce_ms) of the last timed matchStarts (its last chunk)."""
-        s = self._L.ndt2d_matcher_starts(self._m)
-        a, b = C.c_float(0.0), C.c_float(0.0)
-        rc = self._L.ndt2d_starts_last_ms(C.c_void_p(s), C.byref(a), C.byref(b)) if s else _capi.ERR_STATE
-        if rc != _capi.OK:
-            raise Ndt2dError(rc, "ndt2d_starts_last_ms")
-        return a.value, b.value
+        return self._batch_last_ms("starts")
 
     def matchScans(self, jobs, scans, job_scan=None, want_scores=False):
         """matchScan of K jobs -- (scan, pose) pairs -- against the NDT in place, in one call (one
@@ -499,46 +495,20 @@ class ScanMatcherNDT:
                 raise ValueError("matchScans: job_scan must hold scan indices")
             js = np.ascontiguousarray(js, dtype=np.uint32)
             js_ptr = js.ctypes.data_as(C.POINTER(C.c_uint32))
-        poses_out = np.zeros((K, 3))
-        covs = np.full((K, 9), np.nan)
-        scores = np.zeros(K)
-        best = np.full(K, _capi.NO_INDEX, dtype=np.uint64)
-        n_lat = C.c_size_t(0)
-        all_scores, as_ptr, cap = None, None, 0
-        if want_scores:
-            p = self.params
-            n_th = len(search_offsets(p["search_angular_size"], p["search_angular_resolution"]))
-            n_lin = len(search_offsets(p["search_linear_size"], p["search_linear_resolution"]))
-            all_scores = np.zeros((K, n_th * n_lin * n_lin), dtype=np.float64)
-            as_ptr, cap = dptr(all_scores), all_scores.size
+        out = _BatchResults(self.params, K, want_scores)
         self._check(self._L.ndt2d_matcher_match_scans(
             self._m, dptr(jp), js_ptr, K, dptr(pts), offsets.ctypes.data_as(C.POINTER(C.c_size_t)), len(arrays),
-            dptr(poses_out), dptr(covs), dptr(scores), best.ctypes.data_as(C.POINTER(C.c_uint64)), as_ptr, cap,
-            C.byref(n_lat)), "matchScans")
-        has = bool(self._L.ndt2d_matcher_has_ndt(self._m))
-        return [dict(score=float(scores[k]), pose=poses_out[k].copy(),
-                     covariance=covs[k].reshape(3, 3).copy() if has else None,
-                     n_candidates=n_lat.value, best_index=int(best[k]),
-                     scores=all_scores[k] if want_scores else None) for k in range(K)]
+            *out.args), "matchScans")
+        return out.dicts(has_ndt=bool(self._L.ndt2d_matcher_has_ndt(self._m)))
 
     def scans_set_timing(self, enabled):
         """HIP events around the batched scan tracking's search and reduce launches on / off (after
         the first matchScans with an NDT in place: the object is made by it)."""
-        s = self._L.ndt2d_matcher_scans(self._m)
-        if not s:
-            raise Ndt2dError(_capi.ERR_STATE, "scans_set_timing", "no matchScans call yet")
-        rc = self._L.ndt2d_scans_set_timing(C.c_void_p(s), 1 if enabled else 0)
-        if rc != _capi.OK:
-            raise Ndt2dError(rc, "ndt2d_scans_set_timing")
+        self._batch_set_timing("scans", "matchScans", enabled)
 
     def scans_last_ms(self):
         """(search_ms, reduce_ms) of the last timed matchScans (its last chunk)."""
-        s = self._L.ndt2d_matcher_scans(self._m)
-        a, b = C.c_float(0.0), C.c_float(0.0)
-        rc = self._L.ndt2d_scans_last_ms(C.c_void_p(s), C.byref(a), C.byref(b)) if s else _capi.ERR_STATE
-        if rc != _capi.OK:
-            raise Ndt2dError(rc, "ndt2d_scans_last_ms")
-        return a.value, b.value
+        return self._batch_last_ms("scans")
 
     def last_build(self):
         """How the NDT in place was built: "build/fused-small-map", "build/device", "build/host" or ""."""

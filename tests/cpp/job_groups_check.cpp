@@ -1,5 +1,5 @@
 // Host-only check of the grouping of a chunk's jobs by their number of partial sums
-// (ndt_2d_amd/csrc/scans/ndt2d_job_groups.h): the group table, the stable order within a group,
+// (ndt_2d_amd/csrc/batch/ndt2d_job_groups.h): the group table, the stable order within a group,
 // the table that maps a job back to its launch position, and the C of the beam counts the tests
 // use, worked out by hand and cross-checked against sum_chunks.
 #include <cstdint>

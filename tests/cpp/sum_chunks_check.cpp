@@ -1,4 +1,4 @@
-// Host-only check of the chunk plan the batched searches share (ndt_2d_amd/csrc/closure/ndt2d_sum_chunks.h):
+// Host-only check of the chunk plan the batched searches share (ndt_2d_amd/csrc/batch/ndt2d_sum_chunks.h):
 // the values worked out by hand from the small-lattice search's default plan (groups of four beams,
 // chunks of five groups, at most eight chunks) at the beam counts the tests use, and -- for every
 // count up to 4,096 -- the plan transcribed from ndt2d_match_small.hip small_plan.

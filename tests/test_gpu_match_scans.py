@@ -5,7 +5,7 @@ own beams -- in one upload, the search launches, one reduce launch and one read-
 The yardstick of every test is the sequential matchScan per job on the same matcher and, for
 the parity test, the CPU oracle.  Raw scores are compared bit for bit where the sequential path
 runs the small-lattice search with its default plan (a lane of the batched search keeps that
-search's partial sums, closure/ndt2d_walk_fn.h); elsewhere, and for the covariance throughout,
+search's partial sums, batch/ndt2d_walk_fn.h); elsewhere, and for the covariance throughout,
 the bounds are those of tests/test_gpu_match_starts.py (_check_all / _same_as_sequential), whose
 45-scan fixture and SMALL lattice are the base here."""
 import ctypes as C

@@ -257,6 +257,40 @@ def test_edges_one_theta_step_and_one_beam(fixture):
     _check_all(m, got, _sequential(m, sel, one_beam))
 
 
+ONE_ENGINE = STARTS[[0, 2, 7, 9, 11]]   # five starts, [7] off the map
+THREE_STEPS = dict(search_angular_size=0.025, search_angular_resolution=0.02)   # 3 x 7 x 7
+
+
+@pytest.mark.parametrize("max_beams", [100, 21])   # C = 5 and C = 2 partial sums
+def test_starts_are_jobs_of_one_scan(fixture, max_beams):
+    """matchStarts runs on the scan tracking's engine with one scan that every job names: the
+    two calls give the same bits, covariance included."""
+    m = _matcher(fixture, laser_max_beams=max_beams, **THREE_STEPS)
+    query = fixture["query"]
+    as_starts = m.matchStarts(ONE_ENGINE, query, want_scores=True)
+    as_jobs = m.matchScans(ONE_ENGINE, [query], job_scan=[0] * 5, want_scores=True)
+    assert len(as_starts) == len(as_jobs) == 5 and as_starts[0]["n_candidates"] == 3 * 7 * 7
+    assert as_starts[2]["best_index"] == NO_INDEX and as_starts[0]["best_index"] != NO_INDEX
+    for s, j in zip(as_starts, as_jobs):
+        print("score %.17g (start) %.17g (job), best index %d %d" % (s["score"], j["score"], s["best_index"], j["best_index"]))
+        assert np.array_equal(s["score"], j["score"]) and s["best_index"] == j["best_index"]
+        assert np.array_equal(s["pose"], j["pose"]) and np.array_equal(s["scores"], j["scores"])
+        assert np.array_equal(s["covariance"], j["covariance"], equal_nan=True)
+
+
+def test_starts_object_in_chunks_equals_the_scans_object(fixture):
+    """ndt2d_starts_match through 2 slots (chunks of 2, 2 and 1 starts) against ndt2d_scans_match
+    through 16: the same records and scores."""
+    from test_gpu_match_scans import _scans_records
+    m = _matcher(fixture, **THREE_STEPS)
+    query = fixture["query"]
+    starts = _starts_records(m, query, ONE_ENGINE, slots=2)
+    jobs = _scans_records(m, ONE_ENGINE, [query], [0] * 5, slots=16)
+    assert starts[0].shape == (5, 12) and starts[1].shape == (5, 3 * 7 * 7)
+    assert np.array_equal(starts[0], jobs[0], equal_nan=True) and np.array_equal(starts[1], jobs[1])
+    assert starts[0][0, 0] < 0.0 and starts[0][2, 0] == 0.0   # (a start beside the truth scores; the one off the map does not)
+
+
 def test_edges_more_beams_than_one_staging_piece(fixture):
     """1,500 beams: the search block rotates them into LDS in two pieces of 1,024."""
     long_scan = synth.scan(fixture["world"], TRUE_POSE, 9200, n_beams=1500)

@@ -44,21 +44,45 @@ def test_job_groups_under_the_sanitizers(tmp_path):
     exe = os.path.join(str(tmp_path), "job_groups_check")
     subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror",
                            "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-I",
-                           os.path.join(ROOT, "ndt_2d_amd", "csrc", "scans"),
+                           os.path.join(ROOT, "ndt_2d_amd", "csrc", "batch"),
                            os.path.join(ROOT, "tests", "cpp", "job_groups_check.cpp"), "-o", exe])
     done = subprocess.run([exe], capture_output=True, text=True)
     assert done.returncode == 0, done.stdout + done.stderr
     assert done.stdout.rstrip().endswith("OK") and "FAILED" not in done.stdout and not done.stderr, done.stdout + done.stderr
     for beams, chunks in ((1, 1), (20, 1), (21, 2), (60, 3), (80, 4), (100, 5), (120, 6), (140, 7), (160, 8), (720, 8)):
         assert "beams %d: C %d (expected %d)" % (beams, chunks, chunks) in done.stdout
-    # the search takes the plan, the walk and the grouping from the shared headers and keeps no copy
-    text = open(os.path.join(ROOT, "ndt_2d_amd", "csrc", "scans", "ndt2d_scans.hip")).read()
-    assert '#include "../closure/ndt2d_walk_fn.h"\n' in text and '#include "ndt2d_job_groups.h"\n' in text
-    assert "group_jobs(" in text and "lane_walk<C, POW2>(" in text
+    # the search takes the plan, the walk, the kernel and the grouping from the shared headers and keeps
+    # no copy (tests/test_starts_host.py looks at what the three units must not contain)
+    csrc = os.path.join(ROOT, "ndt_2d_amd", "csrc")
+    text = open(os.path.join(csrc, "scans", "ndt2d_scans.hip")).read()
+    assert '#include "batch/ndt2d_batch_search.h"\n' in text and '#include "batch/ndt2d_batch_host.h"\n' in text
+    assert "group_jobs(" in text and "launch_batch_search(" in text and "stage_layout(" in text
     assert "uint32_t sum_chunks" not in text and "void add_beam" not in text
+    kernel = open(os.path.join(csrc, "batch", "ndt2d_batch_search.h")).read()
+    assert '#include "ndt2d_walk_fn.h"\n' in kernel and "lane_walk<C, POW2>(" in kernel
+    host = open(os.path.join(csrc, "batch", "ndt2d_batch_host.h")).read()
+    assert '#include "ndt2d_job_groups.h"\n' in host
     from ndt_2d_amd import build
     assert "scans/ndt2d_scans.hip" in build.SOURCES
-    assert any(h.endswith(os.path.join("scans", "ndt2d_job_groups.h")) for h in build.HEADERS)
+    for name in os.listdir(os.path.join(csrc, "batch")):
+        assert os.path.join(csrc, "batch", name) in build.HEADERS, name
+
+
+def test_stage_layout_under_the_sanitizers(tmp_path):
+    """tests/cpp/stage_layout_check.cpp: a program of its own, built with the host compiler and
+    -fsanitize=address,undefined (the sanitizer's runtime linked into the program), run directly."""
+    exe = os.path.join(str(tmp_path), "stage_layout_check")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror",
+                           "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-I",
+                           os.path.join(ROOT, "ndt_2d_amd", "csrc", "batch"),
+                           os.path.join(ROOT, "tests", "cpp", "stage_layout_check.cpp"), "-o", exe])
+    done = subprocess.run([exe], capture_output=True, text=True)
+    assert done.returncode == 0, done.stdout + done.stderr
+    assert done.stdout.rstrip().endswith("OK") and "FAILED" not in done.stdout and not done.stderr, done.stdout + done.stderr
+    assert "144 cases" in done.stdout
+    # the engine takes its offsets from there and computes none itself
+    text = open(os.path.join(ROOT, "ndt_2d_amd", "csrc", "scans", "ndt2d_scans.hip")).read()
+    assert "stage_layout(" in text and "off_beams" not in text and "& ~size_t(1)" not in text
 
 
 def test_entry_points_refuse_null_arguments_without_a_device():

@@ -42,17 +42,37 @@ def test_relocalize_hip_header_compiles():
 def test_shared_chunk_plan_gives_the_closure_plans_values(tmp_path):
     exe = os.path.join(str(tmp_path), "sum_chunks_check")
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I",
-                           os.path.join(ROOT, "ndt_2d_amd", "csrc", "closure"),
+                           os.path.join(ROOT, "ndt_2d_amd", "csrc", "batch"),
                            os.path.join(ROOT, "tests", "cpp", "sum_chunks_check.cpp"), "-o", exe])
     done = subprocess.run([exe], capture_output=True, text=True)
     assert done.returncode == 0, done.stdout + done.stderr
     for beams, chunks in ((1, 1), (4, 1), (5, 1), (100, 5), (720, 8), (1500, 8)):
         assert "beams %d: chunks %d (expected %d)" % (beams, chunks, chunks) in done.stdout
-    # both batched searches take the plan and the walk from the shared headers, neither keeps a copy
-    for unit in ("closure/ndt2d_closure.hip", "starts/ndt2d_starts.hip"):
-        text = open(os.path.join(ROOT, "ndt_2d_amd", "csrc", unit)).read()
-        assert 'ndt2d_walk_fn.h"\n' in text and "sum_chunks(" in text
-        assert "uint32_t sum_chunks" not in text and "void add_beam" not in text
+    # the three batched searches take the plan, the walk, the kernels, the launch switch and the host
+    # scaffolding from csrc/batch/; none keeps a copy of any of it
+    csrc = os.path.join(ROOT, "ndt_2d_amd", "csrc")
+    shared = "".join(open(os.path.join(csrc, "batch", name)).read() for name in
+                     ("ndt2d_walk_fn.h", "ndt2d_sum_chunks.h", "ndt2d_batch_search.h", "ndt2d_batch_host.h"))
+    for once in ("uint32_t sum_chunks(", "void add_beam(", "void lane_take(", "void block_record(", "batch_search_kernel(",
+                 "batch_reduce_kernel(", "switch (chunks)", "struct InstalledMap", "hipHostMalloc(", "hipEventCreate("):
+        assert shared.count(once) == 1, once
+    for unit in ("closure/ndt2d_closure.hip", "starts/ndt2d_starts.hip", "scans/ndt2d_scans.hip"):
+        text = open(os.path.join(csrc, unit)).read()
+        code = re.sub(r"//[^\n]*", "", text)
+        assert '#include "batch/ndt2d_batch_search.h"\n' in text, unit
+        assert "uint32_t sum_chunks" not in code and "void add_beam" not in code, unit
+        for copied in ("lane_take(", "block_record<", "hipHostMalloc", "hipEventCreate", "switch (chunks)",
+                       "struct InstalledMap"):
+            assert copied not in code, (unit, copied)
+        # no kernel of its own, save the loop closure's build
+        own = code.count("__global__")
+        assert own == (1 if unit.startswith("closure") else 0) and ("closure_build_kernel(" in code) == (own == 1), unit
+    # the start poses run as jobs of the scan tracking's engine
+    starts = open(os.path.join(csrc, "starts", "ndt2d_starts.hip")).read()
+    assert "match_jobs(" in starts and "hipLaunchKernelGGL" not in starts and "hipMemcpyAsync" not in starts
+    from ndt_2d_amd import build
+    for name in os.listdir(os.path.join(csrc, "batch")):
+        assert os.path.join(csrc, "batch", name) in build.HEADERS, name
 
 
 def test_entry_points_refuse_null_arguments_without_a_device():
