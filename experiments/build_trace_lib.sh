@@ -10,5 +10,8 @@ for f in ndt2d_kernels ndt2d_match_lane ndt2d_match_small ndt2d_poses_compact nd
   fi
 done
 wait
-g++ -O3 -std=c++17 -ffp-contract=off -fPIC -I $R/include -I $R/ndt_2d_amd/csrc -c $R/ndt_2d_amd/csrc/ndt2d_host.cpp -o $R/experiments/bin/trace_obj/ndt2d_host.o
+# (the host side: ndt2d_host.cpp and the units under csrc/host/, by the host compiler)
+for f in ndt2d_host host/ndt2d_host_ndt host/ndt2d_multi host/ndt2d_batched host/ndt2d_kld host/ndt2d_synth; do
+  g++ -O3 -std=c++17 -ffp-contract=off -fPIC -I $R/include -I $R/ndt_2d_amd/csrc -c $R/ndt_2d_amd/csrc/$f.cpp -o $R/experiments/bin/trace_obj/$(basename $f).o
+done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $R/experiments/bin/trace_obj/*.o $R/ndt_2d_amd/csrc/ndt2d_build_info.o -ldl -lpthread -o $R/experiments/bin/trace.so

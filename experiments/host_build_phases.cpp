@@ -1,9 +1,10 @@
-// Where the host side of addScans goes, phase by phase (the matcher layer compiled into this program):
+// Where the host side of addScans goes, phase by phase (the host NDT build compiled into this program):
 //   g++ -O3 -std=c++17 -ffp-contract=off -I include -I ndt_2d_amd/csrc experiments/host_build_phases.cpp -L ndt_2d_amd -lndt2d_hip -Wl,-rpath,$PWD/ndt_2d_amd -o experiments/bin/host_build_phases
 //   experiments/bin/host_build_phases 1   (toy map)   |   0   (245 x 245 grid)
-#include "../ndt_2d_amd/csrc/ndt2d_host.cpp"
+#include "../ndt_2d_amd/csrc/host/ndt2d_host_ndt.cpp"
 #include <chrono>
 #include <cstdio>
+using namespace ndt2d::host;
 static double now_us() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 int main(int argc, char ** argv)
 {

@@ -1147,7 +1147,7 @@ int ndt2d_host_build_grid(double ndt_resolution, double range_max, const double 
                           uint32_t * size_y, double * origin_x, double * origin_y);
 /* ... with flags: NDT2D_BUILD_SEQUENTIAL adds every scan's points one after the other, the
  * reference's loop as it stands (src/ndt_model.cpp:132-152), instead of the four quarters of a
- * scan side by side (csrc/ndt2d_host.cpp HostNdt::add_scan) -- the two give the same bits, and
+ * scan side by side (csrc/host/ndt2d_host_ndt.cpp HostNdt::add_scan) -- the two give the same bits, and
  * tests/test_host_logic.py holds them to it; NDT2D_BUILD_CLOSED_FORM takes the closed-form
  * eigenvalues (ndt2d_matcher_set_eigenvalue_form "closed").
  *
@@ -1163,7 +1163,7 @@ int ndt2d_host_build_grid(double ndt_resolution, double range_max, const double 
  * Such a point adds nothing to a cell and +0.0 to a likelihood (src/ndt_model.cpp:169), as any
  * finite point off the grid does.  The device scorers send it to a sentinel record whose arithmetic
  * would make a NaN or infinite beam NaN, so the matcher layer hands such beams on as finite far
- * points: a beam with a coordinate outside +-1e200 m as (-1e300, -1e300) (csrc/ndt2d_host.cpp
+ * points: a beam with a coordinate outside +-1e200 m as (-1e300, -1e300) (csrc/host/ndt2d_host_ndt.cpp
  * subsample_into), and for ndt2d_matcher_match_laser_scan, which converts and subsamples on the
  * device, a kept infinite range as +-FLT_MAX (off_grid_ranges).  The device layer takes its beams as
  * given: a caller of ndt2d_set_beams, ndt2d_set_search_beams or ndt2d_score_poses_beams(_launch)

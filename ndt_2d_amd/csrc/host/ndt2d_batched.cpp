@@ -1,0 +1,381 @@
+// The three batched matches of the matcher -- a scan against all its candidate maps
+// (match_candidates), from K start poses (match_starts), K scans each from its own pose (match_scans):
+// each validates its input, makes one call of its object under csrc/closure, starts or scans for
+// the records of all slots, and hands them to finish_slots(), the tail they share.
+#include <cstring>
+#include <functional>
+#include <string>
+#include <vector>
+
+#include "host/ndt2d_matcher_state.h"
+#include "ndt2d_guard.h"
+
+using namespace ndt2d::host;
+
+namespace
+{
+
+constexpr size_t kRec = NDT2D_MATCH_RECORD_DOUBLES;
+
+// `if (!ndt_) return 0.0;` (reference src/scan_matcher_ndt.cpp:80) for every slot: the other outputs untouched
+void fill_no_ndt(size_t n, double * scores_out, uint64_t * best_index_out)
+{
+  for (size_t k = 0; k < n; ++k)
+  {
+    scores_out[k] = 0.0;
+    if (best_index_out != nullptr) best_index_out[k] = NDT2D_NO_INDEX;
+  }
+}
+
+// all_scores is filled only where it takes the lattice of every slot
+double * scores_if_they_fit(double * all_scores, size_t all_scores_cap, size_t n_slots, size_t n_lattice)
+{
+  return (all_scores != nullptr && all_scores_cap / n_slots >= n_lattice && n_lattice > 0) ? all_scores : nullptr;
+}
+
+// Slot k's part of the caller's output arrays ...
+struct SlotOut
+{
+  double * pose, * covariance, * score;
+  uint64_t * best_index;
+  double * lattice_scores;
+};
+
+// ... which are these (poses, covariances, best indices and lattice scores are optional: scores_if_they_fit)
+struct BatchOut
+{
+  double * poses, * covariances, * scores;
+  uint64_t * best_index;
+  double * lattice_scores;
+  size_t n_lattice;
+  SlotOut slot(size_t k) const
+  {
+    return {poses != nullptr ? poses + 3 * k : nullptr, covariances != nullptr ? covariances + 9 * k : nullptr, scores + k,
+            best_index != nullptr ? best_index + k : nullptr, lattice_scores != nullptr ? lattice_scores + k * n_lattice : nullptr};
+  }
+};
+
+// The sequential call of one slot: matchScan of `points` from `scan_pose_xyt` into the slot's outputs.
+int match_alone(ndt2d_matcher * m, const double * scan_pose_xyt, const double * points_xy, size_t n_points,
+                const SlotOut & o, size_t n_lattice)
+{
+  return ndt2d_matcher_match_scan_ex(m, scan_pose_xyt, points_xy, n_points, o.pose, o.covariance, o.score, o.lattice_scores,
+                                     n_lattice, nullptr, o.best_index);
+}
+
+// The tail of a batched match: slot k's record (records[k]) becomes its best index, pose, covariance and
+// score -- unless sequential[k]: a marked winner (index + 0.5), whose adjudication the sequential call
+// settles, or a batch without points or lattice (every candidate scores -0.0 and none is < 0; the loops
+// do not run), of which the sequential call says what it gives.  alone(k, out) is that call;
+// set_n(k), if any, sets the N of `best / N` (:148) before a record is finished.  The first failure
+// ends the loop, its text prefixed with `slot_name` and the slot.
+int finish_slots(ndt2d_matcher * m, size_t n_slots, const double * records, const std::vector<char> & sequential,
+                 const BatchOut & out, const char * slot_name, const std::function<int(size_t, const SlotOut &)> & alone,
+                 const std::function<void(size_t)> & set_n = nullptr)
+{
+  int rc = NDT2D_OK;
+  for (size_t k = 0; k < n_slots && rc == NDT2D_OK; ++k)
+  {
+    const SlotOut o = out.slot(k);
+    if (sequential[k])
+    {
+      rc = alone(k, o);
+      if (rc != NDT2D_OK) m->err = slot_name + std::to_string(k) + ": " + m->err;
+      continue;
+    }
+    if (set_n) set_n(k);
+    const double * rec = records + k * kRec;
+    if (o.best_index != nullptr) *o.best_index = record_best_index(rec);
+    rc = ndt2d_matcher_finish_match(m, rec, o.pose, o.covariance, o.score);
+  }
+  return rc;
+}
+
+// Candidates the batched match launches at a time: the plugin's global_search_limit_ is a handful.
+constexpr size_t kClosureSlots = 16;
+
+}  // namespace
+
+extern "C" {
+
+int ndt2d_matcher_match_candidates(ndt2d_matcher * m, const double * scan_pose_xyt, const double * points_xy,
+                                   size_t n_points, const size_t * cand_offsets, const size_t * ids,
+                                   const double * poses_xyt, size_t n_candidates, double * poses_out,
+                                   double * covariances_out, double * scores_out, uint64_t * best_index_out,
+                                   double * all_scores, size_t all_scores_cap, size_t * n_lattice_out)
+{
+  NDT2D_C_TRY
+  if (m == nullptr) return NDT2D_ERR_INVALID;
+  if (scan_pose_xyt == nullptr || scores_out == nullptr || (n_points > 0 && points_xy == nullptr) ||
+      (n_candidates > 0 && (cand_offsets == nullptr || ids == nullptr || poses_xyt == nullptr)))
+  {
+    return mfail(m, NDT2D_ERR_INVALID, "match_candidates: null input");
+  }
+  const size_t n_th = m->search.dth.size(), n_lin = m->search.dlin.size();
+  const size_t n_lattice = n_th * n_lin * n_lin;
+  if (n_lattice_out != nullptr) *n_lattice_out = n_lattice;
+  if (n_candidates == 0) return NDT2D_OK;
+  if (n_candidates > (1u << 20)) return mfail(m, NDT2D_ERR_INVALID, "match_candidates: too many candidates");
+  if (m->stores.size() != m->devs.size())
+  {
+    return mfail(m, NDT2D_ERR_INVALID, "match_candidates: candidate 0: unknown scan id (no scan is stored)");
+  }
+  discard_ahead(m);   // a search launched ahead by scoreScan is waited out and dropped
+  if (m->closure == nullptr)
+  {
+    const int rc = ndt2d_closure_create(m->dev, m->stores[0], kClosureSlots, &m->closure);
+    if (rc != NDT2D_OK) return dev_fail(m, rc, "ndt2d_closure_create");
+  }
+  double * scores_ptr = scores_if_they_fit(all_scores, all_scores_cap, n_candidates, n_lattice);
+
+  // the scan as matchScan takes it: subsampled beams (:95-96,110), cos / sin per theta step (:106-107)
+  const size_t use = adopt_scan(m, points_xy, n_points);
+  fill_rotations(m, scan_pose_xyt[2]);
+  m->closure_records.assign(n_candidates * kRec, 0.0);
+  double * records = m->closure_records.data();
+  std::vector<char> sequential(n_candidates, 1);   // (no points, or no lattice: every slot)
+  if (use > 0 && n_lattice > 0)
+  {
+    int rc = ndt2d_scanstore_set_eigenvalue_form(m->stores[0], eigen_form_name(m));
+    if (rc == NDT2D_OK)
+    {
+      rc = ndt2d_closure_match(m->closure, n_candidates, cand_offsets, ids, poses_xyt, m->resolution, m->range_max,
+                               m->beams.host.data(), use, scan_pose_xyt[0], scan_pose_xyt[1], m->search.dth.data(),
+                               m->search.cos_th.data(), m->search.sin_th.data(), n_th, m->search.dlin.data(), n_lin,
+                               records, scores_ptr);
+    }
+    if (rc != NDT2D_OK) return mfail(m, rc, std::string("match_candidates: ") + ndt2d_closure_last_error(m->closure));
+    for (size_t k = 0; k < n_candidates; ++k) sequential[k] = marked_winner(records + k * kRec);
+  }
+  const BatchOut out = {poses_out, covariances_out, scores_out, best_index_out, scores_ptr, n_lattice};
+  const auto alone = [&](size_t k, const SlotOut & o) {
+    // the candidate's map built as the loop would build it, then matchScan
+    const size_t j0 = cand_offsets[k], n_k = cand_offsets[k + 1] - cand_offsets[k];
+    int rc = ndt2d_matcher_reset(m);
+    if (rc == NDT2D_OK) rc = ndt2d_matcher_add_scans_by_id(m, poses_xyt + 3 * j0, ids + j0, n_k);
+    return rc == NDT2D_OK ? match_alone(m, scan_pose_xyt, points_xy, n_points, o, n_lattice) : rc;
+  };
+  const int rc = finish_slots(m, n_candidates, records, sequential, out, "match_candidates: candidate ", alone);
+  // `global_scan_matcher_->reset()` (src/ndt_mapper.cpp:634): no NDT is left in place
+  const int rrc = ndt2d_matcher_reset(m);
+  return rc != NDT2D_OK ? rc : rrc;
+  NDT2D_C_CATCH(m)
+}
+
+ndt2d_closure * ndt2d_matcher_closure(ndt2d_matcher * m) { return m != nullptr ? m->closure : nullptr; }
+
+// Starts the batched match launches at a time: the object's limit (a relocalisation over every
+// graph node under a few headings is hundreds to a few thousand).
+static constexpr size_t kStartsSlots = 4096;
+
+int ndt2d_matcher_match_starts(ndt2d_matcher * m, const double * starts_xyt, size_t n_starts, const double * points_xy,
+                               size_t n_points, double * poses_out, double * covariances_out, double * scores_out,
+                               uint64_t * best_index_out, double * all_scores, size_t all_scores_cap,
+                               size_t * n_lattice_out)
+{
+  NDT2D_C_TRY
+  if (m == nullptr) return NDT2D_ERR_INVALID;
+  if (n_lattice_out != nullptr) *n_lattice_out = 0;
+  if (n_starts == 0) return NDT2D_OK;
+  if (starts_xyt == nullptr || scores_out == nullptr || (n_points > 0 && points_xy == nullptr))
+  {
+    return mfail(m, NDT2D_ERR_INVALID, "match_starts: null input");
+  }
+  if (n_starts > (1u << 20)) return mfail(m, NDT2D_ERR_INVALID, "match_starts: too many starts");
+  if (!m->ndt.have())
+  {
+    fill_no_ndt(n_starts, scores_out, best_index_out);
+    return NDT2D_OK;
+  }
+  for (size_t k = 0; k < n_starts; ++k)
+  {
+    if (!std::isfinite(starts_xyt[3 * k]) || !std::isfinite(starts_xyt[3 * k + 1]) || !std::isfinite(starts_xyt[3 * k + 2]))
+    {
+      return mfail(m, NDT2D_ERR_INVALID, "match_starts: start " + std::to_string(k) + ": the pose is not finite");
+    }
+  }
+  const size_t n_th = m->search.dth.size(), n_lin = m->search.dlin.size();
+  const size_t n_lattice = n_th * n_lin * n_lin;
+  if (n_lattice_out != nullptr) *n_lattice_out = n_lattice;
+  discard_ahead(m);   // a search launched ahead by scoreScan is waited out and dropped
+  if (m->starts == nullptr)
+  {
+    const int rc = ndt2d_starts_create(m->dev, kStartsSlots, &m->starts);
+    if (rc != NDT2D_OK) return dev_fail(m, rc, "ndt2d_starts_create");
+  }
+  double * scores_ptr = scores_if_they_fit(all_scores, all_scores_cap, n_starts, n_lattice);
+
+  // the scan as matchScan takes it: subsampled beams (:95-96,110), once for every start
+  const size_t use = adopt_scan(m, points_xy, n_points);
+  m->starts_records.assign(n_starts * kRec, 0.0);
+  double * records = m->starts_records.data();
+  std::vector<char> sequential(n_starts, 1);   // (no points, or no lattice: every slot)
+  if (use > 0 && n_lattice > 0)
+  {
+    const int rc = ndt2d_starts_match(m->starts, starts_xyt, n_starts, m->beams.host.data(), use, m->search.dth.data(), n_th,
+                                      m->search.dlin.data(), n_lin, records, scores_ptr);
+    if (rc != NDT2D_OK) return mfail(m, rc, std::string("match_starts: ") + ndt2d_starts_last_error(m->starts));
+    m->last_multi = false;
+    for (size_t k = 0; k < n_starts; ++k) sequential[k] = marked_winner(records + k * kRec);
+  }
+  const BatchOut out = {poses_out, covariances_out, scores_out, best_index_out, scores_ptr, n_lattice};
+  return finish_slots(
+    m, n_starts, records, sequential, out, "match_starts: start ",
+    [&](size_t k, const SlotOut & o) { return match_alone(m, starts_xyt + 3 * k, points_xy, n_points, o, n_lattice); },
+    // (a sequential call prepared a search of its own; the records after it are finished with this N)
+    [&](size_t) { m->search.n_use = use; });
+  NDT2D_C_CATCH(m)
+}
+
+ndt2d_starts * ndt2d_matcher_starts(ndt2d_matcher * m) { return m != nullptr ? m->starts : nullptr; }
+
+// Jobs the batched scan tracking launches at a time: the object's limit (a fleet is tens, a
+// replayed bag or a graph's scans hundreds to a few thousand).
+static constexpr size_t kScansSlots = 4096;
+
+int ndt2d_matcher_match_scans(ndt2d_matcher * m, const double * jobs_xyt, const uint32_t * job_scan, size_t n_jobs,
+                              const double * points_xy, const size_t * point_offsets, size_t n_scans, double * poses_out,
+                              double * covariances_out, double * scores_out, uint64_t * best_index_out,
+                              double * all_scores, size_t all_scores_cap, size_t * n_lattice_out)
+{
+  NDT2D_C_TRY
+  if (m == nullptr) return NDT2D_ERR_INVALID;
+  if (n_lattice_out != nullptr) *n_lattice_out = 0;
+  if (n_jobs == 0) return NDT2D_OK;
+  if (jobs_xyt == nullptr || scores_out == nullptr || point_offsets == nullptr)
+  {
+    return mfail(m, NDT2D_ERR_INVALID, "match_scans: null input");
+  }
+  if (n_jobs > (1u << 20) || n_scans > (1u << 20)) return mfail(m, NDT2D_ERR_INVALID, "match_scans: too many jobs or scans");
+  if (!m->ndt.have())
+  {
+    fill_no_ndt(n_jobs, scores_out, best_index_out);
+    return NDT2D_OK;
+  }
+  if (job_scan == nullptr && n_scans != n_jobs)
+  {
+    return mfail(m, NDT2D_ERR_INVALID, "match_scans: no job_scan (job k uses scan k): n_scans must equal n_jobs");
+  }
+  for (size_t sc = 0; sc < n_scans; ++sc)
+  {
+    if (point_offsets[sc + 1] < point_offsets[sc])
+    {
+      return mfail(m, NDT2D_ERR_INVALID, "match_scans: scan " + std::to_string(sc) + ": point_offsets decrease");
+    }
+  }
+  if (n_scans > 0 && point_offsets[n_scans] > point_offsets[0] && points_xy == nullptr)
+  {
+    return mfail(m, NDT2D_ERR_INVALID, "match_scans: null input");
+  }
+  for (size_t k = 0; k < n_jobs; ++k)
+  {
+    if (!std::isfinite(jobs_xyt[3 * k]) || !std::isfinite(jobs_xyt[3 * k + 1]) || !std::isfinite(jobs_xyt[3 * k + 2]))
+    {
+      return mfail(m, NDT2D_ERR_INVALID, "match_scans: job " + std::to_string(k) + ": the pose is not finite");
+    }
+    if (job_scan != nullptr && job_scan[k] >= n_scans)
+    {
+      return mfail(m, NDT2D_ERR_INVALID, "match_scans: job " + std::to_string(k) + ": scan " + std::to_string(job_scan[k]) +
+                                             " of " + std::to_string(n_scans));
+    }
+  }
+  const size_t n_th = m->search.dth.size(), n_lin = m->search.dlin.size();
+  const size_t n_lattice = n_th * n_lin * n_lin;
+  if (n_lattice_out != nullptr) *n_lattice_out = n_lattice;
+  discard_ahead(m);   // a search launched ahead by scoreScan is waited out and dropped
+  if (m->scans == nullptr)
+  {
+    const int rc = ndt2d_scans_create(m->dev, kScansSlots, &m->scans);
+    if (rc != NDT2D_OK) return dev_fail(m, rc, "ndt2d_scans_create");
+  }
+  double * scores_ptr = scores_if_they_fit(all_scores, all_scores_cap, n_jobs, n_lattice);
+  const auto scan_of = [&](size_t k) { return job_scan != nullptr ? static_cast<size_t>(job_scan[k]) : k; };
+
+  // every scan a job names as matchScan takes it: subsampled beams (:95-96,110), once per scan.
+  // sent[s]: its index among the scans the batched call receives (a scan without points is not
+  // among them: its jobs go through the sequential call).
+  constexpr uint32_t kUnseen = ~0u, kEmpty = ~0u - 1u;
+  std::vector<uint32_t> sent(n_scans, kUnseen);
+  std::vector<double> beams, one;
+  std::vector<size_t> beam_offsets(1, 0);
+  std::vector<uint32_t> batch_job, batch_scan;   // the jobs of the batched call and their scans
+  for (size_t k = 0; k < n_jobs && n_lattice > 0; ++k)
+  {
+    const size_t sc = scan_of(k);
+    if (sent[sc] == kUnseen)
+    {
+      subsample_into(one, points_xy + 2 * point_offsets[sc], point_offsets[sc + 1] - point_offsets[sc], m->laser_max_beams);
+      if (one.empty())
+      {
+        sent[sc] = kEmpty;
+      }
+      else
+      {
+        sent[sc] = static_cast<uint32_t>(beam_offsets.size() - 1);
+        beams.insert(beams.end(), one.begin(), one.end());
+        beam_offsets.push_back(beams.size() / 2);
+      }
+    }
+    if (sent[sc] == kEmpty) continue;
+    batch_job.push_back(static_cast<uint32_t>(k));
+    batch_scan.push_back(sent[sc]);
+  }
+  m->search.ready = false;   // no search is prepared on the context
+  std::vector<char> sequential(n_jobs, 1);   // (a job outside the batch: no points, or no lattice)
+  const size_t n_batch = batch_job.size();
+  m->scans_records.assign(n_jobs * kRec, 0.0);   // the batch's records in front, then moved to their jobs' slots
+  double * records = m->scans_records.data();
+  if (n_batch > 0)
+  {
+    // (all jobs in the batch: its scores are the caller's rows; else they are dealt out below)
+    std::vector<double> batch_scores, batch_xyt;
+    const double * xyt = jobs_xyt;
+    double * batch_scores_ptr = scores_ptr;
+    if (n_batch != n_jobs)
+    {
+      batch_xyt.resize(3 * n_batch);
+      for (size_t j = 0; j < n_batch; ++j) std::memcpy(&batch_xyt[3 * j], jobs_xyt + 3 * batch_job[j], 3 * sizeof(double));
+      xyt = batch_xyt.data();
+      if (scores_ptr != nullptr)
+      {
+        batch_scores.resize(n_batch * n_lattice);
+        batch_scores_ptr = batch_scores.data();
+      }
+    }
+    const int rc = ndt2d_scans_match(m->scans, xyt, batch_scan.data(), n_batch, beams.data(), beam_offsets.data(),
+                                     beam_offsets.size() - 1, m->search.dth.data(), n_th, m->search.dlin.data(), n_lin,
+                                     records, batch_scores_ptr);
+    if (rc != NDT2D_OK) return mfail(m, rc, std::string("match_scans: ") + ndt2d_scans_last_error(m->scans));
+    m->last_multi = false;
+    // (from the last: batch_job ascends, so record j's slot batch_job[j] >= j holds no record still to be moved)
+    for (size_t j = n_batch; j-- > 0;)
+    {
+      const size_t k = batch_job[j];
+      if (k != j) std::memcpy(records + k * kRec, records + j * kRec, kRec * sizeof(double));
+      sequential[k] = marked_winner(records + k * kRec);
+      if (!batch_scores.empty() && !sequential[k])
+      {
+        std::memcpy(scores_ptr + k * n_lattice, &batch_scores[j * n_lattice], n_lattice * sizeof(double));
+      }
+    }
+  }
+  const BatchOut out = {poses_out, covariances_out, scores_out, best_index_out, scores_ptr, n_lattice};
+  return finish_slots(
+    m, n_jobs, records, sequential, out, "match_scans: job ",
+    [&](size_t k, const SlotOut & o) {
+      const size_t sc = scan_of(k);
+      return match_alone(m, jobs_xyt + 3 * k, points_xy + 2 * point_offsets[sc], point_offsets[sc + 1] - point_offsets[sc], o,
+                         n_lattice);
+    },
+    [&](size_t k) {
+      // the N of `best / N` (:148) is the job's own scan's
+      const uint32_t s = sent[scan_of(k)];
+      m->search.n_use = beam_offsets[s + 1] - beam_offsets[s];
+      m->search.ready = false;   // (a sequential call in between prepared a search of its own)
+    });
+  NDT2D_C_CATCH(m)
+}
+
+ndt2d_scans * ndt2d_matcher_scans(ndt2d_matcher * m) { return m != nullptr ? m->scans : nullptr; }
+
+}  // extern "C"

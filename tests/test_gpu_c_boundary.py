@@ -91,7 +91,9 @@ def test_every_multi_line_entry_point_is_guarded():
     import re
     root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ndt_2d_amd", "csrc")
     missing = []
-    for name in ("ndt2d_host.cpp", "ndt2d_device.hip"):
+    host = sorted(os.path.join("host", f) for f in os.listdir(os.path.join(root, "host")) if f.endswith(".cpp"))
+    assert len(host) >= 5, host
+    for name in ["ndt2d_host.cpp"] + host + ["ndt2d_device.hip"]:
         lines = open(os.path.join(root, name)).read().split("\n")
         for i, ln in enumerate(lines):
             m = re.match(r'^(?:extern "C" )?int (ndt2d_\w+)\(', ln)

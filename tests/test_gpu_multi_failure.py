@@ -2,7 +2,7 @@
 library makes the k-th launch return NDT2D_ERR_HIP): the call must return that error with every
 device waited out -- no search left pending, no copy into the caller's buffers in flight, the
 device threads released from their barrier -- and the next call must give the right answer on all
-devices.  ndt2d_host.cpp drain_devices / first_failure, DeviceWorkers::barrier."""
+devices.  csrc/host/ndt2d_multi.cpp drain_devices / first_failure, DeviceWorkers::barrier."""
 import json
 import os
 import subprocess

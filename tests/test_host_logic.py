@@ -156,7 +156,7 @@ def _with_off_grid(scans, rng=None):
 
 @pytest.mark.parametrize("cfg", [1, 3])
 def test_quarters_side_by_side_give_the_sequential_bits(cfg):
-    """HostNdt::add_scan (csrc/ndt2d_host.cpp): four chains of Cell::addPoint in flight, the points
+    """HostNdt::add_scan (csrc/host/ndt2d_host_ndt.cpp): four chains of Cell::addPoint in flight, the points
     of a cell still in the reference's order -- every cell bit for bit the sequential loop's."""
     from ndt_2d_amd.scan_matcher import BUILD_SEQUENTIAL
     scans = synth.map_scans(cfg)
@@ -197,9 +197,10 @@ def test_quarters_that_share_cells_keep_the_order(seed):
 
 
 def test_builds_reuse_their_storage_across_geometries():
-    """The matcher rebuilds its NDT in the storage of the one before (the cell stamps of
-    add_scan are never cleared: ids from a running counter): a sequence of different maps
-    through ONE library instance gives what each gives alone."""
+    """A sequence of maps of growing geometry through one loaded library: for each, the quarters side
+    by side give the bits of the sequential loop.  Every ndt2d_host_build_grid_ex call builds in FRESH
+    storage (it hands build_ndt no NDT to reuse), so this does not reach the reuse of a matcher's
+    storage: test_reused_storage_gives_the_bits_of_fresh_storage_under_sanitizers does."""
     from ndt_2d_amd.scan_matcher import BUILD_SEQUENTIAL
     rng = np.random.default_rng(77)
     for i in range(6):
@@ -281,3 +282,85 @@ def test_random_scan_sets_build_bit_for_bit_like_the_sequential_loop_and_the_ora
         m.reset()
         m.addScans(subs)
         assert np.array_equal(a[0].view(np.uint64), np.ascontiguousarray(m.ndt.cells6()).view(np.uint64))
+
+
+# ---- the host NDT as a unit of its own (csrc/host/): reused storage, under the sanitizers ----
+
+def test_every_file_of_the_host_directory_is_built_and_hashed():
+    from ndt_2d_amd import build
+    csrc = os.path.join(os.path.dirname(os.path.dirname(GOLDEN)), "ndt_2d_amd", "csrc")
+    names = sorted(n for n in os.listdir(os.path.join(csrc, "host")) if not n.endswith((".o", ".sha")))   # (build products)
+    assert len(names) >= 7, names
+    for name in names:
+        assert ("host/" + name in build.SOURCES) != (os.path.join(csrc, "host", name) in build.HEADERS), name
+
+
+def _records(blob):
+    """tests/cpp/host_ndt_check.cpp's file: its BUILD records and its LOAD record."""
+    at = [0]
+
+    def take(dtype, n=1):
+        out = np.frombuffer(blob, dtype=dtype, count=n, offset=at[0])
+        at[0] += out.nbytes
+        return out
+    builds, load = [], None
+    while at[0] < len(blob):
+        kind = int(take("<u8")[0])
+        if kind == 1:
+            b = {"sequential": int(take("<u8")[0]), "resolution": float(take("<f8")[0]), "range_max": float(take("<f8")[0])}
+            n_scans = int(take("<u8")[0])
+            b["poses"] = take("<f8", 3 * n_scans).reshape(-1, 3)
+            b["offsets"] = take("<u8", n_scans + 1)
+            b["points"] = take("<f8", 2 * int(b["offsets"][-1])).reshape(-1, 2)
+            b["size"] = tuple(int(v) for v in take("<u8", 2))
+            b["origin"] = tuple(float(v) for v in take("<f8", 2))
+            b["cells"] = take("<f8", 6 * b["size"][0] * b["size"][1]).reshape(-1, 6)
+            builds.append(b)
+        else:
+            assert kind == 2 and load is None
+            sx, sy, n = (int(v) for v in take("<u8", 3))
+            load = {"size": (sx, sy), "index": take("<u8", n), "sparse": take("<f8", 6 * n).reshape(-1, 6),
+                    "packed": take("<f8", 6 * sx * sy).reshape(-1, 6)}
+    return builds, load
+
+
+def test_reused_storage_gives_the_bits_of_fresh_storage_under_sanitizers(tmp_path):
+    """tests/cpp/host_ndt_check.cpp: ONE HostNdt taken through build_ndt(reuse = itself) for a 41 x 41
+    map, a larger, a smaller (true divide), a 1 x 11 sliver and the first geometry again, each side by
+    side and sequentially, then reset_cells + load6 of a packed grid -- built from
+    host/ndt2d_host_ndt.cpp alone with the address and undefined-behaviour sanitizers, which must stay
+    silent; and every build's cells are, byte for byte, what the library builds from the same inputs
+    in fresh storage."""
+    import subprocess
+    from ndt_2d_amd.scan_matcher import BUILD_SEQUENTIAL
+    root = os.path.dirname(os.path.dirname(GOLDEN))
+    exe, out = os.path.join(str(tmp_path), "host_ndt_check"), os.path.join(str(tmp_path), "builds.bin")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off",
+           "-Wall", "-Wextra", "-Werror", "-I", os.path.join(root, "include"), "-I", os.path.join(root, "ndt_2d_amd", "csrc"),
+           os.path.join(root, "tests", "cpp", "host_ndt_check.cpp"),
+           os.path.join(root, "ndt_2d_amd", "csrc", "host", "ndt2d_host_ndt.cpp"), "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([exe, out], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and not r.stderr, (r.returncode, r.stdout, r.stderr)
+    assert "host ndt ok: 10 builds in one object" in r.stdout
+    builds, load = _records(open(out, "rb").read())
+    assert [b["size"] for b in builds] == [(41, 41)] * 2 + [(81, 81)] * 2 + [(21, 21)] * 2 + [(1, 11)] * 2 + [(41, 41)] * 2
+    assert [b["sequential"] for b in builds] == [0, 1] * 5
+    for b in builds:
+        off = [int(o) for o in b["offsets"]]
+        sizes = sorted(off[i + 1] - off[i] for i in range(len(off) - 1))
+        assert sizes == [0, 0, 1, 5, 31, 33, 33, 64, 719, 719]
+        assert np.isnan(b["points"]).any() and np.isinf(b["points"]).any() and (np.abs(b["points"]) == 1e300).any()
+        scans = [(tuple(b["poses"][i]), b["points"][off[i]:off[i + 1]]) for i in range(len(off) - 1)]
+        cells, sx, sy, ox, oy = host_build_grid(b["resolution"], b["range_max"], scans,
+                                                BUILD_SEQUENTIAL if b["sequential"] else 0)
+        assert (sx, sy) == b["size"] and (ox, oy) == b["origin"]
+        assert (cells[:, 5] >= 64).any() and (cells[:, 5] > 0).sum() > 5
+        assert np.ascontiguousarray(cells).tobytes() == b["cells"].tobytes()
+    # the grid loaded back: the third map's, out of the pool the fifth map left
+    grid = builds[5]["cells"]
+    assert load["size"] == builds[5]["size"]
+    assert load["packed"].tobytes() == grid.tobytes()
+    held = np.flatnonzero(grid[:, 5] != 0.0)
+    assert np.array_equal(load["index"], held) and load["sparse"].tobytes() == grid[held].tobytes()
