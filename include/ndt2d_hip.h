@@ -352,6 +352,87 @@ int ndt2d_scans_match(ndt2d_scans * scans, const double * jobs_xyt, const uint32
 int ndt2d_scans_set_timing(ndt2d_scans * scans, int enabled);
 int ndt2d_scans_last_ms(ndt2d_scans * scans, float * search_ms, float * reduce_ms);
 
+/* ---- Newton NDT registration: K (scan, pose) jobs refined in one launch (csrc/refine/) ----
+ *
+ * Every search above ends on the lattice: its pose is quantised to the lattice's pitch.  A job
+ * here is a (scan, pose) pair as in ndt2d_scans_match; for each, a damped Newton iteration on the
+ * scan's NDT score against the grid INSTALLED in the context runs from the job's pose to the
+ * optimum under it.  One call is one upload, ONE kernel launch for the whole iteration of all
+ * jobs of a chunk (a workgroup per job loops until its job stops) and one read-back.
+ * An object of its own beside the context, as ndt2d_scans: it reads the grid installed at the
+ * time of the call (any install path, any size or origin), installs nothing, launches on the
+ * context's current stream, and must be destroyed before ndt2d_destroy(h).
+ *
+ * The objective.  For a pose p = (x, y, theta) and the job's beams b_i (robot frame, already
+ * subsampled), with c = cos theta, s = sin theta:
+ *     q_i = (c bx - s by + x,  s bx + c by + y)
+ *     the cell of q_i is NDT::getIndex's; the beam counts only if the cell can score (n >= 5)
+ *     d = q - mean,  u = I d,  e = exp(-1/2 d^T I d)      I: the cell's information matrix
+ *         (the records hold h = -1/2 I: the exponent is Cell::score's, I = -2 h exactly, and
+ *          u_0 = I00 d0 + I01 d1, u_1 = I01 d0 + I11 d1)
+ *     r = dq/dtheta   = (-s bx - c by,  c bx - s by)
+ *     w = d2q/dtheta2 = (-c bx + s by, -s bx - c by)
+ *     a = (u_0, u_1, u_0 r_0 + u_1 r_1)
+ *     M = [[I00, I01, (I r)_0], [., I11, (I r)_1], [., ., (r_0 (I r)_0 + r_1 (I r)_1) + (u_0 w_0 + u_1 w_1)]]
+ *     f    = -sum e                    (f / N is what ScanMatcherNDT::scorePoints returns)
+ *     g_j  =  sum e a_j
+ *     H_jk =  sum e (-(a_j a_k) + M_jk)          six entries: xx, xy, xt, yy, yt, tt
+ * Ten sums; a beam's ten terms are added by thread (beam mod 256) in beam order, the 256 partial
+ * sums of each by a fixed tree, so two calls give the same bits.  The cell borders are
+ * discontinuities of f (the reference's NDT has no overlapping or interpolated cells); the
+ * iteration only ever accepts a pose that lowers f.
+ *
+ * The iteration.
+ *   1. Evaluate (f, g, H) at the start: evals = 1.  f == 0 (no beam scores): NO_OVERLAP; f not
+ *      finite: NOT_FINITE; either way the pose is returned bit for bit.
+ *   2. lambda = 0.
+ *   3. While evals < max_evals:
+ *        D_j = max(|H_jj|, 1e-12); solve (H + lambda diag D) delta = -g by 3 x 3 Cholesky; on a
+ *        pivot that is not > 0: lambda = max(10 lambda, 1e-3) and again, past 1e12: STALLED.
+ *        |dx| < tol_lin and |dy| < tol_lin and |dtheta| < tol_ang: CONVERGED.
+ *        Evaluate at p + delta (theta is not normalised): evals += 1.
+ *        f' < f: accept p, f, g, H; lambda = lambda / 10, and 0 once that is <= 1e-9.
+ *        else:   lambda = max(10 lambda, 1e-3), past 1e12: STALLED.
+ *   4. Leaving the loop by count: MAX_EVALS (max_evals == 1 is the evaluation alone).
+ * The returned (f, g, H) are those of the returned pose; f never increases.  cos / sin of the
+ * START heading come from the host libm inside the call, those of later headings from the
+ * device's sincos.
+ *
+ *   create   max_jobs (1 .. 4,096): jobs of one chunk; a call with more is processed in chunks
+ *            inside the call.  Chunking changes no bit; a job's bits do not depend on the other
+ *            jobs.
+ *   run      jobs_xyt, job_scan, beams_xy, beam_offsets, n_scans: ndt2d_scans_match's conventions
+ *            (shared scans travel once, a scan no job names is legal and is not uploaded,
+ *            job_scan == NULL: job k uses scan k and n_scans must equal n_jobs; beams are taken
+ *            as given, "Points off the grid" below).  max_evals >= 1; tol_lin (m) and tol_ang
+ *            (rad) >= 0 (the matcher layer's defaults: 32, 1e-6, 1e-6).
+ *            records_out[K][NDT2D_REFINE_RECORD_DOUBLES], by job in the caller's order:
+ *            {x, y, theta | f_start, f | g[3] | H xx, xy, xt, yy, yt, tt | evals, accepted
+ *            steps, status (NDT2D_REFINE_*), the last lambda}.
+ *            Refused with NDT2D_ERR_INVALID before anything is launched: a non-finite job pose or
+ *            job_scan[k] >= n_scans (the message says "job k"), a scan with 0 or more than 2^20
+ *            beams or beam_offsets that decrease ("scan s"), max_evals == 0, a tolerance that is
+ *            negative or not finite, job_scan == NULL with n_scans != n_jobs.  No grid:
+ *            NDT2D_ERR_NO_GRID.  n_jobs == 0: NDT2D_OK, nothing done.
+ *   set_timing / last_ms   HIP events around the kernel launch and the read-back of the last
+ *            (chunk of a) run, off by default. */
+#define NDT2D_REFINE_RECORD_DOUBLES 18
+#define NDT2D_REFINE_CONVERGED 0    /* the Newton step fell below the tolerances */
+#define NDT2D_REFINE_MAX_EVALS 1    /* max_evals evaluations were made */
+#define NDT2D_REFINE_STALLED 2      /* lambda passed 1e12: no step lowers f */
+#define NDT2D_REFINE_NO_OVERLAP 3   /* no beam of the scan scores at the start pose */
+#define NDT2D_REFINE_NOT_FINITE 4   /* f at the start pose is not finite (a degenerate cell) */
+typedef struct ndt2d_refine ndt2d_refine;
+int ndt2d_refine_create(ndt2d_handle h, size_t max_jobs, ndt2d_refine ** out);
+int ndt2d_refine_destroy(ndt2d_refine * refine);
+const char * ndt2d_refine_last_error(ndt2d_refine * refine);
+int ndt2d_refine_run(ndt2d_refine * refine, const double * jobs_xyt, const uint32_t * job_scan,
+                     size_t n_jobs, const double * beams_xy, const size_t * beam_offsets,
+                     size_t n_scans, uint32_t max_evals, double tol_lin, double tol_ang,
+                     double * records_out);
+int ndt2d_refine_set_timing(ndt2d_refine * refine, int enabled);
+int ndt2d_refine_last_ms(ndt2d_refine * refine, float * kernel_ms, float * fetch_ms);
+
 /* Upload the beam endpoints of one scan, robot frame, already subsampled to
  * min(laser_max_beams, points.size()) points by the caller
  * (src/scan_matcher_ndt.cpp:95-96,110 / :165-166,171).  Beams are taken as given: finite,
@@ -1030,6 +1111,34 @@ int ndt2d_matcher_match_scans(ndt2d_matcher * m, const double * jobs_xyt, const 
 /* The batched call's object (made by the first match_scans with an NDT in place; NULL before), for
  * ndt2d_scans_set_timing / _last_ms. */
 ndt2d_scans * ndt2d_matcher_scans(ndt2d_matcher * m);
+/* Newton NDT registration of K jobs -- (scan, pose) pairs -- against the NDT in place, in one call
+ * (ndt2d_refine_run on the first device): from each job's pose -- a lattice winner of match_scans,
+ * an odometry guess -- to the optimum of the scan's score under it.  Scans, jobs and job_scan as
+ * in match_scans; each scan a job names is subsampled once with the matcher's laser_max_beams, as
+ * matchScan / scorePoints subsample it.  Per job k:
+ *     poses_out[3 k ..]        the ABSOLUTE pose reached (not a correction)
+ *     scores_out[k]            f / N at that pose: what score_points gives there
+ *     start_scores_out[k]      f / N at the job's pose                       (optional)
+ *     gradients_out[3 k ..]    g / N                                         (optional)
+ *     hessians_out[9 k ..]     H / N, row-major 3 x 3, symmetric             (optional)
+ *     status_out[k]            NDT2D_REFINE_*
+ *     evals_out[2 k ..]        evaluations, accepted steps                   (optional)
+ * No NDT in place: every score is 0.0, the poses are the jobs' own, status NO_OVERLAP, no
+ * evaluation (src/scan_matcher_ndt.cpp:159); jobs of a scan without points get the same.  A
+ * search launched ahead by score_scan is waited out and dropped first.  The NDT stays in place;
+ * the beams and the prepared search of the context are not touched.  NDT2D_ERR_INVALID, nothing
+ * launched: a non-finite job pose or a scan index out of range ("job k" in the message),
+ * point_offsets that decrease ("scan s"), job_scan == NULL with n_scans != n_jobs, max_evals == 0,
+ * a tolerance that is negative or not finite. */
+int ndt2d_matcher_refine_scans(ndt2d_matcher * m, const double * jobs_xyt, const uint32_t * job_scan,
+                               size_t n_jobs, const double * points_xy, const size_t * point_offsets,
+                               size_t n_scans, uint32_t max_evals, double tol_lin, double tol_ang,
+                               double * poses_out, double * scores_out, double * start_scores_out,
+                               double * gradients_out, double * hessians_out, int32_t * status_out,
+                               uint32_t * evals_out);
+/* The call's object (made by the first refine_scans with an NDT in place; NULL before), for
+ * ndt2d_refine_set_timing / _last_ms. */
+ndt2d_refine * ndt2d_matcher_refine(ndt2d_matcher * m);
 /* The two halves of matchScan, for sharded (multi-GPU) searches:
  * prepare_search subsamples the scan (:95-96,110), builds the offset and
  * cos/sin tables (:103-107,117,119) and uploads them -- after it,

@@ -20,6 +20,9 @@ ERR_STATE = 5
 ERR_ALLOC = 6
 ERR_INTERNAL = 7
 NO_INDEX = (1 << 64) - 1
+# NDT2D_REFINE_*: how a Newton registration job stopped
+REFINE_CONVERGED, REFINE_MAX_EVALS, REFINE_STALLED, REFINE_NO_OVERLAP, REFINE_NOT_FINITE = range(5)
+REFINE_STATUS_NAMES = ("converged", "max_evals", "stalled", "no_overlap", "not_finite")
 MATCH_RECORD_DOUBLES = 12
 POSE_STATS_DOUBLES = 8
 PF_RESULT_DOUBLES = 8
@@ -126,6 +129,12 @@ SIGNATURES = {
     "ndt2d_scans_match": (C.c_int, [_vp, _dp, C.POINTER(_u32), _sz, _dp, _szp, _sz, _dp, _sz, _dp, _sz, _dp, _dp]),
     "ndt2d_scans_set_timing": (C.c_int, [_vp, C.c_int]),
     "ndt2d_scans_last_ms": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "ndt2d_refine_create": (C.c_int, [_vp, _sz, C.POINTER(_vp)]),
+    "ndt2d_refine_destroy": (C.c_int, [_vp]),
+    "ndt2d_refine_last_error": (C.c_char_p, [_vp]),
+    "ndt2d_refine_run": (C.c_int, [_vp, _dp, C.POINTER(_u32), _sz, _dp, _szp, _sz, _u32, _d, _d, _dp]),
+    "ndt2d_refine_set_timing": (C.c_int, [_vp, C.c_int]),
+    "ndt2d_refine_last_ms": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "ndt2d_set_eigenvalue_form": (C.c_int, [_vp, C.c_char_p]),
     "ndt2d_get_grid": (C.c_int, [_vp, _dp, _sz, C.POINTER(_u32), C.POINTER(_u32), _dp, _dp, _dp]),
     "ndt2d_clear_grid": (C.c_int, [_vp]),
@@ -239,6 +248,9 @@ SIGNATURES = {
     "ndt2d_matcher_match_scans": (C.c_int, [_vp, _dp, C.POINTER(_u32), _sz, _dp, _szp, _sz, _dp, _dp, _dp,
                                             C.POINTER(C.c_uint64), _dp, _sz, _szp]),
     "ndt2d_matcher_scans": (_vp, [_vp]),
+    "ndt2d_matcher_refine_scans": (C.c_int, [_vp, _dp, C.POINTER(_u32), _sz, _dp, _szp, _sz, _u32, _d, _d, _dp, _dp, _dp, _dp,
+                                             _dp, C.POINTER(C.c_int32), C.POINTER(_u32)]),
+    "ndt2d_matcher_refine": (_vp, [_vp]),
     "ndt2d_matcher_match_laser_scan": (C.c_int, [_vp, _dp, C.POINTER(C.c_float), _sz,
                                                  C.POINTER(LaserScan), _dp, _dp, _dp, _szp]),
     "ndt2d_matcher_prepare_search": (C.c_int, [_vp, _dp, _dp, _sz, _szp, _szp, _szp]),

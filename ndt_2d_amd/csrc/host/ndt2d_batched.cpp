@@ -1,7 +1,8 @@
 // The three batched matches of the matcher -- a scan against all its candidate maps
 // (match_candidates), from K start poses (match_starts), K scans each from its own pose (match_scans):
 // each validates its input, makes one call of its object under csrc/closure, starts or scans for
-// the records of all slots, and hands them to finish_slots(), the tail they share.
+// the records of all slots, and hands them to finish_slots(), the tail they share -- and the Newton
+// registration of K (scan, pose) jobs (refine_scans), one call of the object under csrc/refine.
 #include <cstring>
 #include <functional>
 #include <string>
@@ -377,5 +378,147 @@ int ndt2d_matcher_match_scans(ndt2d_matcher * m, const double * jobs_xyt, const 
 }
 
 ndt2d_scans * ndt2d_matcher_scans(ndt2d_matcher * m) { return m != nullptr ? m->scans : nullptr; }
+
+// Jobs the Newton registration launches at a time: the object's limit, as match_scans.
+static constexpr size_t kRefineSlots = 4096;
+
+int ndt2d_matcher_refine_scans(ndt2d_matcher * m, const double * jobs_xyt, const uint32_t * job_scan, size_t n_jobs,
+                               const double * points_xy, const size_t * point_offsets, size_t n_scans, uint32_t max_evals,
+                               double tol_lin, double tol_ang, double * poses_out, double * scores_out,
+                               double * start_scores_out, double * gradients_out, double * hessians_out,
+                               int32_t * status_out, uint32_t * evals_out)
+{
+  NDT2D_C_TRY
+  if (m == nullptr) return NDT2D_ERR_INVALID;
+  if (n_jobs == 0) return NDT2D_OK;
+  if (jobs_xyt == nullptr || poses_out == nullptr || scores_out == nullptr || status_out == nullptr || point_offsets == nullptr)
+  {
+    return mfail(m, NDT2D_ERR_INVALID, "refine_scans: null input");
+  }
+  if (n_jobs > (1u << 20) || n_scans > (1u << 20)) return mfail(m, NDT2D_ERR_INVALID, "refine_scans: too many jobs or scans");
+  if (max_evals == 0) return mfail(m, NDT2D_ERR_INVALID, "refine_scans: max_evals == 0");
+  if (!(tol_lin >= 0.0) || !(tol_ang >= 0.0) || !std::isfinite(tol_lin) || !std::isfinite(tol_ang))
+  {
+    return mfail(m, NDT2D_ERR_INVALID, "refine_scans: a tolerance is negative or not finite");
+  }
+  if (job_scan == nullptr && n_scans != n_jobs)
+  {
+    return mfail(m, NDT2D_ERR_INVALID, "refine_scans: no job_scan (job k uses scan k): n_scans must equal n_jobs");
+  }
+  for (size_t sc = 0; sc < n_scans; ++sc)
+  {
+    if (point_offsets[sc + 1] < point_offsets[sc])
+    {
+      return mfail(m, NDT2D_ERR_INVALID, "refine_scans: scan " + std::to_string(sc) + ": point_offsets decrease");
+    }
+  }
+  if (n_scans > 0 && point_offsets[n_scans] > point_offsets[0] && points_xy == nullptr)
+  {
+    return mfail(m, NDT2D_ERR_INVALID, "refine_scans: null input");
+  }
+  for (size_t k = 0; k < n_jobs; ++k)
+  {
+    if (!std::isfinite(jobs_xyt[3 * k]) || !std::isfinite(jobs_xyt[3 * k + 1]) || !std::isfinite(jobs_xyt[3 * k + 2]))
+    {
+      return mfail(m, NDT2D_ERR_INVALID, "refine_scans: job " + std::to_string(k) + ": the pose is not finite");
+    }
+    if (job_scan != nullptr && job_scan[k] >= n_scans)
+    {
+      return mfail(m, NDT2D_ERR_INVALID, "refine_scans: job " + std::to_string(k) + ": scan " + std::to_string(job_scan[k]) +
+                                             " of " + std::to_string(n_scans));
+    }
+  }
+  // `if (!ndt_) return 0.0;` (src/scan_matcher_ndt.cpp:159), and a scan without points: nothing
+  // scores, the job keeps its pose
+  for (size_t k = 0; k < n_jobs; ++k)
+  {
+    std::memcpy(poses_out + 3 * k, jobs_xyt + 3 * k, 3 * sizeof(double));
+    scores_out[k] = 0.0;
+    status_out[k] = NDT2D_REFINE_NO_OVERLAP;
+    if (start_scores_out != nullptr) start_scores_out[k] = 0.0;
+    if (gradients_out != nullptr) std::memset(gradients_out + 3 * k, 0, 3 * sizeof(double));
+    if (hessians_out != nullptr) std::memset(hessians_out + 9 * k, 0, 9 * sizeof(double));
+    if (evals_out != nullptr) evals_out[2 * k] = evals_out[2 * k + 1] = 0u;
+  }
+  if (!m->ndt.have()) return NDT2D_OK;
+  discard_ahead(m);   // a search launched ahead by scoreScan is waited out and dropped
+  if (m->refine == nullptr)
+  {
+    const int rc = ndt2d_refine_create(m->dev, kRefineSlots, &m->refine);
+    if (rc != NDT2D_OK) return dev_fail(m, rc, "ndt2d_refine_create");
+  }
+  const auto scan_of = [&](size_t k) { return job_scan != nullptr ? static_cast<size_t>(job_scan[k]) : k; };
+
+  // every scan a job names as scorePoints takes it: subsampled beams (:165-166,171), once per scan.
+  // sent[s]: its index among the scans the device call receives (a scan without points is not among them)
+  constexpr uint32_t kUnseen = ~0u, kEmpty = ~0u - 1u;
+  std::vector<uint32_t> sent(n_scans, kUnseen);
+  std::vector<double> beams, one, batch_xyt;
+  std::vector<size_t> beam_offsets(1, 0);
+  std::vector<uint32_t> batch_job, batch_scan;   // the jobs of the device call and their scans
+  for (size_t k = 0; k < n_jobs; ++k)
+  {
+    const size_t sc = scan_of(k);
+    if (sent[sc] == kUnseen)
+    {
+      subsample_into(one, points_xy + 2 * point_offsets[sc], point_offsets[sc + 1] - point_offsets[sc], m->laser_max_beams);
+      if (one.empty())
+      {
+        sent[sc] = kEmpty;
+      }
+      else
+      {
+        sent[sc] = static_cast<uint32_t>(beam_offsets.size() - 1);
+        beams.insert(beams.end(), one.begin(), one.end());
+        beam_offsets.push_back(beams.size() / 2);
+      }
+    }
+    if (sent[sc] == kEmpty) continue;
+    batch_job.push_back(static_cast<uint32_t>(k));
+    batch_scan.push_back(sent[sc]);
+    batch_xyt.insert(batch_xyt.end(), jobs_xyt + 3 * k, jobs_xyt + 3 * k + 3);
+  }
+  const size_t n_batch = batch_job.size();
+  if (n_batch == 0) return NDT2D_OK;
+  constexpr size_t kRefRec = NDT2D_REFINE_RECORD_DOUBLES;
+  m->refine_records.assign(n_batch * kRefRec, 0.0);
+  const int rc = ndt2d_refine_run(m->refine, batch_xyt.data(), batch_scan.data(), n_batch, beams.data(), beam_offsets.data(),
+                                  beam_offsets.size() - 1, max_evals, tol_lin, tol_ang, m->refine_records.data());
+  if (rc != NDT2D_OK) return mfail(m, rc, std::string("refine_scans: ") + ndt2d_refine_last_error(m->refine));
+  for (size_t j = 0; j < n_batch; ++j)
+  {
+    const size_t k = batch_job[j];
+    const double * rec = m->refine_records.data() + j * kRefRec;
+    // f, g, H of the sum over the scan's N beams -> of `score / N` (:177)
+    const double n = static_cast<double>(beam_offsets[batch_scan[j] + 1] - beam_offsets[batch_scan[j]]);
+    std::memcpy(poses_out + 3 * k, rec, 3 * sizeof(double));
+    scores_out[k] = rec[4] / n;
+    status_out[k] = static_cast<int32_t>(rec[16]);
+    if (start_scores_out != nullptr) start_scores_out[k] = rec[3] / n;
+    if (gradients_out != nullptr)
+    {
+      for (int d = 0; d < 3; ++d) gradients_out[3 * k + d] = rec[5 + d] / n;
+    }
+    if (hessians_out != nullptr)
+    {
+      double * h = hessians_out + 9 * k;
+      h[0] = rec[8] / n;
+      h[1] = h[3] = rec[9] / n;
+      h[2] = h[6] = rec[10] / n;
+      h[4] = rec[11] / n;
+      h[5] = h[7] = rec[12] / n;
+      h[8] = rec[13] / n;
+    }
+    if (evals_out != nullptr)
+    {
+      evals_out[2 * k] = static_cast<uint32_t>(rec[14]);
+      evals_out[2 * k + 1] = static_cast<uint32_t>(rec[15]);
+    }
+  }
+  return NDT2D_OK;
+  NDT2D_C_CATCH(m)
+}
+
+ndt2d_refine * ndt2d_matcher_refine(ndt2d_matcher * m) { return m != nullptr ? m->refine : nullptr; }
 
 }  // extern "C"

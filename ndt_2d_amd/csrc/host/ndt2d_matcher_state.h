@@ -87,6 +87,8 @@ struct ndt2d_matcher
   std::vector<double> starts_records;      // its records, [K][NDT2D_MATCH_RECORD_DOUBLES]
   ndt2d_scans * scans = nullptr;           // batched scan tracking on the first device (made by the first match_scans)
   std::vector<double> scans_records;       // its records, [K][NDT2D_MATCH_RECORD_DOUBLES]
+  ndt2d_refine * refine = nullptr;         // Newton registration on the first device (made by the first refine_scans)
+  std::vector<double> refine_records;      // its records, [K][NDT2D_REFINE_RECORD_DOUBLES]
   int eigen_form = ndt2d::kEigenFormSchur;   // ndt2d_matcher_set_eigenvalue_form
 
   // The NDT in place: `ndt_` of the reference (scan_matcher_ndt.hpp:102) -- the grid every device of

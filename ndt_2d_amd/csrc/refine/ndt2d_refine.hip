@@ -1,0 +1,421 @@
+// Newton NDT registration of K (scan, pose) jobs against the grid INSTALLED in the context: from
+// each job's pose a damped Newton iteration on the scan's NDT score f(x, y, theta), in one upload,
+// ONE kernel launch for the whole iteration of all jobs and one read-back per chunk (gfx950 /
+// MI355X).  The objective, its ten sums and the iteration are the contract of include/ndt2d_hip.h
+// ("Newton NDT registration"); the step between two evaluations is refine/ndt2d_refine_step.h.
+//
+// Every search of the library ends on the lattice (src/scan_matcher_ndt.cpp:103-143): the pose is
+// quantised to the lattice's pitch.  This follows the gradient and Hessian of the same score from
+// a pose -- a lattice winner, an odometry guess -- to the optimum under it.
+//
+//   refine_kernel<POW2>   grid (job of the chunk), 256 threads.  An evaluation at pose (x, y,
+//       theta): thread t takes beams t, t + 256, ... of the job's scan in order, each through
+//       cell_index / InstalledMap::find / record_exponent / exp_score of the shared device
+//       functions, into ten partial sums {e, e a_0..2, e (-a_j a_k + M_jk)}; lanes reduce with
+//       wave_sum_to_last_lane, the four waves in wave order.  Thread 0 turns the sums into
+//       (f, g, H), runs the step (refine::begin / take) and leaves the trial pose with its cos /
+//       sin and a control word in LDS; the block loops until the job stops, thread 0 writes the
+//       job's record.
+//
+// The beams are read from the chunk's upload at every evaluation: a scan is at most a few KB per
+// job and stays in L2 between the evaluations of its block, so nothing is staged in LDS and a
+// scan of any length (beyond kStageBeams too) takes the same path.
+//
+// Off the grid.  cell_index gives ncell for every point outside the grid (NaN and infinite ones
+// included), bit ncell of the bitmap is 0 and record ncell exists, so no lane indexes beyond
+// either.  A job's beams are read at [beam_first, beam_first + n_beams) of the chunk's upload only;
+// both come from the host's table, checked against the offsets before anything is launched.
+//
+// Determinism.  A thread's sums are its own, lanes reduce over the DPP network, waves in wave
+// order; thread 0 alone decides.  No block waits for another, __syncthreads is the only barrier,
+// stream order the only ordering between the upload, the launch and the read-back; no polls, no
+// atomics.  A job's bits depend on its scan, its pose and the grid alone: not on the other jobs
+// or the chunking.  cos / sin of the START heading come from the host libm inside the call, those
+// of the later headings from the device's sincos.
+//
+// LDS: 4 x 10 wave sums, the pose of the evaluation with its cos / sin (5 doubles) and the control
+// word: 364 bytes.  185 vector registers, no scratch.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "ndt2d_guard.h"
+#include "ndt2d_hip.h"
+#include "batch/ndt2d_batch_search.h"
+#include "batch/ndt2d_batch_host.h"
+#include "refine/ndt2d_refine_step.h"
+
+struct ndt2d_refine : ndt2d::BatchHost
+{
+  size_t max_jobs = 0;                // slots of a chunk
+  std::vector<uint64_t> scan_first;   // scan -> its first beam within the chunk's beams (or: not sent)
+  std::vector<uint32_t> sent;         // the chunk's scans in upload order
+};
+
+namespace ndt2d
+{
+
+namespace
+{
+
+constexpr size_t kMaxScanBeams = size_t(1) << 20;   // what ndt2d_set_beams takes
+constexpr uint64_t kNotSent = ~uint64_t(0);
+constexpr uint32_t kRefineThreads = 256;
+constexpr uint32_t kRefineWaves = kRefineThreads / kWave;
+constexpr int kSums = 10;             // e | e a_0..2 | H xx, xy, xt, yy, yt, tt
+constexpr size_t kRefineRec = NDT2D_REFINE_RECORD_DOUBLES;
+
+static_assert(refine::kConverged == NDT2D_REFINE_CONVERGED && refine::kMaxEvals == NDT2D_REFINE_MAX_EVALS &&
+              refine::kStalled == NDT2D_REFINE_STALLED && refine::kNoOverlap == NDT2D_REFINE_NO_OVERLAP &&
+              refine::kNotFinite == NDT2D_REFINE_NOT_FINITE, "the step's status values are the header's");
+
+// One job of a chunk.
+struct RefineJob
+{
+  double x, y, theta;
+  uint32_t n_beams;      // of its scan
+  uint32_t pad;
+  uint64_t beam_first;   // its scan's first beam within the chunk's beams
+};
+constexpr size_t kRefineJobDoubles = 5;
+static_assert(sizeof(RefineJob) == kRefineJobDoubles * sizeof(double), "jobs travel in a buffer of doubles");
+
+struct RefineArgs
+{
+  GridDesc grid;              // geometry, cells_global, occ_bits
+  const RefineJob * jobs;     // [job of the chunk]
+  const double * trig;        // [job of the chunk][2]: cos, sin of its start heading (host libm)
+  const double * beams_xy;    // the chunk's scans, [beam][2] robot frame
+  refine::Rules rules;
+  double * records;           // [job of the chunk][NDT2D_REFINE_RECORD_DOUBLES]
+};
+
+// One beam's terms at the pose (x, y | c, s) into the thread's ten sums.  Called by every lane of
+// the wave together (exp_score tests the wave); valid = the lane holds a beam.
+template <bool POW2>
+__device__ __forceinline__ void add_terms(const GridDesc & g, const InstalledMap & map, double2 b, bool valid, double x,
+                                          double y, double c, double s, double (&sum)[kSums])
+{
+  const double qx = c * b.x - s * b.y + x;
+  const double qy = s * b.x + c * b.y + y;
+  const uint32_t cell = cell_index<POW2>(g, qx, qy);   // ncell: off the grid
+  uint32_t rank;
+  const bool found = map.find(cell, rank);
+  const bool has = valid & found;
+  const double2 * r = map.record(has ? rank : 0u);
+  const double2 m = r[0], h0 = r[1], h1 = r[2];
+  // (a lane without a record: exponent -inf, e = +0.0, and nothing is added)
+  const double e = exp_score(has ? record_exponent(m.x, m.y, h0.x, h0.y, h1.x, qx, qy) : -HUGE_VAL);
+  if (!has) return;
+  // the information matrix: the records hold h = -0.5 I (exact scaling)
+  const double i00 = -2.0 * h0.x, i01 = -2.0 * h0.y, i11 = -2.0 * h1.x;
+  const double d0 = qx - m.x, d1 = qy - m.y;
+  const double u0 = i00 * d0 + i01 * d1;
+  const double u1 = i01 * d0 + i11 * d1;
+  const double r0 = -s * b.x - c * b.y, r1 = c * b.x - s * b.y;   // dq / dtheta
+  const double w0 = -c * b.x + s * b.y, w1 = -s * b.x - c * b.y;  // d2q / dtheta2
+  const double a2 = u0 * r0 + u1 * r1;
+  const double ir0 = i00 * r0 + i01 * r1;
+  const double ir1 = i01 * r0 + i11 * r1;
+  const double m22 = (r0 * ir0 + r1 * ir1) + (u0 * w0 + u1 * w1);
+  sum[0] += e;
+  sum[1] += e * u0;
+  sum[2] += e * u1;
+  sum[3] += e * a2;
+  sum[4] += e * (-(u0 * u0) + i00);
+  sum[5] += e * (-(u0 * u1) + i01);
+  sum[6] += e * (-(u0 * a2) + ir0);
+  sum[7] += e * (-(u1 * u1) + i11);
+  sum[8] += e * (-(u1 * a2) + ir1);
+  sum[9] += e * (-(a2 * a2) + m22);
+}
+
+template <bool POW2>
+__global__ void __launch_bounds__(kRefineThreads) refine_kernel(const RefineArgs a)
+{
+  __shared__ double wave_sums[kRefineWaves][kSums];
+  __shared__ double at[5];     // the pose of the evaluation: x, y, theta, cos, sin
+  __shared__ uint32_t more;    // the control word: another evaluation is wanted
+  const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
+  const uint32_t job = blockIdx.x;
+  const RefineJob jr = a.jobs[job];   // (uniform over the block)
+  const InstalledMap map{a.grid.occ_bits, a.grid.cells_global};
+  const double2 * beams = reinterpret_cast<const double2 *>(a.beams_xy) + jr.beam_first;
+  const double start[3] = {jr.x, jr.y, jr.theta};
+  refine::State st;   // (thread 0's)
+  if (tid == 0)
+  {
+    at[0] = jr.x;
+    at[1] = jr.y;
+    at[2] = jr.theta;
+    at[3] = a.trig[2 * job];
+    at[4] = a.trig[2 * job + 1];
+  }
+  __syncthreads();
+  for (bool first = true;; first = false)
+  {
+    const double x = at[0], y = at[1], c = at[3], s = at[4];
+    double sum[kSums];
+#pragma unroll
+    for (int k = 0; k < kSums; ++k) sum[k] = 0.0;
+    // (every thread makes the same number of trips: the waves stay whole)
+    for (uint32_t b0 = 0; b0 < jr.n_beams; b0 += kRefineThreads)
+    {
+      const uint32_t b = b0 + tid;
+      const bool valid = b < jr.n_beams;
+      add_terms<POW2>(a.grid, map, beams[valid ? b : jr.n_beams - 1u], valid, x, y, c, s, sum);
+    }
+#pragma unroll
+    for (int k = 0; k < kSums; ++k) sum[k] = wave_sum_to_last_lane(sum[k]);
+    if (lane == kWave - 1)
+    {
+#pragma unroll
+      for (int k = 0; k < kSums; ++k) wave_sums[wave][k] = sum[k];
+    }
+    __syncthreads();
+    if (tid == 0)
+    {
+      double t[kSums];
+#pragma unroll
+      for (int k = 0; k < kSums; ++k)
+      {
+        t[k] = wave_sums[0][k];
+#pragma unroll
+        for (uint32_t w = 1; w < kRefineWaves; ++w) t[k] += wave_sums[w][k];
+      }
+      const refine::Eval e{-t[0], {t[1], t[2], t[3]}, {t[4], t[5], t[6], t[7], t[8], t[9]}};
+      const bool go = first ? refine::begin(st, start, e, a.rules) : refine::take(st, e, a.rules);
+      if (go)
+      {
+        double sn, cs;
+        sincos(st.trial[2], &sn, &cs);
+        at[0] = st.trial[0];
+        at[1] = st.trial[1];
+        at[2] = st.trial[2];
+        at[3] = cs;
+        at[4] = sn;
+      }
+      more = go ? 1u : 0u;
+    }
+    __syncthreads();
+    if (more == 0u) break;   // (uniform; the word is next written behind the next barrier)
+  }
+  if (tid == 0)
+  {
+    double * rec = a.records + static_cast<size_t>(job) * kRefineRec;
+    rec[0] = st.pose[0];
+    rec[1] = st.pose[1];
+    rec[2] = st.pose[2];
+    rec[3] = st.f_start;
+    rec[4] = st.at.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) rec[5 + k] = st.at.g[k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) rec[8 + k] = st.at.H[k];
+    rec[14] = static_cast<double>(st.evals);
+    rec[15] = static_cast<double>(st.steps);
+    rec[16] = static_cast<double>(st.status);
+    rec[17] = st.lambda;
+  }
+}
+
+struct RefineCall
+{
+  const double * jobs_xyt;
+  const uint32_t * job_scan;   // NULL: job k uses scan k
+  size_t n_jobs;
+  const double * beams_xy;
+  const size_t * beam_offsets;
+  size_t n_scans;
+  refine::Rules rules;
+  size_t scan_of(size_t k) const { return job_scan != nullptr ? job_scan[k] : k; }
+};
+
+// Jobs [k0, k1) of a call whose arguments have been checked.  records_out: the call's, whole.
+int refine_chunk(ndt2d_refine * s, const GridDesc & grid, size_t k0, size_t k1, const RefineCall & t, double * records_out)
+{
+  const size_t n_slots = k1 - k0;
+  hipStream_t stream = static_cast<hipStream_t>(ndt2d_get_stream(s->h));
+
+  // the scans this chunk's jobs name, each once, in the order the jobs first name them
+  s->scan_first.assign(t.n_scans, kNotSent);
+  s->sent.clear();
+  size_t n_beams = 0;
+  for (size_t k = k0; k < k1; ++k)
+  {
+    const size_t sc = t.scan_of(k);
+    if (s->scan_first[sc] == kNotSent)
+    {
+      s->scan_first[sc] = n_beams;
+      s->sent.push_back(static_cast<uint32_t>(sc));
+      n_beams += t.beam_offsets[sc + 1] - t.beam_offsets[sc];
+    }
+  }
+
+  // the one upload of the chunk: [beams | jobs | cos / sin pairs] (no lattice, no order table)
+  const StageLayout at = stage_layout(0, 0, n_beams, n_slots, kRefineJobDoubles, 0, 2 * n_slots);
+  NDT2D_BATCH_HIP(s, grow_pair(&s->h_stage, &s->d_stage, &s->stage_cap, at.total));
+  NDT2D_BATCH_HIP(s, grow_pair(&s->h_out, &s->d_out, &s->out_cap, n_slots * kRefineRec));
+  double * st = s->h_stage;
+  for (uint32_t sc : s->sent)
+  {
+    std::memcpy(st + at.beams + 2 * s->scan_first[sc], t.beams_xy + 2 * t.beam_offsets[sc],
+                2 * (t.beam_offsets[sc + 1] - t.beam_offsets[sc]) * sizeof(double));
+  }
+  for (size_t k = k0; k < k1; ++k)
+  {
+    const size_t sc = t.scan_of(k);
+    const double * p = t.jobs_xyt + 3 * k;
+    reinterpret_cast<RefineJob *>(st + at.jobs)[k - k0] =
+      RefineJob{p[0], p[1], p[2], static_cast<uint32_t>(t.beam_offsets[sc + 1] - t.beam_offsets[sc]), 0u, s->scan_first[sc]};
+    // cos / sin of the start heading from the host libm, as everywhere in this library
+    ndt2d_cos_sin(p[2], st + at.trig + 2 * (k - k0), st + at.trig + 2 * (k - k0) + 1);
+  }
+  NDT2D_BATCH_HIP(s, hipMemcpyAsync(s->d_stage, st, at.total * sizeof(double), hipMemcpyHostToDevice, stream));
+  s->timed = false;
+  if (s->timing) NDT2D_BATCH_HIP(s, hipEventRecord(s->ev[0], stream));
+
+  RefineArgs a{};
+  a.grid = grid;
+  a.jobs = reinterpret_cast<const RefineJob *>(s->d_stage + at.jobs);
+  a.trig = s->d_stage + at.trig;
+  a.beams_xy = s->d_stage + at.beams;
+  a.rules = t.rules;
+  a.records = s->d_out;
+  const dim3 blocks(static_cast<uint32_t>(n_slots)), threads(kRefineThreads);
+  if (grid.pow2 != 0) hipLaunchKernelGGL(refine_kernel<true>, blocks, threads, 0, stream, a);
+  else hipLaunchKernelGGL(refine_kernel<false>, blocks, threads, 0, stream, a);
+  NDT2D_BATCH_HIP(s, hipGetLastError());
+  if (s->timing) NDT2D_BATCH_HIP(s, hipEventRecord(s->ev[1], stream));
+  NDT2D_BATCH_HIP(s, hipMemcpyAsync(s->h_out, s->d_out, n_slots * kRefineRec * sizeof(double), hipMemcpyDeviceToHost, stream));
+  if (s->timing) NDT2D_BATCH_HIP(s, hipEventRecord(s->ev[2], stream));
+  NDT2D_BATCH_HIP(s, hipStreamSynchronize(stream));
+  s->timed = s->timing;
+  std::memcpy(records_out + k0 * kRefineRec, s->h_out, n_slots * kRefineRec * sizeof(double));
+  return NDT2D_OK;
+}
+
+}  // namespace
+
+}  // namespace ndt2d
+
+using ndt2d::batch_fail;
+
+extern "C" {
+
+int ndt2d_refine_create(ndt2d_handle h, size_t max_jobs, ndt2d_refine ** out)
+{
+  NDT2D_C_TRY
+  if (out == nullptr) return NDT2D_ERR_INVALID;
+  *out = nullptr;
+  if (h == nullptr || max_jobs == 0 || max_jobs > 4096) return NDT2D_ERR_INVALID;
+  ndt2d_refine * r = new ndt2d_refine();
+  r->h = h;
+  r->device = ndt2d_device_id(h);
+  r->max_jobs = max_jobs;
+  *out = r;
+  return NDT2D_OK;
+  NDT2D_C_CATCH(nullptr)
+}
+
+int ndt2d_refine_destroy(ndt2d_refine * r)
+{
+  NDT2D_C_TRY
+  if (r == nullptr) return NDT2D_ERR_INVALID;
+  ndt2d::batch_drain(r);
+  ndt2d::batch_release(r);
+  delete r;
+  return NDT2D_OK;
+  NDT2D_C_CATCH(nullptr)
+}
+
+const char * ndt2d_refine_last_error(ndt2d_refine * r)
+{
+  return r != nullptr ? r->err.c_str() : "null refine";
+}
+
+int ndt2d_refine_set_timing(ndt2d_refine * r, int enabled)
+{
+  NDT2D_C_TRY
+  return ndt2d::batch_set_timing(r, enabled);
+  NDT2D_C_CATCH(r)
+}
+
+int ndt2d_refine_last_ms(ndt2d_refine * r, float * kernel_ms, float * fetch_ms)
+{
+  NDT2D_C_TRY
+  return ndt2d::batch_last_ms(r, "refine", kernel_ms, fetch_ms);
+  NDT2D_C_CATCH(r)
+}
+
+int ndt2d_refine_run(ndt2d_refine * r, const double * jobs_xyt, const uint32_t * job_scan, size_t n_jobs,
+                     const double * beams_xy, const size_t * beam_offsets, size_t n_scans, uint32_t max_evals,
+                     double tol_lin, double tol_ang, double * records_out)
+{
+  NDT2D_C_TRY
+  if (r == nullptr) return NDT2D_ERR_INVALID;
+  if (n_jobs == 0) return NDT2D_OK;
+  if (jobs_xyt == nullptr || records_out == nullptr || beams_xy == nullptr || beam_offsets == nullptr)
+  {
+    return batch_fail(r, NDT2D_ERR_INVALID, "ndt2d_refine_run: null argument");
+  }
+  if (max_evals == 0) return batch_fail(r, NDT2D_ERR_INVALID, "ndt2d_refine_run: bad argument (max_evals == 0)");
+  if (!(tol_lin >= 0.0) || !(tol_ang >= 0.0) || !std::isfinite(tol_lin) || !std::isfinite(tol_ang))
+  {
+    return batch_fail(r, NDT2D_ERR_INVALID, "ndt2d_refine_run: bad argument (a tolerance is negative or not finite)");
+  }
+  if (n_jobs >= (1u << 24) || n_scans >= (1u << 24)) return batch_fail(r, NDT2D_ERR_INVALID, "ndt2d_refine_run: bad argument (n_jobs, n_scans)");
+  if (job_scan == nullptr && n_scans != n_jobs)
+  {
+    return batch_fail(r, NDT2D_ERR_INVALID, "ndt2d_refine_run: bad argument (no job_scan: job k uses scan k, n_scans must equal n_jobs)");
+  }
+  // every scan and every job is checked before anything is launched
+  for (size_t sc = 0; sc < n_scans; ++sc)
+  {
+    if (beam_offsets[sc + 1] < beam_offsets[sc])
+    {
+      return batch_fail(r, NDT2D_ERR_INVALID, "ndt2d_refine_run: scan " + std::to_string(sc) + ": beam_offsets decrease");
+    }
+    const size_t count = beam_offsets[sc + 1] - beam_offsets[sc];
+    // (what ndt2d_set_beams refuses)
+    if (count == 0 || count > ndt2d::kMaxScanBeams)
+    {
+      return batch_fail(r, NDT2D_ERR_INVALID, "ndt2d_refine_run: scan " + std::to_string(sc) + ": " + std::to_string(count) +
+                                             " beams (1 .. 2^20)");
+    }
+  }
+  for (size_t k = 0; k < n_jobs; ++k)
+  {
+    if (!std::isfinite(jobs_xyt[3 * k]) || !std::isfinite(jobs_xyt[3 * k + 1]) || !std::isfinite(jobs_xyt[3 * k + 2]))
+    {
+      return batch_fail(r, NDT2D_ERR_INVALID, "ndt2d_refine_run: job " + std::to_string(k) + ": the pose is not finite");
+    }
+    if (job_scan != nullptr && job_scan[k] >= n_scans)
+    {
+      return batch_fail(r, NDT2D_ERR_INVALID, "ndt2d_refine_run: job " + std::to_string(k) + ": scan " +
+                                             std::to_string(job_scan[k]) + " of " + std::to_string(n_scans));
+    }
+  }
+  int rc = NDT2D_OK;
+  const ndt2d::GridDesc grid = ndt2d::installed_grid(r->h, &rc);
+  if (rc != NDT2D_OK)
+  {
+    return batch_fail(r, rc, std::string("ndt2d_refine_run") + (rc == NDT2D_ERR_NO_GRID ? ": no grid"
+                                                                : rc == NDT2D_ERR_STATE ? ": the installed grid has no records"
+                                                                                        : ": no grid view"));
+  }
+  NDT2D_BATCH_HIP(r, hipSetDevice(r->device));
+  const ndt2d::RefineCall t{jobs_xyt, job_scan, n_jobs, beams_xy, beam_offsets, n_scans, {max_evals, tol_lin, tol_ang}};
+  // more jobs than slots: in chunks
+  for (size_t k0 = 0; k0 < n_jobs; k0 += r->max_jobs)
+  {
+    rc = ndt2d::refine_chunk(r, grid, k0, std::min(n_jobs, k0 + r->max_jobs), t, records_out);
+    if (rc != NDT2D_OK) return rc;
+  }
+  return NDT2D_OK;
+  NDT2D_C_CATCH(r)
+}
+
+}  // extern "C"

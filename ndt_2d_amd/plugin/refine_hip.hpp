@@ -1,0 +1,163 @@
+// Newton NDT registration for many scans at once on libndt2d_hip.so: K (scan, pose) jobs refined
+// against the NDT in place in one call (ndt2d_matcher_refine_scans, include/ndt2d_hip.h).
+//
+// Every search of the reference ends on the lattice (src/scan_matcher_ndt.cpp:103-143): with the
+// declared defaults the correction matchScan returns is quantised to 5 mm / 2.5 mrad.  A node that
+// wants the optimum under a lattice winner -- or under an odometry guess -- hands the scan and
+// that pose to refine(): a damped Newton iteration on the scan's NDT score, the whole iteration of
+// all jobs in one kernel launch.  addScan() / addJob() collect the jobs as TrackScansHip does,
+// refine() makes the one call; the poses that come back are ABSOLUTE, not corrections.
+//
+// Plain arrays over the C-ABI, as the other mirrors in this directory: nothing of ROS or Eigen.
+#ifndef NDT_2D_HIP__REFINE_HIP_HPP_
+#define NDT_2D_HIP__REFINE_HIP_HPP_
+
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "ndt2d_hip.h"
+
+namespace ndt_2d_hip
+{
+
+// One job's answer.
+struct RefinedScan
+{
+  std::size_t job;           // index into the jobs, in add order
+  std::size_t scan;          // index into the scans
+  double pose[3];            // the pose reached (absolute)
+  double score;              // scorePoints at that pose
+  double start_score;        // scorePoints at the job's own pose
+  double gradient[3];        // of the score at the pose reached
+  double hessian[9];         // row-major; the caller inverts it for a covariance
+  std::uint32_t evals;       // evaluations of the score and its derivatives
+  std::uint32_t steps;       // accepted steps
+  int status;                // NDT2D_REFINE_*
+  bool converged() const { return status == NDT2D_REFINE_CONVERGED; }
+};
+
+class RefineHip
+{
+public:
+  explicit RefineHip(ndt2d_matcher * matcher) : m_(matcher) { clear(); }
+
+  // ndt2d_refine_run's rules; the defaults are the library's.
+  void setRules(std::uint32_t max_evals, double tol_lin, double tol_ang)
+  {
+    max_evals_ = max_evals;
+    tol_lin_ = tol_lin;
+    tol_ang_ = tol_ang;
+  }
+
+  // Forget the scans and jobs collected so far.
+  void clear()
+  {
+    points_.clear();
+    offsets_.assign(1, 0);
+    jobs_.clear();
+    job_scan_.clear();
+  }
+
+  // A scan's robot-frame points; returns its index.
+  std::size_t addScan(const double * points_xy, std::size_t n_points)
+  {
+    points_.insert(points_.end(), points_xy, points_xy + 2 * n_points);
+    offsets_.push_back(points_.size() / 2);
+    return offsets_.size() - 2;
+  }
+
+  // A job: scan `scan` refined from pose_xyt.  Several jobs may name one scan: its points travel
+  // once.  Returns the job's index.
+  std::size_t addJob(std::size_t scan, const double * pose_xyt)
+  {
+    jobs_.insert(jobs_.end(), pose_xyt, pose_xyt + 3);
+    job_scan_.push_back(static_cast<std::uint32_t>(scan));
+    return job_scan_.size() - 1;
+  }
+
+  // A scan and the one job that refines it from pose_xyt.
+  std::size_t add(const double * pose_xyt, const double * points_xy, std::size_t n_points)
+  {
+    return addJob(addScan(points_xy, n_points), pose_xyt);
+  }
+
+  std::size_t jobs() const { return job_scan_.size(); }
+  std::size_t scans() const { return offsets_.size() - 1; }
+
+  // One call for every job collected; refined_out in job order.  false when the device call fails
+  // (last_error()).  The collected scans and jobs stay until clear().
+  bool refine(std::vector<RefinedScan> & refined_out)
+  {
+    refined_out.clear();
+    const std::size_t n_jobs = jobs();
+    if (n_jobs == 0) return true;
+    poses_.assign(3 * n_jobs, 0.0);
+    scores_.assign(n_jobs, 0.0);
+    start_scores_.assign(n_jobs, 0.0);
+    gradients_.assign(3 * n_jobs, 0.0);
+    hessians_.assign(9 * n_jobs, 0.0);
+    status_.assign(n_jobs, NDT2D_REFINE_NO_OVERLAP);
+    evals_.assign(2 * n_jobs, 0u);
+    if (!ok(ndt2d_matcher_refine_scans(m_, jobs_.data(), job_scan_.data(), n_jobs, points_.data(), offsets_.data(), scans(),
+                                       max_evals_, tol_lin_, tol_ang_, poses_.data(), scores_.data(), start_scores_.data(),
+                                       gradients_.data(), hessians_.data(), status_.data(), evals_.data())))
+    {
+      return false;
+    }
+    refined_out.reserve(n_jobs);
+    for (std::size_t k = 0; k < n_jobs; ++k)
+    {
+      RefinedScan r;
+      r.job = k;
+      r.scan = job_scan_[k];
+      r.score = scores_[k];
+      r.start_score = start_scores_[k];
+      for (int d = 0; d < 3; ++d)
+      {
+        r.pose[d] = poses_[3 * k + d];
+        r.gradient[d] = gradients_[3 * k + d];
+      }
+      for (int d = 0; d < 9; ++d) r.hessian[d] = hessians_[9 * k + d];
+      r.evals = evals_[2 * k];
+      r.steps = evals_[2 * k + 1];
+      r.status = status_[k];
+      refined_out.push_back(r);
+    }
+    return true;
+  }
+
+  // HIP events around the call's kernel launch and read-back (after the first refine()).
+  bool lastMs(float * kernel_ms, float * fetch_ms)
+  {
+    ndt2d_refine * r = ndt2d_matcher_refine(m_);
+    if (r == nullptr) return false;
+    return ndt2d_refine_last_ms(r, kernel_ms, fetch_ms) == NDT2D_OK;
+  }
+
+  const std::string & last_error() const { return error_; }
+
+private:
+  bool ok(int rc)
+  {
+    if (rc == NDT2D_OK) return true;
+    error_ = std::string("ndt2d error ") + std::to_string(rc) + ": " + ndt2d_matcher_last_error(m_);
+    return false;
+  }
+
+  ndt2d_matcher * m_;
+  std::uint32_t max_evals_ = 32;
+  double tol_lin_ = 1.0e-6, tol_ang_ = 1.0e-6;
+  std::vector<double> points_, jobs_;
+  std::vector<std::size_t> offsets_;
+  std::vector<std::uint32_t> job_scan_;
+  std::vector<double> poses_, scores_, start_scores_, gradients_, hessians_;
+  std::vector<std::int32_t> status_;
+  std::vector<std::uint32_t> evals_;
+  std::string error_;
+};
+
+}  // namespace ndt_2d_hip
+
+#endif  // NDT_2D_HIP__REFINE_HIP_HPP_

@@ -510,6 +510,53 @@ class ScanMatcherNDT:
         """(search_ms, reduce_ms) of the last timed matchScans (its last chunk)."""
         return self._batch_last_ms("scans")
 
+    def refineScans(self, jobs, scans, job_scan=None, max_evals=32, tol_lin=1e-6, tol_ang=1e-6):
+        """Newton NDT registration of K jobs -- (scan, pose) pairs, as matchScans takes them --
+        against the NDT in place, in one call (one upload, one kernel launch for the whole
+        iteration of all jobs, one read-back): from each job's pose to the optimum of the scan's
+        score under it (include/ndt2d_hip.h, "Newton NDT registration").  Returns one dict per job:
+        pose (absolute, not a correction), score and start_score (what scorePoints gives at the
+        pose and at the job's own), gradient[3] and hessian[3, 3] of that score, evals, steps
+        (accepted), status (_capi.REFINE_*).  No NDT, or a scan without points: score 0.0, the
+        job's own pose, status REFINE_NO_OVERLAP.  The NDT stays in place."""
+        jp = _f64(jobs, (-1, 3))
+        K = len(jp)
+        arrays = [_f64(pts, (-1, 2)) for pts in scans]
+        offsets = np.zeros(len(arrays) + 1, dtype=np.uintp)
+        if arrays:
+            offsets[1:] = np.cumsum([len(a) for a in arrays])
+        pts = np.ascontiguousarray(np.concatenate(arrays) if arrays else np.zeros((0, 2)), dtype=np.float64)
+        js, js_ptr = None, None
+        if job_scan is not None:
+            js = np.ascontiguousarray(job_scan, dtype=np.int64).reshape(-1)
+            if len(js) != K:
+                raise ValueError("refineScans: job_scan must name one scan per job")
+            if np.any(js < 0) or np.any(js >= 2 ** 32):
+                raise ValueError("refineScans: job_scan must hold scan indices")
+            js = np.ascontiguousarray(js, dtype=np.uint32)
+            js_ptr = js.ctypes.data_as(C.POINTER(C.c_uint32))
+        if not 0 <= int(max_evals) < 2 ** 32:
+            raise ValueError("refineScans: max_evals must fit 32 bits")
+        poses, scores, starts = np.zeros((K, 3)), np.zeros(K), np.zeros(K)
+        grads, hess = np.zeros((K, 3)), np.zeros((K, 3, 3))
+        status, evals = np.zeros(K, dtype=np.int32), np.zeros((K, 2), dtype=np.uint32)
+        self._check(self._L.ndt2d_matcher_refine_scans(
+            self._m, dptr(jp), js_ptr, K, dptr(pts), offsets.ctypes.data_as(C.POINTER(C.c_size_t)), len(arrays),
+            int(max_evals), float(tol_lin), float(tol_ang), dptr(poses), dptr(scores), dptr(starts), dptr(grads), dptr(hess),
+            status.ctypes.data_as(C.POINTER(C.c_int32)), evals.ctypes.data_as(C.POINTER(C.c_uint32))), "refineScans")
+        return [dict(pose=poses[k].copy(), score=float(scores[k]), start_score=float(starts[k]), gradient=grads[k].copy(),
+                     hessian=hess[k].copy(), evals=int(evals[k, 0]), steps=int(evals[k, 1]), status=int(status[k]))
+                for k in range(K)]
+
+    def refine_set_timing(self, enabled):
+        """HIP events around the Newton registration's kernel launch and read-back on / off (after
+        the first refineScans with an NDT in place: the object is made by it)."""
+        self._batch_set_timing("refine", "refineScans", enabled)
+
+    def refine_last_ms(self):
+        """(kernel_ms, fetch_ms) of the last timed refineScans (its last chunk)."""
+        return self._batch_last_ms("refine")
+
     def last_build(self):
         """How the NDT in place was built: "build/fused-small-map", "build/device", "build/host" or ""."""
         v = self._L.ndt2d_matcher_last_build(self._m)
@@ -961,3 +1008,23 @@ def track_scans(matcher, jobs, scans, job_scan=None):
         out.append(dict(job=k, scan=int(which[k]), score=float(res["score"]), correction=correction,
                         pose=correction + poses[k], covariance=res["covariance"]))
     return out
+
+
+def refine_matches(matcher, jobs, scans, job_scan=None, **kw):
+    """The lattice search, then the Newton registration from its winners: one matchScans call over
+    the (scan, pose) jobs, one refineScans call from each job's winner -- job pose + correction as
+    the reference adds it (src/ndt_mapper.cpp:557-561), the job's own pose where no lattice
+    candidate scored below 0.  kw: refineScans' max_evals, tol_lin, tol_ang.  Returns, in job
+    order, a list of dict(job, scan, match = matchScans' dict, start = the pose handed on,
+    refined = refineScans' dict, pose = refined["pose"], score = refined["score"])."""
+    poses = np.array(jobs, dtype=np.float64).reshape(-1, 3)
+    if len(poses) == 0:
+        return []
+    which = np.arange(len(poses)) if job_scan is None else np.array(job_scan, dtype=np.int64).reshape(-1)
+    matches = matcher.matchScans(poses, scans, job_scan=job_scan)
+    starts = np.array([np.array(res["pose"], dtype=np.float64) + poses[k] if res["best_index"] != _capi.NO_INDEX
+                       else poses[k] for k, res in enumerate(matches)]).reshape(-1, 3)
+    refined = matcher.refineScans(starts, scans, job_scan=job_scan, **kw)
+    return [dict(job=k, scan=int(which[k]), match=matches[k], start=starts[k].copy(), refined=refined[k],
+                 pose=np.array(refined[k]["pose"], dtype=np.float64), score=float(refined[k]["score"]))
+            for k in range(len(poses))]
