@@ -382,6 +382,22 @@ int ndt2d_scans_last_ms(ndt2d_scans * scans, float * search_ms, float * reduce_m
  * discontinuities of f (the reference's NDT has no overlapping or interpolated cells); the
  * iteration only ever accepts a pose that lowers f.
  *
+ * The neighbourhood (ndt2d_refine_set_neighbourhood: 1, the default and the objective above, or 9).
+ * With 9 a point is scored against the 3 x 3 cells round it (what NDT implementations call direct
+ * neighbours), which takes the jumps at the cell borders down by two to three orders of magnitude:
+ *     a point's own cell (gx, gy) is NDT::getIndex's; a point off the grid (NaN or infinite
+ *         included) contributes nothing
+ *     neighbour j = 0 .. 8 is (dy, dx) = (j / 3 - 1, j % 3 - 1) from the own cell; j = 4 is the own cell
+ *     a neighbour counts only if 0 <= gx + dx < size_x, 0 <= gy + dy < size_y -- clipped on
+ *         (gx, gy), never on the flat index -- and its cell can score (n >= 5)
+ *     each counting neighbour adds the ten terms above, with d = q - that cell's mean and I that
+ *         cell's information matrix; no weighting, no normalisation
+ * A job's items are (beam, neighbour) pairs, i = K beam + j for a neighbourhood of K cells; item
+ * i's ten terms are added by thread (i mod 256) in ascending i, the 256 partial sums by the same
+ * fixed tree.  For K = 1 this is the order above, and the bits are the same.  f == 0 over all
+ * items: NO_OVERLAP; f not finite -- a degenerate neighbour as well as a degenerate own cell --:
+ * NOT_FINITE.  The iteration is the same.  f / N is then no longer what scorePoints returns.
+ *
  * The iteration.
  *   1. Evaluate (f, g, H) at the start: evals = 1.  f == 0 (no beam scores): NO_OVERLAP; f not
  *      finite: NOT_FINITE; either way the pose is returned bit for bit.
@@ -415,7 +431,21 @@ int ndt2d_scans_last_ms(ndt2d_scans * scans, float * search_ms, float * reduce_m
  *            negative or not finite, job_scan == NULL with n_scans != n_jobs.  No grid:
  *            NDT2D_ERR_NO_GRID.  n_jobs == 0: NDT2D_OK, nothing done.
  *   set_timing / last_ms   HIP events around the kernel launch and the read-back of the last
- *            (chunk of a) run, off by default. */
+ *            (chunk of a) run, off by default.
+ *   set_neighbourhood / neighbourhood   cells: 1 (the default) or 9, for the later runs of this
+ *            object; anything else is NDT2D_ERR_INVALID with a message, and the value stays.
+ *   covariance   host arithmetic only: no object, no device, usable without a GPU.  H6: a
+ *            record's six entries xx, xy, xt, yy, yt, tt; cov9_out: H^-1, row-major 3 x 3, symmetric
+ *            bit for bit, by the 3 x 3 Cholesky of the iteration with lambda = 0 and no scaling.
+ *            NDT2D_ERR_STATE, cov9_out untouched: an entry of H (or of the inverse) is not finite,
+ *            or a pivot is not > 0 (H is not positive definite: the pose is no minimum of f, or a
+ *            direction is not observed).  NDT2D_ERR_INVALID: a NULL argument.
+ *            Why H^-1 is a covariance: near the optimum e = exp(-1/2 d^T I d) ~ 1 - 1/2 d^T I d, so
+ *            f ~ -N + 1/2 sum d^T I d and H -> sum J^T I J, J = dq / d(x, y, theta): the information
+ *            matrix of the point-to-distribution residuals under the map's own Gaussians.  H is
+ *            the Hessian of the SUM (the record's), not of f / N: from the matcher layer's H / N,
+ *            multiply by N first.  With neighbourhood 1 the returned H describes f only inside
+ *            the current cell pattern; a covariance is meant to be taken from neighbourhood 9. */
 #define NDT2D_REFINE_RECORD_DOUBLES 18
 #define NDT2D_REFINE_CONVERGED 0    /* the Newton step fell below the tolerances */
 #define NDT2D_REFINE_MAX_EVALS 1    /* max_evals evaluations were made */
@@ -432,6 +462,9 @@ int ndt2d_refine_run(ndt2d_refine * refine, const double * jobs_xyt, const uint3
                      double * records_out);
 int ndt2d_refine_set_timing(ndt2d_refine * refine, int enabled);
 int ndt2d_refine_last_ms(ndt2d_refine * refine, float * kernel_ms, float * fetch_ms);
+int ndt2d_refine_set_neighbourhood(ndt2d_refine * refine, uint32_t cells);
+int ndt2d_refine_neighbourhood(ndt2d_refine * refine, uint32_t * out);
+int ndt2d_refine_covariance(const double * H6, double * cov9_out);
 
 /* Upload the beam endpoints of one scan, robot frame, already subsampled to
  * min(laser_max_beams, points.size()) points by the caller
@@ -1139,6 +1172,15 @@ int ndt2d_matcher_refine_scans(ndt2d_matcher * m, const double * jobs_xyt, const
 /* The call's object (made by the first refine_scans with an NDT in place; NULL before), for
  * ndt2d_refine_set_timing / _last_ms. */
 ndt2d_refine * ndt2d_matcher_refine(ndt2d_matcher * m);
+/* The neighbourhood of the later refine_scans calls: 1 (the default) or 9 cells per point
+ * (ndt2d_refine_set_neighbourhood; anything else: NDT2D_ERR_INVALID, the value stays).  Kept in
+ * the matcher -- the call's object is only made by the first refine_scans -- and applied to every
+ * later call.  With 9, scores_out / start_scores_out are f / N of the 3 x 3 objective: no longer
+ * what score_points gives at that pose; gradients_out / hessians_out are that objective's.  For a
+ * covariance of a refined pose: ndt2d_refine_covariance of hessians_out's six entries times N (the
+ * beams in use, min(laser_max_beams, the scan's points)). */
+int ndt2d_matcher_set_refine_neighbourhood(ndt2d_matcher * m, uint32_t cells);
+int ndt2d_matcher_refine_neighbourhood(ndt2d_matcher * m, uint32_t * out);
 /* The two halves of matchScan, for sharded (multi-GPU) searches:
  * prepare_search subsamples the scan (:95-96,110), builds the offset and
  * cos/sin tables (:103-107,117,119) and uploads them -- after it,

@@ -135,6 +135,9 @@ SIGNATURES = {
     "ndt2d_refine_run": (C.c_int, [_vp, _dp, C.POINTER(_u32), _sz, _dp, _szp, _sz, _u32, _d, _d, _dp]),
     "ndt2d_refine_set_timing": (C.c_int, [_vp, C.c_int]),
     "ndt2d_refine_last_ms": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "ndt2d_refine_set_neighbourhood": (C.c_int, [_vp, _u32]),
+    "ndt2d_refine_neighbourhood": (C.c_int, [_vp, C.POINTER(_u32)]),
+    "ndt2d_refine_covariance": (C.c_int, [_dp, _dp]),
     "ndt2d_set_eigenvalue_form": (C.c_int, [_vp, C.c_char_p]),
     "ndt2d_get_grid": (C.c_int, [_vp, _dp, _sz, C.POINTER(_u32), C.POINTER(_u32), _dp, _dp, _dp]),
     "ndt2d_clear_grid": (C.c_int, [_vp]),
@@ -251,6 +254,8 @@ SIGNATURES = {
     "ndt2d_matcher_refine_scans": (C.c_int, [_vp, _dp, C.POINTER(_u32), _sz, _dp, _szp, _sz, _u32, _d, _d, _dp, _dp, _dp, _dp,
                                              _dp, C.POINTER(C.c_int32), C.POINTER(_u32)]),
     "ndt2d_matcher_refine": (_vp, [_vp]),
+    "ndt2d_matcher_set_refine_neighbourhood": (C.c_int, [_vp, _u32]),
+    "ndt2d_matcher_refine_neighbourhood": (C.c_int, [_vp, C.POINTER(_u32)]),
     "ndt2d_matcher_match_laser_scan": (C.c_int, [_vp, _dp, C.POINTER(C.c_float), _sz,
                                                  C.POINTER(LaserScan), _dp, _dp, _dp, _szp]),
     "ndt2d_matcher_prepare_search": (C.c_int, [_vp, _dp, _dp, _sz, _szp, _szp, _szp]),

@@ -447,6 +447,10 @@ int ndt2d_matcher_refine_scans(ndt2d_matcher * m, const double * jobs_xyt, const
     const int rc = ndt2d_refine_create(m->dev, kRefineSlots, &m->refine);
     if (rc != NDT2D_OK) return dev_fail(m, rc, "ndt2d_refine_create");
   }
+  if (ndt2d_refine_set_neighbourhood(m->refine, m->refine_cells) != NDT2D_OK)
+  {
+    return mfail(m, NDT2D_ERR_INTERNAL, std::string("refine_scans: ") + ndt2d_refine_last_error(m->refine));
+  }
   const auto scan_of = [&](size_t k) { return job_scan != nullptr ? static_cast<size_t>(job_scan[k]) : k; };
 
   // every scan a job names as scorePoints takes it: subsampled beams (:165-166,171), once per scan.
@@ -520,5 +524,27 @@ int ndt2d_matcher_refine_scans(ndt2d_matcher * m, const double * jobs_xyt, const
 }
 
 ndt2d_refine * ndt2d_matcher_refine(ndt2d_matcher * m) { return m != nullptr ? m->refine : nullptr; }
+
+int ndt2d_matcher_set_refine_neighbourhood(ndt2d_matcher * m, uint32_t cells)
+{
+  NDT2D_C_TRY
+  if (m == nullptr) return NDT2D_ERR_INVALID;
+  if (cells != 1 && cells != 9)
+  {
+    return mfail(m, NDT2D_ERR_INVALID, "set_refine_neighbourhood: " + std::to_string(cells) + " cells (1 or 9)");
+  }
+  m->refine_cells = cells;
+  return NDT2D_OK;
+  NDT2D_C_CATCH(m)
+}
+
+int ndt2d_matcher_refine_neighbourhood(ndt2d_matcher * m, uint32_t * out)
+{
+  NDT2D_C_TRY
+  if (m == nullptr || out == nullptr) return NDT2D_ERR_INVALID;
+  *out = m->refine_cells;
+  return NDT2D_OK;
+  NDT2D_C_CATCH(m)
+}
 
 }  // extern "C"

@@ -89,6 +89,7 @@ struct ndt2d_matcher
   std::vector<double> scans_records;       // its records, [K][NDT2D_MATCH_RECORD_DOUBLES]
   ndt2d_refine * refine = nullptr;         // Newton registration on the first device (made by the first refine_scans)
   std::vector<double> refine_records;      // its records, [K][NDT2D_REFINE_RECORD_DOUBLES]
+  uint32_t refine_cells = 1;               // the neighbourhood of the later refine_scans: 1 or 9 (set_refine_neighbourhood)
   int eigen_form = ndt2d::kEigenFormSchur;   // ndt2d_matcher_set_eigenvalue_form
 
   // The NDT in place: `ndt_` of the reference (scan_matcher_ndt.hpp:102) -- the grid every device of

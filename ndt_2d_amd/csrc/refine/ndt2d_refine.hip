@@ -16,6 +16,15 @@
 //       (f, g, H), runs the step (refine::begin / take) and leaves the trial pose with its cos /
 //       sin and a control word in LDS; the block loops until the job stops, thread 0 writes the
 //       job's record.
+//   refine_kernel<POW2, 9>   the objective over the 3 x 3 cells round a point
+//       (ndt2d_refine_set_neighbourhood): a job's items are (beam, neighbour) pairs, i = 9 beam
+//       + j, neighbour j = (dy, dx) = (j / 3 - 1, j % 3 - 1) from the beam's own cell; thread t takes
+//       items t, t + 256, ... in order, so a 100-beam scan occupies all 256 threads.  A neighbour
+//       counts when it lies on the grid -- clipped on (gx, gy), not on the flat index: at gx = 0
+//       the flat index minus one is the last cell of the row below -- and can score.  A trip in
+//       which no lane of the wave holds a counting neighbour is skipped by a wave-wide vote (it
+//       adds nothing).  CELLS = 1 is the loop above, instantiated apart: its code is the one-cell
+//       kernel's as it was.
 //
 // The beams are read from the chunk's upload at every evaluation: a scan is at most a few KB per
 // job and stays in L2 between the evaluations of its block, so nothing is staged in LDS and a
@@ -34,7 +43,7 @@
 // of the later headings from the device's sincos.
 //
 // LDS: 4 x 10 wave sums, the pose of the evaluation with its cos / sin (5 doubles) and the control
-// word: 364 bytes.  185 vector registers, no scratch.
+// word: 364 bytes.  185 vector registers, no scratch (CELLS = 9: DESIGN.md 3.13).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -50,6 +59,7 @@
 struct ndt2d_refine : ndt2d::BatchHost
 {
   size_t max_jobs = 0;                // slots of a chunk
+  uint32_t cells = 1;                 // the neighbourhood of a point: 1 (its own cell) or 9 (the 3 x 3 round it)
   std::vector<uint64_t> scan_first;   // scan -> its first beam within the chunk's beams (or: not sent)
   std::vector<uint32_t> sent;         // the chunk's scans in upload order
 };
@@ -92,15 +102,12 @@ struct RefineArgs
   double * records;           // [job of the chunk][NDT2D_REFINE_RECORD_DOUBLES]
 };
 
-// One beam's terms at the pose (x, y | c, s) into the thread's ten sums.  Called by every lane of
-// the wave together (exp_score tests the wave); valid = the lane holds a beam.
-template <bool POW2>
-__device__ __forceinline__ void add_terms(const GridDesc & g, const InstalledMap & map, double2 b, bool valid, double x,
-                                          double y, double c, double s, double (&sum)[kSums])
+// The terms of the point q = R b + t against the record of `cell` into the thread's ten sums.
+// Called by every lane of the wave together (exp_score tests the wave); valid = the lane holds an
+// item whose cell may count (cell <= ncell; ncell: the sentinel, which never scores).
+__device__ __forceinline__ void add_cell_terms(const InstalledMap & map, uint32_t cell, double2 b, bool valid, double qx,
+                                               double qy, double c, double s, double (&sum)[kSums])
 {
-  const double qx = c * b.x - s * b.y + x;
-  const double qy = s * b.x + c * b.y + y;
-  const uint32_t cell = cell_index<POW2>(g, qx, qy);   // ncell: off the grid
   uint32_t rank;
   const bool found = map.find(cell, rank);
   const bool has = valid & found;
@@ -132,7 +139,32 @@ __device__ __forceinline__ void add_terms(const GridDesc & g, const InstalledMap
   sum[9] += e * (-(a2 * a2) + m22);
 }
 
+// One beam's terms at the pose (x, y | c, s), against the cell it falls in.
 template <bool POW2>
+__device__ __forceinline__ void add_terms(const GridDesc & g, const InstalledMap & map, double2 b, bool valid, double x,
+                                          double y, double c, double s, double (&sum)[kSums])
+{
+  const double qx = c * b.x - s * b.y + x;
+  const double qy = s * b.x + c * b.y + y;
+  const uint32_t cell = cell_index<POW2>(g, qx, qy);   // ncell: off the grid
+  add_cell_terms(map, cell, b, valid, qx, qy, c, s, sum);
+}
+
+// The cell of a (beam, neighbour) item: neighbour j of the point's own cell, (dy, dx) = (j / 3 - 1,
+// j % 3 - 1).  Off the grid (the point itself, NaN and infinite ones included, or the neighbour):
+// the sentinel cell ncell, which never scores.
+template <bool POW2>
+__device__ __forceinline__ uint32_t neighbour_cell(const GridDesc & g, double qx, double qy, uint32_t j)
+{
+  const uint32_t own = cell_index<POW2>(g, qx, qy);   // ncell: off the grid
+  const uint32_t gy = own / g.size_x, gx = own - gy * g.size_x;
+  // (unsigned: gx + dx = -1 wraps to 2^32 - 1 and fails the same compare as gx + dx = size_x)
+  const uint32_t nx = gx + (j % 3u) - 1u, ny = gy + (j / 3u) - 1u;
+  const bool on = (own < g.ncell) & (nx < g.size_x) & (ny < g.size_y);
+  return on ? ny * g.size_x + nx : g.ncell;
+}
+
+template <bool POW2, uint32_t CELLS>
 __global__ void __launch_bounds__(kRefineThreads) refine_kernel(const RefineArgs a)
 {
   __shared__ double wave_sums[kRefineWaves][kSums];
@@ -161,11 +193,33 @@ __global__ void __launch_bounds__(kRefineThreads) refine_kernel(const RefineArgs
 #pragma unroll
     for (int k = 0; k < kSums; ++k) sum[k] = 0.0;
     // (every thread makes the same number of trips: the waves stay whole)
-    for (uint32_t b0 = 0; b0 < jr.n_beams; b0 += kRefineThreads)
+    if constexpr (CELLS == 1)
     {
-      const uint32_t b = b0 + tid;
-      const bool valid = b < jr.n_beams;
-      add_terms<POW2>(a.grid, map, beams[valid ? b : jr.n_beams - 1u], valid, x, y, c, s, sum);
+      for (uint32_t b0 = 0; b0 < jr.n_beams; b0 += kRefineThreads)
+      {
+        const uint32_t b = b0 + tid;
+        const bool valid = b < jr.n_beams;
+        add_terms<POW2>(a.grid, map, beams[valid ? b : jr.n_beams - 1u], valid, x, y, c, s, sum);
+      }
+    }
+    else
+    {
+      // (n_beams <= 2^20: the item count fits 32 bits with room for the last trip's stride)
+      const uint32_t n_items = CELLS * jr.n_beams;
+      for (uint32_t i0 = 0; i0 < n_items; i0 += kRefineThreads)
+      {
+        const uint32_t i = i0 + tid;
+        const bool valid = i < n_items;
+        const uint32_t beam = valid ? i / CELLS : jr.n_beams - 1u;
+        const double2 b = beams[beam];
+        const double qx = c * b.x - s * b.y + x;
+        const double qy = s * b.x + c * b.y + y;
+        const uint32_t cell = valid ? neighbour_cell<POW2>(a.grid, qx, qy, i - beam * CELLS) : a.grid.ncell;
+        uint32_t rank;
+        // no lane of the wave holds a counting neighbour: the trip adds nothing
+        if (!wave_any(map.find(cell, rank))) continue;
+        add_cell_terms(map, cell, b, valid, qx, qy, c, s, sum);
+      }
     }
 #pragma unroll
     for (int k = 0; k < kSums; ++k) sum[k] = wave_sum_to_last_lane(sum[k]);
@@ -219,6 +273,14 @@ __global__ void __launch_bounds__(kRefineThreads) refine_kernel(const RefineArgs
     rec[16] = static_cast<double>(st.status);
     rec[17] = st.lambda;
   }
+}
+
+// CELLS: the neighbourhood of a point, 1 or 9.
+template <uint32_t CELLS>
+void launch_refine(bool pow2, dim3 blocks, dim3 threads, hipStream_t stream, const RefineArgs & a)
+{
+  if (pow2) hipLaunchKernelGGL((refine_kernel<true, CELLS>), blocks, threads, 0, stream, a);
+  else hipLaunchKernelGGL((refine_kernel<false, CELLS>), blocks, threads, 0, stream, a);
 }
 
 struct RefineCall
@@ -285,8 +347,8 @@ int refine_chunk(ndt2d_refine * s, const GridDesc & grid, size_t k0, size_t k1, 
   a.rules = t.rules;
   a.records = s->d_out;
   const dim3 blocks(static_cast<uint32_t>(n_slots)), threads(kRefineThreads);
-  if (grid.pow2 != 0) hipLaunchKernelGGL(refine_kernel<true>, blocks, threads, 0, stream, a);
-  else hipLaunchKernelGGL(refine_kernel<false>, blocks, threads, 0, stream, a);
+  if (s->cells == 9) launch_refine<9>(grid.pow2 != 0, blocks, threads, stream, a);
+  else launch_refine<1>(grid.pow2 != 0, blocks, threads, stream, a);
   NDT2D_BATCH_HIP(s, hipGetLastError());
   if (s->timing) NDT2D_BATCH_HIP(s, hipEventRecord(s->ev[1], stream));
   NDT2D_BATCH_HIP(s, hipMemcpyAsync(s->h_out, s->d_out, n_slots * kRefineRec * sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -348,6 +410,40 @@ int ndt2d_refine_last_ms(ndt2d_refine * r, float * kernel_ms, float * fetch_ms)
   NDT2D_C_TRY
   return ndt2d::batch_last_ms(r, "refine", kernel_ms, fetch_ms);
   NDT2D_C_CATCH(r)
+}
+
+int ndt2d_refine_set_neighbourhood(ndt2d_refine * r, uint32_t cells)
+{
+  NDT2D_C_TRY
+  if (r == nullptr) return NDT2D_ERR_INVALID;
+  if (cells != 1 && cells != 9)
+  {
+    return batch_fail(r, NDT2D_ERR_INVALID, "ndt2d_refine_set_neighbourhood: " + std::to_string(cells) + " cells (1 or 9)");
+  }
+  r->cells = cells;
+  return NDT2D_OK;
+  NDT2D_C_CATCH(r)
+}
+
+int ndt2d_refine_neighbourhood(ndt2d_refine * r, uint32_t * out)
+{
+  NDT2D_C_TRY
+  if (r == nullptr || out == nullptr) return NDT2D_ERR_INVALID;
+  *out = r->cells;
+  return NDT2D_OK;
+  NDT2D_C_CATCH(r)
+}
+
+int ndt2d_refine_covariance(const double * H6, double * cov9_out)
+{
+  NDT2D_C_TRY
+  if (H6 == nullptr || cov9_out == nullptr) return NDT2D_ERR_INVALID;
+  const double H[6] = {H6[0], H6[1], H6[2], H6[3], H6[4], H6[5]};
+  double cov[9];
+  if (!ndt2d::refine::covariance(H, cov)) return NDT2D_ERR_STATE;   // not positive definite, or not finite
+  std::memcpy(cov9_out, cov, sizeof(cov));
+  return NDT2D_OK;
+  NDT2D_C_CATCH(nullptr)
 }
 
 int ndt2d_refine_run(ndt2d_refine * r, const double * jobs_xyt, const uint32_t * job_scan, size_t n_jobs,

@@ -95,6 +95,53 @@ NDT2D_REFINE_HD inline bool damped_solve(const double (&H)[6], const double (&g)
   return true;
 }
 
+// cov = H^-1, row-major 3 x 3, by the same Cholesky with lambda = 0 and no D scaling: H = L L^T,
+// M = L^-1, cov = M^T M.  false: an entry of H is not finite, a pivot is not > 0, or an entry of
+// the inverse is not finite; cov is then not written.  The mirrored entries are copies: cov is
+// symmetric bit for bit.
+NDT2D_REFINE_HD inline bool covariance(const double (&H)[6], double (&cov)[9])
+{
+  for (int k = 0; k < 6; ++k)
+  {
+    if (!finite_value(H[k])) return false;
+  }
+  const double a00 = H[0], a01 = H[1], a02 = H[2], a11 = H[3], a12 = H[4], a22 = H[5];
+  if (!(a00 > 0.0)) return false;
+  const double l00 = sqrt(a00);
+  const double l10 = a01 / l00;
+  const double l20 = a02 / l00;
+  const double p1 = a11 - l10 * l10;
+  if (!(p1 > 0.0)) return false;
+  const double l11 = sqrt(p1);
+  const double l21 = (a12 - l20 * l10) / l11;
+  const double p2 = (a22 - l20 * l20) - l21 * l21;
+  if (!(p2 > 0.0)) return false;
+  const double l22 = sqrt(p2);
+  // M = L^-1 (lower triangular)
+  const double m00 = 1.0 / l00, m11 = 1.0 / l11, m22 = 1.0 / l22;
+  const double m10 = -(l10 * m00) / l11;
+  const double m21 = -(l21 * m11) / l22;
+  const double m20 = -(l20 * m00 + l21 * m10) / l22;
+  const double c00 = (m00 * m00 + m10 * m10) + m20 * m20;
+  const double c01 = m10 * m11 + m20 * m21;
+  const double c02 = m20 * m22;
+  const double c11 = m11 * m11 + m21 * m21;
+  const double c12 = m21 * m22;
+  const double c22 = m22 * m22;
+  if (!finite_value(c00) || !finite_value(c01) || !finite_value(c02) || !finite_value(c11) || !finite_value(c12) ||
+      !finite_value(c22))
+  {
+    return false;
+  }
+  cov[0] = c00;
+  cov[1] = cov[3] = c01;
+  cov[2] = cov[6] = c02;
+  cov[4] = c11;
+  cov[5] = cov[7] = c12;
+  cov[8] = c22;
+  return true;
+}
+
 // lambda after a failure (a pivot, or a trial that did not lower f); false: stalled.
 NDT2D_REFINE_HD inline bool raise_lambda(State & s)
 {

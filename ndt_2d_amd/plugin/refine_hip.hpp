@@ -8,6 +8,11 @@
 // all jobs in one kernel launch.  addScan() / addJob() collect the jobs as TrackScansHip does,
 // refine() makes the one call; the poses that come back are ABSOLUTE, not corrections.
 //
+// setNeighbourhood(9) scores a point against the 3 x 3 cells round it instead of the one it falls
+// in: the objective is then smooth across the cell borders to two or three orders of magnitude,
+// and the inverse of its Hessian is the covariance a constraint wants (RefinedScan::covariance,
+// include/ndt2d_hip.h at ndt2d_refine_covariance).
+//
 // Plain arrays over the C-ABI, as the other mirrors in this directory: nothing of ROS or Eigen.
 #ifndef NDT_2D_HIP__REFINE_HIP_HPP_
 #define NDT_2D_HIP__REFINE_HIP_HPP_
@@ -31,7 +36,10 @@ struct RefinedScan
   double score;              // scorePoints at that pose
   double start_score;        // scorePoints at the job's own pose
   double gradient[3];        // of the score at the pose reached
-  double hessian[9];         // row-major; the caller inverts it for a covariance
+  double hessian[9];         // row-major, of the score (the sum's Hessian / beams)
+  std::size_t beams;         // the scan's beams in use: min(laser_max_beams, its points)
+  double covariance[9];      // row-major inverse of hessian x beams (x, y, theta); valid if has_covariance
+  bool has_covariance;       // false: that Hessian is not positive definite (or the job did not run)
   std::uint32_t evals;       // evaluations of the score and its derivatives
   std::uint32_t steps;       // accepted steps
   int status;                // NDT2D_REFINE_*
@@ -50,6 +58,17 @@ public:
     tol_lin_ = tol_lin;
     tol_ang_ = tol_ang;
   }
+
+  // Cells a point is scored against: 1 (its own, the default) or 9 (the 3 x 3 round it), from the
+  // next refine() on.  laser_max_beams: the matcher's (initialize), which the covariance needs to
+  // turn the score's Hessian back into the sum's.  false: refused (last_error()).
+  bool setNeighbourhood(std::uint32_t cells) { return ok(ndt2d_matcher_set_refine_neighbourhood(m_, cells)); }
+  std::uint32_t neighbourhood()
+  {
+    std::uint32_t cells = 0;
+    return ok(ndt2d_matcher_refine_neighbourhood(m_, &cells)) ? cells : 0u;
+  }
+  void setLaserMaxBeams(std::size_t laser_max_beams) { laser_max_beams_ = laser_max_beams; }
 
   // Forget the scans and jobs collected so far.
   void clear()
@@ -123,6 +142,13 @@ public:
       r.evals = evals_[2 * k];
       r.steps = evals_[2 * k + 1];
       r.status = status_[k];
+      const std::size_t points = offsets_[r.scan + 1] - offsets_[r.scan];
+      r.beams = points < laser_max_beams_ ? points : laser_max_beams_;
+      double sum_hessian[6];
+      const int upper[6] = {0, 1, 2, 4, 5, 8};   // xx, xy, xt, yy, yt, tt
+      for (int d = 0; d < 6; ++d) sum_hessian[d] = r.hessian[upper[d]] * static_cast<double>(r.beams);
+      for (int d = 0; d < 9; ++d) r.covariance[d] = 0.0;
+      r.has_covariance = r.evals > 0 && ndt2d_refine_covariance(sum_hessian, r.covariance) == NDT2D_OK;
       refined_out.push_back(r);
     }
     return true;
@@ -149,6 +175,7 @@ private:
   ndt2d_matcher * m_;
   std::uint32_t max_evals_ = 32;
   double tol_lin_ = 1.0e-6, tol_ang_ = 1.0e-6;
+  std::size_t laser_max_beams_ = 100;   // the plugin's declared default
   std::vector<double> points_, jobs_;
   std::vector<std::size_t> offsets_;
   std::vector<std::uint32_t> job_scan_;

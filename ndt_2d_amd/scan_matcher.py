@@ -510,15 +510,24 @@ class ScanMatcherNDT:
         """(search_ms, reduce_ms) of the last timed matchScans (its last chunk)."""
         return self._batch_last_ms("scans")
 
-    def refineScans(self, jobs, scans, job_scan=None, max_evals=32, tol_lin=1e-6, tol_ang=1e-6):
+    def refineScans(self, jobs, scans, job_scan=None, max_evals=32, tol_lin=1e-6, tol_ang=1e-6, neighbourhood=1):
         """Newton NDT registration of K jobs -- (scan, pose) pairs, as matchScans takes them --
         against the NDT in place, in one call (one upload, one kernel launch for the whole
         iteration of all jobs, one read-back): from each job's pose to the optimum of the scan's
         score under it (include/ndt2d_hip.h, "Newton NDT registration").  Returns one dict per job:
         pose (absolute, not a correction), score and start_score (what scorePoints gives at the
         pose and at the job's own), gradient[3] and hessian[3, 3] of that score, evals, steps
-        (accepted), status (_capi.REFINE_*).  No NDT, or a scan without points: score 0.0, the
-        job's own pose, status REFINE_NO_OVERLAP.  The NDT stays in place."""
+        (accepted), status (_capi.REFINE_*), covariance.  No NDT, or a scan without points: score
+        0.0, the job's own pose, status REFINE_NO_OVERLAP.  The NDT stays in place.
+
+        neighbourhood: 1 (a point is scored against the cell it falls in: scorePoints' objective,
+        whose cell borders are jumps of f) or 9 (against the 3 x 3 cells round it: score,
+        start_score, gradient and hessian are then that objective's, and score is no longer what
+        scorePoints gives).  It is set on the matcher for this call and stays
+        (set_refine_neighbourhood).  covariance: the inverse of hessian x N (the sum's Hessian, N
+        the scan's beams in use) through ndt2d_refine_covariance, a [3, 3] array -- or None where
+        that Hessian is not positive definite; meant to be taken with neighbourhood 9."""
+        self.set_refine_neighbourhood(neighbourhood)
         jp = _f64(jobs, (-1, 3))
         K = len(jp)
         arrays = [_f64(pts, (-1, 2)) for pts in scans]
@@ -544,9 +553,25 @@ class ScanMatcherNDT:
             self._m, dptr(jp), js_ptr, K, dptr(pts), offsets.ctypes.data_as(C.POINTER(C.c_size_t)), len(arrays),
             int(max_evals), float(tol_lin), float(tol_ang), dptr(poses), dptr(scores), dptr(starts), dptr(grads), dptr(hess),
             status.ctypes.data_as(C.POINTER(C.c_int32)), evals.ctypes.data_as(C.POINTER(C.c_uint32))), "refineScans")
-        return [dict(pose=poses[k].copy(), score=float(scores[k]), start_score=float(starts[k]), gradient=grads[k].copy(),
-                     hessian=hess[k].copy(), evals=int(evals[k, 0]), steps=int(evals[k, 1]), status=int(status[k]))
-                for k in range(K)]
+        beams_max = int(self.params["laser_max_beams"])
+        out = []
+        for k in range(K):
+            n = min(beams_max, len(arrays[int(js[k]) if js is not None else k]))
+            out.append(dict(pose=poses[k].copy(), score=float(scores[k]), start_score=float(starts[k]), gradient=grads[k].copy(),
+                            hessian=hess[k].copy(), evals=int(evals[k, 0]), steps=int(evals[k, 1]), status=int(status[k]),
+                            covariance=refine_covariance(hess[k] * float(n))))
+        return out
+
+    def set_refine_neighbourhood(self, cells):
+        """The neighbourhood of the later refineScans calls: 1 or 9 cells per point."""
+        if not 0 <= int(cells) < 2 ** 32:
+            raise ValueError("set_refine_neighbourhood: 1 or 9 cells")
+        self._check(self._L.ndt2d_matcher_set_refine_neighbourhood(self._m, int(cells)), "set_refine_neighbourhood")
+
+    def refine_neighbourhood(self):
+        out = C.c_uint32(0)
+        self._check(self._L.ndt2d_matcher_refine_neighbourhood(self._m, C.byref(out)), "refine_neighbourhood")
+        return int(out.value)
 
     def refine_set_timing(self, enabled):
         """HIP events around the Newton registration's kernel launch and read-back on / off (after
@@ -1010,11 +1035,29 @@ def track_scans(matcher, jobs, scans, job_scan=None):
     return out
 
 
+def refine_covariance(hessian):
+    """H^-1 through ndt2d_refine_covariance (host arithmetic, no device): hessian is the SUM's
+    Hessian, a [3, 3] array or the record's six entries xx, xy, xt, yy, yt, tt.  A [3, 3] array, or
+    None where H is not positive definite or not finite."""
+    h = np.asarray(hessian, dtype=np.float64)
+    if h.size == 9:
+        h = h.reshape(3, 3)
+        h = np.array([h[0, 0], h[0, 1], h[0, 2], h[1, 1], h[1, 2], h[2, 2]])
+    h6 = np.ascontiguousarray(h.reshape(6), dtype=np.float64)
+    cov = np.zeros(9)
+    rc = _capi.lib().ndt2d_refine_covariance(dptr(h6), dptr(cov))
+    if rc == _capi.OK:
+        return cov.reshape(3, 3)
+    if rc == _capi.ERR_STATE:
+        return None
+    raise Ndt2dError(rc, "ndt2d_refine_covariance", "")
+
+
 def refine_matches(matcher, jobs, scans, job_scan=None, **kw):
     """The lattice search, then the Newton registration from its winners: one matchScans call over
     the (scan, pose) jobs, one refineScans call from each job's winner -- job pose + correction as
     the reference adds it (src/ndt_mapper.cpp:557-561), the job's own pose where no lattice
-    candidate scored below 0.  kw: refineScans' max_evals, tol_lin, tol_ang.  Returns, in job
+    candidate scored below 0.  kw: refineScans' max_evals, tol_lin, tol_ang, neighbourhood.  Returns, in job
     order, a list of dict(job, scan, match = matchScans' dict, start = the pose handed on,
     refined = refineScans' dict, pose = refined["pose"], score = refined["score"])."""
     poses = np.array(jobs, dtype=np.float64).reshape(-1, 3)
