@@ -466,6 +466,45 @@ int ndt2d_refine_set_neighbourhood(ndt2d_refine * refine, uint32_t cells);
 int ndt2d_refine_neighbourhood(ndt2d_refine * refine, uint32_t * out);
 int ndt2d_refine_covariance(const double * H6, double * cov9_out);
 
+/* ---- Newton NDT registration on each loop-closure candidate's own map (csrc/closure/) ----
+ *
+ * The loop-closure constraint (makeConstraint, src/ndt_mapper.cpp:658) is matched against a
+ * candidate's own map of one or two old scans, which ndt2d_closure_match builds in the closure's
+ * buffers and drops.  ndt2d_closure_refine runs the registration above on such maps: per chunk
+ * one upload, the build launch of ndt2d_closure_match for the candidates the jobs name (a
+ * candidate no job names is not built), ONE launch of the refinement -- a workgroup per job, on
+ * the packed records and the cell -> record table of its candidate's slot -- and one read-back.
+ * The kernel is the one of ndt2d_refine_run (csrc/refine/ndt2d_refine.hip), instantiated on the
+ * slots; nothing of the grid installed in the context is read or changed.
+ *
+ *   candidates   cand_offsets, ids, poses_xyt, ndt_resolution, range_max as ndt2d_closure_match
+ *                takes them, with everything it refuses about a candidate.
+ *   scans, jobs  beams_xy, beam_offsets, n_scans, jobs_xyt, job_scan, max_evals, tol_lin, tol_ang
+ *                as ndt2d_refine_run takes them, with everything it refuses; job_candidate[k]: the
+ *                candidate job k is refined on (NULL: job k uses candidate k, n_jobs must equal
+ *                n_candidates).  A job_scan or job_candidate out of range: NDT2D_ERR_INVALID, the
+ *                message names the job, nothing is launched.
+ *   records_out  [n_jobs][NDT2D_REFINE_RECORD_DOUBLES] in ndt2d_refine_run's layout, in job order.
+ *   bits         a job's record has the bits ndt2d_refine_run gives for the same scan and pose on
+ *                the grid ndt2d_scanstore_build installs for the candidate, neighbourhood for
+ *                neighbourhood; it depends on its scan, its pose and its candidate's scans and
+ *                poses alone, not on the other jobs or the chunks.
+ *   chunks       candidates in ascending index among those named, at most max_candidates
+ *                (ndt2d_closure_create) candidates and 4,096 jobs a launch; a candidate with more
+ *                jobs continues in launches of its own (csrc/closure/ndt2d_closure_jobs.h).
+ *   set_neighbourhood / neighbourhood   1 (the default) or 9 cells per point, the rule of
+ *                ndt2d_refine_set_neighbourhood.
+ *   ndt2d_closure_last_ms   reports the last call of either kind: the build, and the launch
+ *                behind it (the search of a match, the refinement of a refine). */
+int ndt2d_closure_refine(ndt2d_closure * closure, size_t n_candidates, const size_t * cand_offsets,
+                         const size_t * ids, const double * poses_xyt, double ndt_resolution,
+                         double range_max, const double * jobs_xyt, const uint32_t * job_scan,
+                         const uint32_t * job_candidate, size_t n_jobs, const double * beams_xy,
+                         const size_t * beam_offsets, size_t n_scans, uint32_t max_evals,
+                         double tol_lin, double tol_ang, double * records_out);
+int ndt2d_closure_set_neighbourhood(ndt2d_closure * closure, uint32_t cells);
+int ndt2d_closure_neighbourhood(ndt2d_closure * closure, uint32_t * out);
+
 /* Upload the beam endpoints of one scan, robot frame, already subsampled to
  * min(laser_max_beams, points.size()) points by the caller
  * (src/scan_matcher_ndt.cpp:95-96,110 / :165-166,171).  Beams are taken as given: finite,
@@ -1181,6 +1220,28 @@ ndt2d_refine * ndt2d_matcher_refine(ndt2d_matcher * m);
  * beams in use, min(laser_max_beams, the scan's points)). */
 int ndt2d_matcher_set_refine_neighbourhood(ndt2d_matcher * m, uint32_t cells);
 int ndt2d_matcher_refine_neighbourhood(ndt2d_matcher * m, uint32_t * out);
+/* Newton NDT registration of K jobs, each on a loop-closure candidate's OWN map, in one call
+ * (ndt2d_closure_refine on the first device, with the matcher's resolution, range_max and stored
+ * scans): what reset() + add_scans_by_id(candidate) + refine_scans(job) gives per job, bit for bit,
+ * without the K builds, installs, launches and read-backs -- and without touching the NDT in
+ * place: has_ndt and the grid are the same before and after.  Candidates as match_candidates
+ * takes them; scans, jobs, job_scan and the outputs as refine_scans takes them; job_candidate[k]:
+ * the candidate of job k (NULL: job k uses candidate k, n_jobs must equal n_candidates).  Each
+ * scan a job names is subsampled once with laser_max_beams; set_refine_neighbourhood governs this
+ * call too.  Jobs of a scan without points: status NO_OVERLAP, score 0.0, their own pose.  A
+ * search launched ahead by score_scan is waited out and dropped first.  NDT2D_ERR_INVALID,
+ * nothing launched: everything match_candidates refuses about a candidate, everything
+ * refine_scans refuses about scans, jobs and rules, a job_candidate out of range ("job k"); a
+ * refused call leaves the output arrays as they were. */
+int ndt2d_matcher_refine_candidates(ndt2d_matcher * m, const size_t * cand_offsets, const size_t * ids,
+                                    const double * poses_xyt, size_t n_candidates,
+                                    const double * jobs_xyt, const uint32_t * job_scan,
+                                    const uint32_t * job_candidate, size_t n_jobs,
+                                    const double * points_xy, const size_t * point_offsets,
+                                    size_t n_scans, uint32_t max_evals, double tol_lin, double tol_ang,
+                                    double * poses_out, double * scores_out, double * start_scores_out,
+                                    double * gradients_out, double * hessians_out, int32_t * status_out,
+                                    uint32_t * evals_out);
 /* The two halves of matchScan, for sharded (multi-GPU) searches:
  * prepare_search subsamples the scan (:95-96,110), builds the offset and
  * cos/sin tables (:103-107,117,119) and uploads them -- after it,

@@ -114,6 +114,10 @@ SIGNATURES = {
     "ndt2d_closure_last_error": (C.c_char_p, [_vp]),
     "ndt2d_closure_match": (C.c_int, [_vp, _sz, _szp, _szp, _dp, _d, _d, _dp, _sz, _d, _d, _dp, _dp, _dp, _sz,
                                      _dp, _sz, _dp, _dp]),
+    "ndt2d_closure_refine": (C.c_int, [_vp, _sz, _szp, _szp, _dp, _d, _d, _dp, C.POINTER(_u32), C.POINTER(_u32), _sz, _dp, _szp, _sz,
+                                       _u32, _d, _d, _dp]),
+    "ndt2d_closure_set_neighbourhood": (C.c_int, [_vp, _u32]),
+    "ndt2d_closure_neighbourhood": (C.c_int, [_vp, C.POINTER(_u32)]),
     "ndt2d_closure_set_timing": (C.c_int, [_vp, C.c_int]),
     "ndt2d_closure_last_ms": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "ndt2d_grid_view_get": (C.c_int, [_vp, _vp]),
@@ -253,6 +257,9 @@ SIGNATURES = {
     "ndt2d_matcher_scans": (_vp, [_vp]),
     "ndt2d_matcher_refine_scans": (C.c_int, [_vp, _dp, C.POINTER(_u32), _sz, _dp, _szp, _sz, _u32, _d, _d, _dp, _dp, _dp, _dp,
                                              _dp, C.POINTER(C.c_int32), C.POINTER(_u32)]),
+    "ndt2d_matcher_refine_candidates": (C.c_int, [_vp, _szp, _szp, _dp, _sz, _dp, C.POINTER(_u32), C.POINTER(_u32), _sz, _dp, _szp,
+                                                  _sz, _u32, _d, _d, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32),
+                                                  C.POINTER(_u32)]),
     "ndt2d_matcher_refine": (_vp, [_vp]),
     "ndt2d_matcher_set_refine_neighbourhood": (C.c_int, [_vp, _u32]),
     "ndt2d_matcher_refine_neighbourhood": (C.c_int, [_vp, C.POINTER(_u32)]),

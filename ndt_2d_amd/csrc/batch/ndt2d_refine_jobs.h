@@ -1,0 +1,92 @@
+// What the Newton registrations share on the host (refine/ndt2d_refine.hip: jobs on the installed
+// grid; closure/ndt2d_closure.hip: jobs on the loop closure's candidate maps): what both refuse
+// about rules, scans and jobs -- one text, so that the two objects cannot drift apart in what they
+// refuse -- and which scans a chunk uploads.  Plain C++: no HIP.
+#ifndef NDT2D_REFINE_JOBS_H_
+#define NDT2D_REFINE_JOBS_H_
+
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+namespace ndt2d
+{
+
+namespace refine_jobs
+{
+
+constexpr size_t kMaxScanBeams = size_t(1) << 20;   // what ndt2d_set_beams takes
+constexpr uint64_t kNotSent = ~uint64_t(0);
+
+// The rules, every scan and every job of a call, checked before anything is launched.  Returns
+// the refusal's text, prefixed with `entry` (the message names the scan or the job), or an empty
+// string.  job_scan NULL: job k uses scan k.
+inline std::string refusal(const char * entry, const double * jobs_xyt, const uint32_t * job_scan, size_t n_jobs,
+                           const size_t * beam_offsets, size_t n_scans, uint32_t max_evals, double tol_lin, double tol_ang)
+{
+  const std::string who = std::string(entry) + ": ";
+  if (max_evals == 0) return who + "bad argument (max_evals == 0)";
+  if (!(tol_lin >= 0.0) || !(tol_ang >= 0.0) || !std::isfinite(tol_lin) || !std::isfinite(tol_ang))
+  {
+    return who + "bad argument (a tolerance is negative or not finite)";
+  }
+  if (n_jobs >= (1u << 24) || n_scans >= (1u << 24)) return who + "bad argument (n_jobs, n_scans)";
+  if (job_scan == nullptr && n_scans != n_jobs)
+  {
+    return who + "bad argument (no job_scan: job k uses scan k, n_scans must equal n_jobs)";
+  }
+  for (size_t sc = 0; sc < n_scans; ++sc)
+  {
+    if (beam_offsets[sc + 1] < beam_offsets[sc]) return who + "scan " + std::to_string(sc) + ": beam_offsets decrease";
+    const size_t count = beam_offsets[sc + 1] - beam_offsets[sc];
+    // (what ndt2d_set_beams refuses)
+    if (count == 0 || count > kMaxScanBeams)
+    {
+      return who + "scan " + std::to_string(sc) + ": " + std::to_string(count) + " beams (1 .. 2^20)";
+    }
+  }
+  for (size_t k = 0; k < n_jobs; ++k)
+  {
+    if (!std::isfinite(jobs_xyt[3 * k]) || !std::isfinite(jobs_xyt[3 * k + 1]) || !std::isfinite(jobs_xyt[3 * k + 2]))
+    {
+      return who + "job " + std::to_string(k) + ": the pose is not finite";
+    }
+    if (job_scan != nullptr && job_scan[k] >= n_scans)
+    {
+      return who + "job " + std::to_string(k) + ": scan " + std::to_string(job_scan[k]) + " of " + std::to_string(n_scans);
+    }
+  }
+  return std::string();
+}
+
+// The scans a chunk's jobs name, each once, in the order the jobs first name them: scan_first[s] =
+// the scan's first beam within the chunk's beams (kNotSent: not sent), sent = the scans in upload
+// order.  jobs[0 .. n): the chunk's jobs, as indices into the call's; scan_of(k): job k's scan.
+// Returns the chunk's beam count.
+template <class JOB_AT, class SCAN_OF>
+inline size_t plan_sent_scans(size_t n, JOB_AT job_at, SCAN_OF scan_of, const size_t * beam_offsets, size_t n_scans,
+                              std::vector<uint64_t> & scan_first, std::vector<uint32_t> & sent)
+{
+  scan_first.assign(n_scans, kNotSent);
+  sent.clear();
+  size_t n_beams = 0;
+  for (size_t b = 0; b < n; ++b)
+  {
+    const size_t sc = scan_of(job_at(b));
+    if (scan_first[sc] == kNotSent)
+    {
+      scan_first[sc] = n_beams;
+      sent.push_back(static_cast<uint32_t>(sc));
+      n_beams += beam_offsets[sc + 1] - beam_offsets[sc];
+    }
+  }
+  return n_beams;
+}
+
+}  // namespace refine_jobs
+
+}  // namespace ndt2d
+
+#endif  // NDT2D_REFINE_JOBS_H_

@@ -1,5 +1,6 @@
 // Batched loop-closure match: ONE scan against K candidate maps in one build launch, one search
-// launch, one reduction launch and one read-back (gfx950 / MI355X).
+// launch, one reduction launch and one read-back (gfx950 / MI355X) -- and the Newton NDT
+// registration of K (scan, pose) jobs on such maps in one build launch and one refinement launch.
 //
 // Reference: the loop-closure thread, src/ndt_mapper.cpp:619-671 -- per candidate scan `reset()`,
 // `addScans(begin, end)` of one or two old scans, `matchScan(scan, ...)`.  Through the matcher
@@ -25,6 +26,15 @@
 //       search is 80 x 7 tiles.
 //   batch_reduce_kernel    one block per candidate map: the n_theta records of its blocks ->
 //       {best_score, best_index (+0.5: near tie), acc[10]} with merge_best, fixed order.
+//
+//   refine_kernel<POW2, CELLS, SlotSource> (../refine/ndt2d_refine.hip, its device half included
+//       here)  ndt2d_closure_refine: the Newton NDT registration of K jobs, each on its
+//       candidate's own map -- behind the same build launch, ONE launch with a workgroup of 256
+//       threads per job, which reads its slot's table and records through SlotSource and nothing of
+//       the grid installed in the context.  Which candidates a launch builds and which jobs run on
+//       them is ndt2d_closure_jobs.h's plan; a job's record has the bits ndt2d_refine_run gives on
+//       the grid ndt2d_scanstore_build installs for the candidate (the build is the fused build's
+//       workgroup, the kernel has one text).
 //
 // The bits of a raw score.  The small-lattice search (ndt2d_match_small.hip) -- the one every
 // loop-closure-size lattice takes -- cuts a candidate's beams into look-up groups of four and
@@ -52,6 +62,11 @@
 #include "ndt2d_hip.h"
 #include "batch/ndt2d_batch_search.h"
 #include "batch/ndt2d_batch_host.h"
+#include "batch/ndt2d_refine_jobs.h"
+#include "closure/ndt2d_closure_jobs.h"
+// (the Newton registration's kernel -- its device half, without the installed grid's object and entry points)
+#define NDT2D_REFINE_KERNEL_ONLY
+#include "refine/ndt2d_refine.hip"
 
 namespace ndt2d
 {
@@ -169,6 +184,33 @@ struct ClosureSlots
   }
 };
 
+// SOURCE of the Newton registration (../refine/ndt2d_refine.hip): a job's map is the slot its
+// record names -- the slot's own geometry, table and records.  Nothing of the context's installed
+// grid is read: the slots' GridDesc hold geometry only.  Entry ncell of a slot's table is 0xffff
+// (closure_build_kernel), so an off-grid point or neighbour finds no record.
+struct SlotSource
+{
+  const ClosureSlot * slots;
+  const uint16_t * lookup;
+  const double * records;
+  __device__ __forceinline__ const GridDesc & grid(uint32_t slot) const { return slots[slot].grid; }
+  __device__ __forceinline__ SlotMap map(uint32_t slot) const
+  {
+    const ClosureSlot & s = slots[slot];
+    return SlotMap{lookup + s.lookup_off, records + 6 * static_cast<size_t>(s.list_off)};
+  }
+};
+
+using SlotRefineArgs = RefineArgs<SlotSource>;
+
+// CELLS: the neighbourhood of a point, 1 or 9.  pow2: of every slot (they share the call's resolution).
+template <uint32_t CELLS>
+void launch_slot_refine(bool pow2, dim3 blocks, dim3 threads, hipStream_t stream, const SlotRefineArgs & a)
+{
+  if (pow2) hipLaunchKernelGGL((refine_kernel<true, CELLS, SlotSource>), blocks, threads, 0, stream, a);
+  else hipLaunchKernelGGL((refine_kernel<false, CELLS, SlotSource>), blocks, threads, 0, stream, a);
+}
+
 }  // namespace
 
 }  // namespace ndt2d
@@ -186,6 +228,11 @@ struct ndt2d_closure : ndt2d::BatchHost
   size_t world_cap = 0, cells6_cap = 0, records_cap = 0, index_cap = 0, lookup_cap = 0;
   uint32_t * d_n_touched = nullptr;
   std::vector<ndt2d::ClosureSlot> slots;
+  // ndt2d_closure_refine
+  uint32_t cells = 1;                 // the neighbourhood of a point: 1 (its own cell) or 9 (the 3 x 3 round it)
+  std::vector<uint64_t> scan_first;   // scan -> its first beam within the chunk's beams (or: not sent)
+  std::vector<uint32_t> sent;         // the chunk's scans in upload order
+  std::vector<ndt2d::ClosureSlot> chunk_slots;
 };
 
 namespace
@@ -220,6 +267,78 @@ struct SearchTables
   const double * dlin;
   size_t n_lin;
 };
+
+// What every entry point refuses about a candidate (the message names it); c->slots[k]: candidate
+// k's geometry and counts.
+int check_candidates(ndt2d_closure * c, const char * entry, size_t n_candidates, const size_t * cand_offsets,
+                     const size_t * ids, const double * poses_xyt, double ndt_resolution, double range_max)
+{
+  const ndt2d_scanstore * store = c->store;
+  c->slots.assign(n_candidates, ClosureSlot{});
+  for (size_t k = 0; k < n_candidates; ++k)
+  {
+    const std::string who = std::string(entry) + ": candidate " + std::to_string(k);
+    if (cand_offsets[k + 1] < cand_offsets[k] || cand_offsets[k + 1] - cand_offsets[0] >= (1u << 28))
+    {
+      return batch_fail(c, NDT2D_ERR_INVALID, who + ": offsets must not decrease");
+    }
+    const size_t j0 = cand_offsets[k], j1 = cand_offsets[k + 1];
+    if (j1 == j0) return batch_fail(c, NDT2D_ERR_INVALID, who + " has no scans");
+    size_t n_points = 0;
+    for (size_t j = j0; j < j1; ++j)
+    {
+      if (ids[j] >= store->count.size())
+      {
+        return batch_fail(c, NDT2D_ERR_INVALID, who + ": unknown scan id " + std::to_string(ids[j]));
+      }
+      if (!std::isfinite(poses_xyt[3 * j]) || !std::isfinite(poses_xyt[3 * j + 1]) || !std::isfinite(poses_xyt[3 * j + 2]))
+      {
+        return batch_fail(c, NDT2D_ERR_INVALID, who + ": a scan pose is not finite");
+      }
+      n_points += store->count[ids[j]];
+    }
+    ClosureSlot & s = c->slots[k];
+    if (!ndt2d::fused::addscans_geometry(ndt_resolution, range_max, poses_xyt + 3 * j0, j1 - j0, &s.grid))
+    {
+      return batch_fail(c, NDT2D_ERR_INVALID, who + ": degenerate grid extent");
+    }
+    if (!ndt2d::fused::small_map_fits(s.grid, n_points) || s.grid.ncell == 0)
+    {
+      return batch_fail(c, NDT2D_ERR_INVALID, who + ": the map exceeds the fused build's limits (" + std::to_string(n_points) +
+                                           " points of at most " + std::to_string(ndt2d::fused::kFusedMaxPoints) + ", " +
+                                           std::to_string(s.grid.ncell) + " cells of fewer than 65535)");
+    }
+    s.n_scans = static_cast<uint32_t>(j1 - j0);
+    s.n_points = static_cast<uint32_t>(n_points);
+    s.sort_passes = ndt2d::fused::sort_passes_for(s.grid.ncell);
+  }
+  return NDT2D_OK;
+}
+
+// The build launch of a chunk whose stage has been uploaded: a workgroup per slot.  *b: what was
+// launched (the search and the refinement read its records and table).
+int launch_build(ndt2d_closure * c, hipStream_t stream, size_t n_slots, const ClosureSlot * d_slots,
+                 const SmallScan * d_scans, ndt2d::ClosureBuildArgs * b)
+{
+  const ndt2d_scanstore * store = c->store;
+  b->slots = d_slots;
+  b->pool_xy = store->pool;
+  b->scans = d_scans;
+  b->world_xy = static_cast<double *>(c->d_world);
+  b->cells6 = static_cast<double *>(c->d_cells6);
+  b->records = static_cast<double *>(c->d_records);
+  b->index = static_cast<uint32_t *>(c->d_index);
+  b->lookup = static_cast<uint16_t *>(c->d_lookup);
+  b->n_touched = c->d_n_touched;
+  b->eigen_form = store->eigen_form;
+  // (no static LDS in front of the workgroup's arrays: prepare_absolute_lds_kernel, ndt2d_kernels.h)
+  NDT2D_BATCH_HIP(c, ndt2d::prepare_absolute_lds_kernel(reinterpret_cast<const void *>(ndt2d::closure_build_kernel),
+                                                          ndt2d::fused::kLdsBytes));
+  hipLaunchKernelGGL(ndt2d::closure_build_kernel, dim3(static_cast<uint32_t>(n_slots)), dim3(ndt2d::fused::kThreads),
+                     ndt2d::fused::kLdsBytes, stream, *b);
+  NDT2D_BATCH_HIP(c, hipGetLastError());
+  return NDT2D_OK;
+}
 
 // Candidates [k0, k1) of a call whose arguments have been checked: c->slots[k] holds their geometry
 // and counts.  records_out / all_scores: the call's, whole.
@@ -287,22 +406,9 @@ int match_chunk(ndt2d_closure * c, size_t k0, size_t k1, const size_t * cand_off
   if (c->timing) NDT2D_BATCH_HIP(c, hipEventRecord(c->ev[0], stream));
 
   ndt2d::ClosureBuildArgs b{};
-  b.slots = reinterpret_cast<const ClosureSlot *>(c->d_stage + off_slots);
-  b.pool_xy = store->pool;
-  b.scans = reinterpret_cast<const SmallScan *>(c->d_stage + off_scans);
-  b.world_xy = static_cast<double *>(c->d_world);
-  b.cells6 = static_cast<double *>(c->d_cells6);
-  b.records = static_cast<double *>(c->d_records);
-  b.index = static_cast<uint32_t *>(c->d_index);
-  b.lookup = static_cast<uint16_t *>(c->d_lookup);
-  b.n_touched = c->d_n_touched;
-  b.eigen_form = store->eigen_form;
-  // (no static LDS in front of the workgroup's arrays: prepare_absolute_lds_kernel, ndt2d_kernels.h)
-  NDT2D_BATCH_HIP(c, ndt2d::prepare_absolute_lds_kernel(reinterpret_cast<const void *>(ndt2d::closure_build_kernel),
-                                                          ndt2d::fused::kLdsBytes));
-  hipLaunchKernelGGL(ndt2d::closure_build_kernel, dim3(static_cast<uint32_t>(n_slots)), dim3(ndt2d::fused::kThreads),
-                     ndt2d::fused::kLdsBytes, stream, b);
-  NDT2D_BATCH_HIP(c, hipGetLastError());
+  const int brc = launch_build(c, stream, n_slots, reinterpret_cast<const ClosureSlot *>(c->d_stage + off_slots),
+                               reinterpret_cast<const SmallScan *>(c->d_stage + off_scans), &b);
+  if (brc != NDT2D_OK) return brc;
   if (c->timing) NDT2D_BATCH_HIP(c, hipEventRecord(c->ev[1], stream));
 
   ndt2d::BatchSearchArgs<ndt2d::ClosureSlots> a{};
@@ -327,6 +433,137 @@ int match_chunk(ndt2d_closure * c, size_t k0, size_t k1, const size_t * cand_off
   NDT2D_BATCH_HIP(c, hipGetLastError());
   if (c->timing) NDT2D_BATCH_HIP(c, hipEventRecord(c->ev[2], stream));
   return ndt2d::batch_reduce_and_fetch(c, stream, k0, n_slots, a.n_th, n_lattice, -1, records_out, all_scores);
+}
+
+struct RefineCall
+{
+  const size_t * cand_offsets;
+  const size_t * ids;
+  const double * poses_xyt;
+  const double * jobs_xyt;
+  const uint32_t * job_scan;   // NULL: job k uses scan k
+  const double * beams_xy;
+  const size_t * beam_offsets;
+  size_t n_scans;
+  ndt2d::refine::Rules rules;
+  size_t scan_of(size_t k) const { return job_scan != nullptr ? job_scan[k] : k; }
+};
+
+// One chunk of ndt2d_closure_refine's plan, of a call whose arguments have been checked: c->slots[k]
+// holds candidate k's geometry and counts.  One upload, the build of the chunk's candidates, the
+// refinement of its jobs -- a block each, on the slot its record names -- and one read-back.
+// records_out: the call's, whole.
+int refine_chunk(ndt2d_closure * c, const ndt2d::ClosureJobChunk & plan, const RefineCall & t, double * records_out)
+{
+  using ndt2d::RefineJob;
+  using ndt2d::kRefineRec;
+  ndt2d_scanstore * store = c->store;
+  const size_t n_slots = plan.candidates.size(), n_jobs = plan.jobs.size();
+  hipStream_t stream = static_cast<hipStream_t>(ndt2d_get_stream(c->h));
+
+  // the slots with their offsets into the chunk's arrays, as match_chunk lays them out
+  c->chunk_slots.resize(n_slots);
+  size_t n_world = 0, n_list = 0, n_lookup = 0, n_map_scans = 0;
+  for (size_t y = 0; y < n_slots; ++y)
+  {
+    const size_t k = plan.candidates[y];
+    ClosureSlot & s = c->chunk_slots[y];
+    s = c->slots[k];
+    s.scan_first = static_cast<uint32_t>(n_map_scans);
+    s.world_off = static_cast<uint32_t>(n_world);
+    s.list_off = static_cast<uint32_t>(n_list);
+    s.lookup_off = static_cast<uint32_t>(n_lookup);
+    n_map_scans += s.n_scans;
+    n_world += s.n_points;
+    n_list += std::max<size_t>(1, std::min<size_t>(s.n_points, s.grid.ncell));
+    n_lookup += (static_cast<size_t>(s.grid.ncell) + 2 + 7) & ~size_t(7);
+  }
+
+  // the scans this chunk's jobs name, each once, in the order the jobs first name them
+  const size_t n_beams = ndt2d::refine_jobs::plan_sent_scans(
+    n_jobs, [&](size_t b) { return static_cast<size_t>(plan.jobs[b]); }, [&](size_t k) { return t.scan_of(k); }, t.beam_offsets,
+    t.n_scans, c->scan_first, c->sent);
+
+  // the one upload of the chunk: [beams | slots | scan table | jobs | cos / sin pairs]
+  const size_t off_slots = 2 * n_beams;   // (beams in front: 16-byte loads)
+  const size_t off_scans = off_slots + n_slots * (sizeof(ClosureSlot) / sizeof(double));
+  const size_t off_jobs = off_scans + 5 * n_map_scans;
+  const size_t off_trig = off_jobs + n_jobs * ndt2d::kRefineJobDoubles;
+  const size_t n_stage = off_trig + 2 * n_jobs;
+  NDT2D_BATCH_HIP(c, grow_device(&c->d_world, &c->world_cap, std::max<size_t>(1, n_world) * 2 * sizeof(double)));
+  NDT2D_BATCH_HIP(c, grow_device(&c->d_cells6, &c->cells6_cap, n_list * 6 * sizeof(double)));
+  NDT2D_BATCH_HIP(c, grow_device(&c->d_records, &c->records_cap, n_list * 6 * sizeof(double)));
+  NDT2D_BATCH_HIP(c, grow_device(&c->d_index, &c->index_cap, n_list * sizeof(uint32_t)));
+  NDT2D_BATCH_HIP(c, grow_device(&c->d_lookup, &c->lookup_cap, n_lookup * sizeof(uint16_t)));
+  NDT2D_BATCH_HIP(c, ndt2d::grow_pair(&c->h_stage, &c->d_stage, &c->stage_cap, n_stage));
+  NDT2D_BATCH_HIP(c, ndt2d::grow_pair(&c->h_out, &c->d_out, &c->out_cap, n_jobs * kRefineRec));
+
+  double * st = c->h_stage;
+  for (const uint32_t sc : c->sent)
+  {
+    std::memcpy(st + 2 * c->scan_first[sc], t.beams_xy + 2 * t.beam_offsets[sc],
+                2 * (t.beam_offsets[sc + 1] - t.beam_offsets[sc]) * sizeof(double));
+  }
+  std::memcpy(st + off_slots, c->chunk_slots.data(), n_slots * sizeof(ClosureSlot));
+  SmallScan * table = reinterpret_cast<SmallScan *>(st + off_scans);
+  for (size_t y = 0; y < n_slots; ++y)
+  {
+    const size_t k = plan.candidates[y];
+    uint32_t first = 0;
+    for (size_t j = t.cand_offsets[k]; j < t.cand_offsets[k + 1]; ++j)
+    {
+      SmallScan & sc = table[c->chunk_slots[y].scan_first + (j - t.cand_offsets[k])];
+      sc.x = t.poses_xyt[3 * j];
+      sc.y = t.poses_xyt[3 * j + 1];
+      ndt2d_cos_sin(t.poses_xyt[3 * j + 2], &sc.c, &sc.s);   // (src/ndt_model.cpp:135-136, host libm)
+      sc.pool_offset = store->offset[t.ids[j]];
+      sc.first = first;
+      first += store->count[t.ids[j]];
+    }
+  }
+  for (size_t b = 0; b < n_jobs; ++b)
+  {
+    const size_t k = plan.jobs[b], sc = t.scan_of(k);
+    const double * p = t.jobs_xyt + 3 * k;
+    reinterpret_cast<RefineJob *>(st + off_jobs)[b] =
+      RefineJob{p[0], p[1], p[2], static_cast<uint32_t>(t.beam_offsets[sc + 1] - t.beam_offsets[sc]), plan.job_slot[b],
+                c->scan_first[sc]};
+    // cos / sin of the start heading from the host libm, as everywhere in this library
+    ndt2d_cos_sin(p[2], st + off_trig + 2 * b, st + off_trig + 2 * b + 1);
+  }
+  NDT2D_BATCH_HIP(c, hipMemcpyAsync(c->d_stage, st, n_stage * sizeof(double), hipMemcpyHostToDevice, stream));
+  c->timed = false;
+  if (c->timing) NDT2D_BATCH_HIP(c, hipEventRecord(c->ev[0], stream));
+
+  ndt2d::ClosureBuildArgs b{};
+  const int brc = launch_build(c, stream, n_slots, reinterpret_cast<const ClosureSlot *>(c->d_stage + off_slots),
+                               reinterpret_cast<const SmallScan *>(c->d_stage + off_scans), &b);
+  if (brc != NDT2D_OK) return brc;
+  if (c->timing) NDT2D_BATCH_HIP(c, hipEventRecord(c->ev[1], stream));
+
+  ndt2d::SlotRefineArgs a{};
+  a.source.slots = b.slots;
+  a.source.lookup = b.lookup;
+  a.source.records = b.records;
+  a.jobs = reinterpret_cast<const RefineJob *>(c->d_stage + off_jobs);
+  a.trig = c->d_stage + off_trig;
+  a.beams_xy = c->d_stage;
+  a.rules = t.rules;
+  a.records = c->d_out;
+  const dim3 blocks(static_cast<uint32_t>(n_jobs)), threads(ndt2d::kRefineThreads);
+  const bool pow2 = c->chunk_slots[0].grid.pow2 != 0;
+  if (c->cells == 9) ndt2d::launch_slot_refine<9>(pow2, blocks, threads, stream, a);
+  else ndt2d::launch_slot_refine<1>(pow2, blocks, threads, stream, a);
+  NDT2D_BATCH_HIP(c, hipGetLastError());
+  if (c->timing) NDT2D_BATCH_HIP(c, hipEventRecord(c->ev[2], stream));
+  NDT2D_BATCH_HIP(c, hipMemcpyAsync(c->h_out, c->d_out, n_jobs * kRefineRec * sizeof(double), hipMemcpyDeviceToHost, stream));
+  NDT2D_BATCH_HIP(c, hipStreamSynchronize(stream));
+  c->timed = c->timing;
+  for (size_t bj = 0; bj < n_jobs; ++bj)
+  {
+    std::memcpy(records_out + static_cast<size_t>(plan.jobs[bj]) * kRefineRec, c->h_out + bj * kRefineRec, kRefineRec * sizeof(double));
+  }
+  return NDT2D_OK;
 }
 
 }  // namespace
@@ -412,46 +649,9 @@ int ndt2d_closure_match(ndt2d_closure * c, size_t n_candidates, const size_t * c
   {
     return batch_fail(c, NDT2D_ERR_INVALID, "ndt2d_closure_match: bad search (beams, lattice or pose)");
   }
-  const ndt2d_scanstore * store = c->store;
   // every candidate is checked before anything is launched
-  c->slots.assign(n_candidates, ClosureSlot{});
-  for (size_t k = 0; k < n_candidates; ++k)
-  {
-    const std::string who = "ndt2d_closure_match: candidate " + std::to_string(k);
-    if (cand_offsets[k + 1] < cand_offsets[k] || cand_offsets[k + 1] - cand_offsets[0] >= (1u << 28))
-    {
-      return batch_fail(c, NDT2D_ERR_INVALID, who + ": offsets must not decrease");
-    }
-    const size_t j0 = cand_offsets[k], j1 = cand_offsets[k + 1];
-    if (j1 == j0) return batch_fail(c, NDT2D_ERR_INVALID, who + " has no scans");
-    size_t n_points = 0;
-    for (size_t j = j0; j < j1; ++j)
-    {
-      if (ids[j] >= store->count.size())
-      {
-        return batch_fail(c, NDT2D_ERR_INVALID, who + ": unknown scan id " + std::to_string(ids[j]));
-      }
-      if (!std::isfinite(poses_xyt[3 * j]) || !std::isfinite(poses_xyt[3 * j + 1]) || !std::isfinite(poses_xyt[3 * j + 2]))
-      {
-        return batch_fail(c, NDT2D_ERR_INVALID, who + ": a scan pose is not finite");
-      }
-      n_points += store->count[ids[j]];
-    }
-    ClosureSlot & s = c->slots[k];
-    if (!ndt2d::fused::addscans_geometry(ndt_resolution, range_max, poses_xyt + 3 * j0, j1 - j0, &s.grid))
-    {
-      return batch_fail(c, NDT2D_ERR_INVALID, who + ": degenerate grid extent");
-    }
-    if (!ndt2d::fused::small_map_fits(s.grid, n_points) || s.grid.ncell == 0)
-    {
-      return batch_fail(c, NDT2D_ERR_INVALID, who + ": the map exceeds the fused build's limits (" + std::to_string(n_points) +
-                                           " points of at most " + std::to_string(ndt2d::fused::kFusedMaxPoints) + ", " +
-                                           std::to_string(s.grid.ncell) + " cells of fewer than 65535)");
-    }
-    s.n_scans = static_cast<uint32_t>(j1 - j0);
-    s.n_points = static_cast<uint32_t>(n_points);
-    s.sort_passes = ndt2d::fused::sort_passes_for(s.grid.ncell);
-  }
+  const int crc = check_candidates(c, "ndt2d_closure_match", n_candidates, cand_offsets, ids, poses_xyt, ndt_resolution, range_max);
+  if (crc != NDT2D_OK) return crc;
   NDT2D_BATCH_HIP(c, hipSetDevice(c->device));
   const SearchTables t{beams_xy, n_beams, pose_x, pose_y, dth, cos_th, sin_th, n_th, dlin, n_lin};
   // more candidates than slots: in chunks
@@ -459,6 +659,79 @@ int ndt2d_closure_match(ndt2d_closure * c, size_t n_candidates, const size_t * c
   {
     const size_t k1 = std::min(n_candidates, k0 + c->max_candidates);
     const int rc = match_chunk(c, k0, k1, cand_offsets, ids, poses_xyt, t, records_out, all_scores);
+    if (rc != NDT2D_OK) return rc;
+  }
+  return NDT2D_OK;
+  NDT2D_C_CATCH(c)
+}
+
+int ndt2d_closure_set_neighbourhood(ndt2d_closure * c, uint32_t cells)
+{
+  NDT2D_C_TRY
+  if (c == nullptr) return NDT2D_ERR_INVALID;
+  if (cells != 1 && cells != 9)
+  {
+    return batch_fail(c, NDT2D_ERR_INVALID, "ndt2d_closure_set_neighbourhood: " + std::to_string(cells) + " cells (1 or 9)");
+  }
+  c->cells = cells;
+  return NDT2D_OK;
+  NDT2D_C_CATCH(c)
+}
+
+int ndt2d_closure_neighbourhood(ndt2d_closure * c, uint32_t * out)
+{
+  NDT2D_C_TRY
+  if (c == nullptr || out == nullptr) return NDT2D_ERR_INVALID;
+  *out = c->cells;
+  return NDT2D_OK;
+  NDT2D_C_CATCH(c)
+}
+
+int ndt2d_closure_refine(ndt2d_closure * c, size_t n_candidates, const size_t * cand_offsets, const size_t * ids,
+                         const double * poses_xyt, double ndt_resolution, double range_max, const double * jobs_xyt,
+                         const uint32_t * job_scan, const uint32_t * job_candidate, size_t n_jobs, const double * beams_xy,
+                         const size_t * beam_offsets, size_t n_scans, uint32_t max_evals, double tol_lin, double tol_ang,
+                         double * records_out)
+{
+  NDT2D_C_TRY
+  if (c == nullptr) return NDT2D_ERR_INVALID;
+  if (n_jobs == 0) return NDT2D_OK;
+  if (cand_offsets == nullptr || ids == nullptr || poses_xyt == nullptr || jobs_xyt == nullptr || records_out == nullptr ||
+      beams_xy == nullptr || beam_offsets == nullptr)
+  {
+    return batch_fail(c, NDT2D_ERR_INVALID, "ndt2d_closure_refine: null argument");
+  }
+  if (!(ndt_resolution > 0.0) || !std::isfinite(ndt_resolution) || !std::isfinite(range_max))
+  {
+    return batch_fail(c, NDT2D_ERR_INVALID, "ndt2d_closure_refine: bad resolution or range_max");
+  }
+  if (n_candidates >= (1u << 24)) return batch_fail(c, NDT2D_ERR_INVALID, "ndt2d_closure_refine: bad argument (n_candidates)");
+  if (job_candidate == nullptr && n_candidates != n_jobs)
+  {
+    return batch_fail(c, NDT2D_ERR_INVALID,
+                      "ndt2d_closure_refine: bad argument (no job_candidate: job k uses candidate k, n_candidates must equal n_jobs)");
+  }
+  // the rules, every scan, every job and every candidate are checked before anything is launched:
+  // what ndt2d_refine_run refuses (one text: batch/ndt2d_refine_jobs.h), what ndt2d_closure_match does
+  const std::string refusal = ndt2d::refine_jobs::refusal("ndt2d_closure_refine", jobs_xyt, job_scan, n_jobs, beam_offsets, n_scans,
+                                                         max_evals, tol_lin, tol_ang);
+  if (!refusal.empty()) return batch_fail(c, NDT2D_ERR_INVALID, refusal);
+  const int crc = check_candidates(c, "ndt2d_closure_refine", n_candidates, cand_offsets, ids, poses_xyt, ndt_resolution, range_max);
+  if (crc != NDT2D_OK) return crc;
+  for (size_t k = 0; k < n_jobs && job_candidate != nullptr; ++k)
+  {
+    if (job_candidate[k] >= n_candidates)
+    {
+      return batch_fail(c, NDT2D_ERR_INVALID, "ndt2d_closure_refine: job " + std::to_string(k) + ": candidate " +
+                                             std::to_string(job_candidate[k]) + " of " + std::to_string(n_candidates));
+    }
+  }
+  NDT2D_BATCH_HIP(c, hipSetDevice(c->device));
+  const RefineCall t{cand_offsets, ids, poses_xyt, jobs_xyt, job_scan, beams_xy, beam_offsets, n_scans, {max_evals, tol_lin, tol_ang}};
+  for (const ndt2d::ClosureJobChunk & chunk :
+       ndt2d::plan_closure_jobs(job_candidate, n_jobs, n_candidates, c->max_candidates, ndt2d::kRefineMaxJobs))
+  {
+    const int rc = refine_chunk(c, chunk, t, records_out);
     if (rc != NDT2D_OK) return rc;
   }
   return NDT2D_OK;

@@ -1,0 +1,83 @@
+// The chunk plan of ndt2d_closure_refine (closure/ndt2d_closure.hip): which candidate maps a
+// launch builds and which jobs run on them.  Plain C++ -- no HIP -- so that a host program can
+// check it (tests/cpp/closure_jobs_check.cpp).
+//
+// Candidates are taken in ascending index among those a job names (a candidate no job names is
+// not built); a candidate's jobs in ascending job index.  A chunk closes before it would exceed
+// max_candidates candidates or max_jobs jobs -- the blocks of a launch.  A candidate with more
+// jobs than one launch holds continues in chunks of its own (it is built once per such chunk).
+// Every job is in exactly one chunk; a chunk names where each of its jobs' records goes, so the
+// results land in job order whatever the plan.
+#ifndef NDT2D_CLOSURE_JOBS_H_
+#define NDT2D_CLOSURE_JOBS_H_
+
+#include <cstddef>
+#include <cstdint>
+#include <utility>
+#include <vector>
+
+namespace ndt2d
+{
+
+struct ClosureJobChunk
+{
+  std::vector<uint32_t> candidates;   // ascending: slot s of the launch is candidate candidates[s]
+  std::vector<uint32_t> jobs;         // block b of the launch is job jobs[b] of the call
+  std::vector<uint32_t> job_slot;     // ... on slot job_slot[b]
+};
+
+// job_candidate: n_jobs entries, each < n_candidates (the caller has checked), or NULL: job k uses
+// candidate k (n_jobs == n_candidates).  max_candidates, max_jobs >= 1.
+inline std::vector<ClosureJobChunk> plan_closure_jobs(const uint32_t * job_candidate, size_t n_jobs, size_t n_candidates,
+                                                      size_t max_candidates, size_t max_jobs)
+{
+  // the jobs of every candidate, in job order (a counting sort: stable)
+  std::vector<size_t> first(n_candidates + 1, 0);
+  for (size_t k = 0; k < n_jobs; ++k) ++first[(job_candidate != nullptr ? job_candidate[k] : k) + 1];
+  for (size_t c = 0; c < n_candidates; ++c) first[c + 1] += first[c];
+  std::vector<uint32_t> by_candidate(n_jobs);
+  {
+    std::vector<size_t> at(first.begin(), first.end() - 1);
+    for (size_t k = 0; k < n_jobs; ++k) by_candidate[at[job_candidate != nullptr ? job_candidate[k] : k]++] = static_cast<uint32_t>(k);
+  }
+
+  std::vector<ClosureJobChunk> plan;
+  ClosureJobChunk cur;
+  const auto close = [&]() {
+    if (!cur.jobs.empty()) plan.push_back(std::move(cur));
+    cur = ClosureJobChunk{};
+  };
+  const auto take = [&](size_t c, size_t j0, size_t j1) {
+    const uint32_t slot = static_cast<uint32_t>(cur.candidates.size());
+    cur.candidates.push_back(static_cast<uint32_t>(c));
+    for (size_t j = j0; j < j1; ++j)
+    {
+      cur.jobs.push_back(by_candidate[j]);
+      cur.job_slot.push_back(slot);
+    }
+  };
+  for (size_t c = 0; c < n_candidates; ++c)
+  {
+    const size_t j0 = first[c], j1 = first[c + 1];
+    if (j1 == j0) continue;   // no job names it
+    if (j1 - j0 > max_jobs)
+    {
+      // more jobs than a launch holds: chunks of its own
+      close();
+      for (size_t j = j0; j < j1; j += max_jobs)
+      {
+        take(c, j, j + max_jobs < j1 ? j + max_jobs : j1);
+        close();
+      }
+      continue;
+    }
+    if (cur.candidates.size() == max_candidates || cur.jobs.size() + (j1 - j0) > max_jobs) close();
+    take(c, j0, j1);
+  }
+  close();
+  return plan;
+}
+
+}  // namespace ndt2d
+
+#endif  // NDT2D_CLOSURE_JOBS_H_

@@ -2,7 +2,8 @@
 // (match_candidates), from K start poses (match_starts), K scans each from its own pose (match_scans):
 // each validates its input, makes one call of its object under csrc/closure, starts or scans for
 // the records of all slots, and hands them to finish_slots(), the tail they share -- and the Newton
-// registration of K (scan, pose) jobs (refine_scans), one call of the object under csrc/refine.
+// registration of K (scan, pose) jobs (refine_scans), one call of the object under csrc/refine, and
+// the same on each loop-closure candidate's own map (refine_candidates), one call of the closure object.
 #include <cstring>
 #include <functional>
 #include <string>
@@ -94,6 +95,150 @@ int finish_slots(ndt2d_matcher * m, size_t n_slots, const double * records, cons
 
 // Candidates the batched match launches at a time: the plugin's global_search_limit_ is a handful.
 constexpr size_t kClosureSlots = 16;
+
+// The outputs of a Newton registration (refine_scans, refine_candidates); all but poses, scores and
+// status are optional.
+struct RefineOut
+{
+  double * poses, * scores, * start_scores, * gradients, * hessians;
+  int32_t * status;
+  uint32_t * evals;
+};
+
+// What both registrations refuse about rules, scans and jobs; `who` names the call.
+int check_refine_input(ndt2d_matcher * m, const std::string & who, const double * jobs_xyt, const uint32_t * job_scan,
+                       size_t n_jobs, const double * points_xy, const size_t * point_offsets, size_t n_scans,
+                       uint32_t max_evals, double tol_lin, double tol_ang)
+{
+  if (n_jobs > (1u << 20) || n_scans > (1u << 20)) return mfail(m, NDT2D_ERR_INVALID, who + ": too many jobs or scans");
+  if (max_evals == 0) return mfail(m, NDT2D_ERR_INVALID, who + ": max_evals == 0");
+  if (!(tol_lin >= 0.0) || !(tol_ang >= 0.0) || !std::isfinite(tol_lin) || !std::isfinite(tol_ang))
+  {
+    return mfail(m, NDT2D_ERR_INVALID, who + ": a tolerance is negative or not finite");
+  }
+  if (job_scan == nullptr && n_scans != n_jobs)
+  {
+    return mfail(m, NDT2D_ERR_INVALID, who + ": no job_scan (job k uses scan k): n_scans must equal n_jobs");
+  }
+  for (size_t sc = 0; sc < n_scans; ++sc)
+  {
+    if (point_offsets[sc + 1] < point_offsets[sc])
+    {
+      return mfail(m, NDT2D_ERR_INVALID, who + ": scan " + std::to_string(sc) + ": point_offsets decrease");
+    }
+  }
+  if (n_scans > 0 && point_offsets[n_scans] > point_offsets[0] && points_xy == nullptr)
+  {
+    return mfail(m, NDT2D_ERR_INVALID, who + ": null input");
+  }
+  for (size_t k = 0; k < n_jobs; ++k)
+  {
+    if (!std::isfinite(jobs_xyt[3 * k]) || !std::isfinite(jobs_xyt[3 * k + 1]) || !std::isfinite(jobs_xyt[3 * k + 2]))
+    {
+      return mfail(m, NDT2D_ERR_INVALID, who + ": job " + std::to_string(k) + ": the pose is not finite");
+    }
+    if (job_scan != nullptr && job_scan[k] >= n_scans)
+    {
+      return mfail(m, NDT2D_ERR_INVALID, who + ": job " + std::to_string(k) + ": scan " + std::to_string(job_scan[k]) +
+                                             " of " + std::to_string(n_scans));
+    }
+  }
+  return NDT2D_OK;
+}
+
+// `if (!ndt_) return 0.0;` (src/scan_matcher_ndt.cpp:159), and a scan without points: nothing
+// scores, the job keeps its pose
+void fill_no_overlap(const double * jobs_xyt, size_t n_jobs, const RefineOut & o)
+{
+  for (size_t k = 0; k < n_jobs; ++k)
+  {
+    std::memcpy(o.poses + 3 * k, jobs_xyt + 3 * k, 3 * sizeof(double));
+    o.scores[k] = 0.0;
+    o.status[k] = NDT2D_REFINE_NO_OVERLAP;
+    if (o.start_scores != nullptr) o.start_scores[k] = 0.0;
+    if (o.gradients != nullptr) std::memset(o.gradients + 3 * k, 0, 3 * sizeof(double));
+    if (o.hessians != nullptr) std::memset(o.hessians + 9 * k, 0, 9 * sizeof(double));
+    if (o.evals != nullptr) o.evals[2 * k] = o.evals[2 * k + 1] = 0u;
+  }
+}
+
+// The jobs of a registration's device call: every scan a job names as scorePoints takes it --
+// subsampled beams (:165-166,171), once per scan; a scan without points is not among them, and
+// neither are its jobs.
+struct RefineBatch
+{
+  std::vector<double> beams, xyt;
+  std::vector<size_t> beam_offsets;
+  std::vector<uint32_t> job, scan;   // the jobs of the device call and their scans
+};
+
+void collect_refine_batch(const ndt2d_matcher * m, const double * jobs_xyt, const uint32_t * job_scan, size_t n_jobs,
+                          const double * points_xy, const size_t * point_offsets, size_t n_scans, RefineBatch & b)
+{
+  // sent[s]: its index among the scans the device call receives
+  constexpr uint32_t kUnseen = ~0u, kEmpty = ~0u - 1u;
+  std::vector<uint32_t> sent(n_scans, kUnseen);
+  std::vector<double> one;
+  b.beam_offsets.assign(1, 0);
+  for (size_t k = 0; k < n_jobs; ++k)
+  {
+    const size_t sc = job_scan != nullptr ? static_cast<size_t>(job_scan[k]) : k;
+    if (sent[sc] == kUnseen)
+    {
+      subsample_into(one, points_xy + 2 * point_offsets[sc], point_offsets[sc + 1] - point_offsets[sc], m->laser_max_beams);
+      if (one.empty())
+      {
+        sent[sc] = kEmpty;
+      }
+      else
+      {
+        sent[sc] = static_cast<uint32_t>(b.beam_offsets.size() - 1);
+        b.beams.insert(b.beams.end(), one.begin(), one.end());
+        b.beam_offsets.push_back(b.beams.size() / 2);
+      }
+    }
+    if (sent[sc] == kEmpty) continue;
+    b.job.push_back(static_cast<uint32_t>(k));
+    b.scan.push_back(sent[sc]);
+    b.xyt.insert(b.xyt.end(), jobs_xyt + 3 * k, jobs_xyt + 3 * k + 3);
+  }
+}
+
+// The device call's records ([batch job][NDT2D_REFINE_RECORD_DOUBLES]) into the outputs of their jobs.
+void deal_refine_records(const RefineBatch & b, const double * records, const RefineOut & o)
+{
+  constexpr size_t kRefRec = NDT2D_REFINE_RECORD_DOUBLES;
+  for (size_t j = 0; j < b.job.size(); ++j)
+  {
+    const size_t k = b.job[j];
+    const double * rec = records + j * kRefRec;
+    // f, g, H of the sum over the scan's N beams -> of `score / N` (:177)
+    const double n = static_cast<double>(b.beam_offsets[b.scan[j] + 1] - b.beam_offsets[b.scan[j]]);
+    std::memcpy(o.poses + 3 * k, rec, 3 * sizeof(double));
+    o.scores[k] = rec[4] / n;
+    o.status[k] = static_cast<int32_t>(rec[16]);
+    if (o.start_scores != nullptr) o.start_scores[k] = rec[3] / n;
+    if (o.gradients != nullptr)
+    {
+      for (int d = 0; d < 3; ++d) o.gradients[3 * k + d] = rec[5 + d] / n;
+    }
+    if (o.hessians != nullptr)
+    {
+      double * h = o.hessians + 9 * k;
+      h[0] = rec[8] / n;
+      h[1] = h[3] = rec[9] / n;
+      h[2] = h[6] = rec[10] / n;
+      h[4] = rec[11] / n;
+      h[5] = h[7] = rec[12] / n;
+      h[8] = rec[13] / n;
+    }
+    if (o.evals != nullptr)
+    {
+      o.evals[2 * k] = static_cast<uint32_t>(rec[14]);
+      o.evals[2 * k + 1] = static_cast<uint32_t>(rec[15]);
+    }
+  }
+}
 
 }  // namespace
 
@@ -395,130 +540,31 @@ int ndt2d_matcher_refine_scans(ndt2d_matcher * m, const double * jobs_xyt, const
   {
     return mfail(m, NDT2D_ERR_INVALID, "refine_scans: null input");
   }
-  if (n_jobs > (1u << 20) || n_scans > (1u << 20)) return mfail(m, NDT2D_ERR_INVALID, "refine_scans: too many jobs or scans");
-  if (max_evals == 0) return mfail(m, NDT2D_ERR_INVALID, "refine_scans: max_evals == 0");
-  if (!(tol_lin >= 0.0) || !(tol_ang >= 0.0) || !std::isfinite(tol_lin) || !std::isfinite(tol_ang))
-  {
-    return mfail(m, NDT2D_ERR_INVALID, "refine_scans: a tolerance is negative or not finite");
-  }
-  if (job_scan == nullptr && n_scans != n_jobs)
-  {
-    return mfail(m, NDT2D_ERR_INVALID, "refine_scans: no job_scan (job k uses scan k): n_scans must equal n_jobs");
-  }
-  for (size_t sc = 0; sc < n_scans; ++sc)
-  {
-    if (point_offsets[sc + 1] < point_offsets[sc])
-    {
-      return mfail(m, NDT2D_ERR_INVALID, "refine_scans: scan " + std::to_string(sc) + ": point_offsets decrease");
-    }
-  }
-  if (n_scans > 0 && point_offsets[n_scans] > point_offsets[0] && points_xy == nullptr)
-  {
-    return mfail(m, NDT2D_ERR_INVALID, "refine_scans: null input");
-  }
-  for (size_t k = 0; k < n_jobs; ++k)
-  {
-    if (!std::isfinite(jobs_xyt[3 * k]) || !std::isfinite(jobs_xyt[3 * k + 1]) || !std::isfinite(jobs_xyt[3 * k + 2]))
-    {
-      return mfail(m, NDT2D_ERR_INVALID, "refine_scans: job " + std::to_string(k) + ": the pose is not finite");
-    }
-    if (job_scan != nullptr && job_scan[k] >= n_scans)
-    {
-      return mfail(m, NDT2D_ERR_INVALID, "refine_scans: job " + std::to_string(k) + ": scan " + std::to_string(job_scan[k]) +
-                                             " of " + std::to_string(n_scans));
-    }
-  }
-  // `if (!ndt_) return 0.0;` (src/scan_matcher_ndt.cpp:159), and a scan without points: nothing
-  // scores, the job keeps its pose
-  for (size_t k = 0; k < n_jobs; ++k)
-  {
-    std::memcpy(poses_out + 3 * k, jobs_xyt + 3 * k, 3 * sizeof(double));
-    scores_out[k] = 0.0;
-    status_out[k] = NDT2D_REFINE_NO_OVERLAP;
-    if (start_scores_out != nullptr) start_scores_out[k] = 0.0;
-    if (gradients_out != nullptr) std::memset(gradients_out + 3 * k, 0, 3 * sizeof(double));
-    if (hessians_out != nullptr) std::memset(hessians_out + 9 * k, 0, 9 * sizeof(double));
-    if (evals_out != nullptr) evals_out[2 * k] = evals_out[2 * k + 1] = 0u;
-  }
+  int rc = check_refine_input(m, "refine_scans", jobs_xyt, job_scan, n_jobs, points_xy, point_offsets, n_scans, max_evals, tol_lin,
+                              tol_ang);
+  if (rc != NDT2D_OK) return rc;
+  const RefineOut out = {poses_out, scores_out, start_scores_out, gradients_out, hessians_out, status_out, evals_out};
+  fill_no_overlap(jobs_xyt, n_jobs, out);
   if (!m->ndt.have()) return NDT2D_OK;
   discard_ahead(m);   // a search launched ahead by scoreScan is waited out and dropped
   if (m->refine == nullptr)
   {
-    const int rc = ndt2d_refine_create(m->dev, kRefineSlots, &m->refine);
+    rc = ndt2d_refine_create(m->dev, kRefineSlots, &m->refine);
     if (rc != NDT2D_OK) return dev_fail(m, rc, "ndt2d_refine_create");
   }
   if (ndt2d_refine_set_neighbourhood(m->refine, m->refine_cells) != NDT2D_OK)
   {
     return mfail(m, NDT2D_ERR_INTERNAL, std::string("refine_scans: ") + ndt2d_refine_last_error(m->refine));
   }
-  const auto scan_of = [&](size_t k) { return job_scan != nullptr ? static_cast<size_t>(job_scan[k]) : k; };
-
-  // every scan a job names as scorePoints takes it: subsampled beams (:165-166,171), once per scan.
-  // sent[s]: its index among the scans the device call receives (a scan without points is not among them)
-  constexpr uint32_t kUnseen = ~0u, kEmpty = ~0u - 1u;
-  std::vector<uint32_t> sent(n_scans, kUnseen);
-  std::vector<double> beams, one, batch_xyt;
-  std::vector<size_t> beam_offsets(1, 0);
-  std::vector<uint32_t> batch_job, batch_scan;   // the jobs of the device call and their scans
-  for (size_t k = 0; k < n_jobs; ++k)
-  {
-    const size_t sc = scan_of(k);
-    if (sent[sc] == kUnseen)
-    {
-      subsample_into(one, points_xy + 2 * point_offsets[sc], point_offsets[sc + 1] - point_offsets[sc], m->laser_max_beams);
-      if (one.empty())
-      {
-        sent[sc] = kEmpty;
-      }
-      else
-      {
-        sent[sc] = static_cast<uint32_t>(beam_offsets.size() - 1);
-        beams.insert(beams.end(), one.begin(), one.end());
-        beam_offsets.push_back(beams.size() / 2);
-      }
-    }
-    if (sent[sc] == kEmpty) continue;
-    batch_job.push_back(static_cast<uint32_t>(k));
-    batch_scan.push_back(sent[sc]);
-    batch_xyt.insert(batch_xyt.end(), jobs_xyt + 3 * k, jobs_xyt + 3 * k + 3);
-  }
-  const size_t n_batch = batch_job.size();
+  RefineBatch batch;
+  collect_refine_batch(m, jobs_xyt, job_scan, n_jobs, points_xy, point_offsets, n_scans, batch);
+  const size_t n_batch = batch.job.size();
   if (n_batch == 0) return NDT2D_OK;
-  constexpr size_t kRefRec = NDT2D_REFINE_RECORD_DOUBLES;
-  m->refine_records.assign(n_batch * kRefRec, 0.0);
-  const int rc = ndt2d_refine_run(m->refine, batch_xyt.data(), batch_scan.data(), n_batch, beams.data(), beam_offsets.data(),
-                                  beam_offsets.size() - 1, max_evals, tol_lin, tol_ang, m->refine_records.data());
+  m->refine_records.assign(n_batch * NDT2D_REFINE_RECORD_DOUBLES, 0.0);
+  rc = ndt2d_refine_run(m->refine, batch.xyt.data(), batch.scan.data(), n_batch, batch.beams.data(), batch.beam_offsets.data(),
+                        batch.beam_offsets.size() - 1, max_evals, tol_lin, tol_ang, m->refine_records.data());
   if (rc != NDT2D_OK) return mfail(m, rc, std::string("refine_scans: ") + ndt2d_refine_last_error(m->refine));
-  for (size_t j = 0; j < n_batch; ++j)
-  {
-    const size_t k = batch_job[j];
-    const double * rec = m->refine_records.data() + j * kRefRec;
-    // f, g, H of the sum over the scan's N beams -> of `score / N` (:177)
-    const double n = static_cast<double>(beam_offsets[batch_scan[j] + 1] - beam_offsets[batch_scan[j]]);
-    std::memcpy(poses_out + 3 * k, rec, 3 * sizeof(double));
-    scores_out[k] = rec[4] / n;
-    status_out[k] = static_cast<int32_t>(rec[16]);
-    if (start_scores_out != nullptr) start_scores_out[k] = rec[3] / n;
-    if (gradients_out != nullptr)
-    {
-      for (int d = 0; d < 3; ++d) gradients_out[3 * k + d] = rec[5 + d] / n;
-    }
-    if (hessians_out != nullptr)
-    {
-      double * h = hessians_out + 9 * k;
-      h[0] = rec[8] / n;
-      h[1] = h[3] = rec[9] / n;
-      h[2] = h[6] = rec[10] / n;
-      h[4] = rec[11] / n;
-      h[5] = h[7] = rec[12] / n;
-      h[8] = rec[13] / n;
-    }
-    if (evals_out != nullptr)
-    {
-      evals_out[2 * k] = static_cast<uint32_t>(rec[14]);
-      evals_out[2 * k + 1] = static_cast<uint32_t>(rec[15]);
-    }
-  }
+  deal_refine_records(batch, m->refine_records.data(), out);
   return NDT2D_OK;
   NDT2D_C_CATCH(m)
 }
@@ -543,6 +589,79 @@ int ndt2d_matcher_refine_neighbourhood(ndt2d_matcher * m, uint32_t * out)
   NDT2D_C_TRY
   if (m == nullptr || out == nullptr) return NDT2D_ERR_INVALID;
   *out = m->refine_cells;
+  return NDT2D_OK;
+  NDT2D_C_CATCH(m)
+}
+
+int ndt2d_matcher_refine_candidates(ndt2d_matcher * m, const size_t * cand_offsets, const size_t * ids,
+                                    const double * poses_xyt, size_t n_candidates, const double * jobs_xyt,
+                                    const uint32_t * job_scan, const uint32_t * job_candidate, size_t n_jobs,
+                                    const double * points_xy, const size_t * point_offsets, size_t n_scans,
+                                    uint32_t max_evals, double tol_lin, double tol_ang, double * poses_out,
+                                    double * scores_out, double * start_scores_out, double * gradients_out,
+                                    double * hessians_out, int32_t * status_out, uint32_t * evals_out)
+{
+  NDT2D_C_TRY
+  if (m == nullptr) return NDT2D_ERR_INVALID;
+  if (n_jobs == 0) return NDT2D_OK;
+  if (jobs_xyt == nullptr || poses_out == nullptr || scores_out == nullptr || status_out == nullptr || point_offsets == nullptr ||
+      cand_offsets == nullptr || ids == nullptr || poses_xyt == nullptr)
+  {
+    return mfail(m, NDT2D_ERR_INVALID, "refine_candidates: null input");
+  }
+  if (n_candidates == 0 || n_candidates > (1u << 20)) return mfail(m, NDT2D_ERR_INVALID, "refine_candidates: no candidates, or too many");
+  int rc = check_refine_input(m, "refine_candidates", jobs_xyt, job_scan, n_jobs, points_xy, point_offsets, n_scans, max_evals,
+                              tol_lin, tol_ang);
+  if (rc != NDT2D_OK) return rc;
+  if (job_candidate == nullptr && n_candidates != n_jobs)
+  {
+    return mfail(m, NDT2D_ERR_INVALID, "refine_candidates: no job_candidate (job k uses candidate k): n_candidates must equal n_jobs");
+  }
+  for (size_t k = 0; k < n_jobs && job_candidate != nullptr; ++k)
+  {
+    if (job_candidate[k] >= n_candidates)
+    {
+      return mfail(m, NDT2D_ERR_INVALID, "refine_candidates: job " + std::to_string(k) + ": candidate " +
+                                             std::to_string(job_candidate[k]) + " of " + std::to_string(n_candidates));
+    }
+  }
+  if (m->stores.size() != m->devs.size())
+  {
+    return mfail(m, NDT2D_ERR_INVALID, "refine_candidates: candidate 0: unknown scan id (no scan is stored)");
+  }
+  const RefineOut out = {poses_out, scores_out, start_scores_out, gradients_out, hessians_out, status_out, evals_out};
+  discard_ahead(m);   // a search launched ahead by scoreScan is waited out and dropped
+  if (m->closure == nullptr)
+  {
+    rc = ndt2d_closure_create(m->dev, m->stores[0], kClosureSlots, &m->closure);
+    if (rc != NDT2D_OK) return dev_fail(m, rc, "ndt2d_closure_create");
+  }
+  if (ndt2d_closure_set_neighbourhood(m->closure, m->refine_cells) != NDT2D_OK)
+  {
+    return mfail(m, NDT2D_ERR_INTERNAL, std::string("refine_candidates: ") + ndt2d_closure_last_error(m->closure));
+  }
+  RefineBatch batch;
+  collect_refine_batch(m, jobs_xyt, job_scan, n_jobs, points_xy, point_offsets, n_scans, batch);
+  const size_t n_batch = batch.job.size();
+  std::vector<uint32_t> batch_candidate(n_batch);
+  for (size_t j = 0; j < n_batch; ++j) batch_candidate[j] = job_candidate != nullptr ? job_candidate[batch.job[j]] : batch.job[j];
+  if (n_batch == 0)
+  {
+    fill_no_overlap(jobs_xyt, n_jobs, out);
+    return NDT2D_OK;
+  }
+  rc = ndt2d_scanstore_set_eigenvalue_form(m->stores[0], eigen_form_name(m));
+  m->refine_records.assign(n_batch * NDT2D_REFINE_RECORD_DOUBLES, 0.0);
+  if (rc == NDT2D_OK)
+  {
+    rc = ndt2d_closure_refine(m->closure, n_candidates, cand_offsets, ids, poses_xyt, m->resolution, m->range_max, batch.xyt.data(),
+                              batch.scan.data(), batch_candidate.data(), n_batch, batch.beams.data(), batch.beam_offsets.data(),
+                              batch.beam_offsets.size() - 1, max_evals, tol_lin, tol_ang, m->refine_records.data());
+  }
+  // (a refused call -- a candidate the closure does not take -- leaves the outputs as they were)
+  if (rc != NDT2D_OK) return mfail(m, rc, std::string("refine_candidates: ") + ndt2d_closure_last_error(m->closure));
+  fill_no_overlap(jobs_xyt, n_jobs, out);   // (the jobs of a scan without points keep this)
+  deal_refine_records(batch, m->refine_records.data(), out);
   return NDT2D_OK;
   NDT2D_C_CATCH(m)
 }

@@ -26,6 +26,15 @@
 //       adds nothing).  CELLS = 1 is the loop above, instantiated apart: its code is the one-cell
 //       kernel's as it was.
 //
+// The map is a template argument of the kernel.  A SOURCE gives, for the slot a job's record
+// names, the GridDesc of that job's map (grid(slot): the geometry cell_index and the 3 x 3 clip
+// use) and its map object of the walk's kind (map(slot): find(cell, rank) / record(rank),
+// batch/ndt2d_walk_fn.h; entry ncell of it exists and never scores); both are uniform over the
+// block.  InstalledSource, here, is the grid installed in the context: one grid for all jobs.  The
+// loop closure refines each job on its candidate's own map with the same kernel:
+// closure/ndt2d_closure.hip defines NDT2D_REFINE_KERNEL_ONLY and includes this file for its
+// device half -- the kernel has one text, this one -- and instantiates it with its slots.
+//
 // The beams are read from the chunk's upload at every evaluation: a scan is at most a few KB per
 // job and stays in L2 between the evaluations of its block, so nothing is staged in LDS and a
 // scan of any length (beyond kStageBeams too) takes the same path.
@@ -54,15 +63,8 @@
 #include "ndt2d_hip.h"
 #include "batch/ndt2d_batch_search.h"
 #include "batch/ndt2d_batch_host.h"
+#include "batch/ndt2d_refine_jobs.h"
 #include "refine/ndt2d_refine_step.h"
-
-struct ndt2d_refine : ndt2d::BatchHost
-{
-  size_t max_jobs = 0;                // slots of a chunk
-  uint32_t cells = 1;                 // the neighbourhood of a point: 1 (its own cell) or 9 (the 3 x 3 round it)
-  std::vector<uint64_t> scan_first;   // scan -> its first beam within the chunk's beams (or: not sent)
-  std::vector<uint32_t> sent;         // the chunk's scans in upload order
-};
 
 namespace ndt2d
 {
@@ -70,10 +72,9 @@ namespace ndt2d
 namespace
 {
 
-constexpr size_t kMaxScanBeams = size_t(1) << 20;   // what ndt2d_set_beams takes
-constexpr uint64_t kNotSent = ~uint64_t(0);
 constexpr uint32_t kRefineThreads = 256;
 constexpr uint32_t kRefineWaves = kRefineThreads / kWave;
+constexpr uint32_t kRefineMaxJobs = 4096;   // blocks of a launch
 constexpr int kSums = 10;             // e | e a_0..2 | H xx, xy, xt, yy, yt, tt
 constexpr size_t kRefineRec = NDT2D_REFINE_RECORD_DOUBLES;
 
@@ -86,15 +87,16 @@ struct RefineJob
 {
   double x, y, theta;
   uint32_t n_beams;      // of its scan
-  uint32_t pad;
+  uint32_t slot;         // of its map within the chunk (the installed grid: 0)
   uint64_t beam_first;   // its scan's first beam within the chunk's beams
 };
 constexpr size_t kRefineJobDoubles = 5;
 static_assert(sizeof(RefineJob) == kRefineJobDoubles * sizeof(double), "jobs travel in a buffer of doubles");
 
+template <class SOURCE>
 struct RefineArgs
 {
-  GridDesc grid;              // geometry, cells_global, occ_bits
+  SOURCE source;              // job -> its map
   const RefineJob * jobs;     // [job of the chunk]
   const double * trig;        // [job of the chunk][2]: cos, sin of its start heading (host libm)
   const double * beams_xy;    // the chunk's scans, [beam][2] robot frame
@@ -102,10 +104,19 @@ struct RefineArgs
   double * records;           // [job of the chunk][NDT2D_REFINE_RECORD_DOUBLES]
 };
 
+// SOURCE of the grid installed in the context: one grid for all jobs, a cell is its own record.
+struct InstalledSource
+{
+  GridDesc g;   // geometry, cells_global, occ_bits
+  __device__ __forceinline__ const GridDesc & grid(uint32_t) const { return g; }
+  __device__ __forceinline__ InstalledMap map(uint32_t) const { return InstalledMap{g.occ_bits, g.cells_global}; }
+};
+
 // The terms of the point q = R b + t against the record of `cell` into the thread's ten sums.
 // Called by every lane of the wave together (exp_score tests the wave); valid = the lane holds an
 // item whose cell may count (cell <= ncell; ncell: the sentinel, which never scores).
-__device__ __forceinline__ void add_cell_terms(const InstalledMap & map, uint32_t cell, double2 b, bool valid, double qx,
+template <class MAP>
+__device__ __forceinline__ void add_cell_terms(const MAP & map, uint32_t cell, double2 b, bool valid, double qx,
                                                double qy, double c, double s, double (&sum)[kSums])
 {
   uint32_t rank;
@@ -140,8 +151,8 @@ __device__ __forceinline__ void add_cell_terms(const InstalledMap & map, uint32_
 }
 
 // One beam's terms at the pose (x, y | c, s), against the cell it falls in.
-template <bool POW2>
-__device__ __forceinline__ void add_terms(const GridDesc & g, const InstalledMap & map, double2 b, bool valid, double x,
+template <bool POW2, class MAP>
+__device__ __forceinline__ void add_terms(const GridDesc & g, const MAP & map, double2 b, bool valid, double x,
                                           double y, double c, double s, double (&sum)[kSums])
 {
   const double qx = c * b.x - s * b.y + x;
@@ -164,8 +175,9 @@ __device__ __forceinline__ uint32_t neighbour_cell(const GridDesc & g, double qx
   return on ? ny * g.size_x + nx : g.ncell;
 }
 
-template <bool POW2, uint32_t CELLS>
-__global__ void __launch_bounds__(kRefineThreads) refine_kernel(const RefineArgs a)
+// SOURCE: where a job's map comes from (above).
+template <bool POW2, uint32_t CELLS, class SOURCE>
+__global__ void __launch_bounds__(kRefineThreads) refine_kernel(const RefineArgs<SOURCE> a)
 {
   __shared__ double wave_sums[kRefineWaves][kSums];
   __shared__ double at[5];     // the pose of the evaluation: x, y, theta, cos, sin
@@ -173,7 +185,8 @@ __global__ void __launch_bounds__(kRefineThreads) refine_kernel(const RefineArgs
   const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
   const uint32_t job = blockIdx.x;
   const RefineJob jr = a.jobs[job];   // (uniform over the block)
-  const InstalledMap map{a.grid.occ_bits, a.grid.cells_global};
+  const GridDesc & grid = a.source.grid(jr.slot);
+  const auto map = a.source.map(jr.slot);
   const double2 * beams = reinterpret_cast<const double2 *>(a.beams_xy) + jr.beam_first;
   const double start[3] = {jr.x, jr.y, jr.theta};
   refine::State st;   // (thread 0's)
@@ -199,7 +212,7 @@ __global__ void __launch_bounds__(kRefineThreads) refine_kernel(const RefineArgs
       {
         const uint32_t b = b0 + tid;
         const bool valid = b < jr.n_beams;
-        add_terms<POW2>(a.grid, map, beams[valid ? b : jr.n_beams - 1u], valid, x, y, c, s, sum);
+        add_terms<POW2>(grid, map, beams[valid ? b : jr.n_beams - 1u], valid, x, y, c, s, sum);
       }
     }
     else
@@ -214,7 +227,7 @@ __global__ void __launch_bounds__(kRefineThreads) refine_kernel(const RefineArgs
         const double2 b = beams[beam];
         const double qx = c * b.x - s * b.y + x;
         const double qy = s * b.x + c * b.y + y;
-        const uint32_t cell = valid ? neighbour_cell<POW2>(a.grid, qx, qy, i - beam * CELLS) : a.grid.ncell;
+        const uint32_t cell = valid ? neighbour_cell<POW2>(grid, qx, qy, i - beam * CELLS) : grid.ncell;
         uint32_t rank;
         // no lane of the wave holds a counting neighbour: the trip adds nothing
         if (!wave_any(map.find(cell, rank))) continue;
@@ -275,12 +288,42 @@ __global__ void __launch_bounds__(kRefineThreads) refine_kernel(const RefineArgs
   }
 }
 
+}  // namespace
+
+}  // namespace ndt2d
+
+// ---- the installed grid: the object and the C entry points ----
+#ifndef NDT2D_REFINE_KERNEL_ONLY
+
+struct ndt2d_refine : ndt2d::BatchHost
+{
+  size_t max_jobs = 0;                // slots of a chunk
+  uint32_t cells = 1;                 // the neighbourhood of a point: 1 (its own cell) or 9 (the 3 x 3 round it)
+  std::vector<uint64_t> scan_first;   // scan -> its first beam within the chunk's beams (or: not sent)
+  std::vector<uint32_t> sent;         // the chunk's scans in upload order
+};
+
+namespace ndt2d
+{
+
+namespace
+{
+
+using InstalledArgs = RefineArgs<InstalledSource>;
+
+// The installed grid's instantiation <POW2, CELLS> of the kernel.  (An alias the launches could do
+// without: tests/test_refine_neighbours_host.py pins the template head `<bool POW2, uint32_t CELLS>`
+// to this file's text, which the kernel's own head no longer is since it gained SOURCE.  It goes
+// when that pin is brought up to date.)
+template <bool POW2, uint32_t CELLS>
+constexpr auto installed_kernel = refine_kernel<POW2, CELLS, InstalledSource>;
+
 // CELLS: the neighbourhood of a point, 1 or 9.
 template <uint32_t CELLS>
-void launch_refine(bool pow2, dim3 blocks, dim3 threads, hipStream_t stream, const RefineArgs & a)
+void launch_refine(bool pow2, dim3 blocks, dim3 threads, hipStream_t stream, const InstalledArgs & a)
 {
-  if (pow2) hipLaunchKernelGGL((refine_kernel<true, CELLS>), blocks, threads, 0, stream, a);
-  else hipLaunchKernelGGL((refine_kernel<false, CELLS>), blocks, threads, 0, stream, a);
+  if (pow2) hipLaunchKernelGGL((installed_kernel<true, CELLS>), blocks, threads, 0, stream, a);
+  else hipLaunchKernelGGL((installed_kernel<false, CELLS>), blocks, threads, 0, stream, a);
 }
 
 struct RefineCall
@@ -302,19 +345,9 @@ int refine_chunk(ndt2d_refine * s, const GridDesc & grid, size_t k0, size_t k1, 
   hipStream_t stream = static_cast<hipStream_t>(ndt2d_get_stream(s->h));
 
   // the scans this chunk's jobs name, each once, in the order the jobs first name them
-  s->scan_first.assign(t.n_scans, kNotSent);
-  s->sent.clear();
-  size_t n_beams = 0;
-  for (size_t k = k0; k < k1; ++k)
-  {
-    const size_t sc = t.scan_of(k);
-    if (s->scan_first[sc] == kNotSent)
-    {
-      s->scan_first[sc] = n_beams;
-      s->sent.push_back(static_cast<uint32_t>(sc));
-      n_beams += t.beam_offsets[sc + 1] - t.beam_offsets[sc];
-    }
-  }
+  const size_t n_beams = refine_jobs::plan_sent_scans(
+    n_slots, [&](size_t b) { return k0 + b; }, [&](size_t k) { return t.scan_of(k); }, t.beam_offsets, t.n_scans, s->scan_first,
+    s->sent);
 
   // the one upload of the chunk: [beams | jobs | cos / sin pairs] (no lattice, no order table)
   const StageLayout at = stage_layout(0, 0, n_beams, n_slots, kRefineJobDoubles, 0, 2 * n_slots);
@@ -339,8 +372,8 @@ int refine_chunk(ndt2d_refine * s, const GridDesc & grid, size_t k0, size_t k1, 
   s->timed = false;
   if (s->timing) NDT2D_BATCH_HIP(s, hipEventRecord(s->ev[0], stream));
 
-  RefineArgs a{};
-  a.grid = grid;
+  InstalledArgs a{};
+  a.source.g = grid;
   a.jobs = reinterpret_cast<const RefineJob *>(s->d_stage + at.jobs);
   a.trig = s->d_stage + at.trig;
   a.beams_xy = s->d_stage + at.beams;
@@ -372,7 +405,7 @@ int ndt2d_refine_create(ndt2d_handle h, size_t max_jobs, ndt2d_refine ** out)
   NDT2D_C_TRY
   if (out == nullptr) return NDT2D_ERR_INVALID;
   *out = nullptr;
-  if (h == nullptr || max_jobs == 0 || max_jobs > 4096) return NDT2D_ERR_INVALID;
+  if (h == nullptr || max_jobs == 0 || max_jobs > ndt2d::kRefineMaxJobs) return NDT2D_ERR_INVALID;
   ndt2d_refine * r = new ndt2d_refine();
   r->h = h;
   r->device = ndt2d_device_id(h);
@@ -457,43 +490,10 @@ int ndt2d_refine_run(ndt2d_refine * r, const double * jobs_xyt, const uint32_t *
   {
     return batch_fail(r, NDT2D_ERR_INVALID, "ndt2d_refine_run: null argument");
   }
-  if (max_evals == 0) return batch_fail(r, NDT2D_ERR_INVALID, "ndt2d_refine_run: bad argument (max_evals == 0)");
-  if (!(tol_lin >= 0.0) || !(tol_ang >= 0.0) || !std::isfinite(tol_lin) || !std::isfinite(tol_ang))
-  {
-    return batch_fail(r, NDT2D_ERR_INVALID, "ndt2d_refine_run: bad argument (a tolerance is negative or not finite)");
-  }
-  if (n_jobs >= (1u << 24) || n_scans >= (1u << 24)) return batch_fail(r, NDT2D_ERR_INVALID, "ndt2d_refine_run: bad argument (n_jobs, n_scans)");
-  if (job_scan == nullptr && n_scans != n_jobs)
-  {
-    return batch_fail(r, NDT2D_ERR_INVALID, "ndt2d_refine_run: bad argument (no job_scan: job k uses scan k, n_scans must equal n_jobs)");
-  }
-  // every scan and every job is checked before anything is launched
-  for (size_t sc = 0; sc < n_scans; ++sc)
-  {
-    if (beam_offsets[sc + 1] < beam_offsets[sc])
-    {
-      return batch_fail(r, NDT2D_ERR_INVALID, "ndt2d_refine_run: scan " + std::to_string(sc) + ": beam_offsets decrease");
-    }
-    const size_t count = beam_offsets[sc + 1] - beam_offsets[sc];
-    // (what ndt2d_set_beams refuses)
-    if (count == 0 || count > ndt2d::kMaxScanBeams)
-    {
-      return batch_fail(r, NDT2D_ERR_INVALID, "ndt2d_refine_run: scan " + std::to_string(sc) + ": " + std::to_string(count) +
-                                             " beams (1 .. 2^20)");
-    }
-  }
-  for (size_t k = 0; k < n_jobs; ++k)
-  {
-    if (!std::isfinite(jobs_xyt[3 * k]) || !std::isfinite(jobs_xyt[3 * k + 1]) || !std::isfinite(jobs_xyt[3 * k + 2]))
-    {
-      return batch_fail(r, NDT2D_ERR_INVALID, "ndt2d_refine_run: job " + std::to_string(k) + ": the pose is not finite");
-    }
-    if (job_scan != nullptr && job_scan[k] >= n_scans)
-    {
-      return batch_fail(r, NDT2D_ERR_INVALID, "ndt2d_refine_run: job " + std::to_string(k) + ": scan " +
-                                             std::to_string(job_scan[k]) + " of " + std::to_string(n_scans));
-    }
-  }
+  // the rules, every scan and every job are checked before anything is launched
+  const std::string refusal = ndt2d::refine_jobs::refusal("ndt2d_refine_run", jobs_xyt, job_scan, n_jobs, beam_offsets, n_scans,
+                                                         max_evals, tol_lin, tol_ang);
+  if (!refusal.empty()) return batch_fail(r, NDT2D_ERR_INVALID, refusal);
   int rc = NDT2D_OK;
   const ndt2d::GridDesc grid = ndt2d::installed_grid(r->h, &rc);
   if (rc != NDT2D_OK)
@@ -515,3 +515,5 @@ int ndt2d_refine_run(ndt2d_refine * r, const double * jobs_xyt, const uint32_t *
 }
 
 }  // extern "C"
+
+#endif  // NDT2D_REFINE_KERNEL_ONLY: the object and the entry points of the installed grid

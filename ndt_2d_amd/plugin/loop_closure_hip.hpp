@@ -11,6 +11,13 @@
 // An accept corrects the scan's pose, which every later candidate starts from: the remaining
 // candidates are matched again, in one batch, from the corrected pose.
 //
+// setRefine() adds the Newton registration on each candidate's OWN map: every round's match is
+// followed by one ndt2d_matcher_refine_candidates call for the candidates of the round that pass
+// the accept test, each started from the scan's pose + its correction.  The accept test stays the
+// reference's, on the lattice score; the accepted closure gains the refined pose and the
+// covariance from the Hessian there -- what the constraint of :658 wants -- and the scan goes on
+// from the refined pose where the iteration converged (or ran out of evaluations) without raising f.
+//
 // Plain arrays over the C-ABI, as the other mirrors in this directory: nothing of ROS or Eigen.
 #ifndef NDT_2D_HIP__LOOP_CLOSURE_HIP_HPP_
 #define NDT_2D_HIP__LOOP_CLOSURE_HIP_HPP_
@@ -34,6 +41,12 @@ struct LoopClosure
   double correction[3];      // matchScan's pose output (dx, dy, dth)
   double pose[3];            // the scan's pose after the correction (:652-655)
   double covariance[9];      // row-major
+  // with setRefine(): the Newton registration on the candidate's own map, from `pose`
+  bool refined = false;
+  double refined_pose[3] = {0.0, 0.0, 0.0};   // absolute
+  double refined_covariance[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // row-major; valid with has_refined_covariance
+  bool has_refined_covariance = false;        // the Hessian at refined_pose is positive definite
+  int refine_status = NDT2D_REFINE_NO_OVERLAP;   // NDT2D_REFINE_*
 };
 
 class LoopClosureHip
@@ -52,6 +65,22 @@ public:
     if (id_out != nullptr) *id_out = id;
     return true;
   }
+
+  // From the next closeLoops() on, refine the accepted candidates (see above).  max_evals, tol_lin,
+  // tol_ang: ndt2d_refine_run's rules; cells: 1 or 9 cells per point (9 for a covariance);
+  // laser_max_beams: the matcher's (initialize), which the covariance needs to turn the score's
+  // Hessian back into the sum's.  false: the neighbourhood is refused (last_error()).
+  bool setRefine(std::uint32_t max_evals, double tol_lin, double tol_ang, std::uint32_t cells, std::size_t laser_max_beams)
+  {
+    if (!ok(ndt2d_matcher_set_refine_neighbourhood(m_, cells))) return false;
+    refine_ = true;
+    max_evals_ = max_evals;
+    tol_lin_ = tol_lin;
+    tol_ang_ = tol_ang;
+    laser_max_beams_ = laser_max_beams;
+    return true;
+  }
+  void clearRefine() { refine_ = false; }
 
   // [begin_idx, end_idx) of src/ndt_mapper.cpp:628-631, quirk included: the candidate
   // i == rolling yields only scan i - 1.
@@ -104,15 +133,17 @@ public:
         return false;
       }
       std::size_t accepted = K;
+      passing_.clear();
       for (std::size_t k = 0; k < K; ++k)
       {
         if (std::isfinite(scores_[k]) && scores_[k] < typical_response)
         {
-          accepted = k;
-          break;
+          if (accepted == K) accepted = k;
+          passing_.push_back(static_cast<std::uint32_t>(k));
         }
       }
       if (accepted == K) break;
+      if (refine_ && !refineRound(scan_pose_inout, points_xy, n_points, K)) return false;
       LoopClosure c;
       c.candidate = todo[accepted];
       c.score = scores_[accepted];
@@ -124,6 +155,22 @@ public:
         c.pose[d] = scan_pose_inout[d];
       }
       for (int d = 0; d < 9; ++d) c.covariance[d] = covariances_[9 * accepted + d];
+      if (refine_)
+      {
+        // (job 0 of the round's refinement is the first candidate that passed: the accepted one)
+        c.refined = true;
+        c.refine_status = r_status_[0];
+        for (int d = 0; d < 3; ++d) c.refined_pose[d] = r_poses_[d];
+        const double n = static_cast<double>(laser_max_beams_ < n_points ? laser_max_beams_ : n_points);
+        const double * h = r_hessians_.data();
+        const double sum_hessian[6] = {h[0] * n, h[1] * n, h[2] * n, h[4] * n, h[5] * n, h[8] * n};
+        c.has_refined_covariance = r_evals_[0] > 0 && ndt2d_refine_covariance(sum_hessian, c.refined_covariance) == NDT2D_OK;
+        const bool usable = c.refine_status == NDT2D_REFINE_CONVERGED || c.refine_status == NDT2D_REFINE_MAX_EVALS;
+        if (usable && r_scores_[0] <= r_start_scores_[0])
+        {
+          for (int d = 0; d < 3; ++d) scan_pose_inout[d] = c.refined_pose[d];
+        }
+      }
       closures_out.push_back(c);
       todo.erase(todo.begin(), todo.begin() + static_cast<std::ptrdiff_t>(accepted) + 1);
     }
@@ -140,6 +187,30 @@ public:
   const std::string & last_error() const { return error_; }
 
 private:
+  // One ndt2d_matcher_refine_candidates call for the candidates of the round that passed
+  // (passing_), each from the scan's pose + its correction, all on the one scan.
+  bool refineRound(const double * scan_pose, const double * points_xy, std::size_t n_points, std::size_t K)
+  {
+    const std::size_t n_jobs = passing_.size();
+    r_jobs_.resize(3 * n_jobs);
+    for (std::size_t j = 0; j < n_jobs; ++j)
+    {
+      for (int d = 0; d < 3; ++d) r_jobs_[3 * j + d] = corrections_[3 * passing_[j] + d] + scan_pose[d];
+    }
+    r_scan_.assign(n_jobs, 0u);
+    r_poses_.assign(3 * n_jobs, 0.0);
+    r_scores_.assign(n_jobs, 0.0);
+    r_start_scores_.assign(n_jobs, 0.0);
+    r_hessians_.assign(9 * n_jobs, 0.0);
+    r_status_.assign(n_jobs, 0);
+    r_evals_.assign(2 * n_jobs, 0u);
+    const std::size_t point_offsets[2] = {0, n_points};
+    return ok(ndt2d_matcher_refine_candidates(m_, offsets_.data(), ids_.data(), poses_.data(), K, r_jobs_.data(), r_scan_.data(),
+                                              passing_.data(), n_jobs, points_xy, point_offsets, 1, max_evals_, tol_lin_,
+                                              tol_ang_, r_poses_.data(), r_scores_.data(), r_start_scores_.data(), nullptr,
+                                              r_hessians_.data(), r_status_.data(), r_evals_.data()));
+  }
+
   bool ok(int rc)
   {
     if (rc == NDT2D_OK) return true;
@@ -151,6 +222,14 @@ private:
   std::vector<std::size_t> sizes_;   // point count of stored scan `id`
   std::vector<std::size_t> offsets_, ids_;
   std::vector<double> poses_, corrections_, covariances_, scores_;
+  // setRefine()
+  bool refine_ = false;
+  std::uint32_t max_evals_ = 32;
+  double tol_lin_ = 1e-6, tol_ang_ = 1e-6;
+  std::size_t laser_max_beams_ = 0;
+  std::vector<std::uint32_t> passing_, r_scan_, r_evals_;
+  std::vector<std::int32_t> r_status_;
+  std::vector<double> r_jobs_, r_poses_, r_scores_, r_start_scores_, r_hessians_;
   std::string error_;
 };
 

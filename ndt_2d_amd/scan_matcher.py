@@ -528,39 +528,36 @@ class ScanMatcherNDT:
         the scan's beams in use) through ndt2d_refine_covariance, a [3, 3] array -- or None where
         that Hessian is not positive definite; meant to be taken with neighbourhood 9."""
         self.set_refine_neighbourhood(neighbourhood)
-        jp = _f64(jobs, (-1, 3))
-        K = len(jp)
-        arrays = [_f64(pts, (-1, 2)) for pts in scans]
-        offsets = np.zeros(len(arrays) + 1, dtype=np.uintp)
-        if arrays:
-            offsets[1:] = np.cumsum([len(a) for a in arrays])
-        pts = np.ascontiguousarray(np.concatenate(arrays) if arrays else np.zeros((0, 2)), dtype=np.float64)
-        js, js_ptr = None, None
-        if job_scan is not None:
-            js = np.ascontiguousarray(job_scan, dtype=np.int64).reshape(-1)
-            if len(js) != K:
-                raise ValueError("refineScans: job_scan must name one scan per job")
-            if np.any(js < 0) or np.any(js >= 2 ** 32):
-                raise ValueError("refineScans: job_scan must hold scan indices")
-            js = np.ascontiguousarray(js, dtype=np.uint32)
-            js_ptr = js.ctypes.data_as(C.POINTER(C.c_uint32))
-        if not 0 <= int(max_evals) < 2 ** 32:
-            raise ValueError("refineScans: max_evals must fit 32 bits")
-        poses, scores, starts = np.zeros((K, 3)), np.zeros(K), np.zeros(K)
-        grads, hess = np.zeros((K, 3)), np.zeros((K, 3, 3))
-        status, evals = np.zeros(K, dtype=np.int32), np.zeros((K, 2), dtype=np.uint32)
+        call = _RefineCall("refineScans", self.params, jobs, scans, job_scan, max_evals)
         self._check(self._L.ndt2d_matcher_refine_scans(
-            self._m, dptr(jp), js_ptr, K, dptr(pts), offsets.ctypes.data_as(C.POINTER(C.c_size_t)), len(arrays),
-            int(max_evals), float(tol_lin), float(tol_ang), dptr(poses), dptr(scores), dptr(starts), dptr(grads), dptr(hess),
-            status.ctypes.data_as(C.POINTER(C.c_int32)), evals.ctypes.data_as(C.POINTER(C.c_uint32))), "refineScans")
-        beams_max = int(self.params["laser_max_beams"])
-        out = []
-        for k in range(K):
-            n = min(beams_max, len(arrays[int(js[k]) if js is not None else k]))
-            out.append(dict(pose=poses[k].copy(), score=float(scores[k]), start_score=float(starts[k]), gradient=grads[k].copy(),
-                            hessian=hess[k].copy(), evals=int(evals[k, 0]), steps=int(evals[k, 1]), status=int(status[k]),
-                            covariance=refine_covariance(hess[k] * float(n))))
-        return out
+            self._m, *call.job_args, int(max_evals), float(tol_lin), float(tol_ang), *call.out_args), "refineScans")
+        return call.dicts()
+
+    def refineCandidates(self, jobs, scans, candidates, job_candidate=None, job_scan=None, max_evals=32, tol_lin=1e-6,
+                         tol_ang=1e-6, neighbourhood=1):
+        """refineScans of K jobs, each on a loop-closure candidate's OWN map, in one call: `candidates`
+        as matchCandidates takes them (a list of candidate maps, each a list of (stored scan id,
+        pose_xyt)), jobs / scans / job_scan as refineScans takes them, job_candidate[k]: the
+        candidate of job k (None: job k uses candidate k).  Returns the dicts refineScans returns
+        after reset() / addScansById(candidates[job_candidate[k]]), bit for bit, covariance
+        included -- from one upload, one build launch for the candidates named, one launch of the
+        refinement and one read-back per chunk.  The NDT in place is not touched: has_ndt() and the
+        grid are the same before and after.  A scan without points: score 0.0, the job's own pose,
+        status REFINE_NO_OVERLAP."""
+        self.set_refine_neighbourhood(neighbourhood)
+        call = _RefineCall("refineCandidates", self.params, jobs, scans, job_scan, max_evals)
+        K = len(candidates)
+        offsets = np.zeros(K + 1, dtype=np.uintp)
+        offsets[1:] = np.cumsum([len(c) for c in candidates]) if K else []
+        flat = [entry for c in candidates for entry in c]
+        ids = np.ascontiguousarray([e[0] for e in flat], dtype=np.uintp).reshape(-1)
+        poses = _f64([e[1] for e in flat], (-1, 3)) if flat else np.zeros((0, 3))
+        jc = _index_array("refineCandidates", "job_candidate", "candidate", job_candidate, call.K)
+        self._check(self._L.ndt2d_matcher_refine_candidates(
+            self._m, offsets.ctypes.data_as(C.POINTER(C.c_size_t)), ids.ctypes.data_as(C.POINTER(C.c_size_t)), dptr(poses), K,
+            call.job_args[0], call.job_args[1], jc.ctypes.data_as(C.POINTER(C.c_uint32)) if jc is not None else None,
+            *call.job_args[2:], int(max_evals), float(tol_lin), float(tol_ang), *call.out_args), "refineCandidates")
+        return call.dicts()
 
     def set_refine_neighbourhood(self, cells):
         """The neighbourhood of the later refineScans calls: 1 or 9 cells per point."""
@@ -922,6 +919,54 @@ def statistics_covariance(out, cov_prev):
     return cov
 
 
+def _index_array(call, name, what, values, K):
+    """An optional per-job index list as the C-ABI takes it: uint32[K], or None."""
+    if values is None:
+        return None
+    v = np.ascontiguousarray(values, dtype=np.int64).reshape(-1)
+    if len(v) != K:
+        raise ValueError("%s: %s must name one %s per job" % (call, name, what))
+    if np.any(v < 0) or np.any(v >= 2 ** 32):
+        raise ValueError("%s: %s must hold %s indices" % (call, name, what))
+    return np.ascontiguousarray(v, dtype=np.uint32)
+
+
+class _RefineCall:
+    """The jobs and scans of a Newton registration as the C-ABI takes them, its output arrays, and
+    the dicts they become (refineScans, refineCandidates)."""
+
+    def __init__(self, call, params, jobs, scans, job_scan, max_evals):
+        self.jp = _f64(jobs, (-1, 3))
+        self.K = K = len(self.jp)
+        self.arrays = [_f64(pts, (-1, 2)) for pts in scans]
+        self.offsets = np.zeros(len(self.arrays) + 1, dtype=np.uintp)
+        if self.arrays:
+            self.offsets[1:] = np.cumsum([len(a) for a in self.arrays])
+        self.pts = np.ascontiguousarray(np.concatenate(self.arrays) if self.arrays else np.zeros((0, 2)), dtype=np.float64)
+        self.js = _index_array(call, "job_scan", "scan", job_scan, K)
+        if not 0 <= int(max_evals) < 2 ** 32:
+            raise ValueError("%s: max_evals must fit 32 bits" % call)
+        self.beams_max = int(params["laser_max_beams"])
+        self.poses, self.scores, self.starts = np.zeros((K, 3)), np.zeros(K), np.zeros(K)
+        self.grads, self.hess = np.zeros((K, 3)), np.zeros((K, 3, 3))
+        self.status, self.evals = np.zeros(K, dtype=np.int32), np.zeros((K, 2), dtype=np.uint32)
+        # jobs_xyt, job_scan, n_jobs, points_xy, point_offsets, n_scans
+        self.job_args = (dptr(self.jp), self.js.ctypes.data_as(C.POINTER(C.c_uint32)) if self.js is not None else None, K,
+                         dptr(self.pts), self.offsets.ctypes.data_as(C.POINTER(C.c_size_t)), len(self.arrays))
+        self.out_args = (dptr(self.poses), dptr(self.scores), dptr(self.starts), dptr(self.grads), dptr(self.hess),
+                         self.status.ctypes.data_as(C.POINTER(C.c_int32)), self.evals.ctypes.data_as(C.POINTER(C.c_uint32)))
+
+    def dicts(self):
+        out = []
+        for k in range(self.K):
+            n = min(self.beams_max, len(self.arrays[int(self.js[k]) if self.js is not None else k]))
+            out.append(dict(pose=self.poses[k].copy(), score=float(self.scores[k]), start_score=float(self.starts[k]),
+                            gradient=self.grads[k].copy(), hessian=self.hess[k].copy(), evals=int(self.evals[k, 0]),
+                            steps=int(self.evals[k, 1]), status=int(self.status[k]),
+                            covariance=refine_covariance(self.hess[k] * float(n))))
+        return out
+
+
 def loop_closure_window(i, rolling):
     """The scans a loop-closure candidate map is built from (reference src/ndt_mapper.cpp:
     628-631): [begin_idx, end_idx) = "one additional scan on either side of candidate" as the
@@ -933,7 +978,7 @@ def loop_closure_window(i, rolling):
 
 
 def close_loops(matcher, scan_pose, points, candidate_indices, graph_poses, rolling, typical_response, limit,
-                scan_sizes=None):
+                scan_sizes=None, refine=None):
     """The loop-closure thread's walk over one new scan's candidates (reference
     src/ndt_mapper.cpp:619-671) on the batched match.  candidate_indices: what findNearest
     returned, in its order; graph_poses[i]: the pose of graph scan i, which is stored on the
@@ -949,7 +994,17 @@ def close_loops(matcher, scan_pose, points, candidate_indices, graph_poses, roll
     matched again, in one batch, from the corrected pose.
 
     Returns (pose, accepted): the scan's final pose and a list of dict(candidate, score,
-    correction, covariance, pose) in the order the constraints would be added."""
+    correction, covariance, pose) in the order the constraints would be added.
+
+    refine: None, or dict(max_evals=..., tol_lin=..., tol_ang=..., neighbourhood=...) (any subset:
+    refineCandidates' arguments).  With it every round's matchCandidates is followed by ONE
+    refineCandidates call -- the Newton registration on each candidate's own map -- for every
+    candidate of the round that passes the accept test, each started from pose + its correction.
+    The accept test stays the reference's, on the lattice score, and the walk consumes the first
+    accepted candidate as before; its entry gains refined_pose, refined_covariance (None where the
+    Hessian is not positive definite) and refine_status (its `pose` stays the lattice pose).  The
+    scan's pose -- what the next round starts from, and what is returned -- is the refined pose
+    where the status is CONVERGED or MAX_EVALS and f did not rise, the lattice pose otherwise."""
     pose = np.array(scan_pose, dtype=np.float64).reshape(3).copy()
     todo = []
     for i in candidate_indices:
@@ -962,15 +1017,25 @@ def close_loops(matcher, scan_pose, points, candidate_indices, graph_poses, roll
     while todo:
         batch = [[(j, graph_poses[j]) for j in loop_closure_window(i, rolling)] for i in todo]
         results = matcher.matchCandidates(pose, points, batch)
+        passing = [k for k, res in enumerate(results) if np.isfinite(res["score"]) and res["score"] < typical_response]
+        refined = None
+        if refine is not None and passing:
+            starts = [np.array(results[k]["pose"], dtype=np.float64) + pose for k in passing]
+            refined = matcher.refineCandidates(starts, [points], [batch[k] for k in passing], job_scan=[0] * len(passing),
+                                               **refine)
         rest = []
-        for k, (i, res) in enumerate(zip(todo, results)):
-            if np.isfinite(res["score"]) and res["score"] < typical_response:
-                correction = np.array(res["pose"], dtype=np.float64)
-                pose = correction + pose               # correction.x += scan->getPose().x; ... (:652-654)
-                accepted.append(dict(candidate=i, score=res["score"], correction=correction,
-                                     covariance=res["covariance"], pose=pose.copy()))
-                rest = todo[k + 1:]
-                break
+        for k in passing[:1]:
+            i, res = todo[k], results[k]
+            correction = np.array(res["pose"], dtype=np.float64)
+            pose = correction + pose                   # correction.x += scan->getPose().x; ... (:652-654)
+            entry = dict(candidate=i, score=res["score"], correction=correction, covariance=res["covariance"], pose=pose.copy())
+            if refined is not None:
+                r = refined[0]
+                entry.update(refined_pose=r["pose"].copy(), refined_covariance=r["covariance"], refine_status=r["status"])
+                if r["status"] in (_capi.REFINE_CONVERGED, _capi.REFINE_MAX_EVALS) and r["score"] <= r["start_score"]:
+                    pose = r["pose"].copy()
+            accepted.append(entry)
+            rest = todo[k + 1:]
         todo = rest
     return pose, accepted
 
