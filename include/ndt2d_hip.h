@@ -669,7 +669,15 @@ int ndt2d_pf_measure(ndt2d_handle h, const double * h_poses_xyt, size_t n_poses,
  * 63-64, particle_filter.hpp), i.e. not reproducibly.  Every call below takes the
  * draws either as d_noise = [n][3] float standard normals (device pointer), or
  * with d_noise == NULL from a counter-based stream: Philox4x32-10 keyed by
- * `seed`, counter (first_index + i, step) for particle i, Box-Muller.  The stream
+ * `seed`, counter (first_index + i, step) for particle i, Box-Muller.  In full: counter
+ * words (index lo, index hi, step lo, step hi), key (seed lo, seed hi) give four words
+ * w0..w3; the uniform of a word is the float  u(w) = fl((w >> 8) + 0.5) * 2^-24  with the
+ * sum rounded to nearest even in float32 -- exactly (k + 0.5) 2^-24 for k = w >> 8 below
+ * 2^23, an even multiple of 2^-24 from there, and 1.0f for k = 2^24 - 1: u lies in (0, 1];
+ * r0 = sqrtf(-2 logf(u(w0))), r1 = sqrtf(-2 logf(u(w2))), angles the float products
+ * a0 = 2 pi u(w1), a1 = 2 pi u(w3); the normals are (r0 cosf(a0), r0 sinf(a0), r1 cosf(a1)).
+ * Every draw is finite, |z| <= sqrt(50 ln 2) = 5.887; u = 1 (probability 2^-24 per radius)
+ * gives radius 0 and exactly zero normals.  The stream
  * depends on (seed, step, global particle index) only, so shards of a particle set
  * on different GPUs draw what the whole set would.  ndt2d_pf_noise_launch writes
  * that stream out (the same numbers a fused call uses). */

@@ -10,7 +10,14 @@
 // reproducible.  Here every particle owns a counter-based stream: Philox4x32-10
 // keyed by `seed`, counter = (global particle index, step), four 32-bit words ->
 // two Box-Muller pairs -> the three standard normals the reference draws per
-// particle, in its order.  The stream depends only on (seed, step, index), so a
+// particle, in its order.  The uniform of a word w is the float
+//   u = fl((w >> 8) + 0.5) * 2^-24   (round to nearest even; in (0, 1], see unit_open),
+// radii are sqrtf(-2 logf(u)) of w[0] and w[2], angles the float products 2 pi * u of
+// w[1] and w[3].  u = 1.0f (one word in 2^24) gives radius 0: then both normals of
+// the first pair, or the third normal, are exactly zero; every draw is finite and
+// the largest radius is sqrt(50 ln 2) = 5.887.  This definition is the published
+// stream: tests/noise_restatement.py restates it and the parity tests pin it.
+// The stream depends only on (seed, step, index), so a
 // shard of the particle set produces the numbers the whole set would.  The same
 // device function backs noise_kernel, so a caller (and the parity tests) can read
 // the exact normals a fused launch uses.
@@ -66,7 +73,9 @@ __device__ __forceinline__ void philox4x32_10(uint64_t seed, uint64_t index, uin
   out[3] = c3;
 }
 
-// 24 random bits -> (0, 1): every value and its complement are exact floats
+// 24 random bits k -> (0, 1]: float round-to-nearest-even of k + 0.5, times 2^-24.  The sum is
+// exact only below k = 2^23; from there it needs 25 significand bits and is rounded to even
+// (k even: k, k odd: k + 1), so k = 2^24 - 1 gives 1.0f.  Never 0: the logarithm stays finite.
 __device__ __forceinline__ float unit_open(uint32_t bits)
 {
   return (static_cast<float>(bits >> 8) + 0.5f) * (1.0f / 16777216.0f);

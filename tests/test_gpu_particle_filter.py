@@ -6,10 +6,12 @@ Tolerances: theta goes through exact double adds and an exact fmod, so it is
 compared bit-for-bit; x / y differ by the device sincos's last ulps (1e-12
 absolute bound); statistics by summation order (1e-11 relative)."""
 import ctypes as C
+import math
 
 import numpy as np
 import pytest
 
+import noise_restatement as R
 import oracle_lib as O
 from ndt_2d_amd import ScanMatcherNDT, _capi, synth
 from ndt_2d_amd.particle_filter import MotionModel, ParticleFilter
@@ -359,3 +361,468 @@ def test_eight_wave_groups_give_the_four_wave_bits():
         assert np.allclose(a, b, rtol=1e-12, atol=1e-15)       # (the moment sums meet in another order)
     auto = m.scorePoses(pts, parts)                              # the policy's own choice: the same bits
     assert np.array_equal(auto, out["0"][0])
+
+
+# ---- the noise stream against its CPU restatement ---------------------------------------------
+#
+# tests/noise_restatement.py restates the stream from the header's words (Philox4x32-10, the
+# float32 uniform, Box-Muller) and is itself pinned to the Random123 known answers on the CPU
+# (tests/test_noise_restatement.py).  The device's float32 normals are held to its float64 ones.
+
+# Maximum errors of the device's logf and sinf / cosf in ulp.  The ROCm installs this was written
+# against carry no copy of the HIP math API's accuracy table, so 2 ulp is taken for each.
+E_LOG_ULP = 2
+E_TRIG_ULP = 2
+NOISE_B = E_LOG_ULP + 1 + 2 * E_TRIG_ULP + 1          # = 8, see _noise_ratio
+
+# the grid cap of the streaming kernels (kMaxStreamBlocks, kMaxPosesBlocks) and their block size
+CAP_BLOCKS, BLOCK = 4096, 256
+# the smallest size that sends some threads round their loop again AND leaves a partial wave
+N_BEYOND = CAP_BLOCKS * BLOCK + 257
+SMALL_SIZES = (1, 2, 63, 64, 65, 255, 256, 257, 511)
+
+KAT_STREAM = R.KAT_STREAM          # (seed, step, first) forms of the Random123 known answers
+R_MAX = R.R_MAX                    # sqrt(-2 log 2^-25) = 5.8870501...
+
+
+def _noise(torch, matcher, seed, step, first, n):
+    """ndt2d_pf_noise_launch into a buffer that held NaN: what is not written stays visible."""
+    s = _stream(torch, matcher)
+    with torch.cuda.stream(s):
+        z = torch.full((n, 3), float("nan"), dtype=torch.float32, device="cuda")
+    s.synchronize()
+    matcher.pf_noise_launch(seed, step, first, n, z.data_ptr())
+    matcher.synchronize()
+    return z
+
+
+def _noise_ratio(z_dev, seed, step, first):
+    """max |z_dev - z_ref| / (2^-24 max(1, r)) over the components, r the component's radius.
+
+    The bound on it, in units of 2^-24 max(1, r), term by term for z = r * trig(a), where the
+    uniforms and the float32 angle a are reproduced to the bit (so the arguments carry no error):
+      * logf: E_LOG_ULP ulp; an ulp is at most 2^-23 of the value, so the relative error of
+        -2 log u is at most 2 E_LOG_ULP 2^-24, and the square root halves it:     E_LOG_ULP
+      * sqrtf is correctly rounded, half an ulp <= 2^-24 relative:                 1
+      * cosf / sinf: E_TRIG_ULP ulp of a value of magnitude <= 1, an ulp there at most 2^-23,
+        i.e. 2 E_TRIG_ULP 2^-24 absolute, times r:                                 2 E_TRIG_ULP
+      * the product r * trig is correctly rounded, 2^-24 relative, |z| <= r:       1
+    NOISE_B = E_LOG_ULP + 1 + 2 E_TRIG_ULP + 1 = 8 (2.8e-6 at the largest radius), second-order
+    terms dropped (they are 2^-24 times smaller).  numpy's float32 chain measures 2.9 on the CPU.
+    Largest ratio observed on an MI355X over every case of this file: 3.16 (beyond the cap,
+    n = 1,048,833; 3.10 at n = 20001)."""
+    z_dev = np.asarray(z_dev, dtype=np.float64)
+    assert np.all(np.isfinite(z_dev))
+    z_ref, r = R.normals_reference(seed, step, first, len(z_dev))
+    ratio = np.abs(z_dev - z_ref) / (2.0 ** -24 * np.maximum(1.0, r))
+    return float(ratio.max())
+
+
+@pytest.mark.parametrize("seed,step,first,n", [
+    (0xC0FFEE12345, 7, 0, 20001),
+    (0xC0FFEE12345, 7, 4097, 1000),
+    (0xC0FFEE12345, 7, (1 << 40) + 3, 64),
+    (0xC0FFEE12345, (5 << 32) + 9, 0, 1000),
+    (99 + (1 << 33), 7, 0, 1000),
+] + [(seed, step, first, 1) for seed, step, first in KAT_STREAM])
+def test_noise_stream_is_the_restatement(torch, matcher, seed, step, first, n):
+    """Every word of (seed, step, index) is where the header says: wrong round constants, swapped
+    counter words, a dropped high half, cos / sin or w[1] / w[2] exchanged all move a draw by
+    O(1), the bound is NOISE_B 2^-24 max(1, r) (derived at _noise_ratio).  The last three cases
+    are single draws whose counter and key are the three Random123 known-answer vectors."""
+    z = _noise(torch, matcher, seed, step, first, n).cpu().numpy()
+    ratio = _noise_ratio(z, seed, step, first)
+    print("noise ratio (seed=%#x step=%#x first=%#x n=%d): %.3f" % (seed, step, first, n, ratio))
+    assert ratio <= NOISE_B, ratio
+
+
+def test_noise_sub_range_is_the_slice_of_the_restated_whole(torch, matcher):
+    seed, step = 0xC0FFEE12345, 7
+    whole = _noise(torch, matcher, seed, step, 0, 20001).cpu().numpy()
+    part = _noise(torch, matcher, seed, step, 4097, 1000).cpu().numpy()
+    assert np.array_equal(part, whole[4097:5097])
+
+
+# seed = 1, step = 1: the particle indices whose words have all-ones / all-zero top 24 bits
+# (tests/test_noise_restatement.py asserts the words)
+D_SEED, D_STEP = R.DESIGNED_SEED, R.DESIGNED_STEP
+D_UR_ONE, D_UR_MIN, D_UR2_ONE, D_UR2_MIN, D_UA_ONE, D_UA_MIN = (
+    R.D_UR_ONE, R.D_UR_MIN, R.D_UR2_ONE, R.D_UR2_MIN, R.D_UA_ONE, R.D_UA_MIN)
+
+
+def test_designed_draws_at_the_ends_of_the_uniform(torch, matcher):
+    """The uniform is float32 RNE of (k + 0.5) times 2^-24, in (0, 1]: k = 2^24 - 1 gives 1.0f,
+    radius 0 and exactly zero normals; k = 0 gives the largest radius, sqrt(50 ln 2)."""
+    got = {}
+    for index in (D_UR_ONE, D_UR_MIN, D_UR2_ONE, D_UR2_MIN, D_UA_ONE, D_UA_MIN):
+        z = _noise(torch, matcher, D_SEED, D_STEP, index, 1).cpu().numpy()
+        assert np.all(np.isfinite(z)), (index, z)
+        ratio = _noise_ratio(z, D_SEED, D_STEP, index)
+        print("designed draw %d: z = %r ratio %.3f" % (index, z[0].tolist(), ratio))
+        assert ratio <= NOISE_B, (index, ratio)
+        got[index] = z[0].astype(np.float64)
+    assert got[D_UR_ONE][0] == 0.0 and got[D_UR_ONE][1] == 0.0        # (either sign of zero)
+    assert got[D_UR2_ONE][2] == 0.0
+    tol = NOISE_B * 2.0 ** -24 * R_MAX
+    # (two components, each within tol of the reference's: their hypot within sqrt(2) tol)
+    assert abs(np.hypot(got[D_UR_MIN][0], got[D_UR_MIN][1]) - R_MAX) <= math.sqrt(2.0) * tol
+    _, r = R.normals_reference(D_SEED, D_STEP, D_UR2_MIN, 1)
+    assert r[0, 2] == pytest.approx(R_MAX, rel=1e-15, abs=0)
+    z_ref, _ = R.normals_reference(D_SEED, D_STEP, D_UR2_MIN, 1)
+    assert abs(got[D_UR2_MIN][2] - z_ref[0, 2]) <= tol
+    # angle = float32 2 pi and the smallest angle: the cosine is 1 to the bound, the sine tiny
+    for index in (D_UA_ONE, D_UA_MIN):
+        z_ref, r = R.normals_reference(D_SEED, D_STEP, index, 1)
+        assert z_ref[0, 0] == pytest.approx(r[0, 0], rel=1e-12, abs=0) and abs(z_ref[0, 1]) < 1e-6 * r[0, 0]
+
+
+def test_motion_on_the_zero_radius_draw_matches_oracle(torch, matcher):
+    """The fused Philox path at the index whose radius is 0: the oracle with z = (0, 0, z2)."""
+    z = _noise(torch, matcher, D_SEED, D_STEP, D_UR_ONE, 1).cpu().numpy()
+    z_ref, _ = R.normals_reference(D_SEED, D_STEP, D_UR_ONE, 1)
+    z_want = np.array([[0.0, 0.0, z[0, 2]]], dtype=np.float32)
+    assert abs(float(z[0, 2]) - z_ref[0, 2]) <= NOISE_B * 2.0 ** -24 * max(1.0, abs(z_ref[0, 2]))
+    poses = np.array([[1.25, -0.5, 0.75]])
+    for motion, alphas in ((MOTIONS[4], ALPHAS2), (MOTIONS[6], ALPHAS)):
+        want, _ = O.motion_sample(*motion, alphas, poses, z_want)
+        got = _motion(torch, matcher, poses, motion, alphas, None, D_SEED, D_STEP, D_UR_ONE)
+        assert np.array_equal(got[:, 2], want[:, 2])
+        assert np.max(np.abs(got[:, :2] - want[:, :2])) < 1e-12
+        assert not np.array_equal(got, poses)
+
+
+# ---- the streaming kernels at the sizes where their loops and reductions change shape ----------
+
+def _motion(torch, matcher, poses, motion, alphas, z=None, seed=0, step=0, first=0):
+    n = len(poses)
+    s = _stream(torch, matcher)
+    with torch.cuda.stream(s):
+        d_p = torch.from_numpy(np.ascontiguousarray(poses, dtype=np.float64)).cuda()
+        d_z = None if z is None else torch.from_numpy(np.ascontiguousarray(z, dtype=np.float32)).cuda()
+    s.synchronize()
+    matcher.pf_motion_launch(d_p.data_ptr(), n, *motion, alphas,
+                             None if d_z is None else d_z.data_ptr(), seed, step, first)
+    matcher.synchronize()
+    return d_p.cpu().numpy()
+
+
+def _init(torch, matcher, n, args, z=None, seed=0, step=0, first=0):
+    """ndt2d_pf_init_launch into poses that held -1.0e30 (no init result is that)."""
+    s = _stream(torch, matcher)
+    with torch.cuda.stream(s):
+        d_p = torch.full((n, 3), -1.0e30, dtype=torch.float64, device="cuda")
+        d_z = None if z is None else torch.from_numpy(np.ascontiguousarray(z, dtype=np.float32)).cuda()
+    s.synchronize()
+    matcher.pf_init_launch(d_p.data_ptr(), n, *args, None if d_z is None else d_z.data_ptr(),
+                           seed, step, first)
+    matcher.synchronize()
+    return d_p.cpu().numpy()
+
+
+def _statistics(torch, matcher, poses, w, uniform):
+    """pose_moments_launch + pf_finalize_launch: (the eight raw sums, out[8], weights)."""
+    n = len(poses)
+    s = _stream(torch, matcher)
+    with torch.cuda.stream(s):
+        d_p = torch.from_numpy(np.ascontiguousarray(poses, dtype=np.float64)).cuda()
+        d_w = torch.from_numpy(np.ascontiguousarray(w, dtype=np.float64)).cuda()
+        d_s = torch.full((16,), float("nan"), dtype=torch.float64, device="cuda")
+    s.synchronize()
+    matcher.pose_moments_launch(d_p.data_ptr(), n, None if uniform else d_w.data_ptr(),
+                                d_s.data_ptr())
+    matcher.pf_finalize_launch(d_p.data_ptr(), n, d_w.data_ptr(), d_s.data_ptr(),
+                               d_s.data_ptr() + 64)
+    matcher.synchronize()
+    st = d_s.cpu().numpy()
+    return st[:8].copy(), st[8:].copy(), d_w.cpu().numpy()
+
+
+def _wrap_poses(rng, n):
+    """The particle cloud of test_pose_moments_and_finalize_match_update_statistics: headings
+    around 3.0 rad straddle the +-pi wrap."""
+    poses = np.empty((n, 3))
+    poses[:, :2] = rng.normal([2.0, -1.0], [0.3, 0.6], size=(n, 2))
+    t = rng.normal(3.0, 0.4, size=n)
+    poses[:, 2] = np.where(t > np.pi, t - 2.0 * np.pi, t)
+    assert np.all(np.abs(poses[:, 2]) <= np.pi)
+    return poses
+
+
+def _check_statistics(poses, w, out, w_got, tail=None):
+    """Against ParticleFilter::updateStatistics at the tolerances of
+    test_pose_moments_and_finalize_match_update_statistics."""
+    cov_prev = np.zeros((3, 3))
+    cov_prev[2, 2] = 0.125
+    w_want, mean_want, cov_want = O.pf_update_statistics(poses, w, cov_prev)
+    assert np.allclose(w_got, w_want, rtol=1e-12, atol=0)
+    assert np.allclose(out[1:4], mean_want, rtol=1e-11, atol=1e-13)
+    assert np.allclose([out[4], out[5], out[6]],
+                       [cov_want[0, 0], cov_want[0, 1], cov_want[1, 1]], rtol=1e-8, atol=1e-12)
+    assert cov_prev[2, 2] + out[7] == pytest.approx(cov_want[2, 2], rel=1e-11)
+    if tail is not None:
+        assert np.allclose(w_got[-tail:], (np.asarray(w) / np.sum(w))[-tail:], rtol=1e-12, atol=0)
+        if abs(np.sum(w) - 1.0) > 1e-3:
+            assert np.all(w_got[-tail:] != np.asarray(w)[-tail:])   # normalised in place
+
+
+def _check_motion_and_init(torch, matcher, n, rng, seed, step, first, z_dev, tail=None):
+    """motion_kernel and init_kernel, with given noise and on the Philox path, against the
+    oracle: theta bit for bit, x / y < 1e-12."""
+    poses = _random_poses(rng, n)
+    z = rng.standard_normal((n, 3)).astype(np.float32)
+    motion, alphas = MOTIONS[4], ALPHAS2
+    for noise, kw in ((z, {}), (z_dev, dict(seed=seed, step=step, first=first))):
+        want, _ = O.motion_sample(*motion, alphas, poses, noise)
+        got = _motion(torch, matcher, poses, motion, alphas, None if kw else noise, **kw)
+        assert np.array_equal(got[:, 2], want[:, 2])
+        assert np.max(np.abs(got[:, :2] - want[:, :2])) < 1e-12
+        if tail is not None:
+            assert np.all(np.any(got[-tail:] != poses[-tail:], axis=1))
+    args = (1.25, -3.5, 3.0, 0.3, 0.2, 0.5)
+    for noise, kw in ((z, {}), (z_dev, dict(seed=seed, step=step, first=first))):
+        want = O.pf_init(*args, noise)
+        got = _init(torch, matcher, n, args, None if kw else noise, **kw)
+        assert np.array_equal(got, want)
+        if tail is not None:
+            assert np.all(got[-tail:] != -1.0e30)
+
+
+def test_noise_beyond_the_grid_cap(torch, matcher):
+    """n = 4096 * 256 + 257: 257 threads go round noise_kernel's loop a second time."""
+    seed, step, first = 20240, 3, 11
+    z = _noise(torch, matcher, seed, step, first, N_BEYOND).cpu().numpy()
+    assert np.all(np.isfinite(z[-300:]))
+    ratio = _noise_ratio(z, seed, step, first)
+    print("noise ratio beyond the cap: %.3f" % ratio)
+    assert ratio <= NOISE_B, ratio
+
+
+def test_motion_and_init_beyond_the_grid_cap(torch, matcher):
+    seed, step, first = 20240, 3, 11
+    z_dev = _noise(torch, matcher, seed, step, first, N_BEYOND).cpu().numpy()
+    _check_motion_and_init(torch, matcher, N_BEYOND, np.random.default_rng(41), seed, step, first,
+                           z_dev, tail=300)
+
+
+def _check_statistics_fsum(poses, w, out, w_got):
+    """updateStatistics from correctly rounded sums (math.fsum of the float64 terms), at the
+    tolerances of _check_statistics."""
+    th = poses[:, 2]
+    S = [math.fsum(t.tolist()) for t in _moment_terms(poses, w)]
+    sw = S[0]
+    mx, my, mth = S[1] / sw, S[2] / sw, math.atan2(S[4] / sw, S[3] / sw)
+    r = np.fmod((mth - th) + math.pi, 2.0 * math.pi)
+    d = np.where(r <= 0.0, r + math.pi, r - math.pi)
+    var = math.fsum(((w / sw) * d * d).tolist())
+    assert np.allclose(w_got, w / sw, rtol=1e-12, atol=0)
+    assert np.allclose(out[1:4], [mx, my, mth], rtol=1e-11, atol=1e-13)
+    assert np.allclose([out[4], out[5], out[6]],
+                       [S[5] / sw - mx * mx, S[6] / sw - mx * my, S[7] / sw - my * my],
+                       rtol=1e-8, atol=1e-12)
+    assert 0.125 + out[7] == pytest.approx(0.125 + var, rel=1e-11, abs=0)
+
+
+@pytest.mark.parametrize("uniform", [False, True])
+def test_statistics_beyond_the_grid_cap(torch, matcher, uniform):
+    """Given weights: against the oracle, and against correctly rounded sums.  Uniform weights:
+    against correctly rounded sums only -- the oracle adds the weights one after the other as the
+    reference does, and 1,048,833 equal addends 1/n drift by 1.2e-11 of their sum in that loop
+    (measured on the CPU against math.fsum; random weights: 2.5e-14), which is the oracle's own
+    error and above the 1e-12 the weights are held to."""
+    rng = np.random.default_rng(43)
+    n = N_BEYOND
+    poses = _wrap_poses(rng, n)
+    w = np.full(n, 1.0 / n) if uniform else rng.uniform(0.1, 2.0, size=n)
+    sums, out, w_got = _statistics(torch, matcher, poses, w, uniform)
+    if not uniform:
+        _check_statistics(poses, w, out, w_got, tail=300)
+    _check_statistics_fsum(poses, w, out, w_got)
+    sw = math.fsum(w.tolist())
+    assert abs(sums[0] - sw) <= (_moment_depth(n) + 3) * 2.0 ** -53 * sw and out[0] == sums[0]
+    assert abs(w_got.sum() - 1.0) < 1e-12
+    assert np.allclose(w_got[-300:], w[-300:] / sw, rtol=1e-12, atol=0)       # the tail was written
+    if not uniform:
+        assert np.all(w_got[-300:] != w[-300:])
+
+
+@pytest.mark.parametrize("n", SMALL_SIZES)
+def test_small_and_ragged_sizes(torch, matcher, n):
+    """One particle, a partial wave, whole waves plus one lane, a block whose later waves hold
+    no particle, a second block of one lane: wave_sum over idle lanes and the sh[] rows of idle
+    waves must add exact zeros."""
+    rng = np.random.default_rng(1000 + n)
+    seed, step, first = 5 + n, 2, 70000
+    z_dev = _noise(torch, matcher, seed, step, first, n).cpu().numpy()
+    assert _noise_ratio(z_dev, seed, step, first) <= NOISE_B
+    _check_motion_and_init(torch, matcher, n, rng, seed, step, first, z_dev, tail=min(n, 300))
+    poses = _wrap_poses(rng, n)
+    for uniform in (False, True):
+        w = np.full(n, 1.0 / n) if uniform else rng.uniform(0.1, 2.0, size=n)
+        _, out, w_got = _statistics(torch, matcher, poses, w, uniform)
+        _check_statistics(poses, w, out, w_got, tail=min(n, 300))
+
+
+@pytest.mark.parametrize("uniform", [False, True])
+def test_one_particle_is_its_own_mean(torch, matcher, uniform):
+    """n = 1 with a weight that is a power of two (0.25; uniform: 1/n = 1), so every product and
+    quotient by it is exact: mean x / y are the pose's bits and the covariance sums
+    (w x x) / w - mean_x mean_x are exactly 0.  The circular mean is atan2(sin t, cos t): that is
+    t to the bit at t = 0 (then the theta variance increment is exactly 0 too); at another
+    heading it is t to the functions' last places -- sincos within 2 ulp moves the angle by at
+    most 2^-51, atan2 within 2 ulp by 2^-51 |t| -- and the increment at most that squared."""
+    w = np.array([1.0 if uniform else 0.25])
+    for pose in ([1.2345678901234567, -7.654321098765432, 0.0],
+                 [-3.3333333333333335, 0.1234567890123456, 2.718281828459045]):
+        poses = np.array([pose])
+        sums, out, w_got = _statistics(torch, matcher, poses, w, uniform)
+        _check_statistics(poses, w, out, w_got)
+        assert w_got[0] == 1.0 and out[0] == w[0] and sums[0] == w[0]
+        assert out[1] == pose[0] and out[2] == pose[1]
+        assert out[4] == 0.0 and out[5] == 0.0 and out[6] == 0.0
+        tol = 2.0 ** -51 * (1.0 + abs(pose[2]))
+        print("n = 1: mean theta - theta = %.3e, variance increment %.3e" % (out[3] - pose[2], out[7]))
+        if pose[2] == 0.0:
+            assert out[3] == 0.0 and out[7] == 0.0
+        else:
+            assert abs(out[3] - pose[2]) <= tol and 0.0 <= out[7] <= tol * tol
+
+
+def _moment_terms(poses, w):
+    """The eight terms of every particle in float64, in the kernel's association."""
+    x, y, th = poses[:, 0], poses[:, 1], poses[:, 2]
+    c, s = np.cos(th), np.sin(th)
+    return [w, w * x, w * y, w * c, w * s, (w * x) * x, (w * x) * y, (w * y) * y]
+
+
+def _moment_depth(n):
+    """The most additions a term passes through on its way into a sum, read off moments_kernel
+    and moments_reduce_kernel: the thread's own trips round its loop, 6 levels of the 64-lane
+    wave sum, 3 adds for the block's four waves, the reducer thread's loop over its blocks and
+    the 8 levels of its 256-wide tree."""
+    blocks = min(-(-n // BLOCK), CAP_BLOCKS)
+    trips = -(-n // (blocks * BLOCK))
+    return trips + 6 + 3 + -(-blocks // 256) + 8
+
+
+@pytest.mark.parametrize("weights", ["plain", "zeros", "span", "uniform"])
+@pytest.mark.parametrize("n", [257, 70001, N_BEYOND])
+def test_moment_sums_against_fsum(torch, matcher, n, weights):
+    """The eight raw sums of pose_moments_launch against math.fsum (the correctly rounded sum) of
+    the same float64 terms.  Bound: every addition rounds by at most 2^-53 of a partial sum, which
+    is at most sum |term|, and a term meets _moment_depth(n) = D of them; its two products and the
+    last ulps of the device's sincos against numpy's are 3 2^-53 |term| more:
+        |sum_dev - fsum| <= (D + 3) 2^-53 sum |term|.
+    Largest |sum_dev - fsum| / bound observed on an MI355X: 0.14 (n = 257, D = 19); 0.05 at
+    n = 1,048,833 (D = 35)."""
+    rng = np.random.default_rng(n + 7)
+    poses = _wrap_poses(rng, n)
+    if weights == "zeros":
+        w = rng.uniform(0.1, 2.0, size=n) * (rng.random(n) < 0.5)
+    elif weights == "span":
+        w = 10.0 ** rng.uniform(-12.0, 0.0, size=n)
+        w[0], w[-1] = 1.0e-12, 1.0
+    elif weights == "uniform":
+        w = np.full(n, 1.0 / n)
+    else:
+        w = rng.uniform(0.1, 2.0, size=n)
+    sums, _, _ = _statistics(torch, matcher, poses, w, weights == "uniform")
+    depth = _moment_depth(n)
+    worst = 0.0
+    for k, term in enumerate(_moment_terms(poses, w)):
+        exact = math.fsum(term.tolist())
+        bound = (depth + 3) * 2.0 ** -53 * math.fsum(np.abs(term).tolist())
+        worst = max(worst, abs(sums[k] - exact) / bound)
+        assert abs(sums[k] - exact) <= bound, (k, sums[k], exact, bound)
+    print("moment sums n=%d %s: D=%d, worst |err| / bound = %.3f" % (n, weights, depth, worst))
+
+
+# ---- designed values at the angle wraps --------------------------------------------------------
+
+def _normalize_angle(a):
+    """angles::normalize_angle on Python floats; math.fmod is exact, as the device's is."""
+    r = math.fmod(a + math.pi, 2.0 * math.pi)
+    return r + math.pi if r <= 0.0 else r - math.pi
+
+
+ZERO_ALPHAS = [0.0, 0.0, 0.0, 0.0, 0.0]
+THREE_PI = 3.0 * math.pi
+# (heading, dth) of a pure rotation: trans = 0, rot1 = 0, rot2 = normalize_angle(dth) held as float.
+# 1.5 is a float, and pi - 1.5, 3 pi - 1.5 are exact double differences, so the sums land where named.
+WRAP_CASES = [
+    (math.pi - 1.5, 1.5), (-(math.pi - 1.5), -1.5),         # exactly +pi, exactly -pi
+    (math.pi, 0.0), (-math.pi, 0.0),
+    (-1.5, 1.5), (1.5, -1.5), (0.0, 0.0),                   # exactly 0
+    (THREE_PI - 1.5, 1.5), (-(THREE_PI - 1.5), -1.5),       # 3 pi, -3 pi
+    (THREE_PI, 0.0), (-THREE_PI, 0.0),
+    (1.0e6 + 0.25, 1.5), (-1.0e6 - 0.25, -1.5), (1.0e6 + 0.25, -1.5),
+    (3.0, 0.25), (-3.0, -0.25),                             # across the wrap, off the lattice
+]
+
+
+@pytest.mark.parametrize("given_noise", [True, False])
+def test_motion_lands_on_the_designed_wraps(torch, matcher, given_noise):
+    """All alphas zero: every sigma is 0 and the draw is its mean whatever the noise.  The new
+    heading is normalize_angle((theta + float(rot1)) + float(rot2)) in exact double arithmetic
+    (two adds and an exact fmod), so Python's math.fmod on the same doubles has the same bits."""
+    rng = np.random.default_rng(5)
+    for dth in sorted({d for _, d in WRAP_CASES}):
+        heads = [t for t, d in WRAP_CASES if d == dth]
+        poses = np.array([[0.5 * i - 1.0, 2.0 - 0.25 * i, t] for i, t in enumerate(heads)])
+        z = rng.standard_normal((len(poses), 3)).astype(np.float32) if given_noise else None
+        got = _motion(torch, matcher, poses, (0.0, 0.0, dth), ZERO_ALPHAS, z, 12, 34, 56)
+        rot2 = float(np.float32(_normalize_angle(dth - 0.0)))
+        want = [_normalize_angle((t + 0.0) + rot2) for t in heads]
+        assert got[:, 2].tolist() == want, (dth, got[:, 2].tolist(), want)
+        assert np.array_equal(got[:, :2], poses[:, :2])          # t = 0: x + 0 * cos
+        oracle, _ = O.motion_sample(0.0, 0.0, dth, ZERO_ALPHAS, poses,
+                                    np.zeros((len(poses), 3), dtype=np.float32))
+        assert np.array_equal(got, oracle)
+        for t, th in zip(heads, got[:, 2]):
+            if abs(t + rot2) == math.pi:
+                assert th == math.pi                             # -pi comes out +pi: the <= 0 branch
+            if t + rot2 == 0.0:
+                assert th == 0.0
+    # the designed sums are what their names say
+    assert (math.pi - 1.5) + 1.5 == math.pi and (THREE_PI - 1.5) + 1.5 == THREE_PI
+    assert _normalize_angle(THREE_PI) == math.pi and _normalize_angle(-THREE_PI) == math.pi
+
+
+@pytest.mark.parametrize("given_noise", [True, False])
+def test_init_at_plus_and_minus_pi(torch, matcher, given_noise):
+    """theta = +-pi is held as float (3.14159274 > pi), sigma 0: float pi wraps to just above
+    -pi, float -pi to just below +pi."""
+    n = 65
+    z = np.random.default_rng(6).standard_normal((n, 3)).astype(np.float32) if given_noise else None
+    for theta in (math.pi, -math.pi, 3.0 * math.pi, 0.0):
+        got = _init(torch, matcher, n, (0.5, -0.25, theta, 0.0, 0.0, 0.0), z, 12, 34, 56)
+        want = _normalize_angle(float(np.float32(theta)))
+        assert np.all(got[:, 0] == 0.5) and np.all(got[:, 1] == -0.25)
+        assert got[:, 2].tolist() == [want] * n
+        assert np.array_equal(got, O.pf_init(0.5, -0.25, theta, 0.0, 0.0, 0.0,
+                                             np.zeros((n, 3), dtype=np.float32)))
+    assert _normalize_angle(float(np.float32(math.pi))) < -3.14159
+    assert _normalize_angle(float(np.float32(-math.pi))) > 3.14159
+
+
+def test_circular_mean_at_pi(torch, matcher):
+    """Two particles at headings +3.0 and -3.0.  Equal weights: the sines cancel to +0, the cosine
+    sum is negative, atan2(+0, < 0) is pi exactly; each angular distance is pi - 3 through exact
+    adds and an exact fmod, so the theta variance increment is (pi - 3)^2.  Weights 3 : 1: the oracle."""
+    poses = np.array([[1.0, 2.0, 3.0], [-1.0, 0.5, -3.0]])
+    for uniform, w in ((False, [1.0, 1.0]), (True, [0.5, 0.5]), (False, [0.7, 0.7])):
+        w = np.array(w)
+        sums, out, w_got = _statistics(torch, matcher, poses, w, uniform)
+        assert sums[4] == 0.0 and sums[3] < 0.0
+        assert out[3] == math.pi
+        assert out[7] == pytest.approx((math.pi - 3.0) ** 2, rel=1e-15, abs=0)
+        assert w_got.tolist() == [0.5, 0.5]
+        _check_statistics(poses, w, out, w_got)
+    w = np.array([3.0, 1.0])
+    _, out, w_got = _statistics(torch, matcher, poses, w, False)
+    _check_statistics(poses, w, out, w_got)
+    _, mean_want, _ = O.pf_update_statistics(poses, w)
+    assert 3.0 < mean_want[2] < math.pi and out[3] == pytest.approx(mean_want[2], rel=1e-14, abs=0)
+    w = np.array([1.0, 3.0])
+    _, out, w_got = _statistics(torch, matcher, poses, w, False)
+    _check_statistics(poses, w, out, w_got)
+    assert -math.pi < out[3] < -3.0

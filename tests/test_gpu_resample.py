@@ -17,6 +17,7 @@ import pytest
 
 from ndt_2d_amd import ScanMatcherNDT, _capi, synth
 from ndt_2d_amd.particle_filter import KD_LEAF, MotionModel, ParticleFilter, kld_resample_native
+from noise_restatement import philox4x32_10
 
 pytestmark = pytest.mark.gpu
 
@@ -380,22 +381,6 @@ def test_repeats_are_identical_and_the_table_is_cleared(torch, ctx):
 
 
 # ---- the Philox stream ---------------------------------------------------------------------
-
-def philox4x32_10(counter, key):
-    """Philox4x32-10 (Salmon et al., SC'11) on uint64-held 32-bit words: counter [..., 4],
-    key [..., 2] -> [..., 4]."""
-    m32 = np.uint64(0xffffffff)
-    c = [np.asarray(counter[..., k], dtype=np.uint64) for k in range(4)]
-    k0 = np.asarray(key[..., 0], dtype=np.uint64)
-    k1 = np.asarray(key[..., 1], dtype=np.uint64)
-    for _ in range(10):
-        p0 = np.uint64(0xD2511F53) * c[0]
-        p1 = np.uint64(0xCD9E8D57) * c[2]
-        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k0, p1 & m32, (p0 >> np.uint64(32)) ^ c[3] ^ k1, p0 & m32]
-        k0 = (k0 + np.uint64(0x9E3779B9)) & m32
-        k1 = (k1 + np.uint64(0xBB67AE85)) & m32
-    return np.stack(c, axis=-1)
-
 
 def philox_uniforms(seed, step, first, n):
     i = np.uint64(first) + np.arange(n, dtype=np.uint64)
