@@ -505,6 +505,111 @@ int ndt2d_closure_refine(ndt2d_closure * closure, size_t n_candidates, const siz
 int ndt2d_closure_set_neighbourhood(ndt2d_closure * closure, uint32_t cells);
 int ndt2d_closure_neighbourhood(ndt2d_closure * closure, uint32_t * out);
 
+/* ---- Match verification: inlier, unseen and pierced beams of K (scan, pose) jobs in one launch
+ *      (csrc/verify/) ----
+ *
+ * Every search and the registration above turn a scan and a guess into a pose and one number, the
+ * mean NDT score.  This says which beams of the scan the map explains at that pose: one verdict per
+ * beam, integer counts per job.  A job is a (scan, pose) pair in ndt2d_refine_run's conventions.
+ * One call is one upload, ONE kernel launch per chunk (a workgroup per job) and one read-back.  An
+ * object of its own beside the context, as ndt2d_refine: it reads the grid installed at the time
+ * of the call, installs nothing, launches on the context's current stream, and must be destroyed
+ * before ndt2d_destroy(h).  A job's result depends on its scan, its pose, the grid and the
+ * parameters alone: not on the other jobs or the chunking.  No policy: nothing is accepted or
+ * rejected here.
+ *
+ * Job and beam.  For the job's pose (x, y, theta), c = cos theta and s = sin theta come from the
+ * host libm inside the call.  A beam b (robot frame, taken as given) becomes
+ *     q = (c bx - s by + x,  s bx + c by + y)
+ * as the registration forms it.  The beam's own cell is NDT::getIndex's of q.
+ *
+ * Class of a beam (the two low bits of its byte):
+ *     0  NDT2D_BEAM_OFF      q is off the grid (NaN and infinite points included)
+ *     1  NDT2D_BEAM_UNSEEN   q is on the grid, and no cell of the neighbourhood can score (n >= 5)
+ *     3  NDT2D_BEAM_INLIER   m2 <= gate_inlier
+ *     2  NDT2D_BEAM_OUTLIER  otherwise: !(m2 <= gate_inlier); a NaN m2 (a degenerate cell) is an outlier
+ * The neighbourhood is 1 cell (the beam's own) or 9 (the 3 x 3 round it), by the rule of
+ * ndt2d_refine_set_neighbourhood: neighbour j = 0 .. 8 is (dy, dx) = (j / 3 - 1, j % 3 - 1) from the
+ * own cell (gx, gy), and counts only if 0 <= gx + dx < size_x, 0 <= gy + dy < size_y -- clipped on
+ * (gx, gy), never on the flat index -- and its cell can score.  For a counting cell with mean m and
+ * information I, d = q - m and
+ *     m2 = d^T I d = -2 x (Cell::score's exponent on the record's h = -1/2 I;  I = -2 h exactly)
+ * A beam's m2 is the minimum over its counting neighbours in ascending j: a neighbour replaces the
+ * one held when its m2 is below the held one, or is NaN while the held one is not (a NaN stays:
+ * numpy's argmin).  Ties go to the lowest j.
+ *
+ * The ray.  It is walked only when rays are enabled, the beam is not OFF and the job's origin cell
+ * -- NDT::getIndex of (x, y) -- is on the grid.  Its cells are those of the integer line from the
+ * origin cell (ox, oy) to the beam's own cell (gx, gy) in the all-octant error form the occupancy
+ * grid uses (src/occupancy_grid.cpp:93-131):
+ *     dx = |gx - ox|, dy = -|gy - oy|, sx, sy = the signs, err = dx + dy; the cell (ox, oy) is visited;
+ *     at a visited cell: it is the end cell: stop.
+ *         2 err >= dy: x is the end's: stop;  else err += dy, x += sx
+ *         2 err <= dx (the err just updated): y is the end's: stop;  else err += dx, y += sy
+ *     the cell now reached is visited.  At most dx - dy + 1 cells are visited.  (As there, a walk
+ *     can stop one step short of the end cell; that is inside the end's own 3 x 3, see below.)
+ * A visited cell is TESTED when it is not the origin cell, its Chebyshev distance to the end cell
+ * is > 1 (the end's own 3 x 3 belongs to the end point, not to the ray) and it can score.  For a
+ * tested cell with mean m and information I, o = (x, y), in this operation order:
+ *     u = q - o;  w = m - o
+ *     Iu = (I00 ux + I01 uy,  I01 ux + I11 uy)
+ *     D = ux Iu_0 + uy Iu_1                       (u^T I u)
+ *     N = wx Iu_0 + wy Iu_1                       (u^T I w)
+ *     t = N / D;  t = 0 when !(D > 0);  then !(t >= 0) -> 0 (a NaN too), t > 1 -> 1
+ *     r = w - t u;  Ir as Iu;  r^T I r = rx Ir_0 + ry Ir_1
+ *     the cell PIERCES when r^T I r <= gate_pierce
+ * -- the segment from the robot to the beam's end passes through the cell's Gaussian.  The walk
+ * stops at the first piercing cell: bit 2 (NDT2D_BEAM_PIERCED = 4) of the beam's byte is set and
+ * the cell's flat index recorded.  (A grid side above 2^24 cells with rays enabled is refused.)
+ *
+ *   create   max_jobs (1 .. 4,096): jobs of one chunk; more are processed in chunks inside the
+ *            call (a chunk also ends where its jobs' beams pass 2^24).  Chunking changes no output.
+ *   run      jobs_xyt, job_scan, beams_xy, beam_offsets, n_scans: ndt2d_refine_run's conventions
+ *            (shared scans travel once, a scan no job names is legal and is not uploaded,
+ *            job_scan == NULL: job k uses scan k and n_scans must equal n_jobs).
+ *            records_out[K][NDT2D_VERIFY_RECORD_U32], by job in the caller's order:
+ *            {n_beams, n_off, n_unseen, n_outlier, n_inlier, n_pierced, n_walked, 0}; n_walked:
+ *            the beams whose ray was walked.  Integers: no summation order matters.
+ *            Optional, each may be NULL, per beam, job after job in the caller's order -- job k's
+ *            beams start at the sum of the earlier jobs' scan lengths:
+ *              beam_class_out   uint8: class | NDT2D_BEAM_PIERCED
+ *              beam_m2_out      double: the beam's m2; OFF and UNSEEN give +inf
+ *              beam_cells_out   uint32[.][2]: the cell whose m2 won | the first piercing cell;
+ *                               NDT2D_VERIFY_NO_CELL: none
+ *            Refused with NDT2D_ERR_INVALID before anything is launched: everything
+ *            ndt2d_refine_run refuses about jobs and scans, with "job k" or "scan s" in the
+ *            message.  No grid: NDT2D_ERR_NO_GRID.  n_jobs == 0: NDT2D_OK, nothing done.
+ *   set_neighbourhood / neighbourhood   1 (the default at this layer) or 9
+ *   set_gates / gates   gate_inlier (default 9.0) and gate_pierce (default 1.0): each >= 0 and finite
+ *   set_rays / rays     the ray walk on (the default) or off: enabled is 0 or 1
+ *            Anything else: NDT2D_ERR_INVALID with a message, and the old values stay.  The
+ *            defaults are starting values, not tuned.
+ *   set_timing / last_ms   HIP events around the kernel launch and the read-back of the last
+ *            (chunk of a) run, off by default. */
+#define NDT2D_VERIFY_RECORD_U32 8
+#define NDT2D_BEAM_OFF 0
+#define NDT2D_BEAM_UNSEEN 1
+#define NDT2D_BEAM_OUTLIER 2
+#define NDT2D_BEAM_INLIER 3
+#define NDT2D_BEAM_PIERCED 4        /* bit 2 of a beam's byte: its ray met a piercing cell */
+#define NDT2D_VERIFY_NO_CELL 0xFFFFFFFFu
+typedef struct ndt2d_verify ndt2d_verify;
+int ndt2d_verify_create(ndt2d_handle h, size_t max_jobs, ndt2d_verify ** out);
+int ndt2d_verify_destroy(ndt2d_verify * verify);
+const char * ndt2d_verify_last_error(ndt2d_verify * verify);
+int ndt2d_verify_run(ndt2d_verify * verify, const double * jobs_xyt, const uint32_t * job_scan,
+                     size_t n_jobs, const double * beams_xy, const size_t * beam_offsets,
+                     size_t n_scans, uint32_t * records_out, uint8_t * beam_class_out,
+                     double * beam_m2_out, uint32_t * beam_cells_out);
+int ndt2d_verify_set_neighbourhood(ndt2d_verify * verify, uint32_t cells);
+int ndt2d_verify_neighbourhood(ndt2d_verify * verify, uint32_t * out);
+int ndt2d_verify_set_gates(ndt2d_verify * verify, double gate_inlier, double gate_pierce);
+int ndt2d_verify_gates(ndt2d_verify * verify, double * gate_inlier_out, double * gate_pierce_out);
+int ndt2d_verify_set_rays(ndt2d_verify * verify, int enabled);
+int ndt2d_verify_rays(ndt2d_verify * verify, int * out);
+int ndt2d_verify_set_timing(ndt2d_verify * verify, int enabled);
+int ndt2d_verify_last_ms(ndt2d_verify * verify, float * kernel_ms, float * fetch_ms);
+
 /* Upload the beam endpoints of one scan, robot frame, already subsampled to
  * min(laser_max_beams, points.size()) points by the caller
  * (src/scan_matcher_ndt.cpp:95-96,110 / :165-166,171).  Beams are taken as given: finite,
@@ -1228,6 +1333,39 @@ ndt2d_refine * ndt2d_matcher_refine(ndt2d_matcher * m);
  * beams in use, min(laser_max_beams, the scan's points)). */
 int ndt2d_matcher_set_refine_neighbourhood(ndt2d_matcher * m, uint32_t cells);
 int ndt2d_matcher_refine_neighbourhood(ndt2d_matcher * m, uint32_t * out);
+/* Match verification of K jobs -- (scan, pose) pairs -- against the NDT in place, in one call
+ * (ndt2d_verify_run on the first device, as refine_scans): which beams of each scan the map
+ * explains at the job's pose ("Match verification" above).  Scans, jobs and job_scan as in
+ * refine_scans.  max_beams: 0 takes every point of a scan (filtering a scan before it is stored);
+ * otherwise min(max_beams, the scan's points) points by the subsampling rule of matchScan /
+ * scorePoints (:165-166,171) -- with the matcher's laser_max_beams the verdict is about the beams
+ * the score was computed from.  Per job k:
+ *     records_out[8 k ..]       {n_beams, n_off, n_unseen, n_outlier, n_inlier, n_pierced, n_walked, 0}
+ *     beam_offsets_out[k]       where job k's beams start in the per-beam arrays; [K]: their total   (optional, K + 1)
+ *     beam_class_out, beam_m2_out, beam_cells_out   ndt2d_verify_run's per-beam arrays          (optional)
+ * beam_cap: the beams the per-beam arrays hold; fewer than the jobs' beams: NDT2D_ERR_INVALID, the
+ * message says how many are needed (sum over jobs of the beams in use of their scans).  Jobs of a
+ * scan without points get a record of zeros.  No NDT in place: NDT2D_ERR_NO_GRID.  A search launched
+ * ahead by score_scan is waited out and dropped first.  The NDT stays in place; the beams and the
+ * prepared search of the context are not touched.  NDT2D_ERR_INVALID, nothing launched: what
+ * refine_scans refuses about jobs and scans. */
+int ndt2d_matcher_verify_scans(ndt2d_matcher * m, const double * jobs_xyt, const uint32_t * job_scan,
+                               size_t n_jobs, const double * points_xy, const size_t * point_offsets,
+                               size_t n_scans, size_t max_beams, uint32_t * records_out,
+                               size_t * beam_offsets_out, uint8_t * beam_class_out,
+                               double * beam_m2_out, uint32_t * beam_cells_out, size_t beam_cap);
+/* The call's object (made by the first verify_scans with an NDT in place; NULL before), for
+ * ndt2d_verify_set_timing / _last_ms. */
+ndt2d_verify * ndt2d_matcher_verify(ndt2d_matcher * m);
+/* The parameters of the later verify_scans calls, kept in the matcher and applied to every call:
+ * the neighbourhood (1 or 9; the default at this layer is 9), the gates (each >= 0 and finite;
+ * 9.0 and 1.0) and the ray walk (0 or 1; on).  Anything else: NDT2D_ERR_INVALID, the values stay. */
+int ndt2d_matcher_set_verify_neighbourhood(ndt2d_matcher * m, uint32_t cells);
+int ndt2d_matcher_verify_neighbourhood(ndt2d_matcher * m, uint32_t * out);
+int ndt2d_matcher_set_verify_gates(ndt2d_matcher * m, double gate_inlier, double gate_pierce);
+int ndt2d_matcher_verify_gates(ndt2d_matcher * m, double * gate_inlier_out, double * gate_pierce_out);
+int ndt2d_matcher_set_verify_rays(ndt2d_matcher * m, int enabled);
+int ndt2d_matcher_verify_rays(ndt2d_matcher * m, int * out);
 /* Newton NDT registration of K jobs, each on a loop-closure candidate's OWN map, in one call
  * (ndt2d_closure_refine on the first device, with the matcher's resolution, range_max and stored
  * scans): what reset() + add_scans_by_id(candidate) + refine_scans(job) gives per job, bit for bit,

@@ -23,6 +23,11 @@ NO_INDEX = (1 << 64) - 1
 # NDT2D_REFINE_*: how a Newton registration job stopped
 REFINE_CONVERGED, REFINE_MAX_EVALS, REFINE_STALLED, REFINE_NO_OVERLAP, REFINE_NOT_FINITE = range(5)
 REFINE_STATUS_NAMES = ("converged", "max_evals", "stalled", "no_overlap", "not_finite")
+# NDT2D_BEAM_*: the class of a beam (the two low bits of its byte) and the pierced bit; the record of a job
+BEAM_OFF, BEAM_UNSEEN, BEAM_OUTLIER, BEAM_INLIER = range(4)
+BEAM_PIERCED = 4
+VERIFY_RECORD_U32 = 8
+VERIFY_NO_CELL = 0xFFFFFFFF
 MATCH_RECORD_DOUBLES = 12
 POSE_STATS_DOUBLES = 8
 PF_RESULT_DOUBLES = 8
@@ -142,6 +147,19 @@ SIGNATURES = {
     "ndt2d_refine_set_neighbourhood": (C.c_int, [_vp, _u32]),
     "ndt2d_refine_neighbourhood": (C.c_int, [_vp, C.POINTER(_u32)]),
     "ndt2d_refine_covariance": (C.c_int, [_dp, _dp]),
+    "ndt2d_verify_create": (C.c_int, [_vp, _sz, C.POINTER(_vp)]),
+    "ndt2d_verify_destroy": (C.c_int, [_vp]),
+    "ndt2d_verify_last_error": (C.c_char_p, [_vp]),
+    "ndt2d_verify_run": (C.c_int, [_vp, _dp, C.POINTER(_u32), _sz, _dp, _szp, _sz, C.POINTER(_u32), C.POINTER(C.c_uint8), _dp,
+                                   C.POINTER(_u32)]),
+    "ndt2d_verify_set_neighbourhood": (C.c_int, [_vp, _u32]),
+    "ndt2d_verify_neighbourhood": (C.c_int, [_vp, C.POINTER(_u32)]),
+    "ndt2d_verify_set_gates": (C.c_int, [_vp, _d, _d]),
+    "ndt2d_verify_gates": (C.c_int, [_vp, _dp, _dp]),
+    "ndt2d_verify_set_rays": (C.c_int, [_vp, C.c_int]),
+    "ndt2d_verify_rays": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "ndt2d_verify_set_timing": (C.c_int, [_vp, C.c_int]),
+    "ndt2d_verify_last_ms": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "ndt2d_set_eigenvalue_form": (C.c_int, [_vp, C.c_char_p]),
     "ndt2d_get_grid": (C.c_int, [_vp, _dp, _sz, C.POINTER(_u32), C.POINTER(_u32), _dp, _dp, _dp]),
     "ndt2d_clear_grid": (C.c_int, [_vp]),
@@ -263,6 +281,15 @@ SIGNATURES = {
     "ndt2d_matcher_refine": (_vp, [_vp]),
     "ndt2d_matcher_set_refine_neighbourhood": (C.c_int, [_vp, _u32]),
     "ndt2d_matcher_refine_neighbourhood": (C.c_int, [_vp, C.POINTER(_u32)]),
+    "ndt2d_matcher_verify_scans": (C.c_int, [_vp, _dp, C.POINTER(_u32), _sz, _dp, _szp, _sz, _sz, C.POINTER(_u32), _szp,
+                                             C.POINTER(C.c_uint8), _dp, C.POINTER(_u32), _sz]),
+    "ndt2d_matcher_verify": (_vp, [_vp]),
+    "ndt2d_matcher_set_verify_neighbourhood": (C.c_int, [_vp, _u32]),
+    "ndt2d_matcher_verify_neighbourhood": (C.c_int, [_vp, C.POINTER(_u32)]),
+    "ndt2d_matcher_set_verify_gates": (C.c_int, [_vp, _d, _d]),
+    "ndt2d_matcher_verify_gates": (C.c_int, [_vp, _dp, _dp]),
+    "ndt2d_matcher_set_verify_rays": (C.c_int, [_vp, C.c_int]),
+    "ndt2d_matcher_verify_rays": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "ndt2d_matcher_match_laser_scan": (C.c_int, [_vp, _dp, C.POINTER(C.c_float), _sz,
                                                  C.POINTER(LaserScan), _dp, _dp, _dp, _szp]),
     "ndt2d_matcher_prepare_search": (C.c_int, [_vp, _dp, _dp, _sz, _szp, _szp, _szp]),

@@ -3,7 +3,8 @@
 // each validates its input, makes one call of its object under csrc/closure, starts or scans for
 // the records of all slots, and hands them to finish_slots(), the tail they share -- and the Newton
 // registration of K (scan, pose) jobs (refine_scans), one call of the object under csrc/refine, and
-// the same on each loop-closure candidate's own map (refine_candidates), one call of the closure object.
+// the same on each loop-closure candidate's own map (refine_candidates), one call of the closure object,
+// and the match verification of K (scan, pose) jobs (verify_scans), one call of the object under csrc/verify.
 #include <cstring>
 #include <functional>
 #include <string>
@@ -162,9 +163,9 @@ void fill_no_overlap(const double * jobs_xyt, size_t n_jobs, const RefineOut & o
   }
 }
 
-// The jobs of a registration's device call: every scan a job names as scorePoints takes it --
-// subsampled beams (:165-166,171), once per scan; a scan without points is not among them, and
-// neither are its jobs.
+// The jobs of a registration's (or a verification's) device call: every scan a job names as
+// scorePoints takes it -- subsampled beams (:165-166,171) to max_beams, 0: every point --, once per
+// scan; a scan without points is not among them, and neither are its jobs.
 struct RefineBatch
 {
   std::vector<double> beams, xyt;
@@ -172,7 +173,7 @@ struct RefineBatch
   std::vector<uint32_t> job, scan;   // the jobs of the device call and their scans
 };
 
-void collect_refine_batch(const ndt2d_matcher * m, const double * jobs_xyt, const uint32_t * job_scan, size_t n_jobs,
+void collect_refine_batch(size_t max_beams, const double * jobs_xyt, const uint32_t * job_scan, size_t n_jobs,
                           const double * points_xy, const size_t * point_offsets, size_t n_scans, RefineBatch & b)
 {
   // sent[s]: its index among the scans the device call receives
@@ -185,7 +186,8 @@ void collect_refine_batch(const ndt2d_matcher * m, const double * jobs_xyt, cons
     const size_t sc = job_scan != nullptr ? static_cast<size_t>(job_scan[k]) : k;
     if (sent[sc] == kUnseen)
     {
-      subsample_into(one, points_xy + 2 * point_offsets[sc], point_offsets[sc + 1] - point_offsets[sc], m->laser_max_beams);
+      const size_t n_points = point_offsets[sc + 1] - point_offsets[sc];
+      subsample_into(one, points_xy + 2 * point_offsets[sc], n_points, max_beams != 0 ? max_beams : n_points);
       if (one.empty())
       {
         sent[sc] = kEmpty;
@@ -557,7 +559,7 @@ int ndt2d_matcher_refine_scans(ndt2d_matcher * m, const double * jobs_xyt, const
     return mfail(m, NDT2D_ERR_INTERNAL, std::string("refine_scans: ") + ndt2d_refine_last_error(m->refine));
   }
   RefineBatch batch;
-  collect_refine_batch(m, jobs_xyt, job_scan, n_jobs, points_xy, point_offsets, n_scans, batch);
+  collect_refine_batch(m->laser_max_beams, jobs_xyt, job_scan, n_jobs, points_xy, point_offsets, n_scans, batch);
   const size_t n_batch = batch.job.size();
   if (n_batch == 0) return NDT2D_OK;
   m->refine_records.assign(n_batch * NDT2D_REFINE_RECORD_DOUBLES, 0.0);
@@ -589,6 +591,151 @@ int ndt2d_matcher_refine_neighbourhood(ndt2d_matcher * m, uint32_t * out)
   NDT2D_C_TRY
   if (m == nullptr || out == nullptr) return NDT2D_ERR_INVALID;
   *out = m->refine_cells;
+  return NDT2D_OK;
+  NDT2D_C_CATCH(m)
+}
+
+// Jobs the match verification launches at a time: the object's limit, as refine_scans.
+static constexpr size_t kVerifySlots = 4096;
+
+int ndt2d_matcher_verify_scans(ndt2d_matcher * m, const double * jobs_xyt, const uint32_t * job_scan, size_t n_jobs,
+                               const double * points_xy, const size_t * point_offsets, size_t n_scans, size_t max_beams,
+                               uint32_t * records_out, size_t * beam_offsets_out, uint8_t * beam_class_out,
+                               double * beam_m2_out, uint32_t * beam_cells_out, size_t beam_cap)
+{
+  NDT2D_C_TRY
+  if (m == nullptr) return NDT2D_ERR_INVALID;
+  if (n_jobs == 0)
+  {
+    if (beam_offsets_out != nullptr) beam_offsets_out[0] = 0;
+    return NDT2D_OK;
+  }
+  if (jobs_xyt == nullptr || records_out == nullptr || point_offsets == nullptr)
+  {
+    return mfail(m, NDT2D_ERR_INVALID, "verify_scans: null input");
+  }
+  // (the registration's rules are not this call's: given as ones it takes)
+  int rc = check_refine_input(m, "verify_scans", jobs_xyt, job_scan, n_jobs, points_xy, point_offsets, n_scans, 1u, 0.0, 0.0);
+  if (rc != NDT2D_OK) return rc;
+  if (!m->ndt.have()) return mfail(m, NDT2D_ERR_NO_GRID, "verify_scans: no NDT in place");
+  RefineBatch batch;
+  collect_refine_batch(max_beams, jobs_xyt, job_scan, n_jobs, points_xy, point_offsets, n_scans, batch);
+  const size_t n_batch = batch.job.size();
+  // where each job's beams start in the per-beam arrays: the batch's jobs in order, the jobs of
+  // scans without points between them with no beams
+  size_t n_beams_all = 0;
+  for (size_t j = 0; j < n_batch; ++j) n_beams_all += batch.beam_offsets[batch.scan[j] + 1] - batch.beam_offsets[batch.scan[j]];
+  const bool want_beams = beam_class_out != nullptr || beam_m2_out != nullptr || beam_cells_out != nullptr;
+  if (want_beams && beam_cap < n_beams_all)
+  {
+    return mfail(m, NDT2D_ERR_INVALID, "verify_scans: the per-beam arrays hold " + std::to_string(beam_cap) + " beams, the jobs have " +
+                                           std::to_string(n_beams_all));
+  }
+  std::memset(records_out, 0, n_jobs * NDT2D_VERIFY_RECORD_U32 * sizeof(uint32_t));
+  if (beam_offsets_out != nullptr)
+  {
+    size_t at = 0, j = 0;
+    for (size_t k = 0; k < n_jobs; ++k)
+    {
+      beam_offsets_out[k] = at;
+      if (j < n_batch && batch.job[j] == k)
+      {
+        at += batch.beam_offsets[batch.scan[j] + 1] - batch.beam_offsets[batch.scan[j]];
+        ++j;
+      }
+    }
+    beam_offsets_out[n_jobs] = at;
+  }
+  if (n_batch == 0) return NDT2D_OK;
+  discard_ahead(m);   // a search launched ahead by scoreScan is waited out and dropped
+  if (m->verify == nullptr)
+  {
+    rc = ndt2d_verify_create(m->dev, kVerifySlots, &m->verify);
+    if (rc != NDT2D_OK) return dev_fail(m, rc, "ndt2d_verify_create");
+  }
+  if (ndt2d_verify_set_neighbourhood(m->verify, m->verify_cells) != NDT2D_OK ||
+      ndt2d_verify_set_gates(m->verify, m->verify_gate_inlier, m->verify_gate_pierce) != NDT2D_OK ||
+      ndt2d_verify_set_rays(m->verify, m->verify_rays ? 1 : 0) != NDT2D_OK)
+  {
+    return mfail(m, NDT2D_ERR_INTERNAL, std::string("verify_scans: ") + ndt2d_verify_last_error(m->verify));
+  }
+  // (the per-beam arrays are the batch's, job after job: a job without beams takes no room in them)
+  std::vector<uint32_t> records(n_batch * NDT2D_VERIFY_RECORD_U32);
+  rc = ndt2d_verify_run(m->verify, batch.xyt.data(), batch.scan.data(), n_batch, batch.beams.data(), batch.beam_offsets.data(),
+                        batch.beam_offsets.size() - 1, records.data(), beam_class_out, beam_m2_out, beam_cells_out);
+  if (rc != NDT2D_OK) return mfail(m, rc, std::string("verify_scans: ") + ndt2d_verify_last_error(m->verify));
+  for (size_t j = 0; j < n_batch; ++j)
+  {
+    std::memcpy(records_out + static_cast<size_t>(batch.job[j]) * NDT2D_VERIFY_RECORD_U32, records.data() + j * NDT2D_VERIFY_RECORD_U32,
+                NDT2D_VERIFY_RECORD_U32 * sizeof(uint32_t));
+  }
+  return NDT2D_OK;
+  NDT2D_C_CATCH(m)
+}
+
+ndt2d_verify * ndt2d_matcher_verify(ndt2d_matcher * m) { return m != nullptr ? m->verify : nullptr; }
+
+int ndt2d_matcher_set_verify_neighbourhood(ndt2d_matcher * m, uint32_t cells)
+{
+  NDT2D_C_TRY
+  if (m == nullptr) return NDT2D_ERR_INVALID;
+  if (cells != 1 && cells != 9)
+  {
+    return mfail(m, NDT2D_ERR_INVALID, "set_verify_neighbourhood: " + std::to_string(cells) + " cells (1 or 9)");
+  }
+  m->verify_cells = cells;
+  return NDT2D_OK;
+  NDT2D_C_CATCH(m)
+}
+
+int ndt2d_matcher_verify_neighbourhood(ndt2d_matcher * m, uint32_t * out)
+{
+  NDT2D_C_TRY
+  if (m == nullptr || out == nullptr) return NDT2D_ERR_INVALID;
+  *out = m->verify_cells;
+  return NDT2D_OK;
+  NDT2D_C_CATCH(m)
+}
+
+int ndt2d_matcher_set_verify_gates(ndt2d_matcher * m, double gate_inlier, double gate_pierce)
+{
+  NDT2D_C_TRY
+  if (m == nullptr) return NDT2D_ERR_INVALID;
+  if (!(gate_inlier >= 0.0) || !(gate_pierce >= 0.0) || !std::isfinite(gate_inlier) || !std::isfinite(gate_pierce))
+  {
+    return mfail(m, NDT2D_ERR_INVALID, "set_verify_gates: a gate is negative or not finite");
+  }
+  m->verify_gate_inlier = gate_inlier;
+  m->verify_gate_pierce = gate_pierce;
+  return NDT2D_OK;
+  NDT2D_C_CATCH(m)
+}
+
+int ndt2d_matcher_verify_gates(ndt2d_matcher * m, double * gate_inlier_out, double * gate_pierce_out)
+{
+  NDT2D_C_TRY
+  if (m == nullptr || gate_inlier_out == nullptr || gate_pierce_out == nullptr) return NDT2D_ERR_INVALID;
+  *gate_inlier_out = m->verify_gate_inlier;
+  *gate_pierce_out = m->verify_gate_pierce;
+  return NDT2D_OK;
+  NDT2D_C_CATCH(m)
+}
+
+int ndt2d_matcher_set_verify_rays(ndt2d_matcher * m, int enabled)
+{
+  NDT2D_C_TRY
+  if (m == nullptr) return NDT2D_ERR_INVALID;
+  if (enabled != 0 && enabled != 1) return mfail(m, NDT2D_ERR_INVALID, "set_verify_rays: " + std::to_string(enabled) + " (0 or 1)");
+  m->verify_rays = enabled != 0;
+  return NDT2D_OK;
+  NDT2D_C_CATCH(m)
+}
+
+int ndt2d_matcher_verify_rays(ndt2d_matcher * m, int * out)
+{
+  NDT2D_C_TRY
+  if (m == nullptr || out == nullptr) return NDT2D_ERR_INVALID;
+  *out = m->verify_rays ? 1 : 0;
   return NDT2D_OK;
   NDT2D_C_CATCH(m)
 }
@@ -641,7 +788,7 @@ int ndt2d_matcher_refine_candidates(ndt2d_matcher * m, const size_t * cand_offse
     return mfail(m, NDT2D_ERR_INTERNAL, std::string("refine_candidates: ") + ndt2d_closure_last_error(m->closure));
   }
   RefineBatch batch;
-  collect_refine_batch(m, jobs_xyt, job_scan, n_jobs, points_xy, point_offsets, n_scans, batch);
+  collect_refine_batch(m->laser_max_beams, jobs_xyt, job_scan, n_jobs, points_xy, point_offsets, n_scans, batch);
   const size_t n_batch = batch.job.size();
   std::vector<uint32_t> batch_candidate(n_batch);
   for (size_t j = 0; j < n_batch; ++j) batch_candidate[j] = job_candidate != nullptr ? job_candidate[batch.job[j]] : batch.job[j];

@@ -90,6 +90,10 @@ struct ndt2d_matcher
   ndt2d_refine * refine = nullptr;         // Newton registration on the first device (made by the first refine_scans)
   std::vector<double> refine_records;      // its records, [K][NDT2D_REFINE_RECORD_DOUBLES]
   uint32_t refine_cells = 1;               // the neighbourhood of the later refine_scans: 1 or 9 (set_refine_neighbourhood)
+  ndt2d_verify * verify = nullptr;         // match verification on the first device (made by the first verify_scans)
+  uint32_t verify_cells = 9;               // the parameters of the later verify_scans (set_verify_*): 1 or 9 cells,
+  double verify_gate_inlier = 9.0, verify_gate_pierce = 1.0;   // the gates,
+  bool verify_rays = true;                 // the ray walk
   int eigen_form = ndt2d::kEigenFormSchur;   // ndt2d_matcher_set_eigenvalue_form
 
   // The NDT in place: `ndt_` of the reference (scan_matcher_ndt.hpp:102) -- the grid every device of

@@ -393,6 +393,7 @@ void destroy_matcher(ndt2d_matcher * m)
   if (m->starts != nullptr) (void)ndt2d_starts_destroy(m->starts);            // (before its context)
   if (m->scans != nullptr) (void)ndt2d_scans_destroy(m->scans);               // (before its context)
   if (m->refine != nullptr) (void)ndt2d_refine_destroy(m->refine);            // (before its context)
+  if (m->verify != nullptr) (void)ndt2d_verify_destroy(m->verify);            // (before its context)
   for (ndt2d_scanstore * st : m->stores) (void)ndt2d_scanstore_destroy(st);   // (before their contexts)
   for (ndt2d_handle h : m->devs) (void)ndt2d_build_small_release(h);
   if (m->exchange != nullptr) ndt2d::exchange_destroy(m->exchange);

@@ -579,6 +579,103 @@ class ScanMatcherNDT:
         """(kernel_ms, fetch_ms) of the last timed refineScans (its last chunk)."""
         return self._batch_last_ms("refine")
 
+    def verifyScans(self, jobs, scans, job_scan=None, max_beams=None, neighbourhood=9, gate_inlier=9.0, gate_pierce=1.0,
+                    rays=True, want_beams=False):
+        """Is this match right?  Match verification of K jobs -- (scan, pose) pairs, as refineScans
+        takes them -- against the NDT in place, in one call (one upload, one kernel launch, one
+        read-back): which beams of each scan the map explains at the job's pose
+        (include/ndt2d_hip.h, "Match verification").  Returns one dict per job: n_beams, off (beams
+        that end off the grid), unseen (on the grid, where no cell of the neighbourhood can score),
+        outlier, inlier (m2 <= gate_inlier against the best cell of the neighbourhood), pierced
+        (beams whose ray from the robot passes through a cell's Gaussian before it reaches the
+        end's 3 x 3: in a wrong basin rays pass through walls), walked (beams whose ray was walked).
+        A verdict, no policy: nothing is accepted or rejected here.
+
+        max_beams: None takes the matcher's laser_max_beams -- the beams matchScan / scorePoints
+        computed the score from; 0 every point of the scan (filtering a scan before storeScan); n
+        min(n, the scan's points) by the same subsampling rule.  neighbourhood (1 or 9),
+        gate_inlier, gate_pierce, rays are set on the matcher for this call and stay.  The gates'
+        defaults are starting values, not tuned.
+        want_beams: each dict also holds classes (uint8, _capi.BEAM_OFF / _UNSEEN / _OUTLIER /
+        _INLIER), m2 (+inf for off and unseen), cells ([n, 2] uint32: the cell whose m2 won, the
+        first piercing cell; _capi.VERIFY_NO_CELL: none) and pierced_mask (bool).
+        No NDT in place: Ndt2dError (NDT2D_ERR_NO_GRID).  A scan without points: zeros."""
+        self.set_verify(neighbourhood=neighbourhood, gate_inlier=gate_inlier, gate_pierce=gate_pierce, rays=rays)
+        jp = _f64(jobs, (-1, 3))
+        K = len(jp)
+        arrays = [_f64(pts, (-1, 2)) for pts in scans]
+        offsets = np.zeros(len(arrays) + 1, dtype=np.uintp)
+        if arrays:
+            offsets[1:] = np.cumsum([len(a) for a in arrays])
+        pts = np.ascontiguousarray(np.concatenate(arrays) if arrays else np.zeros((0, 2)), dtype=np.float64)
+        js = _index_array("verifyScans", "job_scan", "scan", job_scan, K)
+        if job_scan is None and len(arrays) != K:
+            raise ValueError("verifyScans: without job_scan job k uses scan k: one scan per job")
+        limit = int(self.params["laser_max_beams"]) if max_beams is None else int(max_beams)
+        if limit < 0:
+            raise ValueError("verifyScans: max_beams must not be negative")
+        which = js if js is not None else np.arange(K)
+        if K and len(arrays) and np.any(np.asarray(which) >= len(arrays)):
+            cap = 0     # (the call refuses the job; nothing is written)
+        else:
+            sizes = [len(arrays[int(sc)]) for sc in which] if len(arrays) else []
+            cap = int(sum(n if limit == 0 else min(limit, n) for n in sizes))
+        records = np.zeros((K, _capi.VERIFY_RECORD_U32), dtype=np.uint32)
+        table = np.zeros(K + 1, dtype=np.uintp)
+        classes = np.zeros(cap, dtype=np.uint8) if want_beams else None
+        m2 = np.zeros(cap, dtype=np.float64) if want_beams else None
+        cells = np.zeros((cap, 2), dtype=np.uint32) if want_beams else None
+        u32p, u8p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)
+        self._check(self._L.ndt2d_matcher_verify_scans(
+            self._m, dptr(jp), js.ctypes.data_as(u32p) if js is not None else None, K, dptr(pts),
+            offsets.ctypes.data_as(C.POINTER(C.c_size_t)), len(arrays), limit, records.ctypes.data_as(u32p),
+            table.ctypes.data_as(C.POINTER(C.c_size_t)), classes.ctypes.data_as(u8p) if want_beams else None,
+            dptr(m2) if want_beams else None, cells.ctypes.data_as(u32p) if want_beams else None, cap), "verifyScans")
+        out = []
+        for k in range(K):
+            r = records[k]
+            d = dict(n_beams=int(r[0]), off=int(r[1]), unseen=int(r[2]), outlier=int(r[3]), inlier=int(r[4]), pierced=int(r[5]),
+                     walked=int(r[6]))
+            if want_beams:
+                a, b = int(table[k]), int(table[k + 1])
+                d.update(classes=classes[a:b] & 3, m2=m2[a:b].copy(), cells=cells[a:b].copy(),
+                         pierced_mask=(classes[a:b] & _capi.BEAM_PIERCED) != 0)
+            out.append(d)
+        return out
+
+    def set_verify(self, neighbourhood=None, gate_inlier=None, gate_pierce=None, rays=None):
+        """The parameters of the later verifyScans calls (None: as it is): the neighbourhood (1 or
+        9 cells per point), the gates (each >= 0 and finite), the ray walk (bool)."""
+        if neighbourhood is not None:
+            if not 0 <= int(neighbourhood) < 2 ** 32:
+                raise ValueError("set_verify: 1 or 9 cells")
+            self._check(self._L.ndt2d_matcher_set_verify_neighbourhood(self._m, int(neighbourhood)), "set_verify_neighbourhood")
+        if gate_inlier is not None or gate_pierce is not None:
+            have = self.verify_parameters()
+            self._check(self._L.ndt2d_matcher_set_verify_gates(
+                self._m, float(have["gate_inlier"] if gate_inlier is None else gate_inlier),
+                float(have["gate_pierce"] if gate_pierce is None else gate_pierce)), "set_verify_gates")
+        if rays is not None:
+            self._check(self._L.ndt2d_matcher_set_verify_rays(self._m, 1 if rays else 0), "set_verify_rays")
+
+    def verify_parameters(self):
+        """dict(neighbourhood, gate_inlier, gate_pierce, rays) of the later verifyScans calls."""
+        cells, rays = C.c_uint32(0), C.c_int(0)
+        gi, gp = C.c_double(0.0), C.c_double(0.0)
+        self._check(self._L.ndt2d_matcher_verify_neighbourhood(self._m, C.byref(cells)), "verify_neighbourhood")
+        self._check(self._L.ndt2d_matcher_verify_gates(self._m, C.byref(gi), C.byref(gp)), "verify_gates")
+        self._check(self._L.ndt2d_matcher_verify_rays(self._m, C.byref(rays)), "verify_rays")
+        return dict(neighbourhood=int(cells.value), gate_inlier=gi.value, gate_pierce=gp.value, rays=bool(rays.value))
+
+    def verify_set_timing(self, enabled):
+        """HIP events around the verification's kernel launch and read-back on / off (after the
+        first verifyScans with an NDT in place: the object is made by it)."""
+        self._batch_set_timing("verify", "verifyScans", enabled)
+
+    def verify_last_ms(self):
+        """(kernel_ms, fetch_ms) of the last timed verifyScans (its last chunk)."""
+        return self._batch_last_ms("verify")
+
     def last_build(self):
         """How the NDT in place was built: "build/fused-small-map", "build/device", "build/host" or ""."""
         v = self._L.ndt2d_matcher_last_build(self._m)
@@ -1053,7 +1150,7 @@ def heading_fan(poses, n_headings):
     return out
 
 
-def relocalize(matcher, points, start_poses, accept_below=None):
+def relocalize(matcher, points, start_poses, accept_below=None, verify=None):
     """Where in the matcher's map was this scan taken?  One matchStarts call from every start
     pose -- what a node that loaded its map does instead of refusing scans until somebody posts
     `initialpose` (reference src/ndt_mapper.cpp:315-320).  Returns the starts ranked by score
@@ -1061,7 +1158,12 @@ def relocalize(matcher, points, start_poses, accept_below=None):
     correction = matchScan's pose output, pose = start pose + correction as the reference adds
     it (:557-561), score, covariance).  Starts without a winner (no lattice candidate below 0)
     follow those with one, non-finite scores come last.  accept_below: keep only
-    isfinite(score) and score < accept_below, the loop-closure rule (:645)."""
+    isfinite(score) and score < accept_below, the loop-closure rule (:645).
+
+    verify: None, or dict(max_beams=..., neighbourhood=..., gate_inlier=..., gate_pierce=..., rays=...)
+    (any subset: verifyScans' arguments).  With it the ranked starts gain `verify`: the
+    verification counts of the scan at their corrected pose, from ONE extra verifyScans call over
+    all of them.  The ranking and what is kept stay as they are: a verdict, no policy."""
     starts = np.array(start_poses, dtype=np.float64).reshape(-1, 3)
     if len(starts) == 0:
         return []
@@ -1078,7 +1180,12 @@ def relocalize(matcher, points, start_poses, accept_below=None):
         ranked.append((key, dict(start=k, correction=correction, pose=correction + starts[k], score=score,
                                  covariance=res["covariance"])))
     ranked.sort(key=lambda e: e[0])
-    return [entry for _, entry in ranked]
+    entries = [entry for _, entry in ranked]
+    if verify is not None and entries:
+        counts = matcher.verifyScans([e["pose"] for e in entries], [points], job_scan=[0] * len(entries), **verify)
+        for e, c in zip(entries, counts):
+            e["verify"] = c
+    return entries
 
 
 def track_scans(matcher, jobs, scans, job_scan=None):
@@ -1098,6 +1205,13 @@ def track_scans(matcher, jobs, scans, job_scan=None):
         out.append(dict(job=k, scan=int(which[k]), score=float(res["score"]), correction=correction,
                         pose=correction + poses[k], covariance=res["covariance"]))
     return out
+
+
+def explained_mask(result):
+    """The beams of a verifyScans result (one job's dict, want_beams=True) worth storing: the map
+    does not contradict them -- class is not BEAM_OUTLIER and the ray is not pierced.  A bool array
+    over the job's beams (with max_beams=0: over the scan's points)."""
+    return (np.asarray(result["classes"]) != _capi.BEAM_OUTLIER) & ~np.asarray(result["pierced_mask"], dtype=bool)
 
 
 def refine_covariance(hessian):
