@@ -1,8 +1,8 @@
-"""profiles/host_split_ab.json: ndt_2d_amd/tools/latency_probe.c linked against the parent commit's library
+"""profiles/<NAME>.json (NAME: host_split_ab unless given): ndt_2d_amd/tools/latency_probe.c linked against the parent commit's library
 and against the tree's, run in turn in one session (parent1, branch1, parent2, ...), each run's JSON
 line kept as DIR/probe_<run>.json.
 
-    python experiments/host_split_ab.py DIR > profiles/host_split_ab.json
+    python experiments/host_split_ab.py DIR [NAME] > profiles/NAME.json
 
 The margin of a figure is the spread the parent shows against itself; a branch figure above the
 parent's highest on a majority of the branch runs is a regression."""
@@ -16,7 +16,7 @@ COLUMNS = [("match_scan_us", None), ("mapper_cycle_us", None), ("mapper_cycle_p9
            ("mapper_cycle_us", "real_lidar_map")]
 
 
-def main(where):
+def main(where, experiment="host_split_ab"):
     runs = {}
     for name in sorted(os.listdir(where)):
         if name.startswith("probe_") and name.endswith(".json"):
@@ -32,7 +32,7 @@ def main(where):
         rows.append({"column": (sub + "." if sub else "") + col, "values": vals, "parent_lo": lo, "parent_hi": hi,
                      "branch_runs_above_every_parent_run": slow,
                      "verdict": "regression" if 2 * len(slow) > len(branches) else "within the parent's own spread"})
-    json.dump({"experiment": "host_split_ab",
+    json.dump({"experiment": experiment,
                "what": "latency_probe.c (bench.py's default-search settings) against the parent's library and the tree's, "
                        "in turn, one session, one MI355X; microseconds",
                "rule": "margin = the spread of the parent's own runs; a branch figure above the parent's highest on a "
@@ -42,4 +42,4 @@ def main(where):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1])
+    main(*sys.argv[1:3])

@@ -26,7 +26,7 @@
 // only ordering between the launches; inside the workgroup the only barrier is __syncthreads.
 //
 // Why through the list install and not by writing the scorers' layouts from the workgroup: the
-// context's buffers are private to ndt2d_device.hip, and the kernel sources at the top of csrc/
+// context's buffers are private to csrc/device/, and the kernel sources at the top of csrc/
 // are pinned by the hash the committed counter profiles carry (profiles/r06_pmc.json,
 // tests/test_bench_artefacts.py) -- this directory stands beside them, like resample/ and
 // occupancy_map/, and goes through the public boundary.  For the same reason Cell::compute is

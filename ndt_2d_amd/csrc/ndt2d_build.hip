@@ -468,7 +468,7 @@ int key_bits(uint32_t ncell)
 }  // namespace
 
 // The compacted form of a device-built grid (what the host install of a small grid prepares on
-// the CPU, ndt2d_device.hip ndt2d_set_grid): the records of the cells that can score, in cell
+// the CPU, device/ndt2d_context_grid.hip ndt2d_set_grid): the records of the cells that can score, in cell
 // order, followed by the sentinel's, and the cell -> record table (uint16; cells that cannot score
 // and entry ncell, "outside", point at the sentinel).  The searches keep both in LDS -- 15 KB
 // instead of 81 at cfg-2, two blocks to a CU -- and were 8-20 % slower on a device-built grid

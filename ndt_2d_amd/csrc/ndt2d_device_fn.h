@@ -311,7 +311,7 @@ __device__ __forceinline__ void raise_host_flag(double * flag_slot, unsigned lon
 // polling the others' `done` words: ndt2d_match_small.hip, score_few_kernel) says so to the host
 // instead of trapping -- a trap faults the whole HIP context and with it every matcher of the
 // process: the flag leaves as seq | kHostFlagGaveUp, which the host's wait turns into
-// NDT2D_ERR_HIP for THIS call only (ndt2d_device.hip wait_host_flag).
+// NDT2D_ERR_HIP for THIS call only (device/ndt2d_context.h wait_host_flag).
 // (kHostFlagGaveUp itself: ndt2d_kernels.h, the host reads it too)
 // The bound is TIME, read from the chip's 100 MHz wall clock (round 6; until then a count of
 // poll trips, nominally two seconds -- but trips are not time: on a time-sliced or oversubscribed

@@ -1,6 +1,6 @@
 // The C boundary lets no C++ exception through (include/ndt2d_hip.h: "int status, no exceptions";
 // the plugin's caller is rclcpp's executor, reference src/ndt_mapper.cpp).  Every multi-line
-// extern "C" entry point of ndt2d_host.cpp / ndt2d_device.hip has its body between these two
+// extern "C" entry point of ndt2d_host.cpp, host/ and device/ has its body between these two
 // macros: std::bad_alloc / std::length_error -- a std::vector sized by a pose of 1e15 or an
 // infinite range_max that slipped past the argument checks -- become NDT2D_ERR_ALLOC, anything else
 // NDT2D_ERR_INTERNAL, the message goes where ndt2d_last_error / ndt2d_matcher_last_error find it,

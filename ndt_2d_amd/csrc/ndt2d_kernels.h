@@ -1,5 +1,5 @@
 // Internal interface between the HIP kernels (ndt2d_kernels.hip) and the
-// device-layer C-ABI (ndt2d_device.hip).  Not installed; the public boundary is
+// device-layer C-ABI (device/).  Not installed; the public boundary is
 // include/ndt2d_hip.h.
 #ifndef NDT2D_KERNELS_H_
 #define NDT2D_KERNELS_H_
@@ -241,7 +241,7 @@ hipError_t launch_score_poses(const PosesArgs & args, double * workspace, double
                               unsigned long long host_seq = 0);
 
 // out[k] = ((rows[0][k] + rows[1][k]) + rows[2][k]) + ... for the 8 moment sums of n_rows pieces of
-// a particle set scored piece by piece (the pipelined pose batches of ndt2d_device.hip).
+// a particle set scored piece by piece (the pipelined pose batches of device/ndt2d_context_poses.hip).
 hipError_t launch_sum_moment_rows(const double * rows, uint32_t n_rows, double * out, hipStream_t stream);
 
 // The moment sums of updateStatistics as a kernel argument (by_value != 0) -- see launch_pf_finalize.

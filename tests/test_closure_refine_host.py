@@ -105,7 +105,7 @@ def test_one_kernel_text_for_both_map_sources():
     assert "occ_bits" not in source and "cells_global" not in source
     assert "template <bool POW2, uint32_t CELLS, class SOURCE>" in refine and "#ifndef NDT2D_REFINE_KERNEL_ONLY" in refine
     assert "a.source.grid(jr.slot)" in refine and "a.source.map(jr.slot)" in refine
-    # the included file is hashed with the headers, as ndt2d_device.hip is: an edit to the kernel makes
+    # the included file is hashed with the headers: an edit to the kernel makes
     # the closure's object stale too, so the library cannot come to hold two texts of it
     from ndt_2d_amd import build
     assert os.path.join(csrc, "refine", "ndt2d_refine.hip") in build.HEADERS

@@ -93,7 +93,9 @@ def test_every_multi_line_entry_point_is_guarded():
     missing = []
     host = sorted(os.path.join("host", f) for f in os.listdir(os.path.join(root, "host")) if f.endswith(".cpp"))
     assert len(host) >= 5, host
-    for name in ["ndt2d_host.cpp"] + host + ["ndt2d_device.hip"]:
+    device = sorted(os.path.join("device", f) for f in os.listdir(os.path.join(root, "device")) if f.endswith(".hip"))
+    assert len(device) >= 5, device
+    for name in ["ndt2d_host.cpp"] + host + device:
         lines = open(os.path.join(root, name)).read().split("\n")
         for i, ln in enumerate(lines):
             m = re.match(r'^(?:extern "C" )?int (ndt2d_\w+)\(', ln)
@@ -111,3 +113,43 @@ def test_every_multi_line_entry_point_is_guarded():
             if "NDT2D_C_TRY" not in body and "catch (...)" not in body:
                 missing.append(m.group(1))
     assert not missing, missing
+
+
+@pytest.mark.gpu
+def test_destroying_one_context_leaves_the_other_ones_buffers_alone():
+    """A context's buffers free themselves with it (csrc/device/ndt2d_context.h): two contexts with the
+    same 8 x 8 grid, 16 beams and 3 x 3 x 3 search give the same match, and the second gives it again
+    after the first is destroyed -- a destructor that freed what it does not own, or twice, would show here."""
+    import ctypes as C
+    L = _capi.lib()
+    cells = np.zeros((64, 6))
+    for j in range(8):
+        for i in range(8):
+            cells[j * 8 + i] = [0.25 * i + 0.125, 0.25 * j + 0.125, 16.0, 0.0, 16.0, 10.0 if (i + j) % 3 else 0.0]
+    ang = np.linspace(0.0, 2.0 * np.pi, 16, endpoint=False)
+    beams = np.ascontiguousarray(np.stack([0.6 * np.cos(ang), 0.6 * np.sin(ang)], axis=1))
+    dth = np.array([-0.1, 0.0, 0.1])
+    ct, st, dlin = np.cos(dth), np.sin(dth), np.array([-0.25, 0.0, 0.25])
+
+    def context():
+        h = C.c_void_p()
+        assert L.ndt2d_create(C.byref(h), 0) == _capi.OK
+        assert L.ndt2d_set_grid(h, _capi.dptr(cells), 8, 8, 0.25, 0.0, 0.0) == _capi.OK
+        assert L.ndt2d_set_beams(h, _capi.dptr(beams), 16) == _capi.OK
+        assert L.ndt2d_set_search(h, 1.0, 1.0, _capi.dptr(dth), _capi.dptr(ct), _capi.dptr(st), 3,
+                                  _capi.dptr(dlin), 3) == _capi.OK
+        return h
+
+    def match(h):
+        scores, res = np.full(27, 123.0), _capi.MatchResult()
+        assert L.ndt2d_match(h, 0, 3, _capi.dptr(scores), C.byref(res)) == _capi.OK, L.ndt2d_last_error(h)
+        return scores.tobytes(), bytes(res)
+
+    first, second = context(), context()
+    one, two = match(first), match(second)
+    assert L.ndt2d_destroy(first) == _capi.OK
+    again = match(second)
+    assert L.ndt2d_destroy(second) == _capi.OK
+    assert one == two == again
+    scores = np.frombuffer(one[0])
+    assert np.isfinite(scores).all() and (scores != 123.0).all() and scores.min() < scores.max()   # (a search ran)
