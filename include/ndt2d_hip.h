@@ -610,6 +610,55 @@ int ndt2d_verify_rays(ndt2d_verify * verify, int * out);
 int ndt2d_verify_set_timing(ndt2d_verify * verify, int enabled);
 int ndt2d_verify_last_ms(ndt2d_verify * verify, float * kernel_ms, float * fetch_ms);
 
+/* ---- Match verification on each loop-closure candidate's own map (csrc/closure/) ----
+ *
+ * A loop-closure match is made against the candidate's own map of one or two old scans, which
+ * ndt2d_closure_match and ndt2d_closure_refine build in the closure's buffers and drop.
+ * ndt2d_closure_verify runs the verification above on such maps: per chunk one upload, the build
+ * launch of ndt2d_closure_match for the candidates the jobs name (a candidate no job names is not
+ * built), ONE launch of the verification -- a workgroup per job, on the packed records and the
+ * cell -> record table of its candidate's slot -- and one read-back.  The kernel is the one of
+ * ndt2d_verify_run (csrc/verify/ndt2d_verify.hip), instantiated on the slots; nothing of the grid
+ * installed in the context is read or changed, and no installed grid is no error here.  A verdict,
+ * not a policy: nothing is accepted or rejected.
+ *
+ *   candidates   cand_offsets, ids, poses_xyt, ndt_resolution, range_max as ndt2d_closure_match
+ *                takes them, with everything it refuses about a candidate.
+ *   scans, jobs  beams_xy, beam_offsets, n_scans, jobs_xyt, job_scan as ndt2d_verify_run takes
+ *                them, with everything it refuses; job_candidate[k]: the candidate job k is
+ *                verified on (NULL: job k uses candidate k, n_jobs must equal n_candidates).  A
+ *                job_scan or job_candidate out of range: NDT2D_ERR_INVALID, the message names the
+ *                job ("job k").  A slot grid side above 2^24 cells with rays enabled:
+ *                NDT2D_ERR_INVALID.  A refused call launches nothing and leaves the outputs as they
+ *                were.
+ *   outputs      records_out, beam_class_out, beam_m2_out, beam_cells_out in ndt2d_verify_run's
+ *                layouts and job order; the per-beam arrays are optional, each may be NULL.
+ *   bits         a job's record and per-beam outputs are what ndt2d_verify_run gives for the same
+ *                scan, pose and parameters on the grid ndt2d_scanstore_build installs for that
+ *                candidate; a job depends on nothing but its scan, its pose, its candidate and
+ *                the parameters: not on the other jobs or the chunks.
+ *   chunks       the plan of ndt2d_closure_refine (csrc/closure/ndt2d_closure_jobs.h): at most
+ *                max_candidates candidates and 4,096 jobs a launch; a chunk also closes where its
+ *                jobs' per-beam results pass 2^24 (a job more is taken whole).
+ *   set_verify_neighbourhood / _gates / _rays and their getters   the parameters of this call,
+ *                kept on the closure object with ndt2d_verify's rules, defaults (1 cell, 9.0 and
+ *                1.0, rays on) and refusals; the neighbourhood is apart from the refinement's
+ *                ndt2d_closure_set_neighbourhood.
+ *   ndt2d_closure_last_ms   after this call: the build and the verify launch of its last chunk. */
+int ndt2d_closure_verify(ndt2d_closure * closure, size_t n_candidates, const size_t * cand_offsets,
+                         const size_t * ids, const double * poses_xyt, double ndt_resolution,
+                         double range_max, const double * jobs_xyt, const uint32_t * job_scan,
+                         const uint32_t * job_candidate, size_t n_jobs, const double * beams_xy,
+                         const size_t * beam_offsets, size_t n_scans, uint32_t * records_out,
+                         uint8_t * beam_class_out, double * beam_m2_out, uint32_t * beam_cells_out);
+int ndt2d_closure_set_verify_neighbourhood(ndt2d_closure * closure, uint32_t cells);
+int ndt2d_closure_verify_neighbourhood(ndt2d_closure * closure, uint32_t * out);
+int ndt2d_closure_set_verify_gates(ndt2d_closure * closure, double gate_inlier, double gate_pierce);
+int ndt2d_closure_verify_gates(ndt2d_closure * closure, double * gate_inlier_out,
+                               double * gate_pierce_out);
+int ndt2d_closure_set_verify_rays(ndt2d_closure * closure, int enabled);
+int ndt2d_closure_verify_rays(ndt2d_closure * closure, int * out);
+
 /* Upload the beam endpoints of one scan, robot frame, already subsampled to
  * min(laser_max_beams, points.size()) points by the caller
  * (src/scan_matcher_ndt.cpp:95-96,110 / :165-166,171).  Beams are taken as given: finite,
@@ -1388,6 +1437,26 @@ int ndt2d_matcher_refine_candidates(ndt2d_matcher * m, const size_t * cand_offse
                                     double * poses_out, double * scores_out, double * start_scores_out,
                                     double * gradients_out, double * hessians_out, int32_t * status_out,
                                     uint32_t * evals_out);
+/* Match verification of K jobs, each on a loop-closure candidate's OWN map, in one call
+ * (ndt2d_closure_verify on the first device, with the matcher's resolution, range_max and stored
+ * scans): what reset() + add_scans_by_id(candidate) + verify_scans(job) gives per job, bit for bit,
+ * without the K builds, installs, launches and read-backs -- and without touching the NDT in
+ * place: has_ndt and the grid are the same before and after, and no NDT in place is no error.
+ * Candidates and job_candidate as refine_candidates takes them; scans, jobs, job_scan, max_beams,
+ * the outputs and beam_cap as verify_scans takes them.  Governed by the matcher's verify
+ * parameters (set_verify_neighbourhood, _gates, _rays).  Jobs of a scan without points get a
+ * record of zeros.  A search launched ahead by score_scan is waited out and dropped first.
+ * NDT2D_ERR_INVALID, nothing launched, the outputs as they were: everything match_candidates
+ * refuses about a candidate, everything verify_scans refuses about scans and jobs, a
+ * job_candidate out of range ("job k"). */
+int ndt2d_matcher_verify_candidates(ndt2d_matcher * m, const size_t * cand_offsets, const size_t * ids,
+                                    const double * poses_xyt, size_t n_candidates,
+                                    const double * jobs_xyt, const uint32_t * job_scan,
+                                    const uint32_t * job_candidate, size_t n_jobs,
+                                    const double * points_xy, const size_t * point_offsets,
+                                    size_t n_scans, size_t max_beams, uint32_t * records_out,
+                                    size_t * beam_offsets_out, uint8_t * beam_class_out,
+                                    double * beam_m2_out, uint32_t * beam_cells_out, size_t beam_cap);
 /* The two halves of matchScan, for sharded (multi-GPU) searches:
  * prepare_search subsamples the scan (:95-96,110), builds the offset and
  * cos/sin tables (:103-107,117,119) and uploads them -- after it,

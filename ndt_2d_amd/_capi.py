@@ -123,6 +123,14 @@ SIGNATURES = {
                                        _u32, _d, _d, _dp]),
     "ndt2d_closure_set_neighbourhood": (C.c_int, [_vp, _u32]),
     "ndt2d_closure_neighbourhood": (C.c_int, [_vp, C.POINTER(_u32)]),
+    "ndt2d_closure_verify": (C.c_int, [_vp, _sz, _szp, _szp, _dp, _d, _d, _dp, C.POINTER(_u32), C.POINTER(_u32), _sz, _dp, _szp, _sz,
+                                       C.POINTER(_u32), C.POINTER(C.c_uint8), _dp, C.POINTER(_u32)]),
+    "ndt2d_closure_set_verify_neighbourhood": (C.c_int, [_vp, _u32]),
+    "ndt2d_closure_verify_neighbourhood": (C.c_int, [_vp, C.POINTER(_u32)]),
+    "ndt2d_closure_set_verify_gates": (C.c_int, [_vp, _d, _d]),
+    "ndt2d_closure_verify_gates": (C.c_int, [_vp, _dp, _dp]),
+    "ndt2d_closure_set_verify_rays": (C.c_int, [_vp, C.c_int]),
+    "ndt2d_closure_verify_rays": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "ndt2d_closure_set_timing": (C.c_int, [_vp, C.c_int]),
     "ndt2d_closure_last_ms": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "ndt2d_grid_view_get": (C.c_int, [_vp, _vp]),
@@ -283,6 +291,8 @@ SIGNATURES = {
     "ndt2d_matcher_refine_neighbourhood": (C.c_int, [_vp, C.POINTER(_u32)]),
     "ndt2d_matcher_verify_scans": (C.c_int, [_vp, _dp, C.POINTER(_u32), _sz, _dp, _szp, _sz, _sz, C.POINTER(_u32), _szp,
                                              C.POINTER(C.c_uint8), _dp, C.POINTER(_u32), _sz]),
+    "ndt2d_matcher_verify_candidates": (C.c_int, [_vp, _szp, _szp, _dp, _sz, _dp, C.POINTER(_u32), C.POINTER(_u32), _sz, _dp, _szp,
+                                                  _sz, _sz, C.POINTER(_u32), _szp, C.POINTER(C.c_uint8), _dp, C.POINTER(_u32), _sz]),
     "ndt2d_matcher_verify": (_vp, [_vp]),
     "ndt2d_matcher_set_verify_neighbourhood": (C.c_int, [_vp, _u32]),
     "ndt2d_matcher_verify_neighbourhood": (C.c_int, [_vp, C.POINTER(_u32)]),

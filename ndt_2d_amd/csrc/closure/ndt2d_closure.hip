@@ -1,6 +1,7 @@
 // Batched loop-closure match: ONE scan against K candidate maps in one build launch, one search
 // launch, one reduction launch and one read-back (gfx950 / MI355X) -- and the Newton NDT
-// registration of K (scan, pose) jobs on such maps in one build launch and one refinement launch.
+// registration of K (scan, pose) jobs on such maps in one build launch and one refinement launch,
+// and their match verification in one build launch and one verify launch.
 //
 // Reference: the loop-closure thread, src/ndt_mapper.cpp:619-671 -- per candidate scan `reset()`,
 // `addScans(begin, end)` of one or two old scans, `matchScan(scan, ...)`.  Through the matcher
@@ -26,6 +27,13 @@
 //       search is 80 x 7 tiles.
 //   batch_reduce_kernel    one block per candidate map: the n_theta records of its blocks ->
 //       {best_score, best_index (+0.5: near tie), acc[10]} with merge_best, fixed order.
+//
+//   verify_kernel<POW2, CELLS, SlotSource> (../verify/ndt2d_verify.hip, its device half included
+//       here)  ndt2d_closure_verify: the match verification of K (scan, pose) jobs, each on its
+//       candidate's own map, behind the same build launch in ONE launch with a workgroup of 256
+//       threads per job; the plan is ndt2d_closure_jobs.h's with the jobs' beams as weights.  A
+//       job's record and per-beam results have the bits ndt2d_verify_run gives on the grid
+//       ndt2d_scanstore_build installs for the candidate.
 //
 //   refine_kernel<POW2, CELLS, SlotSource> (../refine/ndt2d_refine.hip, its device half included
 //       here)  ndt2d_closure_refine: the Newton NDT registration of K jobs, each on its
@@ -67,6 +75,9 @@
 // (the Newton registration's kernel -- its device half, without the installed grid's object and entry points)
 #define NDT2D_REFINE_KERNEL_ONLY
 #include "refine/ndt2d_refine.hip"
+// (the match verification's kernel -- its device half, likewise)
+#define NDT2D_VERIFY_KERNEL_ONLY
+#include "verify/ndt2d_verify.hip"
 
 namespace ndt2d
 {
@@ -211,6 +222,18 @@ void launch_slot_refine(bool pow2, dim3 blocks, dim3 threads, hipStream_t stream
   else hipLaunchKernelGGL((refine_kernel<false, CELLS, SlotSource>), blocks, threads, 0, stream, a);
 }
 
+using SlotVerifyArgs = VerifyArgs<SlotSource>;
+
+// The match verification (../verify/ndt2d_verify.hip) on the slots: find() is "can score" for the
+// neighbourhood and for the ray alike (a table entry exists only for cells of n >= 5), the clip, the
+// line and the origin cell run on the slot's own geometry.
+template <uint32_t CELLS>
+void launch_slot_verify(bool pow2, dim3 blocks, dim3 threads, hipStream_t stream, const SlotVerifyArgs & a)
+{
+  if (pow2) hipLaunchKernelGGL((verify_kernel<true, CELLS, SlotSource>), blocks, threads, 0, stream, a);
+  else hipLaunchKernelGGL((verify_kernel<false, CELLS, SlotSource>), blocks, threads, 0, stream, a);
+}
+
 }  // namespace
 
 }  // namespace ndt2d
@@ -218,7 +241,7 @@ void launch_slot_refine(bool pow2, dim3 blocks, dim3 threads, hipStream_t stream
 // ---- the object and the C entry points ----
 
 // (BatchHost's stage: [tables | beams | slots | scan table]; its events: before the build, behind
-// it, behind the search)
+// it, behind the search -- or the refinement, or the verification)
 struct ndt2d_closure : ndt2d::BatchHost
 {
   ndt2d_scanstore * store = nullptr;
@@ -233,6 +256,12 @@ struct ndt2d_closure : ndt2d::BatchHost
   std::vector<uint64_t> scan_first;   // scan -> its first beam within the chunk's beams (or: not sent)
   std::vector<uint32_t> sent;         // the chunk's scans in upload order
   std::vector<ndt2d::ClosureSlot> chunk_slots;
+  // ndt2d_closure_verify: ndt2d_verify's parameters and defaults
+  uint32_t verify_cells = 1;
+  double gate_inlier = 9.0, gate_pierce = 1.0;
+  bool rays = true;
+  std::vector<size_t> job_first;      // job of the call -> its first beam within the caller's per-beam arrays
+  std::vector<size_t> job_beams;      // job of the call -> the beams of its scan (its weight in the plan)
 };
 
 namespace
@@ -435,6 +464,59 @@ int match_chunk(ndt2d_closure * c, size_t k0, size_t k1, const size_t * cand_off
   return ndt2d::batch_reduce_and_fetch(c, stream, k0, n_slots, a.n_th, n_lattice, -1, records_out, all_scores);
 }
 
+// The slots of one chunk of a job plan (ndt2d_closure_jobs.h) into c->chunk_slots, with their
+// offsets into the chunk's arrays as match_chunk lays them out, and the arrays grown to hold them.
+// c->slots[k] holds candidate k's geometry and counts.  *n_map_scans: the scans of the chunk's maps.
+int place_chunk_slots(ndt2d_closure * c, const ndt2d::ClosureJobChunk & plan, size_t * n_map_scans)
+{
+  const size_t n_slots = plan.candidates.size();
+  c->chunk_slots.resize(n_slots);
+  size_t n_world = 0, n_list = 0, n_lookup = 0, n_scans = 0;
+  for (size_t y = 0; y < n_slots; ++y)
+  {
+    const size_t k = plan.candidates[y];
+    ClosureSlot & s = c->chunk_slots[y];
+    s = c->slots[k];
+    s.scan_first = static_cast<uint32_t>(n_scans);
+    s.world_off = static_cast<uint32_t>(n_world);
+    s.list_off = static_cast<uint32_t>(n_list);
+    s.lookup_off = static_cast<uint32_t>(n_lookup);
+    n_scans += s.n_scans;
+    n_world += s.n_points;
+    n_list += std::max<size_t>(1, std::min<size_t>(s.n_points, s.grid.ncell));
+    n_lookup += (static_cast<size_t>(s.grid.ncell) + 2 + 7) & ~size_t(7);
+  }
+  *n_map_scans = n_scans;
+  NDT2D_BATCH_HIP(c, grow_device(&c->d_world, &c->world_cap, std::max<size_t>(1, n_world) * 2 * sizeof(double)));
+  NDT2D_BATCH_HIP(c, grow_device(&c->d_cells6, &c->cells6_cap, n_list * 6 * sizeof(double)));
+  NDT2D_BATCH_HIP(c, grow_device(&c->d_records, &c->records_cap, n_list * 6 * sizeof(double)));
+  NDT2D_BATCH_HIP(c, grow_device(&c->d_index, &c->index_cap, n_list * sizeof(uint32_t)));
+  NDT2D_BATCH_HIP(c, grow_device(&c->d_lookup, &c->lookup_cap, n_lookup * sizeof(uint16_t)));
+  return NDT2D_OK;
+}
+
+// The scan table of the chunk's maps (c->chunk_slots: place_chunk_slots), as the build reads it.
+void fill_scan_table(const ndt2d_closure * c, const ndt2d::ClosureJobChunk & plan, const size_t * cand_offsets,
+                     const size_t * ids, const double * poses_xyt, SmallScan * table)
+{
+  const ndt2d_scanstore * store = c->store;
+  for (size_t y = 0; y < plan.candidates.size(); ++y)
+  {
+    const size_t k = plan.candidates[y];
+    uint32_t first = 0;
+    for (size_t j = cand_offsets[k]; j < cand_offsets[k + 1]; ++j)
+    {
+      SmallScan & sc = table[c->chunk_slots[y].scan_first + (j - cand_offsets[k])];
+      sc.x = poses_xyt[3 * j];
+      sc.y = poses_xyt[3 * j + 1];
+      ndt2d_cos_sin(poses_xyt[3 * j + 2], &sc.c, &sc.s);   // (src/ndt_model.cpp:135-136, host libm)
+      sc.pool_offset = store->offset[ids[j]];
+      sc.first = first;
+      first += store->count[ids[j]];
+    }
+  }
+}
+
 struct RefineCall
 {
   const size_t * cand_offsets;
@@ -457,27 +539,12 @@ int refine_chunk(ndt2d_closure * c, const ndt2d::ClosureJobChunk & plan, const R
 {
   using ndt2d::RefineJob;
   using ndt2d::kRefineRec;
-  ndt2d_scanstore * store = c->store;
   const size_t n_slots = plan.candidates.size(), n_jobs = plan.jobs.size();
   hipStream_t stream = static_cast<hipStream_t>(ndt2d_get_stream(c->h));
 
-  // the slots with their offsets into the chunk's arrays, as match_chunk lays them out
-  c->chunk_slots.resize(n_slots);
-  size_t n_world = 0, n_list = 0, n_lookup = 0, n_map_scans = 0;
-  for (size_t y = 0; y < n_slots; ++y)
-  {
-    const size_t k = plan.candidates[y];
-    ClosureSlot & s = c->chunk_slots[y];
-    s = c->slots[k];
-    s.scan_first = static_cast<uint32_t>(n_map_scans);
-    s.world_off = static_cast<uint32_t>(n_world);
-    s.list_off = static_cast<uint32_t>(n_list);
-    s.lookup_off = static_cast<uint32_t>(n_lookup);
-    n_map_scans += s.n_scans;
-    n_world += s.n_points;
-    n_list += std::max<size_t>(1, std::min<size_t>(s.n_points, s.grid.ncell));
-    n_lookup += (static_cast<size_t>(s.grid.ncell) + 2 + 7) & ~size_t(7);
-  }
+  size_t n_map_scans = 0;
+  const int prc = place_chunk_slots(c, plan, &n_map_scans);
+  if (prc != NDT2D_OK) return prc;
 
   // the scans this chunk's jobs name, each once, in the order the jobs first name them
   const size_t n_beams = ndt2d::refine_jobs::plan_sent_scans(
@@ -490,11 +557,6 @@ int refine_chunk(ndt2d_closure * c, const ndt2d::ClosureJobChunk & plan, const R
   const size_t off_jobs = off_scans + 5 * n_map_scans;
   const size_t off_trig = off_jobs + n_jobs * ndt2d::kRefineJobDoubles;
   const size_t n_stage = off_trig + 2 * n_jobs;
-  NDT2D_BATCH_HIP(c, grow_device(&c->d_world, &c->world_cap, std::max<size_t>(1, n_world) * 2 * sizeof(double)));
-  NDT2D_BATCH_HIP(c, grow_device(&c->d_cells6, &c->cells6_cap, n_list * 6 * sizeof(double)));
-  NDT2D_BATCH_HIP(c, grow_device(&c->d_records, &c->records_cap, n_list * 6 * sizeof(double)));
-  NDT2D_BATCH_HIP(c, grow_device(&c->d_index, &c->index_cap, n_list * sizeof(uint32_t)));
-  NDT2D_BATCH_HIP(c, grow_device(&c->d_lookup, &c->lookup_cap, n_lookup * sizeof(uint16_t)));
   NDT2D_BATCH_HIP(c, ndt2d::grow_pair(&c->h_stage, &c->d_stage, &c->stage_cap, n_stage));
   NDT2D_BATCH_HIP(c, ndt2d::grow_pair(&c->h_out, &c->d_out, &c->out_cap, n_jobs * kRefineRec));
 
@@ -505,22 +567,7 @@ int refine_chunk(ndt2d_closure * c, const ndt2d::ClosureJobChunk & plan, const R
                 2 * (t.beam_offsets[sc + 1] - t.beam_offsets[sc]) * sizeof(double));
   }
   std::memcpy(st + off_slots, c->chunk_slots.data(), n_slots * sizeof(ClosureSlot));
-  SmallScan * table = reinterpret_cast<SmallScan *>(st + off_scans);
-  for (size_t y = 0; y < n_slots; ++y)
-  {
-    const size_t k = plan.candidates[y];
-    uint32_t first = 0;
-    for (size_t j = t.cand_offsets[k]; j < t.cand_offsets[k + 1]; ++j)
-    {
-      SmallScan & sc = table[c->chunk_slots[y].scan_first + (j - t.cand_offsets[k])];
-      sc.x = t.poses_xyt[3 * j];
-      sc.y = t.poses_xyt[3 * j + 1];
-      ndt2d_cos_sin(t.poses_xyt[3 * j + 2], &sc.c, &sc.s);   // (src/ndt_model.cpp:135-136, host libm)
-      sc.pool_offset = store->offset[t.ids[j]];
-      sc.first = first;
-      first += store->count[t.ids[j]];
-    }
-  }
+  fill_scan_table(c, plan, t.cand_offsets, t.ids, t.poses_xyt, reinterpret_cast<SmallScan *>(st + off_scans));
   for (size_t b = 0; b < n_jobs; ++b)
   {
     const size_t k = plan.jobs[b], sc = t.scan_of(k);
@@ -562,6 +609,112 @@ int refine_chunk(ndt2d_closure * c, const ndt2d::ClosureJobChunk & plan, const R
   for (size_t bj = 0; bj < n_jobs; ++bj)
   {
     std::memcpy(records_out + static_cast<size_t>(plan.jobs[bj]) * kRefineRec, c->h_out + bj * kRefineRec, kRefineRec * sizeof(double));
+  }
+  return NDT2D_OK;
+}
+
+struct SlotVerifyCall
+{
+  const size_t * cand_offsets;
+  const size_t * ids;
+  const double * poses_xyt;
+  ndt2d::VerifyCall v;   // the jobs, the scans and the outputs, as ndt2d_verify_run takes them
+};
+
+// One chunk of ndt2d_closure_verify's plan, of a call whose arguments have been checked: one upload,
+// the build of the chunk's candidates, the verification of its jobs -- a block each, on the slot its
+// record names -- and one read-back.  The chunk's per-beam results lie job after job in the plan's
+// order; c->job_first[k]: where job k's go in the caller's arrays.
+int verify_chunk(ndt2d_closure * c, const ndt2d::ClosureJobChunk & plan, const SlotVerifyCall & t)
+{
+  using ndt2d::VerifyJob;
+  constexpr size_t kVerRec = ndt2d::kVerifyRec;
+  const ndt2d::VerifyCall & v = t.v;
+  const size_t n_slots = plan.candidates.size(), n_jobs = plan.jobs.size();
+  hipStream_t stream = static_cast<hipStream_t>(ndt2d_get_stream(c->h));
+
+  size_t n_map_scans = 0;
+  const int prc = place_chunk_slots(c, plan, &n_map_scans);
+  if (prc != NDT2D_OK) return prc;
+
+  // the scans this chunk's jobs name, each once, in the order the jobs first name them
+  const size_t n_beams = ndt2d::refine_jobs::plan_sent_scans(
+    n_jobs, [&](size_t b) { return static_cast<size_t>(plan.jobs[b]); }, [&](size_t k) { return v.scan_of(k); }, v.beam_offsets,
+    v.n_scans, c->scan_first, c->sent);
+  size_t n_out = 0;
+  for (size_t b = 0; b < n_jobs; ++b) n_out += v.beams_of(plan.jobs[b]);
+
+  // the one upload of the chunk: [beams | slots | scan table | jobs | cos / sin pairs]
+  const size_t off_slots = 2 * n_beams;   // (beams in front: 16-byte loads)
+  const size_t off_scans = off_slots + n_slots * (sizeof(ClosureSlot) / sizeof(double));
+  const size_t off_jobs = off_scans + 5 * n_map_scans;
+  const size_t off_trig = off_jobs + n_jobs * ndt2d::kVerifyJobDoubles;
+  const size_t n_stage = off_trig + 2 * n_jobs;
+  const ndt2d::VerifyOutLayout out = ndt2d::verify_out_layout(n_jobs, n_out, v);
+  NDT2D_BATCH_HIP(c, ndt2d::grow_pair(&c->h_stage, &c->d_stage, &c->stage_cap, n_stage));
+  NDT2D_BATCH_HIP(c, ndt2d::grow_pair(&c->h_out, &c->d_out, &c->out_cap, out.total));
+
+  double * st = c->h_stage;
+  for (const uint32_t sc : c->sent)
+  {
+    std::memcpy(st + 2 * c->scan_first[sc], v.beams_xy + 2 * v.beam_offsets[sc],
+                2 * (v.beam_offsets[sc + 1] - v.beam_offsets[sc]) * sizeof(double));
+  }
+  std::memcpy(st + off_slots, c->chunk_slots.data(), n_slots * sizeof(ClosureSlot));
+  fill_scan_table(c, plan, t.cand_offsets, t.ids, t.poses_xyt, reinterpret_cast<SmallScan *>(st + off_scans));
+  size_t out_first = 0;
+  for (size_t b = 0; b < n_jobs; ++b)
+  {
+    const size_t k = plan.jobs[b];
+    const double * p = v.jobs_xyt + 3 * k;
+    reinterpret_cast<VerifyJob *>(st + off_jobs)[b] =
+      VerifyJob{p[0], p[1], static_cast<uint32_t>(v.beams_of(k)), plan.job_slot[b], c->scan_first[v.scan_of(k)], out_first};
+    out_first += v.beams_of(k);
+    // cos / sin of the heading from the host libm, as everywhere in this library
+    ndt2d_cos_sin(p[2], st + off_trig + 2 * b, st + off_trig + 2 * b + 1);
+  }
+  NDT2D_BATCH_HIP(c, hipMemcpyAsync(c->d_stage, st, n_stage * sizeof(double), hipMemcpyHostToDevice, stream));
+  c->timed = false;
+  if (c->timing) NDT2D_BATCH_HIP(c, hipEventRecord(c->ev[0], stream));
+
+  ndt2d::ClosureBuildArgs b{};
+  const int brc = launch_build(c, stream, n_slots, reinterpret_cast<const ClosureSlot *>(c->d_stage + off_slots),
+                               reinterpret_cast<const SmallScan *>(c->d_stage + off_scans), &b);
+  if (brc != NDT2D_OK) return brc;
+  if (c->timing) NDT2D_BATCH_HIP(c, hipEventRecord(c->ev[1], stream));
+
+  ndt2d::SlotVerifyArgs a{};
+  a.source.slots = b.slots;
+  a.source.lookup = b.lookup;
+  a.source.records = b.records;
+  a.jobs = reinterpret_cast<const VerifyJob *>(c->d_stage + off_jobs);
+  a.trig = c->d_stage + off_trig;
+  a.beams_xy = c->d_stage;
+  a.rules = ndt2d::VerifyRules{c->gate_inlier, c->gate_pierce, c->rays ? 1u : 0u};
+  a.records = reinterpret_cast<uint32_t *>(c->d_out);
+  a.beam_m2 = v.beam_m2_out != nullptr ? c->d_out + out.m2 : nullptr;
+  a.beam_cells = v.beam_cells_out != nullptr ? reinterpret_cast<uint32_t *>(c->d_out + out.cells) : nullptr;
+  a.beam_class = v.beam_class_out != nullptr ? reinterpret_cast<uint8_t *>(c->d_out + out.classes) : nullptr;
+  const dim3 blocks(static_cast<uint32_t>(n_jobs)), threads(ndt2d::kVerifyThreads);
+  const bool pow2 = c->chunk_slots[0].grid.pow2 != 0;
+  if (c->verify_cells == 9) ndt2d::launch_slot_verify<9>(pow2, blocks, threads, stream, a);
+  else ndt2d::launch_slot_verify<1>(pow2, blocks, threads, stream, a);
+  NDT2D_BATCH_HIP(c, hipGetLastError());
+  if (c->timing) NDT2D_BATCH_HIP(c, hipEventRecord(c->ev[2], stream));
+  NDT2D_BATCH_HIP(c, hipMemcpyAsync(c->h_out, c->d_out, out.total * sizeof(double), hipMemcpyDeviceToHost, stream));
+  NDT2D_BATCH_HIP(c, hipStreamSynchronize(stream));
+  c->timed = c->timing;
+  const uint32_t * records = reinterpret_cast<const uint32_t *>(c->h_out);
+  const uint8_t * classes = reinterpret_cast<const uint8_t *>(c->h_out + out.classes);
+  size_t at = 0;
+  for (size_t bj = 0; bj < n_jobs; ++bj)
+  {
+    const size_t k = plan.jobs[bj], n = v.beams_of(k), to = c->job_first[k];
+    std::memcpy(v.records_out + k * kVerRec, records + bj * kVerRec, kVerRec * sizeof(uint32_t));
+    if (v.beam_m2_out != nullptr) std::memcpy(v.beam_m2_out + to, c->h_out + out.m2 + at, n * sizeof(double));
+    if (v.beam_cells_out != nullptr) std::memcpy(v.beam_cells_out + 2 * to, c->h_out + out.cells + at, n * 2 * sizeof(uint32_t));
+    if (v.beam_class_out != nullptr) std::memcpy(v.beam_class_out + to, classes + at, n);
+    at += n;
   }
   return NDT2D_OK;
 }
@@ -732,6 +885,147 @@ int ndt2d_closure_refine(ndt2d_closure * c, size_t n_candidates, const size_t * 
        ndt2d::plan_closure_jobs(job_candidate, n_jobs, n_candidates, c->max_candidates, ndt2d::kRefineMaxJobs))
   {
     const int rc = refine_chunk(c, chunk, t, records_out);
+    if (rc != NDT2D_OK) return rc;
+  }
+  return NDT2D_OK;
+  NDT2D_C_CATCH(c)
+}
+
+int ndt2d_closure_set_verify_neighbourhood(ndt2d_closure * c, uint32_t cells)
+{
+  NDT2D_C_TRY
+  if (c == nullptr) return NDT2D_ERR_INVALID;
+  if (cells != 1 && cells != 9)
+  {
+    return batch_fail(c, NDT2D_ERR_INVALID, "ndt2d_closure_set_verify_neighbourhood: " + std::to_string(cells) + " cells (1 or 9)");
+  }
+  c->verify_cells = cells;
+  return NDT2D_OK;
+  NDT2D_C_CATCH(c)
+}
+
+int ndt2d_closure_verify_neighbourhood(ndt2d_closure * c, uint32_t * out)
+{
+  NDT2D_C_TRY
+  if (c == nullptr || out == nullptr) return NDT2D_ERR_INVALID;
+  *out = c->verify_cells;
+  return NDT2D_OK;
+  NDT2D_C_CATCH(c)
+}
+
+int ndt2d_closure_set_verify_gates(ndt2d_closure * c, double gate_inlier, double gate_pierce)
+{
+  NDT2D_C_TRY
+  if (c == nullptr) return NDT2D_ERR_INVALID;
+  if (!(gate_inlier >= 0.0) || !(gate_pierce >= 0.0) || !std::isfinite(gate_inlier) || !std::isfinite(gate_pierce))
+  {
+    return batch_fail(c, NDT2D_ERR_INVALID, "ndt2d_closure_set_verify_gates: a gate is negative or not finite");
+  }
+  c->gate_inlier = gate_inlier;
+  c->gate_pierce = gate_pierce;
+  return NDT2D_OK;
+  NDT2D_C_CATCH(c)
+}
+
+int ndt2d_closure_verify_gates(ndt2d_closure * c, double * gate_inlier_out, double * gate_pierce_out)
+{
+  NDT2D_C_TRY
+  if (c == nullptr || gate_inlier_out == nullptr || gate_pierce_out == nullptr) return NDT2D_ERR_INVALID;
+  *gate_inlier_out = c->gate_inlier;
+  *gate_pierce_out = c->gate_pierce;
+  return NDT2D_OK;
+  NDT2D_C_CATCH(c)
+}
+
+int ndt2d_closure_set_verify_rays(ndt2d_closure * c, int enabled)
+{
+  NDT2D_C_TRY
+  if (c == nullptr) return NDT2D_ERR_INVALID;
+  if (enabled != 0 && enabled != 1)
+  {
+    return batch_fail(c, NDT2D_ERR_INVALID, "ndt2d_closure_set_verify_rays: " + std::to_string(enabled) + " (0 or 1)");
+  }
+  c->rays = enabled != 0;
+  return NDT2D_OK;
+  NDT2D_C_CATCH(c)
+}
+
+int ndt2d_closure_verify_rays(ndt2d_closure * c, int * out)
+{
+  NDT2D_C_TRY
+  if (c == nullptr || out == nullptr) return NDT2D_ERR_INVALID;
+  *out = c->rays ? 1 : 0;
+  return NDT2D_OK;
+  NDT2D_C_CATCH(c)
+}
+
+int ndt2d_closure_verify(ndt2d_closure * c, size_t n_candidates, const size_t * cand_offsets, const size_t * ids,
+                         const double * poses_xyt, double ndt_resolution, double range_max, const double * jobs_xyt,
+                         const uint32_t * job_scan, const uint32_t * job_candidate, size_t n_jobs, const double * beams_xy,
+                         const size_t * beam_offsets, size_t n_scans, uint32_t * records_out, uint8_t * beam_class_out,
+                         double * beam_m2_out, uint32_t * beam_cells_out)
+{
+  NDT2D_C_TRY
+  if (c == nullptr) return NDT2D_ERR_INVALID;
+  if (n_jobs == 0) return NDT2D_OK;
+  if (cand_offsets == nullptr || ids == nullptr || poses_xyt == nullptr || jobs_xyt == nullptr || records_out == nullptr ||
+      beams_xy == nullptr || beam_offsets == nullptr)
+  {
+    return batch_fail(c, NDT2D_ERR_INVALID, "ndt2d_closure_verify: null argument");
+  }
+  if (!(ndt_resolution > 0.0) || !std::isfinite(ndt_resolution) || !std::isfinite(range_max))
+  {
+    return batch_fail(c, NDT2D_ERR_INVALID, "ndt2d_closure_verify: bad resolution or range_max");
+  }
+  if (n_candidates >= (1u << 24)) return batch_fail(c, NDT2D_ERR_INVALID, "ndt2d_closure_verify: bad argument (n_candidates)");
+  if (job_candidate == nullptr && n_candidates != n_jobs)
+  {
+    return batch_fail(c, NDT2D_ERR_INVALID,
+                      "ndt2d_closure_verify: bad argument (no job_candidate: job k uses candidate k, n_candidates must equal n_jobs)");
+  }
+  // every scan, every job and every candidate are checked before anything is launched: what
+  // ndt2d_verify_run refuses (one text: batch/ndt2d_refine_jobs.h; the registration's rules are not
+  // this call's: given as ones it takes), what ndt2d_closure_match does
+  const std::string refusal =
+    ndt2d::refine_jobs::refusal("ndt2d_closure_verify", jobs_xyt, job_scan, n_jobs, beam_offsets, n_scans, 1u, 0.0, 0.0);
+  if (!refusal.empty()) return batch_fail(c, NDT2D_ERR_INVALID, refusal);
+  const int crc = check_candidates(c, "ndt2d_closure_verify", n_candidates, cand_offsets, ids, poses_xyt, ndt_resolution, range_max);
+  if (crc != NDT2D_OK) return crc;
+  for (size_t k = 0; k < n_jobs && job_candidate != nullptr; ++k)
+  {
+    if (job_candidate[k] >= n_candidates)
+    {
+      return batch_fail(c, NDT2D_ERR_INVALID, "ndt2d_closure_verify: job " + std::to_string(k) + ": candidate " +
+                                             std::to_string(job_candidate[k]) + " of " + std::to_string(n_candidates));
+    }
+  }
+  for (size_t k = 0; k < n_candidates && c->rays; ++k)
+  {
+    const GridDesc & g = c->slots[k].grid;
+    if (g.size_x > ndt2d::verify::kMaxGridSide || g.size_y > ndt2d::verify::kMaxGridSide)
+    {
+      return batch_fail(c, NDT2D_ERR_INVALID,
+                        "ndt2d_closure_verify: candidate " + std::to_string(k) + ": a grid side above 2^24 cells (rays enabled)");
+    }
+  }
+  NDT2D_BATCH_HIP(c, hipSetDevice(c->device));
+  const SlotVerifyCall t{cand_offsets, ids, poses_xyt,
+                         {jobs_xyt, job_scan, n_jobs, beams_xy, beam_offsets, n_scans, records_out, beam_class_out, beam_m2_out,
+                          beam_cells_out}};
+  // job k's beams start at the sum of the earlier jobs' scan lengths
+  c->job_first.resize(n_jobs + 1);
+  c->job_beams.resize(n_jobs);
+  c->job_first[0] = 0;
+  for (size_t k = 0; k < n_jobs; ++k)
+  {
+    c->job_beams[k] = t.v.beams_of(k);
+    c->job_first[k + 1] = c->job_first[k] + c->job_beams[k];
+  }
+  for (const ndt2d::ClosureJobChunk & chunk :
+       ndt2d::plan_closure_jobs(job_candidate, n_jobs, n_candidates, c->max_candidates, ndt2d::kVerifyMaxJobs, c->job_beams.data(),
+                                ndt2d::kVerifyChunkBeams))
+  {
+    const int rc = verify_chunk(c, chunk, t);
     if (rc != NDT2D_OK) return rc;
   }
   return NDT2D_OK;

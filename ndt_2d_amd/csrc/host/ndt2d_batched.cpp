@@ -4,7 +4,8 @@
 // the records of all slots, and hands them to finish_slots(), the tail they share -- and the Newton
 // registration of K (scan, pose) jobs (refine_scans), one call of the object under csrc/refine, and
 // the same on each loop-closure candidate's own map (refine_candidates), one call of the closure object,
-// and the match verification of K (scan, pose) jobs (verify_scans), one call of the object under csrc/verify.
+// and the match verification of K (scan, pose) jobs (verify_scans), one call of the object under csrc/verify,
+// and the same on each loop-closure candidate's own map (verify_candidates), one call of the closure object.
 #include <cstring>
 #include <functional>
 #include <string>
@@ -147,6 +148,26 @@ int check_refine_input(ndt2d_matcher * m, const std::string & who, const double 
   return NDT2D_OK;
 }
 
+// What refine_candidates and verify_candidates refuse about the jobs' candidates; `who` names the call.
+int check_job_candidates(ndt2d_matcher * m, const std::string & who, const uint32_t * job_candidate, size_t n_jobs,
+                         size_t n_candidates)
+{
+  if (job_candidate == nullptr && n_candidates != n_jobs)
+  {
+    return mfail(m, NDT2D_ERR_INVALID, who + ": no job_candidate (job k uses candidate k): n_candidates must equal n_jobs");
+  }
+  for (size_t k = 0; k < n_jobs && job_candidate != nullptr; ++k)
+  {
+    if (job_candidate[k] >= n_candidates)
+    {
+      return mfail(m, NDT2D_ERR_INVALID, who + ": job " + std::to_string(k) + ": candidate " + std::to_string(job_candidate[k]) +
+                                             " of " + std::to_string(n_candidates));
+    }
+  }
+  if (m->stores.size() != m->devs.size()) return mfail(m, NDT2D_ERR_INVALID, who + ": candidate 0: unknown scan id (no scan is stored)");
+  return NDT2D_OK;
+}
+
 // `if (!ndt_) return 0.0;` (src/scan_matcher_ndt.cpp:159), and a scan without points: nothing
 // scores, the job keeps its pose
 void fill_no_overlap(const double * jobs_xyt, size_t n_jobs, const RefineOut & o)
@@ -204,6 +225,23 @@ void collect_refine_batch(size_t max_beams, const double * jobs_xyt, const uint3
     b.scan.push_back(sent[sc]);
     b.xyt.insert(b.xyt.end(), jobs_xyt + 3 * k, jobs_xyt + 3 * k + 3);
   }
+}
+
+// Where each job's beams start in a verification's per-beam arrays ([n_jobs + 1]): the batch's jobs
+// in order, the jobs of scans without points between them with no beams.
+void fill_verify_offsets(const RefineBatch & b, size_t n_jobs, size_t * beam_offsets_out)
+{
+  size_t at = 0, j = 0;
+  for (size_t k = 0; k < n_jobs; ++k)
+  {
+    beam_offsets_out[k] = at;
+    if (j < b.job.size() && b.job[j] == k)
+    {
+      at += b.beam_offsets[b.scan[j] + 1] - b.beam_offsets[b.scan[j]];
+      ++j;
+    }
+  }
+  beam_offsets_out[n_jobs] = at;
 }
 
 // The device call's records ([batch job][NDT2D_REFINE_RECORD_DOUBLES]) into the outputs of their jobs.
@@ -632,20 +670,7 @@ int ndt2d_matcher_verify_scans(ndt2d_matcher * m, const double * jobs_xyt, const
                                            std::to_string(n_beams_all));
   }
   std::memset(records_out, 0, n_jobs * NDT2D_VERIFY_RECORD_U32 * sizeof(uint32_t));
-  if (beam_offsets_out != nullptr)
-  {
-    size_t at = 0, j = 0;
-    for (size_t k = 0; k < n_jobs; ++k)
-    {
-      beam_offsets_out[k] = at;
-      if (j < n_batch && batch.job[j] == k)
-      {
-        at += batch.beam_offsets[batch.scan[j] + 1] - batch.beam_offsets[batch.scan[j]];
-        ++j;
-      }
-    }
-    beam_offsets_out[n_jobs] = at;
-  }
+  if (beam_offsets_out != nullptr) fill_verify_offsets(batch, n_jobs, beam_offsets_out);
   if (n_batch == 0) return NDT2D_OK;
   discard_ahead(m);   // a search launched ahead by scoreScan is waited out and dropped
   if (m->verify == nullptr)
@@ -760,22 +785,8 @@ int ndt2d_matcher_refine_candidates(ndt2d_matcher * m, const size_t * cand_offse
   int rc = check_refine_input(m, "refine_candidates", jobs_xyt, job_scan, n_jobs, points_xy, point_offsets, n_scans, max_evals,
                               tol_lin, tol_ang);
   if (rc != NDT2D_OK) return rc;
-  if (job_candidate == nullptr && n_candidates != n_jobs)
-  {
-    return mfail(m, NDT2D_ERR_INVALID, "refine_candidates: no job_candidate (job k uses candidate k): n_candidates must equal n_jobs");
-  }
-  for (size_t k = 0; k < n_jobs && job_candidate != nullptr; ++k)
-  {
-    if (job_candidate[k] >= n_candidates)
-    {
-      return mfail(m, NDT2D_ERR_INVALID, "refine_candidates: job " + std::to_string(k) + ": candidate " +
-                                             std::to_string(job_candidate[k]) + " of " + std::to_string(n_candidates));
-    }
-  }
-  if (m->stores.size() != m->devs.size())
-  {
-    return mfail(m, NDT2D_ERR_INVALID, "refine_candidates: candidate 0: unknown scan id (no scan is stored)");
-  }
+  rc = check_job_candidates(m, "refine_candidates", job_candidate, n_jobs, n_candidates);
+  if (rc != NDT2D_OK) return rc;
   const RefineOut out = {poses_out, scores_out, start_scores_out, gradients_out, hessians_out, status_out, evals_out};
   discard_ahead(m);   // a search launched ahead by scoreScan is waited out and dropped
   if (m->closure == nullptr)
@@ -809,6 +820,81 @@ int ndt2d_matcher_refine_candidates(ndt2d_matcher * m, const size_t * cand_offse
   if (rc != NDT2D_OK) return mfail(m, rc, std::string("refine_candidates: ") + ndt2d_closure_last_error(m->closure));
   fill_no_overlap(jobs_xyt, n_jobs, out);   // (the jobs of a scan without points keep this)
   deal_refine_records(batch, m->refine_records.data(), out);
+  return NDT2D_OK;
+  NDT2D_C_CATCH(m)
+}
+
+int ndt2d_matcher_verify_candidates(ndt2d_matcher * m, const size_t * cand_offsets, const size_t * ids,
+                                    const double * poses_xyt, size_t n_candidates, const double * jobs_xyt,
+                                    const uint32_t * job_scan, const uint32_t * job_candidate, size_t n_jobs,
+                                    const double * points_xy, const size_t * point_offsets, size_t n_scans, size_t max_beams,
+                                    uint32_t * records_out, size_t * beam_offsets_out, uint8_t * beam_class_out,
+                                    double * beam_m2_out, uint32_t * beam_cells_out, size_t beam_cap)
+{
+  NDT2D_C_TRY
+  if (m == nullptr) return NDT2D_ERR_INVALID;
+  if (n_jobs == 0)
+  {
+    if (beam_offsets_out != nullptr) beam_offsets_out[0] = 0;
+    return NDT2D_OK;
+  }
+  if (jobs_xyt == nullptr || records_out == nullptr || point_offsets == nullptr || cand_offsets == nullptr || ids == nullptr ||
+      poses_xyt == nullptr)
+  {
+    return mfail(m, NDT2D_ERR_INVALID, "verify_candidates: null input");
+  }
+  if (n_candidates == 0 || n_candidates > (1u << 20)) return mfail(m, NDT2D_ERR_INVALID, "verify_candidates: no candidates, or too many");
+  // (the registration's rules are not this call's: given as ones it takes)
+  int rc = check_refine_input(m, "verify_candidates", jobs_xyt, job_scan, n_jobs, points_xy, point_offsets, n_scans, 1u, 0.0, 0.0);
+  if (rc != NDT2D_OK) return rc;
+  rc = check_job_candidates(m, "verify_candidates", job_candidate, n_jobs, n_candidates);
+  if (rc != NDT2D_OK) return rc;
+  RefineBatch batch;
+  collect_refine_batch(max_beams, jobs_xyt, job_scan, n_jobs, points_xy, point_offsets, n_scans, batch);
+  const size_t n_batch = batch.job.size();
+  size_t n_beams_all = 0;
+  for (size_t j = 0; j < n_batch; ++j) n_beams_all += batch.beam_offsets[batch.scan[j] + 1] - batch.beam_offsets[batch.scan[j]];
+  const bool want_beams = beam_class_out != nullptr || beam_m2_out != nullptr || beam_cells_out != nullptr;
+  if (want_beams && beam_cap < n_beams_all)
+  {
+    return mfail(m, NDT2D_ERR_INVALID, "verify_candidates: the per-beam arrays hold " + std::to_string(beam_cap) +
+                                           " beams, the jobs have " + std::to_string(n_beams_all));
+  }
+  std::vector<uint32_t> records(n_batch * NDT2D_VERIFY_RECORD_U32);
+  if (n_batch != 0)
+  {
+    discard_ahead(m);   // a search launched ahead by scoreScan is waited out and dropped
+    if (m->closure == nullptr)
+    {
+      rc = ndt2d_closure_create(m->dev, m->stores[0], kClosureSlots, &m->closure);
+      if (rc != NDT2D_OK) return dev_fail(m, rc, "ndt2d_closure_create");
+    }
+    if (ndt2d_closure_set_verify_neighbourhood(m->closure, m->verify_cells) != NDT2D_OK ||
+        ndt2d_closure_set_verify_gates(m->closure, m->verify_gate_inlier, m->verify_gate_pierce) != NDT2D_OK ||
+        ndt2d_closure_set_verify_rays(m->closure, m->verify_rays ? 1 : 0) != NDT2D_OK)
+    {
+      return mfail(m, NDT2D_ERR_INTERNAL, std::string("verify_candidates: ") + ndt2d_closure_last_error(m->closure));
+    }
+    std::vector<uint32_t> batch_candidate(n_batch);
+    for (size_t j = 0; j < n_batch; ++j) batch_candidate[j] = job_candidate != nullptr ? job_candidate[batch.job[j]] : batch.job[j];
+    rc = ndt2d_scanstore_set_eigenvalue_form(m->stores[0], eigen_form_name(m));
+    if (rc == NDT2D_OK)
+    {
+      // (the per-beam arrays are the batch's, job after job: a job without beams takes no room in them)
+      rc = ndt2d_closure_verify(m->closure, n_candidates, cand_offsets, ids, poses_xyt, m->resolution, m->range_max, batch.xyt.data(),
+                                batch.scan.data(), batch_candidate.data(), n_batch, batch.beams.data(), batch.beam_offsets.data(),
+                                batch.beam_offsets.size() - 1, records.data(), beam_class_out, beam_m2_out, beam_cells_out);
+    }
+    // (a refused call -- a candidate the closure does not take -- leaves the outputs as they were)
+    if (rc != NDT2D_OK) return mfail(m, rc, std::string("verify_candidates: ") + ndt2d_closure_last_error(m->closure));
+  }
+  std::memset(records_out, 0, n_jobs * NDT2D_VERIFY_RECORD_U32 * sizeof(uint32_t));   // (the jobs of a scan without points keep this)
+  if (beam_offsets_out != nullptr) fill_verify_offsets(batch, n_jobs, beam_offsets_out);
+  for (size_t j = 0; j < n_batch; ++j)
+  {
+    std::memcpy(records_out + static_cast<size_t>(batch.job[j]) * NDT2D_VERIFY_RECORD_U32, records.data() + j * NDT2D_VERIFY_RECORD_U32,
+                NDT2D_VERIFY_RECORD_U32 * sizeof(uint32_t));
+  }
   return NDT2D_OK;
   NDT2D_C_CATCH(m)
 }

@@ -24,7 +24,9 @@
 // The map is a template argument of the kernel, as of refine_kernel: a SOURCE gives, for the slot
 // a job's record names, the GridDesc of that job's map and its map object (find(cell, rank) /
 // record(rank)); both are uniform over the block.  InstalledSource, here, is the grid installed in
-// the context: one grid for all jobs.  It is the only instantiation.
+// the context: one grid for all jobs.  closure/ndt2d_closure.hip defines NDT2D_VERIFY_KERNEL_ONLY
+// and includes this file for its device half -- the kernel and the layout of what comes back --
+// to instantiate the kernel on its candidate slots (SlotSource): one text for both.
 //
 // The beams are read from the chunk's upload, once each.  LDS holds the waves' counters only.
 //
@@ -97,15 +99,6 @@ struct VerifyArgs
   uint8_t * beam_class;
   double * beam_m2;
   uint32_t * beam_cells;      // [.][2]
-};
-
-// SOURCE of the grid installed in the context: one grid for all jobs, a cell is its own record.
-// (refine/ndt2d_refine.hip keeps its own: that unit's text is pinned by its tests.)
-struct InstalledSource
-{
-  GridDesc g;   // geometry, cells_global, occ_bits
-  __device__ __forceinline__ const GridDesc & grid(uint32_t) const { return g; }
-  __device__ __forceinline__ InstalledMap map(uint32_t) const { return InstalledMap{g.occ_bits, g.cells_global}; }
 };
 
 // m2 = d^T I d of the point against the record: -2 x Cell::score's exponent (I = -2 h exactly).
@@ -255,38 +248,7 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_kernel(const VerifyArgs
   }
 }
 
-}  // namespace
-
-}  // namespace ndt2d
-
-// ---- the installed grid: the object and the C entry points ----
-
-struct ndt2d_verify : ndt2d::BatchHost
-{
-  size_t max_jobs = 0;                // slots of a chunk
-  uint32_t cells = 1;                 // the neighbourhood of a point: 1 (its own cell) or 9 (the 3 x 3 round it)
-  double gate_inlier = 9.0, gate_pierce = 1.0;
-  bool rays = true;
-  std::vector<uint64_t> scan_first;   // scan -> its first beam within the chunk's beams (or: not sent)
-  std::vector<uint32_t> sent;         // the chunk's scans in upload order
-  std::vector<size_t> job_first;      // job of the call -> its first beam within the caller's per-beam arrays
-};
-
-namespace ndt2d
-{
-
-namespace
-{
-
-using InstalledVerifyArgs = VerifyArgs<InstalledSource>;
-
-// CELLS: the neighbourhood of a point, 1 or 9.
-template <uint32_t CELLS>
-void launch_verify(bool pow2, dim3 blocks, dim3 threads, hipStream_t stream, const InstalledVerifyArgs & a)
-{
-  if (pow2) hipLaunchKernelGGL((verify_kernel<true, CELLS, InstalledSource>), blocks, threads, 0, stream, a);
-  else hipLaunchKernelGGL((verify_kernel<false, CELLS, InstalledSource>), blocks, threads, 0, stream, a);
-}
+// ---- what every call of the kernel shares on the host ----
 
 struct VerifyCall
 {
@@ -319,6 +281,51 @@ VerifyOutLayout verify_out_layout(size_t n_slots, size_t n_out, const VerifyCall
   l.classes = l.cells + (t.beam_cells_out != nullptr ? n_out : 0);
   l.total = l.classes + (t.beam_class_out != nullptr ? (n_out + 7) / 8 : 0);
   return l;
+}
+
+}  // namespace
+
+}  // namespace ndt2d
+
+// ---- the installed grid: the object and the C entry points ----
+
+#ifndef NDT2D_VERIFY_KERNEL_ONLY
+
+struct ndt2d_verify : ndt2d::BatchHost
+{
+  size_t max_jobs = 0;                // slots of a chunk
+  uint32_t cells = 1;                 // the neighbourhood of a point: 1 (its own cell) or 9 (the 3 x 3 round it)
+  double gate_inlier = 9.0, gate_pierce = 1.0;
+  bool rays = true;
+  std::vector<uint64_t> scan_first;   // scan -> its first beam within the chunk's beams (or: not sent)
+  std::vector<uint32_t> sent;         // the chunk's scans in upload order
+  std::vector<size_t> job_first;      // job of the call -> its first beam within the caller's per-beam arrays
+};
+
+namespace ndt2d
+{
+
+namespace
+{
+
+// SOURCE of the grid installed in the context: one grid for all jobs, a cell is its own record.
+// (Behind the guard: refine/ndt2d_refine.hip has one of the same name in its device half, and the
+// closure's unit includes both halves.)
+struct InstalledSource
+{
+  GridDesc g;   // geometry, cells_global, occ_bits
+  __device__ __forceinline__ const GridDesc & grid(uint32_t) const { return g; }
+  __device__ __forceinline__ InstalledMap map(uint32_t) const { return InstalledMap{g.occ_bits, g.cells_global}; }
+};
+
+using InstalledVerifyArgs = VerifyArgs<InstalledSource>;
+
+// CELLS: the neighbourhood of a point, 1 or 9.
+template <uint32_t CELLS>
+void launch_verify(bool pow2, dim3 blocks, dim3 threads, hipStream_t stream, const InstalledVerifyArgs & a)
+{
+  if (pow2) hipLaunchKernelGGL((verify_kernel<true, CELLS, InstalledSource>), blocks, threads, 0, stream, a);
+  else hipLaunchKernelGGL((verify_kernel<false, CELLS, InstalledSource>), blocks, threads, 0, stream, a);
 }
 
 // Jobs [k0, k1) of a call whose arguments have been checked; they hold n_out beams.
@@ -552,3 +559,5 @@ int ndt2d_verify_run(ndt2d_verify * v, const double * jobs_xyt, const uint32_t *
 }
 
 }  // extern "C"
+
+#endif  // NDT2D_VERIFY_KERNEL_ONLY: the object and the entry points of the installed grid

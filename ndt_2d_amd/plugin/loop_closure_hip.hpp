@@ -18,6 +18,12 @@
 // covariance from the Hessian there -- what the constraint of :658 wants -- and the scan goes on
 // from the refined pose where the iteration converged (or ran out of evaluations) without raising f.
 //
+// setVerify() adds the match verification on each candidate's OWN map: every round makes one
+// ndt2d_matcher_verify_candidates call for the candidates that pass the accept test, each at the
+// pose the walk would adopt for it (the refined pose where it is usable, the lattice pose
+// otherwise); the accepted closure gains the counts.  A verdict, no policy: the walk, the closures
+// and the scan's pose are what they are without it.
+//
 // Plain arrays over the C-ABI, as the other mirrors in this directory: nothing of ROS or Eigen.
 #ifndef NDT_2D_HIP__LOOP_CLOSURE_HIP_HPP_
 #define NDT_2D_HIP__LOOP_CLOSURE_HIP_HPP_
@@ -47,6 +53,11 @@ struct LoopClosure
   double refined_covariance[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // row-major; valid with has_refined_covariance
   bool has_refined_covariance = false;        // the Hessian at refined_pose is positive definite
   int refine_status = NDT2D_REFINE_NO_OVERLAP;   // NDT2D_REFINE_*
+  // with setVerify(): the match verification on the candidate's own map, at verified_pose
+  bool verified = false;
+  double verified_pose[3] = {0.0, 0.0, 0.0};   // absolute: the pose the walk adopted
+  // {n_beams, n_off, n_unseen, n_outlier, n_inlier, n_pierced, n_walked, 0}
+  std::uint32_t verify[NDT2D_VERIFY_RECORD_U32] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
 };
 
 class LoopClosureHip
@@ -81,6 +92,22 @@ public:
     return true;
   }
   void clearRefine() { refine_ = false; }
+
+  // From the next closeLoops() on, verify the accepted candidates (see above).  max_beams: 0 takes
+  // every point of the scan, otherwise the subsampling rule of matchScan (the matcher's
+  // laser_max_beams: the beams the score was computed from); cells: 1 or 9; the gates and the ray
+  // walk: ndt2d_verify's rules.  They are the matcher's verify parameters: verify_scans calls on the
+  // same matcher take them too.  false: a parameter is refused (last_error()).
+  bool setVerify(std::size_t max_beams, std::uint32_t cells, double gate_inlier, double gate_pierce, bool rays)
+  {
+    if (!ok(ndt2d_matcher_set_verify_neighbourhood(m_, cells))) return false;
+    if (!ok(ndt2d_matcher_set_verify_gates(m_, gate_inlier, gate_pierce))) return false;
+    if (!ok(ndt2d_matcher_set_verify_rays(m_, rays ? 1 : 0))) return false;
+    verify_ = true;
+    verify_max_beams_ = max_beams;
+    return true;
+  }
+  void clearVerify() { verify_ = false; }
 
   // [begin_idx, end_idx) of src/ndt_mapper.cpp:628-631, quirk included: the candidate
   // i == rolling yields only scan i - 1.
@@ -144,6 +171,7 @@ public:
       }
       if (accepted == K) break;
       if (refine_ && !refineRound(scan_pose_inout, points_xy, n_points, K)) return false;
+      if (verify_ && !verifyRound(scan_pose_inout, points_xy, n_points, K)) return false;
       LoopClosure c;
       c.candidate = todo[accepted];
       c.score = scores_[accepted];
@@ -165,11 +193,17 @@ public:
         const double * h = r_hessians_.data();
         const double sum_hessian[6] = {h[0] * n, h[1] * n, h[2] * n, h[4] * n, h[5] * n, h[8] * n};
         c.has_refined_covariance = r_evals_[0] > 0 && ndt2d_refine_covariance(sum_hessian, c.refined_covariance) == NDT2D_OK;
-        const bool usable = c.refine_status == NDT2D_REFINE_CONVERGED || c.refine_status == NDT2D_REFINE_MAX_EVALS;
-        if (usable && r_scores_[0] <= r_start_scores_[0])
+        if (refineUsable(0))
         {
           for (int d = 0; d < 3; ++d) scan_pose_inout[d] = c.refined_pose[d];
         }
+      }
+      if (verify_)
+      {
+        // (job 0 of the round's verification, likewise)
+        c.verified = true;
+        for (int d = 0; d < 3; ++d) c.verified_pose[d] = v_jobs_[d];
+        for (int d = 0; d < NDT2D_VERIFY_RECORD_U32; ++d) c.verify[d] = v_records_[static_cast<std::size_t>(d)];
       }
       closures_out.push_back(c);
       todo.erase(todo.begin(), todo.begin() + static_cast<std::ptrdiff_t>(accepted) + 1);
@@ -211,6 +245,35 @@ private:
                                               r_hessians_.data(), r_status_.data(), r_evals_.data()));
   }
 
+  // The walk adopts job j's refined pose: the registration ended in order and f did not rise.
+  bool refineUsable(std::size_t j) const
+  {
+    const bool ended = r_status_[j] == NDT2D_REFINE_CONVERGED || r_status_[j] == NDT2D_REFINE_MAX_EVALS;
+    return ended && r_scores_[j] <= r_start_scores_[j];
+  }
+
+  // One ndt2d_matcher_verify_candidates call for the candidates of the round that passed
+  // (passing_), each at the pose the walk would adopt for it, all on the one scan.
+  bool verifyRound(const double * scan_pose, const double * points_xy, std::size_t n_points, std::size_t K)
+  {
+    const std::size_t n_jobs = passing_.size();
+    v_jobs_.resize(3 * n_jobs);
+    for (std::size_t j = 0; j < n_jobs; ++j)
+    {
+      const bool refined = refine_ && refineUsable(j);
+      for (int d = 0; d < 3; ++d)
+      {
+        v_jobs_[3 * j + d] = refined ? r_poses_[3 * j + d] : corrections_[3 * passing_[j] + d] + scan_pose[d];
+      }
+    }
+    r_scan_.assign(n_jobs, 0u);
+    v_records_.assign(NDT2D_VERIFY_RECORD_U32 * n_jobs, 0u);
+    const std::size_t point_offsets[2] = {0, n_points};
+    return ok(ndt2d_matcher_verify_candidates(m_, offsets_.data(), ids_.data(), poses_.data(), K, v_jobs_.data(), r_scan_.data(),
+                                              passing_.data(), n_jobs, points_xy, point_offsets, 1, verify_max_beams_,
+                                              v_records_.data(), nullptr, nullptr, nullptr, nullptr, 0));
+  }
+
   bool ok(int rc)
   {
     if (rc == NDT2D_OK) return true;
@@ -230,6 +293,11 @@ private:
   std::vector<std::uint32_t> passing_, r_scan_, r_evals_;
   std::vector<std::int32_t> r_status_;
   std::vector<double> r_jobs_, r_poses_, r_scores_, r_start_scores_, r_hessians_;
+  // setVerify()
+  bool verify_ = false;
+  std::size_t verify_max_beams_ = 0;
+  std::vector<double> v_jobs_;
+  std::vector<std::uint32_t> v_records_;
   std::string error_;
 };
 

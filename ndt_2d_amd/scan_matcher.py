@@ -444,7 +444,8 @@ class ScanMatcherNDT:
         self._batch_set_timing("closure", "matchCandidates", enabled)
 
     def closure_last_ms(self):
-        """(build_ms, search_ms) of the last timed matchCandidates (its last chunk)."""
+        """(build_ms, search_ms) of the last timed matchCandidates (its last chunk); after a
+        refineCandidates or a verifyCandidates: the build and that call's own launch."""
         return self._batch_last_ms("closure")
 
     def matchStarts(self, start_poses, points, want_scores=False):
@@ -601,6 +602,39 @@ class ScanMatcherNDT:
         first piercing cell; _capi.VERIFY_NO_CELL: none) and pierced_mask (bool).
         No NDT in place: Ndt2dError (NDT2D_ERR_NO_GRID).  A scan without points: zeros."""
         self.set_verify(neighbourhood=neighbourhood, gate_inlier=gate_inlier, gate_pierce=gate_pierce, rays=rays)
+        return self._verify_call("verifyScans", jobs, scans, job_scan, max_beams, want_beams,
+                                 lambda job_args, out_args: self._L.ndt2d_matcher_verify_scans(self._m, *job_args, *out_args))
+
+    def verifyCandidates(self, jobs, scans, candidates, job_candidate=None, job_scan=None, max_beams=None, neighbourhood=9,
+                         gate_inlier=9.0, gate_pierce=1.0, rays=True, want_beams=False):
+        """verifyScans of K jobs, each on a loop-closure candidate's OWN map, in one call: `candidates`
+        as matchCandidates takes them (a list of candidate maps, each a list of (stored scan id,
+        pose_xyt)), jobs / scans / job_scan and the keywords as verifyScans takes them,
+        job_candidate[k]: the candidate of job k (None: job k uses candidate k).  Returns the dicts
+        verifyScans returns after reset() / addScansById(candidates[job_candidate[k]]), bit for bit,
+        the per-beam arrays included -- from one upload, one build launch for the candidates named,
+        one launch of the verification and one read-back per chunk.  The NDT in place is not
+        touched: has_ndt() and the grid are the same before and after, and none in place is no
+        error.  A scan without points: zeros.  A verdict, no policy."""
+        self.set_verify(neighbourhood=neighbourhood, gate_inlier=gate_inlier, gate_pierce=gate_pierce, rays=rays)
+        K = len(candidates)
+        offsets = np.zeros(K + 1, dtype=np.uintp)
+        offsets[1:] = np.cumsum([len(c) for c in candidates]) if K else []
+        flat = [entry for c in candidates for entry in c]
+        ids = np.ascontiguousarray([e[0] for e in flat], dtype=np.uintp).reshape(-1)
+        poses = _f64([e[1] for e in flat], (-1, 3)) if flat else np.zeros((0, 3))
+        szp = C.POINTER(C.c_size_t)
+
+        def launch(job_args, out_args):
+            jc = _index_array("verifyCandidates", "job_candidate", "candidate", job_candidate, job_args[2])
+            return self._L.ndt2d_matcher_verify_candidates(
+                self._m, offsets.ctypes.data_as(szp), ids.ctypes.data_as(szp), dptr(poses), K, job_args[0], job_args[1],
+                jc.ctypes.data_as(C.POINTER(C.c_uint32)) if jc is not None else None, *job_args[2:], *out_args)
+        return self._verify_call("verifyCandidates", jobs, scans, job_scan, max_beams, want_beams, launch)
+
+    def _verify_call(self, who, jobs, scans, job_scan, max_beams, want_beams, launch):
+        """The arrays of a verification call, the call (launch(job_args, out_args): the C entry's
+        arguments from jobs_xyt to max_beams, and from records_out on) and its result dicts."""
         jp = _f64(jobs, (-1, 3))
         K = len(jp)
         arrays = [_f64(pts, (-1, 2)) for pts in scans]
@@ -608,12 +642,12 @@ class ScanMatcherNDT:
         if arrays:
             offsets[1:] = np.cumsum([len(a) for a in arrays])
         pts = np.ascontiguousarray(np.concatenate(arrays) if arrays else np.zeros((0, 2)), dtype=np.float64)
-        js = _index_array("verifyScans", "job_scan", "scan", job_scan, K)
+        js = _index_array(who, "job_scan", "scan", job_scan, K)
         if job_scan is None and len(arrays) != K:
-            raise ValueError("verifyScans: without job_scan job k uses scan k: one scan per job")
+            raise ValueError(who + ": without job_scan job k uses scan k: one scan per job")
         limit = int(self.params["laser_max_beams"]) if max_beams is None else int(max_beams)
         if limit < 0:
-            raise ValueError("verifyScans: max_beams must not be negative")
+            raise ValueError(who + ": max_beams must not be negative")
         which = js if js is not None else np.arange(K)
         if K and len(arrays) and np.any(np.asarray(which) >= len(arrays)):
             cap = 0     # (the call refuses the job; nothing is written)
@@ -626,11 +660,12 @@ class ScanMatcherNDT:
         m2 = np.zeros(cap, dtype=np.float64) if want_beams else None
         cells = np.zeros((cap, 2), dtype=np.uint32) if want_beams else None
         u32p, u8p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)
-        self._check(self._L.ndt2d_matcher_verify_scans(
-            self._m, dptr(jp), js.ctypes.data_as(u32p) if js is not None else None, K, dptr(pts),
-            offsets.ctypes.data_as(C.POINTER(C.c_size_t)), len(arrays), limit, records.ctypes.data_as(u32p),
-            table.ctypes.data_as(C.POINTER(C.c_size_t)), classes.ctypes.data_as(u8p) if want_beams else None,
-            dptr(m2) if want_beams else None, cells.ctypes.data_as(u32p) if want_beams else None, cap), "verifyScans")
+        self._check(launch(
+            (dptr(jp), js.ctypes.data_as(u32p) if js is not None else None, K, dptr(pts),
+             offsets.ctypes.data_as(C.POINTER(C.c_size_t)), len(arrays), limit),
+            (records.ctypes.data_as(u32p), table.ctypes.data_as(C.POINTER(C.c_size_t)),
+             classes.ctypes.data_as(u8p) if want_beams else None, dptr(m2) if want_beams else None,
+             cells.ctypes.data_as(u32p) if want_beams else None, cap)), who)
         out = []
         for k in range(K):
             r = records[k]
@@ -1074,8 +1109,13 @@ def loop_closure_window(i, rolling):
     return list(range(begin_idx, end_idx))
 
 
+def _refine_usable(r):
+    """close_loops adopts a refined pose: the registration ended in order and f did not rise."""
+    return r["status"] in (_capi.REFINE_CONVERGED, _capi.REFINE_MAX_EVALS) and r["score"] <= r["start_score"]
+
+
 def close_loops(matcher, scan_pose, points, candidate_indices, graph_poses, rolling, typical_response, limit,
-                scan_sizes=None, refine=None):
+                scan_sizes=None, refine=None, verify=None):
     """The loop-closure thread's walk over one new scan's candidates (reference
     src/ndt_mapper.cpp:619-671) on the batched match.  candidate_indices: what findNearest
     returned, in its order; graph_poses[i]: the pose of graph scan i, which is stored on the
@@ -1101,7 +1141,15 @@ def close_loops(matcher, scan_pose, points, candidate_indices, graph_poses, roll
     accepted candidate as before; its entry gains refined_pose, refined_covariance (None where the
     Hessian is not positive definite) and refine_status (its `pose` stays the lattice pose).  The
     scan's pose -- what the next round starts from, and what is returned -- is the refined pose
-    where the status is CONVERGED or MAX_EVALS and f did not rise, the lattice pose otherwise."""
+    where the status is CONVERGED or MAX_EVALS and f did not rise, the lattice pose otherwise.
+
+    verify: None, or dict(max_beams=..., neighbourhood=..., gate_inlier=..., gate_pierce=..., rays=...)
+    (any subset: verifyCandidates' arguments, as relocalize's `verify`).  With it every round makes
+    ONE verifyCandidates call over the candidates that pass the accept test, each on its own map at
+    the pose the walk would adopt for it -- the refined pose where `refine` is given and usable by
+    the rule above, the lattice pose otherwise.  The accepted entry gains `verify` (the counts) and
+    `verified_pose`.  The walk, the accepted list and the returned pose are what they are without
+    it: a verdict, no policy."""
     pose = np.array(scan_pose, dtype=np.float64).reshape(3).copy()
     todo = []
     for i in candidate_indices:
@@ -1120,6 +1168,16 @@ def close_loops(matcher, scan_pose, points, candidate_indices, graph_poses, roll
             starts = [np.array(results[k]["pose"], dtype=np.float64) + pose for k in passing]
             refined = matcher.refineCandidates(starts, [points], [batch[k] for k in passing], job_scan=[0] * len(passing),
                                                **refine)
+        verdicts = None
+        if verify is not None and passing:
+            adopted = []
+            for n, k in enumerate(passing):
+                at = np.array(results[k]["pose"], dtype=np.float64) + pose
+                if refined is not None and _refine_usable(refined[n]):
+                    at = refined[n]["pose"].copy()
+                adopted.append(at)
+            verdicts = matcher.verifyCandidates(adopted, [points], [batch[k] for k in passing], job_scan=[0] * len(passing),
+                                                **verify)
         rest = []
         for k in passing[:1]:
             i, res = todo[k], results[k]
@@ -1129,8 +1187,10 @@ def close_loops(matcher, scan_pose, points, candidate_indices, graph_poses, roll
             if refined is not None:
                 r = refined[0]
                 entry.update(refined_pose=r["pose"].copy(), refined_covariance=r["covariance"], refine_status=r["status"])
-                if r["status"] in (_capi.REFINE_CONVERGED, _capi.REFINE_MAX_EVALS) and r["score"] <= r["start_score"]:
+                if _refine_usable(r):
                     pose = r["pose"].copy()
+            if verdicts is not None:
+                entry.update(verify=verdicts[0], verified_pose=adopted[0].copy())
             accepted.append(entry)
             rest = todo[k + 1:]
         todo = rest
