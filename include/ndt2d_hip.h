@@ -659,6 +659,118 @@ int ndt2d_closure_verify_gates(ndt2d_closure * closure, double * gate_inlier_out
 int ndt2d_closure_set_verify_rays(ndt2d_closure * closure, int enabled);
 int ndt2d_closure_verify_rays(ndt2d_closure * closure, int * out);
 
+/* ---- Pose graph: optimise scan poses against the constraints, K masks in one launch
+ *      (csrc/posegraph/) ----
+ *
+ * What the loop-closure thread does with its constraints (src/ndt_mapper.cpp:680,
+ * src/ceres_solver.cpp:50-120): move the scan poses so that the relative poses the constraints
+ * measured are met as well as their weights allow.  An object of its own beside the context, as
+ * ndt2d_refine: it launches on the context's current stream and must be destroyed before
+ * ndt2d_destroy(h).  K jobs share one graph; a job is a mask over the constraints (the question
+ * "is this closure consistent with the others?" is the solve with and without it).  One call is ONE
+ * launch of the solver per chunk, a workgroup per job; nothing is asked of the host between the
+ * iterations.  Ceres is not reproduced step by step: the contract is the minimiser and the rules below.
+ *
+ * The problem.  n poses (x, y, theta) and m constraints {begin, end, transform[3], information[9]
+ * row-major}; begin and end index the poses, as scans[constraint->begin] does.  Pose `fixed` is
+ * held (the reference holds scans[0]).
+ *
+ * The residual of a constraint a = begin, b = end with transform t
+ * (include/ndt_2d/ceres_solver_pose.hpp:86-108), R(.) the rotation:
+ *     e_xy    = R(theta_a)^T (p_b - p_a) - t_xy
+ *     e_theta = Normalize((theta_b - theta_a) - t_theta)
+ *     Normalize(v) = v - 2pi floor((v + pi) / 2pi), 2pi formed as 2.0 * pi: into [-pi, pi)
+ *     r = W e
+ * Normalize uses IEEE + - x / and floor only and the unit is compiled without contraction: the
+ * unweighted e_theta has the bits a float64 restatement gives.  cos and sin of theta_a are the
+ * device library's.
+ *
+ * The weighting.  L: the lower Cholesky factor of `information`, computed on the host at upload.
+ *     "reference"    (default) W = L, what src/ceres_solver.cpp:132 passes as the "square root
+ *                    information".  A quirk: the cost is then e^T L^T L e, which is NOT
+ *                    e^T information e (= e^T L L^T e) unless L is diagonal.
+ *     "information"  W = L^T: the cost is e^T information e.
+ * A constraint whose information gives a Cholesky pivot <= 0 or not finite (not symmetric positive
+ * definite as far as the factorisation can tell; Eigen's llt() goes on silently there, and the
+ * zeros of a default-constructed Constraint are such a case) is refused.  Only the lower triangle
+ * is read.
+ *
+ * The cost of a job: F = 1/2 sum |r_c|^2 over its enabled constraints; chi2_c = |r_c|^2.
+ *
+ * The Jacobians are analytic (csrc/posegraph/ndt2d_posegraph_fn.h), with c = cos theta_a,
+ * s = sin theta_a and (ex, ey) = R(theta_a)^T (p_b - p_a):
+ *     A = de/d(pose a) = [-c -s ey; s -c -ex; 0 0 -1]     B = de/d(pose b) = [c s 0; -s c 0; 0 0 1]
+ *
+ * The solver.  Levenberg-Marquardt: each iteration solves (H + lambda D) delta = -g, H = J^T J,
+ * g = J^T r, D = diag(H) clamped to [1e-6, 1e32], by conjugate gradients that never form H, with
+ * the 3 x 3 diagonal blocks of H + lambda D as preconditioner.  The trial point x + delta is
+ * accepted when the gain ratio (F(x) - F(x + delta)) / (model decrease) is above 1e-3 -- or when
+ * |F(x) - F(x + delta)| is below 256 eps F, where the ratio is the rounding of the cost's own sum
+ * and the (positive) model decrease decides.  The damping update, the CG forcing term and the CG
+ * cap are the implementation's (the kernel's head says which).  Stop rules, each evaluated in the
+ * kernel, a tolerance of 0 disables its rule:
+ *     max_iterations          iterations made, accepted or not      NDT2D_POSEGRAPH_MAX_ITERATIONS
+ *     gradient_tolerance      |g|_inf <= it, at the start or after an accepted step
+ *                                                                    NDT2D_POSEGRAPH_CONVERGED_GRADIENT
+ *     function_tolerance      |F_before - F| <= it x F_before after an accepted step
+ *                                                                    NDT2D_POSEGRAPH_CONVERGED_COST
+ *     parameter_tolerance     |delta|_2 <= it x (|x|_2 + it)         NDT2D_POSEGRAPH_CONVERGED_STEP
+ *     a start cost that is not finite: NDT2D_POSEGRAPH_FAILED, the job's start poses are returned.
+ * Ceres's defaults are 100 (src/ceres_solver.cpp:39), 1e-10, 1e-6, 1e-8.
+ *
+ * What a result depends on: the graph, the job's mask and the parameters -- not the other jobs, the
+ * chunking or the run: bit-identical run to run.  No floating-point atomics: a node's sums are
+ * gathers over its incident constraints in ascending constraint index, dot products are reduced in
+ * a fixed tree.  A node with no enabled constraint in a job, and the fixed node, keep their poses
+ * bit for bit.  A component not connected to the fixed pose has no unique minimiser; the damped
+ * system is still definite, and a minimiser is returned.
+ *
+ *   create     max_nodes (1 .. 2^30), max_constraints (0 .. 2^30), max_jobs (1 .. 65,535: jobs of
+ *              one chunk; more are processed in chunks inside the call, which changes no output).
+ *   set_graph  Refused with NDT2D_ERR_INVALID before anything changes, the message names the
+ *              index: n == 0 (the reference returns false for no scans), sizes beyond the
+ *              capacities, fixed >= n, a non-finite pose ("pose i"), and per constraint
+ *              ("constraint c") an index out of range, begin == end, a non-finite transform or
+ *              information, an information that is not positive definite.  A refused graph leaves
+ *              the one in place.  m == 0 or n == 1 is legal: nothing moves, CONVERGED_GRADIENT.
+ *   set_weighting / weighting   "reference" or "information"; anything else: NDT2D_ERR_INVALID.
+ *   evaluate   enabled[K][m] bytes (non-zero: on) or NULL for every constraint on; at the graph's
+ *              poses: cost_out[K]; optional chi2_out[K][m] and residuals_out[K][m][6] = e then r,
+ *              of every constraint, enabled or not (the mask selects what F sums).
+ *   solve      poses_out[K][n][3]; records_out[K][NDT2D_POSEGRAPH_RECORD_DOUBLES] = {status,
+ *              iterations, cg_iterations, initial_cost, final_cost, final |g|_inf}; optional
+ *              chi2_out[K][2][m]: every constraint's chi2 at the start and at the job's final poses
+ *              (a switched-off closure's chi2 against the others' solution is the verdict on it;
+ *              no policy is applied).  initial_cost is evaluate's F bit for bit.
+ *              n_jobs == 0: NDT2D_OK, nothing done.  Before set_graph: NDT2D_ERR_STATE.  A negative
+ *              or non-finite tolerance: NDT2D_ERR_INVALID.
+ *   set_timing / last_ms   HIP events around the kernel launches and the read-back of the last
+ *              (chunk of a) call, off by default. */
+#define NDT2D_POSEGRAPH_RECORD_DOUBLES 6
+#define NDT2D_POSEGRAPH_CONVERGED_GRADIENT 0
+#define NDT2D_POSEGRAPH_CONVERGED_COST 1
+#define NDT2D_POSEGRAPH_CONVERGED_STEP 2
+#define NDT2D_POSEGRAPH_MAX_ITERATIONS 3
+#define NDT2D_POSEGRAPH_FAILED 4
+typedef struct ndt2d_posegraph ndt2d_posegraph;
+int ndt2d_posegraph_create(ndt2d_handle h, size_t max_nodes, size_t max_constraints, size_t max_jobs,
+                           ndt2d_posegraph ** out);
+int ndt2d_posegraph_destroy(ndt2d_posegraph * posegraph);
+const char * ndt2d_posegraph_last_error(ndt2d_posegraph * posegraph);
+int ndt2d_posegraph_set_graph(ndt2d_posegraph * posegraph, const double * poses_xyt, size_t n,
+                              const uint32_t * begin, const uint32_t * end, const double * transform,
+                              const double * information, size_t m, size_t fixed);
+int ndt2d_posegraph_set_weighting(ndt2d_posegraph * posegraph, const char * weighting);
+const char * ndt2d_posegraph_weighting(ndt2d_posegraph * posegraph);
+int ndt2d_posegraph_evaluate(ndt2d_posegraph * posegraph, const uint8_t * enabled, size_t n_jobs,
+                             double * cost_out, double * chi2_out, double * residuals_out);
+int ndt2d_posegraph_solve(ndt2d_posegraph * posegraph, const uint8_t * enabled, size_t n_jobs,
+                          uint32_t max_iterations, double gradient_tolerance,
+                          double function_tolerance, double parameter_tolerance, double * poses_out,
+                          double * records_out, double * chi2_out);
+int ndt2d_posegraph_set_timing(ndt2d_posegraph * posegraph, int enabled);
+int ndt2d_posegraph_last_ms(ndt2d_posegraph * posegraph, float * kernel_ms, float * fetch_ms);
+
 /* Upload the beam endpoints of one scan, robot frame, already subsampled to
  * min(laser_max_beams, points.size()) points by the caller
  * (src/scan_matcher_ndt.cpp:95-96,110 / :165-166,171).  Beams are taken as given: finite,

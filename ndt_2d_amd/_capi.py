@@ -28,6 +28,10 @@ BEAM_OFF, BEAM_UNSEEN, BEAM_OUTLIER, BEAM_INLIER = range(4)
 BEAM_PIERCED = 4
 VERIFY_RECORD_U32 = 8
 VERIFY_NO_CELL = 0xFFFFFFFF
+# NDT2D_POSEGRAPH_*: how a pose-graph job stopped; the doubles of its record
+POSEGRAPH_CONVERGED_GRADIENT, POSEGRAPH_CONVERGED_COST, POSEGRAPH_CONVERGED_STEP, POSEGRAPH_MAX_ITERATIONS, POSEGRAPH_FAILED = range(5)
+POSEGRAPH_STATUS_NAMES = ("converged_gradient", "converged_cost", "converged_step", "max_iterations", "failed")
+POSEGRAPH_RECORD_DOUBLES = 6
 MATCH_RECORD_DOUBLES = 12
 POSE_STATS_DOUBLES = 8
 PF_RESULT_DOUBLES = 8
@@ -168,6 +172,16 @@ SIGNATURES = {
     "ndt2d_verify_rays": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "ndt2d_verify_set_timing": (C.c_int, [_vp, C.c_int]),
     "ndt2d_verify_last_ms": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "ndt2d_posegraph_create": (C.c_int, [_vp, _sz, _sz, _sz, C.POINTER(_vp)]),
+    "ndt2d_posegraph_destroy": (C.c_int, [_vp]),
+    "ndt2d_posegraph_last_error": (C.c_char_p, [_vp]),
+    "ndt2d_posegraph_set_graph": (C.c_int, [_vp, _dp, _sz, C.POINTER(_u32), C.POINTER(_u32), _dp, _dp, _sz, _sz]),
+    "ndt2d_posegraph_set_weighting": (C.c_int, [_vp, C.c_char_p]),
+    "ndt2d_posegraph_weighting": (C.c_char_p, [_vp]),
+    "ndt2d_posegraph_evaluate": (C.c_int, [_vp, C.POINTER(C.c_uint8), _sz, _dp, _dp, _dp]),
+    "ndt2d_posegraph_solve": (C.c_int, [_vp, C.POINTER(C.c_uint8), _sz, _u32, _d, _d, _d, _dp, _dp, _dp]),
+    "ndt2d_posegraph_set_timing": (C.c_int, [_vp, C.c_int]),
+    "ndt2d_posegraph_last_ms": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "ndt2d_set_eigenvalue_form": (C.c_int, [_vp, C.c_char_p]),
     "ndt2d_get_grid": (C.c_int, [_vp, _dp, _sz, C.POINTER(_u32), C.POINTER(_u32), _dp, _dp, _dp]),
     "ndt2d_clear_grid": (C.c_int, [_vp]),

@@ -1,0 +1,941 @@
+// Pose-graph optimisation on the device: N poses (x, y, theta), M relative-pose constraints, one
+// pose held fixed, and K independent jobs over the one graph, each with its own mask of enabled
+// constraints -- Levenberg-Marquardt with a matrix-free, block-Jacobi preconditioned conjugate
+// gradient inside, the whole iteration in ONE kernel launch (gfx950 / MI355X).  The residual, the
+// weighting, the cost, the stop rules and the records are the contract of include/ndt2d_hip.h
+// ("Pose graph"); the arithmetic of a constraint is posegraph/ndt2d_posegraph_fn.h.
+//
+//   posegraph_solve_kernel     grid (job of the chunk), 1,024 threads: one workgroup per job.  Thread
+//       t owns nodes t, t + 1024, ... in every phase and constraints t, t + 1024, ... of the cost.
+//       The graph (start poses, constraints with W, the node -> constraint table) lies in HBM and is
+//       shared by the jobs; a job's vectors (x, trial x, g, p, r, z, Hp, delta, the diagonal blocks
+//       of H, the preconditioner's inverses, cos / sin per node) lie in its own workspace in HBM.
+//       The LM loop, the gain ratio, accept / reject and the stop rules are evaluated by every
+//       thread on the same reduced values: all control flow is uniform, __syncthreads the only
+//       barrier, and the host is not asked between iterations.
+//   posegraph_evaluate_kernel  grid (job), 1,024 threads: e, r = W e and chi2 = |r|^2 of every
+//       constraint at the job's poses (thread t: constraints t, t + 1024, ...), F = 1/2 sum chi2
+//       over the enabled ones by the same reduction the solver uses -- a solve's initial_cost is
+//       evaluate's F bit for bit.
+//
+// Determinism.  No atomics.  A node's sums (g, its block of H, (H p)_i) are gathers over its incident
+// constraints in ascending constraint index (the host's table); a dot product is each thread's
+// strided partial in ascending order, the wave by an xor butterfly (every lane ends with the same
+// bits), the 16 waves' partials through LDS, summed in wave order by every thread.  A job reads the
+// shared graph, its mask and its own workspace only: its result does not depend on the other jobs.
+//
+// Bounds.  Every loop is bounded before it starts: by n, m, a node's degree, max_iterations or the
+// CG cap.  Node and constraint indices are checked by the host at upload (ndt2d_posegraph_set_graph);
+// a job's workspace is [job][kPgNodeDoubles * n] doubles.
+//
+// LDS: 2 x 5 x 16 partials, 1,280 bytes.  Registers and scratch: DESIGN.md 3.18.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "ndt2d_guard.h"
+#include "ndt2d_hip.h"
+#include "batch/ndt2d_batch_host.h"
+#include "posegraph/ndt2d_posegraph_fn.h"
+
+namespace ndt2d
+{
+
+namespace
+{
+
+namespace pg = posegraph;
+
+constexpr uint32_t kPgThreads = 1024;
+constexpr uint32_t kPgWaves = kPgThreads / kWave;
+constexpr int kPgSums = 5;                      // sums one reduction carries at most
+constexpr size_t kPgMaxJobs = 65535;            // blocks of a launch
+constexpr size_t kPgMaxNodes = size_t(1) << 30;
+constexpr size_t kPgMaxConstraints = size_t(1) << 30;   // (2 m table entries, each constraint << 1 | side, in 32 bits)
+constexpr size_t kPgRec = NDT2D_POSEGRAPH_RECORD_DOUBLES;
+constexpr uint32_t kPgCgCap = 8192;
+// per node of a job's workspace: x, trial x, g, p, r, z, Hp, delta (3 each), H's block and the
+// preconditioner's inverse (6 each), cos / sin at x and at the trial x (2 each), active (1)
+constexpr size_t kPgNodeDoubles = 8 * 3 + 2 * 6 + 2 * 2 + 1;
+
+// Levenberg-Marquardt's own constants (free to the implementation: the contract is the minimiser).
+constexpr double kPgLambda0 = 1e-4;             // 1 / Ceres's initial trust-region radius
+constexpr double kPgLambdaMin = 1e-32, kPgLambdaMax = 1e32;
+constexpr double kPgDiagMin = 1e-6, kPgDiagMax = 1e32;   // the clamp of diag(H) in the damping, as Ceres's
+constexpr double kPgMinGain = 1e-3;             // a step is accepted above this gain ratio
+constexpr double kPgNoise = 256.0 * 2.220446049250313e-16;   // |dF| <= this x F: below the cost's own rounding
+
+struct PgGraph
+{
+  const double * poses;        // [n][3] the start poses
+  const double * transform;    // [m][3]
+  const double * W;            // [m][9] row-major: L or L^T of the information
+  const uint32_t * begin;      // [m]
+  const uint32_t * end;        // [m]
+  const uint32_t * node_ptr;   // [n + 1]
+  const uint32_t * node_con;   // [2 m]: constraint << 1 | (the node is its end), ascending per node
+  uint32_t n, m, fixed;
+};
+
+struct PgRules
+{
+  uint32_t max_iterations;
+  double gradient_tolerance, function_tolerance, parameter_tolerance;
+};
+
+struct PgScratch
+{
+  double part[2][kPgSums][kPgWaves];
+};
+
+__device__ __forceinline__ double pg_wave_sum(double v)
+{
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+__device__ __forceinline__ double pg_wave_max(double v)
+{
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+  return v;
+}
+
+// The thread's index, opaque to the optimiser at each use: otherwise it forms the thread's address
+// into every array of every phase once, ahead of the iteration, and holds dozens of 64-bit
+// pointers in vector registers across it (into scratch, at 128 registers a thread).
+__device__ __forceinline__ uint32_t pg_tid()
+{
+  uint32_t t = threadIdx.x;
+  asm volatile("" : "+v"(t));
+  return t;
+}
+
+// A value every lane holds with the same bits, moved to scalar registers: the solver's scalars and
+// its control flow then cost no vector registers.
+__device__ __forceinline__ double pg_uniform(double v)
+{
+  const uint64_t bits = __double_as_longlong(v);
+  const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(bits));
+  const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(bits >> 32));
+  return __longlong_as_double(static_cast<long long>((static_cast<uint64_t>(hi) << 32) | lo));
+}
+
+// N sums over the block, the same bits in every thread.  The two halves of `part` alternate, so one
+// barrier per reduction is enough: a thread writes a half again only behind the barrier of the
+// reduction in between, which every thread reaches after it has read that half.  The barrier also
+// orders the block's global writes before it against the reads behind it.
+template <int N>
+__device__ __forceinline__ void pg_block_sum(double (&v)[N], PgScratch & sc, uint32_t & parity)
+{
+  static_assert(N <= kPgSums, "room in the scratch");
+  const uint32_t lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < N; ++k)
+  {
+    const double w = pg_wave_sum(v[k]);
+    if (lane == 0) sc.part[parity][k][wave] = w;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < N; ++k)
+  {
+    double t = sc.part[parity][k][0];
+#pragma unroll
+    for (uint32_t w = 1; w < kPgWaves; ++w) t += sc.part[parity][k][w];
+    v[k] = pg_uniform(t);
+  }
+  parity ^= 1u;
+}
+
+__device__ __forceinline__ double pg_block_max(double v, PgScratch & sc, uint32_t & parity)
+{
+  const uint32_t lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+  const double w = pg_wave_max(v);
+  if (lane == 0) sc.part[parity][0][wave] = w;
+  __syncthreads();
+  double t = sc.part[parity][0][0];
+#pragma unroll
+  for (uint32_t k = 1; k < kPgWaves; ++k) t = fmax(t, sc.part[parity][0][k]);
+  parity ^= 1u;
+  return pg_uniform(t);
+}
+
+// e, r = W e of constraint c at the poses xs; returns chi2 = |r|^2.  cos / sin of pose a's heading
+// are the device library's, here and in the node cache: the same bits for the same heading.
+// trig: [node][2] cos, sin of the headings in xs, or NULL to take them here.
+__device__ __forceinline__ double pg_constraint(const PgGraph & G, uint32_t c, const double * xs, const double * trig, double * e, double * r)
+{
+  const size_t a = G.begin[c];
+  const double * pa = xs + 3 * a;
+  const double * pb = xs + 3 * static_cast<size_t>(G.end[c]);
+  double sn, cs;
+  if (trig != nullptr)
+  {
+    cs = trig[2 * a];
+    sn = trig[2 * a + 1];
+  }
+  else
+  {
+    sincos(pa[2], &sn, &cs);
+  }
+  const pg::Frame f = pg::frame(cs, sn, pa, pb);
+  pg::error(f, pa[2], pb[2], G.transform + 3 * static_cast<size_t>(c), e);
+  pg::mul(G.W + 9 * static_cast<size_t>(c), e, r);
+  return (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2];
+}
+
+// F = 1/2 sum of chi2 over the job's enabled constraints at xs.
+__device__ double pg_cost(const PgGraph & G, const uint8_t * en, const double * xs, const double * trig, PgScratch & sc, uint32_t & parity)
+{
+  double acc[1] = {0.0};
+  for (uint32_t c = pg_tid(); c < G.m; c += kPgThreads)
+  {
+    if (en != nullptr && en[c] == 0) continue;
+    double e[3], r[3];
+    acc[0] += pg_constraint(G, c, xs, trig, e, r);
+  }
+  pg_block_sum(acc, sc, parity);
+  return 0.5 * acc[0];
+}
+
+// A job's workspace.
+struct PgWork
+{
+  double * x, * xt, * g, * p, * r, * z, * hp, * d, * hd, * mi, * cs, * cst, * act;
+  __device__ PgWork(double * base, size_t n)
+  {
+    x = base;
+    xt = x + 3 * n;
+    g = xt + 3 * n;
+    p = g + 3 * n;
+    r = p + 3 * n;
+    z = r + 3 * n;
+    hp = z + 3 * n;
+    d = hp + 3 * n;
+    hd = d + 3 * n;
+    mi = hd + 6 * n;
+    cs = mi + 6 * n;
+    cst = cs + 2 * n;
+    act = cst + 2 * n;
+  }
+};
+
+// The frame of constraint c at the job's x, from the node cache.
+__device__ __forceinline__ pg::Frame pg_frame(const PgWork & w, uint32_t a, uint32_t b)
+{
+  return pg::frame(w.cs[2 * static_cast<size_t>(a)], w.cs[2 * static_cast<size_t>(a) + 1], w.x + 3 * static_cast<size_t>(a),
+                   w.x + 3 * static_cast<size_t>(b));
+}
+
+// g, the diagonal blocks of H = J^T J and the active flags at x; returns |g|_inf.  A node that is
+// fixed or has no enabled constraint is not active: its g and block are zero.
+__device__ double pg_linearize(const PgGraph & G, const uint8_t * en, const PgWork & w, PgScratch & sc, uint32_t & parity)
+{
+  double gmax = 0.0;
+  for (uint32_t i = pg_tid(); i < G.n; i += kPgThreads)
+  {
+    double gi[3] = {0.0, 0.0, 0.0}, S[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    uint32_t count = 0;
+    const uint32_t k1 = G.node_ptr[i + 1];
+    for (uint32_t k = G.node_ptr[i]; k < k1; ++k)
+    {
+      const uint32_t entry = G.node_con[k], c = entry >> 1;
+      if (en != nullptr && en[c] == 0) continue;
+      ++count;
+      const uint32_t a = G.begin[c], b = G.end[c];
+      const pg::Frame f = pg_frame(w, a, b);
+      const double * W = G.W + 9 * static_cast<size_t>(c);
+      double e[3], r[3], v[3], y[3], E[9];
+      pg::error(f, w.x[3 * static_cast<size_t>(a) + 2], w.x[3 * static_cast<size_t>(b) + 2], G.transform + 3 * static_cast<size_t>(c), e);
+      pg::mul(W, e, r);
+      pg::mul_t(W, r, v);
+      if (entry & 1u)
+      {
+        pg::apply_bt(f, v, y);
+        pg::jacobian_b(f, E);
+      }
+      else
+      {
+        pg::apply_at(f, v, y);
+        pg::jacobian_a(f, E);
+      }
+      gi[0] += y[0];
+      gi[1] += y[1];
+      gi[2] += y[2];
+      pg::add_jtj(W, E, S);
+    }
+    const bool active = count != 0u && i != G.fixed;
+    const size_t at = static_cast<size_t>(i);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) w.g[3 * at + j] = active ? gi[j] : 0.0;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) w.hd[6 * at + j] = active ? S[j] : 0.0;
+    w.act[at] = active ? 1.0 : 0.0;
+    if (active) gmax = fmax(gmax, fmax(fabs(gi[0]), fmax(fabs(gi[1]), fabs(gi[2]))));
+  }
+  return pg_block_max(gmax, sc, parity);
+}
+
+__device__ __forceinline__ double pg_clamp_diag(double v) { return fmin(fmax(v, kPgDiagMin), kPgDiagMax); }
+
+// hp_i = ((H + lambda D) p)_i of the thread's nodes; returns the thread's share of p . hp.
+__device__ double pg_matvec(const PgGraph & G, const uint8_t * en, const PgWork & w, double lambda)
+{
+  double php = 0.0;
+  for (uint32_t i = pg_tid(); i < G.n; i += kPgThreads)
+  {
+    const size_t at = static_cast<size_t>(i);
+    double acc[3] = {0.0, 0.0, 0.0};
+    if (w.act[at] != 0.0)
+    {
+      const uint32_t k1 = G.node_ptr[i + 1];
+      for (uint32_t k = G.node_ptr[i]; k < k1; ++k)
+      {
+        const uint32_t entry = G.node_con[k], c = entry >> 1;
+        if (en != nullptr && en[c] == 0) continue;
+        const uint32_t a = G.begin[c], b = G.end[c];
+        const pg::Frame f = pg_frame(w, a, b);
+        const double * W = G.W + 9 * static_cast<size_t>(c);
+        double va[3], vb[3], v[3], u[3], t[3], y[3];
+        pg::apply_a(f, w.p + 3 * static_cast<size_t>(a), va);
+        pg::apply_b(f, w.p + 3 * static_cast<size_t>(b), vb);
+        v[0] = va[0] + vb[0];
+        v[1] = va[1] + vb[1];
+        v[2] = va[2] + vb[2];
+        pg::mul(W, v, u);
+        pg::mul_t(W, u, t);
+        if (entry & 1u) pg::apply_bt(f, t, y);
+        else pg::apply_at(f, t, y);
+        acc[0] += y[0];
+        acc[1] += y[1];
+        acc[2] += y[2];
+      }
+      const double * S = w.hd + 6 * at;
+      const double * pi = w.p + 3 * at;
+      acc[0] += lambda * pg_clamp_diag(S[0]) * pi[0];
+      acc[1] += lambda * pg_clamp_diag(S[3]) * pi[1];
+      acc[2] += lambda * pg_clamp_diag(S[5]) * pi[2];
+      php += (pi[0] * acc[0] + pi[1] * acc[1]) + pi[2] * acc[2];
+    }
+    w.hp[3 * at] = acc[0];
+    w.hp[3 * at + 1] = acc[1];
+    w.hp[3 * at + 2] = acc[2];
+  }
+  return php;
+}
+
+// cos / sin of the headings of the thread's own nodes of xs into trig.  One body for the start and
+// the trial point, in a loop of its own: the library's argument reduction is the largest register
+// user of this file, and nothing else is live round it.
+__device__ __forceinline__ void pg_trig(const double * xs, double * trig, uint32_t n)
+{
+  for (uint32_t i = pg_tid(); i < n; i += kPgThreads)
+  {
+    const size_t at = static_cast<size_t>(i);
+    double sn, cs;
+    sincos(xs[3 * at + 2], &sn, &cs);
+    trig[2 * at] = cs;
+    trig[2 * at + 1] = sn;
+  }
+}
+
+__global__ void __launch_bounds__(kPgThreads) posegraph_solve_kernel(const PgGraph G, const uint8_t * enabled, double * workspace,
+                                                                      const PgRules rules, double * poses_out, double * records)
+{
+  __shared__ PgScratch sc;
+  uint32_t parity = 0;
+  const uint32_t tid = threadIdx.x;
+  const size_t job = blockIdx.x, n = G.n;
+  const uint8_t * en = enabled != nullptr ? enabled + job * G.m : nullptr;
+  const PgWork w(workspace + job * kPgNodeDoubles * n, n);
+
+  for (uint32_t i = pg_tid(); i < G.n; i += kPgThreads)
+  {
+    const size_t at = static_cast<size_t>(i);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) w.x[3 * at + j] = G.poses[3 * at + j];
+  }
+  pg_trig(w.x, w.cs, G.n);
+  __syncthreads();
+
+  double F = pg_cost(G, en, w.x, w.cs, sc, parity);
+  const double F0 = F;
+  double gmax = 0.0;
+  uint32_t status = NDT2D_POSEGRAPH_MAX_ITERATIONS, iterations = 0, cg_total = 0;
+  const uint32_t cg_cap = G.n >= kPgCgCap ? kPgCgCap : min(3u * G.n + 16u, kPgCgCap);
+  if (!isfinite(F))
+  {
+    status = NDT2D_POSEGRAPH_FAILED;
+  }
+  else
+  {
+    gmax = pg_linearize(G, en, w, sc, parity);
+    if (gmax <= rules.gradient_tolerance) status = NDT2D_POSEGRAPH_CONVERGED_GRADIENT;
+  }
+  double lambda = kPgLambda0, nu = 2.0, g_start = -1.0;
+
+  while (status == NDT2D_POSEGRAPH_MAX_ITERATIONS && iterations < rules.max_iterations)
+  {
+    ++iterations;
+    // ---- the step: (H + lambda D) delta = -g by preconditioned conjugate gradients from 0 ----
+    double s2[2] = {0.0, 0.0};
+    for (uint32_t i = pg_tid(); i < G.n; i += kPgThreads)
+    {
+      const size_t at = static_cast<size_t>(i);
+      double S[6], M[6], r[3], z[3];
+#pragma unroll
+      for (int j = 0; j < 6; ++j) S[j] = w.hd[6 * at + j];
+      S[0] += lambda * pg_clamp_diag(S[0]);
+      S[3] += lambda * pg_clamp_diag(S[3]);
+      S[5] += lambda * pg_clamp_diag(S[5]);
+      if (w.act[at] == 0.0 || !pg::invert_sym(S, M))
+      {
+#pragma unroll
+        for (int j = 0; j < 6; ++j) M[j] = 0.0;
+      }
+#pragma unroll
+      for (int j = 0; j < 6; ++j) w.mi[6 * at + j] = M[j];
+#pragma unroll
+      for (int j = 0; j < 3; ++j) r[j] = -w.g[3 * at + j];
+      pg::mul_sym(M, r, z);
+#pragma unroll
+      for (int j = 0; j < 3; ++j)
+      {
+        w.r[3 * at + j] = r[j];
+        w.z[3 * at + j] = z[j];
+        w.p[3 * at + j] = z[j];
+        w.d[3 * at + j] = 0.0;
+      }
+      s2[0] += (r[0] * z[0] + r[1] * z[1]) + r[2] * z[2];
+      s2[1] += (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2];
+    }
+    pg_block_sum(s2, sc, parity);
+    double rz = s2[0];
+    const double r_start = sqrt(s2[1]);
+    if (g_start < 0.0) g_start = r_start;
+    // the forcing term: loose far from the minimiser, tighter with the gradient (superlinear)
+    const double target = fmin(0.1, sqrt(r_start / g_start)) * r_start;
+    for (uint32_t k = 0; k < cg_cap; ++k)
+    {
+      double s1[1] = {pg_matvec(G, en, w, lambda)};
+      pg_block_sum(s1, sc, parity);
+      if (!(s1[0] > 0.0) || !(rz > 0.0)) break;   // (p = 0, or a direction rounding made useless)
+      const double alpha = rz / s1[0];
+      s2[0] = 0.0;
+      s2[1] = 0.0;
+      for (uint32_t i = pg_tid(); i < G.n; i += kPgThreads)
+      {
+        const size_t at = static_cast<size_t>(i);
+        double r[3], z[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+        {
+          w.d[3 * at + j] += alpha * w.p[3 * at + j];
+          r[j] = w.r[3 * at + j] - alpha * w.hp[3 * at + j];
+          w.r[3 * at + j] = r[j];
+        }
+        pg::mul_sym(w.mi + 6 * at, r, z);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) w.z[3 * at + j] = z[j];
+        s2[0] += (r[0] * z[0] + r[1] * z[1]) + r[2] * z[2];
+        s2[1] += (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2];
+      }
+      pg_block_sum(s2, sc, parity);
+      ++cg_total;
+      if (sqrt(s2[1]) <= target) break;
+      const double beta = s2[0] / rz;
+      rz = s2[0];
+      for (uint32_t i = pg_tid(); i < G.n; i += kPgThreads)
+      {
+        const size_t at = static_cast<size_t>(i);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) w.p[3 * at + j] = w.z[3 * at + j] + beta * w.p[3 * at + j];
+      }
+      __syncthreads();
+    }
+
+    // ---- the trial point and what the model says of it ----
+    // with rho the CG residual left in r: delta^T H delta = -g.delta - lambda delta^T D delta - delta.r,
+    // so the model's decrease -g.delta - 1/2 delta^T H delta = 1/2 (lambda delta^T D delta + delta.r - g.delta)
+    double s5[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (uint32_t i = pg_tid(); i < G.n; i += kPgThreads)
+    {
+      const size_t at = static_cast<size_t>(i);
+      const double * S = w.hd + 6 * at;
+      const double D[3] = {pg_clamp_diag(S[0]), pg_clamp_diag(S[3]), pg_clamp_diag(S[5])};
+#pragma unroll
+      for (int j = 0; j < 3; ++j)
+      {
+        const double x = w.x[3 * at + j], d = w.d[3 * at + j];
+        const double xt = d == 0.0 ? x : x + d;   // (a pose that does not move keeps its bits, -0.0 included)
+        w.xt[3 * at + j] = xt;
+        s5[0] += w.g[3 * at + j] * d;
+        s5[1] += lambda * D[j] * d * d;
+        s5[2] += d * w.r[3 * at + j];
+        s5[3] += d * d;
+        s5[4] += x * x;
+      }
+    }
+    pg_trig(w.xt, w.cst, G.n);   // (each thread its own nodes: no barrier in between)
+    pg_block_sum(s5, sc, parity);
+    const double predicted = 0.5 * ((s5[1] + s5[2]) - s5[0]);
+    const double step = sqrt(s5[3]), x_norm = sqrt(s5[4]);
+    if (rules.parameter_tolerance > 0.0 && step <= rules.parameter_tolerance * (x_norm + rules.parameter_tolerance))
+    {
+      status = NDT2D_POSEGRAPH_CONVERGED_STEP;
+      break;
+    }
+    const double Ft = pg_cost(G, en, w.xt, w.cst, sc, parity);
+    const double dF = F - Ft;
+    // below the rounding of the cost's own sum the gain ratio is noise: the model decides
+    const bool noise = fabs(dF) <= kPgNoise * F;
+    const double gain = dF / predicted;
+    if (isfinite(Ft) && predicted > 0.0 && (noise || gain > kPgMinGain))
+    {
+      for (uint32_t i = pg_tid(); i < G.n; i += kPgThreads)
+      {
+        const size_t at = static_cast<size_t>(i);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) w.x[3 * at + j] = w.xt[3 * at + j];
+        w.cs[2 * at] = w.cst[2 * at];
+        w.cs[2 * at + 1] = w.cst[2 * at + 1];
+      }
+      __syncthreads();
+      gmax = pg_linearize(G, en, w, sc, parity);
+      const double t = 2.0 * gain - 1.0;
+      lambda *= noise ? 1.0 / 3.0 : fmax(1.0 / 3.0, 1.0 - t * t * t);
+      lambda = fmin(fmax(lambda, kPgLambdaMin), kPgLambdaMax);
+      nu = 2.0;
+      const double F_before = F;
+      F = Ft;
+      if (gmax <= rules.gradient_tolerance) status = NDT2D_POSEGRAPH_CONVERGED_GRADIENT;
+      else if (rules.function_tolerance > 0.0 && fabs(dF) <= rules.function_tolerance * F_before) status = NDT2D_POSEGRAPH_CONVERGED_COST;
+    }
+    else
+    {
+      lambda = fmin(lambda * nu, kPgLambdaMax);
+      nu *= 2.0;
+    }
+  }
+
+  // (FAILED: x still holds the start poses)
+  for (uint32_t i = pg_tid(); i < G.n; i += kPgThreads)
+  {
+    const size_t at = static_cast<size_t>(i);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) poses_out[(job * n + at) * 3 + j] = w.x[3 * at + j];
+  }
+  if (tid == 0)
+  {
+    double * rec = records + job * kPgRec;
+    rec[0] = static_cast<double>(status);
+    rec[1] = static_cast<double>(iterations);
+    rec[2] = static_cast<double>(cg_total);
+    rec[3] = F0;
+    rec[4] = F;
+    rec[5] = gmax;
+  }
+}
+
+// poses: the job's at poses + job x pose_stride doubles (0: the graph's start poses for every job).
+__global__ void __launch_bounds__(kPgThreads) posegraph_evaluate_kernel(const PgGraph G, const uint8_t * enabled, const double * poses,
+                                                                         size_t pose_stride, double * cost, double * chi2, size_t chi2_stride,
+                                                                         double * residuals)
+{
+  __shared__ PgScratch sc;
+  uint32_t parity = 0;
+  const size_t job = blockIdx.x;
+  const uint8_t * en = enabled != nullptr ? enabled + job * G.m : nullptr;
+  const double * xs = poses + job * pose_stride;
+  double acc[1] = {0.0};
+  for (uint32_t c = pg_tid(); c < G.m; c += kPgThreads)
+  {
+    double e[3], r[3];
+    const double q = pg_constraint(G, c, xs, nullptr, e, r);
+    if (chi2 != nullptr) chi2[job * chi2_stride + c] = q;
+    if (residuals != nullptr)
+    {
+      double * out = residuals + (job * G.m + c) * 6;
+#pragma unroll
+      for (int j = 0; j < 3; ++j)
+      {
+        out[j] = e[j];
+        out[3 + j] = r[j];
+      }
+    }
+    if (en == nullptr || en[c] != 0) acc[0] += q;
+  }
+  pg_block_sum(acc, sc, parity);
+  if (threadIdx.x == 0 && cost != nullptr) cost[job] = 0.5 * acc[0];
+}
+
+}  // namespace
+
+}  // namespace ndt2d
+
+// ---- the object and the C entry points ----
+
+struct ndt2d_posegraph : ndt2d::BatchHost
+{
+  size_t max_nodes = 0, max_constraints = 0, max_jobs = 0;
+  bool information_weighting = false;   // W = L^T instead of L
+  bool has_graph = false, weights_sent = false;
+  size_t n = 0, m = 0, fixed = 0;
+  std::vector<double> chol;             // [m][9] the lower Cholesky factors
+  std::vector<double> stage;            // what an upload is put together in
+  std::vector<uint32_t> index;
+  // on the device: [poses 3 n | transforms 3 m | W 9 m], [begin m | end m | node_ptr n + 1 | node_con 2 m],
+  // the chunk's masks, the chunk's workspaces
+  void * d_graph = nullptr, * d_index = nullptr, * d_enabled = nullptr, * d_work = nullptr;
+  size_t graph_cap = 0, index_cap = 0, enabled_cap = 0, work_cap = 0;
+};
+
+namespace ndt2d
+{
+
+namespace
+{
+
+PgGraph pg_device_graph(const ndt2d_posegraph * s)
+{
+  PgGraph G{};
+  const double * d = static_cast<const double *>(s->d_graph);
+  const uint32_t * u = static_cast<const uint32_t *>(s->d_index);
+  G.poses = d;
+  G.transform = d + 3 * s->n;
+  G.W = d + 3 * s->n + 3 * s->m;
+  G.begin = u;
+  G.end = u + s->m;
+  G.node_ptr = u + 2 * s->m;
+  G.node_con = u + 2 * s->m + s->n + 1;
+  G.n = static_cast<uint32_t>(s->n);
+  G.m = static_cast<uint32_t>(s->m);
+  G.fixed = static_cast<uint32_t>(s->fixed);
+  return G;
+}
+
+// W of every constraint by the weighting in force, behind a change of either.
+int pg_send_weights(ndt2d_posegraph * s, hipStream_t stream)
+{
+  if (s->weights_sent || s->m == 0) return NDT2D_OK;
+  s->stage.resize(9 * s->m);
+  for (size_t c = 0; c < s->m; ++c)
+  {
+    const double * L = s->chol.data() + 9 * c;
+    double * W = s->stage.data() + 9 * c;
+    for (int i = 0; i < 3; ++i)
+    {
+      for (int j = 0; j < 3; ++j) W[3 * i + j] = s->information_weighting ? L[3 * j + i] : L[3 * i + j];
+    }
+  }
+  NDT2D_BATCH_HIP(s, hipMemcpyAsync(static_cast<double *>(s->d_graph) + 3 * s->n + 3 * s->m, s->stage.data(), 9 * s->m * sizeof(double),
+                                    hipMemcpyHostToDevice, stream));
+  NDT2D_BATCH_HIP(s, hipStreamSynchronize(stream));   // (the stage is reused)
+  s->weights_sent = true;
+  return NDT2D_OK;
+}
+
+// The masks of jobs [k0, k1) on the device, or NULL for none.
+int pg_send_masks(ndt2d_posegraph * s, hipStream_t stream, const uint8_t * enabled, size_t k0, size_t k1, const uint8_t ** out)
+{
+  *out = nullptr;
+  if (enabled == nullptr || s->m == 0) return NDT2D_OK;
+  const size_t bytes = (k1 - k0) * s->m;
+  NDT2D_BATCH_HIP(s, grow_device(&s->d_enabled, &s->enabled_cap, bytes));
+  NDT2D_BATCH_HIP(s, hipMemcpyAsync(s->d_enabled, enabled + k0 * s->m, bytes, hipMemcpyHostToDevice, stream));
+  *out = static_cast<const uint8_t *>(s->d_enabled);
+  return NDT2D_OK;
+}
+
+int pg_ready(ndt2d_posegraph * s, const char * who)
+{
+  if (!s->has_graph) return batch_fail(s, NDT2D_ERR_STATE, std::string(who) + ": no graph (ndt2d_posegraph_set_graph)");
+  return NDT2D_OK;
+}
+
+}  // namespace
+
+}  // namespace ndt2d
+
+using ndt2d::batch_fail;
+
+extern "C" {
+
+int ndt2d_posegraph_create(ndt2d_handle h, size_t max_nodes, size_t max_constraints, size_t max_jobs, ndt2d_posegraph ** out)
+{
+  NDT2D_C_TRY
+  if (out == nullptr) return NDT2D_ERR_INVALID;
+  *out = nullptr;
+  if (h == nullptr || max_nodes == 0 || max_nodes > ndt2d::kPgMaxNodes || max_constraints > ndt2d::kPgMaxConstraints || max_jobs == 0 ||
+      max_jobs > ndt2d::kPgMaxJobs)
+  {
+    return NDT2D_ERR_INVALID;
+  }
+  ndt2d_posegraph * s = new ndt2d_posegraph();
+  s->h = h;
+  s->device = ndt2d_device_id(h);
+  s->max_nodes = max_nodes;
+  s->max_constraints = max_constraints;
+  s->max_jobs = max_jobs;
+  *out = s;
+  return NDT2D_OK;
+  NDT2D_C_CATCH(nullptr)
+}
+
+int ndt2d_posegraph_destroy(ndt2d_posegraph * s)
+{
+  NDT2D_C_TRY
+  if (s == nullptr) return NDT2D_ERR_INVALID;
+  ndt2d::batch_drain(s);
+  ndt2d::batch_release(s);
+  for (void * p : {s->d_graph, s->d_index, s->d_enabled, s->d_work})
+  {
+    if (p != nullptr) (void)hipFree(p);
+  }
+  delete s;
+  return NDT2D_OK;
+  NDT2D_C_CATCH(nullptr)
+}
+
+const char * ndt2d_posegraph_last_error(ndt2d_posegraph * s)
+{
+  return s != nullptr ? s->err.c_str() : "null posegraph";
+}
+
+int ndt2d_posegraph_set_timing(ndt2d_posegraph * s, int enabled)
+{
+  NDT2D_C_TRY
+  return ndt2d::batch_set_timing(s, enabled);
+  NDT2D_C_CATCH(s)
+}
+
+int ndt2d_posegraph_last_ms(ndt2d_posegraph * s, float * kernel_ms, float * fetch_ms)
+{
+  NDT2D_C_TRY
+  return ndt2d::batch_last_ms(s, "posegraph", kernel_ms, fetch_ms);
+  NDT2D_C_CATCH(s)
+}
+
+int ndt2d_posegraph_set_weighting(ndt2d_posegraph * s, const char * weighting)
+{
+  NDT2D_C_TRY
+  if (s == nullptr) return NDT2D_ERR_INVALID;
+  const std::string name = weighting != nullptr ? weighting : "";
+  if (name != "reference" && name != "information")
+  {
+    return batch_fail(s, NDT2D_ERR_INVALID, "ndt2d_posegraph_set_weighting: \"" + name + "\" (\"reference\" or \"information\")");
+  }
+  const bool information = name == "information";
+  if (information != s->information_weighting) s->weights_sent = false;
+  s->information_weighting = information;
+  return NDT2D_OK;
+  NDT2D_C_CATCH(s)
+}
+
+const char * ndt2d_posegraph_weighting(ndt2d_posegraph * s)
+{
+  return s == nullptr ? "" : s->information_weighting ? "information" : "reference";
+}
+
+int ndt2d_posegraph_set_graph(ndt2d_posegraph * s, const double * poses_xyt, size_t n, const uint32_t * begin, const uint32_t * end,
+                              const double * transform, const double * information, size_t m, size_t fixed)
+{
+  NDT2D_C_TRY
+  if (s == nullptr) return NDT2D_ERR_INVALID;
+  const std::string who = "ndt2d_posegraph_set_graph: ";
+  if (n == 0) return batch_fail(s, NDT2D_ERR_INVALID, who + "no poses");
+  if (poses_xyt == nullptr || (m != 0 && (begin == nullptr || end == nullptr || transform == nullptr || information == nullptr)))
+  {
+    return batch_fail(s, NDT2D_ERR_INVALID, who + "null argument");
+  }
+  if (n > s->max_nodes)
+  {
+    return batch_fail(s, NDT2D_ERR_INVALID, who + std::to_string(n) + " poses, the capacity is " + std::to_string(s->max_nodes));
+  }
+  if (m > s->max_constraints)
+  {
+    return batch_fail(s, NDT2D_ERR_INVALID, who + std::to_string(m) + " constraints, the capacity is " + std::to_string(s->max_constraints));
+  }
+  if (fixed >= n) return batch_fail(s, NDT2D_ERR_INVALID, who + "fixed pose " + std::to_string(fixed) + " of " + std::to_string(n));
+  for (size_t i = 0; i < 3 * n; ++i)
+  {
+    if (!std::isfinite(poses_xyt[i])) return batch_fail(s, NDT2D_ERR_INVALID, who + "pose " + std::to_string(i / 3) + " is not finite");
+  }
+  // every constraint is checked before the object changes: a refused graph leaves the old one in place
+  std::vector<double> chol(9 * m);
+  for (size_t c = 0; c < m; ++c)
+  {
+    const std::string name = "constraint " + std::to_string(c);
+    if (begin[c] >= n || end[c] >= n)
+    {
+      return batch_fail(s, NDT2D_ERR_INVALID, who + name + " names pose " + std::to_string(begin[c] >= n ? begin[c] : end[c]) + " of " +
+                                                std::to_string(n));
+    }
+    if (begin[c] == end[c]) return batch_fail(s, NDT2D_ERR_INVALID, who + name + " begins and ends at pose " + std::to_string(begin[c]));
+    for (int j = 0; j < 3; ++j)
+    {
+      if (!std::isfinite(transform[3 * c + j])) return batch_fail(s, NDT2D_ERR_INVALID, who + name + ": its transform is not finite");
+    }
+    for (int j = 0; j < 9; ++j)
+    {
+      if (!std::isfinite(information[9 * c + j])) return batch_fail(s, NDT2D_ERR_INVALID, who + name + ": its information is not finite");
+    }
+    if (!ndt2d::posegraph::cholesky_lower(information + 9 * c, chol.data() + 9 * c))
+    {
+      return batch_fail(s, NDT2D_ERR_INVALID, who + name + ": its information is not symmetric positive definite");
+    }
+  }
+  NDT2D_BATCH_HIP(s, hipSetDevice(s->device));
+  hipStream_t stream = static_cast<hipStream_t>(ndt2d_get_stream(s->h));
+  s->has_graph = false;
+  // the node -> constraint table: a node's constraints in ascending constraint index
+  s->index.assign(2 * m + n + 1 + 2 * m, 0u);
+  uint32_t * u_begin = s->index.data(), * u_end = u_begin + m, * ptr = u_end + m, * con = ptr + n + 1;
+  for (size_t c = 0; c < m; ++c)
+  {
+    u_begin[c] = begin[c];
+    u_end[c] = end[c];
+    ++ptr[begin[c] + 1];
+    ++ptr[end[c] + 1];
+  }
+  for (size_t i = 0; i < n; ++i) ptr[i + 1] += ptr[i];
+  {
+    std::vector<uint32_t> fill(ptr, ptr + n);
+    for (size_t c = 0; c < m; ++c)
+    {
+      con[fill[begin[c]]++] = static_cast<uint32_t>(c << 1);
+      con[fill[end[c]]++] = static_cast<uint32_t>(c << 1) | 1u;
+    }
+  }
+  s->stage.resize(3 * n + 3 * m);
+  std::memcpy(s->stage.data(), poses_xyt, 3 * n * sizeof(double));
+  if (m != 0) std::memcpy(s->stage.data() + 3 * n, transform, 3 * m * sizeof(double));
+  NDT2D_BATCH_HIP(s, ndt2d::grow_device(&s->d_graph, &s->graph_cap, (3 * n + 12 * m) * sizeof(double)));
+  NDT2D_BATCH_HIP(s, ndt2d::grow_device(&s->d_index, &s->index_cap, s->index.size() * sizeof(uint32_t)));
+  NDT2D_BATCH_HIP(s, hipMemcpyAsync(s->d_graph, s->stage.data(), s->stage.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+  NDT2D_BATCH_HIP(s, hipMemcpyAsync(s->d_index, s->index.data(), s->index.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+  NDT2D_BATCH_HIP(s, hipStreamSynchronize(stream));
+  s->chol.swap(chol);
+  s->n = n;
+  s->m = m;
+  s->fixed = fixed;
+  s->weights_sent = false;
+  s->has_graph = true;
+  return NDT2D_OK;
+  NDT2D_C_CATCH(s)
+}
+
+int ndt2d_posegraph_evaluate(ndt2d_posegraph * s, const uint8_t * enabled, size_t n_jobs, double * cost_out, double * chi2_out,
+                             double * residuals_out)
+{
+  NDT2D_C_TRY
+  if (s == nullptr) return NDT2D_ERR_INVALID;
+  if (n_jobs == 0) return NDT2D_OK;
+  if (cost_out == nullptr) return batch_fail(s, NDT2D_ERR_INVALID, "ndt2d_posegraph_evaluate: null argument");
+  int rc = ndt2d::pg_ready(s, "ndt2d_posegraph_evaluate");
+  if (rc != NDT2D_OK) return rc;
+  NDT2D_BATCH_HIP(s, hipSetDevice(s->device));
+  hipStream_t stream = static_cast<hipStream_t>(ndt2d_get_stream(s->h));
+  rc = ndt2d::pg_send_weights(s, stream);
+  if (rc != NDT2D_OK) return rc;
+  const ndt2d::PgGraph G = ndt2d::pg_device_graph(s);
+  const size_t m = s->m;
+  for (size_t k0 = 0; k0 < n_jobs; k0 += s->max_jobs)
+  {
+    const size_t k1 = std::min(n_jobs, k0 + s->max_jobs), kc = k1 - k0;
+    const uint8_t * d_en = nullptr;
+    rc = ndt2d::pg_send_masks(s, stream, enabled, k0, k1, &d_en);
+    if (rc != NDT2D_OK) return rc;
+    // what comes back: [cost kc | chi2 kc m | residuals kc m 6]
+    const size_t at_chi2 = kc, at_res = at_chi2 + (chi2_out != nullptr ? kc * m : 0);
+    const size_t total = at_res + (residuals_out != nullptr ? kc * m * 6 : 0);
+    NDT2D_BATCH_HIP(s, ndt2d::grow_pair(&s->h_out, &s->d_out, &s->out_cap, total));
+    s->timed = false;
+    if (s->timing) NDT2D_BATCH_HIP(s, hipEventRecord(s->ev[0], stream));
+    hipLaunchKernelGGL(ndt2d::posegraph_evaluate_kernel, dim3(static_cast<uint32_t>(kc)), dim3(ndt2d::kPgThreads), 0, stream, G, d_en,
+                       G.poses, size_t(0), s->d_out, chi2_out != nullptr ? s->d_out + at_chi2 : nullptr, m,
+                       residuals_out != nullptr ? s->d_out + at_res : nullptr);
+    NDT2D_BATCH_HIP(s, hipGetLastError());
+    if (s->timing) NDT2D_BATCH_HIP(s, hipEventRecord(s->ev[1], stream));
+    NDT2D_BATCH_HIP(s, hipMemcpyAsync(s->h_out, s->d_out, total * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (s->timing) NDT2D_BATCH_HIP(s, hipEventRecord(s->ev[2], stream));
+    NDT2D_BATCH_HIP(s, hipStreamSynchronize(stream));
+    s->timed = s->timing;
+    std::memcpy(cost_out + k0, s->h_out, kc * sizeof(double));
+    if (chi2_out != nullptr && m != 0) std::memcpy(chi2_out + k0 * m, s->h_out + at_chi2, kc * m * sizeof(double));
+    if (residuals_out != nullptr && m != 0) std::memcpy(residuals_out + k0 * m * 6, s->h_out + at_res, kc * m * 6 * sizeof(double));
+  }
+  return NDT2D_OK;
+  NDT2D_C_CATCH(s)
+}
+
+int ndt2d_posegraph_solve(ndt2d_posegraph * s, const uint8_t * enabled, size_t n_jobs, uint32_t max_iterations, double gradient_tolerance,
+                          double function_tolerance, double parameter_tolerance, double * poses_out, double * records_out,
+                          double * chi2_out)
+{
+  NDT2D_C_TRY
+  if (s == nullptr) return NDT2D_ERR_INVALID;
+  if (n_jobs == 0) return NDT2D_OK;
+  if (poses_out == nullptr || records_out == nullptr) return batch_fail(s, NDT2D_ERR_INVALID, "ndt2d_posegraph_solve: null argument");
+  if (!(gradient_tolerance >= 0.0) || !(function_tolerance >= 0.0) || !(parameter_tolerance >= 0.0) || !std::isfinite(gradient_tolerance) ||
+      !std::isfinite(function_tolerance) || !std::isfinite(parameter_tolerance))
+  {
+    return batch_fail(s, NDT2D_ERR_INVALID, "ndt2d_posegraph_solve: a tolerance is negative or not finite");
+  }
+  int rc = ndt2d::pg_ready(s, "ndt2d_posegraph_solve");
+  if (rc != NDT2D_OK) return rc;
+  NDT2D_BATCH_HIP(s, hipSetDevice(s->device));
+  hipStream_t stream = static_cast<hipStream_t>(ndt2d_get_stream(s->h));
+  rc = ndt2d::pg_send_weights(s, stream);
+  if (rc != NDT2D_OK) return rc;
+  const ndt2d::PgGraph G = ndt2d::pg_device_graph(s);
+  const ndt2d::PgRules rules{max_iterations, gradient_tolerance, function_tolerance, parameter_tolerance};
+  const size_t n = s->n, m = s->m;
+  for (size_t k0 = 0; k0 < n_jobs; k0 += s->max_jobs)
+  {
+    const size_t k1 = std::min(n_jobs, k0 + s->max_jobs), kc = k1 - k0;
+    const uint8_t * d_en = nullptr;
+    rc = ndt2d::pg_send_masks(s, stream, enabled, k0, k1, &d_en);
+    if (rc != NDT2D_OK) return rc;
+    NDT2D_BATCH_HIP(s, ndt2d::grow_device(&s->d_work, &s->work_cap, kc * ndt2d::kPgNodeDoubles * n * sizeof(double)));
+    // what comes back: [poses kc n 3 | records kc 6 | chi2 kc 2 m (start, end)]
+    const size_t at_rec = kc * n * 3, at_chi2 = at_rec + kc * ndt2d::kPgRec;
+    const size_t total = at_chi2 + (chi2_out != nullptr ? kc * 2 * m : 0);
+    NDT2D_BATCH_HIP(s, ndt2d::grow_pair(&s->h_out, &s->d_out, &s->out_cap, total));
+    s->timed = false;
+    if (s->timing) NDT2D_BATCH_HIP(s, hipEventRecord(s->ev[0], stream));
+    const dim3 blocks(static_cast<uint32_t>(kc)), threads(ndt2d::kPgThreads);
+    if (chi2_out != nullptr)
+    {
+      hipLaunchKernelGGL(ndt2d::posegraph_evaluate_kernel, blocks, threads, 0, stream, G, d_en, G.poses, size_t(0),
+                         static_cast<double *>(nullptr), s->d_out + at_chi2, 2 * m, static_cast<double *>(nullptr));
+      NDT2D_BATCH_HIP(s, hipGetLastError());
+    }
+    hipLaunchKernelGGL(ndt2d::posegraph_solve_kernel, blocks, threads, 0, stream, G, d_en, static_cast<double *>(s->d_work), rules, s->d_out,
+                       s->d_out + at_rec);
+    NDT2D_BATCH_HIP(s, hipGetLastError());
+    if (chi2_out != nullptr)
+    {
+      hipLaunchKernelGGL(ndt2d::posegraph_evaluate_kernel, blocks, threads, 0, stream, G, d_en, static_cast<const double *>(s->d_out), 3 * n,
+                         static_cast<double *>(nullptr), s->d_out + at_chi2 + m, 2 * m, static_cast<double *>(nullptr));
+      NDT2D_BATCH_HIP(s, hipGetLastError());
+    }
+    if (s->timing) NDT2D_BATCH_HIP(s, hipEventRecord(s->ev[1], stream));
+    NDT2D_BATCH_HIP(s, hipMemcpyAsync(s->h_out, s->d_out, total * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (s->timing) NDT2D_BATCH_HIP(s, hipEventRecord(s->ev[2], stream));
+    NDT2D_BATCH_HIP(s, hipStreamSynchronize(stream));
+    s->timed = s->timing;
+    std::memcpy(poses_out + k0 * n * 3, s->h_out, kc * n * 3 * sizeof(double));
+    std::memcpy(records_out + k0 * ndt2d::kPgRec, s->h_out + at_rec, kc * ndt2d::kPgRec * sizeof(double));
+    if (chi2_out != nullptr && m != 0) std::memcpy(chi2_out + k0 * 2 * m, s->h_out + at_chi2, kc * 2 * m * sizeof(double));
+  }
+  return NDT2D_OK;
+  NDT2D_C_CATCH(s)
+}
+
+}  // extern "C"

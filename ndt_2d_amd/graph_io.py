@@ -287,6 +287,33 @@ class Graph:
         found.sort()
         return [i for _, i in found]
 
+    # src/ceres_solver.cpp:50-120
+    def optimize(self, matcher, **kw):
+        """CeresSolver::optimize(constraints, scans) on the device (pose_graph.PoseGraph): the
+        poses are taken from the scans, scans[0] is held, one job with every constraint on is
+        solved, and the poses are written back unless the solve FAILED.  kw: PoseGraph.optimize's
+        tolerances and `weighting`.  Returns whether the solution is usable -- False for no scans,
+        as the reference; `last_optimize` keeps the job's record."""
+        from . import _capi
+        from .pose_graph import PoseGraph
+        self.last_optimize = None
+        if not self.scans:
+            return False
+        weighting = kw.pop("weighting", "reference")
+        pg = PoseGraph(matcher, max_nodes=len(self.scans), max_constraints=max(1, len(self.constraints)), max_jobs=1)
+        try:
+            pg.set_weighting(weighting)
+            pg.set_graph(np.array([s.pose for s in self.scans], dtype=np.float64), self.constraints, fixed=0)
+            result = pg.optimize(**kw)[0]
+        finally:
+            pg.close()
+        self.last_optimize = result
+        if result["status"] == _capi.POSEGRAPH_FAILED:
+            return False
+        for s, pose in zip(self.scans, result["poses"]):
+            s.pose = pose.copy()
+        return True
+
     def scan_tuples(self, indices=None):
         """The scans as ScanMatcherNDT.addScans / OccupancyGrid.getMsg take them."""
         scans = self.scans if indices is None else [self.scans[i] for i in indices]

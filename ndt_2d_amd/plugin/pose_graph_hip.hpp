@@ -1,0 +1,238 @@
+// The loop-closure thread's global optimisation (reference src/ndt_mapper.cpp:680,
+// solver_->optimize(graph_->constraints, graph_->scans); src/ceres_solver.cpp:50-120) on
+// libndt2d_hip.so: ndt2d_posegraph (include/ndt2d_hip.h, "Pose graph") -- Levenberg-Marquardt on
+// the device, one launch, scans[0] held as the reference holds it.
+//
+// optimize(constraints, scans) has the shape of CeresSolver::optimize: it returns false for no
+// scans or a failed solve and otherwise writes the corrected poses back into the scans.  It is a
+// template over the node's own types and touches only what the reference's have:
+//     constraint->begin, ->end, ->transform(i), ->information(i, j)           (ndt_2d::Constraint)
+//     scan->getPose() with .x .y .theta, scan->setPose(pose)                   (ndt_2d::Scan, Pose2d)
+// so nothing of ROS, Eigen or Ceres is included here; the overload on plain arrays is what it
+// calls.  Unlike CeresSolver the whole problem is handed over at every call (no residual blocks
+// are kept between calls), and a constraint whose information is not positive definite makes the
+// call fail with a message that names it, where Eigen's llt() goes on silently.
+//
+// consistency(): the second use -- every switchable closure solved with and without: K masks over
+// the one graph in one launch, chi2 of each closure against the solution of the others.  A verdict,
+// no policy.
+#ifndef NDT_2D_HIP__POSE_GRAPH_HIP_HPP_
+#define NDT_2D_HIP__POSE_GRAPH_HIP_HPP_
+
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "ndt2d_hip.h"
+
+namespace ndt_2d_hip
+{
+
+// How one job ended.
+struct PoseGraphRecord
+{
+  int status = NDT2D_POSEGRAPH_FAILED;   // NDT2D_POSEGRAPH_*
+  std::uint32_t iterations = 0, cg_iterations = 0;
+  double initial_cost = 0.0, final_cost = 0.0, gradient = 0.0;
+  bool usable() const { return status != NDT2D_POSEGRAPH_FAILED; }
+};
+
+class PoseGraphHip
+{
+public:
+  explicit PoseGraphHip(ndt2d_matcher * matcher) : m_(matcher) {}
+  PoseGraphHip(const PoseGraphHip &) = delete;
+  PoseGraphHip & operator=(const PoseGraphHip &) = delete;
+  ~PoseGraphHip()
+  {
+    if (pg_ != nullptr) ndt2d_posegraph_destroy(pg_);
+  }
+
+  // Ceres's defaults (src/ceres_solver.cpp:39 and ceres::Solver::Options); a tolerance of 0
+  // disables its rule.
+  void setMaxIterations(std::uint32_t n) { max_iterations_ = n; }
+  void setTolerances(double gradient, double function, double parameter)
+  {
+    gradient_tolerance_ = gradient;
+    function_tolerance_ = function;
+    parameter_tolerance_ = parameter;
+  }
+  // "reference": W = L as the reference passes it (the cost is e^T L^T L e); "information": W = L^T.
+  void setWeighting(const std::string & weighting) { weighting_ = weighting; }
+
+  // Plain arrays: poses_xyt[n][3] in and out, constraints as ndt2d_posegraph_set_graph takes them.
+  // false: no poses, a refused graph or a failed solve (last_error()); the poses stay then.
+  bool optimize(double * poses_xyt, std::size_t n, const std::uint32_t * begin, const std::uint32_t * end, const double * transform,
+                const double * information, std::size_t m)
+  {
+    record_ = PoseGraphRecord();
+    if (n == 0) return false;   // `if (scans.empty()) return false;`
+    if (!upload(poses_xyt, n, begin, end, transform, information, m, 1)) return false;
+    out_.assign(3 * n, 0.0);
+    double rec[NDT2D_POSEGRAPH_RECORD_DOUBLES];
+    if (!ok(ndt2d_posegraph_solve(pg_, nullptr, 1, max_iterations_, gradient_tolerance_, function_tolerance_, parameter_tolerance_,
+                                  out_.data(), rec, nullptr)))
+    {
+      return false;
+    }
+    record_ = unpack(rec);
+    if (!record_.usable()) return false;   // `if (!summary.IsSolutionUsable()) return false;`
+    for (std::size_t i = 0; i < 3 * n; ++i) poses_xyt[i] = out_[i];
+    return true;
+  }
+
+  // CeresSolver::optimize(constraints, scans): containers of (smart) pointers to the node's types.
+  template <class Constraints, class Scans>
+  bool optimize(const Constraints & constraints, Scans & scans)
+  {
+    poses_.clear();
+    for (const auto & scan : scans)
+    {
+      const auto pose = scan->getPose();
+      poses_.push_back(pose.x);
+      poses_.push_back(pose.y);
+      poses_.push_back(pose.theta);
+    }
+    gather(constraints);
+    const std::size_t n = poses_.size() / 3;
+    if (!optimize(poses_.data(), n, begin_.data(), end_.data(), transform_.data(), information_.data(), begin_.size())) return false;
+    std::size_t i = 0;
+    for (auto & scan : scans)
+    {
+      auto pose = scan->getPose();
+      pose.x = poses_[3 * i];
+      pose.y = poses_[3 * i + 1];
+      pose.theta = poses_[3 * i + 2];
+      scan->setPose(pose);
+      ++i;
+    }
+    return true;
+  }
+
+  // Every switchable constraint solved without: job 0 has every constraint on, job 1 + k has the
+  // k-th switchable constraint (in the order of `constraints`) off.  chi2_out[job][constraint] at
+  // the job's solution; records_out per job.  The scans are not changed.
+  template <class Constraints, class Scans>
+  bool consistency(const Constraints & constraints, const Scans & scans, std::vector<std::vector<double>> & chi2_out,
+                   std::vector<PoseGraphRecord> & records_out)
+  {
+    chi2_out.clear();
+    records_out.clear();
+    poses_.clear();
+    std::vector<std::size_t> switchable;
+    for (const auto & scan : scans)
+    {
+      const auto pose = scan->getPose();
+      poses_.push_back(pose.x);
+      poses_.push_back(pose.y);
+      poses_.push_back(pose.theta);
+    }
+    gather(constraints);
+    std::size_t c = 0;
+    for (const auto & constraint : constraints)
+    {
+      if (constraint->switchable) switchable.push_back(c);
+      ++c;
+    }
+    const std::size_t n = poses_.size() / 3, m = begin_.size(), jobs = 1 + switchable.size();
+    if (n == 0) return false;
+    if (!upload(poses_.data(), n, begin_.data(), end_.data(), transform_.data(), information_.data(), m, jobs)) return false;
+    std::vector<std::uint8_t> enabled(jobs * m, 1);
+    for (std::size_t k = 0; k < switchable.size(); ++k) enabled[(1 + k) * m + switchable[k]] = 0;
+    out_.assign(jobs * 3 * n, 0.0);
+    std::vector<double> rec(jobs * NDT2D_POSEGRAPH_RECORD_DOUBLES), chi2(jobs * 2 * m);
+    if (!ok(ndt2d_posegraph_solve(pg_, enabled.data(), jobs, max_iterations_, gradient_tolerance_, function_tolerance_,
+                                  parameter_tolerance_, out_.data(), rec.data(), chi2.data())))
+    {
+      return false;
+    }
+    for (std::size_t k = 0; k < jobs; ++k)
+    {
+      records_out.push_back(unpack(rec.data() + k * NDT2D_POSEGRAPH_RECORD_DOUBLES));
+      chi2_out.emplace_back(chi2.begin() + (2 * k + 1) * m, chi2.begin() + (2 * k + 2) * m);
+    }
+    return true;
+  }
+
+  const PoseGraphRecord & record() const { return record_; }   // of the last optimize()
+  const std::string & last_error() const { return error_; }
+
+private:
+  template <class Constraints>
+  void gather(const Constraints & constraints)
+  {
+    begin_.clear();
+    end_.clear();
+    transform_.clear();
+    information_.clear();
+    for (const auto & constraint : constraints)
+    {
+      begin_.push_back(static_cast<std::uint32_t>(constraint->begin));
+      end_.push_back(static_cast<std::uint32_t>(constraint->end));
+      for (int i = 0; i < 3; ++i) transform_.push_back(constraint->transform(i));
+      for (int i = 0; i < 3; ++i)
+      {
+        for (int j = 0; j < 3; ++j) information_.push_back(constraint->information(i, j));
+      }
+    }
+  }
+
+  // The object (made anew when a capacity is passed) holding the graph.
+  bool upload(const double * poses_xyt, std::size_t n, const std::uint32_t * begin, const std::uint32_t * end, const double * transform,
+              const double * information, std::size_t m, std::size_t jobs)
+  {
+    if (pg_ == nullptr || n > max_nodes_ || m > max_constraints_ || jobs > max_jobs_)
+    {
+      if (pg_ != nullptr) ndt2d_posegraph_destroy(pg_);
+      pg_ = nullptr;
+      max_nodes_ = n > 2 * max_nodes_ ? n : 2 * max_nodes_;
+      max_constraints_ = m > 2 * max_constraints_ ? m : 2 * max_constraints_;
+      max_jobs_ = jobs > max_jobs_ ? (jobs < 65535 ? jobs : 65535) : max_jobs_;
+      const int rc = ndt2d_posegraph_create(ndt2d_matcher_device(m_), max_nodes_, max_constraints_, max_jobs_, &pg_);
+      if (rc != NDT2D_OK)
+      {
+        error_ = "ndt2d error " + std::to_string(rc) + ": ndt2d_posegraph_create";
+        max_nodes_ = max_constraints_ = 0;
+        max_jobs_ = 1;
+        return false;
+      }
+    }
+    if (!ok(ndt2d_posegraph_set_weighting(pg_, weighting_.c_str()))) return false;
+    return ok(ndt2d_posegraph_set_graph(pg_, poses_xyt, n, begin, end, transform, information, m, 0));
+  }
+
+  static PoseGraphRecord unpack(const double * rec)
+  {
+    PoseGraphRecord r;
+    r.status = static_cast<int>(rec[0]);
+    r.iterations = static_cast<std::uint32_t>(rec[1]);
+    r.cg_iterations = static_cast<std::uint32_t>(rec[2]);
+    r.initial_cost = rec[3];
+    r.final_cost = rec[4];
+    r.gradient = rec[5];
+    return r;
+  }
+
+  bool ok(int rc)
+  {
+    if (rc == NDT2D_OK) return true;
+    error_ = std::string("ndt2d error ") + std::to_string(rc) + ": " + ndt2d_posegraph_last_error(pg_);
+    return false;
+  }
+
+  ndt2d_matcher * m_;
+  ndt2d_posegraph * pg_ = nullptr;
+  std::size_t max_nodes_ = 0, max_constraints_ = 0, max_jobs_ = 1;
+  std::uint32_t max_iterations_ = 100;
+  double gradient_tolerance_ = 1e-10, function_tolerance_ = 1e-6, parameter_tolerance_ = 1e-8;
+  std::string weighting_ = "reference";
+  std::vector<double> poses_, transform_, information_, out_;
+  std::vector<std::uint32_t> begin_, end_;
+  PoseGraphRecord record_;
+  std::string error_;
+};
+
+}  // namespace ndt_2d_hip
+
+#endif  // NDT_2D_HIP__POSE_GRAPH_HIP_HPP_

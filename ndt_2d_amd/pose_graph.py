@@ -1,0 +1,213 @@
+"""The pose graph on the device: ndt2d_posegraph (include/ndt2d_hip.h, "Pose graph") and what turns
+the loop-closure results into its constraints.
+
+`PoseGraph(matcher)` stands beside the matcher's device context, as `Resampler` does: `set_graph`
+uploads poses and constraints, `evaluate` gives the residuals and the cost, `optimize` moves the
+poses -- K masks over one graph in one launch.  `make_constraint` restates the reference's
+makeConstraint (src/constraint.cpp:35-56), `closure_constraints` turns `close_loops`' accepted list
+into the switchable constraints the loop-closure thread adds (src/ndt_mapper.cpp:658-661).
+`graph_io.Graph.optimize` is CeresSolver::optimize on top of these."""
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import _capi
+from ._capi import Ndt2dError, dptr
+from .graph_io import Constraint
+
+DEFAULT_TOLERANCES = dict(max_iterations=100, gradient_tolerance=1e-10, function_tolerance=1e-6, parameter_tolerance=1e-8)
+
+
+def _inverse3(m):
+    """The inverse of a 3 x 3 by cofactors (Eigen's Matrix3d::inverse)."""
+    a, b, c, d, e, f, g, h, i = (float(v) for v in np.asarray(m, dtype=np.float64).reshape(9))
+    c00, c01, c02 = e * i - f * h, f * g - d * i, d * h - e * g
+    det = a * c00 + b * c01 + c * c02
+    inv = 1.0 / det
+    return np.array([[c00 * inv, (c * h - b * i) * inv, (b * f - c * e) * inv],
+                     [c01 * inv, (a * i - c * g) * inv, (c * d - a * f) * inv],
+                     [c02 * inv, (b * g - a * h) * inv, (a * e - b * d) * inv]])
+
+
+def make_constraint(begin, end, from_pose, to_pose, covariance):
+    """makeConstraint (src/constraint.cpp:35-56): the transform is to_pose in from_pose's frame, the
+    heading difference is not wrapped, the information is the covariance's inverse; not switchable."""
+    fx, fy, fth = (float(v) for v in from_pose)
+    tx, ty, tth = (float(v) for v in to_pose)
+    dx, dy = tx - fx, ty - fy
+    costh, sinth = math.cos(fth), math.sin(fth)
+    transform = (costh * dx + sinth * dy, -sinth * dx + costh * dy, tth - fth)
+    return Constraint(begin, end, transform, _inverse3(covariance), switchable=False)
+
+
+def closure_constraints(accepted, scan_index, graph_poses):
+    """`close_loops`' accepted list as the constraints the loop-closure thread adds: for each entry
+    makeConstraint(candidate, scan, covariance) with the scan at the pose the walk adopted for it,
+    switchable.  Where the entry has a refined pose the walk adopted (`refine_usable`, close_loops'
+    own rule) and a refined covariance, these are used; the lattice pose and covariance otherwise."""
+    out = []
+    for entry in accepted:
+        pose, covariance = entry["pose"], entry["covariance"]
+        if entry.get("refine_usable") and entry.get("refined_covariance") is not None:
+            pose, covariance = entry["refined_pose"], entry["refined_covariance"]
+        c = make_constraint(entry["candidate"], scan_index, graph_poses[entry["candidate"]], pose, covariance)
+        c.switchable = True
+        out.append(c)
+    return out
+
+
+def check_masks(masks, switchable):
+    """masks [K, m] as bytes (non-zero: on).  A mask may switch off switchable constraints only:
+    ValueError names the first mask and constraint that break the rule."""
+    switchable = np.asarray(switchable, dtype=bool).reshape(-1)
+    en = np.ascontiguousarray(np.asarray(masks).reshape(-1, len(switchable)) != 0, dtype=np.uint8)
+    off = (en == 0) & ~switchable[None, :]
+    if off.any():
+        k, c = (int(v) for v in np.argwhere(off)[0])
+        raise ValueError("mask %d switches off constraint %d, which is not switchable" % (k, c))
+    return en
+
+
+class PoseGraph:
+    """ndt2d_posegraph on the matcher's device context.  The capacities grow with the graphs given
+    to set_graph (the object is made anew when one is passed)."""
+
+    def __init__(self, matcher, max_nodes=1024, max_constraints=4096, max_jobs=256):
+        self._L = matcher._L
+        self._p = None
+        self._matcher = matcher   # the context must outlive the object
+        self._caps = (0, 0, 0)
+        self._weighting = "reference"
+        self._timing = False
+        self.n = self.m = 0
+        self.switchable = np.zeros(0, dtype=bool)
+        self._create(int(max_nodes), int(max_constraints), int(max_jobs))
+
+    def _create(self, max_nodes, max_constraints, max_jobs):
+        p = C.c_void_p()
+        self._matcher._dev_check(self._L.ndt2d_posegraph_create(self._matcher.device_handle, max_nodes, max_constraints, max_jobs, C.byref(p)),
+                                 "ndt2d_posegraph_create")
+        old, self._p = self._p, p
+        if old:
+            self._L.ndt2d_posegraph_destroy(old)
+        self._caps = (max_nodes, max_constraints, max_jobs)
+        self._check(self._L.ndt2d_posegraph_set_weighting(self._p, self._weighting.encode()), "ndt2d_posegraph_set_weighting")
+        if self._timing:
+            self.set_timing(True)
+
+    def close(self):
+        if getattr(self, "_p", None):
+            self._L.ndt2d_posegraph_destroy(self._p)
+            self._p = None
+        self._matcher = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc, where):
+        if rc != _capi.OK:
+            msg = self._L.ndt2d_posegraph_last_error(self._p)
+            raise Ndt2dError(rc, where, msg.decode() if msg else "")
+
+    def set_weighting(self, weighting):
+        """"reference": W = L, the reference's; "information": W = L^T, the cost is e^T information e."""
+        self._check(self._L.ndt2d_posegraph_set_weighting(self._p, str(weighting).encode()), "ndt2d_posegraph_set_weighting")
+        self._weighting = str(weighting)
+
+    def weighting(self):
+        return self._L.ndt2d_posegraph_weighting(self._p).decode()
+
+    def set_graph(self, poses, constraints=None, fixed=0, begin=None, end=None, transform=None, information=None, switchable=None):
+        """poses [n, 3]; the constraints as graph_io.Constraint objects, or as the arrays begin, end
+        [m], transform [m, 3], information [m, 3, 3] and (optional) switchable [m]."""
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+        if constraints is not None:
+            begin = [c.begin for c in constraints]
+            end = [c.end for c in constraints]
+            transform = [c.transform for c in constraints]
+            information = [c.information for c in constraints]
+            switchable = [c.switchable for c in constraints]
+        m = 0 if begin is None else len(begin)
+        for name, idx in (("begin", begin), ("end", end)):
+            for c in range(m):
+                if not 0 <= int(idx[c]) < 2 ** 32:
+                    raise ValueError("constraint %d: %s = %d" % (c, name, int(idx[c])))
+        b = np.ascontiguousarray(np.zeros(0) if m == 0 else begin, dtype=np.uint32).reshape(m)
+        e = np.ascontiguousarray(np.zeros(0) if m == 0 else end, dtype=np.uint32).reshape(m)
+        t = np.ascontiguousarray(np.zeros((0, 3)) if m == 0 else transform, dtype=np.float64).reshape(m, 3)
+        info = np.ascontiguousarray(np.zeros((0, 9)) if m == 0 else information, dtype=np.float64).reshape(m, 9)
+        caps = self._caps
+        if len(poses) > caps[0] or m > caps[1]:
+            self._create(max(caps[0], len(poses)), max(caps[1], m), caps[2])
+        u32p = C.POINTER(C.c_uint32)
+        self._check(self._L.ndt2d_posegraph_set_graph(self._p, dptr(poses), len(poses), b.ctypes.data_as(u32p), e.ctypes.data_as(u32p), dptr(t),
+                                                      dptr(info), m, int(fixed)), "ndt2d_posegraph_set_graph")
+        self.n, self.m = len(poses), m
+        self.switchable = np.zeros(m, dtype=bool) if switchable is None else np.array(switchable, dtype=bool).reshape(m)
+
+    def _masks(self, masks):
+        """(bytes [K, m] or None, K); a mask may switch off switchable constraints only."""
+        if masks is None:
+            return None, 1
+        en = check_masks(masks, self.switchable)
+        return en, len(en)
+
+    @staticmethod
+    def _u8(a):
+        return None if a is None else a.ctypes.data_as(C.POINTER(C.c_uint8))
+
+    def evaluate(self, masks=None, want_residuals=False):
+        """At the graph's poses, per mask (None: one job, every constraint on): dict(cost, chi2 [m],
+        and with want_residuals e [m, 3] and r [m, 3])."""
+        en, K = self._masks(masks)
+        cost = np.zeros(K)
+        chi2 = np.zeros((K, self.m))
+        res = np.zeros((K, self.m, 6)) if want_residuals else None
+        self._check(self._L.ndt2d_posegraph_evaluate(self._p, self._u8(en), K, dptr(cost), dptr(chi2), None if res is None else dptr(res)),
+                    "ndt2d_posegraph_evaluate")
+        out = []
+        for k in range(K):
+            d = dict(cost=float(cost[k]), chi2=chi2[k].copy())
+            if want_residuals:
+                d.update(e=res[k, :, :3].copy(), r=res[k, :, 3:].copy())
+            out.append(d)
+        return out
+
+    def optimize(self, masks=None, **tolerances):
+        """One job per mask (None: one job, every constraint on), all in one launch.  tolerances:
+        max_iterations, gradient_tolerance, function_tolerance, parameter_tolerance (Ceres's defaults;
+        0 disables a rule).  Returns per job dict(poses [n, 3], status, status_name, iterations,
+        cg_iterations, initial_cost, final_cost, gradient, chi2_start [m], chi2 [m])."""
+        unknown = set(tolerances) - set(DEFAULT_TOLERANCES)
+        if unknown:
+            raise TypeError("optimize: unknown argument(s) %s" % sorted(unknown))
+        tol = dict(DEFAULT_TOLERANCES, **tolerances)
+        en, K = self._masks(masks)
+        poses = np.zeros((K, self.n, 3))
+        records = np.zeros((K, _capi.POSEGRAPH_RECORD_DOUBLES))
+        chi2 = np.zeros((K, 2, self.m))
+        self._check(self._L.ndt2d_posegraph_solve(self._p, self._u8(en), K, int(tol["max_iterations"]), float(tol["gradient_tolerance"]),
+                                                  float(tol["function_tolerance"]), float(tol["parameter_tolerance"]), dptr(poses),
+                                                  dptr(records), dptr(chi2)), "ndt2d_posegraph_solve")
+        out = []
+        for k in range(K):
+            status = int(records[k, 0])
+            out.append(dict(poses=poses[k].copy(), status=status, status_name=_capi.POSEGRAPH_STATUS_NAMES[status],
+                            iterations=int(records[k, 1]), cg_iterations=int(records[k, 2]), initial_cost=float(records[k, 3]),
+                            final_cost=float(records[k, 4]), gradient=float(records[k, 5]), chi2_start=chi2[k, 0].copy(),
+                            chi2=chi2[k, 1].copy()))
+        return out
+
+    def set_timing(self, enabled):
+        self._check(self._L.ndt2d_posegraph_set_timing(self._p, 1 if enabled else 0), "ndt2d_posegraph_set_timing")
+        self._timing = bool(enabled)
+
+    def last_ms(self):
+        """(kernel_ms, fetch_ms) of the last call's last chunk (set_timing(True))."""
+        a, b = C.c_float(0.0), C.c_float(0.0)
+        self._check(self._L.ndt2d_posegraph_last_ms(self._p, C.byref(a), C.byref(b)), "ndt2d_posegraph_last_ms")
+        return a.value, b.value

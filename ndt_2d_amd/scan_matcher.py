@@ -1139,7 +1139,8 @@ def close_loops(matcher, scan_pose, points, candidate_indices, graph_poses, roll
     candidate of the round that passes the accept test, each started from pose + its correction.
     The accept test stays the reference's, on the lattice score, and the walk consumes the first
     accepted candidate as before; its entry gains refined_pose, refined_covariance (None where the
-    Hessian is not positive definite) and refine_status (its `pose` stays the lattice pose).  The
+    Hessian is not positive definite), refine_status and refine_usable, the rule of the next
+    sentence as a flag (its `pose` stays the lattice pose).  The
     scan's pose -- what the next round starts from, and what is returned -- is the refined pose
     where the status is CONVERGED or MAX_EVALS and f did not rise, the lattice pose otherwise.
 
@@ -1186,7 +1187,8 @@ def close_loops(matcher, scan_pose, points, candidate_indices, graph_poses, roll
             entry = dict(candidate=i, score=res["score"], correction=correction, covariance=res["covariance"], pose=pose.copy())
             if refined is not None:
                 r = refined[0]
-                entry.update(refined_pose=r["pose"].copy(), refined_covariance=r["covariance"], refine_status=r["status"])
+                entry.update(refined_pose=r["pose"].copy(), refined_covariance=r["covariance"], refine_status=r["status"],
+                             refine_usable=_refine_usable(r))
                 if _refine_usable(r):
                     pose = r["pose"].copy()
             if verdicts is not None:
