@@ -63,6 +63,12 @@ inline int batch_fail(BatchHost * s, int code, const std::string & msg)
   return code;
 }
 
+// The end of a setter: what it refuses (a text of batch/ndt2d_refine_jobs.h's kind), or nothing.
+inline int batch_refuse(BatchHost * s, const std::string & refusal)
+{
+  return refusal.empty() ? NDT2D_OK : batch_fail(s, NDT2D_ERR_INVALID, refusal);
+}
+
 inline int batch_fail_hip(BatchHost * s, hipError_t e, const char * what)
 {
   (void)hipGetLastError();  // clear sticky state

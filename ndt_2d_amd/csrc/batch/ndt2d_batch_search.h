@@ -141,6 +141,15 @@ struct InstalledMap
   }
 };
 
+// SOURCE (refine/ndt2d_refine_kernel.h, verify/ndt2d_verify_kernel.h) of the grid installed in the
+// context: one grid for all jobs, a cell is its own record.
+struct InstalledSource
+{
+  GridDesc g;   // geometry, cells_global, occ_bits
+  __device__ __forceinline__ const GridDesc & grid(uint32_t) const { return g; }
+  __device__ __forceinline__ InstalledMap map(uint32_t) const { return InstalledMap{g.occ_bits, g.cells_global}; }
+};
+
 // One job of a chunk on the installed grid.
 struct JobRec
 {

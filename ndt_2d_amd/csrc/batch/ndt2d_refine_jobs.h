@@ -1,13 +1,15 @@
 // What the Newton registrations share on the host (refine/ndt2d_refine.hip: jobs on the installed
 // grid; closure/ndt2d_closure.hip: jobs on the loop closure's candidate maps): what both refuse
 // about rules, scans and jobs -- one text, so that the two objects cannot drift apart in what they
-// refuse -- and which scans a chunk uploads.  Plain C++: no HIP.
+// refuse -- and which scans a chunk uploads, with their copy into the stage (the verifications,
+// verify/ndt2d_verify.hip and the closure's, take all three too).  Plain C++: no HIP.
 #ifndef NDT2D_REFINE_JOBS_H_
 #define NDT2D_REFINE_JOBS_H_
 
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -83,6 +85,18 @@ inline size_t plan_sent_scans(size_t n, JOB_AT job_at, SCAN_OF scan_of, const si
     }
   }
   return n_beams;
+}
+
+// The beams of the sent scans into the chunk's beams (`to`, [beam][2]), each scan at its
+// scan_first; beams_xy / beam_offsets: the call's.
+inline void copy_sent_scans(const std::vector<uint32_t> & sent, const std::vector<uint64_t> & scan_first, const double * beams_xy,
+                            const size_t * beam_offsets, double * to)
+{
+  for (const uint32_t sc : sent)
+  {
+    std::memcpy(to + 2 * scan_first[sc], beams_xy + 2 * beam_offsets[sc],
+                2 * (beam_offsets[sc + 1] - beam_offsets[sc]) * sizeof(double));
+  }
 }
 
 }  // namespace refine_jobs

@@ -28,15 +28,15 @@
 //   batch_reduce_kernel    one block per candidate map: the n_theta records of its blocks ->
 //       {best_score, best_index (+0.5: near tie), acc[10]} with merge_best, fixed order.
 //
-//   verify_kernel<POW2, CELLS, SlotSource> (../verify/ndt2d_verify.hip, its device half included
-//       here)  ndt2d_closure_verify: the match verification of K (scan, pose) jobs, each on its
+//   verify_kernel<POW2, CELLS, SlotSource> (../verify/ndt2d_verify_kernel.h)
+//       ndt2d_closure_verify: the match verification of K (scan, pose) jobs, each on its
 //       candidate's own map, behind the same build launch in ONE launch with a workgroup of 256
 //       threads per job; the plan is ndt2d_closure_jobs.h's with the jobs' beams as weights.  A
 //       job's record and per-beam results have the bits ndt2d_verify_run gives on the grid
 //       ndt2d_scanstore_build installs for the candidate.
 //
-//   refine_kernel<POW2, CELLS, SlotSource> (../refine/ndt2d_refine.hip, its device half included
-//       here)  ndt2d_closure_refine: the Newton NDT registration of K jobs, each on its
+//   refine_kernel<POW2, CELLS, SlotSource> (../refine/ndt2d_refine_kernel.h)
+//       ndt2d_closure_refine: the Newton NDT registration of K jobs, each on its
 //       candidate's own map -- behind the same build launch, ONE launch with a workgroup of 256
 //       threads per job, which reads its slot's table and records through SlotSource and nothing of
 //       the grid installed in the context.  Which candidates a launch builds and which jobs run on
@@ -60,6 +60,14 @@
 // give the same bits.
 //
 // LDS of the search block: kStageBeams x {ox, oy} = 16 KB, reused for one record per wave.
+//
+// The host side.  What keeps device indices in range exists once: place_chunk_slots (the slots'
+// offsets into the launch's arrays, from slot_extent of ndt2d_closure_jobs.h, and the arrays'
+// growth) and fill_scan_table serve the three entry points -- the match's chunk [k0, k1) is the
+// plan whose candidates are k0 .. k1 - 1 -- and job_chunk is the one path of a chunk of jobs: the
+// sent scans, the stage [beams | slots | scan table | jobs | cos / sin], the upload, the build, the
+// launch, the read-back; the refinement and the verification give it their job record, their launch
+// and the scatter of what came back.  check_job_call is what both refuse, in one order.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -72,12 +80,8 @@
 #include "batch/ndt2d_batch_host.h"
 #include "batch/ndt2d_refine_jobs.h"
 #include "closure/ndt2d_closure_jobs.h"
-// (the Newton registration's kernel -- its device half, without the installed grid's object and entry points)
-#define NDT2D_REFINE_KERNEL_ONLY
-#include "refine/ndt2d_refine.hip"
-// (the match verification's kernel -- its device half, likewise)
-#define NDT2D_VERIFY_KERNEL_ONLY
-#include "verify/ndt2d_verify.hip"
+#include "refine/ndt2d_refine_kernel.h"
+#include "verify/ndt2d_verify_kernel.h"
 
 namespace ndt2d
 {
@@ -195,7 +199,7 @@ struct ClosureSlots
   }
 };
 
-// SOURCE of the Newton registration (../refine/ndt2d_refine.hip): a job's map is the slot its
+// SOURCE of the Newton registration (../refine/ndt2d_refine_kernel.h): a job's map is the slot its
 // record names -- the slot's own geometry, table and records.  Nothing of the context's installed
 // grid is read: the slots' GridDesc hold geometry only.  Entry ncell of a slot's table is 0xffff
 // (closure_build_kernel), so an off-grid point or neighbour finds no record.
@@ -224,7 +228,7 @@ void launch_slot_refine(bool pow2, dim3 blocks, dim3 threads, hipStream_t stream
 
 using SlotVerifyArgs = VerifyArgs<SlotSource>;
 
-// The match verification (../verify/ndt2d_verify.hip) on the slots: find() is "can score" for the
+// The match verification (../verify/ndt2d_verify_kernel.h) on the slots: find() is "can score" for the
 // neighbourhood and for the ray alike (a table entry exists only for cells of n >= 5), the clip, the
 // line and the origin cell run on the slot's own geometry.
 template <uint32_t CELLS>
@@ -250,17 +254,16 @@ struct ndt2d_closure : ndt2d::BatchHost
   void * d_world = nullptr, * d_cells6 = nullptr, * d_records = nullptr, * d_index = nullptr, * d_lookup = nullptr;
   size_t world_cap = 0, cells6_cap = 0, records_cap = 0, index_cap = 0, lookup_cap = 0;
   uint32_t * d_n_touched = nullptr;
-  std::vector<ndt2d::ClosureSlot> slots;
+  std::vector<ndt2d::ClosureSlot> slots;         // candidate of the call -> its geometry and counts
+  std::vector<ndt2d::ClosureSlot> chunk_slots;   // slot of the launch, placed
+  std::vector<uint32_t> match_candidates;        // ndt2d_closure_match: slot of the launch -> candidate
   // ndt2d_closure_refine
   uint32_t cells = 1;                 // the neighbourhood of a point: 1 (its own cell) or 9 (the 3 x 3 round it)
   std::vector<uint64_t> scan_first;   // scan -> its first beam within the chunk's beams (or: not sent)
   std::vector<uint32_t> sent;         // the chunk's scans in upload order
-  std::vector<ndt2d::ClosureSlot> chunk_slots;
-  // ndt2d_closure_verify: ndt2d_verify's parameters and defaults
-  uint32_t verify_cells = 1;
-  double gate_inlier = 9.0, gate_pierce = 1.0;
-  bool rays = true;
-  std::vector<size_t> job_first;      // job of the call -> its first beam within the caller's per-beam arrays
+  // ndt2d_closure_verify
+  ndt2d::VerifySettings verify;       // ndt2d_verify's, with its defaults
+  std::vector<size_t> job_first;     // job of the call -> its first beam within the caller's per-beam arrays
   std::vector<size_t> job_beams;      // job of the call -> the beams of its scan (its weight in the plan)
 };
 
@@ -369,41 +372,88 @@ int launch_build(ndt2d_closure * c, hipStream_t stream, size_t n_slots, const Cl
   return NDT2D_OK;
 }
 
-// Candidates [k0, k1) of a call whose arguments have been checked: c->slots[k] holds their geometry
-// and counts.  records_out / all_scores: the call's, whole.
-int match_chunk(ndt2d_closure * c, size_t k0, size_t k1, const size_t * cand_offsets, const size_t * ids,
-                const double * poses_xyt, const SearchTables & t, double * records_out, double * all_scores)
+// The candidates of a call: candidate k is scans ids[cand_offsets[k] .. cand_offsets[k + 1]) at poses_xyt.
+struct CandidateMaps
 {
-  ndt2d_scanstore * store = c->store;
-  const size_t n_slots = k1 - k0;
-  const size_t n_scans = cand_offsets[k1] - cand_offsets[k0];
-  const size_t n_lattice = t.n_th * t.n_lin * t.n_lin;
-  hipStream_t stream = static_cast<hipStream_t>(ndt2d_get_stream(c->h));
+  const size_t * cand_offsets;
+  const size_t * ids;
+  const double * poses_xyt;
+};
 
-  // offsets of the slots into the chunk's arrays
-  size_t n_world = 0, n_list = 0, n_lookup = 0;
-  for (size_t k = k0; k < k1; ++k)
+// The slots of one launch -- candidates[y] of the call on slot y: a chunk of a job plan
+// (ndt2d_closure_jobs.h), or the match's k0 .. k1 - 1 -- into c->chunk_slots: c->slots[k] (candidate
+// k's geometry and counts, check_candidates) with its offsets into the launch's arrays, the running
+// sums of slot_extent, and the arrays grown to hold them.  *n_map_scans: the scans of the slots' maps.
+int place_chunk_slots(ndt2d_closure * c, const std::vector<uint32_t> & candidates, size_t * n_map_scans)
+{
+  const size_t n_slots = candidates.size();
+  c->chunk_slots.resize(n_slots);
+  size_t n_world = 0, n_list = 0, n_lookup = 0, n_scans = 0;
+  for (size_t y = 0; y < n_slots; ++y)
   {
-    ClosureSlot & s = c->slots[k];
-    s.scan_first = static_cast<uint32_t>(cand_offsets[k] - cand_offsets[k0]);
+    ClosureSlot & s = c->chunk_slots[y];
+    s = c->slots[candidates[y]];
+    const ndt2d::SlotExtent e = ndt2d::slot_extent(s.n_points, s.grid.ncell);
+    s.scan_first = static_cast<uint32_t>(n_scans);
     s.world_off = static_cast<uint32_t>(n_world);
     s.list_off = static_cast<uint32_t>(n_list);
     s.lookup_off = static_cast<uint32_t>(n_lookup);
+    n_scans += s.n_scans;
     n_world += s.n_points;
-    n_list += std::max<size_t>(1, std::min<size_t>(s.n_points, s.grid.ncell));
-    n_lookup += (static_cast<size_t>(s.grid.ncell) + 2 + 7) & ~size_t(7);
+    n_list += e.list;
+    n_lookup += e.lookup;
   }
+  *n_map_scans = n_scans;
+  NDT2D_BATCH_HIP(c, grow_device(&c->d_world, &c->world_cap, std::max<size_t>(1, n_world) * 2 * sizeof(double)));
+  NDT2D_BATCH_HIP(c, grow_device(&c->d_cells6, &c->cells6_cap, n_list * 6 * sizeof(double)));
+  NDT2D_BATCH_HIP(c, grow_device(&c->d_records, &c->records_cap, n_list * 6 * sizeof(double)));
+  NDT2D_BATCH_HIP(c, grow_device(&c->d_index, &c->index_cap, n_list * sizeof(uint32_t)));
+  NDT2D_BATCH_HIP(c, grow_device(&c->d_lookup, &c->lookup_cap, n_lookup * sizeof(uint16_t)));
+  return NDT2D_OK;
+}
+
+// The scan table of the slots' maps (c->chunk_slots: place_chunk_slots), as the build reads it.
+void fill_scan_table(const ndt2d_closure * c, const std::vector<uint32_t> & candidates, const CandidateMaps & m, SmallScan * table)
+{
+  const ndt2d_scanstore * store = c->store;
+  for (size_t y = 0; y < candidates.size(); ++y)
+  {
+    const size_t k = candidates[y];
+    uint32_t first = 0;
+    for (size_t j = m.cand_offsets[k]; j < m.cand_offsets[k + 1]; ++j)
+    {
+      SmallScan & sc = table[c->chunk_slots[y].scan_first + (j - m.cand_offsets[k])];
+      sc.x = m.poses_xyt[3 * j];
+      sc.y = m.poses_xyt[3 * j + 1];
+      ndt2d_cos_sin(m.poses_xyt[3 * j + 2], &sc.c, &sc.s);   // (src/ndt_model.cpp:135-136, host libm)
+      sc.pool_offset = store->offset[m.ids[j]];
+      sc.first = first;
+      first += store->count[m.ids[j]];
+    }
+  }
+}
+
+// Candidates [k0, k1) of a call whose arguments have been checked: c->slots[k] holds their geometry
+// and counts.  records_out / all_scores: the call's, whole.
+int match_chunk(ndt2d_closure * c, size_t k0, size_t k1, const CandidateMaps & m, const SearchTables & t, double * records_out,
+                double * all_scores)
+{
+  const size_t n_slots = k1 - k0;
+  const size_t n_lattice = t.n_th * t.n_lin * t.n_lin;
+  hipStream_t stream = static_cast<hipStream_t>(ndt2d_get_stream(c->h));
+
+  // the chunk as a plan: slot y is candidate k0 + y
+  c->match_candidates.resize(n_slots);
+  for (size_t y = 0; y < n_slots; ++y) c->match_candidates[y] = static_cast<uint32_t>(k0 + y);
+  size_t n_scans = 0;
+  const int prc = place_chunk_slots(c, c->match_candidates, &n_scans);
+  if (prc != NDT2D_OK) return prc;
 
   // [tables | beams | slots | scan table]
   const size_t n_tables = 3 * t.n_th + t.n_lin;
   const size_t off_beams = (n_tables + 1) & ~size_t(1), off_slots = off_beams + 2 * t.n_beams;   // (beams: 16-byte loads)
   const size_t off_scans = off_slots + n_slots * (sizeof(ClosureSlot) / sizeof(double));
   const size_t n_stage = off_scans + 5 * n_scans;
-  NDT2D_BATCH_HIP(c, grow_device(&c->d_world, &c->world_cap, std::max<size_t>(1, n_world) * 2 * sizeof(double)));
-  NDT2D_BATCH_HIP(c, grow_device(&c->d_cells6, &c->cells6_cap, n_list * 6 * sizeof(double)));
-  NDT2D_BATCH_HIP(c, grow_device(&c->d_records, &c->records_cap, n_list * 6 * sizeof(double)));
-  NDT2D_BATCH_HIP(c, grow_device(&c->d_index, &c->index_cap, n_list * sizeof(uint32_t)));
-  NDT2D_BATCH_HIP(c, grow_device(&c->d_lookup, &c->lookup_cap, n_lookup * sizeof(uint16_t)));
   const size_t n_out = n_slots * (kRec + (all_scores != nullptr ? n_lattice : 0));
   NDT2D_BATCH_HIP(c, ndt2d::batch_grow(c, n_stage, n_slots, t.n_th, n_out));
 
@@ -413,22 +463,8 @@ int match_chunk(ndt2d_closure * c, size_t k0, size_t k1, const size_t * cand_off
   std::memcpy(st + 2 * t.n_th, t.sin_th, t.n_th * sizeof(double));
   std::memcpy(st + 3 * t.n_th, t.dlin, t.n_lin * sizeof(double));
   std::memcpy(st + off_beams, t.beams_xy, 2 * t.n_beams * sizeof(double));
-  std::memcpy(st + off_slots, c->slots.data() + k0, n_slots * sizeof(ClosureSlot));
-  SmallScan * table = reinterpret_cast<SmallScan *>(st + off_scans);
-  for (size_t k = k0; k < k1; ++k)
-  {
-    uint32_t first = 0;
-    for (size_t j = cand_offsets[k]; j < cand_offsets[k + 1]; ++j)
-    {
-      SmallScan & sc = table[j - cand_offsets[k0]];
-      sc.x = poses_xyt[3 * j];
-      sc.y = poses_xyt[3 * j + 1];
-      ndt2d_cos_sin(poses_xyt[3 * j + 2], &sc.c, &sc.s);   // (src/ndt_model.cpp:135-136, host libm)
-      sc.pool_offset = store->offset[ids[j]];
-      sc.first = first;
-      first += store->count[ids[j]];
-    }
-  }
+  std::memcpy(st + off_slots, c->chunk_slots.data(), n_slots * sizeof(ClosureSlot));
+  fill_scan_table(c, c->match_candidates, m, reinterpret_cast<SmallScan *>(st + off_scans));
 
   NDT2D_BATCH_HIP(c, hipMemcpyAsync(c->d_stage, st, n_stage * sizeof(double), hipMemcpyHostToDevice, stream));
   c->timed = false;
@@ -457,71 +493,89 @@ int match_chunk(ndt2d_closure * c, size_t k0, size_t k1, const size_t * cand_off
   a.scores = all_scores != nullptr ? c->d_out + n_slots * kRec : nullptr;
   a.partials = static_cast<double *>(c->d_partials);
   const dim3 grid(a.n_th, static_cast<uint32_t>(n_slots));
-  ndt2d::launch_batch_search(ndt2d::sum_chunks(a.slots.n_beams), c->slots[k0].grid.pow2 != 0, grid,
+  ndt2d::launch_batch_search(ndt2d::sum_chunks(a.slots.n_beams), c->chunk_slots[0].grid.pow2 != 0, grid,
                              dim3(ndt2d::batch_search_threads(t.n_lin * t.n_lin)), stream, a);
   NDT2D_BATCH_HIP(c, hipGetLastError());
   if (c->timing) NDT2D_BATCH_HIP(c, hipEventRecord(c->ev[2], stream));
   return ndt2d::batch_reduce_and_fetch(c, stream, k0, n_slots, a.n_th, n_lattice, -1, records_out, all_scores);
 }
 
-// The slots of one chunk of a job plan (ndt2d_closure_jobs.h) into c->chunk_slots, with their
-// offsets into the chunk's arrays as match_chunk lays them out, and the arrays grown to hold them.
-// c->slots[k] holds candidate k's geometry and counts.  *n_map_scans: the scans of the chunk's maps.
-int place_chunk_slots(ndt2d_closure * c, const ndt2d::ClosureJobChunk & plan, size_t * n_map_scans)
+// What a chunk's launch reads, on the device: the built slots, the jobs' records, the cos / sin
+// pairs of their headings and the chunk's beams.
+struct ChunkOnDevice
 {
-  const size_t n_slots = plan.candidates.size();
-  c->chunk_slots.resize(n_slots);
-  size_t n_world = 0, n_list = 0, n_lookup = 0, n_scans = 0;
-  for (size_t y = 0; y < n_slots; ++y)
-  {
-    const size_t k = plan.candidates[y];
-    ClosureSlot & s = c->chunk_slots[y];
-    s = c->slots[k];
-    s.scan_first = static_cast<uint32_t>(n_scans);
-    s.world_off = static_cast<uint32_t>(n_world);
-    s.list_off = static_cast<uint32_t>(n_list);
-    s.lookup_off = static_cast<uint32_t>(n_lookup);
-    n_scans += s.n_scans;
-    n_world += s.n_points;
-    n_list += std::max<size_t>(1, std::min<size_t>(s.n_points, s.grid.ncell));
-    n_lookup += (static_cast<size_t>(s.grid.ncell) + 2 + 7) & ~size_t(7);
-  }
-  *n_map_scans = n_scans;
-  NDT2D_BATCH_HIP(c, grow_device(&c->d_world, &c->world_cap, std::max<size_t>(1, n_world) * 2 * sizeof(double)));
-  NDT2D_BATCH_HIP(c, grow_device(&c->d_cells6, &c->cells6_cap, n_list * 6 * sizeof(double)));
-  NDT2D_BATCH_HIP(c, grow_device(&c->d_records, &c->records_cap, n_list * 6 * sizeof(double)));
-  NDT2D_BATCH_HIP(c, grow_device(&c->d_index, &c->index_cap, n_list * sizeof(uint32_t)));
-  NDT2D_BATCH_HIP(c, grow_device(&c->d_lookup, &c->lookup_cap, n_lookup * sizeof(uint16_t)));
-  return NDT2D_OK;
-}
+  ndt2d::SlotSource source;
+  const double * jobs, * trig, * beams_xy;
+  dim3 blocks;   // a block per job
+  bool pow2;     // of every slot
+  hipStream_t stream;
+};
 
-// The scan table of the chunk's maps (c->chunk_slots: place_chunk_slots), as the build reads it.
-void fill_scan_table(const ndt2d_closure * c, const ndt2d::ClosureJobChunk & plan, const size_t * cand_offsets,
-                     const size_t * ids, const double * poses_xyt, SmallScan * table)
+// One chunk of a job plan -- the refinement's or the verification's -- of a call whose arguments
+// have been checked (c->slots[k]: candidate k's geometry and counts): one upload, [beams | slots |
+// scan table | jobs | cos / sin pairs], the build of the chunk's candidates, the launch on its jobs
+// -- a block each, on the slot its record names -- and one read-back of n_back doubles into
+// c->h_out, waited for.  t: the call's jobs and scans (jobs_xyt, scan_of, beams_xy, beam_offsets,
+// n_scans).  write_job(b, k, first, to): the record (job_doubles doubles) of block b, job k of the
+// call, whose scan's first beam within the chunk's beams is `first`.  launch(d): the kernel on
+// d.stream.  The events: before the build, behind it, behind the launch.
+template <class CALL, class WRITE_JOB, class LAUNCH>
+int job_chunk(ndt2d_closure * c, const ndt2d::ClosureJobChunk & plan, const CandidateMaps & m, const CALL & t, size_t job_doubles,
+              size_t n_back, WRITE_JOB write_job, LAUNCH launch)
 {
-  const ndt2d_scanstore * store = c->store;
-  for (size_t y = 0; y < plan.candidates.size(); ++y)
+  const size_t n_slots = plan.candidates.size(), n_jobs = plan.jobs.size();
+  hipStream_t stream = static_cast<hipStream_t>(ndt2d_get_stream(c->h));
+
+  size_t n_map_scans = 0;
+  const int prc = place_chunk_slots(c, plan.candidates, &n_map_scans);
+  if (prc != NDT2D_OK) return prc;
+
+  // the scans this chunk's jobs name, each once, in the order the jobs first name them
+  const size_t n_beams = ndt2d::refine_jobs::plan_sent_scans(
+    n_jobs, [&](size_t b) { return static_cast<size_t>(plan.jobs[b]); }, [&](size_t k) { return t.scan_of(k); }, t.beam_offsets,
+    t.n_scans, c->scan_first, c->sent);
+
+  const size_t off_slots = 2 * n_beams;   // (beams in front: 16-byte loads)
+  const size_t off_scans = off_slots + n_slots * (sizeof(ClosureSlot) / sizeof(double));
+  const size_t off_jobs = off_scans + 5 * n_map_scans;
+  const size_t off_trig = off_jobs + n_jobs * job_doubles;
+  const size_t n_stage = off_trig + 2 * n_jobs;
+  NDT2D_BATCH_HIP(c, ndt2d::grow_pair(&c->h_stage, &c->d_stage, &c->stage_cap, n_stage));
+  NDT2D_BATCH_HIP(c, ndt2d::grow_pair(&c->h_out, &c->d_out, &c->out_cap, n_back));
+
+  double * st = c->h_stage;
+  ndt2d::refine_jobs::copy_sent_scans(c->sent, c->scan_first, t.beams_xy, t.beam_offsets, st);
+  std::memcpy(st + off_slots, c->chunk_slots.data(), n_slots * sizeof(ClosureSlot));
+  fill_scan_table(c, plan.candidates, m, reinterpret_cast<SmallScan *>(st + off_scans));
+  for (size_t b = 0; b < n_jobs; ++b)
   {
-    const size_t k = plan.candidates[y];
-    uint32_t first = 0;
-    for (size_t j = cand_offsets[k]; j < cand_offsets[k + 1]; ++j)
-    {
-      SmallScan & sc = table[c->chunk_slots[y].scan_first + (j - cand_offsets[k])];
-      sc.x = poses_xyt[3 * j];
-      sc.y = poses_xyt[3 * j + 1];
-      ndt2d_cos_sin(poses_xyt[3 * j + 2], &sc.c, &sc.s);   // (src/ndt_model.cpp:135-136, host libm)
-      sc.pool_offset = store->offset[ids[j]];
-      sc.first = first;
-      first += store->count[ids[j]];
-    }
+    const size_t k = plan.jobs[b];
+    write_job(b, k, c->scan_first[t.scan_of(k)], st + off_jobs + b * job_doubles);
+    // cos / sin of the job's heading from the host libm, as everywhere in this library
+    ndt2d_cos_sin(t.jobs_xyt[3 * k + 2], st + off_trig + 2 * b, st + off_trig + 2 * b + 1);
   }
+  NDT2D_BATCH_HIP(c, hipMemcpyAsync(c->d_stage, st, n_stage * sizeof(double), hipMemcpyHostToDevice, stream));
+  c->timed = false;
+  if (c->timing) NDT2D_BATCH_HIP(c, hipEventRecord(c->ev[0], stream));
+
+  ndt2d::ClosureBuildArgs b{};
+  const int brc = launch_build(c, stream, n_slots, reinterpret_cast<const ClosureSlot *>(c->d_stage + off_slots),
+                               reinterpret_cast<const SmallScan *>(c->d_stage + off_scans), &b);
+  if (brc != NDT2D_OK) return brc;
+  if (c->timing) NDT2D_BATCH_HIP(c, hipEventRecord(c->ev[1], stream));
+
+  launch(ChunkOnDevice{{b.slots, b.lookup, b.records}, c->d_stage + off_jobs, c->d_stage + off_trig, c->d_stage,
+                       dim3(static_cast<uint32_t>(n_jobs)), c->chunk_slots[0].grid.pow2 != 0, stream});
+  NDT2D_BATCH_HIP(c, hipGetLastError());
+  if (c->timing) NDT2D_BATCH_HIP(c, hipEventRecord(c->ev[2], stream));
+  NDT2D_BATCH_HIP(c, hipMemcpyAsync(c->h_out, c->d_out, n_back * sizeof(double), hipMemcpyDeviceToHost, stream));
+  NDT2D_BATCH_HIP(c, hipStreamSynchronize(stream));
+  c->timed = c->timing;
+  return NDT2D_OK;
 }
 
 struct RefineCall
 {
-  const size_t * cand_offsets;
-  const size_t * ids;
-  const double * poses_xyt;
   const double * jobs_xyt;
   const uint32_t * job_scan;   // NULL: job k uses scan k
   const double * beams_xy;
@@ -531,81 +585,33 @@ struct RefineCall
   size_t scan_of(size_t k) const { return job_scan != nullptr ? job_scan[k] : k; }
 };
 
-// One chunk of ndt2d_closure_refine's plan, of a call whose arguments have been checked: c->slots[k]
-// holds candidate k's geometry and counts.  One upload, the build of the chunk's candidates, the
-// refinement of its jobs -- a block each, on the slot its record names -- and one read-back.
-// records_out: the call's, whole.
-int refine_chunk(ndt2d_closure * c, const ndt2d::ClosureJobChunk & plan, const RefineCall & t, double * records_out)
+// One chunk of ndt2d_closure_refine's plan.  records_out: the call's, whole.
+int refine_chunk(ndt2d_closure * c, const ndt2d::ClosureJobChunk & plan, const CandidateMaps & m, const RefineCall & t,
+                 double * records_out)
 {
   using ndt2d::RefineJob;
   using ndt2d::kRefineRec;
-  const size_t n_slots = plan.candidates.size(), n_jobs = plan.jobs.size();
-  hipStream_t stream = static_cast<hipStream_t>(ndt2d_get_stream(c->h));
-
-  size_t n_map_scans = 0;
-  const int prc = place_chunk_slots(c, plan, &n_map_scans);
-  if (prc != NDT2D_OK) return prc;
-
-  // the scans this chunk's jobs name, each once, in the order the jobs first name them
-  const size_t n_beams = ndt2d::refine_jobs::plan_sent_scans(
-    n_jobs, [&](size_t b) { return static_cast<size_t>(plan.jobs[b]); }, [&](size_t k) { return t.scan_of(k); }, t.beam_offsets,
-    t.n_scans, c->scan_first, c->sent);
-
-  // the one upload of the chunk: [beams | slots | scan table | jobs | cos / sin pairs]
-  const size_t off_slots = 2 * n_beams;   // (beams in front: 16-byte loads)
-  const size_t off_scans = off_slots + n_slots * (sizeof(ClosureSlot) / sizeof(double));
-  const size_t off_jobs = off_scans + 5 * n_map_scans;
-  const size_t off_trig = off_jobs + n_jobs * ndt2d::kRefineJobDoubles;
-  const size_t n_stage = off_trig + 2 * n_jobs;
-  NDT2D_BATCH_HIP(c, ndt2d::grow_pair(&c->h_stage, &c->d_stage, &c->stage_cap, n_stage));
-  NDT2D_BATCH_HIP(c, ndt2d::grow_pair(&c->h_out, &c->d_out, &c->out_cap, n_jobs * kRefineRec));
-
-  double * st = c->h_stage;
-  for (const uint32_t sc : c->sent)
-  {
-    std::memcpy(st + 2 * c->scan_first[sc], t.beams_xy + 2 * t.beam_offsets[sc],
-                2 * (t.beam_offsets[sc + 1] - t.beam_offsets[sc]) * sizeof(double));
-  }
-  std::memcpy(st + off_slots, c->chunk_slots.data(), n_slots * sizeof(ClosureSlot));
-  fill_scan_table(c, plan, t.cand_offsets, t.ids, t.poses_xyt, reinterpret_cast<SmallScan *>(st + off_scans));
-  for (size_t b = 0; b < n_jobs; ++b)
-  {
-    const size_t k = plan.jobs[b], sc = t.scan_of(k);
-    const double * p = t.jobs_xyt + 3 * k;
-    reinterpret_cast<RefineJob *>(st + off_jobs)[b] =
-      RefineJob{p[0], p[1], p[2], static_cast<uint32_t>(t.beam_offsets[sc + 1] - t.beam_offsets[sc]), plan.job_slot[b],
-                c->scan_first[sc]};
-    // cos / sin of the start heading from the host libm, as everywhere in this library
-    ndt2d_cos_sin(p[2], st + off_trig + 2 * b, st + off_trig + 2 * b + 1);
-  }
-  NDT2D_BATCH_HIP(c, hipMemcpyAsync(c->d_stage, st, n_stage * sizeof(double), hipMemcpyHostToDevice, stream));
-  c->timed = false;
-  if (c->timing) NDT2D_BATCH_HIP(c, hipEventRecord(c->ev[0], stream));
-
-  ndt2d::ClosureBuildArgs b{};
-  const int brc = launch_build(c, stream, n_slots, reinterpret_cast<const ClosureSlot *>(c->d_stage + off_slots),
-                               reinterpret_cast<const SmallScan *>(c->d_stage + off_scans), &b);
-  if (brc != NDT2D_OK) return brc;
-  if (c->timing) NDT2D_BATCH_HIP(c, hipEventRecord(c->ev[1], stream));
-
-  ndt2d::SlotRefineArgs a{};
-  a.source.slots = b.slots;
-  a.source.lookup = b.lookup;
-  a.source.records = b.records;
-  a.jobs = reinterpret_cast<const RefineJob *>(c->d_stage + off_jobs);
-  a.trig = c->d_stage + off_trig;
-  a.beams_xy = c->d_stage;
-  a.rules = t.rules;
-  a.records = c->d_out;
-  const dim3 blocks(static_cast<uint32_t>(n_jobs)), threads(ndt2d::kRefineThreads);
-  const bool pow2 = c->chunk_slots[0].grid.pow2 != 0;
-  if (c->cells == 9) ndt2d::launch_slot_refine<9>(pow2, blocks, threads, stream, a);
-  else ndt2d::launch_slot_refine<1>(pow2, blocks, threads, stream, a);
-  NDT2D_BATCH_HIP(c, hipGetLastError());
-  if (c->timing) NDT2D_BATCH_HIP(c, hipEventRecord(c->ev[2], stream));
-  NDT2D_BATCH_HIP(c, hipMemcpyAsync(c->h_out, c->d_out, n_jobs * kRefineRec * sizeof(double), hipMemcpyDeviceToHost, stream));
-  NDT2D_BATCH_HIP(c, hipStreamSynchronize(stream));
-  c->timed = c->timing;
+  const size_t n_jobs = plan.jobs.size();
+  const int rc = job_chunk(
+    c, plan, m, t, ndt2d::kRefineJobDoubles, n_jobs * kRefineRec,
+    [&](size_t b, size_t k, uint64_t first, double * to) {
+      const double * p = t.jobs_xyt + 3 * k;
+      const size_t sc = t.scan_of(k);
+      *reinterpret_cast<RefineJob *>(to) =
+        RefineJob{p[0], p[1], p[2], static_cast<uint32_t>(t.beam_offsets[sc + 1] - t.beam_offsets[sc]), plan.job_slot[b], first};
+    },
+    [&](const ChunkOnDevice & d) {
+      ndt2d::SlotRefineArgs a{};
+      a.source = d.source;
+      a.jobs = reinterpret_cast<const RefineJob *>(d.jobs);
+      a.trig = d.trig;
+      a.beams_xy = d.beams_xy;
+      a.rules = t.rules;
+      a.records = c->d_out;
+      if (c->cells == 9) ndt2d::launch_slot_refine<9>(d.pow2, d.blocks, dim3(ndt2d::kRefineThreads), d.stream, a);
+      else ndt2d::launch_slot_refine<1>(d.pow2, d.blocks, dim3(ndt2d::kRefineThreads), d.stream, a);
+    });
+  if (rc != NDT2D_OK) return rc;
   for (size_t bj = 0; bj < n_jobs; ++bj)
   {
     std::memcpy(records_out + static_cast<size_t>(plan.jobs[bj]) * kRefineRec, c->h_out + bj * kRefineRec, kRefineRec * sizeof(double));
@@ -613,97 +619,40 @@ int refine_chunk(ndt2d_closure * c, const ndt2d::ClosureJobChunk & plan, const R
   return NDT2D_OK;
 }
 
-struct SlotVerifyCall
-{
-  const size_t * cand_offsets;
-  const size_t * ids;
-  const double * poses_xyt;
-  ndt2d::VerifyCall v;   // the jobs, the scans and the outputs, as ndt2d_verify_run takes them
-};
-
-// One chunk of ndt2d_closure_verify's plan, of a call whose arguments have been checked: one upload,
-// the build of the chunk's candidates, the verification of its jobs -- a block each, on the slot its
-// record names -- and one read-back.  The chunk's per-beam results lie job after job in the plan's
-// order; c->job_first[k]: where job k's go in the caller's arrays.
-int verify_chunk(ndt2d_closure * c, const ndt2d::ClosureJobChunk & plan, const SlotVerifyCall & t)
+// One chunk of ndt2d_closure_verify's plan.  v: the jobs, the scans and the outputs, as
+// ndt2d_verify_run takes them.  The chunk's per-beam results lie job after job in the plan's order;
+// c->job_first[k]: where job k's go in the caller's arrays.
+int verify_chunk(ndt2d_closure * c, const ndt2d::ClosureJobChunk & plan, const CandidateMaps & m, const ndt2d::VerifyCall & v)
 {
   using ndt2d::VerifyJob;
   constexpr size_t kVerRec = ndt2d::kVerifyRec;
-  const ndt2d::VerifyCall & v = t.v;
-  const size_t n_slots = plan.candidates.size(), n_jobs = plan.jobs.size();
-  hipStream_t stream = static_cast<hipStream_t>(ndt2d_get_stream(c->h));
-
-  size_t n_map_scans = 0;
-  const int prc = place_chunk_slots(c, plan, &n_map_scans);
-  if (prc != NDT2D_OK) return prc;
-
-  // the scans this chunk's jobs name, each once, in the order the jobs first name them
-  const size_t n_beams = ndt2d::refine_jobs::plan_sent_scans(
-    n_jobs, [&](size_t b) { return static_cast<size_t>(plan.jobs[b]); }, [&](size_t k) { return v.scan_of(k); }, v.beam_offsets,
-    v.n_scans, c->scan_first, c->sent);
+  const size_t n_jobs = plan.jobs.size();
   size_t n_out = 0;
   for (size_t b = 0; b < n_jobs; ++b) n_out += v.beams_of(plan.jobs[b]);
-
-  // the one upload of the chunk: [beams | slots | scan table | jobs | cos / sin pairs]
-  const size_t off_slots = 2 * n_beams;   // (beams in front: 16-byte loads)
-  const size_t off_scans = off_slots + n_slots * (sizeof(ClosureSlot) / sizeof(double));
-  const size_t off_jobs = off_scans + 5 * n_map_scans;
-  const size_t off_trig = off_jobs + n_jobs * ndt2d::kVerifyJobDoubles;
-  const size_t n_stage = off_trig + 2 * n_jobs;
   const ndt2d::VerifyOutLayout out = ndt2d::verify_out_layout(n_jobs, n_out, v);
-  NDT2D_BATCH_HIP(c, ndt2d::grow_pair(&c->h_stage, &c->d_stage, &c->stage_cap, n_stage));
-  NDT2D_BATCH_HIP(c, ndt2d::grow_pair(&c->h_out, &c->d_out, &c->out_cap, out.total));
-
-  double * st = c->h_stage;
-  for (const uint32_t sc : c->sent)
-  {
-    std::memcpy(st + 2 * c->scan_first[sc], v.beams_xy + 2 * v.beam_offsets[sc],
-                2 * (v.beam_offsets[sc + 1] - v.beam_offsets[sc]) * sizeof(double));
-  }
-  std::memcpy(st + off_slots, c->chunk_slots.data(), n_slots * sizeof(ClosureSlot));
-  fill_scan_table(c, plan, t.cand_offsets, t.ids, t.poses_xyt, reinterpret_cast<SmallScan *>(st + off_scans));
   size_t out_first = 0;
-  for (size_t b = 0; b < n_jobs; ++b)
-  {
-    const size_t k = plan.jobs[b];
-    const double * p = v.jobs_xyt + 3 * k;
-    reinterpret_cast<VerifyJob *>(st + off_jobs)[b] =
-      VerifyJob{p[0], p[1], static_cast<uint32_t>(v.beams_of(k)), plan.job_slot[b], c->scan_first[v.scan_of(k)], out_first};
-    out_first += v.beams_of(k);
-    // cos / sin of the heading from the host libm, as everywhere in this library
-    ndt2d_cos_sin(p[2], st + off_trig + 2 * b, st + off_trig + 2 * b + 1);
-  }
-  NDT2D_BATCH_HIP(c, hipMemcpyAsync(c->d_stage, st, n_stage * sizeof(double), hipMemcpyHostToDevice, stream));
-  c->timed = false;
-  if (c->timing) NDT2D_BATCH_HIP(c, hipEventRecord(c->ev[0], stream));
-
-  ndt2d::ClosureBuildArgs b{};
-  const int brc = launch_build(c, stream, n_slots, reinterpret_cast<const ClosureSlot *>(c->d_stage + off_slots),
-                               reinterpret_cast<const SmallScan *>(c->d_stage + off_scans), &b);
-  if (brc != NDT2D_OK) return brc;
-  if (c->timing) NDT2D_BATCH_HIP(c, hipEventRecord(c->ev[1], stream));
-
-  ndt2d::SlotVerifyArgs a{};
-  a.source.slots = b.slots;
-  a.source.lookup = b.lookup;
-  a.source.records = b.records;
-  a.jobs = reinterpret_cast<const VerifyJob *>(c->d_stage + off_jobs);
-  a.trig = c->d_stage + off_trig;
-  a.beams_xy = c->d_stage;
-  a.rules = ndt2d::VerifyRules{c->gate_inlier, c->gate_pierce, c->rays ? 1u : 0u};
-  a.records = reinterpret_cast<uint32_t *>(c->d_out);
-  a.beam_m2 = v.beam_m2_out != nullptr ? c->d_out + out.m2 : nullptr;
-  a.beam_cells = v.beam_cells_out != nullptr ? reinterpret_cast<uint32_t *>(c->d_out + out.cells) : nullptr;
-  a.beam_class = v.beam_class_out != nullptr ? reinterpret_cast<uint8_t *>(c->d_out + out.classes) : nullptr;
-  const dim3 blocks(static_cast<uint32_t>(n_jobs)), threads(ndt2d::kVerifyThreads);
-  const bool pow2 = c->chunk_slots[0].grid.pow2 != 0;
-  if (c->verify_cells == 9) ndt2d::launch_slot_verify<9>(pow2, blocks, threads, stream, a);
-  else ndt2d::launch_slot_verify<1>(pow2, blocks, threads, stream, a);
-  NDT2D_BATCH_HIP(c, hipGetLastError());
-  if (c->timing) NDT2D_BATCH_HIP(c, hipEventRecord(c->ev[2], stream));
-  NDT2D_BATCH_HIP(c, hipMemcpyAsync(c->h_out, c->d_out, out.total * sizeof(double), hipMemcpyDeviceToHost, stream));
-  NDT2D_BATCH_HIP(c, hipStreamSynchronize(stream));
-  c->timed = c->timing;
+  const int rc = job_chunk(
+    c, plan, m, v, ndt2d::kVerifyJobDoubles, out.total,
+    [&](size_t b, size_t k, uint64_t first, double * to) {
+      const double * p = v.jobs_xyt + 3 * k;
+      *reinterpret_cast<VerifyJob *>(to) = VerifyJob{p[0], p[1], static_cast<uint32_t>(v.beams_of(k)), plan.job_slot[b], first, out_first};
+      out_first += v.beams_of(k);
+    },
+    [&](const ChunkOnDevice & d) {
+      ndt2d::SlotVerifyArgs a{};
+      a.source = d.source;
+      a.jobs = reinterpret_cast<const VerifyJob *>(d.jobs);
+      a.trig = d.trig;
+      a.beams_xy = d.beams_xy;
+      a.rules = c->verify.rules();
+      a.records = reinterpret_cast<uint32_t *>(c->d_out);
+      a.beam_m2 = v.beam_m2_out != nullptr ? c->d_out + out.m2 : nullptr;
+      a.beam_cells = v.beam_cells_out != nullptr ? reinterpret_cast<uint32_t *>(c->d_out + out.cells) : nullptr;
+      a.beam_class = v.beam_class_out != nullptr ? reinterpret_cast<uint8_t *>(c->d_out + out.classes) : nullptr;
+      if (c->verify.cells == 9) ndt2d::launch_slot_verify<9>(d.pow2, d.blocks, dim3(ndt2d::kVerifyThreads), d.stream, a);
+      else ndt2d::launch_slot_verify<1>(d.pow2, d.blocks, dim3(ndt2d::kVerifyThreads), d.stream, a);
+    });
+  if (rc != NDT2D_OK) return rc;
   const uint32_t * records = reinterpret_cast<const uint32_t *>(c->h_out);
   const uint8_t * classes = reinterpret_cast<const uint8_t *>(c->h_out + out.classes);
   size_t at = 0;
@@ -715,6 +664,47 @@ int verify_chunk(ndt2d_closure * c, const ndt2d::ClosureJobChunk & plan, const S
     if (v.beam_cells_out != nullptr) std::memcpy(v.beam_cells_out + 2 * to, c->h_out + out.cells + at, n * 2 * sizeof(uint32_t));
     if (v.beam_class_out != nullptr) std::memcpy(v.beam_class_out + to, classes + at, n);
     at += n;
+  }
+  return NDT2D_OK;
+}
+
+// What ndt2d_closure_refine and ndt2d_closure_verify (`entry`) refuse, every check before anything
+// is launched: null arguments, the grid's parameters, the rules, every scan and every job -- what
+// ndt2d_refine_run refuses, one text: batch/ndt2d_refine_jobs.h (the verification gives rules it
+// takes) -- every candidate, as ndt2d_closure_match does, and the jobs' candidates.
+int check_job_call(ndt2d_closure * c, const char * entry, size_t n_candidates, const CandidateMaps & m, double ndt_resolution,
+                   double range_max, const double * jobs_xyt, const uint32_t * job_scan, const uint32_t * job_candidate,
+                   size_t n_jobs, const double * beams_xy, const size_t * beam_offsets, size_t n_scans, const void * records_out,
+                   uint32_t max_evals, double tol_lin, double tol_ang)
+{
+  const std::string who = std::string(entry) + ": ";
+  if (m.cand_offsets == nullptr || m.ids == nullptr || m.poses_xyt == nullptr || jobs_xyt == nullptr || records_out == nullptr ||
+      beams_xy == nullptr || beam_offsets == nullptr)
+  {
+    return batch_fail(c, NDT2D_ERR_INVALID, who + "null argument");
+  }
+  if (!(ndt_resolution > 0.0) || !std::isfinite(ndt_resolution) || !std::isfinite(range_max))
+  {
+    return batch_fail(c, NDT2D_ERR_INVALID, who + "bad resolution or range_max");
+  }
+  if (n_candidates >= (1u << 24)) return batch_fail(c, NDT2D_ERR_INVALID, who + "bad argument (n_candidates)");
+  if (job_candidate == nullptr && n_candidates != n_jobs)
+  {
+    return batch_fail(c, NDT2D_ERR_INVALID,
+                      who + "bad argument (no job_candidate: job k uses candidate k, n_candidates must equal n_jobs)");
+  }
+  const std::string refusal =
+    ndt2d::refine_jobs::refusal(entry, jobs_xyt, job_scan, n_jobs, beam_offsets, n_scans, max_evals, tol_lin, tol_ang);
+  if (!refusal.empty()) return batch_fail(c, NDT2D_ERR_INVALID, refusal);
+  const int crc = check_candidates(c, entry, n_candidates, m.cand_offsets, m.ids, m.poses_xyt, ndt_resolution, range_max);
+  if (crc != NDT2D_OK) return crc;
+  for (size_t k = 0; k < n_jobs && job_candidate != nullptr; ++k)
+  {
+    if (job_candidate[k] >= n_candidates)
+    {
+      return batch_fail(c, NDT2D_ERR_INVALID, who + "job " + std::to_string(k) + ": candidate " + std::to_string(job_candidate[k]) +
+                                             " of " + std::to_string(n_candidates));
+    }
   }
   return NDT2D_OK;
 }
@@ -811,7 +801,7 @@ int ndt2d_closure_match(ndt2d_closure * c, size_t n_candidates, const size_t * c
   for (size_t k0 = 0; k0 < n_candidates; k0 += c->max_candidates)
   {
     const size_t k1 = std::min(n_candidates, k0 + c->max_candidates);
-    const int rc = match_chunk(c, k0, k1, cand_offsets, ids, poses_xyt, t, records_out, all_scores);
+    const int rc = match_chunk(c, k0, k1, {cand_offsets, ids, poses_xyt}, t, records_out, all_scores);
     if (rc != NDT2D_OK) return rc;
   }
   return NDT2D_OK;
@@ -849,42 +839,16 @@ int ndt2d_closure_refine(ndt2d_closure * c, size_t n_candidates, const size_t * 
   NDT2D_C_TRY
   if (c == nullptr) return NDT2D_ERR_INVALID;
   if (n_jobs == 0) return NDT2D_OK;
-  if (cand_offsets == nullptr || ids == nullptr || poses_xyt == nullptr || jobs_xyt == nullptr || records_out == nullptr ||
-      beams_xy == nullptr || beam_offsets == nullptr)
-  {
-    return batch_fail(c, NDT2D_ERR_INVALID, "ndt2d_closure_refine: null argument");
-  }
-  if (!(ndt_resolution > 0.0) || !std::isfinite(ndt_resolution) || !std::isfinite(range_max))
-  {
-    return batch_fail(c, NDT2D_ERR_INVALID, "ndt2d_closure_refine: bad resolution or range_max");
-  }
-  if (n_candidates >= (1u << 24)) return batch_fail(c, NDT2D_ERR_INVALID, "ndt2d_closure_refine: bad argument (n_candidates)");
-  if (job_candidate == nullptr && n_candidates != n_jobs)
-  {
-    return batch_fail(c, NDT2D_ERR_INVALID,
-                      "ndt2d_closure_refine: bad argument (no job_candidate: job k uses candidate k, n_candidates must equal n_jobs)");
-  }
-  // the rules, every scan, every job and every candidate are checked before anything is launched:
-  // what ndt2d_refine_run refuses (one text: batch/ndt2d_refine_jobs.h), what ndt2d_closure_match does
-  const std::string refusal = ndt2d::refine_jobs::refusal("ndt2d_closure_refine", jobs_xyt, job_scan, n_jobs, beam_offsets, n_scans,
-                                                         max_evals, tol_lin, tol_ang);
-  if (!refusal.empty()) return batch_fail(c, NDT2D_ERR_INVALID, refusal);
-  const int crc = check_candidates(c, "ndt2d_closure_refine", n_candidates, cand_offsets, ids, poses_xyt, ndt_resolution, range_max);
+  const CandidateMaps m{cand_offsets, ids, poses_xyt};
+  const int crc = check_job_call(c, "ndt2d_closure_refine", n_candidates, m, ndt_resolution, range_max, jobs_xyt, job_scan,
+                                 job_candidate, n_jobs, beams_xy, beam_offsets, n_scans, records_out, max_evals, tol_lin, tol_ang);
   if (crc != NDT2D_OK) return crc;
-  for (size_t k = 0; k < n_jobs && job_candidate != nullptr; ++k)
-  {
-    if (job_candidate[k] >= n_candidates)
-    {
-      return batch_fail(c, NDT2D_ERR_INVALID, "ndt2d_closure_refine: job " + std::to_string(k) + ": candidate " +
-                                             std::to_string(job_candidate[k]) + " of " + std::to_string(n_candidates));
-    }
-  }
   NDT2D_BATCH_HIP(c, hipSetDevice(c->device));
-  const RefineCall t{cand_offsets, ids, poses_xyt, jobs_xyt, job_scan, beams_xy, beam_offsets, n_scans, {max_evals, tol_lin, tol_ang}};
+  const RefineCall t{jobs_xyt, job_scan, beams_xy, beam_offsets, n_scans, {max_evals, tol_lin, tol_ang}};
   for (const ndt2d::ClosureJobChunk & chunk :
        ndt2d::plan_closure_jobs(job_candidate, n_jobs, n_candidates, c->max_candidates, ndt2d::kRefineMaxJobs))
   {
-    const int rc = refine_chunk(c, chunk, t, records_out);
+    const int rc = refine_chunk(c, chunk, m, t, records_out);
     if (rc != NDT2D_OK) return rc;
   }
   return NDT2D_OK;
@@ -895,12 +859,7 @@ int ndt2d_closure_set_verify_neighbourhood(ndt2d_closure * c, uint32_t cells)
 {
   NDT2D_C_TRY
   if (c == nullptr) return NDT2D_ERR_INVALID;
-  if (cells != 1 && cells != 9)
-  {
-    return batch_fail(c, NDT2D_ERR_INVALID, "ndt2d_closure_set_verify_neighbourhood: " + std::to_string(cells) + " cells (1 or 9)");
-  }
-  c->verify_cells = cells;
-  return NDT2D_OK;
+  return ndt2d::batch_refuse(c, c->verify.set_cells("ndt2d_closure_set_verify_neighbourhood", cells));
   NDT2D_C_CATCH(c)
 }
 
@@ -908,7 +867,7 @@ int ndt2d_closure_verify_neighbourhood(ndt2d_closure * c, uint32_t * out)
 {
   NDT2D_C_TRY
   if (c == nullptr || out == nullptr) return NDT2D_ERR_INVALID;
-  *out = c->verify_cells;
+  *out = c->verify.cells;
   return NDT2D_OK;
   NDT2D_C_CATCH(c)
 }
@@ -917,13 +876,7 @@ int ndt2d_closure_set_verify_gates(ndt2d_closure * c, double gate_inlier, double
 {
   NDT2D_C_TRY
   if (c == nullptr) return NDT2D_ERR_INVALID;
-  if (!(gate_inlier >= 0.0) || !(gate_pierce >= 0.0) || !std::isfinite(gate_inlier) || !std::isfinite(gate_pierce))
-  {
-    return batch_fail(c, NDT2D_ERR_INVALID, "ndt2d_closure_set_verify_gates: a gate is negative or not finite");
-  }
-  c->gate_inlier = gate_inlier;
-  c->gate_pierce = gate_pierce;
-  return NDT2D_OK;
+  return ndt2d::batch_refuse(c, c->verify.set_gates("ndt2d_closure_set_verify_gates", gate_inlier, gate_pierce));
   NDT2D_C_CATCH(c)
 }
 
@@ -931,8 +884,8 @@ int ndt2d_closure_verify_gates(ndt2d_closure * c, double * gate_inlier_out, doub
 {
   NDT2D_C_TRY
   if (c == nullptr || gate_inlier_out == nullptr || gate_pierce_out == nullptr) return NDT2D_ERR_INVALID;
-  *gate_inlier_out = c->gate_inlier;
-  *gate_pierce_out = c->gate_pierce;
+  *gate_inlier_out = c->verify.gate_inlier;
+  *gate_pierce_out = c->verify.gate_pierce;
   return NDT2D_OK;
   NDT2D_C_CATCH(c)
 }
@@ -941,12 +894,7 @@ int ndt2d_closure_set_verify_rays(ndt2d_closure * c, int enabled)
 {
   NDT2D_C_TRY
   if (c == nullptr) return NDT2D_ERR_INVALID;
-  if (enabled != 0 && enabled != 1)
-  {
-    return batch_fail(c, NDT2D_ERR_INVALID, "ndt2d_closure_set_verify_rays: " + std::to_string(enabled) + " (0 or 1)");
-  }
-  c->rays = enabled != 0;
-  return NDT2D_OK;
+  return ndt2d::batch_refuse(c, c->verify.set_rays("ndt2d_closure_set_verify_rays", enabled));
   NDT2D_C_CATCH(c)
 }
 
@@ -954,7 +902,7 @@ int ndt2d_closure_verify_rays(ndt2d_closure * c, int * out)
 {
   NDT2D_C_TRY
   if (c == nullptr || out == nullptr) return NDT2D_ERR_INVALID;
-  *out = c->rays ? 1 : 0;
+  *out = c->verify.rays ? 1 : 0;
   return NDT2D_OK;
   NDT2D_C_CATCH(c)
 }
@@ -968,38 +916,12 @@ int ndt2d_closure_verify(ndt2d_closure * c, size_t n_candidates, const size_t * 
   NDT2D_C_TRY
   if (c == nullptr) return NDT2D_ERR_INVALID;
   if (n_jobs == 0) return NDT2D_OK;
-  if (cand_offsets == nullptr || ids == nullptr || poses_xyt == nullptr || jobs_xyt == nullptr || records_out == nullptr ||
-      beams_xy == nullptr || beam_offsets == nullptr)
-  {
-    return batch_fail(c, NDT2D_ERR_INVALID, "ndt2d_closure_verify: null argument");
-  }
-  if (!(ndt_resolution > 0.0) || !std::isfinite(ndt_resolution) || !std::isfinite(range_max))
-  {
-    return batch_fail(c, NDT2D_ERR_INVALID, "ndt2d_closure_verify: bad resolution or range_max");
-  }
-  if (n_candidates >= (1u << 24)) return batch_fail(c, NDT2D_ERR_INVALID, "ndt2d_closure_verify: bad argument (n_candidates)");
-  if (job_candidate == nullptr && n_candidates != n_jobs)
-  {
-    return batch_fail(c, NDT2D_ERR_INVALID,
-                      "ndt2d_closure_verify: bad argument (no job_candidate: job k uses candidate k, n_candidates must equal n_jobs)");
-  }
-  // every scan, every job and every candidate are checked before anything is launched: what
-  // ndt2d_verify_run refuses (one text: batch/ndt2d_refine_jobs.h; the registration's rules are not
-  // this call's: given as ones it takes), what ndt2d_closure_match does
-  const std::string refusal =
-    ndt2d::refine_jobs::refusal("ndt2d_closure_verify", jobs_xyt, job_scan, n_jobs, beam_offsets, n_scans, 1u, 0.0, 0.0);
-  if (!refusal.empty()) return batch_fail(c, NDT2D_ERR_INVALID, refusal);
-  const int crc = check_candidates(c, "ndt2d_closure_verify", n_candidates, cand_offsets, ids, poses_xyt, ndt_resolution, range_max);
+  const CandidateMaps m{cand_offsets, ids, poses_xyt};
+  // (the registration's rules are not this call's: given as ones the shared check takes)
+  const int crc = check_job_call(c, "ndt2d_closure_verify", n_candidates, m, ndt_resolution, range_max, jobs_xyt, job_scan,
+                                 job_candidate, n_jobs, beams_xy, beam_offsets, n_scans, records_out, 1u, 0.0, 0.0);
   if (crc != NDT2D_OK) return crc;
-  for (size_t k = 0; k < n_jobs && job_candidate != nullptr; ++k)
-  {
-    if (job_candidate[k] >= n_candidates)
-    {
-      return batch_fail(c, NDT2D_ERR_INVALID, "ndt2d_closure_verify: job " + std::to_string(k) + ": candidate " +
-                                             std::to_string(job_candidate[k]) + " of " + std::to_string(n_candidates));
-    }
-  }
-  for (size_t k = 0; k < n_candidates && c->rays; ++k)
+  for (size_t k = 0; k < n_candidates && c->verify.rays; ++k)
   {
     const GridDesc & g = c->slots[k].grid;
     if (g.size_x > ndt2d::verify::kMaxGridSide || g.size_y > ndt2d::verify::kMaxGridSide)
@@ -1009,23 +931,22 @@ int ndt2d_closure_verify(ndt2d_closure * c, size_t n_candidates, const size_t * 
     }
   }
   NDT2D_BATCH_HIP(c, hipSetDevice(c->device));
-  const SlotVerifyCall t{cand_offsets, ids, poses_xyt,
-                         {jobs_xyt, job_scan, n_jobs, beams_xy, beam_offsets, n_scans, records_out, beam_class_out, beam_m2_out,
-                          beam_cells_out}};
+  const ndt2d::VerifyCall v{jobs_xyt,    job_scan,       n_jobs,      beams_xy,      beam_offsets, n_scans,
+                            records_out, beam_class_out, beam_m2_out, beam_cells_out};
   // job k's beams start at the sum of the earlier jobs' scan lengths
   c->job_first.resize(n_jobs + 1);
   c->job_beams.resize(n_jobs);
   c->job_first[0] = 0;
   for (size_t k = 0; k < n_jobs; ++k)
   {
-    c->job_beams[k] = t.v.beams_of(k);
+    c->job_beams[k] = v.beams_of(k);
     c->job_first[k + 1] = c->job_first[k] + c->job_beams[k];
   }
   for (const ndt2d::ClosureJobChunk & chunk :
        ndt2d::plan_closure_jobs(job_candidate, n_jobs, n_candidates, c->max_candidates, ndt2d::kVerifyMaxJobs, c->job_beams.data(),
                                 ndt2d::kVerifyChunkBeams))
   {
-    const int rc = verify_chunk(c, chunk, t);
+    const int rc = verify_chunk(c, chunk, m, v);
     if (rc != NDT2D_OK) return rc;
   }
   return NDT2D_OK;

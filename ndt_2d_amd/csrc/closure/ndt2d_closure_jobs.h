@@ -1,6 +1,7 @@
 // The chunk plan of ndt2d_closure_refine and ndt2d_closure_verify (closure/ndt2d_closure.hip): which
-// candidate maps a launch builds and which jobs run on them.  Plain C++ -- no HIP -- so that a host program can
-// check it (tests/cpp/closure_jobs_check.cpp).
+// candidate maps a launch builds and which jobs run on them -- and what a slot takes of a launch's
+// arrays (slot_extent: every entry point's slot offsets are its running sums).  Plain C++ -- no HIP
+// -- so that a host program can check it (tests/cpp/closure_jobs_check.cpp).
 //
 // Candidates are taken in ascending index among those a job names (a candidate no job names is
 // not built); a candidate's jobs in ascending job index.  A chunk closes before it would exceed
@@ -16,6 +17,7 @@
 #ifndef NDT2D_CLOSURE_JOBS_H_
 #define NDT2D_CLOSURE_JOBS_H_
 
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <utility>
@@ -23,6 +25,20 @@
 
 namespace ndt2d
 {
+
+// What one slot -- a candidate map of n_points points on ncell cells -- takes of a launch's arrays:
+// touched-cell records (at least one, so that no slot is empty) and uint16 table entries (the
+// cells, "off the grid" and padding to a multiple of 8, so that every slot's table starts on 16
+// bytes).  The slots' offsets are the running sums of these, nothing else.
+struct SlotExtent
+{
+  size_t list, lookup;
+};
+
+inline SlotExtent slot_extent(size_t n_points, size_t ncell)
+{
+  return SlotExtent{std::max<size_t>(1, std::min(n_points, ncell)), (ncell + 2 + 7) & ~size_t(7)};
+}
 
 struct ClosureJobChunk
 {

@@ -1,4 +1,4 @@
-// The step of the Newton NDT registration (refine/ndt2d_refine.hip): what ONE thread does between
+// The step of the Newton NDT registration (refine/ndt2d_refine_kernel.h): what ONE thread does between
 // two evaluations of (f, g, H) -- the 3 x 3 Cholesky solve of the damped system, the lambda rule
 // and the stop rules of include/ndt2d_hip.h ("Newton NDT registration").  Plain C++ without HIP
 // types, host and device: the kernel's thread 0 runs it, and a stand-alone host program checks it

@@ -1,4 +1,4 @@
-// The ray of the match verification (verify/ndt2d_verify.hip): the integer line from the job's
+// The ray of the match verification (verify/ndt2d_verify_kernel.h): the integer line from the job's
 // origin cell to a beam's own cell, and the closest approach of the segment robot -> beam end to a
 // cell's Gaussian -- the contract of include/ndt2d_hip.h ("Match verification", "The ray").  Plain
 // C++ without HIP types, host and device: every lane of the kernel runs it for its beam, and a

@@ -1,6 +1,8 @@
-// The chunk plan of ndt2d_closure_refine (ndt_2d_amd/csrc/closure/ndt2d_closure_jobs.h), a program
-// of its own over the plain-C++ header: built with the host compiler and the sanitizers, run
-// directly (tests/test_closure_refine_host.py).  Prints OK, or FAILED lines.
+// The chunk plan of ndt2d_closure_refine and what a slot takes of a launch's arrays
+// (ndt_2d_amd/csrc/closure/ndt2d_closure_jobs.h), and the sent scans of a chunk with their copy into
+// the stage (ndt_2d_amd/csrc/batch/ndt2d_refine_jobs.h): a program of its own over the plain-C++
+// headers, built with the host compiler and the sanitizers, run directly
+// (tests/test_closure_refine_host.py).  Prints OK, or FAILED lines.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -8,6 +10,7 @@
 #include <vector>
 
 #include "ndt2d_closure_jobs.h"
+#include "ndt2d_refine_jobs.h"
 
 using ndt2d::ClosureJobChunk;
 using ndt2d::plan_closure_jobs;
@@ -147,6 +150,61 @@ int main()
       check_plan(plan, jc.data(), n_jobs, n_candidates, max_candidates, max_jobs);
       if (n_jobs == 0) CHECK(plan.empty());
     }
+  }
+  // what a slot takes of a launch's arrays: list entries max(1, min(n_points, ncell)), table
+  // entries a multiple of 8 that hold the cells, "off the grid" and the pair store's padding;
+  // slots placed one behind the other by the running sums do not overlap
+  {
+    const size_t cases[4][2] = {{0, 1}, {3, 65534}, {2048, 7}, {5, 6}};
+    const size_t want_list[4] = {1, 3, 7, 5};
+    size_t list_off = 0, lookup_off = 0;
+    for (int i = 0; i < 4; ++i)
+    {
+      const size_t n_points = cases[i][0], ncell = cases[i][1];
+      const ndt2d::SlotExtent e = ndt2d::slot_extent(n_points, ncell);
+      CHECK(e.list == want_list[i] && e.list >= 1 && e.list >= std::min(n_points, ncell));
+      CHECK(e.lookup % 8 == 0 && e.lookup >= ncell + 2 && e.lookup < ncell + 2 + 8);
+      // the build clears (ncell + 2) / 2 pairs of entries from the slot's first: within the slot
+      CHECK(2 * ((ncell + 2) / 2) <= e.lookup);
+      // this slot is [off, off + extent); the next starts where it ends, on a multiple of 8
+      const size_t list_end = list_off + e.list, lookup_end = lookup_off + e.lookup;
+      CHECK(lookup_off % 8 == 0 && list_end > list_off && lookup_end >= lookup_off + ncell + 2);
+      list_off = list_end;
+      lookup_off = lookup_end;
+    }
+    CHECK(list_off == 1 + 3 + 7 + 5 && lookup_off == 8 + 65536 + 16 + 8);
+  }
+  // the sent scans of a chunk and their copy into the stage: each named scan once, in the order the
+  // jobs first name them, its beams at its scan_first, nothing written beyond the chunk's beams
+  {
+    const size_t beam_offsets[5] = {0, 3, 3 + 1, 3 + 1 + 4, 3 + 1 + 4 + 2};   // scans of 3, 1, 4, 2 beams
+    std::vector<double> beams(2 * 10);
+    for (size_t i = 0; i < beams.size(); ++i) beams[i] = 100.0 + static_cast<double>(i);
+    const uint32_t job_scan[5] = {2, 0, 2, 3, 0};   // scan 1 is not named
+    const uint32_t chunk_jobs[4] = {4, 2, 3, 0};    // the chunk's jobs, as indices into the call's
+    std::vector<uint64_t> scan_first;
+    std::vector<uint32_t> sent;
+    const size_t n_beams = ndt2d::refine_jobs::plan_sent_scans(
+      4, [&](size_t b) { return static_cast<size_t>(chunk_jobs[b]); }, [&](size_t k) { return static_cast<size_t>(job_scan[k]); },
+      beam_offsets, 4, scan_first, sent);
+    CHECK(n_beams == 3 + 4 + 2 && (sent == std::vector<uint32_t>{0, 2, 3}));
+    CHECK(scan_first.size() == 4 && scan_first[0] == 0 && scan_first[2] == 3 && scan_first[3] == 7);
+    CHECK(scan_first[1] == ndt2d::refine_jobs::kNotSent);
+    std::vector<double> stage(2 * n_beams, -1.0);   // (exactly the chunk's beams: a write beyond is the sanitizer's)
+    ndt2d::refine_jobs::copy_sent_scans(sent, scan_first, beams.data(), beam_offsets, stage.data());
+    for (const uint32_t sc : sent)
+    {
+      for (size_t i = 0; i < 2 * (beam_offsets[sc + 1] - beam_offsets[sc]); ++i)
+      {
+        CHECK(stage[2 * scan_first[sc] + i] == beams[2 * beam_offsets[sc] + i]);
+      }
+    }
+    CHECK(std::none_of(stage.begin(), stage.end(), [](double v) { return v == -1.0; }));
+    // no job: nothing is sent, nothing copied
+    const size_t none = ndt2d::refine_jobs::plan_sent_scans(
+      0, [&](size_t b) { return b; }, [&](size_t k) { return k; }, beam_offsets, 4, scan_first, sent);
+    CHECK(none == 0 && sent.empty());
+    ndt2d::refine_jobs::copy_sent_scans(sent, scan_first, beams.data(), beam_offsets, nullptr);
   }
   std::printf(failures == 0 ? "OK\n" : "%d checks FAILED\n", failures);
   return failures == 0 ? 0 : 1;

@@ -73,11 +73,14 @@ def test_chunk_plan_under_the_sanitizers(tmp_path):
     """tests/cpp/closure_jobs_check.cpp: a program of its own over the plain-C++ header, built with
     the host compiler and -fsanitize=address,undefined (the sanitizer's runtime linked into the
     program), run directly: K = 1, unnamed candidates, a scrambled job list, 5 candidates through 2
-    slots, 4,097 jobs on one candidate, and every plan returning each job exactly once."""
+    slots, 4,097 jobs on one candidate, and every plan returning each job exactly once; what a slot
+    takes of a launch's arrays for (n_points, ncell) = (0, 1), (3, 65534), (2048, 7), (5, 6); the sent
+    scans of a chunk and their copy into a stage of exactly the chunk's beams."""
     exe = os.path.join(str(tmp_path), "closure_jobs_check")
     subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
                            "-fno-sanitize-recover=all", "-static-libasan", "-I",
-                           os.path.join(ROOT, "ndt_2d_amd", "csrc", "closure"),
+                           os.path.join(ROOT, "ndt_2d_amd", "csrc", "closure"), "-I",
+                           os.path.join(ROOT, "ndt_2d_amd", "csrc", "batch"),
                            os.path.join(ROOT, "tests", "cpp", "closure_jobs_check.cpp"), "-o", exe])
     done = subprocess.run([exe], capture_output=True, text=True)
     assert done.returncode == 0, done.stdout + done.stderr
@@ -91,24 +94,43 @@ def test_chunk_plan_under_the_sanitizers(tmp_path):
 
 
 def test_one_kernel_text_for_both_map_sources():
-    """The closure instantiates the refinement's kernel from csrc/refine/ndt2d_refine.hip -- it
-    holds no copy of the evaluation -- reads nothing of the installed grid in its source, and
-    launches a block per job."""
+    """The closure instantiates the refinement's kernel from csrc/refine/ndt2d_refine_kernel.h, the
+    header the installed grid's unit includes too -- it holds no copy of the evaluation -- reads
+    nothing of the installed grid in its source, and launches a block per job."""
     csrc = os.path.join(ROOT, "ndt_2d_amd", "csrc")
     closure = re.sub(r"//[^\n]*", "", open(os.path.join(csrc, "closure", "ndt2d_closure.hip")).read())
     refine = re.sub(r"//[^\n]*", "", open(os.path.join(csrc, "refine", "ndt2d_refine.hip")).read())
-    assert '#define NDT2D_REFINE_KERNEL_ONLY\n#include "refine/ndt2d_refine.hip"\n' in closure
+    kernel = re.sub(r"//[^\n]*", "", open(os.path.join(csrc, "refine", "ndt2d_refine_kernel.h")).read())
+    assert '#include "refine/ndt2d_refine_kernel.h"\n' in closure and '#include "refine/ndt2d_refine_kernel.h"\n' in refine
     assert "refine_kernel<true, CELLS, SlotSource>" in closure and "refine_kernel<false, CELLS, SlotSource>" in closure
     for absent in ("record_exponent(", "exp_score(", "wave_sum_to_last_lane(", "refine::begin(", "atomic", "__threadfence"):
         assert absent not in closure, absent
     source = closure[closure.index("struct SlotSource"):closure.index("using SlotRefineArgs")]
     assert "occ_bits" not in source and "cells_global" not in source
-    assert "template <bool POW2, uint32_t CELLS, class SOURCE>" in refine and "#ifndef NDT2D_REFINE_KERNEL_ONLY" in refine
-    assert "a.source.grid(jr.slot)" in refine and "a.source.map(jr.slot)" in refine
-    # the included file is hashed with the headers: an edit to the kernel makes
-    # the closure's object stale too, so the library cannot come to hold two texts of it
+    assert "template <bool POW2, uint32_t CELLS, class SOURCE>\n__global__" in kernel
+    assert "a.source.grid(jr.slot)" in kernel and "a.source.map(jr.slot)" in kernel
+    # exactly one __global__ of either shared kernel under csrc/, neither macro of the old layout
+    # anywhere, and no unit includes a .hip
+    count = {"refine_kernel": 0, "verify_kernel": 0}
+    for base, _, names in os.walk(csrc):
+        for n in names:
+            if n.endswith((".hip", ".h", ".cpp")):
+                raw = open(os.path.join(base, n)).read()
+                for name in count:
+                    count[name] += len(re.findall(r"__global__[^;{]*\b%s\b" % name, re.sub(r"//[^\n]*", "", raw)))
+                assert "NDT2D_REFINE_KERNEL_ONLY" not in raw and "NDT2D_VERIFY_KERNEL_ONLY" not in raw, n
+                assert not re.search(r'#\s*include\s*["<][^">]*\.hip[">]', raw), n
+    assert count == {"refine_kernel": 1, "verify_kernel": 1}
+    assert closure.count("__global__") == 1 and closure.count("hipLaunchKernelGGL(ndt2d::closure_build_kernel") == 1
+    # the refinement's chunk is the shared path with its job record, its launch and its scatter
+    chunk = closure[closure.index("int refine_chunk("):closure.index("int verify_chunk(")]
+    assert "job_chunk(" in chunk and "RefineJob{" in chunk and "launch_slot_refine<9>(" in chunk and "launch_slot_refine<1>(" in chunk
+    assert "hipMemcpyAsync" not in chunk and "launch_build(" not in chunk
+    # the kernel's header is hashed with the headers: an edit to the kernel makes the unit's and
+    # the closure's object stale, so the library cannot come to hold two texts of it
     from ndt_2d_amd import build
-    assert os.path.join(csrc, "refine", "ndt2d_refine.hip") in build.HEADERS
+    assert os.path.join(csrc, "refine", "ndt2d_refine_kernel.h") in build.HEADERS
+    assert not [h for h in build.HEADERS if h.endswith(".hip")]
     assert os.path.join(csrc, "refine", "ndt2d_refine_step.h") in build.HEADERS
     # (an object's hash covers its source and every listed header: build._input_sha256)
     assert "HEADERS" in build._input_sha256.__code__.co_names
@@ -123,10 +145,14 @@ def test_both_objects_refuse_by_one_text():
     assert path in build.HEADERS
     code = re.sub(r"//[^\n]*", "", open(path).read())
     assert "hip" not in code.lower() and "inline std::string refusal(" in code and "plan_sent_scans(" in code
-    for unit in ("closure/ndt2d_closure.hip", "refine/ndt2d_refine.hip"):
+    assert "inline void copy_sent_scans(" in code
+    for unit in ("closure/ndt2d_closure.hip", "refine/ndt2d_refine.hip", "verify/ndt2d_verify.hip"):
         text = re.sub(r"//[^\n]*", "", open(os.path.join(csrc, unit)).read())
         assert '#include "batch/ndt2d_refine_jobs.h"' in text, unit
         assert "refine_jobs::refusal(" in text and "refine_jobs::plan_sent_scans(" in text, unit
+        # the copy of the sent scans into the stage is the header's, once per chunk path
+        assert text.count("refine_jobs::copy_sent_scans(") == 1 and "2 * (t.beam_offsets[" not in text and \
+            "2 * (v.beam_offsets[" not in text, unit
         for copied in ("beam_offsets decrease", "the pose is not finite", "1 << 20", "kNotSent"):
             assert copied not in text, (unit, copied)
 

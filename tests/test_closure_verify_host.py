@@ -84,41 +84,73 @@ def test_plugin_members_compile():
 
 
 def test_one_kernel_text_for_both_map_sources():
-    """The closure instantiates the verification's kernel from csrc/verify/ndt2d_verify.hip -- it
-    holds no copy of the evaluation or of the ray walk -- reads nothing of the installed grid in its
-    source, refuses by the shared text, and nothing new sits at the top level of csrc/."""
+    """The closure instantiates the verification's kernel from csrc/verify/ndt2d_verify_kernel.h,
+    the header the installed grid's unit includes too -- it holds no copy of the evaluation or of the
+    ray walk -- reads nothing of the installed grid in its source, refuses by the shared text, runs
+    its chunks through the one path it shares with the refinement, and nothing new sits at the top
+    level of csrc/."""
     closure, verify = _code("closure", "ndt2d_closure.hip"), _code("verify", "ndt2d_verify.hip")
-    assert '#define NDT2D_VERIFY_KERNEL_ONLY\n#include "verify/ndt2d_verify.hip"\n' in closure
+    kernel = _code("verify", "ndt2d_verify_kernel.h")
+    assert '#include "verify/ndt2d_verify_kernel.h"\n' in closure and '#include "verify/ndt2d_verify_kernel.h"\n' in verify
     assert "verify_kernel<true, CELLS, SlotSource>" in closure and "verify_kernel<false, CELLS, SlotSource>" in closure
     for absent in ("record_exponent(", "record_m2(", "verify::line_begin(", "verify::line_next(", "verify::approach(",
                    "verify::pierces(", "__builtin_amdgcn_ballot_w64(", "atomic", "__threadfence"):
         assert absent not in closure, absent
-    assert "#ifndef NDT2D_VERIFY_KERNEL_ONLY" in verify and "a.source.grid(jr.slot)" in verify and "a.source.map(jr.slot)" in verify
-    # the object, the installed grid's source and the entry points sit behind the guard; the kernel in front of it
-    guard = verify.index("#ifndef NDT2D_VERIFY_KERNEL_ONLY")
-    assert verify.index("verify_kernel(const VerifyArgs<SOURCE> a)") < guard < verify.index("struct ndt2d_verify")
-    assert guard < verify.index("struct InstalledSource") and guard < verify.index('extern "C"')
-    # one __global__ of that name in the tree
-    count = 0
+    assert "a.source.grid(jr.slot)" in kernel and "a.source.map(jr.slot)" in kernel
+    # the kernel in the header; the object, the entry points and the launches in the unit; the
+    # installed grid's source in neither
+    assert "verify_kernel(const VerifyArgs<SOURCE> a)" in kernel and "verify_kernel(const VerifyArgs<SOURCE> a)" not in verify
+    for host_side in ("struct ndt2d_verify", 'extern "C"', "hipLaunchKernelGGL"):
+        assert host_side in verify and host_side not in kernel, host_side
+    assert "struct InstalledSource" not in verify and "struct InstalledSource" not in kernel
+    # one __global__ of either name in the tree, neither macro anywhere, no .hip included
+    count = {"refine_kernel": 0, "verify_kernel": 0}
     for base, _, names in os.walk(CSRC):
         for n in names:
             if n.endswith((".hip", ".h", ".cpp")):
-                count += len(re.findall(r"__global__[^;{]*\bverify_kernel\b", _code(base, n)))
-    assert count == 1
-    # one closure_build_kernel, launched by one launch_build, which the verification calls too
+                raw = open(os.path.join(base, n)).read()
+                for name in count:
+                    count[name] += len(re.findall(r"__global__[^;{]*\b%s\b" % name, _code(base, n)))
+                assert "NDT2D_VERIFY_KERNEL_ONLY" not in raw and "NDT2D_REFINE_KERNEL_ONLY" not in raw, n
+                assert not re.search(r'#\s*include\s*["<][^">]*\.hip[">]', raw), n
+    assert count == {"refine_kernel": 1, "verify_kernel": 1}
+    # one closure_build_kernel, launched by one launch_build, which the one path of a chunk calls:
+    # there the upload, the read-back and the wait; none in what the verification adds to it
     assert closure.count("__global__") == 1 and closure.count("hipLaunchKernelGGL(ndt2d::closure_build_kernel") == 1
-    chunk = closure[closure.index("int verify_chunk("):closure.index('extern "C"')]
-    assert "launch_build(" in chunk and chunk.count("hipMemcpyAsync") == 2 and chunk.count("hipStreamSynchronize") == 1
+    shared = closure[closure.index("int job_chunk("):closure.index("struct RefineCall")]
+    assert "launch_build(" in shared and shared.count("hipMemcpyAsync") == 2 and shared.count("hipStreamSynchronize") == 1
+    assert "place_chunk_slots(" in shared and "fill_scan_table(" in shared and "refine_jobs::copy_sent_scans(" in shared
+    per_path = closure[closure.index("struct RefineCall"):closure.index("int check_job_call(")]
+    assert "int refine_chunk(" in per_path and "int verify_chunk(" in per_path and per_path.count("job_chunk(") == 2
+    for absent in ("hipMemcpyAsync", "hipStreamSynchronize", "hipEventRecord", "launch_build(", "grow_pair(", "grow_device("):
+        assert absent not in per_path, absent
+    # the slots' offsets and the scan table exist once, for the match too
+    assert closure.count("s.lookup_off = ") == 1 and closure.count("sc.pool_offset = ") == 1 and closure.count("slot_extent(") == 1
+    assert closure.count("grow_device(&c->d_lookup") == 1 and "int match_chunk(" in closure
+    match = closure[closure.index("int match_chunk("):closure.index("struct ChunkOnDevice")]
+    assert "place_chunk_slots(" in match and "fill_scan_table(" in match
     source = closure[closure.index("struct SlotSource"):closure.index("using SlotRefineArgs")]
     assert "occ_bits" not in source and "cells_global" not in source and "installed_grid(" not in closure
-    # what it refuses about jobs and scans is the shared text; the chunks are the plan's
+    # what it refuses about jobs and scans is the shared text, through the check both entries share;
+    # the chunks are the plan's
     entry = closure[closure.index("int ndt2d_closure_verify("):]
-    assert 'refine_jobs::refusal("ndt2d_closure_verify"' in entry and "check_candidates(" in entry and "plan_closure_jobs(" in entry
+    assert 'check_job_call(c, "ndt2d_closure_verify"' in entry and "plan_closure_jobs(" in entry
+    assert 'check_job_call(c, "ndt2d_closure_refine"' in closure
+    check = closure[closure.index("int check_job_call("):closure.index('extern "C"')]
+    assert "refine_jobs::refusal(entry" in check and "check_candidates(c, entry" in check
+    assert check.index("null argument") < check.index("bad resolution or range_max") < check.index("bad argument (n_candidates)") \
+        < check.index("no job_candidate") < check.index("refine_jobs::refusal(") < check.index("check_candidates(") \
+        < check.index('": candidate "')
     for copied in ("beam_offsets decrease", "the pose is not finite", "1 << 20", "kNotSent"):
         assert copied not in closure, copied
-    # the included file is hashed with the headers: an edit to the kernel makes the closure's object stale too
+    # the settings and what they refuse are the header's, held once by either object
+    assert "ndt2d::VerifySettings verify;" in closure and "ndt2d::VerifySettings set;" in verify
+    for copied in ("cells (1 or 9)\"", "a gate is negative", "(0 or 1)"):
+        assert copied not in verify and closure.count(copied) == (1 if copied.startswith("cells") else 0), copied
+    # the kernel's header is hashed with the headers: an edit to the kernel makes the closure's object stale too
     from ndt_2d_amd import build
-    assert os.path.join(CSRC, "verify", "ndt2d_verify.hip") in build.HEADERS and "verify/ndt2d_verify.hip" in build.SOURCES
+    assert os.path.join(CSRC, "verify", "ndt2d_verify_kernel.h") in build.HEADERS and "verify/ndt2d_verify.hip" in build.SOURCES
+    assert not [h for h in build.HEADERS if h.endswith(".hip")]
     top = sorted(n for n in os.listdir(CSRC) if os.path.isfile(os.path.join(CSRC, n)))
     assert not [n for n in top if "verify" in n or "closure" in n]
 

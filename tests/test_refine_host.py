@@ -60,16 +60,27 @@ def test_build_lists_and_the_unit_keeps_no_copy():
     assert os.path.join(csrc, "refine", "ndt2d_refine_step.h") in build.HEADERS
     for name in os.listdir(os.path.join(csrc, "batch")):
         assert os.path.join(csrc, "batch", name) in build.HEADERS, name
+    assert os.path.join(csrc, "refine", "ndt2d_refine_kernel.h") in build.HEADERS
     text = open(os.path.join(csrc, "refine", "ndt2d_refine.hip")).read()
-    code = re.sub(r"//[^\n]*", "", text)
-    # the shared device functions, the batch host and the stage layout are used, not copied
-    assert '#include "batch/ndt2d_batch_host.h"\n' in text and '#include "refine/ndt2d_refine_step.h"\n' in text
-    for used in ("BatchHost", "installed_grid(", "InstalledMap", "stage_layout(", "cell_index<POW2>(", "record_exponent(",
-                 "exp_score(", "wave_sum_to_last_lane(", "refine::begin(", "refine::take("):
+    kernel_text = open(os.path.join(csrc, "refine", "ndt2d_refine_kernel.h")).read()
+    code, kernel = re.sub(r"//[^\n]*", "", text), re.sub(r"//[^\n]*", "", kernel_text)
+    # the shared device functions, the batch host and the stage layout are used, not copied: the
+    # host's words in the unit, the kernel's in its header, which the unit includes
+    assert '#include "batch/ndt2d_batch_host.h"\n' in text and '#include "refine/ndt2d_refine_kernel.h"\n' in text
+    assert '#include "refine/ndt2d_refine_step.h"\n' in kernel_text and '#include "batch/ndt2d_batch_search.h"\n' in kernel_text
+    for used in ("BatchHost", "installed_grid(", "InstalledSource", "stage_layout("):
         assert used in code, used
-    for absent in ("hipHostMalloc", "hipEventCreate", "atomic", "__threadfence", "struct InstalledMap", "v_fma_f64"):
-        assert absent not in code, absent
-    assert code.count("__global__") == 1 and code.count("hipLaunchKernelGGL") == 2     # one kernel: pow2 / divide
+    for used in ("cell_index<POW2>(", "record_exponent(", "exp_score(", "wave_sum_to_last_lane(", "refine::begin(", "refine::take("):
+        assert used in kernel and used not in code, used
+    # the installed grid's source is the shared one, beside InstalledMap, which it reads through
+    search = re.sub(r"//[^\n]*", "", open(os.path.join(csrc, "batch", "ndt2d_batch_search.h")).read())
+    assert search.count("struct InstalledSource") == 1 and "InstalledMap map(uint32_t) const" in search
+    for absent in ("hipHostMalloc", "hipEventCreate", "atomic", "__threadfence", "struct InstalledMap", "v_fma_f64",
+                   "struct InstalledSource"):
+        assert absent not in code and absent not in kernel, absent
+    # one kernel, in the header; launched from the unit: pow2 / divide
+    assert kernel.count("__global__") == 1 and code.count("__global__") == 0
+    assert code.count("hipLaunchKernelGGL") == 2 and kernel.count("hipLaunchKernelGGL") == 0
     # the step is plain C++: no HIP header, no HIP type
     step = open(os.path.join(csrc, "refine", "ndt2d_refine_step.h")).read()
     assert "hip_runtime" not in step and "double2" not in step and "__host__ __device__" in step

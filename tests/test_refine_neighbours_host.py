@@ -254,8 +254,13 @@ def test_plugin_members_compile():
 
 
 def test_kernel_keeps_one_cell_apart_and_clips_on_the_cell():
-    text = open(os.path.join(ROOT, "ndt_2d_amd", "csrc", "refine", "ndt2d_refine.hip")).read()
-    code = re.sub(r"//[^\n]*", "", text)
-    assert "template <bool POW2, uint32_t CELLS>" in code and "if constexpr (CELLS == 1)" in code
+    refine = os.path.join(ROOT, "ndt_2d_amd", "csrc", "refine")
+    code = re.sub(r"//[^\n]*", "", open(os.path.join(refine, "ndt2d_refine.hip")).read())
+    kernel = re.sub(r"//[^\n]*", "", open(os.path.join(refine, "ndt2d_refine_kernel.h")).read())
+    # the kernel's own head, in its header
+    assert "template <bool POW2, uint32_t CELLS, class SOURCE>\n__global__" in kernel and "if constexpr (CELLS == 1)" in kernel
+    assert "(nx < g.size_x) & (ny < g.size_y)" in kernel and "wave_any(" in kernel and kernel.count("__global__") == 1
+    # the unit instantiates both neighbourhoods of it, by name
     assert "launch_refine<9>(" in code and "launch_refine<1>(" in code
-    assert "(nx < g.size_x) & (ny < g.size_y)" in code and "wave_any(" in code
+    assert "refine_kernel<true, CELLS, InstalledSource>" in code and "refine_kernel<false, CELLS, InstalledSource>" in code
+    assert "installed_kernel" not in code and "installed_kernel" not in kernel

@@ -68,19 +68,36 @@ def test_build_lists_and_the_shape_of_the_unit():
     csrc = os.path.join(ROOT, "ndt_2d_amd", "csrc")
     assert "verify/ndt2d_verify.hip" in build.SOURCES
     assert os.path.join(csrc, "verify", "ndt2d_verify_ray.h") in build.HEADERS
+    assert os.path.join(csrc, "verify", "ndt2d_verify_kernel.h") in build.HEADERS
     text = open(os.path.join(csrc, "verify", "ndt2d_verify.hip")).read()
-    code = re.sub(r"//[^\n]*", "", text)
-    # the shared device functions, the batch host and the stage layout are used, not copied
-    assert '#include "batch/ndt2d_batch_host.h"\n' in text and '#include "verify/ndt2d_verify_ray.h"\n' in text
-    for used in ("BatchHost", "installed_grid(", "InstalledMap", "stage_layout(", "cell_index<POW2>(", "record_exponent(",
-                 "refine_jobs::refusal(", "refine_jobs::plan_sent_scans(", "verify::line_begin(", "verify::line_next(",
-                 "verify::approach(", "__builtin_amdgcn_ballot_w64(", "__popcll("):
+    kernel_text = open(os.path.join(csrc, "verify", "ndt2d_verify_kernel.h")).read()
+    code, kernel = re.sub(r"//[^\n]*", "", text), re.sub(r"//[^\n]*", "", kernel_text)
+    # the shared device functions, the batch host and the stage layout are used, not copied: the
+    # host's words in the unit, the kernel's in its header, which the unit includes
+    assert '#include "batch/ndt2d_batch_host.h"\n' in text and '#include "verify/ndt2d_verify_kernel.h"\n' in text
+    assert '#include "verify/ndt2d_verify_ray.h"\n' in kernel_text and '#include "batch/ndt2d_batch_search.h"\n' in kernel_text
+    for used in ("BatchHost", "installed_grid(", "InstalledSource", "stage_layout(", "refine_jobs::refusal(",
+                 "refine_jobs::plan_sent_scans(", "refine_jobs::copy_sent_scans("):
         assert used in code, used
-    for absent in ("hipHostMalloc", "hipEventCreate", "atomic", "__threadfence", "struct InstalledMap", "while (true)", "while (1)",
-                   "for (;;)"):
-        assert absent not in code, absent
-    assert code.count("__global__") == 1 and code.count("hipLaunchKernelGGL") == 2     # one kernel: pow2 / divide
-    assert "template <bool POW2, uint32_t CELLS, class SOURCE>" in code
+    for used in ("cell_index<POW2>(", "record_exponent(", "verify::line_begin(", "verify::line_next(", "verify::approach(",
+                 "__builtin_amdgcn_ballot_w64(", "__popcll("):
+        assert used in kernel and used not in code, used
+    search = re.sub(r"//[^\n]*", "", open(os.path.join(csrc, "batch", "ndt2d_batch_search.h")).read())
+    assert search.count("struct InstalledSource") == 1 and "InstalledMap map(uint32_t) const" in search
+    for absent in ("hipHostMalloc", "hipEventCreate", "atomic", "__threadfence", "struct InstalledMap", "struct InstalledSource",
+                   "while (true)", "while (1)", "for (;;)"):
+        assert absent not in code and absent not in kernel, absent
+    # one kernel, in the header; launched from the unit: pow2 / divide
+    assert kernel.count("__global__") == 1 and code.count("__global__") == 0
+    assert code.count("hipLaunchKernelGGL") == 2 and kernel.count("hipLaunchKernelGGL") == 0
+    assert "template <bool POW2, uint32_t CELLS, class SOURCE>\n__global__" in kernel
+    # the settings and what they refuse exist once, in the header; the setters are thin calls
+    assert kernel.count("struct VerifySettings") == 1 and "a gate is negative or not finite" in kernel
+    for copied in ("cells (1 or 9)", "a gate is negative", "(0 or 1)", "std::isfinite("):
+        assert copied not in code, copied
+    for setter in ("set_cells(\"ndt2d_verify_set_neighbourhood\"", "set_gates(\"ndt2d_verify_set_gates\"",
+                   "set_rays(\"ndt2d_verify_set_rays\""):
+        assert setter in code, setter
     # every extern "C" body that can throw sits between the guards (last_error returns a stored string)
     assert code.count("NDT2D_C_TRY") == code.count("NDT2D_C_CATCH") == 11
     # the ray is plain C++: no HIP header, no HIP type, no open loop
