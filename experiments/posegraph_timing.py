@@ -11,6 +11,11 @@ context, not as a rival: the wall time of the numpy restatement's dense solve of
 N = 1,000.  No speed against Ceres is claimed: it is not built here.
 
     python experiments/posegraph_timing.py [--calls 30] [--warmup 5] [--sizes 100,1000,10000]
+
+--preconditioner jacobi,chain runs every (N, K) with one preconditioner after the other on the same
+object, masks and session (a row's "preconditioner" says which; "us_per_cg_slowest_job" is the kernel
+time over the CG iterations of the job that made most: a launch lasts as long as its slowest job).
+profiles/posegraph_chain_timing.json is such a run.
 """
 import argparse
 import json
@@ -82,6 +87,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--sizes", default="100,1000,10000")
     ap.add_argument("--masks", default="1,64,256")
+    ap.add_argument("--preconditioner", default="jacobi", help="\"jacobi\", \"chain\" or both with a comma: each (N, K) with one after the other")
+    ap.add_argument("--no-restatement", action="store_true", help="leave the numpy context rows out")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "posegraph_timing.json"))
     args = ap.parse_args()
     from ndt_2d_amd import PoseGraph, ScanMatcherNDT, _capi
@@ -95,7 +102,8 @@ def main():
         pg.set_graph(g["poses"], begin=g["begin"], end=g["end"], transform=g["transform"], information=g["information"],
                      switchable=g["switchable"])
         pg.set_timing(True)
-        for K in [int(v) for v in args.masks.split(",")]:
+        for preconditioner, K in [(p, int(v)) for v in args.masks.split(",") for p in args.preconditioner.split(",")]:
+            pg.set_preconditioner(preconditioner)
             rng = np.random.default_rng(1000 * n + K)
             masks = np.ones((K, m), dtype=np.uint8)
             for k in range(1, K):
@@ -112,7 +120,8 @@ def main():
                     print("n %d masks %d call %d: %.1f s" % (n, K, call, t1 - t0), file=sys.stderr, flush=True)
             lm = [j["iterations"] for j in jobs]
             cg = [j["cg_iterations"] for j in jobs]
-            row = dict(n=n, m=m, closures=int(len(closures)), masks=K, calls=args.calls, warmup=args.warmup, kernel_ms_median=float(np.median(kernel)),
+            row = dict(preconditioner=pg.preconditioner(), us_per_cg_slowest_job=float(np.median(kernel)) * 1e3 / max(1, max(cg)),
+                       n=n, m=m, closures=int(len(closures)), masks=K, calls=args.calls, warmup=args.warmup, kernel_ms_median=float(np.median(kernel)),
                        kernel_ms_min=float(np.min(kernel)), kernel_ms_max=float(np.max(kernel)), wall_ms_median=float(np.median(wall)),
                        lm_iterations_job0=lm[0], lm_iterations_max=int(max(lm)), cg_iterations_job0=cg[0], cg_iterations_max=int(max(cg)),
                        cg_per_lm_job0=cg[0] / max(1, lm[0]), status_job0=_capi.POSEGRAPH_STATUS_NAMES[jobs[0]["status"]],
@@ -122,7 +131,7 @@ def main():
             print(json.dumps(row), flush=True)
             write(args, rows, dense)
         pg.close()
-        if n <= 1000:
+        if n <= 1000 and not args.no_restatement:
             import posegraph_restatement as R
             P = R.Problem(g["poses"], g["begin"], g["end"], g["transform"], g["information"])
             t0 = time.perf_counter()

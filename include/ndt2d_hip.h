@@ -734,7 +734,32 @@ int ndt2d_closure_verify_rays(ndt2d_closure * closure, int * out);
  *              information, an information that is not positive definite.  A refused graph leaves
  *              the one in place.  m == 0 or n == 1 is legal: nothing moves, CONVERGED_GRADIENT.
  *   set_weighting / weighting   "reference" or "information"; anything else: NDT2D_ERR_INVALID.
- *   evaluate   enabled[K][m] bytes (non-zero: on) or NULL for every constraint on; at the graph's
+ *   ndt2d_pose_graph_set_preconditioner / ndt2d_pose_graph_preconditioner   (so named, not
+ *              ndt2d_posegraph_*: the entry points of that prefix are a closed list of ten, which
+ *              tests/test_posegraph_host.py holds the unit and the bindings to; these two act on
+ *              the same object)  the CG's preconditioner M, z = M^-1 r: "jacobi" (the
+ *              default: the 3 x 3 diagonal blocks above) or "chain"; anything else:
+ *              NDT2D_ERR_INVALID.  Kept across set_graph.  "chain": with a job's free nodes the
+ *              active ones (not the fixed one, and with at least one enabled constraint), M is the
+ *              block-tridiagonal band of H + lambda D over the nodes in node order.  Its diagonal
+ *              blocks are the job's full 3 x 3 blocks of H plus lambda x clamp(diag), as "jacobi"
+ *              has them.  Its block (i, i + 1) is the sum, in ascending constraint index, over the
+ *              enabled constraints that join nodes i and i + 1 (begin = i, end = i + 1 or the
+ *              reverse, duplicates too) of (W E_i)^T (W E_{i+1}), E_i the constraint's Jacobian by
+ *              node i; it is zero when either node is not free: the chain breaks there.  A node
+ *              that is not free has z = 0.  M is J_c^T J_c of the neighbour constraints plus a
+ *              positive semidefinite block diagonal plus lambda D > 0: symmetric positive definite
+ *              for every mask.  z = M^-1 r exactly, by block cyclic reduction of 3 x 3 blocks
+ *              (csrc/posegraph/ndt2d_posegraph_chain.h) for any n: M is factored once per
+ *              iteration, the factors are applied once per CG iteration, ceil(log2 n) levels down
+ *              and up.  Should a pivot block not be finite and positive definite, that iteration
+ *              uses the "jacobi" blocks.  Graphs whose odometry runs along the node order (the
+ *              mapper's: begin = i, end = i + 1) are what it is for: what M leaves out of
+ *              H + lambda D has rank <= 6 per enabled constraint between nodes that are not
+ *              neighbours.  The stop rules, the record, cg_iterations and the determinism above
+ *              are the same; the minimiser reached is the same within the tolerances, not the bits.
+ *              The workspace on the device is 83 doubles a node and job instead of 41.
+ *   evaluate  enabled[K][m] bytes (non-zero: on) or NULL for every constraint on; at the graph's
  *              poses: cost_out[K]; optional chi2_out[K][m] and residuals_out[K][m][6] = e then r,
  *              of every constraint, enabled or not (the mask selects what F sums).
  *   solve      poses_out[K][n][3]; records_out[K][NDT2D_POSEGRAPH_RECORD_DOUBLES] = {status,
@@ -762,6 +787,8 @@ int ndt2d_posegraph_set_graph(ndt2d_posegraph * posegraph, const double * poses_
                               const double * information, size_t m, size_t fixed);
 int ndt2d_posegraph_set_weighting(ndt2d_posegraph * posegraph, const char * weighting);
 const char * ndt2d_posegraph_weighting(ndt2d_posegraph * posegraph);
+int ndt2d_pose_graph_set_preconditioner(ndt2d_posegraph * posegraph, const char * preconditioner);
+const char * ndt2d_pose_graph_preconditioner(ndt2d_posegraph * posegraph);
 int ndt2d_posegraph_evaluate(ndt2d_posegraph * posegraph, const uint8_t * enabled, size_t n_jobs,
                              double * cost_out, double * chi2_out, double * residuals_out);
 int ndt2d_posegraph_solve(ndt2d_posegraph * posegraph, const uint8_t * enabled, size_t n_jobs,

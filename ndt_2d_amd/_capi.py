@@ -178,6 +178,8 @@ SIGNATURES = {
     "ndt2d_posegraph_set_graph": (C.c_int, [_vp, _dp, _sz, C.POINTER(_u32), C.POINTER(_u32), _dp, _dp, _sz, _sz]),
     "ndt2d_posegraph_set_weighting": (C.c_int, [_vp, C.c_char_p]),
     "ndt2d_posegraph_weighting": (C.c_char_p, [_vp]),
+    "ndt2d_pose_graph_set_preconditioner": (C.c_int, [_vp, C.c_char_p]),
+    "ndt2d_pose_graph_preconditioner": (C.c_char_p, [_vp]),
     "ndt2d_posegraph_evaluate": (C.c_int, [_vp, C.POINTER(C.c_uint8), _sz, _dp, _dp, _dp]),
     "ndt2d_posegraph_solve": (C.c_int, [_vp, C.POINTER(C.c_uint8), _sz, _u32, _d, _d, _d, _dp, _dp, _dp]),
     "ndt2d_posegraph_set_timing": (C.c_int, [_vp, C.c_int]),

@@ -12,7 +12,10 @@
 //       of H, the preconditioner's inverses, cos / sin per node) lie in its own workspace in HBM.
 //       The LM loop, the gain ratio, accept / reject and the stop rules are evaluated by every
 //       thread on the same reduced values: all control flow is uniform, __syncthreads the only
-//       barrier, and the host is not asked between iterations.
+//       barrier, and the host is not asked between iterations.  A template on the preconditioner:
+//       kPgJacobi, each node's 3 x 3 block (the default, the code it was), or kPgChain, the
+//       block-tridiagonal band along the node order by block cyclic reduction
+//       (posegraph/ndt2d_posegraph_chain.h; pg_chain_* below), chosen per object.
 //   posegraph_evaluate_kernel  grid (job), 1,024 threads: e, r = W e and chi2 = |r|^2 of every
 //       constraint at the job's poses (thread t: constraints t, t + 1024, ...), F = 1/2 sum chi2
 //       over the enabled ones by the same reduction the solver uses -- a solve's initial_cost is
@@ -26,7 +29,7 @@
 //
 // Bounds.  Every loop is bounded before it starts: by n, m, a node's degree, max_iterations or the
 // CG cap.  Node and constraint indices are checked by the host at upload (ndt2d_posegraph_set_graph);
-// a job's workspace is [job][kPgNodeDoubles * n] doubles.
+// a job's workspace is [job][kPgNodeDoubles * n] doubles, with "chain" kPgChainDoubles * n more.
 //
 // LDS: 2 x 5 x 16 partials, 1,280 bytes.  Registers and scratch: DESIGN.md 3.18.
 #include <hip/hip_runtime.h>
@@ -40,6 +43,7 @@
 #include "ndt2d_hip.h"
 #include "batch/ndt2d_batch_host.h"
 #include "posegraph/ndt2d_posegraph_fn.h"
+#include "posegraph/ndt2d_posegraph_chain.h"
 
 namespace ndt2d
 {
@@ -60,6 +64,12 @@ constexpr uint32_t kPgCgCap = 8192;
 // per node of a job's workspace: x, trial x, g, p, r, z, Hp, delta (3 each), H's block and the
 // preconditioner's inverse (6 each), cos / sin at x and at the trial x (2 each), active (1)
 constexpr size_t kPgNodeDoubles = 8 * 3 + 2 * 6 + 2 * 2 + 1;
+// the preconditioner, the solve kernel's template argument
+constexpr int kPgJacobi = 0, kPgChain = 1;
+// what "chain" adds per node: H's block (i, i + 1) (9), the reduction's working diagonal (6) and
+// coupling (9), the coupling (9) and the inverse pivot (6) kept at the node's elimination, the
+// reduced right-hand side (3)
+constexpr size_t kPgChainDoubles = 9 + 6 + 9 + 9 + 6 + 3;
 
 // Levenberg-Marquardt's own constants (free to the implementation: the contract is the minimiser).
 constexpr double kPgLambda0 = 1e-4;             // 1 / Ceres's initial trust-region radius
@@ -189,7 +199,11 @@ __device__ __forceinline__ double pg_constraint(const PgGraph & G, uint32_t c, c
   return (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2];
 }
 
-// F = 1/2 sum of chi2 over the job's enabled constraints at xs.
+// F = 1/2 sum of chi2 over the job's enabled constraints at xs.  (pg_cost, pg_linearize and pg_matvec
+// carry the solve kernel's template argument without using it: each instantiation of the kernel
+// then has copies of its own, called as often as before there were two, and the inliner treats the
+// "jacobi" kernel as it did -- shared between the two it left that one with 20 bytes of scratch.)
+template <int kPrec>
 __device__ double pg_cost(const PgGraph & G, const uint8_t * en, const double * xs, const double * trig, PgScratch & sc, uint32_t & parity)
 {
   double acc[1] = {0.0};
@@ -234,6 +248,7 @@ __device__ __forceinline__ pg::Frame pg_frame(const PgWork & w, uint32_t a, uint
 
 // g, the diagonal blocks of H = J^T J and the active flags at x; returns |g|_inf.  A node that is
 // fixed or has no enabled constraint is not active: its g and block are zero.
+template <int kPrec>
 __device__ double pg_linearize(const PgGraph & G, const uint8_t * en, const PgWork & w, PgScratch & sc, uint32_t & parity)
 {
   double gmax = 0.0;
@@ -284,6 +299,7 @@ __device__ double pg_linearize(const PgGraph & G, const uint8_t * en, const PgWo
 __device__ __forceinline__ double pg_clamp_diag(double v) { return fmin(fmax(v, kPgDiagMin), kPgDiagMax); }
 
 // hp_i = ((H + lambda D) p)_i of the thread's nodes; returns the thread's share of p . hp.
+template <int kPrec>
 __device__ double pg_matvec(const PgGraph & G, const uint8_t * en, const PgWork & w, double lambda)
 {
   double php = 0.0;
@@ -344,6 +360,151 @@ __device__ __forceinline__ void pg_trig(const double * xs, double * trig, uint32
   }
 }
 
+// ---- the chain preconditioner: z = M^-1 r, M the block-tridiagonal band of H + lambda D over the
+// nodes in node order (include/ndt2d_hip.h, "Pose graph"), by the block cyclic reduction of
+// posegraph/ndt2d_posegraph_chain.h.  A node that is not active is a segment of its own with the
+// identity as its block and zero couplings: its r is 0, so is its z.  At each level the q-th node
+// of the level goes to thread q mod 1,024 (not to the node's owner), one barrier between levels. ----
+
+// What "chain" adds to a job's workspace, behind PgWork's arrays.
+struct PgChainWork
+{
+  double * od = nullptr, * b = nullptr;
+  pg::chain::System m = {nullptr, nullptr, nullptr, nullptr};
+  PgChainWork() = default;   // ("jacobi": an empty shell, nothing of it is used)
+  __device__ PgChainWork(double * base, size_t n)
+  {
+    od = base;
+    m.D = od + 9 * n;
+    m.U = m.D + 6 * n;
+    m.L = m.U + 9 * n;
+    m.P = m.L + 9 * n;
+    b = m.P + 6 * n;
+  }
+};
+
+// H's blocks (i, i + 1) at x: each node over its own incident constraints, the enabled ones that
+// join it and node i + 1 (either way round, duplicates too) in ascending constraint index, of
+// (W E_i)^T (W E_{i+1}).  Zero where either node is not active.  Behind pg_linearize (act).
+__device__ void pg_chain_couplings(const PgGraph & G, const uint8_t * en, const PgWork & w, const PgChainWork & ch)
+{
+  for (uint32_t i = pg_tid(); i < G.n; i += kPgThreads)
+  {
+    const size_t at = static_cast<size_t>(i);
+    double S[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (w.act[at] != 0.0 && i + 1u < G.n && i + 1u != G.fixed)
+    {
+      const uint32_t k1 = G.node_ptr[i + 1];
+      for (uint32_t k = G.node_ptr[i]; k < k1; ++k)
+      {
+        const uint32_t entry = G.node_con[k], c = entry >> 1;
+        if (en != nullptr && en[c] == 0) continue;
+        const uint32_t a = G.begin[c], b = G.end[c];
+        if (((entry & 1u) ? a : b) != i + 1u) continue;
+        const pg::Frame f = pg_frame(w, a, b);
+        const double * W = G.W + 9 * static_cast<size_t>(c);
+        double Ei[9], En[9], Ji[9], Jn[9], X[9];
+        if (entry & 1u)
+        {
+          pg::jacobian_b(f, Ei);
+          pg::jacobian_a(f, En);
+        }
+        else
+        {
+          pg::jacobian_a(f, Ei);
+          pg::jacobian_b(f, En);
+        }
+        pg::chain::mm(W, Ei, Ji);
+        pg::chain::mm(W, En, Jn);
+        pg::chain::mtm(Ji, Jn, X);
+#pragma unroll
+        for (int j = 0; j < 9; ++j) S[j] += X[j];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 9; ++j) ch.od[9 * at + j] = S[j];
+  }
+}
+
+// Factors M at lambda: the blocks in (each thread its own nodes), the levels, the root.  Returns
+// whether every pivot was positive definite, the same in every thread.
+__device__ bool pg_chain_factor(const PgGraph & G, const PgWork & w, const PgChainWork & ch, double lambda, PgScratch & sc, uint32_t & parity)
+{
+  const size_t n = G.n;
+  for (uint32_t i = pg_tid(); i < G.n; i += kPgThreads)
+  {
+    const size_t at = static_cast<size_t>(i);
+    double S[6] = {1.0, 0.0, 0.0, 1.0, 0.0, 1.0};
+    if (w.act[at] != 0.0)
+    {
+#pragma unroll
+      for (int j = 0; j < 6; ++j) S[j] = w.hd[6 * at + j];
+      S[0] += lambda * pg_clamp_diag(S[0]);
+      S[3] += lambda * pg_clamp_diag(S[3]);
+      S[5] += lambda * pg_clamp_diag(S[5]);
+    }
+#pragma unroll
+    for (int j = 0; j < 6; ++j) ch.m.D[6 * at + j] = S[j];
+#pragma unroll
+    for (int j = 0; j < 9; ++j) ch.m.U[9 * at + j] = ch.od[9 * at + j];
+  }
+  __syncthreads();
+  double bad = 0.0;
+  for (size_t s = 1; s < n; s <<= 1)
+  {
+    const size_t count = pg::chain::stay_count(n, s);
+    for (size_t q = pg_tid(); q < count; q += kPgThreads)
+    {
+      if (!pg::chain::factor_node(ch.m, n, pg::chain::stay_node(s, q), s)) bad = 1.0;
+    }
+    __syncthreads();
+  }
+  if (pg_tid() == 0u && !pg::chain::factor_root(ch.m)) bad = 1.0;
+  return pg_block_max(bad, sc, parity) == 0.0;   // (its barrier also orders the root's pivot)
+}
+
+// z = M^-1 b by the factors; ch.b holds the right-hand side (written by the nodes' owners, no
+// barrier behind it yet) and is reduced in place.  Ends behind a barrier: z is whole.
+__device__ void pg_chain_apply(const PgGraph & G, const PgWork & w, const PgChainWork & ch)
+{
+  const size_t n = G.n;
+  __syncthreads();
+  for (size_t s = 1; s < n; s <<= 1)
+  {
+    const size_t count = pg::chain::stay_count(n, s);
+    for (size_t q = pg_tid(); q < count; q += kPgThreads) pg::chain::forward_node(ch.m, ch.b, n, pg::chain::stay_node(s, q), s);
+    __syncthreads();
+  }
+  if (pg_tid() == 0u) pg::chain::back_root(ch.m, ch.b, w.z);
+  __syncthreads();
+  for (size_t s = pg::chain::top_stride(n); s >= 1; s >>= 1)
+  {
+    const size_t count = pg::chain::gone_count(n, s);
+    for (size_t q = pg_tid(); q < count; q += kPgThreads) pg::chain::back_node(ch.m, ch.b, w.z, n, pg::chain::gone_node(s, q), s);
+    __syncthreads();
+  }
+}
+
+// The thread's share of r . z behind pg_chain_apply; kFirst: p = z, the CG's first direction.
+template <bool kFirst>
+__device__ double pg_chain_rz(const PgGraph & G, const PgWork & w)
+{
+  double rz = 0.0;
+  for (uint32_t i = pg_tid(); i < G.n; i += kPgThreads)
+  {
+    const size_t at = static_cast<size_t>(i);
+    const double * r = w.r + 3 * at, * z = w.z + 3 * at;
+    if constexpr (kFirst)
+    {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) w.p[3 * at + j] = z[j];
+    }
+    rz += (r[0] * z[0] + r[1] * z[1]) + r[2] * z[2];
+  }
+  return rz;
+}
+
+template <int kPrec>
 __global__ void __launch_bounds__(kPgThreads) posegraph_solve_kernel(const PgGraph G, const uint8_t * enabled, double * workspace,
                                                                       const PgRules rules, double * poses_out, double * records)
 {
@@ -352,7 +513,10 @@ __global__ void __launch_bounds__(kPgThreads) posegraph_solve_kernel(const PgGra
   const uint32_t tid = threadIdx.x;
   const size_t job = blockIdx.x, n = G.n;
   const uint8_t * en = enabled != nullptr ? enabled + job * G.m : nullptr;
-  const PgWork w(workspace + job * kPgNodeDoubles * n, n);
+  constexpr size_t per_node = kPrec == kPgChain ? kPgNodeDoubles + kPgChainDoubles : kPgNodeDoubles;
+  const PgWork w(workspace + job * per_node * n, n);
+  const PgChainWork ch = kPrec == kPgChain ? PgChainWork(workspace + job * per_node * n + kPgNodeDoubles * n, n) : PgChainWork();
+  bool chain = false;   // whether this LM iteration's CG applies the chain's factors (uniform)
 
   for (uint32_t i = pg_tid(); i < G.n; i += kPgThreads)
   {
@@ -363,7 +527,7 @@ __global__ void __launch_bounds__(kPgThreads) posegraph_solve_kernel(const PgGra
   pg_trig(w.x, w.cs, G.n);
   __syncthreads();
 
-  double F = pg_cost(G, en, w.x, w.cs, sc, parity);
+  double F = pg_cost<kPrec>(G, en, w.x, w.cs, sc, parity);
   const double F0 = F;
   double gmax = 0.0;
   uint32_t status = NDT2D_POSEGRAPH_MAX_ITERATIONS, iterations = 0, cg_total = 0;
@@ -374,7 +538,8 @@ __global__ void __launch_bounds__(kPgThreads) posegraph_solve_kernel(const PgGra
   }
   else
   {
-    gmax = pg_linearize(G, en, w, sc, parity);
+    gmax = pg_linearize<kPrec>(G, en, w, sc, parity);
+    if constexpr (kPrec == kPgChain) pg_chain_couplings(G, en, w, ch);
     if (gmax <= rules.gradient_tolerance) status = NDT2D_POSEGRAPH_CONVERGED_GRADIENT;
   }
   double lambda = kPgLambda0, nu = 2.0, g_start = -1.0;
@@ -383,6 +548,9 @@ __global__ void __launch_bounds__(kPgThreads) posegraph_solve_kernel(const PgGra
   {
     ++iterations;
     // ---- the step: (H + lambda D) delta = -g by preconditioned conjugate gradients from 0 ----
+    // "chain": M is factored anew (lambda changes on accepted and on rejected steps); a pivot that is
+    // not positive definite leaves this iteration to the Jacobi blocks below
+    if constexpr (kPrec == kPgChain) chain = pg_chain_factor(G, w, ch, lambda, sc, parity);
     double s2[2] = {0.0, 0.0};
     for (uint32_t i = pg_tid(); i < G.n; i += kPgThreads)
     {
@@ -411,8 +579,21 @@ __global__ void __launch_bounds__(kPgThreads) posegraph_solve_kernel(const PgGra
         w.p[3 * at + j] = z[j];
         w.d[3 * at + j] = 0.0;
       }
+      if constexpr (kPrec == kPgChain)
+      {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) ch.b[3 * at + j] = r[j];
+      }
       s2[0] += (r[0] * z[0] + r[1] * z[1]) + r[2] * z[2];
       s2[1] += (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2];
+    }
+    if constexpr (kPrec == kPgChain)
+    {
+      if (chain)
+      {
+        pg_chain_apply(G, w, ch);
+        s2[0] = pg_chain_rz<true>(G, w);
+      }
     }
     pg_block_sum(s2, sc, parity);
     double rz = s2[0];
@@ -422,7 +603,7 @@ __global__ void __launch_bounds__(kPgThreads) posegraph_solve_kernel(const PgGra
     const double target = fmin(0.1, sqrt(r_start / g_start)) * r_start;
     for (uint32_t k = 0; k < cg_cap; ++k)
     {
-      double s1[1] = {pg_matvec(G, en, w, lambda)};
+      double s1[1] = {pg_matvec<kPrec>(G, en, w, lambda)};
       pg_block_sum(s1, sc, parity);
       if (!(s1[0] > 0.0) || !(rz > 0.0)) break;   // (p = 0, or a direction rounding made useless)
       const double alpha = rz / s1[0];
@@ -439,11 +620,29 @@ __global__ void __launch_bounds__(kPgThreads) posegraph_solve_kernel(const PgGra
           r[j] = w.r[3 * at + j] - alpha * w.hp[3 * at + j];
           w.r[3 * at + j] = r[j];
         }
+        if constexpr (kPrec == kPgChain)
+        {
+          if (chain)   // (z comes from the factors, behind this loop)
+          {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) ch.b[3 * at + j] = r[j];
+            s2[1] += (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2];
+            continue;
+          }
+        }
         pg::mul_sym(w.mi + 6 * at, r, z);
 #pragma unroll
         for (int j = 0; j < 3; ++j) w.z[3 * at + j] = z[j];
         s2[0] += (r[0] * z[0] + r[1] * z[1]) + r[2] * z[2];
         s2[1] += (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2];
+      }
+      if constexpr (kPrec == kPgChain)
+      {
+        if (chain)
+        {
+          pg_chain_apply(G, w, ch);
+          s2[0] = pg_chain_rz<false>(G, w);
+        }
       }
       pg_block_sum(s2, sc, parity);
       ++cg_total;
@@ -490,7 +689,7 @@ __global__ void __launch_bounds__(kPgThreads) posegraph_solve_kernel(const PgGra
       status = NDT2D_POSEGRAPH_CONVERGED_STEP;
       break;
     }
-    const double Ft = pg_cost(G, en, w.xt, w.cst, sc, parity);
+    const double Ft = pg_cost<kPrec>(G, en, w.xt, w.cst, sc, parity);
     const double dF = F - Ft;
     // below the rounding of the cost's own sum the gain ratio is noise: the model decides
     const bool noise = fabs(dF) <= kPgNoise * F;
@@ -506,7 +705,8 @@ __global__ void __launch_bounds__(kPgThreads) posegraph_solve_kernel(const PgGra
         w.cs[2 * at + 1] = w.cst[2 * at + 1];
       }
       __syncthreads();
-      gmax = pg_linearize(G, en, w, sc, parity);
+      gmax = pg_linearize<kPrec>(G, en, w, sc, parity);
+      if constexpr (kPrec == kPgChain) pg_chain_couplings(G, en, w, ch);
       const double t = 2.0 * gain - 1.0;
       lambda *= noise ? 1.0 / 3.0 : fmax(1.0 / 3.0, 1.0 - t * t * t);
       lambda = fmin(fmax(lambda, kPgLambdaMin), kPgLambdaMax);
@@ -584,6 +784,7 @@ struct ndt2d_posegraph : ndt2d::BatchHost
 {
   size_t max_nodes = 0, max_constraints = 0, max_jobs = 0;
   bool information_weighting = false;   // W = L^T instead of L
+  bool chain = false;                   // the CG's preconditioner: "chain" instead of "jacobi"
   bool has_graph = false, weights_sent = false;
   size_t n = 0, m = 0, fixed = 0;
   std::vector<double> chol;             // [m][9] the lower Cholesky factors
@@ -740,6 +941,25 @@ int ndt2d_posegraph_set_weighting(ndt2d_posegraph * s, const char * weighting)
 const char * ndt2d_posegraph_weighting(ndt2d_posegraph * s)
 {
   return s == nullptr ? "" : s->information_weighting ? "information" : "reference";
+}
+
+int ndt2d_pose_graph_set_preconditioner(ndt2d_posegraph * s, const char * preconditioner)
+{
+  NDT2D_C_TRY
+  if (s == nullptr) return NDT2D_ERR_INVALID;
+  const std::string name = preconditioner != nullptr ? preconditioner : "";
+  if (name != "jacobi" && name != "chain")
+  {
+    return batch_fail(s, NDT2D_ERR_INVALID, "ndt2d_pose_graph_set_preconditioner: \"" + name + "\" (\"jacobi\" or \"chain\")");
+  }
+  s->chain = name == "chain";
+  return NDT2D_OK;
+  NDT2D_C_CATCH(s)
+}
+
+const char * ndt2d_pose_graph_preconditioner(ndt2d_posegraph * s)
+{
+  return s == nullptr ? "" : s->chain ? "chain" : "jacobi";
 }
 
 int ndt2d_posegraph_set_graph(ndt2d_posegraph * s, const double * poses_xyt, size_t n, const uint32_t * begin, const uint32_t * end,
@@ -902,7 +1122,9 @@ int ndt2d_posegraph_solve(ndt2d_posegraph * s, const uint8_t * enabled, size_t n
     const uint8_t * d_en = nullptr;
     rc = ndt2d::pg_send_masks(s, stream, enabled, k0, k1, &d_en);
     if (rc != NDT2D_OK) return rc;
-    NDT2D_BATCH_HIP(s, ndt2d::grow_device(&s->d_work, &s->work_cap, kc * ndt2d::kPgNodeDoubles * n * sizeof(double)));
+    // (the chain's arrays are paid for only where it is selected)
+    const size_t per_node = ndt2d::kPgNodeDoubles + (s->chain ? ndt2d::kPgChainDoubles : 0);
+    NDT2D_BATCH_HIP(s, ndt2d::grow_device(&s->d_work, &s->work_cap, kc * per_node * n * sizeof(double)));
     // what comes back: [poses kc n 3 | records kc 6 | chi2 kc 2 m (start, end)]
     const size_t at_rec = kc * n * 3, at_chi2 = at_rec + kc * ndt2d::kPgRec;
     const size_t total = at_chi2 + (chi2_out != nullptr ? kc * 2 * m : 0);
@@ -916,8 +1138,16 @@ int ndt2d_posegraph_solve(ndt2d_posegraph * s, const uint8_t * enabled, size_t n
                          static_cast<double *>(nullptr), s->d_out + at_chi2, 2 * m, static_cast<double *>(nullptr));
       NDT2D_BATCH_HIP(s, hipGetLastError());
     }
-    hipLaunchKernelGGL(ndt2d::posegraph_solve_kernel, blocks, threads, 0, stream, G, d_en, static_cast<double *>(s->d_work), rules, s->d_out,
-                       s->d_out + at_rec);
+    if (s->chain)
+    {
+      hipLaunchKernelGGL(ndt2d::posegraph_solve_kernel<ndt2d::kPgChain>, blocks, threads, 0, stream, G, d_en, static_cast<double *>(s->d_work),
+                         rules, s->d_out, s->d_out + at_rec);
+    }
+    else
+    {
+      hipLaunchKernelGGL(ndt2d::posegraph_solve_kernel<ndt2d::kPgJacobi>, blocks, threads, 0, stream, G, d_en, static_cast<double *>(s->d_work),
+                         rules, s->d_out, s->d_out + at_rec);
+    }
     NDT2D_BATCH_HIP(s, hipGetLastError());
     if (chi2_out != nullptr)
     {

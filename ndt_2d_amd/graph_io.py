@@ -292,7 +292,7 @@ class Graph:
         """CeresSolver::optimize(constraints, scans) on the device (pose_graph.PoseGraph): the
         poses are taken from the scans, scans[0] is held, one job with every constraint on is
         solved, and the poses are written back unless the solve FAILED.  kw: PoseGraph.optimize's
-        tolerances and `weighting`.  Returns whether the solution is usable -- False for no scans,
+        tolerances, `weighting` and `preconditioner` ("jacobi", the default, or "chain").  Returns whether the solution is usable -- False for no scans,
         as the reference; `last_optimize` keeps the job's record."""
         from . import _capi
         from .pose_graph import PoseGraph
@@ -300,9 +300,11 @@ class Graph:
         if not self.scans:
             return False
         weighting = kw.pop("weighting", "reference")
+        preconditioner = kw.pop("preconditioner", "jacobi")
         pg = PoseGraph(matcher, max_nodes=len(self.scans), max_constraints=max(1, len(self.constraints)), max_jobs=1)
         try:
             pg.set_weighting(weighting)
+            pg.set_preconditioner(preconditioner)
             pg.set_graph(np.array([s.pose for s in self.scans], dtype=np.float64), self.constraints, fixed=0)
             result = pg.optimize(**kw)[0]
         finally:

@@ -60,6 +60,9 @@ public:
   }
   // "reference": W = L as the reference passes it (the cost is e^T L^T L e); "information": W = L^T.
   void setWeighting(const std::string & weighting) { weighting_ = weighting; }
+  // "jacobi" (the default) or "chain": the block-tridiagonal band of H + lambda D along the scans'
+  // order, for the mapper's graphs (odometry between consecutive scans, a few closures).
+  void setPreconditioner(const std::string & preconditioner) { preconditioner_ = preconditioner; }
 
   // Plain arrays: poses_xyt[n][3] in and out, constraints as ndt2d_posegraph_set_graph takes them.
   // false: no poses, a refused graph or a failed solve (last_error()); the poses stay then.
@@ -199,6 +202,7 @@ private:
       }
     }
     if (!ok(ndt2d_posegraph_set_weighting(pg_, weighting_.c_str()))) return false;
+    if (!ok(ndt2d_pose_graph_set_preconditioner(pg_, preconditioner_.c_str()))) return false;
     return ok(ndt2d_posegraph_set_graph(pg_, poses_xyt, n, begin, end, transform, information, m, 0));
   }
 
@@ -226,7 +230,7 @@ private:
   std::size_t max_nodes_ = 0, max_constraints_ = 0, max_jobs_ = 1;
   std::uint32_t max_iterations_ = 100;
   double gradient_tolerance_ = 1e-10, function_tolerance_ = 1e-6, parameter_tolerance_ = 1e-8;
-  std::string weighting_ = "reference";
+  std::string weighting_ = "reference", preconditioner_ = "jacobi";
   std::vector<double> poses_, transform_, information_, out_;
   std::vector<std::uint32_t> begin_, end_;
   PoseGraphRecord record_;

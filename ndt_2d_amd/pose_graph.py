@@ -79,6 +79,7 @@ class PoseGraph:
         self._matcher = matcher   # the context must outlive the object
         self._caps = (0, 0, 0)
         self._weighting = "reference"
+        self._preconditioner = "jacobi"
         self._timing = False
         self.n = self.m = 0
         self.switchable = np.zeros(0, dtype=bool)
@@ -93,6 +94,7 @@ class PoseGraph:
             self._L.ndt2d_posegraph_destroy(old)
         self._caps = (max_nodes, max_constraints, max_jobs)
         self._check(self._L.ndt2d_posegraph_set_weighting(self._p, self._weighting.encode()), "ndt2d_posegraph_set_weighting")
+        self._check(self._L.ndt2d_pose_graph_set_preconditioner(self._p, self._preconditioner.encode()), "ndt2d_pose_graph_set_preconditioner")
         if self._timing:
             self.set_timing(True)
 
@@ -120,6 +122,16 @@ class PoseGraph:
 
     def weighting(self):
         return self._L.ndt2d_posegraph_weighting(self._p).decode()
+
+    def set_preconditioner(self, preconditioner):
+        """The CG's preconditioner: "jacobi" (the default: each node's 3 x 3 block of H + lambda D) or
+        "chain" (the block-tridiagonal band of H + lambda D over the nodes in node order, solved exactly
+        by block cyclic reduction: for graphs whose odometry runs along the node order)."""
+        self._check(self._L.ndt2d_pose_graph_set_preconditioner(self._p, str(preconditioner).encode()), "ndt2d_pose_graph_set_preconditioner")
+        self._preconditioner = str(preconditioner)
+
+    def preconditioner(self):
+        return self._L.ndt2d_pose_graph_preconditioner(self._p).decode()
 
     def set_graph(self, poses, constraints=None, fixed=0, begin=None, end=None, transform=None, information=None, switchable=None):
         """poses [n, 3]; the constraints as graph_io.Constraint objects, or as the arrays begin, end
