@@ -39,10 +39,10 @@ h = hist.cpu().numpy()
 names = ["items", "chunks_pretested", "beams_in_lookup_groups", "groups_with_a_live_lane", "beams_with_a_live_lane",
          "exact_evaluations", "evaluations_by_reference_index", "evaluations_with_exp", "skip_refreshes",
          "items_reduced", "single_beams"]
-p1 = (n_lin + 7) // 8
+items = float(h[200])   # (theta, tile) work items: the edge of the lattice may be cut into strip tiles
 out = {"what": "path counts of one search, wave-level events (experiments/lane_paths.py, -DNDT2D_LANE_PATHS build)",
        "cfg": cfg, "variant": m.last_variant(), "n_theta_run": n_th_run, "n_lin": n_lin, "beams": n_b,
-       "wave_beams": n_th_run * p1 * p1 * n_b, "units": n_th_run * n_lin * n_lin * n_b,
+       "wave_beams": items * n_b, "units": n_th_run * n_lin * n_lin * n_b,
        "build_info": _capi.build_info(),
        "counts": {n: float(h[200 + i]) for i, n in enumerate(names)}}
 print(json.dumps(out, indent=1))

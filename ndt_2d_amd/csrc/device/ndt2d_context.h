@@ -138,6 +138,7 @@ struct ndt2d_context
   double pose_x = 0.0, pose_y = 0.0;
   double dlin_absmax = 0.0;
   double patch_span = -1.0;   // see MatchArgs::patch_span
+  double strip_span_long = 0.0, strip_span_short = 0.0;   // see MatchArgs::strip_span_long
   double beam_rmax = 0.0;
   bool has_search = false;
 

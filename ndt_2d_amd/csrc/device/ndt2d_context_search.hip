@@ -3,6 +3,7 @@
 #include <limits>
 
 #include "device/ndt2d_context.h"
+#include "ndt2d_lane_fn.h"   // lane_strip_shape
 
 using namespace ndt2d_device;
 
@@ -27,6 +28,22 @@ void lattice_extent(ndt2d_context * h, const double * dlin, size_t n_lin)
     }
     if (h->patch_span >= 0.0 && dlin[last] - dlin[i] > h->patch_span) h->patch_span = dlin[last] - dlin[i];
   }
+  // the strip tiles of the lattice edge (ndt2d::lane_tiling): their long side's aligned groups,
+  // and the short side -- the steps behind the last whole group of eight
+  h->strip_span_long = h->strip_span_short = 0.0;
+  uint32_t long_log2 = 0;
+  if (!ndt2d::lane_strip_shape(static_cast<uint32_t>(n_lin), &long_log2)) return;
+  for (size_t k = 0; k + 1 < n_lin; ++k)
+  {
+    if (!(dlin[k + 1] >= dlin[k])) return;   // not ascending (or NaN): no claim
+  }
+  const size_t group = static_cast<size_t>(1) << long_log2;
+  for (size_t i = 0; i < n_lin; i += group)
+  {
+    const size_t last = i + group - 1 < n_lin ? i + group - 1 : n_lin - 1;
+    if (dlin[last] - dlin[i] > h->strip_span_long) h->strip_span_long = dlin[last] - dlin[i];
+  }
+  h->strip_span_short = dlin[n_lin - 1] - dlin[n_lin / 8 * 8];
 }
 
 }  // namespace
@@ -207,6 +224,8 @@ int ndt2d_match_launch_strided(ndt2d_handle h, size_t th_first, size_t th_stride
   a.dlin = h->tables_ptr + 3 * h->n_th;
   a.dlin_absmax = h->dlin_absmax;
   a.patch_span = h->patch_span;
+  a.strip_span_long = h->strip_span_long;
+  a.strip_span_short = h->strip_span_short;
   a.beam_rmax = h->beam_rmax;
   a.n_th = static_cast<uint32_t>(h->n_th);
   a.n_lin = static_cast<uint32_t>(h->n_lin);

@@ -76,6 +76,11 @@ struct MatchArgs
   // max over the 8-step patches i = 0, 8, ... of dlin[i + 7] - dlin[i] (host side); negative
   // if dlin is not ascending within a patch: the first lane of a patch is then not its corner
   double patch_span;
+  // The same for the strip tiles of the lattice edge (lane_tiling, ndt2d_lane_fn.h): the widest
+  // run of dlin over the aligned groups of a strip tile's long side (64 / W steps) and
+  // dlin[n_lin - 1] - dlin[8 * (n_lin / 8)] for its short side.  strip_span_long <= 0: no claim
+  // (dlin not ascending, or a lattice that has no strips) -- the search keeps 8 x 8 patches.
+  double strip_span_long, strip_span_short;
   uint32_t n_th, n_lin;
   // theta steps th_begin + k * th_stride, k in [0, th_end - th_begin): a contiguous slab
   // (stride 1) or one rank's share of an interleaved sharding

@@ -62,9 +62,98 @@ struct LaneGeom
   // map sub-cells per axis of the patch's first lane; -1: no pre-test (wider patches,
   // lattices whose first lane is not the patch's corner, the control mode).
   int32_t box_span;
+  // Strip tiles at the lattice edge (lane_tiling below): 1 if the unsplit dynamic-item searches
+  // of this lattice use them, with the pre-test's spans of a strip tile's long and short side
+  // (sub-cells, by the rule of box_span; at most kMaxStripSpan).  0: 8 x 8 patches throughout.
+  int32_t strips;
+  int32_t strip_span_long, strip_span_short;
 };
 
 constexpr int kMaxBoxSpan = 3;   // the pre-test reads a 4 x 4 sub-cell box
+constexpr int kMaxStripSpan = 7; // ... and an 8 x 8 box for a strip tile
+
+// Tiling of one theta step's n_lin x n_lin translations into work items of 64 candidates, a
+// function of n_lin alone (and of whether the lattice may use strips at all, LaneGeom::strips).
+// With full = n_lin / 8 and rem = n_lin % 8, the core is full x full tiles of 8 x 8.  For
+// 1 <= rem <= 4 the 8 x 8 patches of the last row and column would be at least half shadow
+// lanes; instead, with W = 4, 4, 2, 1 for rem = 4, 3, 2, 1 and L = 64 / W,
+//   the strip ix >= 8 full, all iy,        is cut into tiles W wide and L tall (tiles_x of them),
+//   the strip iy >= 8 full, ix < 8 full,   into tiles L wide and W tall
+// (n_lin = 100: 144 + 7 + 6 = 157 items instead of 169).  Any other rem, or strips == false:
+// (full + 1)^2 patches of 8 x 8, item p = patch (p / row, p % row).
+// Item p of a theta step: p < core is tile (p / row, p % row) of 8 x 8; then the tiles of the
+// first strip from iy = 0, then those of the second from ix = 0.
+struct LaneTiling
+{
+  uint32_t row;        // 8 x 8 tiles per axis
+  uint32_t core;       // row * row: items below it are 8 x 8 tiles
+  uint32_t long_log2;  // log2 L
+  uint32_t tiles_x;    // tiles of the first strip
+  uint32_t per_theta;  // items of a theta step
+};
+
+__host__ __device__ inline bool lane_strip_shape(uint32_t n_lin, uint32_t * long_log2)
+{
+  const uint32_t rem = n_lin % kPatch;
+  if (rem == 0 || rem > 4) return false;
+  *long_log2 = rem == 1 ? 6u : (rem == 2 ? 5u : 4u);
+  return true;
+}
+
+__host__ __device__ inline LaneTiling lane_tiling(uint32_t n_lin, bool strips)
+{
+  LaneTiling t;
+  uint32_t long_log2 = 3;
+  if (strips && lane_strip_shape(n_lin, &long_log2))
+  {
+    const uint32_t full = n_lin / kPatch;
+    const uint32_t round_up = (1u << long_log2) - 1u;
+    t.row = full;
+    t.core = full * full;
+    t.long_log2 = long_log2;
+    t.tiles_x = (n_lin + round_up) >> long_log2;
+    t.per_theta = t.core + t.tiles_x + ((full * kPatch + round_up) >> long_log2);
+    return t;
+  }
+  t.row = (n_lin + kPatch - 1) / kPatch;
+  t.core = t.row * t.row;
+  t.long_log2 = 3;
+  t.tiles_x = 0;
+  t.per_theta = t.core;
+  return t;
+}
+
+// Tile of item p: its corner (x0, y0), log2 of its height h (lane l is the candidate
+// (x0 + (l >> log2 h), y0 + (l & (h - 1))), so lane 0 is the corner), and the end of its
+// candidates along x (the second strip stops where the first begins; along y every tile ends
+// at n_lin).  Lanes beyond either end shadow the last candidate before it.
+__host__ __device__ inline void lane_tile(const LaneTiling & t, uint32_t n_lin, uint32_t p, uint32_t & x0,
+                                          uint32_t & y0, uint32_t & h_log2, uint32_t & x_end)
+{
+  if (p < t.core)
+  {
+    const uint32_t pxi = p / t.row;
+    x0 = pxi * kPatch;
+    y0 = (p - pxi * t.row) * kPatch;
+    h_log2 = 3;
+    x_end = n_lin;
+    return;
+  }
+  const uint32_t q = p - t.core;
+  if (q < t.tiles_x)
+  {
+    x0 = t.row * kPatch;
+    y0 = q << t.long_log2;
+    h_log2 = t.long_log2;
+    x_end = n_lin;
+    return;
+  }
+  x0 = (q - t.tiles_x) << t.long_log2;
+  y0 = t.row * kPatch;
+  h_log2 = 6u - t.long_log2;
+  x_end = t.row * kPatch;
+}
+
 constexpr int kMaxBlockLog2 = 3; // coarsest map: one byte per 8 x 8 grid cells (windows up to 2,048 cells)
 
 // Upper bound of Cell::score's exponent e(p) = q^T h q, q = p - mean (h = -0.5 *
@@ -385,6 +474,33 @@ __device__ __forceinline__ bool patch_can_score(double s, int32_t span)
   return (any & columns) != 0u;
 }
 
+// The same for a strip tile (lane_tiling), whose candidates lie within span_x / span_y sub-cells
+// (each at most kMaxStripSpan) of the corner: up to eight rows of eight bytes, three dwords a row.
+__device__ __forceinline__ bool strip_can_score(double s, int32_t span_x, int32_t span_y)
+{
+  typedef const __attribute__((address_space(3), aligned(4))) uint32_t * lds_u32_ptr;
+  const uint32_t lo = static_cast<uint32_t>(__double2loint(s));
+  const uint32_t hi = static_cast<uint32_t>(__double2hiint(s));
+  const uint32_t address = __builtin_amdgcn_perm(hi, lo, 0x0c0c0502u);   // (cell y << 8) | cell x
+  const uint32_t base = address & ~3u;
+  const uint32_t shift = address & 3u;
+  uint32_t any_lo = 0, any_hi = 0;
+#pragma unroll
+  for (int r = 0; r <= kMaxStripSpan; ++r)
+  {
+    if (r <= span_y)
+    {
+      const lds_u32_ptr p = reinterpret_cast<lds_u32_ptr>(base + static_cast<uint32_t>(r) * kMapStride);
+      const uint32_t w0 = p[0], w1 = p[1], w2 = p[2];
+      any_lo |= __builtin_amdgcn_alignbyte(w1, w0, shift);   // bytes x .. x + 3 of the row
+      any_hi |= __builtin_amdgcn_alignbyte(w2, w1, shift);   // bytes x + 4 .. x + 7
+    }
+  }
+  // levels live in bits 2..7 of a byte; keep columns 0 .. span_x
+  const uint64_t columns = 0xfcfcfcfcfcfcfcfcull >> (8 * (kMaxStripSpan - span_x));
+  return ((any_lo & static_cast<uint32_t>(columns)) | (any_hi & static_cast<uint32_t>(columns >> 32))) != 0u;
+}
+
 // Cell::score's exponent against packed record idx of the LDS copy, addressed with
 // 32-bit LDS arithmetic (one v_mad_u32_u24; idx < 2^24 for any grid that fits LDS).
 __device__ __forceinline__ double lds_record_exponent(uint32_t cells_address, uint32_t idx,
@@ -652,11 +768,31 @@ inline bool lane_geometry(const MatchArgs & args, size_t lds_per_block, LaneGeom
   // lanes differ from the first by rint(d_i * s) - rint(d_0 * s) <= span * s + 1 fixed-point
   // units per axis; a box that starts in the first lane's sub-cell ends floor of that later
   geo->box_span = -1;
+  const auto span_sub_cells = [&](double span) {
+    const double span_units = std::ceil(span * args.grid.inv_cell_size * geo->unit_scale) + 2.0;
+    return std::floor((65535.0 + span_units) / 65536.0);
+  };
   if (args.patch_span >= 0.0)
   {
-    const double span_units = std::ceil(args.patch_span * args.grid.inv_cell_size * geo->unit_scale) + 2.0;
-    const double sub_cells = std::floor((65535.0 + span_units) / 65536.0);
+    const double sub_cells = span_sub_cells(args.patch_span);
     if (sub_cells <= static_cast<double>(kMaxBoxSpan)) geo->box_span = static_cast<int32_t>(sub_cells);
+  }
+  // Strip tiles only with a pre-test of their own: a strip shape whose span the 8 x 8 box
+  // cannot hold leaves the whole lattice on 8 x 8 patches.
+  geo->strips = 0;
+  geo->strip_span_long = geo->strip_span_short = 0;
+  uint32_t long_log2 = 0;
+  if (geo->box_span >= 0 && lane_strip_shape(args.n_lin, &long_log2) && args.strip_span_long > 0.0 &&
+      args.strip_span_short >= 0.0)
+  {
+    const double sub_long = span_sub_cells(args.strip_span_long);
+    const double sub_short = span_sub_cells(args.strip_span_short);
+    if (sub_long <= static_cast<double>(kMaxStripSpan) && sub_short <= static_cast<double>(kMaxStripSpan))
+    {
+      geo->strips = 1;
+      geo->strip_span_long = static_cast<int32_t>(sub_long);
+      geo->strip_span_short = static_cast<int32_t>(sub_short);
+    }
   }
   return true;
 }

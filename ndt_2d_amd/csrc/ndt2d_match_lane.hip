@@ -10,6 +10,11 @@
 // :108-115) is wave-uniform; a small pre-kernel tabulates it per (theta, beam)
 // and the search kernel reads it with scalar loads.
 //
+// Where n_lin leaves one to four steps behind its last whole group of eight, the patches of
+// the last row and column would be at least half lanes that repeat the edge candidate; the
+// unsplit dynamic-item forms cut that edge into strip tiles of 4 x 16, 2 x 32 or 1 x 64 instead
+// (lane_tiling, ndt2d_lane_fn.h).  A candidate's sum does not depend on the tile that holds it.
+//
 // The 64 points of a patch for one beam lie within 0.16 m of each other, so
 // they fall into one to four NDT cells, and four cells out of five hold no
 // distribution (n < 5: likelihood exactly 0, src/ndt_model.cpp:107).  The kernel
@@ -136,12 +141,19 @@ __global__ void __launch_bounds__(256) outer_table_kernel(const MatchArgs a, dou
 // Work item -> (theta step of the launch, patch).  Theta steps are visited from the middle
 // of the range outwards: the steps around the scan's own heading are the expensive ones
 // when the guess is any good.
+__device__ __forceinline__ void item_step(uint32_t item, uint32_t patches, uint32_t th_mid, uint32_t & t,
+                                          uint32_t & p)
+{
+  const uint32_t rank = item / patches;
+  p = item - rank * patches;
+  t = (rank & 1u) ? th_mid + (rank + 1u) / 2u : th_mid - rank / 2u;
+}
+
 __device__ __forceinline__ void item_place(uint32_t item, uint32_t patches, uint32_t patches_1d,
                                            uint32_t th_mid, uint32_t & t, uint32_t & pxi, uint32_t & pyi)
 {
-  const uint32_t rank = item / patches;
-  const uint32_t p = item - rank * patches;
-  t = (rank & 1u) ? th_mid + (rank + 1u) / 2u : th_mid - rank / 2u;
+  uint32_t p;
+  item_step(item, patches, th_mid, t, p);
   pxi = p / patches_1d;
   pyi = p - pxi * patches_1d;
 }
@@ -166,7 +178,8 @@ __device__ __forceinline__ double no_index_here()
   return __hiloint2double(static_cast<int>(hi), static_cast<int>(lo));
 }
 
-template <int THREADS, bool POW2, bool LDS_RECORDS, bool DYNAMIC_ITEMS, bool COMPACT, bool PARTS = false>
+template <int THREADS, bool POW2, bool LDS_RECORDS, bool DYNAMIC_ITEMS, bool COMPACT, bool PARTS = false,
+          bool STRIPS = false>
 __device__ __forceinline__ void match_lane_body(
   const MatchArgs & a, const double4 * __restrict__ outer, const uint8_t * __restrict__ map_image,
   const LaneGeom & geo)
@@ -232,8 +245,13 @@ __device__ __forceinline__ void match_lane_body(
   const uint32_t lane = threadIdx.x & (kWave - 1);
   const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint32_t n_lin = a.n_lin;
-  const uint32_t patches_1d = (n_lin + kPatch - 1) / kPatch;
-  const uint32_t patches = patches_1d * patches_1d;
+  // STRIPS: the lattice edge is cut into strip tiles (lane_tiling; the launcher picks this
+  // instantiation of an unsplit dynamic-item form when LaneGeom::strips says so -- a lattice
+  // without strips runs the code it always ran, every scalar instruction per item and per
+  // 64 beams shows in a search whose items are mostly passed over)
+  static_assert(!STRIPS || (DYNAMIC_ITEMS && !PARTS), "strip tiles: the unsplit dynamic-item forms only");
+  const LaneTiling tiling = lane_tiling(n_lin, STRIPS);
+  const uint32_t patches = tiling.per_theta;
   // PARTS: a work item is (theta, patch, part of the beams); item / beam_parts is the
   // (theta, patch) item of the unsplit search
   const uint32_t n_items = (a.th_end - a.th_begin) * patches * (PARTS ? a.beam_parts : 1u);
@@ -255,7 +273,7 @@ __device__ __forceinline__ void match_lane_body(
   for (int k = 0; k < 10; ++k) acc[k] = 0.0;
   for (uint32_t item = worker; item < n_items;)
   {
-    uint32_t t, pxi, pyi;
+    uint32_t t, p;
 #ifdef NDT2D_LANE_TRACE
     {
       const unsigned long long now = wall_clock64();
@@ -275,14 +293,28 @@ __device__ __forceinline__ void match_lane_body(
 #endif
     const uint32_t whole_item = PARTS ? item / a.beam_parts : item;
     const uint32_t part = PARTS ? item - whole_item * a.beam_parts : 0u;
-    item_place(whole_item, patches, patches_1d, th_mid, t, pxi, pyi);
-    // (lane -> patch position per item, two instructions, rather than two registers held for good)
+    item_step(whole_item, patches, th_mid, t, p);
+    // the item's tile: wave-uniform, kept in scalar registers across the beam loop
+    uint32_t x0, y0, h_log2, x_end;
+    if (STRIPS)
+    {
+      lane_tile(tiling, n_lin, p, x0, y0, h_log2, x_end);
+    }
+    else
+    {
+      x0 = p / tiling.row * kPatch;
+      y0 = (p - p / tiling.row * tiling.row) * kPatch;
+      h_log2 = 3;
+      x_end = n_lin;
+    }
+    const bool strip_tile = STRIPS && p >= tiling.core;
+    // (lane -> tile position per item, two instructions, rather than two registers held for good)
     uint32_t lane_here = lane;
     asm volatile("" : "+v"(lane_here));
-    const uint32_t ix = pxi * kPatch + (lane_here >> 3);
-    const uint32_t iy = pyi * kPatch + (lane_here & 7);
-    // lanes beyond the lattice edge shadow the edge candidate and are dropped below
-    const double dx = a.dlin[min(ix, n_lin - 1)];
+    const uint32_t ix = x0 + (lane_here >> h_log2);
+    const uint32_t iy = y0 + (lane_here & ((1u << h_log2) - 1u));
+    // lanes beyond the tile's end shadow its last candidate and are dropped below
+    const double dx = a.dlin[min(ix, x_end - 1)];
     const double dy = a.dlin[min(iy, n_lin - 1)];
     const double dxy = packed_offset(dx, dy, inv_scaled);
     const double4 * __restrict__ row = outer + static_cast<size_t>(t) * a.n_beams;
@@ -306,7 +338,18 @@ __device__ __forceinline__ void match_lane_body(
       if (geo.box_span >= 0)
       {
         const double k = row[min(b0 + lane, a.n_beams - 1u)].z;
-        can_score = __builtin_amdgcn_ballot_w64(patch_can_score(k + dxy_corner, geo.box_span));
+        if (strip_tile)
+        {
+          // h < 8: the tile's long side lies along x
+          const bool along_x = h_log2 < 3u;
+          can_score = __builtin_amdgcn_ballot_w64(
+            strip_can_score(k + dxy_corner, along_x ? geo.strip_span_long : geo.strip_span_short,
+                            along_x ? geo.strip_span_short : geo.strip_span_long));
+        }
+        else
+        {
+          can_score = __builtin_amdgcn_ballot_w64(patch_can_score(k + dxy_corner, geo.box_span));
+        }
         NDT2D_PATH(201, 1);
       }
 #ifdef NDT2D_LANE_TRACE
@@ -359,9 +402,9 @@ __device__ __forceinline__ void match_lane_body(
     // held in registers across the beam loop: the kernel runs at 80 VGPRs and used to spill them)
     uint32_t lane_again = lane;
     asm volatile("" : "+v"(lane_again));
-    const uint32_t ix_e = pxi * kPatch + (lane_again >> 3);
-    const uint32_t iy_e = pyi * kPatch + (lane_again & 7);
-    if ((ix_e < n_lin) & (iy_e < n_lin))
+    const uint32_t ix_e = x0 + (lane_again >> h_log2);
+    const uint32_t iy_e = y0 + (lane_again & ((1u << h_log2) - 1u));
+    if ((ix_e < x_end) & (iy_e < n_lin))
     {
       const uint32_t ix = ix_e, iy = iy_e;
       const double score = -sum;  // (:127)
@@ -471,33 +514,35 @@ __device__ __forceinline__ void match_lane_body(
   }
 }
 
-template <int THREADS, bool POW2, bool LDS_RECORDS, bool DYNAMIC_ITEMS>
+// STRIPS (the dynamic-item forms here and below): strip tiles at the lattice edge, see match_lane_body.
+template <int THREADS, bool POW2, bool LDS_RECORDS, bool DYNAMIC_ITEMS, bool STRIPS = false>
 __global__ void __launch_bounds__(THREADS) match_lane_kernel(
   const MatchArgs a, const double4 * __restrict__ outer, const uint8_t * __restrict__ map_image,
   const LaneGeom geo)
 {
-  match_lane_body<THREADS, POW2, LDS_RECORDS, DYNAMIC_ITEMS, false>(a, outer, map_image, geo);
+  match_lane_body<THREADS, POW2, LDS_RECORDS, DYNAMIC_ITEMS, false, false, STRIPS>(a, outer, map_image, geo);
 }
 
 // The compacted-records form: 768-thread blocks held to 80 VGPRs, two per CU = six waves
 // per SIMD (a block's waves must spread evenly over the four SIMDs: 640-thread blocks
 // would put six waves of two blocks on one SIMD, which its register file cannot hold).
+template <bool STRIPS>
 __global__ void __launch_bounds__(kLaneThreadsCompact) __attribute__((amdgpu_waves_per_eu(NDT2D_LANE_COMPACT_WAVES_PER_EU)))
 match_lane_compact_kernel(const MatchArgs a, const double4 * __restrict__ outer,
                           const uint8_t * __restrict__ map_image, const LaneGeom geo)
 {
-  match_lane_body<kLaneThreadsCompact, true, true, true, true>(a, outer, map_image, geo);
+  match_lane_body<kLaneThreadsCompact, true, true, true, true, false, STRIPS>(a, outer, map_image, geo);
 }
 
 // Maps too large for LDS (records gathered from the 64-byte-stride HBM copy through L2):
 // the LDS image is the occupancy map alone, so two 768-thread blocks fit a CU as well --
 // six waves per SIMD to cover the gathers' latency instead of four.
-template <bool POW2>
+template <bool POW2, bool STRIPS>
 __global__ void __launch_bounds__(kLaneThreadsCompact) __attribute__((amdgpu_waves_per_eu(NDT2D_LANE_COMPACT_WAVES_PER_EU)))
 match_lane_gather6_kernel(const MatchArgs a, const double4 * __restrict__ outer,
                           const uint8_t * __restrict__ map_image, const LaneGeom geo)
 {
-  match_lane_body<kLaneThreadsCompact, POW2, false, true, false>(a, outer, map_image, geo);
+  match_lane_body<kLaneThreadsCompact, POW2, false, true, false, false, STRIPS>(a, outer, map_image, geo);
 }
 
 // The beam-part forms of the two six-wave kernels (mid-size lattices, MatchArgs::beam_parts).
@@ -728,7 +773,13 @@ hipError_t launch_match_lane(const MatchArgs & args_in, double * outer, double *
   if (!(compact_possible || gather6_possible)) beam_parts = 1;
   args.beam_parts = beam_parts;
   args.part_beams = part_beams;
-  const uint64_t n_sub_items = n_items * beam_parts;
+  // The unsplit dynamic-item forms run the strip tiling (one record per item: fewer of them);
+  // everything that picks a kernel form above and below keeps counting 8 x 8 patches.
+  if (!(dynamic_items && beam_parts == 1)) geo.strips = 0;
+  const bool strips = geo.strips != 0;
+  const uint64_t n_tiles =
+    static_cast<uint64_t>(args.th_end - args.th_begin) * lane_tiling(args.n_lin, geo.strips != 0).per_theta;
+  const uint64_t n_sub_items = beam_parts > 1 ? n_items * beam_parts : n_tiles;
 
   // Few work items (the plugin's default lattice is 720 of them): 256-thread blocks
   // put them on four times as many CUs -- as long as every wave still gets at most
@@ -736,7 +787,7 @@ hipError_t launch_match_lane(const MatchArgs & args_in, double * outer, double *
   // is what puts more waves on a CU.
   const bool small = beam_parts == 1 && n_items <= static_cast<uint64_t>(cus) * (kLaneThreadsSmall / kWave);
   const uint32_t waves_per_block = (small ? kLaneThreadsSmall : kLaneThreads) / kWave;
-  uint32_t blocks = static_cast<uint32_t>((n_items + waves_per_block - 1) / waves_per_block);
+  uint32_t blocks = static_cast<uint32_t>((n_tiles + waves_per_block - 1) / waves_per_block);
   uint32_t max_blocks = static_cast<uint32_t>(cus);
   if (max_blocks * waves_per_block > max_workers) max_blocks = max_workers / waves_per_block;
   if (blocks > max_blocks) blocks = max_blocks;
@@ -781,14 +832,16 @@ hipError_t launch_match_lane(const MatchArgs & args_in, double * outer, double *
   const bool pow2 = args.grid.pow2 != 0;
   auto pick = [&](auto threads_tag) -> hipError_t {
     constexpr int T = decltype(threads_tag)::value;
-    auto with_items = [&](auto dyn_tag) -> hipError_t {
+    auto with_items = [&](auto dyn_tag, auto strips_tag) -> hipError_t {
       constexpr bool D = decltype(dyn_tag)::value;
-      return lds_records ? (pow2 ? launch(match_lane_kernel<T, true, true, D>, T)
-                                 : launch(match_lane_kernel<T, false, true, D>, T))
-                         : (pow2 ? launch(match_lane_kernel<T, true, false, D>, T)
-                                 : launch(match_lane_kernel<T, false, false, D>, T));
+      constexpr bool S = decltype(strips_tag)::value;
+      return lds_records ? (pow2 ? launch(match_lane_kernel<T, true, true, D, S>, T)
+                                 : launch(match_lane_kernel<T, false, true, D, S>, T))
+                         : (pow2 ? launch(match_lane_kernel<T, true, false, D, S>, T)
+                                 : launch(match_lane_kernel<T, false, false, D, S>, T));
     };
-    return dynamic_items ? with_items(std::true_type{}) : with_items(std::false_type{});
+    if (!dynamic_items) return with_items(std::false_type{}, std::false_type{});
+    return strips ? with_items(std::true_type{}, std::true_type{}) : with_items(std::true_type{}, std::false_type{});
   };
   if (beam_parts > 1)
   {
@@ -804,12 +857,15 @@ hipError_t launch_match_lane(const MatchArgs & args_in, double * outer, double *
   }
   else if (compact)
   {
-    e = launch(match_lane_compact_kernel, kLaneThreadsCompact);
+    e = strips ? launch(match_lane_compact_kernel<true>, kLaneThreadsCompact)
+               : launch(match_lane_compact_kernel<false>, kLaneThreadsCompact);
   }
   else if (gather6)
   {
-    e = pow2 ? launch(match_lane_gather6_kernel<true>, kLaneThreadsCompact)
-             : launch(match_lane_gather6_kernel<false>, kLaneThreadsCompact);
+    e = pow2 ? (strips ? launch(match_lane_gather6_kernel<true, true>, kLaneThreadsCompact)
+                       : launch(match_lane_gather6_kernel<true, false>, kLaneThreadsCompact))
+             : (strips ? launch(match_lane_gather6_kernel<false, true>, kLaneThreadsCompact)
+                       : launch(match_lane_gather6_kernel<false, false>, kLaneThreadsCompact));
   }
   else
   {
@@ -819,7 +875,9 @@ hipError_t launch_match_lane(const MatchArgs & args_in, double * outer, double *
   if (parts_out != nullptr) *parts_out = beam_parts;
   if (n_workers_out != nullptr)
   {
-    *n_workers_out = dynamic_items ? static_cast<uint32_t>(n_items) : blocks * waves_per_block;
+    // (records: one per item -- tiles of the unsplit form, patches of the beam-part form -- or per wave)
+    *n_workers_out = dynamic_items ? static_cast<uint32_t>(beam_parts > 1 ? n_items : n_tiles)
+                                   : blocks * waves_per_block;
   }
   return e;
 }
