@@ -18,6 +18,7 @@
 #include "ndt2d_batch_search.h"
 #include "ndt2d_hip.h"
 #include "ndt2d_job_groups.h"
+#include "ndt2d_refine_jobs.h"
 
 namespace ndt2d
 {
@@ -267,20 +268,15 @@ struct JobsEngine : BatchHost
 
 // A call's arguments, checked by the entry point: finite poses, job_scan[k] < n_scans, every
 // scan 1 .. 2^20 beams, a lattice ndt2d_set_search takes.
-struct JobsCall
+struct JobsCall : refine_jobs::JobList
 {
-  const double * jobs_xyt;
-  const uint32_t * job_scan;   // NULL: job k uses scan k
-  bool one_scan;               // start poses: every job uses scan 0 (n_scans = 1), the blocks take StartSlots
-  size_t n_jobs;
-  const double * beams_xy;
-  const size_t * beam_offsets;
-  size_t n_scans;
+  bool one_scan;   // start poses: every job uses scan 0 (n_scans = 1, no job_scan), the blocks take StartSlots
   const double * dth;
   size_t n_th;
   const double * dlin;
   size_t n_lin;
-  size_t scan_of(size_t k) const { return one_scan ? 0 : job_scan != nullptr ? job_scan[k] : k; }
+  size_t scan_of(size_t k) const { return one_scan ? 0 : JobList::scan_of(k); }
+  size_t beams_of(size_t k) const { return beam_offsets[scan_of(k) + 1] - beam_offsets[scan_of(k)]; }
 };
 
 // The checked call against the grid installed now, in chunks of e->max_jobs; `who` names the

@@ -1,8 +1,11 @@
-// What the Newton registrations share on the host (refine/ndt2d_refine.hip: jobs on the installed
-// grid; closure/ndt2d_closure.hip: jobs on the loop closure's candidate maps): what both refuse
-// about rules, scans and jobs -- one text, so that the two objects cannot drift apart in what they
-// refuse -- and which scans a chunk uploads, with their copy into the stage (the verifications,
-// verify/ndt2d_verify.hip and the closure's, take all three too).  Plain C++: no HIP.
+// The (scan, pose) job list every batched call takes, on the host: K jobs over S scans, each scan's
+// beams once however many jobs name it.  The searches (scans/ndt2d_scans.hip, with starts/ through
+// its engine), the Newton registrations (refine/ndt2d_refine.hip: jobs on the installed grid;
+// closure/ndt2d_closure.hip: jobs on the loop closure's candidate maps) and the verifications
+// (verify/ndt2d_verify.hip and the closure's) share it: the list itself, what they refuse about
+// scans and jobs -- one text, so that the objects cannot drift apart in what they refuse --, what
+// the registrations refuse about their rules, and which scans a chunk uploads, with their copy
+// into the stage.  Plain C++: no HIP.
 #ifndef NDT2D_REFINE_JOBS_H_
 #define NDT2D_REFINE_JOBS_H_
 
@@ -22,11 +25,22 @@ namespace refine_jobs
 constexpr size_t kMaxScanBeams = size_t(1) << 20;   // what ndt2d_set_beams takes
 constexpr uint64_t kNotSent = ~uint64_t(0);
 
-// The rules, every scan and every job of a call, checked before anything is launched.  Returns
-// the refusal's text, prefixed with `entry` (the message names the scan or the job), or an empty
-// string.  job_scan NULL: job k uses scan k.
-inline std::string refusal(const char * entry, const double * jobs_xyt, const uint32_t * job_scan, size_t n_jobs,
-                           const size_t * beam_offsets, size_t n_scans, uint32_t max_evals, double tol_lin, double tol_ang)
+// A call's jobs and scans.  The objects' own calls hold one beside what only they take.
+struct JobList
+{
+  const double * jobs_xyt;
+  const uint32_t * job_scan;   // NULL: job k uses scan k
+  size_t n_jobs;
+  const double * beams_xy;
+  const size_t * beam_offsets;
+  size_t n_scans;
+  size_t scan_of(size_t k) const { return job_scan != nullptr ? job_scan[k] : k; }
+  size_t beams_of(size_t k) const { return beam_offsets[scan_of(k) + 1] - beam_offsets[scan_of(k)]; }
+};
+
+// What a registration refuses about its rules: the refusal's text, prefixed with `entry`, or an
+// empty string.
+inline std::string rules_refusal(const char * entry, uint32_t max_evals, double tol_lin, double tol_ang)
 {
   const std::string who = std::string(entry) + ": ";
   if (max_evals == 0) return who + "bad argument (max_evals == 0)";
@@ -34,6 +48,16 @@ inline std::string refusal(const char * entry, const double * jobs_xyt, const ui
   {
     return who + "bad argument (a tolerance is negative or not finite)";
   }
+  return std::string();
+}
+
+// Every scan and every job of a call, checked before anything is launched.  Returns the refusal's
+// text, prefixed with `entry` (the message names the scan or the job), or an empty string.
+// job_scan NULL: job k uses scan k.
+inline std::string refusal(const char * entry, const double * jobs_xyt, const uint32_t * job_scan, size_t n_jobs,
+                           const size_t * beam_offsets, size_t n_scans)
+{
+  const std::string who = std::string(entry) + ": ";
   if (n_jobs >= (1u << 24) || n_scans >= (1u << 24)) return who + "bad argument (n_jobs, n_scans)";
   if (job_scan == nullptr && n_scans != n_jobs)
   {
@@ -61,6 +85,14 @@ inline std::string refusal(const char * entry, const double * jobs_xyt, const ui
     }
   }
   return std::string();
+}
+
+// The rules, then the list: what a registration refuses, in that order.
+inline std::string refusal(const char * entry, const double * jobs_xyt, const uint32_t * job_scan, size_t n_jobs,
+                           const size_t * beam_offsets, size_t n_scans, uint32_t max_evals, double tol_lin, double tol_ang)
+{
+  const std::string rules = rules_refusal(entry, max_evals, tol_lin, tol_ang);
+  return !rules.empty() ? rules : refusal(entry, jobs_xyt, job_scan, n_jobs, beam_offsets, n_scans);
 }
 
 // The scans a chunk's jobs name, each once, in the order the jobs first name them: scan_first[s] =

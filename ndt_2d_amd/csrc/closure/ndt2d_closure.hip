@@ -574,15 +574,9 @@ int job_chunk(ndt2d_closure * c, const ndt2d::ClosureJobChunk & plan, const Cand
   return NDT2D_OK;
 }
 
-struct RefineCall
+struct RefineCall : ndt2d::refine_jobs::JobList
 {
-  const double * jobs_xyt;
-  const uint32_t * job_scan;   // NULL: job k uses scan k
-  const double * beams_xy;
-  const size_t * beam_offsets;
-  size_t n_scans;
   ndt2d::refine::Rules rules;
-  size_t scan_of(size_t k) const { return job_scan != nullptr ? job_scan[k] : k; }
 };
 
 // One chunk of ndt2d_closure_refine's plan.  records_out: the call's, whole.
@@ -596,9 +590,7 @@ int refine_chunk(ndt2d_closure * c, const ndt2d::ClosureJobChunk & plan, const C
     c, plan, m, t, ndt2d::kRefineJobDoubles, n_jobs * kRefineRec,
     [&](size_t b, size_t k, uint64_t first, double * to) {
       const double * p = t.jobs_xyt + 3 * k;
-      const size_t sc = t.scan_of(k);
-      *reinterpret_cast<RefineJob *>(to) =
-        RefineJob{p[0], p[1], p[2], static_cast<uint32_t>(t.beam_offsets[sc + 1] - t.beam_offsets[sc]), plan.job_slot[b], first};
+      *reinterpret_cast<RefineJob *>(to) = RefineJob{p[0], p[1], p[2], static_cast<uint32_t>(t.beams_of(k)), plan.job_slot[b], first};
     },
     [&](const ChunkOnDevice & d) {
       ndt2d::SlotRefineArgs a{};
@@ -670,12 +662,12 @@ int verify_chunk(ndt2d_closure * c, const ndt2d::ClosureJobChunk & plan, const C
 
 // What ndt2d_closure_refine and ndt2d_closure_verify (`entry`) refuse, every check before anything
 // is launched: null arguments, the grid's parameters, the rules, every scan and every job -- what
-// ndt2d_refine_run refuses, one text: batch/ndt2d_refine_jobs.h (the verification gives rules it
-// takes) -- every candidate, as ndt2d_closure_match does, and the jobs' candidates.
+// ndt2d_refine_run refuses, one text: batch/ndt2d_refine_jobs.h (rules NULL: the verification,
+// which has none) -- every candidate, as ndt2d_closure_match does, and the jobs' candidates.
 int check_job_call(ndt2d_closure * c, const char * entry, size_t n_candidates, const CandidateMaps & m, double ndt_resolution,
                    double range_max, const double * jobs_xyt, const uint32_t * job_scan, const uint32_t * job_candidate,
                    size_t n_jobs, const double * beams_xy, const size_t * beam_offsets, size_t n_scans, const void * records_out,
-                   uint32_t max_evals, double tol_lin, double tol_ang)
+                   const ndt2d::refine::Rules * rules)
 {
   const std::string who = std::string(entry) + ": ";
   if (m.cand_offsets == nullptr || m.ids == nullptr || m.poses_xyt == nullptr || jobs_xyt == nullptr || records_out == nullptr ||
@@ -694,7 +686,9 @@ int check_job_call(ndt2d_closure * c, const char * entry, size_t n_candidates, c
                       who + "bad argument (no job_candidate: job k uses candidate k, n_candidates must equal n_jobs)");
   }
   const std::string refusal =
-    ndt2d::refine_jobs::refusal(entry, jobs_xyt, job_scan, n_jobs, beam_offsets, n_scans, max_evals, tol_lin, tol_ang);
+    rules != nullptr
+      ? ndt2d::refine_jobs::refusal(entry, jobs_xyt, job_scan, n_jobs, beam_offsets, n_scans, rules->max_evals, rules->tol_lin, rules->tol_ang)
+      : ndt2d::refine_jobs::refusal(entry, jobs_xyt, job_scan, n_jobs, beam_offsets, n_scans);
   if (!refusal.empty()) return batch_fail(c, NDT2D_ERR_INVALID, refusal);
   const int crc = check_candidates(c, entry, n_candidates, m.cand_offsets, m.ids, m.poses_xyt, ndt_resolution, range_max);
   if (crc != NDT2D_OK) return crc;
@@ -840,11 +834,12 @@ int ndt2d_closure_refine(ndt2d_closure * c, size_t n_candidates, const size_t * 
   if (c == nullptr) return NDT2D_ERR_INVALID;
   if (n_jobs == 0) return NDT2D_OK;
   const CandidateMaps m{cand_offsets, ids, poses_xyt};
+  const ndt2d::refine::Rules rules{max_evals, tol_lin, tol_ang};
   const int crc = check_job_call(c, "ndt2d_closure_refine", n_candidates, m, ndt_resolution, range_max, jobs_xyt, job_scan,
-                                 job_candidate, n_jobs, beams_xy, beam_offsets, n_scans, records_out, max_evals, tol_lin, tol_ang);
+                                 job_candidate, n_jobs, beams_xy, beam_offsets, n_scans, records_out, &rules);
   if (crc != NDT2D_OK) return crc;
   NDT2D_BATCH_HIP(c, hipSetDevice(c->device));
-  const RefineCall t{jobs_xyt, job_scan, beams_xy, beam_offsets, n_scans, {max_evals, tol_lin, tol_ang}};
+  const RefineCall t{{jobs_xyt, job_scan, n_jobs, beams_xy, beam_offsets, n_scans}, rules};
   for (const ndt2d::ClosureJobChunk & chunk :
        ndt2d::plan_closure_jobs(job_candidate, n_jobs, n_candidates, c->max_candidates, ndt2d::kRefineMaxJobs))
   {
@@ -917,9 +912,8 @@ int ndt2d_closure_verify(ndt2d_closure * c, size_t n_candidates, const size_t * 
   if (c == nullptr) return NDT2D_ERR_INVALID;
   if (n_jobs == 0) return NDT2D_OK;
   const CandidateMaps m{cand_offsets, ids, poses_xyt};
-  // (the registration's rules are not this call's: given as ones the shared check takes)
   const int crc = check_job_call(c, "ndt2d_closure_verify", n_candidates, m, ndt_resolution, range_max, jobs_xyt, job_scan,
-                                 job_candidate, n_jobs, beams_xy, beam_offsets, n_scans, records_out, 1u, 0.0, 0.0);
+                                 job_candidate, n_jobs, beams_xy, beam_offsets, n_scans, records_out, nullptr);
   if (crc != NDT2D_OK) return crc;
   for (size_t k = 0; k < n_candidates && c->verify.rays; ++k)
   {
@@ -931,7 +925,7 @@ int ndt2d_closure_verify(ndt2d_closure * c, size_t n_candidates, const size_t * 
     }
   }
   NDT2D_BATCH_HIP(c, hipSetDevice(c->device));
-  const ndt2d::VerifyCall v{jobs_xyt,    job_scan,       n_jobs,      beams_xy,      beam_offsets, n_scans,
+  const ndt2d::VerifyCall v{{jobs_xyt, job_scan, n_jobs, beams_xy, beam_offsets, n_scans},
                             records_out, beam_class_out, beam_m2_out, beam_cells_out};
   // job k's beams start at the sum of the earlier jobs' scan lengths
   c->job_first.resize(n_jobs + 1);

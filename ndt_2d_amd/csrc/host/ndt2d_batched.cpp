@@ -6,11 +6,14 @@
 // the same on each loop-closure candidate's own map (refine_candidates), one call of the closure object,
 // and the match verification of K (scan, pose) jobs (verify_scans), one call of the object under csrc/verify,
 // and the same on each loop-closure candidate's own map (verify_candidates), one call of the closure object.
+// The five calls on a (scan, pose) job list check it, collect its batch and deal the records back through
+// host/ndt2d_job_batch.h.
 #include <cstring>
 #include <functional>
 #include <string>
 #include <vector>
 
+#include "host/ndt2d_job_batch.h"
 #include "host/ndt2d_matcher_state.h"
 #include "ndt2d_guard.h"
 
@@ -98,54 +101,29 @@ int finish_slots(ndt2d_matcher * m, size_t n_slots, const double * records, cons
 // Candidates the batched match launches at a time: the plugin's global_search_limit_ is a handful.
 constexpr size_t kClosureSlots = 16;
 
-// The outputs of a Newton registration (refine_scans, refine_candidates); all but poses, scores and
-// status are optional.
-struct RefineOut
+// The registration's rules, as refine_scans and refine_candidates take them.
+struct RefineRules
 {
-  double * poses, * scores, * start_scores, * gradients, * hessians;
-  int32_t * status;
-  uint32_t * evals;
+  uint32_t max_evals;
+  double tol_lin, tol_ang;
 };
 
-// What both registrations refuse about rules, scans and jobs; `who` names the call.
-int check_refine_input(ndt2d_matcher * m, const std::string & who, const double * jobs_xyt, const uint32_t * job_scan,
-                       size_t n_jobs, const double * points_xy, const size_t * point_offsets, size_t n_scans,
-                       uint32_t max_evals, double tol_lin, double tol_ang)
+// What the batched calls on a job list refuse about its size, the rules (NULL: a verification, which
+// has none), the scans and the jobs, in that order; `who` names the call.
+int check_job_input(ndt2d_matcher * m, const std::string & who, const double * jobs_xyt, const uint32_t * job_scan, size_t n_jobs,
+                    const double * points_xy, const size_t * point_offsets, size_t n_scans, const RefineRules * rules)
 {
-  if (n_jobs > (1u << 20) || n_scans > (1u << 20)) return mfail(m, NDT2D_ERR_INVALID, who + ": too many jobs or scans");
-  if (max_evals == 0) return mfail(m, NDT2D_ERR_INVALID, who + ": max_evals == 0");
-  if (!(tol_lin >= 0.0) || !(tol_ang >= 0.0) || !std::isfinite(tol_lin) || !std::isfinite(tol_ang))
+  std::string refusal = job_list_size_refusal(who, n_jobs, n_scans);
+  if (refusal.empty() && rules != nullptr)
   {
-    return mfail(m, NDT2D_ERR_INVALID, who + ": a tolerance is negative or not finite");
-  }
-  if (job_scan == nullptr && n_scans != n_jobs)
-  {
-    return mfail(m, NDT2D_ERR_INVALID, who + ": no job_scan (job k uses scan k): n_scans must equal n_jobs");
-  }
-  for (size_t sc = 0; sc < n_scans; ++sc)
-  {
-    if (point_offsets[sc + 1] < point_offsets[sc])
+    if (rules->max_evals == 0) refusal = who + ": max_evals == 0";
+    else if (!(rules->tol_lin >= 0.0) || !(rules->tol_ang >= 0.0) || !std::isfinite(rules->tol_lin) || !std::isfinite(rules->tol_ang))
     {
-      return mfail(m, NDT2D_ERR_INVALID, who + ": scan " + std::to_string(sc) + ": point_offsets decrease");
+      refusal = who + ": a tolerance is negative or not finite";
     }
   }
-  if (n_scans > 0 && point_offsets[n_scans] > point_offsets[0] && points_xy == nullptr)
-  {
-    return mfail(m, NDT2D_ERR_INVALID, who + ": null input");
-  }
-  for (size_t k = 0; k < n_jobs; ++k)
-  {
-    if (!std::isfinite(jobs_xyt[3 * k]) || !std::isfinite(jobs_xyt[3 * k + 1]) || !std::isfinite(jobs_xyt[3 * k + 2]))
-    {
-      return mfail(m, NDT2D_ERR_INVALID, who + ": job " + std::to_string(k) + ": the pose is not finite");
-    }
-    if (job_scan != nullptr && job_scan[k] >= n_scans)
-    {
-      return mfail(m, NDT2D_ERR_INVALID, who + ": job " + std::to_string(k) + ": scan " + std::to_string(job_scan[k]) +
-                                             " of " + std::to_string(n_scans));
-    }
-  }
-  return NDT2D_OK;
+  if (refusal.empty()) refusal = job_list_refusal(who, jobs_xyt, job_scan, n_jobs, points_xy, point_offsets, n_scans);
+  return refusal.empty() ? NDT2D_OK : mfail(m, NDT2D_ERR_INVALID, refusal);
 }
 
 // What refine_candidates and verify_candidates refuse about the jobs' candidates; `who` names the call.
@@ -184,100 +162,63 @@ void fill_no_overlap(const double * jobs_xyt, size_t n_jobs, const RefineOut & o
   }
 }
 
-// The jobs of a registration's (or a verification's) device call: every scan a job names as
-// scorePoints takes it -- subsampled beams (:165-166,171) to max_beams, 0: every point --, once per
-// scan; a scan without points is not among them, and neither are its jobs.
-struct RefineBatch
+// The candidates of the batch's jobs; job_candidate NULL: job k uses candidate k.
+std::vector<uint32_t> batch_candidates(const JobBatch & batch, const uint32_t * job_candidate)
 {
-  std::vector<double> beams, xyt;
-  std::vector<size_t> beam_offsets;
-  std::vector<uint32_t> job, scan;   // the jobs of the device call and their scans
+  std::vector<uint32_t> out(batch.size());
+  for (size_t j = 0; j < batch.size(); ++j) out[j] = job_candidate != nullptr ? job_candidate[batch.job[j]] : batch.job[j];
+  return out;
+}
+
+// The closure object, made by the first call that needs it.
+int ensure_closure(ndt2d_matcher * m)
+{
+  if (m->closure != nullptr) return NDT2D_OK;
+  const int rc = ndt2d_closure_create(m->dev, m->stores[0], kClosureSlots, &m->closure);
+  return rc == NDT2D_OK ? NDT2D_OK : dev_fail(m, rc, "ndt2d_closure_create");
+}
+
+// Where a verification's results go (verify_scans, verify_candidates); all but records are optional.
+struct VerifyOut
+{
+  uint32_t * records;
+  size_t * beam_offsets;
+  uint8_t * beam_class;
+  double * beam_m2;
+  uint32_t * beam_cells;
+  size_t beam_cap;
 };
 
-void collect_refine_batch(size_t max_beams, const double * jobs_xyt, const uint32_t * job_scan, size_t n_jobs,
-                          const double * points_xy, const size_t * point_offsets, size_t n_scans, RefineBatch & b)
+// What both verifications do round their device call: the capacity refusal, the zeroed records and
+// the offsets table of all n_jobs jobs -- before the device call (fill_first) or only after it
+// succeeded --, the call on a batch that has jobs, and its records dealt to their jobs.
+// run(records): the device call into [batch job][NDT2D_VERIFY_RECORD_U32]; the per-beam arrays are
+// the batch's, job after job: a job without beams takes no room in them.
+template <class RUN>
+int verify_batch(ndt2d_matcher * m, const std::string & who, const JobBatch & batch, size_t n_jobs, const VerifyOut & out,
+                 bool fill_first, RUN run)
 {
-  // sent[s]: its index among the scans the device call receives
-  constexpr uint32_t kUnseen = ~0u, kEmpty = ~0u - 1u;
-  std::vector<uint32_t> sent(n_scans, kUnseen);
-  std::vector<double> one;
-  b.beam_offsets.assign(1, 0);
-  for (size_t k = 0; k < n_jobs; ++k)
+  const size_t n_beams_all = batch_beams(batch);
+  const bool want_beams = out.beam_class != nullptr || out.beam_m2 != nullptr || out.beam_cells != nullptr;
+  if (want_beams && out.beam_cap < n_beams_all)
   {
-    const size_t sc = job_scan != nullptr ? static_cast<size_t>(job_scan[k]) : k;
-    if (sent[sc] == kUnseen)
-    {
-      const size_t n_points = point_offsets[sc + 1] - point_offsets[sc];
-      subsample_into(one, points_xy + 2 * point_offsets[sc], n_points, max_beams != 0 ? max_beams : n_points);
-      if (one.empty())
-      {
-        sent[sc] = kEmpty;
-      }
-      else
-      {
-        sent[sc] = static_cast<uint32_t>(b.beam_offsets.size() - 1);
-        b.beams.insert(b.beams.end(), one.begin(), one.end());
-        b.beam_offsets.push_back(b.beams.size() / 2);
-      }
-    }
-    if (sent[sc] == kEmpty) continue;
-    b.job.push_back(static_cast<uint32_t>(k));
-    b.scan.push_back(sent[sc]);
-    b.xyt.insert(b.xyt.end(), jobs_xyt + 3 * k, jobs_xyt + 3 * k + 3);
+    return mfail(m, NDT2D_ERR_INVALID, who + ": the per-beam arrays hold " + std::to_string(out.beam_cap) + " beams, the jobs have " +
+                                           std::to_string(n_beams_all));
   }
-}
-
-// Where each job's beams start in a verification's per-beam arrays ([n_jobs + 1]): the batch's jobs
-// in order, the jobs of scans without points between them with no beams.
-void fill_verify_offsets(const RefineBatch & b, size_t n_jobs, size_t * beam_offsets_out)
-{
-  size_t at = 0, j = 0;
-  for (size_t k = 0; k < n_jobs; ++k)
+  const auto fill = [&]() {
+    std::memset(out.records, 0, n_jobs * NDT2D_VERIFY_RECORD_U32 * sizeof(uint32_t));   // (the jobs of a scan without points keep this)
+    if (out.beam_offsets != nullptr) fill_verify_offsets(batch, n_jobs, out.beam_offsets);
+  };
+  if (fill_first) fill();
+  std::vector<uint32_t> records(batch.size() * NDT2D_VERIFY_RECORD_U32);
+  if (batch.size() != 0)
   {
-    beam_offsets_out[k] = at;
-    if (j < b.job.size() && b.job[j] == k)
-    {
-      at += b.beam_offsets[b.scan[j] + 1] - b.beam_offsets[b.scan[j]];
-      ++j;
-    }
+    const int rc = run(records.data());
+    if (rc != NDT2D_OK) return rc;
   }
-  beam_offsets_out[n_jobs] = at;
-}
-
-// The device call's records ([batch job][NDT2D_REFINE_RECORD_DOUBLES]) into the outputs of their jobs.
-void deal_refine_records(const RefineBatch & b, const double * records, const RefineOut & o)
-{
-  constexpr size_t kRefRec = NDT2D_REFINE_RECORD_DOUBLES;
-  for (size_t j = 0; j < b.job.size(); ++j)
-  {
-    const size_t k = b.job[j];
-    const double * rec = records + j * kRefRec;
-    // f, g, H of the sum over the scan's N beams -> of `score / N` (:177)
-    const double n = static_cast<double>(b.beam_offsets[b.scan[j] + 1] - b.beam_offsets[b.scan[j]]);
-    std::memcpy(o.poses + 3 * k, rec, 3 * sizeof(double));
-    o.scores[k] = rec[4] / n;
-    o.status[k] = static_cast<int32_t>(rec[16]);
-    if (o.start_scores != nullptr) o.start_scores[k] = rec[3] / n;
-    if (o.gradients != nullptr)
-    {
-      for (int d = 0; d < 3; ++d) o.gradients[3 * k + d] = rec[5 + d] / n;
-    }
-    if (o.hessians != nullptr)
-    {
-      double * h = o.hessians + 9 * k;
-      h[0] = rec[8] / n;
-      h[1] = h[3] = rec[9] / n;
-      h[2] = h[6] = rec[10] / n;
-      h[4] = rec[11] / n;
-      h[5] = h[7] = rec[12] / n;
-      h[8] = rec[13] / n;
-    }
-    if (o.evals != nullptr)
-    {
-      o.evals[2 * k] = static_cast<uint32_t>(rec[14]);
-      o.evals[2 * k + 1] = static_cast<uint32_t>(rec[15]);
-    }
-  }
+  if (!fill_first) fill();
+  deal_verify_records(batch, records.data(), NDT2D_VERIFY_RECORD_U32, out.records);
+  return NDT2D_OK;
 }
 
 }  // namespace
@@ -307,11 +248,8 @@ int ndt2d_matcher_match_candidates(ndt2d_matcher * m, const double * scan_pose_x
     return mfail(m, NDT2D_ERR_INVALID, "match_candidates: candidate 0: unknown scan id (no scan is stored)");
   }
   discard_ahead(m);   // a search launched ahead by scoreScan is waited out and dropped
-  if (m->closure == nullptr)
-  {
-    const int rc = ndt2d_closure_create(m->dev, m->stores[0], kClosureSlots, &m->closure);
-    if (rc != NDT2D_OK) return dev_fail(m, rc, "ndt2d_closure_create");
-  }
+  const int crc = ensure_closure(m);
+  if (crc != NDT2D_OK) return crc;
   double * scores_ptr = scores_if_they_fit(all_scores, all_scores_cap, n_candidates, n_lattice);
 
   // the scan as matchScan takes it: subsampled beams (:95-96,110), cos / sin per theta step (:106-107)
@@ -432,39 +370,16 @@ int ndt2d_matcher_match_scans(ndt2d_matcher * m, const double * jobs_xyt, const 
   {
     return mfail(m, NDT2D_ERR_INVALID, "match_scans: null input");
   }
-  if (n_jobs > (1u << 20) || n_scans > (1u << 20)) return mfail(m, NDT2D_ERR_INVALID, "match_scans: too many jobs or scans");
+  // (the list's size is refused before the `if (!ndt_)` return, everything else of it after)
+  std::string refusal = job_list_size_refusal("match_scans", n_jobs, n_scans);
+  if (!refusal.empty()) return mfail(m, NDT2D_ERR_INVALID, refusal);
   if (!m->ndt.have())
   {
     fill_no_ndt(n_jobs, scores_out, best_index_out);
     return NDT2D_OK;
   }
-  if (job_scan == nullptr && n_scans != n_jobs)
-  {
-    return mfail(m, NDT2D_ERR_INVALID, "match_scans: no job_scan (job k uses scan k): n_scans must equal n_jobs");
-  }
-  for (size_t sc = 0; sc < n_scans; ++sc)
-  {
-    if (point_offsets[sc + 1] < point_offsets[sc])
-    {
-      return mfail(m, NDT2D_ERR_INVALID, "match_scans: scan " + std::to_string(sc) + ": point_offsets decrease");
-    }
-  }
-  if (n_scans > 0 && point_offsets[n_scans] > point_offsets[0] && points_xy == nullptr)
-  {
-    return mfail(m, NDT2D_ERR_INVALID, "match_scans: null input");
-  }
-  for (size_t k = 0; k < n_jobs; ++k)
-  {
-    if (!std::isfinite(jobs_xyt[3 * k]) || !std::isfinite(jobs_xyt[3 * k + 1]) || !std::isfinite(jobs_xyt[3 * k + 2]))
-    {
-      return mfail(m, NDT2D_ERR_INVALID, "match_scans: job " + std::to_string(k) + ": the pose is not finite");
-    }
-    if (job_scan != nullptr && job_scan[k] >= n_scans)
-    {
-      return mfail(m, NDT2D_ERR_INVALID, "match_scans: job " + std::to_string(k) + ": scan " + std::to_string(job_scan[k]) +
-                                             " of " + std::to_string(n_scans));
-    }
-  }
+  refusal = job_list_refusal("match_scans", jobs_xyt, job_scan, n_jobs, points_xy, point_offsets, n_scans);
+  if (!refusal.empty()) return mfail(m, NDT2D_ERR_INVALID, refusal);
   const size_t n_th = m->search.dth.size(), n_lin = m->search.dlin.size();
   const size_t n_lattice = n_th * n_lin * n_lin;
   if (n_lattice_out != nullptr) *n_lattice_out = n_lattice;
@@ -477,73 +392,33 @@ int ndt2d_matcher_match_scans(ndt2d_matcher * m, const double * jobs_xyt, const 
   double * scores_ptr = scores_if_they_fit(all_scores, all_scores_cap, n_jobs, n_lattice);
   const auto scan_of = [&](size_t k) { return job_scan != nullptr ? static_cast<size_t>(job_scan[k]) : k; };
 
-  // every scan a job names as matchScan takes it: subsampled beams (:95-96,110), once per scan.
-  // sent[s]: its index among the scans the batched call receives (a scan without points is not
-  // among them: its jobs go through the sequential call).
-  constexpr uint32_t kUnseen = ~0u, kEmpty = ~0u - 1u;
-  std::vector<uint32_t> sent(n_scans, kUnseen);
-  std::vector<double> beams, one;
-  std::vector<size_t> beam_offsets(1, 0);
-  std::vector<uint32_t> batch_job, batch_scan;   // the jobs of the batched call and their scans
-  for (size_t k = 0; k < n_jobs && n_lattice > 0; ++k)
-  {
-    const size_t sc = scan_of(k);
-    if (sent[sc] == kUnseen)
-    {
-      subsample_into(one, points_xy + 2 * point_offsets[sc], point_offsets[sc + 1] - point_offsets[sc], m->laser_max_beams);
-      if (one.empty())
-      {
-        sent[sc] = kEmpty;
-      }
-      else
-      {
-        sent[sc] = static_cast<uint32_t>(beam_offsets.size() - 1);
-        beams.insert(beams.end(), one.begin(), one.end());
-        beam_offsets.push_back(beams.size() / 2);
-      }
-    }
-    if (sent[sc] == kEmpty) continue;
-    batch_job.push_back(static_cast<uint32_t>(k));
-    batch_scan.push_back(sent[sc]);
-  }
+  // the jobs of the batched call, laser_max_beams as it is (0: no beams); a job outside it -- no
+  // points, or no lattice: then nothing is collected -- goes through the sequential call
+  JobBatch batch;
+  if (n_lattice > 0) collect_job_batch(m->laser_max_beams, jobs_xyt, job_scan, n_jobs, points_xy, point_offsets, n_scans, batch);
   m->search.ready = false;   // no search is prepared on the context
-  std::vector<char> sequential(n_jobs, 1);   // (a job outside the batch: no points, or no lattice)
-  const size_t n_batch = batch_job.size();
+  std::vector<char> sequential(n_jobs, 1);
+  const size_t n_batch = batch.size();
   m->scans_records.assign(n_jobs * kRec, 0.0);   // the batch's records in front, then moved to their jobs' slots
   double * records = m->scans_records.data();
   if (n_batch > 0)
   {
     // (all jobs in the batch: its scores are the caller's rows; else they are dealt out below)
-    std::vector<double> batch_scores, batch_xyt;
-    const double * xyt = jobs_xyt;
+    std::vector<double> batch_scores;
     double * batch_scores_ptr = scores_ptr;
-    if (n_batch != n_jobs)
+    if (n_batch != n_jobs && scores_ptr != nullptr)
     {
-      batch_xyt.resize(3 * n_batch);
-      for (size_t j = 0; j < n_batch; ++j) std::memcpy(&batch_xyt[3 * j], jobs_xyt + 3 * batch_job[j], 3 * sizeof(double));
-      xyt = batch_xyt.data();
-      if (scores_ptr != nullptr)
-      {
-        batch_scores.resize(n_batch * n_lattice);
-        batch_scores_ptr = batch_scores.data();
-      }
+      batch_scores.resize(n_batch * n_lattice);
+      batch_scores_ptr = batch_scores.data();
     }
-    const int rc = ndt2d_scans_match(m->scans, xyt, batch_scan.data(), n_batch, beams.data(), beam_offsets.data(),
-                                     beam_offsets.size() - 1, m->search.dth.data(), n_th, m->search.dlin.data(), n_lin,
-                                     records, batch_scores_ptr);
+    const int rc = ndt2d_scans_match(m->scans, batch.xyt.data(), batch.scan.data(), n_batch, batch.beams.data(),
+                                     batch.beam_offsets.data(), batch.scans(), m->search.dth.data(), n_th, m->search.dlin.data(),
+                                     n_lin, records, batch_scores_ptr);
     if (rc != NDT2D_OK) return mfail(m, rc, std::string("match_scans: ") + ndt2d_scans_last_error(m->scans));
     m->last_multi = false;
-    // (from the last: batch_job ascends, so record j's slot batch_job[j] >= j holds no record still to be moved)
-    for (size_t j = n_batch; j-- > 0;)
-    {
-      const size_t k = batch_job[j];
-      if (k != j) std::memcpy(records + k * kRec, records + j * kRec, kRec * sizeof(double));
-      sequential[k] = marked_winner(records + k * kRec);
-      if (!batch_scores.empty() && !sequential[k])
-      {
-        std::memcpy(scores_ptr + k * n_lattice, &batch_scores[j * n_lattice], n_lattice * sizeof(double));
-      }
-    }
+    move_match_records(batch, kRec, records);
+    for (size_t j = 0; j < n_batch; ++j) sequential[batch.job[j]] = marked_winner(records + batch.job[j] * kRec);
+    if (!batch_scores.empty()) deal_lattice_scores(batch, batch_scores.data(), n_lattice, sequential, scores_ptr);
   }
   const BatchOut out = {poses_out, covariances_out, scores_out, best_index_out, scores_ptr, n_lattice};
   return finish_slots(
@@ -555,8 +430,7 @@ int ndt2d_matcher_match_scans(ndt2d_matcher * m, const double * jobs_xyt, const 
     },
     [&](size_t k) {
       // the N of `best / N` (:148) is the job's own scan's
-      const uint32_t s = sent[scan_of(k)];
-      m->search.n_use = beam_offsets[s + 1] - beam_offsets[s];
+      m->search.n_use = batch.scan_beams(batch.sent[scan_of(k)]);
       m->search.ready = false;   // (a sequential call in between prepared a search of its own)
     });
   NDT2D_C_CATCH(m)
@@ -580,8 +454,8 @@ int ndt2d_matcher_refine_scans(ndt2d_matcher * m, const double * jobs_xyt, const
   {
     return mfail(m, NDT2D_ERR_INVALID, "refine_scans: null input");
   }
-  int rc = check_refine_input(m, "refine_scans", jobs_xyt, job_scan, n_jobs, points_xy, point_offsets, n_scans, max_evals, tol_lin,
-                              tol_ang);
+  const RefineRules rules = {max_evals, tol_lin, tol_ang};
+  int rc = check_job_input(m, "refine_scans", jobs_xyt, job_scan, n_jobs, points_xy, point_offsets, n_scans, &rules);
   if (rc != NDT2D_OK) return rc;
   const RefineOut out = {poses_out, scores_out, start_scores_out, gradients_out, hessians_out, status_out, evals_out};
   fill_no_overlap(jobs_xyt, n_jobs, out);
@@ -596,15 +470,15 @@ int ndt2d_matcher_refine_scans(ndt2d_matcher * m, const double * jobs_xyt, const
   {
     return mfail(m, NDT2D_ERR_INTERNAL, std::string("refine_scans: ") + ndt2d_refine_last_error(m->refine));
   }
-  RefineBatch batch;
-  collect_refine_batch(m->laser_max_beams, jobs_xyt, job_scan, n_jobs, points_xy, point_offsets, n_scans, batch);
-  const size_t n_batch = batch.job.size();
-  if (n_batch == 0) return NDT2D_OK;
-  m->refine_records.assign(n_batch * NDT2D_REFINE_RECORD_DOUBLES, 0.0);
-  rc = ndt2d_refine_run(m->refine, batch.xyt.data(), batch.scan.data(), n_batch, batch.beams.data(), batch.beam_offsets.data(),
-                        batch.beam_offsets.size() - 1, max_evals, tol_lin, tol_ang, m->refine_records.data());
+  JobBatch batch;
+  collect_job_batch(m->laser_max_beams != 0 ? m->laser_max_beams : kEveryPoint, jobs_xyt, job_scan, n_jobs, points_xy, point_offsets,
+                    n_scans, batch);
+  if (batch.size() == 0) return NDT2D_OK;
+  m->refine_records.assign(batch.size() * NDT2D_REFINE_RECORD_DOUBLES, 0.0);
+  rc = ndt2d_refine_run(m->refine, batch.xyt.data(), batch.scan.data(), batch.size(), batch.beams.data(), batch.beam_offsets.data(),
+                        batch.scans(), max_evals, tol_lin, tol_ang, m->refine_records.data());
   if (rc != NDT2D_OK) return mfail(m, rc, std::string("refine_scans: ") + ndt2d_refine_last_error(m->refine));
-  deal_refine_records(batch, m->refine_records.data(), out);
+  deal_refine_records(batch, m->refine_records.data(), NDT2D_REFINE_RECORD_DOUBLES, out);
   return NDT2D_OK;
   NDT2D_C_CATCH(m)
 }
@@ -652,49 +526,29 @@ int ndt2d_matcher_verify_scans(ndt2d_matcher * m, const double * jobs_xyt, const
   {
     return mfail(m, NDT2D_ERR_INVALID, "verify_scans: null input");
   }
-  // (the registration's rules are not this call's: given as ones it takes)
-  int rc = check_refine_input(m, "verify_scans", jobs_xyt, job_scan, n_jobs, points_xy, point_offsets, n_scans, 1u, 0.0, 0.0);
+  int rc = check_job_input(m, "verify_scans", jobs_xyt, job_scan, n_jobs, points_xy, point_offsets, n_scans, nullptr);
   if (rc != NDT2D_OK) return rc;
   if (!m->ndt.have()) return mfail(m, NDT2D_ERR_NO_GRID, "verify_scans: no NDT in place");
-  RefineBatch batch;
-  collect_refine_batch(max_beams, jobs_xyt, job_scan, n_jobs, points_xy, point_offsets, n_scans, batch);
-  const size_t n_batch = batch.job.size();
-  // where each job's beams start in the per-beam arrays: the batch's jobs in order, the jobs of
-  // scans without points between them with no beams
-  size_t n_beams_all = 0;
-  for (size_t j = 0; j < n_batch; ++j) n_beams_all += batch.beam_offsets[batch.scan[j] + 1] - batch.beam_offsets[batch.scan[j]];
-  const bool want_beams = beam_class_out != nullptr || beam_m2_out != nullptr || beam_cells_out != nullptr;
-  if (want_beams && beam_cap < n_beams_all)
-  {
-    return mfail(m, NDT2D_ERR_INVALID, "verify_scans: the per-beam arrays hold " + std::to_string(beam_cap) + " beams, the jobs have " +
-                                           std::to_string(n_beams_all));
-  }
-  std::memset(records_out, 0, n_jobs * NDT2D_VERIFY_RECORD_U32 * sizeof(uint32_t));
-  if (beam_offsets_out != nullptr) fill_verify_offsets(batch, n_jobs, beam_offsets_out);
-  if (n_batch == 0) return NDT2D_OK;
-  discard_ahead(m);   // a search launched ahead by scoreScan is waited out and dropped
-  if (m->verify == nullptr)
-  {
-    rc = ndt2d_verify_create(m->dev, kVerifySlots, &m->verify);
-    if (rc != NDT2D_OK) return dev_fail(m, rc, "ndt2d_verify_create");
-  }
-  if (ndt2d_verify_set_neighbourhood(m->verify, m->verify_cells) != NDT2D_OK ||
-      ndt2d_verify_set_gates(m->verify, m->verify_gate_inlier, m->verify_gate_pierce) != NDT2D_OK ||
-      ndt2d_verify_set_rays(m->verify, m->verify_rays ? 1 : 0) != NDT2D_OK)
-  {
-    return mfail(m, NDT2D_ERR_INTERNAL, std::string("verify_scans: ") + ndt2d_verify_last_error(m->verify));
-  }
-  // (the per-beam arrays are the batch's, job after job: a job without beams takes no room in them)
-  std::vector<uint32_t> records(n_batch * NDT2D_VERIFY_RECORD_U32);
-  rc = ndt2d_verify_run(m->verify, batch.xyt.data(), batch.scan.data(), n_batch, batch.beams.data(), batch.beam_offsets.data(),
-                        batch.beam_offsets.size() - 1, records.data(), beam_class_out, beam_m2_out, beam_cells_out);
-  if (rc != NDT2D_OK) return mfail(m, rc, std::string("verify_scans: ") + ndt2d_verify_last_error(m->verify));
-  for (size_t j = 0; j < n_batch; ++j)
-  {
-    std::memcpy(records_out + static_cast<size_t>(batch.job[j]) * NDT2D_VERIFY_RECORD_U32, records.data() + j * NDT2D_VERIFY_RECORD_U32,
-                NDT2D_VERIFY_RECORD_U32 * sizeof(uint32_t));
-  }
-  return NDT2D_OK;
+  JobBatch batch;
+  collect_job_batch(max_beams != 0 ? max_beams : kEveryPoint, jobs_xyt, job_scan, n_jobs, points_xy, point_offsets, n_scans, batch);
+  const VerifyOut out = {records_out, beam_offsets_out, beam_class_out, beam_m2_out, beam_cells_out, beam_cap};
+  return verify_batch(m, "verify_scans", batch, n_jobs, out, true, [&](uint32_t * records) {
+    discard_ahead(m);   // a search launched ahead by scoreScan is waited out and dropped
+    if (m->verify == nullptr)
+    {
+      const int crc = ndt2d_verify_create(m->dev, kVerifySlots, &m->verify);
+      if (crc != NDT2D_OK) return dev_fail(m, crc, "ndt2d_verify_create");
+    }
+    if (ndt2d_verify_set_neighbourhood(m->verify, m->verify_cells) != NDT2D_OK ||
+        ndt2d_verify_set_gates(m->verify, m->verify_gate_inlier, m->verify_gate_pierce) != NDT2D_OK ||
+        ndt2d_verify_set_rays(m->verify, m->verify_rays ? 1 : 0) != NDT2D_OK)
+    {
+      return mfail(m, NDT2D_ERR_INTERNAL, std::string("verify_scans: ") + ndt2d_verify_last_error(m->verify));
+    }
+    const int vrc = ndt2d_verify_run(m->verify, batch.xyt.data(), batch.scan.data(), batch.size(), batch.beams.data(),
+                                     batch.beam_offsets.data(), batch.scans(), records, beam_class_out, beam_m2_out, beam_cells_out);
+    return vrc == NDT2D_OK ? NDT2D_OK : mfail(m, vrc, std::string("verify_scans: ") + ndt2d_verify_last_error(m->verify));
+  });
   NDT2D_C_CATCH(m)
 }
 
@@ -782,44 +636,40 @@ int ndt2d_matcher_refine_candidates(ndt2d_matcher * m, const size_t * cand_offse
     return mfail(m, NDT2D_ERR_INVALID, "refine_candidates: null input");
   }
   if (n_candidates == 0 || n_candidates > (1u << 20)) return mfail(m, NDT2D_ERR_INVALID, "refine_candidates: no candidates, or too many");
-  int rc = check_refine_input(m, "refine_candidates", jobs_xyt, job_scan, n_jobs, points_xy, point_offsets, n_scans, max_evals,
-                              tol_lin, tol_ang);
+  const RefineRules rules = {max_evals, tol_lin, tol_ang};
+  int rc = check_job_input(m, "refine_candidates", jobs_xyt, job_scan, n_jobs, points_xy, point_offsets, n_scans, &rules);
   if (rc != NDT2D_OK) return rc;
   rc = check_job_candidates(m, "refine_candidates", job_candidate, n_jobs, n_candidates);
   if (rc != NDT2D_OK) return rc;
   const RefineOut out = {poses_out, scores_out, start_scores_out, gradients_out, hessians_out, status_out, evals_out};
   discard_ahead(m);   // a search launched ahead by scoreScan is waited out and dropped
-  if (m->closure == nullptr)
-  {
-    rc = ndt2d_closure_create(m->dev, m->stores[0], kClosureSlots, &m->closure);
-    if (rc != NDT2D_OK) return dev_fail(m, rc, "ndt2d_closure_create");
-  }
+  rc = ensure_closure(m);
+  if (rc != NDT2D_OK) return rc;
   if (ndt2d_closure_set_neighbourhood(m->closure, m->refine_cells) != NDT2D_OK)
   {
     return mfail(m, NDT2D_ERR_INTERNAL, std::string("refine_candidates: ") + ndt2d_closure_last_error(m->closure));
   }
-  RefineBatch batch;
-  collect_refine_batch(m->laser_max_beams, jobs_xyt, job_scan, n_jobs, points_xy, point_offsets, n_scans, batch);
-  const size_t n_batch = batch.job.size();
-  std::vector<uint32_t> batch_candidate(n_batch);
-  for (size_t j = 0; j < n_batch; ++j) batch_candidate[j] = job_candidate != nullptr ? job_candidate[batch.job[j]] : batch.job[j];
-  if (n_batch == 0)
+  JobBatch batch;
+  collect_job_batch(m->laser_max_beams != 0 ? m->laser_max_beams : kEveryPoint, jobs_xyt, job_scan, n_jobs, points_xy, point_offsets,
+                    n_scans, batch);
+  if (batch.size() == 0)
   {
     fill_no_overlap(jobs_xyt, n_jobs, out);
     return NDT2D_OK;
   }
+  const std::vector<uint32_t> batch_candidate = batch_candidates(batch, job_candidate);
   rc = ndt2d_scanstore_set_eigenvalue_form(m->stores[0], eigen_form_name(m));
-  m->refine_records.assign(n_batch * NDT2D_REFINE_RECORD_DOUBLES, 0.0);
+  m->refine_records.assign(batch.size() * NDT2D_REFINE_RECORD_DOUBLES, 0.0);
   if (rc == NDT2D_OK)
   {
     rc = ndt2d_closure_refine(m->closure, n_candidates, cand_offsets, ids, poses_xyt, m->resolution, m->range_max, batch.xyt.data(),
-                              batch.scan.data(), batch_candidate.data(), n_batch, batch.beams.data(), batch.beam_offsets.data(),
-                              batch.beam_offsets.size() - 1, max_evals, tol_lin, tol_ang, m->refine_records.data());
+                              batch.scan.data(), batch_candidate.data(), batch.size(), batch.beams.data(), batch.beam_offsets.data(),
+                              batch.scans(), max_evals, tol_lin, tol_ang, m->refine_records.data());
   }
   // (a refused call -- a candidate the closure does not take -- leaves the outputs as they were)
   if (rc != NDT2D_OK) return mfail(m, rc, std::string("refine_candidates: ") + ndt2d_closure_last_error(m->closure));
   fill_no_overlap(jobs_xyt, n_jobs, out);   // (the jobs of a scan without points keep this)
-  deal_refine_records(batch, m->refine_records.data(), out);
+  deal_refine_records(batch, m->refine_records.data(), NDT2D_REFINE_RECORD_DOUBLES, out);
   return NDT2D_OK;
   NDT2D_C_CATCH(m)
 }
@@ -844,58 +694,34 @@ int ndt2d_matcher_verify_candidates(ndt2d_matcher * m, const size_t * cand_offse
     return mfail(m, NDT2D_ERR_INVALID, "verify_candidates: null input");
   }
   if (n_candidates == 0 || n_candidates > (1u << 20)) return mfail(m, NDT2D_ERR_INVALID, "verify_candidates: no candidates, or too many");
-  // (the registration's rules are not this call's: given as ones it takes)
-  int rc = check_refine_input(m, "verify_candidates", jobs_xyt, job_scan, n_jobs, points_xy, point_offsets, n_scans, 1u, 0.0, 0.0);
+  int rc = check_job_input(m, "verify_candidates", jobs_xyt, job_scan, n_jobs, points_xy, point_offsets, n_scans, nullptr);
   if (rc != NDT2D_OK) return rc;
   rc = check_job_candidates(m, "verify_candidates", job_candidate, n_jobs, n_candidates);
   if (rc != NDT2D_OK) return rc;
-  RefineBatch batch;
-  collect_refine_batch(max_beams, jobs_xyt, job_scan, n_jobs, points_xy, point_offsets, n_scans, batch);
-  const size_t n_batch = batch.job.size();
-  size_t n_beams_all = 0;
-  for (size_t j = 0; j < n_batch; ++j) n_beams_all += batch.beam_offsets[batch.scan[j] + 1] - batch.beam_offsets[batch.scan[j]];
-  const bool want_beams = beam_class_out != nullptr || beam_m2_out != nullptr || beam_cells_out != nullptr;
-  if (want_beams && beam_cap < n_beams_all)
-  {
-    return mfail(m, NDT2D_ERR_INVALID, "verify_candidates: the per-beam arrays hold " + std::to_string(beam_cap) +
-                                           " beams, the jobs have " + std::to_string(n_beams_all));
-  }
-  std::vector<uint32_t> records(n_batch * NDT2D_VERIFY_RECORD_U32);
-  if (n_batch != 0)
-  {
+  JobBatch batch;
+  collect_job_batch(max_beams != 0 ? max_beams : kEveryPoint, jobs_xyt, job_scan, n_jobs, points_xy, point_offsets, n_scans, batch);
+  const VerifyOut out = {records_out, beam_offsets_out, beam_class_out, beam_m2_out, beam_cells_out, beam_cap};
+  // (a refused call -- a candidate the closure does not take -- leaves the outputs as they were)
+  return verify_batch(m, "verify_candidates", batch, n_jobs, out, false, [&](uint32_t * records) {
     discard_ahead(m);   // a search launched ahead by scoreScan is waited out and dropped
-    if (m->closure == nullptr)
-    {
-      rc = ndt2d_closure_create(m->dev, m->stores[0], kClosureSlots, &m->closure);
-      if (rc != NDT2D_OK) return dev_fail(m, rc, "ndt2d_closure_create");
-    }
+    int crc = ensure_closure(m);
+    if (crc != NDT2D_OK) return crc;
     if (ndt2d_closure_set_verify_neighbourhood(m->closure, m->verify_cells) != NDT2D_OK ||
         ndt2d_closure_set_verify_gates(m->closure, m->verify_gate_inlier, m->verify_gate_pierce) != NDT2D_OK ||
         ndt2d_closure_set_verify_rays(m->closure, m->verify_rays ? 1 : 0) != NDT2D_OK)
     {
       return mfail(m, NDT2D_ERR_INTERNAL, std::string("verify_candidates: ") + ndt2d_closure_last_error(m->closure));
     }
-    std::vector<uint32_t> batch_candidate(n_batch);
-    for (size_t j = 0; j < n_batch; ++j) batch_candidate[j] = job_candidate != nullptr ? job_candidate[batch.job[j]] : batch.job[j];
-    rc = ndt2d_scanstore_set_eigenvalue_form(m->stores[0], eigen_form_name(m));
-    if (rc == NDT2D_OK)
+    const std::vector<uint32_t> batch_candidate = batch_candidates(batch, job_candidate);
+    crc = ndt2d_scanstore_set_eigenvalue_form(m->stores[0], eigen_form_name(m));
+    if (crc == NDT2D_OK)
     {
-      // (the per-beam arrays are the batch's, job after job: a job without beams takes no room in them)
-      rc = ndt2d_closure_verify(m->closure, n_candidates, cand_offsets, ids, poses_xyt, m->resolution, m->range_max, batch.xyt.data(),
-                                batch.scan.data(), batch_candidate.data(), n_batch, batch.beams.data(), batch.beam_offsets.data(),
-                                batch.beam_offsets.size() - 1, records.data(), beam_class_out, beam_m2_out, beam_cells_out);
+      crc = ndt2d_closure_verify(m->closure, n_candidates, cand_offsets, ids, poses_xyt, m->resolution, m->range_max, batch.xyt.data(),
+                                 batch.scan.data(), batch_candidate.data(), batch.size(), batch.beams.data(), batch.beam_offsets.data(),
+                                 batch.scans(), records, beam_class_out, beam_m2_out, beam_cells_out);
     }
-    // (a refused call -- a candidate the closure does not take -- leaves the outputs as they were)
-    if (rc != NDT2D_OK) return mfail(m, rc, std::string("verify_candidates: ") + ndt2d_closure_last_error(m->closure));
-  }
-  std::memset(records_out, 0, n_jobs * NDT2D_VERIFY_RECORD_U32 * sizeof(uint32_t));   // (the jobs of a scan without points keep this)
-  if (beam_offsets_out != nullptr) fill_verify_offsets(batch, n_jobs, beam_offsets_out);
-  for (size_t j = 0; j < n_batch; ++j)
-  {
-    std::memcpy(records_out + static_cast<size_t>(batch.job[j]) * NDT2D_VERIFY_RECORD_U32, records.data() + j * NDT2D_VERIFY_RECORD_U32,
-                NDT2D_VERIFY_RECORD_U32 * sizeof(uint32_t));
-  }
-  return NDT2D_OK;
+    return crc == NDT2D_OK ? NDT2D_OK : mfail(m, crc, std::string("verify_candidates: ") + ndt2d_closure_last_error(m->closure));
+  });
   NDT2D_C_CATCH(m)
 }
 

@@ -7,6 +7,7 @@
 //   * ndt2d_matcher_state.h     struct ndt2d_matcher and what the matcher's units share,
 //   * ndt2d_multi.cpp           the calls dealt to all devices of a multi-device matcher,
 //   * ndt2d_batched.cpp         match_candidates / match_starts / match_scans,
+//   * ndt2d_job_batch.h         the (scan, pose) job list of the batched calls: refusals, batch, way back,
 //   * ndt2d_kld.cpp, ndt2d_synth.cpp   the host KLD resampler, the synthetic workload generator.
 // Scoring arithmetic on the HOST exists in exactly two places, both by design
 // and neither a fallback -- a matcher cannot be created without a GPU: (1) one pose of a scan

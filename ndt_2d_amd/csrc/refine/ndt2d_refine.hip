@@ -47,16 +47,9 @@ void launch_refine(bool pow2, dim3 blocks, dim3 threads, hipStream_t stream, con
   else hipLaunchKernelGGL((refine_kernel<false, CELLS, InstalledSource>), blocks, threads, 0, stream, a);
 }
 
-struct RefineCall
+struct RefineCall : refine_jobs::JobList
 {
-  const double * jobs_xyt;
-  const uint32_t * job_scan;   // NULL: job k uses scan k
-  size_t n_jobs;
-  const double * beams_xy;
-  const size_t * beam_offsets;
-  size_t n_scans;
   refine::Rules rules;
-  size_t scan_of(size_t k) const { return job_scan != nullptr ? job_scan[k] : k; }
 };
 
 // Jobs [k0, k1) of a call whose arguments have been checked.  records_out: the call's, whole.
@@ -78,10 +71,9 @@ int refine_chunk(ndt2d_refine * s, const GridDesc & grid, size_t k0, size_t k1, 
   refine_jobs::copy_sent_scans(s->sent, s->scan_first, t.beams_xy, t.beam_offsets, st + at.beams);
   for (size_t k = k0; k < k1; ++k)
   {
-    const size_t sc = t.scan_of(k);
     const double * p = t.jobs_xyt + 3 * k;
     reinterpret_cast<RefineJob *>(st + at.jobs)[k - k0] =
-      RefineJob{p[0], p[1], p[2], static_cast<uint32_t>(t.beam_offsets[sc + 1] - t.beam_offsets[sc]), 0u, s->scan_first[sc]};
+      RefineJob{p[0], p[1], p[2], static_cast<uint32_t>(t.beams_of(k)), 0u, s->scan_first[t.scan_of(k)]};
     // cos / sin of the start heading from the host libm, as everywhere in this library
     ndt2d_cos_sin(p[2], st + at.trig + 2 * (k - k0), st + at.trig + 2 * (k - k0) + 1);
   }
@@ -220,7 +212,7 @@ int ndt2d_refine_run(ndt2d_refine * r, const double * jobs_xyt, const uint32_t *
                                                                                         : ": no grid view"));
   }
   NDT2D_BATCH_HIP(r, hipSetDevice(r->device));
-  const ndt2d::RefineCall t{jobs_xyt, job_scan, n_jobs, beams_xy, beam_offsets, n_scans, {max_evals, tol_lin, tol_ang}};
+  const ndt2d::RefineCall t{{jobs_xyt, job_scan, n_jobs, beams_xy, beam_offsets, n_scans}, {max_evals, tol_lin, tol_ang}};
   // more jobs than slots: in chunks
   for (size_t k0 = 0; k0 < n_jobs; k0 += r->max_jobs)
   {

@@ -46,7 +46,6 @@
 // LDS of the search block: kStageBeams x {ox, oy} = 16 KB, reused for one record per wave.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <string>
 
 #include "ndt2d_guard.h"
@@ -64,9 +63,6 @@ namespace ndt2d
 namespace
 {
 
-constexpr size_t kMaxScanBeams = size_t(1) << 20;   // what ndt2d_set_beams takes
-constexpr uint64_t kNotSent = ~uint64_t(0);
-
 // Jobs [k0, k1) of a call whose arguments have been checked.  records_out / all_scores: the call's, whole.
 // t.one_scan (start poses: every job names scan 0) takes the same steps and switches three things:
 // the records are StartRec (24 bytes, no beam offset or count), there is no order table in the
@@ -81,22 +77,11 @@ int match_chunk(JobsEngine * s, const GridDesc & grid, size_t k0, size_t k1, con
   hipStream_t stream = static_cast<hipStream_t>(ndt2d_get_stream(s->h));
 
   // the scans this chunk's jobs name, each once, in the order the jobs first name them
-  s->scan_first.assign(t.n_scans, kNotSent);
-  s->sent.clear();
+  const size_t n_beams = refine_jobs::plan_sent_scans(
+    n_slots, [&](size_t b) { return k0 + b; }, [&](size_t k) { return t.scan_of(k); }, t.beam_offsets, t.n_scans, s->scan_first,
+    s->sent);
   s->job_beams.resize(n_slots);
-  size_t n_beams = 0;
-  for (size_t k = k0; k < k1; ++k)
-  {
-    const size_t sc = t.scan_of(k);
-    const size_t count = t.beam_offsets[sc + 1] - t.beam_offsets[sc];
-    if (s->scan_first[sc] == kNotSent)
-    {
-      s->scan_first[sc] = n_beams;
-      s->sent.push_back(static_cast<uint32_t>(sc));
-      n_beams += count;
-    }
-    s->job_beams[k - k0] = static_cast<uint32_t>(count);
-  }
+  for (size_t k = k0; k < k1; ++k) s->job_beams[k - k0] = static_cast<uint32_t>(t.beams_of(k));
   group_jobs(s->job_beams.data(), n_slots, s->groups);
   heading_rows(t.jobs_xyt, k0, k1, t.dth, t.n_th, s->row_of, s->trig, s->rows);
 
@@ -109,11 +94,7 @@ int match_chunk(JobsEngine * s, const GridDesc & grid, size_t k0, size_t k1, con
   double * st = s->h_stage;
   std::memcpy(st + at.dth, t.dth, t.n_th * sizeof(double));
   std::memcpy(st + at.dlin, t.dlin, t.n_lin * sizeof(double));
-  for (uint32_t sc : s->sent)
-  {
-    std::memcpy(st + at.beams + 2 * s->scan_first[sc], t.beams_xy + 2 * t.beam_offsets[sc],
-                2 * (t.beam_offsets[sc + 1] - t.beam_offsets[sc]) * sizeof(double));
-  }
+  refine_jobs::copy_sent_scans(s->sent, s->scan_first, t.beams_xy, t.beam_offsets, st + at.beams);
   for (size_t k = k0; k < k1; ++k)
   {
     const double x = t.jobs_xyt[3 * k], y = t.jobs_xyt[3 * k + 1];
@@ -262,39 +243,10 @@ int ndt2d_scans_match(ndt2d_scans * s, const double * jobs_xyt, const uint32_t *
   {
     return batch_fail(s, NDT2D_ERR_INVALID, "ndt2d_scans_match: bad argument (lattice)");
   }
-  if (n_jobs >= (1u << 24) || n_scans >= (1u << 24)) return batch_fail(s, NDT2D_ERR_INVALID, "ndt2d_scans_match: bad argument (n_jobs, n_scans)");
-  if (job_scan == nullptr && n_scans != n_jobs)
-  {
-    return batch_fail(s, NDT2D_ERR_INVALID, "ndt2d_scans_match: bad argument (no job_scan: job k uses scan k, n_scans must equal n_jobs)");
-  }
-  // every scan and every job is checked before anything is launched
-  for (size_t sc = 0; sc < n_scans; ++sc)
-  {
-    if (beam_offsets[sc + 1] < beam_offsets[sc])
-    {
-      return batch_fail(s, NDT2D_ERR_INVALID, "ndt2d_scans_match: scan " + std::to_string(sc) + ": beam_offsets decrease");
-    }
-    const size_t count = beam_offsets[sc + 1] - beam_offsets[sc];
-    // (what ndt2d_set_beams refuses)
-    if (count == 0 || count > ndt2d::kMaxScanBeams)
-    {
-      return batch_fail(s, NDT2D_ERR_INVALID, "ndt2d_scans_match: scan " + std::to_string(sc) + ": " + std::to_string(count) +
-                                             " beams (1 .. 2^20)");
-    }
-  }
-  for (size_t k = 0; k < n_jobs; ++k)
-  {
-    if (!std::isfinite(jobs_xyt[3 * k]) || !std::isfinite(jobs_xyt[3 * k + 1]) || !std::isfinite(jobs_xyt[3 * k + 2]))
-    {
-      return batch_fail(s, NDT2D_ERR_INVALID, "ndt2d_scans_match: job " + std::to_string(k) + ": the pose is not finite");
-    }
-    if (job_scan != nullptr && job_scan[k] >= n_scans)
-    {
-      return batch_fail(s, NDT2D_ERR_INVALID, "ndt2d_scans_match: job " + std::to_string(k) + ": scan " +
-                                             std::to_string(job_scan[k]) + " of " + std::to_string(n_scans));
-    }
-  }
-  const ndt2d::JobsCall t{jobs_xyt, job_scan, false, n_jobs, beams_xy, beam_offsets, n_scans, dth, n_th, dlin, n_lin};
+  // every scan and every job is checked before anything is launched: the shared text
+  const std::string refusal = ndt2d::refine_jobs::refusal("ndt2d_scans_match", jobs_xyt, job_scan, n_jobs, beam_offsets, n_scans);
+  if (!refusal.empty()) return batch_fail(s, NDT2D_ERR_INVALID, refusal);
+  const ndt2d::JobsCall t{{jobs_xyt, job_scan, n_jobs, beams_xy, beam_offsets, n_scans}, false, dth, n_th, dlin, n_lin};
   return ndt2d::match_jobs(s, "ndt2d_scans_match", t, records_out, all_scores);
   NDT2D_C_CATCH(s)
 }

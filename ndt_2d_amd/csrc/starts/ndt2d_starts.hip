@@ -113,7 +113,7 @@ int ndt2d_starts_match(ndt2d_starts * s, const double * starts_xyt, size_t n_sta
     }
   }
   const size_t beam_offsets[2] = {0, n_beams};
-  const ndt2d::JobsCall t{starts_xyt, nullptr, true, n_starts, beams_xy, beam_offsets, 1, dth, n_th, dlin, n_lin};
+  const ndt2d::JobsCall t{{starts_xyt, nullptr, n_starts, beams_xy, beam_offsets, 1}, true, dth, n_th, dlin, n_lin};
   return ndt2d::match_jobs(s, "ndt2d_starts_match", t, records_out, all_scores);
   NDT2D_C_CATCH(s)
 }

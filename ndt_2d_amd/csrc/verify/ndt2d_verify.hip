@@ -220,9 +220,8 @@ int ndt2d_verify_run(ndt2d_verify * v, const double * jobs_xyt, const uint32_t *
     return batch_fail(v, NDT2D_ERR_INVALID, "ndt2d_verify_run: null argument");
   }
   // every scan and every job are checked before anything is launched: what the registration
-  // refuses (its rules are not this call's: given as ones it takes)
-  const std::string refusal =
-    ndt2d::refine_jobs::refusal("ndt2d_verify_run", jobs_xyt, job_scan, n_jobs, beam_offsets, n_scans, 1u, 0.0, 0.0);
+  // refuses about them
+  const std::string refusal = ndt2d::refine_jobs::refusal("ndt2d_verify_run", jobs_xyt, job_scan, n_jobs, beam_offsets, n_scans);
   if (!refusal.empty()) return batch_fail(v, NDT2D_ERR_INVALID, refusal);
   int rc = NDT2D_OK;
   const ndt2d::GridDesc grid = ndt2d::installed_grid(v->h, &rc);
@@ -237,7 +236,7 @@ int ndt2d_verify_run(ndt2d_verify * v, const double * jobs_xyt, const uint32_t *
     return batch_fail(v, NDT2D_ERR_INVALID, "ndt2d_verify_run: a grid side above 2^24 cells (rays enabled)");
   }
   NDT2D_BATCH_HIP(v, hipSetDevice(v->device));
-  const ndt2d::VerifyCall t{jobs_xyt, job_scan,    n_jobs,         beams_xy,    beam_offsets,  n_scans,
+  const ndt2d::VerifyCall t{{jobs_xyt, job_scan, n_jobs, beams_xy, beam_offsets, n_scans},
                             records_out, beam_class_out, beam_m2_out, beam_cells_out};
   // job k's beams start at the sum of the earlier jobs' scan lengths
   v->job_first.resize(n_jobs + 1);

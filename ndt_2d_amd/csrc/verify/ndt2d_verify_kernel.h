@@ -52,6 +52,7 @@
 
 #include "ndt2d_hip.h"
 #include "batch/ndt2d_batch_search.h"
+#include "batch/ndt2d_refine_jobs.h"
 #include "verify/ndt2d_verify_ray.h"
 
 namespace ndt2d
@@ -281,20 +282,13 @@ struct VerifySettings
   }
 };
 
-struct VerifyCall
+// A verification's jobs and scans (batch/ndt2d_refine_jobs.h) and where its results go.
+struct VerifyCall : refine_jobs::JobList
 {
-  const double * jobs_xyt;
-  const uint32_t * job_scan;   // NULL: job k uses scan k
-  size_t n_jobs;
-  const double * beams_xy;
-  const size_t * beam_offsets;
-  size_t n_scans;
   uint32_t * records_out;
   uint8_t * beam_class_out;
   double * beam_m2_out;
   uint32_t * beam_cells_out;
-  size_t scan_of(size_t k) const { return job_scan != nullptr ? job_scan[k] : k; }
-  size_t beams_of(size_t k) const { return beam_offsets[scan_of(k) + 1] - beam_offsets[scan_of(k)]; }
 };
 
 // Where what comes back lies in the out pair (doubles): [records | m2 | cells | classes], the

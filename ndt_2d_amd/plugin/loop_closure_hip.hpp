@@ -34,6 +34,7 @@
 #include <string>
 #include <vector>
 
+#include "job_list.hpp"
 #include "ndt2d_hip.h"
 
 namespace ndt_2d_hip
@@ -60,10 +61,10 @@ struct LoopClosure
   std::uint32_t verify[NDT2D_VERIFY_RECORD_U32] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
 };
 
-class LoopClosureHip
+class LoopClosureHip : public MatcherCalls
 {
 public:
-  explicit LoopClosureHip(ndt2d_matcher * matcher) : m_(matcher) {}
+  explicit LoopClosureHip(ndt2d_matcher * matcher) : MatcherCalls(matcher) {}
 
   // A scan appended to the graph: its points go to the device once.  Returns false on failure.
   // The id the matcher hands out is the scan's index as long as every graph scan is stored in order.
@@ -189,7 +190,7 @@ public:
         c.refined = true;
         c.refine_status = r_status_[0];
         for (int d = 0; d < 3; ++d) c.refined_pose[d] = r_poses_[d];
-        const double n = static_cast<double>(laser_max_beams_ < n_points ? laser_max_beams_ : n_points);
+        const double n = static_cast<double>(beams_in_use(n_points, laser_max_beams_, false));
         const double * h = r_hessians_.data();
         const double sum_hessian[6] = {h[0] * n, h[1] * n, h[2] * n, h[4] * n, h[5] * n, h[8] * n};
         c.has_refined_covariance = r_evals_[0] > 0 && ndt2d_refine_covariance(sum_hessian, c.refined_covariance) == NDT2D_OK;
@@ -217,8 +218,6 @@ public:
     sizes_.clear();
     return ok(ndt2d_matcher_drop_scans(m_));
   }
-
-  const std::string & last_error() const { return error_; }
 
 private:
   // One ndt2d_matcher_refine_candidates call for the candidates of the round that passed
@@ -274,14 +273,6 @@ private:
                                               v_records_.data(), nullptr, nullptr, nullptr, nullptr, 0));
   }
 
-  bool ok(int rc)
-  {
-    if (rc == NDT2D_OK) return true;
-    error_ = std::string("ndt2d error ") + std::to_string(rc) + ": " + ndt2d_matcher_last_error(m_);
-    return false;
-  }
-
-  ndt2d_matcher * m_;
   std::vector<std::size_t> sizes_;   // point count of stored scan `id`
   std::vector<std::size_t> offsets_, ids_;
   std::vector<double> poses_, corrections_, covariances_, scores_;
@@ -298,7 +289,6 @@ private:
   std::size_t verify_max_beams_ = 0;
   std::vector<double> v_jobs_;
   std::vector<std::uint32_t> v_records_;
-  std::string error_;
 };
 
 }  // namespace ndt_2d_hip

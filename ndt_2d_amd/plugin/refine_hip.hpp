@@ -22,6 +22,7 @@
 #include <string>
 #include <vector>
 
+#include "job_list.hpp"
 #include "ndt2d_hip.h"
 
 namespace ndt_2d_hip
@@ -46,10 +47,11 @@ struct RefinedScan
   bool converged() const { return status == NDT2D_REFINE_CONVERGED; }
 };
 
-class RefineHip
+// addScan() / addJob() / add(), clear(), jobs() and scans() are JobList's (job_list.hpp).
+class RefineHip : public JobList, public MatcherCalls
 {
 public:
-  explicit RefineHip(ndt2d_matcher * matcher) : m_(matcher) { clear(); }
+  explicit RefineHip(ndt2d_matcher * matcher) : MatcherCalls(matcher) {}
 
   // ndt2d_refine_run's rules; the defaults are the library's.
   void setRules(std::uint32_t max_evals, double tol_lin, double tol_ang)
@@ -69,41 +71,6 @@ public:
     return ok(ndt2d_matcher_refine_neighbourhood(m_, &cells)) ? cells : 0u;
   }
   void setLaserMaxBeams(std::size_t laser_max_beams) { laser_max_beams_ = laser_max_beams; }
-
-  // Forget the scans and jobs collected so far.
-  void clear()
-  {
-    points_.clear();
-    offsets_.assign(1, 0);
-    jobs_.clear();
-    job_scan_.clear();
-  }
-
-  // A scan's robot-frame points; returns its index.
-  std::size_t addScan(const double * points_xy, std::size_t n_points)
-  {
-    points_.insert(points_.end(), points_xy, points_xy + 2 * n_points);
-    offsets_.push_back(points_.size() / 2);
-    return offsets_.size() - 2;
-  }
-
-  // A job: scan `scan` refined from pose_xyt.  Several jobs may name one scan: its points travel
-  // once.  Returns the job's index.
-  std::size_t addJob(std::size_t scan, const double * pose_xyt)
-  {
-    jobs_.insert(jobs_.end(), pose_xyt, pose_xyt + 3);
-    job_scan_.push_back(static_cast<std::uint32_t>(scan));
-    return job_scan_.size() - 1;
-  }
-
-  // A scan and the one job that refines it from pose_xyt.
-  std::size_t add(const double * pose_xyt, const double * points_xy, std::size_t n_points)
-  {
-    return addJob(addScan(points_xy, n_points), pose_xyt);
-  }
-
-  std::size_t jobs() const { return job_scan_.size(); }
-  std::size_t scans() const { return offsets_.size() - 1; }
 
   // One call for every job collected; refined_out in job order.  false when the device call fails
   // (last_error()).  The collected scans and jobs stay until clear().
@@ -142,8 +109,7 @@ public:
       r.evals = evals_[2 * k];
       r.steps = evals_[2 * k + 1];
       r.status = status_[k];
-      const std::size_t points = offsets_[r.scan + 1] - offsets_[r.scan];
-      r.beams = points < laser_max_beams_ ? points : laser_max_beams_;
+      r.beams = beams_in_use(points_of(r.scan), laser_max_beams_, false);
       double sum_hessian[6];
       const int upper[6] = {0, 1, 2, 4, 5, 8};   // xx, xy, xt, yy, yt, tt
       for (int d = 0; d < 6; ++d) sum_hessian[d] = r.hessian[upper[d]] * static_cast<double>(r.beams);
@@ -162,27 +128,13 @@ public:
     return ndt2d_refine_last_ms(r, kernel_ms, fetch_ms) == NDT2D_OK;
   }
 
-  const std::string & last_error() const { return error_; }
-
 private:
-  bool ok(int rc)
-  {
-    if (rc == NDT2D_OK) return true;
-    error_ = std::string("ndt2d error ") + std::to_string(rc) + ": " + ndt2d_matcher_last_error(m_);
-    return false;
-  }
-
-  ndt2d_matcher * m_;
   std::uint32_t max_evals_ = 32;
   double tol_lin_ = 1.0e-6, tol_ang_ = 1.0e-6;
   std::size_t laser_max_beams_ = 100;   // the plugin's declared default
-  std::vector<double> points_, jobs_;
-  std::vector<std::size_t> offsets_;
-  std::vector<std::uint32_t> job_scan_;
   std::vector<double> poses_, scores_, start_scores_, gradients_, hessians_;
   std::vector<std::int32_t> status_;
   std::vector<std::uint32_t> evals_;
-  std::string error_;
 };
 
 }  // namespace ndt_2d_hip

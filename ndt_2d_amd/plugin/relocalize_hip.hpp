@@ -20,6 +20,7 @@
 #include <string>
 #include <vector>
 
+#include "job_list.hpp"
 #include "ndt2d_hip.h"
 
 namespace ndt_2d_hip
@@ -36,10 +37,10 @@ struct Relocalization
   double covariance[9];      // row-major
 };
 
-class RelocalizeHip
+class RelocalizeHip : public MatcherCalls
 {
 public:
-  explicit RelocalizeHip(ndt2d_matcher * matcher) : m_(matcher) {}
+  explicit RelocalizeHip(ndt2d_matcher * matcher) : MatcherCalls(matcher) {}
 
   // Every pose under n_headings equally spaced headings, the first its own: appends
   // (x, y, theta + 2 pi j / n_headings), j = 0 .. n_headings - 1, per pose to starts_out.
@@ -109,20 +110,9 @@ public:
     return ndt2d_starts_last_ms(s, search_ms, reduce_ms) == NDT2D_OK;
   }
 
-  const std::string & last_error() const { return error_; }
-
 private:
-  bool ok(int rc)
-  {
-    if (rc == NDT2D_OK) return true;
-    error_ = std::string("ndt2d error ") + std::to_string(rc) + ": " + ndt2d_matcher_last_error(m_);
-    return false;
-  }
-
-  ndt2d_matcher * m_;
   std::vector<double> corrections_, covariances_, scores_;
   std::vector<uint64_t> best_;
-  std::string error_;
 };
 
 }  // namespace ndt_2d_hip

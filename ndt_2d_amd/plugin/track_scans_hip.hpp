@@ -18,6 +18,7 @@
 #include <string>
 #include <vector>
 
+#include "job_list.hpp"
 #include "ndt2d_hip.h"
 
 namespace ndt_2d_hip
@@ -35,45 +36,11 @@ struct TrackedScan
   double covariance[9];      // row-major
 };
 
-class TrackScansHip
+// addScan() / addJob() / add(), clear(), jobs() and scans() are JobList's (job_list.hpp).
+class TrackScansHip : public JobList, public MatcherCalls
 {
 public:
-  explicit TrackScansHip(ndt2d_matcher * matcher) : m_(matcher) { clear(); }
-
-  // Forget the scans and jobs collected so far.
-  void clear()
-  {
-    points_.clear();
-    offsets_.assign(1, 0);
-    jobs_.clear();
-    job_scan_.clear();
-  }
-
-  // A scan's robot-frame points; returns its index.
-  std::size_t addScan(const double * points_xy, std::size_t n_points)
-  {
-    points_.insert(points_.end(), points_xy, points_xy + 2 * n_points);
-    offsets_.push_back(points_.size() / 2);
-    return offsets_.size() - 2;
-  }
-
-  // A job: scan `scan` matched from pose_xyt.  Several jobs may name one scan (a heading fan per
-  // robot): its points travel once.  Returns the job's index.
-  std::size_t addJob(std::size_t scan, const double * pose_xyt)
-  {
-    jobs_.insert(jobs_.end(), pose_xyt, pose_xyt + 3);
-    job_scan_.push_back(static_cast<uint32_t>(scan));
-    return job_scan_.size() - 1;
-  }
-
-  // A scan and the one job that matches it from pose_xyt (the node's own case).
-  std::size_t add(const double * pose_xyt, const double * points_xy, std::size_t n_points)
-  {
-    return addJob(addScan(points_xy, n_points), pose_xyt);
-  }
-
-  std::size_t jobs() const { return job_scan_.size(); }
-  std::size_t scans() const { return offsets_.size() - 1; }
+  explicit TrackScansHip(ndt2d_matcher * matcher) : MatcherCalls(matcher) {}
 
   // One batched match of every job collected; tracked_out in job order.  false when the device
   // call fails (last_error()).  The collected scans and jobs stay until clear().
@@ -119,23 +86,9 @@ public:
     return ndt2d_scans_last_ms(s, search_ms, reduce_ms) == NDT2D_OK;
   }
 
-  const std::string & last_error() const { return error_; }
-
 private:
-  bool ok(int rc)
-  {
-    if (rc == NDT2D_OK) return true;
-    error_ = std::string("ndt2d error ") + std::to_string(rc) + ": " + ndt2d_matcher_last_error(m_);
-    return false;
-  }
-
-  ndt2d_matcher * m_;
-  std::vector<double> points_, jobs_;
-  std::vector<std::size_t> offsets_;
-  std::vector<uint32_t> job_scan_;
   std::vector<double> corrections_, covariances_, scores_;
   std::vector<uint64_t> best_;
-  std::string error_;
 };
 
 }  // namespace ndt_2d_hip

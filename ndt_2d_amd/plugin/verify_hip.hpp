@@ -21,6 +21,7 @@
 #include <string>
 #include <vector>
 
+#include "job_list.hpp"
 #include "ndt2d_hip.h"
 
 namespace ndt_2d_hip
@@ -45,10 +46,11 @@ struct VerifiedScan
   }
 };
 
-class VerifyHip
+// addScan() / addJob() / add(), clear(), jobs() and scans() are JobList's (job_list.hpp).
+class VerifyHip : public JobList, public MatcherCalls
 {
 public:
-  explicit VerifyHip(ndt2d_matcher * matcher) : m_(matcher) { clear(); }
+  explicit VerifyHip(ndt2d_matcher * matcher) : MatcherCalls(matcher) {}
 
   // The parameters of the next verify() on; false: refused (last_error()), the value stays.
   bool setNeighbourhood(std::uint32_t cells) { return ok(ndt2d_matcher_set_verify_neighbourhood(m_, cells)); }
@@ -58,41 +60,6 @@ public:
   // laser_max_beams for a verdict about the beams the score came from; 0: every point.
   void setMaxBeams(std::size_t max_beams) { max_beams_ = max_beams; }
   void setWantBeams(bool want) { want_beams_ = want; }
-
-  // Forget the scans and jobs collected so far.
-  void clear()
-  {
-    points_.clear();
-    offsets_.assign(1, 0);
-    jobs_.clear();
-    job_scan_.clear();
-  }
-
-  // A scan's robot-frame points; returns its index.
-  std::size_t addScan(const double * points_xy, std::size_t n_points)
-  {
-    points_.insert(points_.end(), points_xy, points_xy + 2 * n_points);
-    offsets_.push_back(points_.size() / 2);
-    return offsets_.size() - 2;
-  }
-
-  // A job: scan `scan` verified at pose_xyt.  Several jobs may name one scan: its points travel
-  // once.  Returns the job's index.
-  std::size_t addJob(std::size_t scan, const double * pose_xyt)
-  {
-    jobs_.insert(jobs_.end(), pose_xyt, pose_xyt + 3);
-    job_scan_.push_back(static_cast<std::uint32_t>(scan));
-    return job_scan_.size() - 1;
-  }
-
-  // A scan and the one job that verifies it at pose_xyt.
-  std::size_t add(const double * pose_xyt, const double * points_xy, std::size_t n_points)
-  {
-    return addJob(addScan(points_xy, n_points), pose_xyt);
-  }
-
-  std::size_t jobs() const { return job_scan_.size(); }
-  std::size_t scans() const { return offsets_.size() - 1; }
 
   // One call for every job collected; verified_out in job order.  false when the call fails
   // (last_error(); no NDT in place is such a failure).  The collected scans and jobs stay until clear().
@@ -106,8 +73,7 @@ public:
     {
       const std::size_t sc = job_scan_[k];
       if (sc >= scans()) continue;   // (the call refuses the job)
-      const std::size_t points = offsets_[sc + 1] - offsets_[sc];
-      cap += (max_beams_ == 0 || points < max_beams_) ? points : max_beams_;
+      cap += beams_in_use(points_of(sc), max_beams_, true);
     }
     records_.assign(NDT2D_VERIFY_RECORD_U32 * n_jobs, 0u);
     table_.assign(n_jobs + 1, 0);
@@ -156,27 +122,13 @@ public:
     return ndt2d_verify_last_ms(v, kernel_ms, fetch_ms) == NDT2D_OK;
   }
 
-  const std::string & last_error() const { return error_; }
-
 private:
-  bool ok(int rc)
-  {
-    if (rc == NDT2D_OK) return true;
-    error_ = std::string("ndt2d error ") + std::to_string(rc) + ": " + ndt2d_matcher_last_error(m_);
-    return false;
-  }
-
-  ndt2d_matcher * m_;
   std::size_t max_beams_ = 100;   // the plugin's declared laser_max_beams default
   bool want_beams_ = false;
-  std::vector<double> points_, jobs_;
-  std::vector<std::size_t> offsets_;
-  std::vector<std::uint32_t> job_scan_;
   std::vector<std::uint32_t> records_, cells_;
   std::vector<std::size_t> table_;
   std::vector<std::uint8_t> classes_;
   std::vector<double> m2_;
-  std::string error_;
 };
 
 }  // namespace ndt_2d_hip

@@ -409,11 +409,7 @@ class ScanMatcherNDT:
         sp = _f64(scan_pose, (3,))
         pts = _f64(points, (-1, 2))
         K = len(candidates)
-        offsets = np.zeros(K + 1, dtype=np.uint64)
-        offsets[1:] = np.cumsum([len(c) for c in candidates]) if K else []
-        flat = [entry for c in candidates for entry in c]
-        ids = np.ascontiguousarray([e[0] for e in flat], dtype=np.uint64).reshape(-1)
-        poses = _f64([e[1] for e in flat], (-1, 3)) if flat else np.zeros((0, 3))
+        offsets, ids, poses = _pack_candidates(candidates)
         out = _BatchResults(self.params, K, want_scores, best_fill=0)
         self._check(self._L.ndt2d_matcher_match_candidates(
             self._m, dptr(sp), dptr(pts), len(pts), offsets.ctypes.data_as(C.POINTER(C.c_size_t)),
@@ -480,26 +476,9 @@ class ScanMatcherNDT:
         job, the dict matchScan(jobs[k], scans[job_scan[k]]) returns: `pose` is (0, 0, 0) unless
         a lattice candidate scores below 0, covariance is None when there is no NDT.  The NDT
         stays in place."""
-        jp = _f64(jobs, (-1, 3))
-        K = len(jp)
-        arrays = [_f64(pts, (-1, 2)) for pts in scans]
-        offsets = np.zeros(len(arrays) + 1, dtype=np.uintp)
-        if arrays:
-            offsets[1:] = np.cumsum([len(a) for a in arrays])
-        pts = np.ascontiguousarray(np.concatenate(arrays) if arrays else np.zeros((0, 2)), dtype=np.float64)
-        js, js_ptr = None, None
-        if job_scan is not None:
-            js = np.ascontiguousarray(job_scan, dtype=np.int64).reshape(-1)
-            if len(js) != K:
-                raise ValueError("matchScans: job_scan must name one scan per job")
-            if np.any(js < 0) or np.any(js >= 2 ** 32):
-                raise ValueError("matchScans: job_scan must hold scan indices")
-            js = np.ascontiguousarray(js, dtype=np.uint32)
-            js_ptr = js.ctypes.data_as(C.POINTER(C.c_uint32))
-        out = _BatchResults(self.params, K, want_scores)
-        self._check(self._L.ndt2d_matcher_match_scans(
-            self._m, dptr(jp), js_ptr, K, dptr(pts), offsets.ctypes.data_as(C.POINTER(C.c_size_t)), len(arrays),
-            *out.args), "matchScans")
+        lst = _JobList("matchScans", jobs, scans, job_scan)
+        out = _BatchResults(self.params, lst.K, want_scores)
+        self._check(self._L.ndt2d_matcher_match_scans(self._m, *lst.args, *out.args), "matchScans")
         return out.dicts(has_ndt=bool(self._L.ndt2d_matcher_has_ndt(self._m)))
 
     def scans_set_timing(self, enabled):
@@ -548,11 +527,7 @@ class ScanMatcherNDT:
         self.set_refine_neighbourhood(neighbourhood)
         call = _RefineCall("refineCandidates", self.params, jobs, scans, job_scan, max_evals)
         K = len(candidates)
-        offsets = np.zeros(K + 1, dtype=np.uintp)
-        offsets[1:] = np.cumsum([len(c) for c in candidates]) if K else []
-        flat = [entry for c in candidates for entry in c]
-        ids = np.ascontiguousarray([e[0] for e in flat], dtype=np.uintp).reshape(-1)
-        poses = _f64([e[1] for e in flat], (-1, 3)) if flat else np.zeros((0, 3))
+        offsets, ids, poses = _pack_candidates(candidates)
         jc = _index_array("refineCandidates", "job_candidate", "candidate", job_candidate, call.K)
         self._check(self._L.ndt2d_matcher_refine_candidates(
             self._m, offsets.ctypes.data_as(C.POINTER(C.c_size_t)), ids.ctypes.data_as(C.POINTER(C.c_size_t)), dptr(poses), K,
@@ -618,11 +593,7 @@ class ScanMatcherNDT:
         error.  A scan without points: zeros.  A verdict, no policy."""
         self.set_verify(neighbourhood=neighbourhood, gate_inlier=gate_inlier, gate_pierce=gate_pierce, rays=rays)
         K = len(candidates)
-        offsets = np.zeros(K + 1, dtype=np.uintp)
-        offsets[1:] = np.cumsum([len(c) for c in candidates]) if K else []
-        flat = [entry for c in candidates for entry in c]
-        ids = np.ascontiguousarray([e[0] for e in flat], dtype=np.uintp).reshape(-1)
-        poses = _f64([e[1] for e in flat], (-1, 3)) if flat else np.zeros((0, 3))
+        offsets, ids, poses = _pack_candidates(candidates)
         szp = C.POINTER(C.c_size_t)
 
         def launch(job_args, out_args):
@@ -635,20 +606,14 @@ class ScanMatcherNDT:
     def _verify_call(self, who, jobs, scans, job_scan, max_beams, want_beams, launch):
         """The arrays of a verification call, the call (launch(job_args, out_args): the C entry's
         arguments from jobs_xyt to max_beams, and from records_out on) and its result dicts."""
-        jp = _f64(jobs, (-1, 3))
-        K = len(jp)
-        arrays = [_f64(pts, (-1, 2)) for pts in scans]
-        offsets = np.zeros(len(arrays) + 1, dtype=np.uintp)
-        if arrays:
-            offsets[1:] = np.cumsum([len(a) for a in arrays])
-        pts = np.ascontiguousarray(np.concatenate(arrays) if arrays else np.zeros((0, 2)), dtype=np.float64)
-        js = _index_array(who, "job_scan", "scan", job_scan, K)
+        lst = _JobList(who, jobs, scans, job_scan)
+        K, arrays = lst.K, lst.arrays
         if job_scan is None and len(arrays) != K:
             raise ValueError(who + ": without job_scan job k uses scan k: one scan per job")
         limit = int(self.params["laser_max_beams"]) if max_beams is None else int(max_beams)
         if limit < 0:
             raise ValueError(who + ": max_beams must not be negative")
-        which = js if js is not None else np.arange(K)
+        which = lst.js if lst.js is not None else np.arange(K)
         if K and len(arrays) and np.any(np.asarray(which) >= len(arrays)):
             cap = 0     # (the call refuses the job; nothing is written)
         else:
@@ -661,8 +626,7 @@ class ScanMatcherNDT:
         cells = np.zeros((cap, 2), dtype=np.uint32) if want_beams else None
         u32p, u8p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)
         self._check(launch(
-            (dptr(jp), js.ctypes.data_as(u32p) if js is not None else None, K, dptr(pts),
-             offsets.ctypes.data_as(C.POINTER(C.c_size_t)), len(arrays), limit),
+            lst.args + (limit,),
             (records.ctypes.data_as(u32p), table.ctypes.data_as(C.POINTER(C.c_size_t)),
              classes.ctypes.data_as(u8p) if want_beams else None, dptr(m2) if want_beams else None,
              cells.ctypes.data_as(u32p) if want_beams else None, cap)), who)
@@ -1063,35 +1027,61 @@ def _index_array(call, name, what, values, K):
     return np.ascontiguousarray(v, dtype=np.uint32)
 
 
-class _RefineCall:
-    """The jobs and scans of a Newton registration as the C-ABI takes them, its output arrays, and
-    the dicts they become (refineScans, refineCandidates)."""
+class _JobList:
+    """K (scan, pose) jobs over S scans as the C-ABI takes them (matchScans, refineScans,
+    verifyScans, refineCandidates, verifyCandidates): jp [K, 3], arrays (the scans), pts (their
+    points, each scan once), offsets (uintp [S + 1]), js (uint32 [K], or None: job k uses scan k).
+    args: jobs_xyt, job_scan, n_jobs, points_xy, point_offsets, n_scans."""
 
-    def __init__(self, call, params, jobs, scans, job_scan, max_evals):
+    def __init__(self, call, jobs, scans, job_scan):
         self.jp = _f64(jobs, (-1, 3))
-        self.K = K = len(self.jp)
+        self.K = len(self.jp)
         self.arrays = [_f64(pts, (-1, 2)) for pts in scans]
         self.offsets = np.zeros(len(self.arrays) + 1, dtype=np.uintp)
         if self.arrays:
             self.offsets[1:] = np.cumsum([len(a) for a in self.arrays])
         self.pts = np.ascontiguousarray(np.concatenate(self.arrays) if self.arrays else np.zeros((0, 2)), dtype=np.float64)
-        self.js = _index_array(call, "job_scan", "scan", job_scan, K)
+        self.js = _index_array(call, "job_scan", "scan", job_scan, self.K)
+        self.args = (dptr(self.jp), self.js.ctypes.data_as(C.POINTER(C.c_uint32)) if self.js is not None else None, self.K,
+                     dptr(self.pts), self.offsets.ctypes.data_as(C.POINTER(C.c_size_t)), len(self.arrays))
+
+    def scan_of(self, k):
+        return int(self.js[k]) if self.js is not None else k
+
+
+def _pack_candidates(candidates):
+    """Candidate maps, each a list of (stored scan id, pose_xyt), as the C-ABI takes them:
+    (cand_offsets uintp [K + 1], ids uintp, poses_xyt [n, 3])."""
+    offsets = np.zeros(len(candidates) + 1, dtype=np.uintp)
+    if len(candidates):
+        offsets[1:] = np.cumsum([len(c) for c in candidates])
+    flat = [entry for c in candidates for entry in c]
+    ids = np.ascontiguousarray([e[0] for e in flat], dtype=np.uintp).reshape(-1)
+    poses = _f64([e[1] for e in flat], (-1, 3)) if flat else np.zeros((0, 3))
+    return offsets, ids, poses
+
+
+class _RefineCall:
+    """The jobs and scans of a Newton registration as the C-ABI takes them, its output arrays, and
+    the dicts they become (refineScans, refineCandidates)."""
+
+    def __init__(self, call, params, jobs, scans, job_scan, max_evals):
+        self.list = _JobList(call, jobs, scans, job_scan)
+        self.K = K = self.list.K
         if not 0 <= int(max_evals) < 2 ** 32:
             raise ValueError("%s: max_evals must fit 32 bits" % call)
         self.beams_max = int(params["laser_max_beams"])
         self.poses, self.scores, self.starts = np.zeros((K, 3)), np.zeros(K), np.zeros(K)
         self.grads, self.hess = np.zeros((K, 3)), np.zeros((K, 3, 3))
         self.status, self.evals = np.zeros(K, dtype=np.int32), np.zeros((K, 2), dtype=np.uint32)
-        # jobs_xyt, job_scan, n_jobs, points_xy, point_offsets, n_scans
-        self.job_args = (dptr(self.jp), self.js.ctypes.data_as(C.POINTER(C.c_uint32)) if self.js is not None else None, K,
-                         dptr(self.pts), self.offsets.ctypes.data_as(C.POINTER(C.c_size_t)), len(self.arrays))
+        self.job_args = self.list.args
         self.out_args = (dptr(self.poses), dptr(self.scores), dptr(self.starts), dptr(self.grads), dptr(self.hess),
                          self.status.ctypes.data_as(C.POINTER(C.c_int32)), self.evals.ctypes.data_as(C.POINTER(C.c_uint32)))
 
     def dicts(self):
         out = []
         for k in range(self.K):
-            n = min(self.beams_max, len(self.arrays[int(self.js[k]) if self.js is not None else k]))
+            n = min(self.beams_max, len(self.list.arrays[self.list.scan_of(k)]))
             out.append(dict(pose=self.poses[k].copy(), score=float(self.scores[k]), start_score=float(self.starts[k]),
                             gradient=self.grads[k].copy(), hessian=self.hess[k].copy(), evals=int(self.evals[k, 0]),
                             steps=int(self.evals[k, 1]), status=int(self.status[k]),
