@@ -16,6 +16,14 @@ N = 1,000.  No speed against Ceres is claimed: it is not built here.
 object, masks and session (a row's "preconditioner" says which; "us_per_cg_slowest_job" is the kernel
 time over the CG iterations of the job that made most: a launch lasts as long as its slowest job).
 profiles/posegraph_chain_timing.json is such a run.
+
+--loss trivial,huber,cauchy runs every (N, K, preconditioner) under one loss after the other (at
+--loss-scale, on the constraints --loss-on says: "all" or "switchable", the closures), again on the
+same object, masks and session; a row's "loss" says which, and its costs are the robust ones.  The
+closures of these graphs are true ones that the start poses' drift has carried out of the loss's
+quadratic part: the robust rows make more LM iterations, not another kind of step.
+profiles/posegraph_robust_timing.json is put together from such runs ("jacobi" at N = 100, "chain"
+at N = 1,000), with the rows of the commit before the losses taken in the same session.
 """
 import argparse
 import json
@@ -88,6 +96,9 @@ def main():
     ap.add_argument("--sizes", default="100,1000,10000")
     ap.add_argument("--masks", default="1,64,256")
     ap.add_argument("--preconditioner", default="jacobi", help="\"jacobi\", \"chain\" or both with a comma: each (N, K) with one after the other")
+    ap.add_argument("--loss", default="", help="\"trivial\", \"huber\", \"cauchy\" or several with commas: each configuration under one after the other")
+    ap.add_argument("--loss-scale", type=float, default=1.0)
+    ap.add_argument("--loss-on", default="all", choices=["all", "switchable"])
     ap.add_argument("--no-restatement", action="store_true", help="leave the numpy context rows out")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "posegraph_timing.json"))
     args = ap.parse_args()
@@ -102,8 +113,11 @@ def main():
         pg.set_graph(g["poses"], begin=g["begin"], end=g["end"], transform=g["transform"], information=g["information"],
                      switchable=g["switchable"])
         pg.set_timing(True)
-        for preconditioner, K in [(p, int(v)) for v in args.masks.split(",") for p in args.preconditioner.split(",")]:
+        losses = args.loss.split(",") if args.loss else [None]   # (None: an object no loss was ever set on)
+        for preconditioner, K, loss in [(p, int(v), ls) for v in args.masks.split(",") for p in args.preconditioner.split(",") for ls in losses]:
             pg.set_preconditioner(preconditioner)
+            if loss is not None:
+                pg.set_loss(loss, args.loss_scale, args.loss_on)
             rng = np.random.default_rng(1000 * n + K)
             masks = np.ones((K, m), dtype=np.uint8)
             for k in range(1, K):
@@ -120,7 +134,7 @@ def main():
                     print("n %d masks %d call %d: %.1f s" % (n, K, call, t1 - t0), file=sys.stderr, flush=True)
             lm = [j["iterations"] for j in jobs]
             cg = [j["cg_iterations"] for j in jobs]
-            row = dict(preconditioner=pg.preconditioner(), us_per_cg_slowest_job=float(np.median(kernel)) * 1e3 / max(1, max(cg)),
+            row = dict(preconditioner=pg.preconditioner(), loss=loss or "trivial", us_per_cg_slowest_job=float(np.median(kernel)) * 1e3 / max(1, max(cg)),
                        n=n, m=m, closures=int(len(closures)), masks=K, calls=args.calls, warmup=args.warmup, kernel_ms_median=float(np.median(kernel)),
                        kernel_ms_min=float(np.min(kernel)), kernel_ms_max=float(np.max(kernel)), wall_ms_median=float(np.median(wall)),
                        lm_iterations_job0=lm[0], lm_iterations_max=int(max(lm)), cg_iterations_job0=cg[0], cg_iterations_max=int(max(cg)),

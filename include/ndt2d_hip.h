@@ -770,7 +770,42 @@ int ndt2d_closure_verify_rays(ndt2d_closure * closure, int * out);
  *              n_jobs == 0: NDT2D_OK, nothing done.  Before set_graph: NDT2D_ERR_STATE.  A negative
  *              or non-finite tolerance: NDT2D_ERR_INVALID.
  *   set_timing / last_ms   HIP events around the kernel launches and the read-back of the last
- *              (chunk of a) call, off by default. */
+ *              (chunk of a) call, off by default.
+ *
+ * Robust losses (ndt2d_robust_*: a third prefix on the same object, for the reason given at the
+ * preconditioner's).  A loss rho is applied to chosen constraints; with s_c = |r_c|^2, a scale
+ * a > 0 and b = a^2 (csrc/posegraph/ndt2d_posegraph_loss.h; Ceres's HuberLoss and CauchyLoss):
+ *     "trivial" (default)  rho = s                  rho' = 1                    rho'' = 0
+ *     "huber"    s <= b: as trivial; otherwise, q = sqrt(s):
+ *                          rho = 2 a q - b          rho' = max(DBL_MIN, a / q)  rho'' = -rho' / (2 s)
+ *     "cauchy"   u = 1 + s / b:
+ *                          rho = b log(u)           rho' = max(DBL_MIN, 1 / u)  rho'' = -rho'^2 / b
+ * A constraint the loss is not applied to has rho = s.  The cost of a job is then
+ *     F = 1/2 sum rho(s_c) over its enabled constraints,
+ * and, both losses having rho'' <= 0 (Ceres's corrector applies no second-order term there), the
+ * linearisation is plain reweighting:
+ *     g = sum rho'_c J_c^T r_c          H = sum rho'_c J_c^T J_c
+ * This g is the exact gradient of F; H is positive semidefinite because rho' > 0.  Everything the
+ * solver above is said to do it does on these: D = diag(H) of the reweighted H, the gain ratio on the
+ * robust F, the noise rule, the stop rules (|g|_inf of this g, F the robust cost), the record.
+ * "chain"'s band is the band of the reweighted H + lambda D: a constraint's off-diagonal block
+ * carries its rho'_c.  rho'_c is evaluated once per linearisation, at the accepted point, the same
+ * bits wherever it is used; a job's workspace on the device gains m doubles for it.  Under a loss
+ * cost_out, initial_cost and final_cost are the robust F, while chi2_out stays |r_c|^2: the weight
+ * of a constraint at the solution is rho'(chi2 at the end), ndt2d_robust_rho on the host (a
+ * verdict on each constraint from one solve; no policy is applied).  What a result depends on is
+ * the graph, the job's mask, the loss with its scale and selection, and the parameters; the
+ * determinism above holds.  With "trivial" the kernels are the ones without a loss, bit for bit.
+ *   ndt2d_robust_rho       rho3_out = {rho, rho', rho''} of `kind` at `scale` and s; a pure host
+ *              function.  NDT2D_ERR_INVALID: an unknown kind, a scale that is not finite and > 0
+ *              (whatever the kind), an s that is negative or not finite, a NULL rho3_out.
+ *   ndt2d_robust_set_loss / ndt2d_robust_loss   the loss of the object; kept across set_graph.
+ *              "trivial" ignores the scale (and keeps the one set before).  Anything invalid (as for
+ *              ndt2d_robust_rho): NDT2D_ERR_INVALID, the setting in place stays.  ndt2d_robust_loss
+ *              returns the kind ("" for NULL) and, if scale_out is not NULL, the scale (1 at first).
+ *   ndt2d_robust_select    robust[m] bytes: the constraints the loss applies to (non-zero: applied);
+ *              NULL: every constraint.  m must be the graph's m (NDT2D_ERR_INVALID otherwise); before
+ *              set_graph: NDT2D_ERR_STATE.  set_graph resets the selection to every constraint. */
 #define NDT2D_POSEGRAPH_RECORD_DOUBLES 6
 #define NDT2D_POSEGRAPH_CONVERGED_GRADIENT 0
 #define NDT2D_POSEGRAPH_CONVERGED_COST 1
@@ -797,6 +832,10 @@ int ndt2d_posegraph_solve(ndt2d_posegraph * posegraph, const uint8_t * enabled, 
                           double * records_out, double * chi2_out);
 int ndt2d_posegraph_set_timing(ndt2d_posegraph * posegraph, int enabled);
 int ndt2d_posegraph_last_ms(ndt2d_posegraph * posegraph, float * kernel_ms, float * fetch_ms);
+int ndt2d_robust_rho(const char * kind, double scale, double s, double * rho3_out);
+int ndt2d_robust_set_loss(ndt2d_posegraph * posegraph, const char * kind, double scale);
+const char * ndt2d_robust_loss(ndt2d_posegraph * posegraph, double * scale_out);
+int ndt2d_robust_select(ndt2d_posegraph * posegraph, const uint8_t * robust, size_t m);
 
 /* Upload the beam endpoints of one scan, robot frame, already subsampled to
  * min(laser_max_beams, points.size()) points by the caller

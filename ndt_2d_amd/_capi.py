@@ -184,6 +184,10 @@ SIGNATURES = {
     "ndt2d_posegraph_solve": (C.c_int, [_vp, C.POINTER(C.c_uint8), _sz, _u32, _d, _d, _d, _dp, _dp, _dp]),
     "ndt2d_posegraph_set_timing": (C.c_int, [_vp, C.c_int]),
     "ndt2d_posegraph_last_ms": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "ndt2d_robust_rho": (C.c_int, [C.c_char_p, _d, _d, _dp]),
+    "ndt2d_robust_set_loss": (C.c_int, [_vp, C.c_char_p, _d]),
+    "ndt2d_robust_loss": (C.c_char_p, [_vp, _dp]),
+    "ndt2d_robust_select": (C.c_int, [_vp, C.POINTER(C.c_uint8), _sz]),
     "ndt2d_set_eigenvalue_form": (C.c_int, [_vp, C.c_char_p]),
     "ndt2d_get_grid": (C.c_int, [_vp, _dp, _sz, C.POINTER(_u32), C.POINTER(_u32), _dp, _dp, _dp]),
     "ndt2d_clear_grid": (C.c_int, [_vp]),

@@ -15,11 +15,16 @@
 //       barrier, and the host is not asked between iterations.  A template on the preconditioner:
 //       kPgJacobi, each node's 3 x 3 block (the default, the code it was), or kPgChain, the
 //       block-tridiagonal band along the node order by block cyclic reduction
-//       (posegraph/ndt2d_posegraph_chain.h; pg_chain_* below), chosen per object.
+//       (posegraph/ndt2d_posegraph_chain.h; pg_chain_* below), chosen per object.  A second template
+//       argument is the loss (posegraph/ndt2d_posegraph_loss.h): kLoss = 0, none -- the code as it
+//       was, bit for bit -- or Huber or Cauchy on chosen constraints: F sums rho(chi2), and g, the
+//       blocks of H, the matrix-vector product and the chain's couplings carry rho' per constraint,
+//       taken at the accepted point by pg_linearize and kept in the job's workspace (PgLoss,
+//       pg_weights below).
 //   posegraph_evaluate_kernel  grid (job), 1,024 threads: e, r = W e and chi2 = |r|^2 of every
 //       constraint at the job's poses (thread t: constraints t, t + 1024, ...), F = 1/2 sum chi2
 //       over the enabled ones by the same reduction the solver uses -- a solve's initial_cost is
-//       evaluate's F bit for bit.
+//       evaluate's F bit for bit.  The same template argument kLoss: F then sums rho(chi2).
 //
 // Determinism.  No atomics.  A node's sums (g, its block of H, (H p)_i) are gathers over its incident
 // constraints in ascending constraint index (the host's table); a dot product is each thread's
@@ -29,7 +34,9 @@
 //
 // Bounds.  Every loop is bounded before it starts: by n, m, a node's degree, max_iterations or the
 // CG cap.  Node and constraint indices are checked by the host at upload (ndt2d_posegraph_set_graph);
-// a job's workspace is [job][kPgNodeDoubles * n] doubles, with "chain" kPgChainDoubles * n more.
+// a job's workspace is [job][kPgNodeDoubles * n] doubles, with "chain" kPgChainDoubles * n more and
+// under a loss m more in front (pg_job_doubles); the loss's two doubles and m bytes lie behind the
+// graph's arrays, which ndt2d_posegraph_set_graph sizes for them.
 //
 // LDS: 2 x 5 x 16 partials, 1,280 bytes.  Registers and scratch: DESIGN.md 3.18.
 #include <hip/hip_runtime.h>
@@ -44,6 +51,7 @@
 #include "batch/ndt2d_batch_host.h"
 #include "posegraph/ndt2d_posegraph_fn.h"
 #include "posegraph/ndt2d_posegraph_chain.h"
+#include "posegraph/ndt2d_posegraph_loss.h"
 
 namespace ndt2d
 {
@@ -99,6 +107,28 @@ struct PgRules
 struct PgScratch
 {
   double part[2][kPgSums][kPgWaves];
+};
+
+// The loss of a robust instantiation (kLoss: pg::kLossHuber, pg::kLossCauchy): its scale a with
+// b = a^2, and which constraints it applies to.  Both lie with the graph -- {a, b} behind W in the
+// graph's doubles, the selection's m bytes behind node_con in its index (ndt2d_posegraph_set_graph
+// leaves the room, pg_send_loss fills it) -- so that the kernels' arguments are the ones they had
+// and the instantiations without a loss are the code they were.  Formed from G where it is used.
+template <int kLoss>
+struct PgLoss
+{
+  double a, b;
+  const uint8_t * on;   // [m], non-zero: the loss applies
+  __device__ __forceinline__ explicit PgLoss(const PgGraph & G)
+  {
+    const double * scale = G.W + 9 * static_cast<size_t>(G.m);
+    a = scale[0];
+    b = scale[1];
+    on = reinterpret_cast<const uint8_t *>(G.node_con + 2 * static_cast<size_t>(G.m));
+  }
+  // rho(s) and rho'(s) of constraint c; a constraint the loss is not applied to has rho = s
+  __device__ __forceinline__ double rho(uint32_t c, double s) const { return on[c] != 0 ? pg::loss_rho<kLoss>(s, a, b) : s; }
+  __device__ __forceinline__ double weight(uint32_t c, double s) const { return on[c] != 0 ? pg::loss_weight<kLoss>(s, a, b) : 1.0; }
 };
 
 __device__ __forceinline__ double pg_wave_sum(double v)
@@ -199,11 +229,13 @@ __device__ __forceinline__ double pg_constraint(const PgGraph & G, uint32_t c, c
   return (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2];
 }
 
-// F = 1/2 sum of chi2 over the job's enabled constraints at xs.  (pg_cost, pg_linearize and pg_matvec
-// carry the solve kernel's template argument without using it: each instantiation of the kernel
-// then has copies of its own, called as often as before there were two, and the inliner treats the
-// "jacobi" kernel as it did -- shared between the two it left that one with 20 bytes of scratch.)
-template <int kPrec>
+// F = 1/2 sum of rho(chi2) over the job's enabled constraints at xs; without a loss rho(s) = s.
+// (pg_cost, pg_linearize and pg_matvec carry the solve kernel's template argument kPrec without
+// using it: each instantiation of the kernel then has copies of its own, called as often as before
+// there were two, and the inliner treats the "jacobi" kernel as it did -- shared between the two it
+// left that one with 20 bytes of scratch.  kLoss they use, under `if constexpr`: with kLoss = 0
+// nothing of it is compiled.)
+template <int kPrec, int kLoss>
 __device__ double pg_cost(const PgGraph & G, const uint8_t * en, const double * xs, const double * trig, PgScratch & sc, uint32_t & parity)
 {
   double acc[1] = {0.0};
@@ -211,7 +243,8 @@ __device__ double pg_cost(const PgGraph & G, const uint8_t * en, const double * 
   {
     if (en != nullptr && en[c] == 0) continue;
     double e[3], r[3];
-    acc[0] += pg_constraint(G, c, xs, trig, e, r);
+    if constexpr (kLoss == 0) acc[0] += pg_constraint(G, c, xs, trig, e, r);
+    else acc[0] += PgLoss<kLoss>(G).rho(c, pg_constraint(G, c, xs, trig, e, r));
   }
   pg_block_sum(acc, sc, parity);
   return 0.5 * acc[0];
@@ -246,9 +279,16 @@ __device__ __forceinline__ pg::Frame pg_frame(const PgWork & w, uint32_t a, uint
                    w.x + 3 * static_cast<size_t>(b));
 }
 
-// g, the diagonal blocks of H = J^T J and the active flags at x; returns |g|_inf.  A node that is
+// A robust job's rho' per constraint, m doubles in front of its node arrays.  Written by
+// pg_linearize (by the thread that meets the constraint as its begin node: one entry of node_con),
+// read behind its closing barrier by pg_matvec and pg_chain_couplings.
+__device__ __forceinline__ double * pg_weights(const PgGraph & G, const PgWork & w) { return w.x - G.m; }
+
+// g, the diagonal blocks of H = J^T J and the active flags at x; returns |g|_inf.  Under a loss
+// g = sum rho' J^T r and H = sum rho' J^T J: both ends of a constraint take rho' from their own r
+// (the same operations on the same values: the same bits), the begin end keeps it.  A node that is
 // fixed or has no enabled constraint is not active: its g and block are zero.
-template <int kPrec>
+template <int kPrec, int kLoss>
 __device__ double pg_linearize(const PgGraph & G, const uint8_t * en, const PgWork & w, PgScratch & sc, uint32_t & parity)
 {
   double gmax = 0.0;
@@ -268,6 +308,12 @@ __device__ double pg_linearize(const PgGraph & G, const uint8_t * en, const PgWo
       double e[3], r[3], v[3], y[3], E[9];
       pg::error(f, w.x[3 * static_cast<size_t>(a) + 2], w.x[3 * static_cast<size_t>(b) + 2], G.transform + 3 * static_cast<size_t>(c), e);
       pg::mul(W, e, r);
+      [[maybe_unused]] double rw = 1.0;
+      if constexpr (kLoss != 0)
+      {
+        rw = PgLoss<kLoss>(G).weight(c, (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]);   // (chi2 as pg_constraint forms it)
+        if ((entry & 1u) == 0u) pg_weights(G, w)[c] = rw;
+      }
       pg::mul_t(W, r, v);
       if (entry & 1u)
       {
@@ -279,10 +325,23 @@ __device__ double pg_linearize(const PgGraph & G, const uint8_t * en, const PgWo
         pg::apply_at(f, v, y);
         pg::jacobian_a(f, E);
       }
-      gi[0] += y[0];
-      gi[1] += y[1];
-      gi[2] += y[2];
-      pg::add_jtj(W, E, S);
+      if constexpr (kLoss == 0)
+      {
+        gi[0] += y[0];
+        gi[1] += y[1];
+        gi[2] += y[2];
+        pg::add_jtj(W, E, S);
+      }
+      else
+      {
+        double T[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        pg::add_jtj(W, E, T);
+        gi[0] += rw * y[0];
+        gi[1] += rw * y[1];
+        gi[2] += rw * y[2];
+#pragma unroll
+        for (int j = 0; j < 6; ++j) S[j] += rw * T[j];
+      }
     }
     const bool active = count != 0u && i != G.fixed;
     const size_t at = static_cast<size_t>(i);
@@ -299,7 +358,7 @@ __device__ double pg_linearize(const PgGraph & G, const uint8_t * en, const PgWo
 __device__ __forceinline__ double pg_clamp_diag(double v) { return fmin(fmax(v, kPgDiagMin), kPgDiagMax); }
 
 // hp_i = ((H + lambda D) p)_i of the thread's nodes; returns the thread's share of p . hp.
-template <int kPrec>
+template <int kPrec, int kLoss>
 __device__ double pg_matvec(const PgGraph & G, const uint8_t * en, const PgWork & w, double lambda)
 {
   double php = 0.0;
@@ -327,9 +386,19 @@ __device__ double pg_matvec(const PgGraph & G, const uint8_t * en, const PgWork 
         pg::mul_t(W, u, t);
         if (entry & 1u) pg::apply_bt(f, t, y);
         else pg::apply_at(f, t, y);
-        acc[0] += y[0];
-        acc[1] += y[1];
-        acc[2] += y[2];
+        if constexpr (kLoss == 0)
+        {
+          acc[0] += y[0];
+          acc[1] += y[1];
+          acc[2] += y[2];
+        }
+        else
+        {
+          const double rw = pg_weights(G, w)[c];
+          acc[0] += rw * y[0];
+          acc[1] += rw * y[1];
+          acc[2] += rw * y[2];
+        }
       }
       const double * S = w.hd + 6 * at;
       const double * pi = w.p + 3 * at;
@@ -385,7 +454,9 @@ struct PgChainWork
 
 // H's blocks (i, i + 1) at x: each node over its own incident constraints, the enabled ones that
 // join it and node i + 1 (either way round, duplicates too) in ascending constraint index, of
-// (W E_i)^T (W E_{i+1}).  Zero where either node is not active.  Behind pg_linearize (act).
+// (W E_i)^T (W E_{i+1}), under a loss each weighted by the constraint's rho': the band of the
+// reweighted H.  Zero where either node is not active.  Behind pg_linearize (act, rho').
+template <int kLoss>
 __device__ void pg_chain_couplings(const PgGraph & G, const uint8_t * en, const PgWork & w, const PgChainWork & ch)
 {
   for (uint32_t i = pg_tid(); i < G.n; i += kPgThreads)
@@ -418,7 +489,11 @@ __device__ void pg_chain_couplings(const PgGraph & G, const uint8_t * en, const 
         pg::chain::mm(W, En, Jn);
         pg::chain::mtm(Ji, Jn, X);
 #pragma unroll
-        for (int j = 0; j < 9; ++j) S[j] += X[j];
+        for (int j = 0; j < 9; ++j)
+        {
+          if constexpr (kLoss == 0) S[j] += X[j];
+          else S[j] += pg_weights(G, w)[c] * X[j];
+        }
       }
     }
 #pragma unroll
@@ -504,7 +579,7 @@ __device__ double pg_chain_rz(const PgGraph & G, const PgWork & w)
   return rz;
 }
 
-template <int kPrec>
+template <int kPrec, int kLoss>
 __global__ void __launch_bounds__(kPgThreads) posegraph_solve_kernel(const PgGraph G, const uint8_t * enabled, double * workspace,
                                                                       const PgRules rules, double * poses_out, double * records)
 {
@@ -514,8 +589,10 @@ __global__ void __launch_bounds__(kPgThreads) posegraph_solve_kernel(const PgGra
   const size_t job = blockIdx.x, n = G.n;
   const uint8_t * en = enabled != nullptr ? enabled + job * G.m : nullptr;
   constexpr size_t per_node = kPrec == kPgChain ? kPgNodeDoubles + kPgChainDoubles : kPgNodeDoubles;
-  const PgWork w(workspace + job * per_node * n, n);
-  const PgChainWork ch = kPrec == kPgChain ? PgChainWork(workspace + job * per_node * n + kPgNodeDoubles * n, n) : PgChainWork();
+  // (a robust job: rho' of its m constraints, then the node arrays)
+  double * const base = kLoss == 0 ? workspace + job * per_node * n : workspace + job * (per_node * n + G.m) + G.m;
+  const PgWork w(base, n);
+  const PgChainWork ch = kPrec == kPgChain ? PgChainWork(base + kPgNodeDoubles * n, n) : PgChainWork();
   bool chain = false;   // whether this LM iteration's CG applies the chain's factors (uniform)
 
   for (uint32_t i = pg_tid(); i < G.n; i += kPgThreads)
@@ -527,7 +604,7 @@ __global__ void __launch_bounds__(kPgThreads) posegraph_solve_kernel(const PgGra
   pg_trig(w.x, w.cs, G.n);
   __syncthreads();
 
-  double F = pg_cost<kPrec>(G, en, w.x, w.cs, sc, parity);
+  double F = pg_cost<kPrec, kLoss>(G, en, w.x, w.cs, sc, parity);
   const double F0 = F;
   double gmax = 0.0;
   uint32_t status = NDT2D_POSEGRAPH_MAX_ITERATIONS, iterations = 0, cg_total = 0;
@@ -538,8 +615,8 @@ __global__ void __launch_bounds__(kPgThreads) posegraph_solve_kernel(const PgGra
   }
   else
   {
-    gmax = pg_linearize<kPrec>(G, en, w, sc, parity);
-    if constexpr (kPrec == kPgChain) pg_chain_couplings(G, en, w, ch);
+    gmax = pg_linearize<kPrec, kLoss>(G, en, w, sc, parity);
+    if constexpr (kPrec == kPgChain) pg_chain_couplings<kLoss>(G, en, w, ch);
     if (gmax <= rules.gradient_tolerance) status = NDT2D_POSEGRAPH_CONVERGED_GRADIENT;
   }
   double lambda = kPgLambda0, nu = 2.0, g_start = -1.0;
@@ -603,7 +680,7 @@ __global__ void __launch_bounds__(kPgThreads) posegraph_solve_kernel(const PgGra
     const double target = fmin(0.1, sqrt(r_start / g_start)) * r_start;
     for (uint32_t k = 0; k < cg_cap; ++k)
     {
-      double s1[1] = {pg_matvec<kPrec>(G, en, w, lambda)};
+      double s1[1] = {pg_matvec<kPrec, kLoss>(G, en, w, lambda)};
       pg_block_sum(s1, sc, parity);
       if (!(s1[0] > 0.0) || !(rz > 0.0)) break;   // (p = 0, or a direction rounding made useless)
       const double alpha = rz / s1[0];
@@ -689,7 +766,7 @@ __global__ void __launch_bounds__(kPgThreads) posegraph_solve_kernel(const PgGra
       status = NDT2D_POSEGRAPH_CONVERGED_STEP;
       break;
     }
-    const double Ft = pg_cost<kPrec>(G, en, w.xt, w.cst, sc, parity);
+    const double Ft = pg_cost<kPrec, kLoss>(G, en, w.xt, w.cst, sc, parity);
     const double dF = F - Ft;
     // below the rounding of the cost's own sum the gain ratio is noise: the model decides
     const bool noise = fabs(dF) <= kPgNoise * F;
@@ -705,8 +782,8 @@ __global__ void __launch_bounds__(kPgThreads) posegraph_solve_kernel(const PgGra
         w.cs[2 * at + 1] = w.cst[2 * at + 1];
       }
       __syncthreads();
-      gmax = pg_linearize<kPrec>(G, en, w, sc, parity);
-      if constexpr (kPrec == kPgChain) pg_chain_couplings(G, en, w, ch);
+      gmax = pg_linearize<kPrec, kLoss>(G, en, w, sc, parity);
+      if constexpr (kPrec == kPgChain) pg_chain_couplings<kLoss>(G, en, w, ch);
       const double t = 2.0 * gain - 1.0;
       lambda *= noise ? 1.0 / 3.0 : fmax(1.0 / 3.0, 1.0 - t * t * t);
       lambda = fmin(fmax(lambda, kPgLambdaMin), kPgLambdaMax);
@@ -743,6 +820,8 @@ __global__ void __launch_bounds__(kPgThreads) posegraph_solve_kernel(const PgGra
 }
 
 // poses: the job's at poses + job x pose_stride doubles (0: the graph's start poses for every job).
+// Under a loss the cost sums rho(chi2); chi2 itself is written as it is.
+template <int kLoss>
 __global__ void __launch_bounds__(kPgThreads) posegraph_evaluate_kernel(const PgGraph G, const uint8_t * enabled, const double * poses,
                                                                          size_t pose_stride, double * cost, double * chi2, size_t chi2_stride,
                                                                          double * residuals)
@@ -768,7 +847,11 @@ __global__ void __launch_bounds__(kPgThreads) posegraph_evaluate_kernel(const Pg
         out[3 + j] = r[j];
       }
     }
-    if (en == nullptr || en[c] != 0) acc[0] += q;
+    if (en == nullptr || en[c] != 0)
+    {
+      if constexpr (kLoss == 0) acc[0] += q;
+      else acc[0] += PgLoss<kLoss>(G).rho(c, q);
+    }
   }
   pg_block_sum(acc, sc, parity);
   if (threadIdx.x == 0 && cost != nullptr) cost[job] = 0.5 * acc[0];
@@ -786,12 +869,16 @@ struct ndt2d_posegraph : ndt2d::BatchHost
   bool information_weighting = false;   // W = L^T instead of L
   bool chain = false;                   // the CG's preconditioner: "chain" instead of "jacobi"
   bool has_graph = false, weights_sent = false;
+  int loss = ndt2d::posegraph::kLossTrivial;   // the loss (kLoss*), its scale, and whether the device has them
+  double loss_scale = 1.0;
+  bool loss_sent = false;
+  std::vector<uint8_t> robust;          // [m] the constraints the loss applies to; empty: every one
   size_t n = 0, m = 0, fixed = 0;
   std::vector<double> chol;             // [m][9] the lower Cholesky factors
   std::vector<double> stage;            // what an upload is put together in
   std::vector<uint32_t> index;
-  // on the device: [poses 3 n | transforms 3 m | W 9 m], [begin m | end m | node_ptr n + 1 | node_con 2 m],
-  // the chunk's masks, the chunk's workspaces
+  // on the device: [poses 3 n | transforms 3 m | W 9 m | the loss's a, b], [begin m | end m | node_ptr n + 1 |
+  // node_con 2 m | the loss's selection, m bytes], the chunk's masks, the chunk's workspaces
   void * d_graph = nullptr, * d_index = nullptr, * d_enabled = nullptr, * d_work = nullptr;
   size_t graph_cap = 0, index_cap = 0, enabled_cap = 0, work_cap = 0;
 };
@@ -841,6 +928,73 @@ int pg_send_weights(ndt2d_posegraph * s, hipStream_t stream)
   return NDT2D_OK;
 }
 
+// The loss's scale and selection beside the graph (PgLoss), behind a change of either; nothing
+// without a loss.
+int pg_send_loss(ndt2d_posegraph * s, hipStream_t stream)
+{
+  if (s->loss == pg::kLossTrivial || s->loss_sent) return NDT2D_OK;
+  const double scale[2] = {s->loss_scale, s->loss_scale * s->loss_scale};
+  NDT2D_BATCH_HIP(s, hipMemcpyAsync(static_cast<double *>(s->d_graph) + 3 * s->n + 12 * s->m, scale, sizeof(scale), hipMemcpyHostToDevice,
+                                    stream));
+  const std::vector<uint8_t> every(s->robust.empty() ? s->m : 0, uint8_t(1));
+  const std::vector<uint8_t> & on = s->robust.empty() ? every : s->robust;
+  if (s->m != 0)
+  {
+    NDT2D_BATCH_HIP(s, hipMemcpyAsync(static_cast<uint32_t *>(s->d_index) + s->index.size(), on.data(), s->m, hipMemcpyHostToDevice, stream));
+  }
+  NDT2D_BATCH_HIP(s, hipStreamSynchronize(stream));   // (both sources are locals)
+  s->loss_sent = true;
+  return NDT2D_OK;
+}
+
+// A job's workspace in doubles: the node arrays, the chain's where it is selected, rho' per
+// constraint under a loss.
+size_t pg_job_doubles(const ndt2d_posegraph * s)
+{
+  return (kPgNodeDoubles + (s->chain ? kPgChainDoubles : 0)) * s->n + (s->loss != pg::kLossTrivial ? s->m : 0);
+}
+
+template <int kLoss>
+void pg_launch_evaluate(hipStream_t stream, uint32_t jobs, const PgGraph & G, const uint8_t * d_en, const double * poses, size_t pose_stride,
+                        double * cost, double * chi2, size_t chi2_stride, double * residuals)
+{
+  hipLaunchKernelGGL(posegraph_evaluate_kernel<kLoss>, dim3(jobs), dim3(kPgThreads), 0, stream, G, d_en, poses, pose_stride, cost, chi2,
+                     chi2_stride, residuals);
+}
+
+// The evaluate kernel of the object's loss.
+void pg_evaluate(const ndt2d_posegraph * s, hipStream_t stream, uint32_t jobs, const PgGraph & G, const uint8_t * d_en, const double * poses,
+                 size_t pose_stride, double * cost, double * chi2, size_t chi2_stride, double * residuals)
+{
+  if (s->loss == pg::kLossHuber) pg_launch_evaluate<pg::kLossHuber>(stream, jobs, G, d_en, poses, pose_stride, cost, chi2, chi2_stride, residuals);
+  else if (s->loss == pg::kLossCauchy) pg_launch_evaluate<pg::kLossCauchy>(stream, jobs, G, d_en, poses, pose_stride, cost, chi2, chi2_stride, residuals);
+  else pg_launch_evaluate<pg::kLossTrivial>(stream, jobs, G, d_en, poses, pose_stride, cost, chi2, chi2_stride, residuals);
+}
+
+template <int kLoss>
+void pg_launch_solve(const ndt2d_posegraph * s, hipStream_t stream, uint32_t jobs, const PgGraph & G, const uint8_t * d_en, const PgRules & rules,
+                     double * poses_out, double * records)
+{
+  double * work = static_cast<double *>(s->d_work);
+  if (s->chain)
+  {
+    hipLaunchKernelGGL((posegraph_solve_kernel<kPgChain, kLoss>), dim3(jobs), dim3(kPgThreads), 0, stream, G, d_en, work, rules, poses_out, records);
+  }
+  else
+  {
+    hipLaunchKernelGGL((posegraph_solve_kernel<kPgJacobi, kLoss>), dim3(jobs), dim3(kPgThreads), 0, stream, G, d_en, work, rules, poses_out, records);
+  }
+}
+
+// The solve kernel of the object's preconditioner and loss.
+void pg_solve(const ndt2d_posegraph * s, hipStream_t stream, uint32_t jobs, const PgGraph & G, const uint8_t * d_en, const PgRules & rules,
+              double * poses_out, double * records)
+{
+  if (s->loss == pg::kLossHuber) pg_launch_solve<pg::kLossHuber>(s, stream, jobs, G, d_en, rules, poses_out, records);
+  else if (s->loss == pg::kLossCauchy) pg_launch_solve<pg::kLossCauchy>(s, stream, jobs, G, d_en, rules, poses_out, records);
+  else pg_launch_solve<pg::kLossTrivial>(s, stream, jobs, G, d_en, rules, poses_out, records);
+}
+
 // The masks of jobs [k0, k1) on the device, or NULL for none.
 int pg_send_masks(ndt2d_posegraph * s, hipStream_t stream, const uint8_t * enabled, size_t k0, size_t k1, const uint8_t ** out)
 {
@@ -851,6 +1005,18 @@ int pg_send_masks(ndt2d_posegraph * s, hipStream_t stream, const uint8_t * enabl
   NDT2D_BATCH_HIP(s, hipMemcpyAsync(s->d_enabled, enabled + k0 * s->m, bytes, hipMemcpyHostToDevice, stream));
   *out = static_cast<const uint8_t *>(s->d_enabled);
   return NDT2D_OK;
+}
+
+constexpr const char * kPgLossNames[3] = {"trivial", "huber", "cauchy"};
+
+// kLoss* of a loss's name, -1 for none.
+int pg_loss_kind(const char * kind)
+{
+  for (int k = 0; k < 3; ++k)
+  {
+    if (kind != nullptr && std::strcmp(kind, kPgLossNames[k]) == 0) return k;
+  }
+  return -1;
 }
 
 int pg_ready(ndt2d_posegraph * s, const char * who)
@@ -962,6 +1128,69 @@ const char * ndt2d_pose_graph_preconditioner(ndt2d_posegraph * s)
   return s == nullptr ? "" : s->chain ? "chain" : "jacobi";
 }
 
+// ---- robust losses (include/ndt2d_hip.h, "Robust losses") ----
+
+int ndt2d_robust_rho(const char * kind, double scale, double s, double * rho3_out)
+{
+  NDT2D_C_TRY
+  const int loss = ndt2d::pg_loss_kind(kind);
+  if (rho3_out == nullptr || loss < 0 || !(scale > 0.0) || !std::isfinite(scale) || !(s >= 0.0) || !std::isfinite(s)) return NDT2D_ERR_INVALID;
+  return ndt2d::posegraph::loss_evaluate(loss, scale, s, rho3_out) ? NDT2D_OK : NDT2D_ERR_INVALID;
+  NDT2D_C_CATCH(nullptr)
+}
+
+int ndt2d_robust_set_loss(ndt2d_posegraph * s, const char * kind, double scale)
+{
+  NDT2D_C_TRY
+  if (s == nullptr) return NDT2D_ERR_INVALID;
+  const int loss = ndt2d::pg_loss_kind(kind);
+  if (loss < 0)
+  {
+    return batch_fail(s, NDT2D_ERR_INVALID, std::string("ndt2d_robust_set_loss: \"") + (kind != nullptr ? kind : "") +
+                                              "\" (\"trivial\", \"huber\" or \"cauchy\")");
+  }
+  if (loss != ndt2d::posegraph::kLossTrivial)
+  {
+    if (!(scale > 0.0) || !std::isfinite(scale)) return batch_fail(s, NDT2D_ERR_INVALID, "ndt2d_robust_set_loss: the scale is not finite and > 0");
+    if (scale != s->loss_scale) s->loss_sent = false;
+    s->loss_scale = scale;
+  }
+  s->loss = loss;
+  return NDT2D_OK;
+  NDT2D_C_CATCH(s)
+}
+
+const char * ndt2d_robust_loss(ndt2d_posegraph * s, double * scale_out)
+{
+  if (s != nullptr && scale_out != nullptr) *scale_out = s->loss_scale;
+  return s == nullptr ? "" : ndt2d::kPgLossNames[s->loss];
+}
+
+int ndt2d_robust_select(ndt2d_posegraph * s, const uint8_t * robust, size_t m)
+{
+  NDT2D_C_TRY
+  if (s == nullptr) return NDT2D_ERR_INVALID;
+  const int rc = ndt2d::pg_ready(s, "ndt2d_robust_select");
+  if (rc != NDT2D_OK) return rc;
+  if (robust == nullptr)
+  {
+    s->robust.clear();
+  }
+  else
+  {
+    if (m != s->m)
+    {
+      return batch_fail(s, NDT2D_ERR_INVALID, "ndt2d_robust_select: " + std::to_string(m) + " bytes, the graph has " + std::to_string(s->m) +
+                                                " constraints");
+    }
+    s->robust.assign(robust, robust + m);
+    if (m == 0) s->robust.clear();
+  }
+  s->loss_sent = false;
+  return NDT2D_OK;
+  NDT2D_C_CATCH(s)
+}
+
 int ndt2d_posegraph_set_graph(ndt2d_posegraph * s, const double * poses_xyt, size_t n, const uint32_t * begin, const uint32_t * end,
                               const double * transform, const double * information, size_t m, size_t fixed)
 {
@@ -1035,8 +1264,9 @@ int ndt2d_posegraph_set_graph(ndt2d_posegraph * s, const double * poses_xyt, siz
   s->stage.resize(3 * n + 3 * m);
   std::memcpy(s->stage.data(), poses_xyt, 3 * n * sizeof(double));
   if (m != 0) std::memcpy(s->stage.data() + 3 * n, transform, 3 * m * sizeof(double));
-  NDT2D_BATCH_HIP(s, ndt2d::grow_device(&s->d_graph, &s->graph_cap, (3 * n + 12 * m) * sizeof(double)));
-  NDT2D_BATCH_HIP(s, ndt2d::grow_device(&s->d_index, &s->index_cap, s->index.size() * sizeof(uint32_t)));
+  // (with room for a loss's scale and selection: PgLoss)
+  NDT2D_BATCH_HIP(s, ndt2d::grow_device(&s->d_graph, &s->graph_cap, (3 * n + 12 * m + 2) * sizeof(double)));
+  NDT2D_BATCH_HIP(s, ndt2d::grow_device(&s->d_index, &s->index_cap, s->index.size() * sizeof(uint32_t) + m));
   NDT2D_BATCH_HIP(s, hipMemcpyAsync(s->d_graph, s->stage.data(), s->stage.size() * sizeof(double), hipMemcpyHostToDevice, stream));
   NDT2D_BATCH_HIP(s, hipMemcpyAsync(s->d_index, s->index.data(), s->index.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
   NDT2D_BATCH_HIP(s, hipStreamSynchronize(stream));
@@ -1045,6 +1275,8 @@ int ndt2d_posegraph_set_graph(ndt2d_posegraph * s, const double * poses_xyt, siz
   s->m = m;
   s->fixed = fixed;
   s->weights_sent = false;
+  s->robust.clear();
+  s->loss_sent = false;
   s->has_graph = true;
   return NDT2D_OK;
   NDT2D_C_CATCH(s)
@@ -1063,6 +1295,8 @@ int ndt2d_posegraph_evaluate(ndt2d_posegraph * s, const uint8_t * enabled, size_
   hipStream_t stream = static_cast<hipStream_t>(ndt2d_get_stream(s->h));
   rc = ndt2d::pg_send_weights(s, stream);
   if (rc != NDT2D_OK) return rc;
+  rc = ndt2d::pg_send_loss(s, stream);
+  if (rc != NDT2D_OK) return rc;
   const ndt2d::PgGraph G = ndt2d::pg_device_graph(s);
   const size_t m = s->m;
   for (size_t k0 = 0; k0 < n_jobs; k0 += s->max_jobs)
@@ -1077,9 +1311,8 @@ int ndt2d_posegraph_evaluate(ndt2d_posegraph * s, const uint8_t * enabled, size_
     NDT2D_BATCH_HIP(s, ndt2d::grow_pair(&s->h_out, &s->d_out, &s->out_cap, total));
     s->timed = false;
     if (s->timing) NDT2D_BATCH_HIP(s, hipEventRecord(s->ev[0], stream));
-    hipLaunchKernelGGL(ndt2d::posegraph_evaluate_kernel, dim3(static_cast<uint32_t>(kc)), dim3(ndt2d::kPgThreads), 0, stream, G, d_en,
-                       G.poses, size_t(0), s->d_out, chi2_out != nullptr ? s->d_out + at_chi2 : nullptr, m,
-                       residuals_out != nullptr ? s->d_out + at_res : nullptr);
+    ndt2d::pg_evaluate(s, stream, static_cast<uint32_t>(kc), G, d_en, G.poses, size_t(0), s->d_out,
+                       chi2_out != nullptr ? s->d_out + at_chi2 : nullptr, m, residuals_out != nullptr ? s->d_out + at_res : nullptr);
     NDT2D_BATCH_HIP(s, hipGetLastError());
     if (s->timing) NDT2D_BATCH_HIP(s, hipEventRecord(s->ev[1], stream));
     NDT2D_BATCH_HIP(s, hipMemcpyAsync(s->h_out, s->d_out, total * sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -1113,6 +1346,8 @@ int ndt2d_posegraph_solve(ndt2d_posegraph * s, const uint8_t * enabled, size_t n
   hipStream_t stream = static_cast<hipStream_t>(ndt2d_get_stream(s->h));
   rc = ndt2d::pg_send_weights(s, stream);
   if (rc != NDT2D_OK) return rc;
+  rc = ndt2d::pg_send_loss(s, stream);
+  if (rc != NDT2D_OK) return rc;
   const ndt2d::PgGraph G = ndt2d::pg_device_graph(s);
   const ndt2d::PgRules rules{max_iterations, gradient_tolerance, function_tolerance, parameter_tolerance};
   const size_t n = s->n, m = s->m;
@@ -1122,37 +1357,25 @@ int ndt2d_posegraph_solve(ndt2d_posegraph * s, const uint8_t * enabled, size_t n
     const uint8_t * d_en = nullptr;
     rc = ndt2d::pg_send_masks(s, stream, enabled, k0, k1, &d_en);
     if (rc != NDT2D_OK) return rc;
-    // (the chain's arrays are paid for only where it is selected)
-    const size_t per_node = ndt2d::kPgNodeDoubles + (s->chain ? ndt2d::kPgChainDoubles : 0);
-    NDT2D_BATCH_HIP(s, ndt2d::grow_device(&s->d_work, &s->work_cap, kc * per_node * n * sizeof(double)));
+    // (the chain's arrays and a loss's weights are paid for only where they are selected)
+    NDT2D_BATCH_HIP(s, ndt2d::grow_device(&s->d_work, &s->work_cap, kc * ndt2d::pg_job_doubles(s) * sizeof(double)));
     // what comes back: [poses kc n 3 | records kc 6 | chi2 kc 2 m (start, end)]
     const size_t at_rec = kc * n * 3, at_chi2 = at_rec + kc * ndt2d::kPgRec;
     const size_t total = at_chi2 + (chi2_out != nullptr ? kc * 2 * m : 0);
     NDT2D_BATCH_HIP(s, ndt2d::grow_pair(&s->h_out, &s->d_out, &s->out_cap, total));
     s->timed = false;
     if (s->timing) NDT2D_BATCH_HIP(s, hipEventRecord(s->ev[0], stream));
-    const dim3 blocks(static_cast<uint32_t>(kc)), threads(ndt2d::kPgThreads);
+    const uint32_t blocks = static_cast<uint32_t>(kc);
     if (chi2_out != nullptr)
     {
-      hipLaunchKernelGGL(ndt2d::posegraph_evaluate_kernel, blocks, threads, 0, stream, G, d_en, G.poses, size_t(0),
-                         static_cast<double *>(nullptr), s->d_out + at_chi2, 2 * m, static_cast<double *>(nullptr));
+      ndt2d::pg_evaluate(s, stream, blocks, G, d_en, G.poses, size_t(0), nullptr, s->d_out + at_chi2, 2 * m, nullptr);
       NDT2D_BATCH_HIP(s, hipGetLastError());
     }
-    if (s->chain)
-    {
-      hipLaunchKernelGGL(ndt2d::posegraph_solve_kernel<ndt2d::kPgChain>, blocks, threads, 0, stream, G, d_en, static_cast<double *>(s->d_work),
-                         rules, s->d_out, s->d_out + at_rec);
-    }
-    else
-    {
-      hipLaunchKernelGGL(ndt2d::posegraph_solve_kernel<ndt2d::kPgJacobi>, blocks, threads, 0, stream, G, d_en, static_cast<double *>(s->d_work),
-                         rules, s->d_out, s->d_out + at_rec);
-    }
+    ndt2d::pg_solve(s, stream, blocks, G, d_en, rules, s->d_out, s->d_out + at_rec);
     NDT2D_BATCH_HIP(s, hipGetLastError());
     if (chi2_out != nullptr)
     {
-      hipLaunchKernelGGL(ndt2d::posegraph_evaluate_kernel, blocks, threads, 0, stream, G, d_en, static_cast<const double *>(s->d_out), 3 * n,
-                         static_cast<double *>(nullptr), s->d_out + at_chi2 + m, 2 * m, static_cast<double *>(nullptr));
+      ndt2d::pg_evaluate(s, stream, blocks, G, d_en, s->d_out, 3 * n, nullptr, s->d_out + at_chi2 + m, 2 * m, nullptr);
       NDT2D_BATCH_HIP(s, hipGetLastError());
     }
     if (s->timing) NDT2D_BATCH_HIP(s, hipEventRecord(s->ev[1], stream));

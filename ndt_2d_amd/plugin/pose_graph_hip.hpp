@@ -63,15 +63,27 @@ public:
   // "jacobi" (the default) or "chain": the block-tridiagonal band of H + lambda D along the scans'
   // order, for the mapper's graphs (odometry between consecutive scans, a few closures).
   void setPreconditioner(const std::string & preconditioner) { preconditioner_ = preconditioner; }
+  // "trivial" (the default: the reference passes no loss function), "huber" or "cauchy" at `scale`,
+  // applied to the switchable constraints (the closures): a gross outlier among them has almost no
+  // pull on the poses.  The costs of the record are then the robust ones.
+  void setLoss(const std::string & kind, double scale)
+  {
+    loss_ = kind;
+    loss_scale_ = scale;
+  }
 
   // Plain arrays: poses_xyt[n][3] in and out, constraints as ndt2d_posegraph_set_graph takes them.
   // false: no poses, a refused graph or a failed solve (last_error()); the poses stay then.
+  // Called directly, a loss applies to every constraint (the arrays do not say which are switchable).
   bool optimize(double * poses_xyt, std::size_t n, const std::uint32_t * begin, const std::uint32_t * end, const double * transform,
                 const double * information, std::size_t m)
   {
     record_ = PoseGraphRecord();
+    std::vector<std::uint8_t> robust;
+    robust.swap(robust_);       // (what the container overload gathered, for this call only)
     if (n == 0) return false;   // `if (scans.empty()) return false;`
     if (!upload(poses_xyt, n, begin, end, transform, information, m, 1)) return false;
+    if (robust.size() == m && m != 0 && !ok(ndt2d_robust_select(pg_, robust.data(), m))) return false;
     out_.assign(3 * n, 0.0);
     double rec[NDT2D_POSEGRAPH_RECORD_DOUBLES];
     if (!ok(ndt2d_posegraph_solve(pg_, nullptr, 1, max_iterations_, gradient_tolerance_, function_tolerance_, parameter_tolerance_,
@@ -141,6 +153,8 @@ public:
     const std::size_t n = poses_.size() / 3, m = begin_.size(), jobs = 1 + switchable.size();
     if (n == 0) return false;
     if (!upload(poses_.data(), n, begin_.data(), end_.data(), transform_.data(), information_.data(), m, jobs)) return false;
+    if (m != 0 && !ok(ndt2d_robust_select(pg_, robust_.data(), m))) return false;
+    robust_.clear();
     std::vector<std::uint8_t> enabled(jobs * m, 1);
     for (std::size_t k = 0; k < switchable.size(); ++k) enabled[(1 + k) * m + switchable[k]] = 0;
     out_.assign(jobs * 3 * n, 0.0);
@@ -169,8 +183,10 @@ private:
     end_.clear();
     transform_.clear();
     information_.clear();
+    robust_.clear();
     for (const auto & constraint : constraints)
     {
+      robust_.push_back(constraint->switchable ? 1 : 0);
       begin_.push_back(static_cast<std::uint32_t>(constraint->begin));
       end_.push_back(static_cast<std::uint32_t>(constraint->end));
       for (int i = 0; i < 3; ++i) transform_.push_back(constraint->transform(i));
@@ -203,6 +219,7 @@ private:
     }
     if (!ok(ndt2d_posegraph_set_weighting(pg_, weighting_.c_str()))) return false;
     if (!ok(ndt2d_pose_graph_set_preconditioner(pg_, preconditioner_.c_str()))) return false;
+    if (!ok(ndt2d_robust_set_loss(pg_, loss_.c_str(), loss_scale_))) return false;
     return ok(ndt2d_posegraph_set_graph(pg_, poses_xyt, n, begin, end, transform, information, m, 0));
   }
 
@@ -230,9 +247,11 @@ private:
   std::size_t max_nodes_ = 0, max_constraints_ = 0, max_jobs_ = 1;
   std::uint32_t max_iterations_ = 100;
   double gradient_tolerance_ = 1e-10, function_tolerance_ = 1e-6, parameter_tolerance_ = 1e-8;
-  std::string weighting_ = "reference", preconditioner_ = "jacobi";
+  std::string weighting_ = "reference", preconditioner_ = "jacobi", loss_ = "trivial";
+  double loss_scale_ = 1.0;
   std::vector<double> poses_, transform_, information_, out_;
   std::vector<std::uint32_t> begin_, end_;
+  std::vector<std::uint8_t> robust_;   // gather's: which constraints are switchable, until the call that uses it
   PoseGraphRecord record_;
   std::string error_;
 };

@@ -69,6 +69,24 @@ def check_masks(masks, switchable):
     return en
 
 
+def robust_weights(kind, scale, chi2):
+    """rho'(chi2) of the loss `kind` at `scale`, elementwise: what ndt2d_robust_rho gives as rho',
+    bit for bit (IEEE division and square root only), without a call per value."""
+    s = np.asarray(chi2, dtype=np.float64)
+    a = float(scale)
+    b = a * a
+    tiny = np.finfo(np.float64).tiny
+    if kind == "trivial":
+        return np.ones_like(s)
+    if kind == "huber":
+        inside = s <= b
+        return np.where(inside, 1.0, np.maximum(tiny, a / np.sqrt(np.where(inside, 1.0, s))))
+    if kind == "cauchy":
+        with np.errstate(over="ignore"):   # (s / b beyond the doubles: rho' is DBL_MIN there)
+            return np.maximum(tiny, 1.0 / (1.0 + s / b))
+    raise ValueError("robust_weights: \"%s\" (\"trivial\", \"huber\" or \"cauchy\")" % kind)
+
+
 class PoseGraph:
     """ndt2d_posegraph on the matcher's device context.  The capacities grow with the graphs given
     to set_graph (the object is made anew when one is passed)."""
@@ -80,6 +98,7 @@ class PoseGraph:
         self._caps = (0, 0, 0)
         self._weighting = "reference"
         self._preconditioner = "jacobi"
+        self._loss = ("trivial", 1.0, "all")   # kind, scale, on
         self._timing = False
         self.n = self.m = 0
         self.switchable = np.zeros(0, dtype=bool)
@@ -95,6 +114,8 @@ class PoseGraph:
         self._caps = (max_nodes, max_constraints, max_jobs)
         self._check(self._L.ndt2d_posegraph_set_weighting(self._p, self._weighting.encode()), "ndt2d_posegraph_set_weighting")
         self._check(self._L.ndt2d_pose_graph_set_preconditioner(self._p, self._preconditioner.encode()), "ndt2d_pose_graph_set_preconditioner")
+        if self._loss[0] != "trivial":
+            self._check(self._L.ndt2d_robust_set_loss(self._p, self._loss[0].encode(), self._loss[1]), "ndt2d_robust_set_loss")
         if self._timing:
             self.set_timing(True)
 
@@ -133,6 +154,40 @@ class PoseGraph:
     def preconditioner(self):
         return self._L.ndt2d_pose_graph_preconditioner(self._p).decode()
 
+    def set_loss(self, kind, scale=1.0, on="all"):
+        """The loss rho of the cost F = 1/2 sum rho(chi2): "trivial" (the default, rho(s) = s),
+        "huber" or "cauchy" at `scale` (include/ndt2d_hip.h, "Robust losses").  on: the constraints
+        it applies to -- "all", "switchable" (those set_graph was told are switchable: the closures)
+        or a byte array [m] (non-zero: applied).  Kept across set_graph; "all" and "switchable" are
+        applied anew to every graph, an array to graphs of its length."""
+        kind = str(kind)
+        if not isinstance(on, str):
+            on = np.ascontiguousarray(np.asarray(on).reshape(-1) != 0, dtype=np.uint8)
+            if self.n and len(on) != self.m:
+                raise ValueError("set_loss: on has %d entries, the graph has %d constraints" % (len(on), self.m))
+        elif on not in ("all", "switchable"):
+            raise ValueError("set_loss: on = %r (\"all\", \"switchable\" or a byte array)" % (on,))
+        self._check(self._L.ndt2d_robust_set_loss(self._p, kind.encode(), float(scale)), "ndt2d_robust_set_loss")
+        self._loss = (kind, self.loss()[1], on)
+        if self.n:
+            self._select()
+
+    def loss(self):
+        """(kind, scale) as the object holds them."""
+        scale = C.c_double(0.0)
+        return self._L.ndt2d_robust_loss(self._p, C.byref(scale)).decode(), scale.value
+
+    def _select(self):
+        """The loss's selection for the graph in place."""
+        on = self._loss[2]
+        if isinstance(on, str):
+            sel = None if on == "all" else np.ascontiguousarray(self.switchable, dtype=np.uint8)
+        else:
+            if len(on) != self.m:
+                raise ValueError("set_loss: on has %d entries, the graph has %d constraints" % (len(on), self.m))
+            sel = on
+        self._check(self._L.ndt2d_robust_select(self._p, self._u8(sel), self.m), "ndt2d_robust_select")
+
     def set_graph(self, poses, constraints=None, fixed=0, begin=None, end=None, transform=None, information=None, switchable=None):
         """poses [n, 3]; the constraints as graph_io.Constraint objects, or as the arrays begin, end
         [m], transform [m, 3], information [m, 3, 3] and (optional) switchable [m]."""
@@ -160,6 +215,8 @@ class PoseGraph:
                                                       dptr(info), m, int(fixed)), "ndt2d_posegraph_set_graph")
         self.n, self.m = len(poses), m
         self.switchable = np.zeros(m, dtype=bool) if switchable is None else np.array(switchable, dtype=bool).reshape(m)
+        if self._loss[0] != "trivial" and not (isinstance(self._loss[2], str) and self._loss[2] == "all"):
+            self._select()                                            # (set_graph has reset the selection to every constraint)
 
     def _masks(self, masks):
         """(bytes [K, m] or None, K); a mask may switch off switchable constraints only."""
@@ -193,7 +250,9 @@ class PoseGraph:
         """One job per mask (None: one job, every constraint on), all in one launch.  tolerances:
         max_iterations, gradient_tolerance, function_tolerance, parameter_tolerance (Ceres's defaults;
         0 disables a rule).  Returns per job dict(poses [n, 3], status, status_name, iterations,
-        cg_iterations, initial_cost, final_cost, gradient, chi2_start [m], chi2 [m])."""
+        cg_iterations, initial_cost, final_cost, gradient, chi2_start [m], chi2 [m]).  Under a loss
+        (set_loss) the costs are the robust F, chi2 stays |r|^2, and a job's dict gains weights [m]:
+        rho'(chi2) of each constraint at the job's final poses, 1 where the loss does not apply."""
         unknown = set(tolerances) - set(DEFAULT_TOLERANCES)
         if unknown:
             raise TypeError("optimize: unknown argument(s) %s" % sorted(unknown))
@@ -205,6 +264,7 @@ class PoseGraph:
         self._check(self._L.ndt2d_posegraph_solve(self._p, self._u8(en), K, int(tol["max_iterations"]), float(tol["gradient_tolerance"]),
                                                   float(tol["function_tolerance"]), float(tol["parameter_tolerance"]), dptr(poses),
                                                   dptr(records), dptr(chi2)), "ndt2d_posegraph_solve")
+        weights = self._weights(chi2[:, 1]) if self._loss[0] != "trivial" else None
         out = []
         for k in range(K):
             status = int(records[k, 0])
@@ -212,7 +272,15 @@ class PoseGraph:
                             iterations=int(records[k, 1]), cg_iterations=int(records[k, 2]), initial_cost=float(records[k, 3]),
                             final_cost=float(records[k, 4]), gradient=float(records[k, 5]), chi2_start=chi2[k, 0].copy(),
                             chi2=chi2[k, 1].copy()))
+            if weights is not None:
+                out[-1]["weights"] = weights[k]
         return out
+
+    def _weights(self, chi2):
+        """rho'(chi2) [K, m] (ndt2d_robust_rho's, by robust_weights), 1 where the loss does not apply."""
+        kind, scale, on = self._loss
+        applies = np.ones(self.m, dtype=bool) if isinstance(on, str) and on == "all" else (self.switchable if isinstance(on, str) else on != 0)
+        return np.where(applies[None, :], robust_weights(kind, scale, chi2), 1.0)
 
     def set_timing(self, enabled):
         self._check(self._L.ndt2d_posegraph_set_timing(self._p, 1 if enabled else 0), "ndt2d_posegraph_set_timing")
