@@ -805,7 +805,69 @@ int ndt2d_closure_verify_rays(ndt2d_closure * closure, int * out);
  *              returns the kind ("" for NULL) and, if scale_out is not NULL, the scale (1 at first).
  *   ndt2d_robust_select    robust[m] bytes: the constraints the loss applies to (non-zero: applied);
  *              NULL: every constraint.  m must be the graph's m (NDT2D_ERR_INVALID otherwise); before
- *              set_graph: NDT2D_ERR_STATE.  set_graph resets the selection to every constraint. */
+ *              set_graph: NDT2D_ERR_STATE.  set_graph resets the selection to every constraint.
+ *
+ * Marginal covariances (ndt2d_marginals_*: a fourth prefix on the same object, for the same
+ * reason).  How certain the poses are: block columns of the inverse of the matrix the solver
+ * linearises, of the object's graph under a job's mask, the object's weighting and loss, at poses
+ * x -- the graph's own (poses NULL), or one [n][3] set per job, so that solve's poses_out goes
+ * straight in.
+ *     The matrix.  H = sum rho'_c J_c^T J_c over the job's enabled constraints, exactly the H above,
+ * rho' evaluated at x (1 without a loss).  F: the job's free nodes -- not the fixed one, and with at
+ * least one enabled constraint.  The result is the inverse of
+ *     H_FF + damping clamp(diag H_FF),      damping >= 0, the clamp the solver's [1e-6, 1e32].
+ * With damping = 0 this is Sigma = H_FF^-1: under "information" the Gauss-Newton covariance of the
+ * poses (H is then sum rho' J^T information J), under "reference" the inverse of the reference's own
+ * quirky H (J^T L^T L J), which is a covariance only where every L is diagonal.
+ *     The outputs.  For each job and each of Q query nodes q the block column Sigma[:, q]: n blocks
+ * of 3 x 3, row-major; the blocks of nodes not in F are zero.
+ *     blocks_out[K][Q][Q][9]   always: block (i, j) is the rows of node q_i in the column of q_j, as
+ *                              computed, not symmetrised.
+ *     columns_out[K][Q][n][9]  optional (NULL: not read back).
+ *     records_out[K][Q][NDT2D_MARGINALS_RECORD_DOUBLES] = {status, cg_iterations, |r|_2 of the
+ *                              node's columns 0, 1, 2 at the end}.
+ * Duplicate queries are legal.  A query on the fixed node or on a node with no enabled constraint
+ * gets a zero column, residuals 0 and NDT2D_MARGINALS_NOT_FREE.
+ *     The solve.  Each of the three unit vectors of a query node by preconditioned conjugate
+ * gradients from 0, with the object's preconditioner: "jacobi", or "chain" with the band factored
+ * once per job (the damping does not change; a pivot that is not positive definite leaves the job
+ * to the Jacobi blocks, as in the solver).  The three columns of a node advance in lockstep in one
+ * workgroup; cg_iterations is the iterations of the last of them to stop.  A column stops when its
+ * recurrence residual has |r|_2 <= tolerance, tested after each iteration (the right-hand side has
+ * norm 1; tolerance > 0), when p . H p <= 0 or a value is not finite (BREAKDOWN), or at
+ * max_cg_iterations (0: the solver's cap, min(3 n + 16, 8192)); it is then frozen.  The status of a
+ * query is BREAKDOWN if a column broke down, else CG_CAP if one met the cap, else CONVERGED.  A
+ * query in a component not joined to the fixed pose has no inverse at damping = 0: it is promised
+ * only "not CONVERGED", and its columns stay as the iteration left them.
+ *     Determinism.  The solver's rules: no atomics, gathers in ascending constraint index, fixed
+ * reduction trees.  A column's bits depend on the graph, the mask, the poses, the settings and its
+ * node -- not on the other queries, the other jobs, their order, the chunking or the run.
+ *     The workspace on the device is made at the first call (create's arguments are what they
+ * were) and freed by destroy: per job of a chunk a solver workspace (41 doubles a node, 83 under
+ * "chain", m more under a loss) plus one, per workgroup of a chunk 45 doubles a node, 54 under "chain".
+ * The pairs run in chunks of at most max_jobs pairs.  A pair is one workgroup with its three columns
+ * in lockstep, or, while three workgroups a pair still find a compute unit of the device each, three
+ * workgroups with one column each -- the same operations per column, the same bits.  Neither the
+ * chunking nor the form changes an output.
+ *   ndt2d_marginals_columns   NDT2D_ERR_INVALID before anything runs: a NULL object; NULL nodes,
+ *              blocks_out or records_out with Q > 0; a node index >= n (the message names it); a
+ *              non-finite pose in poses ("job k pose i"); a negative or non-finite damping; a
+ *              tolerance that is not finite and > 0.  Q == 0 or n_jobs == 0: NDT2D_OK, nothing done.
+ *              Before set_graph: NDT2D_ERR_STATE.  set_timing / last_ms cover its two launches.
+ *   ndt2d_marginals_relative  a pure host function (csrc/posegraph/ndt2d_posegraph_relative.h): the
+ *              predicted transform of b in a's frame (R_a^T (p_b - p_a), theta_b - theta_a) and its
+ *              covariance [A B] sym(joint) [A B]^T with the A and B above and joint[2][2][9] =
+ *              {aa, ab, ba, bb} (blocks_out of the call with nodes = {a, b}), sym(J) = (J + J^T) / 2.
+ *              A zero aa block means a is held.  NDT2D_ERR_INVALID: a NULL or non-finite argument.
+ *   ndt2d_marginals_distance  a pure host function: e = meas - pred, the heading through Normalize,
+ *              S = covariance_pred + covariance_meas, d2_out = e^T S^-1 e.  NDT2D_ERR_INVALID: a NULL
+ *              or non-finite argument, or S not positive definite by the Cholesky above (only its
+ *              lower triangle is read).  A verdict, no policy: no accept rule anywhere changes. */
+#define NDT2D_MARGINALS_RECORD_DOUBLES 5
+#define NDT2D_MARGINALS_CONVERGED 0
+#define NDT2D_MARGINALS_CG_CAP 1
+#define NDT2D_MARGINALS_BREAKDOWN 2
+#define NDT2D_MARGINALS_NOT_FREE 3
 #define NDT2D_POSEGRAPH_RECORD_DOUBLES 6
 #define NDT2D_POSEGRAPH_CONVERGED_GRADIENT 0
 #define NDT2D_POSEGRAPH_CONVERGED_COST 1
@@ -836,6 +898,15 @@ int ndt2d_robust_rho(const char * kind, double scale, double s, double * rho3_ou
 int ndt2d_robust_set_loss(ndt2d_posegraph * posegraph, const char * kind, double scale);
 const char * ndt2d_robust_loss(ndt2d_posegraph * posegraph, double * scale_out);
 int ndt2d_robust_select(ndt2d_posegraph * posegraph, const uint8_t * robust, size_t m);
+int ndt2d_marginals_columns(ndt2d_posegraph * posegraph, const uint8_t * enabled, size_t n_jobs,
+                            const double * poses, const uint32_t * nodes, size_t n_nodes,
+                            double damping, double tolerance, uint32_t max_cg_iterations,
+                            double * blocks_out, double * columns_out, double * records_out);
+int ndt2d_marginals_relative(const double * pose_a, const double * pose_b, const double * joint,
+                             double * transform_out, double * covariance_out);
+int ndt2d_marginals_distance(const double * transform_pred, const double * covariance_pred,
+                             const double * transform_meas, const double * covariance_meas,
+                             double * d2_out);
 
 /* Upload the beam endpoints of one scan, robot frame, already subsampled to
  * min(laser_max_beams, points.size()) points by the caller

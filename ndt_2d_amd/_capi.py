@@ -32,6 +32,10 @@ VERIFY_NO_CELL = 0xFFFFFFFF
 POSEGRAPH_CONVERGED_GRADIENT, POSEGRAPH_CONVERGED_COST, POSEGRAPH_CONVERGED_STEP, POSEGRAPH_MAX_ITERATIONS, POSEGRAPH_FAILED = range(5)
 POSEGRAPH_STATUS_NAMES = ("converged_gradient", "converged_cost", "converged_step", "max_iterations", "failed")
 POSEGRAPH_RECORD_DOUBLES = 6
+# NDT2D_MARGINALS_*: how a query of the marginal covariances ended; the doubles of its record
+MARGINALS_CONVERGED, MARGINALS_CG_CAP, MARGINALS_BREAKDOWN, MARGINALS_NOT_FREE = range(4)
+MARGINALS_STATUS_NAMES = ("converged", "cg_cap", "breakdown", "not_free")
+MARGINALS_RECORD_DOUBLES = 5
 MATCH_RECORD_DOUBLES = 12
 POSE_STATS_DOUBLES = 8
 PF_RESULT_DOUBLES = 8
@@ -188,6 +192,9 @@ SIGNATURES = {
     "ndt2d_robust_set_loss": (C.c_int, [_vp, C.c_char_p, _d]),
     "ndt2d_robust_loss": (C.c_char_p, [_vp, _dp]),
     "ndt2d_robust_select": (C.c_int, [_vp, C.POINTER(C.c_uint8), _sz]),
+    "ndt2d_marginals_columns": (C.c_int, [_vp, C.POINTER(C.c_uint8), _sz, _dp, C.POINTER(_u32), _sz, _d, _d, _u32, _dp, _dp, _dp]),
+    "ndt2d_marginals_relative": (C.c_int, [_dp, _dp, _dp, _dp, _dp]),
+    "ndt2d_marginals_distance": (C.c_int, [_dp, _dp, _dp, _dp, _dp]),
     "ndt2d_set_eigenvalue_form": (C.c_int, [_vp, C.c_char_p]),
     "ndt2d_get_grid": (C.c_int, [_vp, _dp, _sz, C.POINTER(_u32), C.POINTER(_u32), _dp, _dp, _dp]),
     "ndt2d_clear_grid": (C.c_int, [_vp]),

@@ -320,6 +320,40 @@ class Graph:
             s.pose = pose.copy()
         return True
 
+    def closure_distances(self, matcher, constraints, weighting="information", preconditioner="jacobi", **kw):
+        """For each proposed constraint the squared Mahalanobis distance of its transform (with its
+        information inverted as its covariance) from what the graph as it stands predicts for
+        (begin, end): the relative pose of the two scans with the covariance from their joint
+        marginal (PoseGraph.marginals at the scans' poses, scans[0] held; one call covers the
+        distinct end nodes).  kw: marginals' damping, tolerance and max_cg_iterations.  A verdict
+        per constraint, no policy; nothing of the graph changes.  `last_closure_distances` keeps
+        the statuses and the predictions."""
+        from .pose_graph import PoseGraph, _inverse3, closure_distance, relative_covariance
+        constraints = list(constraints)
+        self.last_closure_distances = None
+        if not constraints:
+            return []
+        poses = np.array([s.pose for s in self.scans], dtype=np.float64)
+        nodes = sorted({int(c.begin) for c in constraints} | {int(c.end) for c in constraints})
+        at = {v: i for i, v in enumerate(nodes)}
+        pg = PoseGraph(matcher, max_nodes=len(self.scans), max_constraints=max(1, len(self.constraints)), max_jobs=max(1, len(nodes)))
+        try:
+            pg.set_weighting(weighting)
+            pg.set_preconditioner(preconditioner)
+            pg.set_graph(poses, self.constraints, fixed=0)
+            got = pg.marginals(nodes, **kw)[0]
+        finally:
+            pg.close()
+        out, predictions = [], []
+        for c in constraints:
+            ia, ib = at[int(c.begin)], at[int(c.end)]
+            joint = got["blocks"][np.ix_([ia, ib], [ia, ib])]
+            t, cov = relative_covariance(poses[int(c.begin)], poses[int(c.end)], joint)
+            predictions.append((t, cov))
+            out.append(closure_distance(t, cov, c.transform, _inverse3(c.information)))
+        self.last_closure_distances = dict(nodes=nodes, status=got["status"], cg_iterations=got["cg_iterations"], predictions=predictions)
+        return out
+
     def scan_tuples(self, indices=None):
         """The scans as ScanMatcherNDT.addScans / OccupancyGrid.getMsg take them."""
         scans = self.scans if indices is None else [self.scans[i] for i in indices]

@@ -172,6 +172,74 @@ public:
     return true;
   }
 
+  // Marginal covariances of chosen scans of the graph as it stands (include/ndt2d_hip.h, "Marginal
+  // covariances"; scans[0] held, every constraint on, the loss set here on the switchable ones):
+  // blocks_out[Q][Q][9], block (i, j) the rows of nodes[i] in the column of nodes[j]; status_out[Q]
+  // NDT2D_MARGINALS_*.  false: no scans, a refused graph or call (last_error()).  The scans are not
+  // changed; damping >= 0, 0 for the inverse itself.
+  template <class Constraints, class Scans>
+  bool marginals(const Constraints & constraints, const Scans & scans, const std::vector<std::uint32_t> & nodes,
+                 std::vector<double> & blocks_out, std::vector<int> & status_out, double damping = 0.0, double tolerance = 1e-10)
+  {
+    blocks_out.clear();
+    status_out.clear();
+    poses_.clear();
+    for (const auto & scan : scans)
+    {
+      const auto pose = scan->getPose();
+      poses_.push_back(pose.x);
+      poses_.push_back(pose.y);
+      poses_.push_back(pose.theta);
+    }
+    gather(constraints);
+    const std::size_t n = poses_.size() / 3, m = begin_.size(), q = nodes.size();
+    if (n == 0) return false;
+    if (!upload(poses_.data(), n, begin_.data(), end_.data(), transform_.data(), information_.data(), m, q > 0 ? q : 1)) return false;
+    if (m != 0 && !ok(ndt2d_robust_select(pg_, robust_.data(), m))) return false;
+    robust_.clear();
+    blocks_out.assign(q * q * 9, 0.0);
+    std::vector<double> rec(q * NDT2D_MARGINALS_RECORD_DOUBLES, 0.0);
+    if (!ok(ndt2d_marginals_columns(pg_, nullptr, 1, nullptr, nodes.data(), q, damping, tolerance, 0, blocks_out.data(), nullptr, rec.data())))
+    {
+      return false;
+    }
+    for (std::size_t i = 0; i < q; ++i) status_out.push_back(static_cast<int>(rec[i * NDT2D_MARGINALS_RECORD_DOUBLES]));
+    return true;
+  }
+
+  // The predicted transform of scan b in scan a's frame with its covariance (transform_out[3],
+  // covariance_out[9] row-major): marginals() of {a, b}, then ndt2d_marginals_relative.  false
+  // also where a column did not converge (a component not joined to scans[0]).
+  template <class Constraints, class Scans>
+  bool relativeCovariance(const Constraints & constraints, const Scans & scans, std::uint32_t a, std::uint32_t b, double * transform_out,
+                          double * covariance_out, double damping = 0.0, double tolerance = 1e-10)
+  {
+    std::vector<double> joint;
+    std::vector<int> status;
+    if (!marginals(constraints, scans, std::vector<std::uint32_t>{a, b}, joint, status, damping, tolerance)) return false;
+    for (int s : status)
+    {
+      if (s != NDT2D_MARGINALS_CONVERGED && s != NDT2D_MARGINALS_NOT_FREE)
+      {
+        error_ = "ndt2d_marginals_columns: a column did not converge (status " + std::to_string(s) + ")";
+        return false;
+      }
+    }
+    return ok(ndt2d_marginals_relative(poses_.data() + 3 * a, poses_.data() + 3 * b, joint.data(), transform_out, covariance_out));
+  }
+
+  // The squared Mahalanobis distance of a proposed constraint (its transform, its information
+  // inverted by the caller into covariance_meas[9]) from the graph's prediction for (begin, end)
+  // as relativeCovariance gives it: against chi^2 with 3 degrees of freedom.  A verdict, no policy.
+  template <class Constraints, class Scans>
+  bool closureDistance(const Constraints & constraints, const Scans & scans, std::uint32_t begin, std::uint32_t end,
+                       const double * transform_meas, const double * covariance_meas, double & d2_out)
+  {
+    double t[3], cov[9];
+    if (!relativeCovariance(constraints, scans, begin, end, t, cov)) return false;
+    return ok(ndt2d_marginals_distance(t, cov, transform_meas, covariance_meas, &d2_out));
+  }
+
   const PoseGraphRecord & record() const { return record_; }   // of the last optimize()
   const std::string & last_error() const { return error_; }
 

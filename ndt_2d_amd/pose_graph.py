@@ -87,6 +87,32 @@ def robust_weights(kind, scale, chi2):
     raise ValueError("robust_weights: \"%s\" (\"trivial\", \"huber\" or \"cauchy\")" % kind)
 
 
+def relative_covariance(pose_a, pose_b, joint):
+    """ndt2d_marginals_relative: (transform [3], covariance [3, 3]) of pose b in pose a's frame from
+    the joint marginal [2, 2, 3, 3] = [[aa, ab], [ba, bb]] (marginals' blocks for nodes = [a, b])."""
+    pa = np.ascontiguousarray(pose_a, dtype=np.float64).reshape(3)
+    pb = np.ascontiguousarray(pose_b, dtype=np.float64).reshape(3)
+    j = np.ascontiguousarray(joint, dtype=np.float64).reshape(36)
+    t, cov = np.zeros(3), np.zeros((3, 3))
+    rc = _capi.lib().ndt2d_marginals_relative(dptr(pa), dptr(pb), dptr(j), dptr(t), dptr(cov))
+    if rc != _capi.OK:
+        raise Ndt2dError(rc, "ndt2d_marginals_relative", "a value is not finite")
+    return t, cov
+
+
+def closure_distance(transform_pred, covariance_pred, transform_meas, covariance_meas):
+    """ndt2d_marginals_distance: d^2 = e^T (covariance_pred + covariance_meas)^-1 e of
+    e = meas - pred, the heading through Normalize.  Ndt2dError where the sum is not positive
+    definite.  A verdict: against chi^2 with 3 degrees of freedom if both covariances are honest."""
+    args = [np.ascontiguousarray(v, dtype=np.float64).reshape(size)
+            for v, size in ((transform_pred, 3), (covariance_pred, 9), (transform_meas, 3), (covariance_meas, 9))]
+    d2 = np.zeros(1)
+    rc = _capi.lib().ndt2d_marginals_distance(dptr(args[0]), dptr(args[1]), dptr(args[2]), dptr(args[3]), dptr(d2))
+    if rc != _capi.OK:
+        raise Ndt2dError(rc, "ndt2d_marginals_distance", "a value is not finite, or the covariances' sum is not positive definite")
+    return float(d2[0])
+
+
 class PoseGraph:
     """ndt2d_posegraph on the matcher's device context.  The capacities grow with the graphs given
     to set_graph (the object is made anew when one is passed)."""
@@ -275,6 +301,51 @@ class PoseGraph:
             if weights is not None:
                 out[-1]["weights"] = weights[k]
         return out
+
+    def marginals(self, nodes, masks=None, poses=None, damping=0.0, tolerance=1e-10, max_cg_iterations=0, want_columns=False):
+        """Block columns of (H_FF + damping clamp(diag H_FF))^-1 for the query `nodes` [Q]
+        (include/ndt2d_hip.h, "Marginal covariances"): one job per mask (None: one job, every
+        constraint on), at the graph's poses or at poses [K, n, 3] (optimize's, one set per job).
+        Returns per job dict(blocks [Q, Q, 3, 3], status [Q], cg_iterations [Q], residuals [Q, 3],
+        and with want_columns columns [Q, n, 3, 3])."""
+        en, K = self._masks(masks)
+        q = np.asarray(nodes).reshape(-1)
+        for v in q:
+            if not 0 <= int(v) < 2 ** 32:
+                raise ValueError("marginals: node %d" % int(v))
+        q = np.ascontiguousarray(q, dtype=np.uint32)
+        Q = len(q)
+        if poses is not None:
+            poses = np.ascontiguousarray(poses, dtype=np.float64)
+            if poses.size != K * self.n * 3:
+                raise ValueError("marginals: poses has %d values, %d jobs of %d poses need %d" % (poses.size, K, self.n, K * self.n * 3))
+        blocks = np.zeros((K, Q, Q, 3, 3))
+        records = np.zeros((K, Q, _capi.MARGINALS_RECORD_DOUBLES))
+        columns = np.zeros((K, Q, self.n, 3, 3)) if want_columns else None
+        self._check(self._L.ndt2d_marginals_columns(self._p, self._u8(en), K, None if poses is None else dptr(poses),
+                                                    q.ctypes.data_as(C.POINTER(C.c_uint32)), Q, float(damping), float(tolerance),
+                                                    int(max_cg_iterations), dptr(blocks), None if columns is None else dptr(columns),
+                                                    dptr(records)), "ndt2d_marginals_columns")
+        out = []
+        for k in range(K):
+            d = dict(blocks=blocks[k].copy(), status=records[k, :, 0].astype(np.int64), cg_iterations=records[k, :, 1].astype(np.int64),
+                     residuals=records[k, :, 2:].copy())
+            if want_columns:
+                d["columns"] = columns[k].copy()
+            out.append(d)
+        return out
+
+    def relative_covariance(self, a, b, poses=None, mask=None, **kw):
+        """The predicted transform of node b in node a's frame and its covariance from the joint
+        marginal of the two: one marginals call with nodes = [a, b], then ndt2d_marginals_relative.
+        poses [n, 3]: where to linearise (required: the object does not read its poses back).
+        Returns dict(transform [3], covariance [3, 3], status [2], joint [2, 2, 3, 3])."""
+        if poses is None:
+            raise ValueError("relative_covariance: poses [n, 3] (the poses the graph was given, or optimize's)")
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(self.n, 3)
+        got = self.marginals([a, b], masks=None if mask is None else np.asarray(mask).reshape(1, -1), poses=poses[None], **kw)[0]
+        t, cov = relative_covariance(poses[int(a)], poses[int(b)], got["blocks"])
+        return dict(transform=t, covariance=cov, status=got["status"], joint=got["blocks"])
 
     def _weights(self, chi2):
         """rho'(chi2) [K, m] (ndt2d_robust_rho's, by robust_weights), 1 where the loss does not apply."""
