@@ -17,7 +17,7 @@ claimed: it has nothing to compare.
 
 The design's one unmeasured claim, three columns in lockstep in one workgroup against one column per
 workgroup with three times the workgroups.  The library takes one or the other by the size of a
-chunk (pg_marginals_form); --build-forms compiles the pose-graph unit twice more, with
+chunk (pg_marginals_form); --build-forms compiles the marginals unit twice more, with
 -DNDT2D_MARGINALS_LOCKSTEP and -DNDT2D_MARGINALS_ONE_COLUMN, which force a form, and links
 experiments/bin/libndt2d_hip_lockstep.so and libndt2d_hip_onecol.so from the library's other objects
 (no GPU needed); --ab LABEL runs N = 1,000, K = 1 with --ab-queries query nodes and both
@@ -29,10 +29,9 @@ record, beside the rows above:
     NDT2D_HIP_LIB=experiments/bin/libndt2d_hip_lockstep.so python experiments/posegraph_marginals_timing.py --ab lockstep --ab-queries 16,85,256,999
     NDT2D_HIP_LIB=experiments/bin/libndt2d_hip_onecol.so python experiments/posegraph_marginals_timing.py --ab one_column --ab-queries 16,85,256,999
 
-The chain's factors applied column after column (the library's) against to the live columns in one
-pass over the levels, sharing its barriers: libndt2d_hip_lockstep_together.so and
-libndt2d_hip_onecol_together.so have -DNDT2D_MARGINALS_APPLY_TOGETHER beside the form's macro; their rows
-go under "ab"["lockstep_together"] and "ab"["one_column_together"] the same way.
+The record's "ab"["lockstep_together"] and "ab"["one_column_together"] rows are of a third form, the
+chain's factors applied to the live columns in one pass over the levels: measured once, decided
+against and removed from the unit (DESIGN.md 3.18.3 names the commit that has it).
 """
 import argparse
 import json
@@ -51,21 +50,20 @@ sys.path.insert(0, os.path.join(ROOT, "experiments"))
 from posegraph_timing import loop_graph  # noqa: E402
 
 
-FORMS = {"lockstep": ["NDT2D_MARGINALS_LOCKSTEP"], "onecol": ["NDT2D_MARGINALS_ONE_COLUMN"],
-         "lockstep_together": ["NDT2D_MARGINALS_LOCKSTEP", "NDT2D_MARGINALS_APPLY_TOGETHER"], "onecol_together": ["NDT2D_MARGINALS_ONE_COLUMN", "NDT2D_MARGINALS_APPLY_TOGETHER"]}
+FORMS = {"lockstep": ["NDT2D_MARGINALS_LOCKSTEP"], "onecol": ["NDT2D_MARGINALS_ONE_COLUMN"]}
 
 
 def build_forms():
-    """The library with marginals_columns_kernel's form forced, once each way: the pose-graph unit
+    """The library with marginals_columns_kernel's form forced, once each way: the marginals unit
     compiled anew with the macro, every other object as the library's own build left it."""
     from concurrent.futures import ThreadPoolExecutor
     from ndt_2d_amd import build
     out_dir = os.path.join(ROOT, "experiments", "bin")
     os.makedirs(out_dir, exist_ok=True)
-    unit = "posegraph/ndt2d_posegraph.hip"
+    unit = "posegraph/ndt2d_posegraph_marginals.hip"
 
     def compile_form(name):
-        obj = os.path.join(out_dir, "ndt2d_posegraph_%s.o" % name)
+        obj = os.path.join(out_dir, "ndt2d_posegraph_marginals_%s.o" % name)
         subprocess.check_call([build.hipcc(), "--offload-arch=" + build.ARCH] + build.FLAGS + ["-D" + v for v in FORMS[name]] +
                               ["-I", os.path.join(ROOT, "include"), "-I", build._CSRC, "-c", os.path.join(build._CSRC, unit), "-o", obj])
         return obj

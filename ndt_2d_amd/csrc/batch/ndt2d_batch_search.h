@@ -16,6 +16,7 @@
 #ifndef NDT2D_BATCH_SEARCH_H_
 #define NDT2D_BATCH_SEARCH_H_
 
+#include "ndt2d_installed_map.h"
 #include "ndt2d_stage_layout.h"
 #include "ndt2d_walk_fn.h"
 
@@ -125,32 +126,7 @@ inline uint32_t batch_search_threads(size_t n_cand)
   return static_cast<uint32_t>(waves < kSearchMaxThreads ? waves : kSearchMaxThreads);
 }
 
-// The installed grid as the lane's walk reads it: a cell is its own record.
-struct InstalledMap
-{
-  const uint32_t * occ_bits;
-  const double * cells_global;
-  __device__ __forceinline__ bool find(uint32_t cell, uint32_t & rank) const
-  {
-    rank = cell;   // (<= ncell: bit ncell is 0)
-    return ((occ_bits[cell >> 5] >> (cell & 31u)) & 1u) != 0u;
-  }
-  __device__ __forceinline__ const double2 * record(uint32_t rank) const
-  {
-    return reinterpret_cast<const double2 *>(cells_global + static_cast<size_t>(rank) * kCellStrideGlobal);
-  }
-};
-
-// SOURCE (refine/ndt2d_refine_kernel.h, verify/ndt2d_verify_kernel.h) of the grid installed in the
-// context: one grid for all jobs, a cell is its own record.
-struct InstalledSource
-{
-  GridDesc g;   // geometry, cells_global, occ_bits
-  __device__ __forceinline__ const GridDesc & grid(uint32_t) const { return g; }
-  __device__ __forceinline__ InstalledMap map(uint32_t) const { return InstalledMap{g.occ_bits, g.cells_global}; }
-};
-
-// One job of a chunk on the installed grid.
+// One job of a chunk on the installed grid (InstalledMap: ndt2d_installed_map.h).
 struct JobRec
 {
   double x, y;

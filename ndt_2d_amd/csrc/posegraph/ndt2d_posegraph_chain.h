@@ -1,4 +1,4 @@
-// The chain preconditioner of the pose graph (posegraph/ndt2d_posegraph.hip, "chain"): a symmetric
+// The chain preconditioner of the pose graph (posegraph/ndt2d_posegraph_kernel.h, "chain"): a symmetric
 // positive definite block-tridiagonal system of n nodes with 3 x 3 blocks, factored and solved
 // exactly by block cyclic reduction without pivoting, for any n.  Plain C++ without HIP types, host
 // and device, as posegraph/ndt2d_posegraph_fn.h: the kernel runs the per-node steps below with one

@@ -1,4 +1,4 @@
-// The arithmetic of the pose graph (posegraph/ndt2d_posegraph.hip): the residual of one constraint,
+// The arithmetic of the pose graph (posegraph/ndt2d_posegraph_kernel.h): the residual of one constraint,
 // its analytic Jacobians, the products the matrix-free solver needs, the 3 x 3 symmetric inverse of
 // the block-Jacobi preconditioner and the host's Cholesky of an information matrix -- the contract
 // of include/ndt2d_hip.h ("Pose graph").  Plain C++ without HIP types, host and device: every

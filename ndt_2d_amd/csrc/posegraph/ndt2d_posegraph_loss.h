@@ -1,4 +1,4 @@
-// The robust losses of the pose graph (posegraph/ndt2d_posegraph.hip): rho(s), rho'(s) and rho''(s)
+// The robust losses of the pose graph (posegraph/ndt2d_posegraph_kernel.h): rho(s), rho'(s) and rho''(s)
 // of s = |r|^2 >= 0 at a scale a > 0, b = a^2 -- the contract of include/ndt2d_hip.h ("Pose graph",
 // robust losses).  Plain C++ without HIP types, host and device, as posegraph/ndt2d_posegraph_fn.h:
 // the kernels' threads run it, ndt2d_robust_rho hands it out on the host, and a stand-alone host

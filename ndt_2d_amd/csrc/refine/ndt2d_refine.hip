@@ -10,7 +10,7 @@
 //
 // The kernel, its job record and its arguments are refine/ndt2d_refine_kernel.h (the loop closure
 // instantiates the same text on its candidate slots); here: the object, the chunk on the installed
-// grid -- InstalledSource, batch/ndt2d_batch_search.h -- and the C entry points.
+// grid -- InstalledSource, batch/ndt2d_installed_map.h -- and the C entry points.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -19,8 +19,9 @@
 
 #include "ndt2d_guard.h"
 #include "ndt2d_hip.h"
-#include "batch/ndt2d_batch_host.h"
+#include "batch/ndt2d_batch_state.h"
 #include "batch/ndt2d_refine_jobs.h"
+#include "batch/ndt2d_stage_layout.h"
 #include "refine/ndt2d_refine_kernel.h"
 
 struct ndt2d_refine : ndt2d::BatchHost
@@ -78,8 +79,6 @@ int refine_chunk(ndt2d_refine * s, const GridDesc & grid, size_t k0, size_t k1, 
     ndt2d_cos_sin(p[2], st + at.trig + 2 * (k - k0), st + at.trig + 2 * (k - k0) + 1);
   }
   NDT2D_BATCH_HIP(s, hipMemcpyAsync(s->d_stage, st, at.total * sizeof(double), hipMemcpyHostToDevice, stream));
-  s->timed = false;
-  if (s->timing) NDT2D_BATCH_HIP(s, hipEventRecord(s->ev[0], stream));
 
   InstalledArgs a{};
   a.source.g = grid;
@@ -88,15 +87,13 @@ int refine_chunk(ndt2d_refine * s, const GridDesc & grid, size_t k0, size_t k1, 
   a.beams_xy = s->d_stage + at.beams;
   a.rules = t.rules;
   a.records = s->d_out;
-  const dim3 blocks(static_cast<uint32_t>(n_slots)), threads(kRefineThreads);
-  if (s->cells == 9) launch_refine<9>(grid.pow2 != 0, blocks, threads, stream, a);
-  else launch_refine<1>(grid.pow2 != 0, blocks, threads, stream, a);
-  NDT2D_BATCH_HIP(s, hipGetLastError());
-  if (s->timing) NDT2D_BATCH_HIP(s, hipEventRecord(s->ev[1], stream));
-  NDT2D_BATCH_HIP(s, hipMemcpyAsync(s->h_out, s->d_out, n_slots * kRefineRec * sizeof(double), hipMemcpyDeviceToHost, stream));
-  if (s->timing) NDT2D_BATCH_HIP(s, hipEventRecord(s->ev[2], stream));
-  NDT2D_BATCH_HIP(s, hipStreamSynchronize(stream));
-  s->timed = s->timing;
+  const int rc = batch_round_trip(s, stream, n_slots * kRefineRec, [&] {
+    const dim3 blocks(static_cast<uint32_t>(n_slots)), threads(kRefineThreads);
+    if (s->cells == 9) launch_refine<9>(grid.pow2 != 0, blocks, threads, stream, a);
+    else launch_refine<1>(grid.pow2 != 0, blocks, threads, stream, a);
+    return NDT2D_OK;
+  });
+  if (rc != NDT2D_OK) return rc;
   std::memcpy(records_out + k0 * kRefineRec, s->h_out, n_slots * kRefineRec * sizeof(double));
   return NDT2D_OK;
 }

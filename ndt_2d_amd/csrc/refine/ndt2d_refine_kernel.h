@@ -26,7 +26,7 @@
 // names, the GridDesc of that job's map (grid(slot): the geometry cell_index and the 3 x 3 clip
 // use) and its map object of the walk's kind (map(slot): find(cell, rank) / record(rank),
 // batch/ndt2d_walk_fn.h; entry ncell of it exists and never scores); both are uniform over the
-// block.  InstalledSource (batch/ndt2d_batch_search.h) is the grid installed in the context: one
+// block.  InstalledSource (batch/ndt2d_installed_map.h) is the grid installed in the context: one
 // grid for all jobs, refine/ndt2d_refine.hip.  The loop closure refines each job on its candidate's
 // own map with the same kernel: closure/ndt2d_closure.hip includes this header too -- the kernel has
 // one text, this one -- and instantiates it with its slots.
@@ -58,7 +58,7 @@
 #include <cmath>
 
 #include "ndt2d_hip.h"
-#include "batch/ndt2d_batch_search.h"
+#include "batch/ndt2d_installed_map.h"
 #include "refine/ndt2d_refine_step.h"
 
 namespace ndt2d

@@ -9,7 +9,7 @@
 // The kernel, its job record, its arguments, the settings and the layout of what comes back are
 // verify/ndt2d_verify_kernel.h (the loop closure instantiates the same text on its candidate
 // slots); here: the object, the chunk on the installed grid -- InstalledSource,
-// batch/ndt2d_batch_search.h -- and the C entry points.
+// batch/ndt2d_installed_map.h -- and the C entry points.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -17,8 +17,9 @@
 
 #include "ndt2d_guard.h"
 #include "ndt2d_hip.h"
-#include "batch/ndt2d_batch_host.h"
+#include "batch/ndt2d_batch_state.h"
 #include "batch/ndt2d_refine_jobs.h"
+#include "batch/ndt2d_stage_layout.h"
 #include "verify/ndt2d_verify_kernel.h"
 
 struct ndt2d_verify : ndt2d::BatchHost
@@ -74,8 +75,6 @@ int verify_chunk(ndt2d_verify * s, const GridDesc & grid, size_t k0, size_t k1, 
     ndt2d_cos_sin(p[2], st + at.trig + 2 * (k - k0), st + at.trig + 2 * (k - k0) + 1);
   }
   NDT2D_BATCH_HIP(s, hipMemcpyAsync(s->d_stage, st, at.total * sizeof(double), hipMemcpyHostToDevice, stream));
-  s->timed = false;
-  if (s->timing) NDT2D_BATCH_HIP(s, hipEventRecord(s->ev[0], stream));
 
   InstalledVerifyArgs a{};
   a.source.g = grid;
@@ -87,15 +86,13 @@ int verify_chunk(ndt2d_verify * s, const GridDesc & grid, size_t k0, size_t k1, 
   a.beam_m2 = t.beam_m2_out != nullptr ? s->d_out + out.m2 : nullptr;
   a.beam_cells = t.beam_cells_out != nullptr ? reinterpret_cast<uint32_t *>(s->d_out + out.cells) : nullptr;
   a.beam_class = t.beam_class_out != nullptr ? reinterpret_cast<uint8_t *>(s->d_out + out.classes) : nullptr;
-  const dim3 blocks(static_cast<uint32_t>(n_slots)), threads(kVerifyThreads);
-  if (s->set.cells == 9) launch_verify<9>(grid.pow2 != 0, blocks, threads, stream, a);
-  else launch_verify<1>(grid.pow2 != 0, blocks, threads, stream, a);
-  NDT2D_BATCH_HIP(s, hipGetLastError());
-  if (s->timing) NDT2D_BATCH_HIP(s, hipEventRecord(s->ev[1], stream));
-  NDT2D_BATCH_HIP(s, hipMemcpyAsync(s->h_out, s->d_out, out.total * sizeof(double), hipMemcpyDeviceToHost, stream));
-  if (s->timing) NDT2D_BATCH_HIP(s, hipEventRecord(s->ev[2], stream));
-  NDT2D_BATCH_HIP(s, hipStreamSynchronize(stream));
-  s->timed = s->timing;
+  const int rc = batch_round_trip(s, stream, out.total, [&] {
+    const dim3 blocks(static_cast<uint32_t>(n_slots)), threads(kVerifyThreads);
+    if (s->set.cells == 9) launch_verify<9>(grid.pow2 != 0, blocks, threads, stream, a);
+    else launch_verify<1>(grid.pow2 != 0, blocks, threads, stream, a);
+    return NDT2D_OK;
+  });
+  if (rc != NDT2D_OK) return rc;
   std::memcpy(t.records_out + k0 * kVerifyRec, s->h_out, n_slots * kVerifyRec * sizeof(uint32_t));
   if (t.beam_m2_out != nullptr) std::memcpy(t.beam_m2_out + out0, s->h_out + out.m2, n_out * sizeof(double));
   if (t.beam_cells_out != nullptr) std::memcpy(t.beam_cells_out + 2 * out0, s->h_out + out.cells, n_out * 2 * sizeof(uint32_t));

@@ -22,7 +22,7 @@
 //
 // The map is a template argument of the kernel, as of refine_kernel: a SOURCE gives, for the slot
 // a job's record names, the GridDesc of that job's map and its map object (find(cell, rank) /
-// record(rank)); both are uniform over the block.  InstalledSource (batch/ndt2d_batch_search.h) is
+// record(rank)); both are uniform over the block.  InstalledSource (batch/ndt2d_installed_map.h) is
 // the grid installed in the context: one grid for all jobs, verify/ndt2d_verify.hip.
 // closure/ndt2d_closure.hip includes this header too and instantiates the kernel on its candidate
 // slots (SlotSource): one text for both.
@@ -51,7 +51,7 @@
 #include <string>
 
 #include "ndt2d_hip.h"
-#include "batch/ndt2d_batch_search.h"
+#include "batch/ndt2d_installed_map.h"
 #include "batch/ndt2d_refine_jobs.h"
 #include "verify/ndt2d_verify_ray.h"
 

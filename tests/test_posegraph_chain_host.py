@@ -47,8 +47,12 @@ def test_the_entry_points_are_declared_bound_and_hashed():
         assert name in _capi.SIGNATURES, name
     assert _capi.SIGNATURES["ndt2d_pose_graph_preconditioner"][0] is _capi.C.c_char_p
     assert os.path.join(ROOT, "ndt_2d_amd", "csrc", "posegraph", "ndt2d_posegraph_chain.h") in build.HEADERS
+    # the reduction is used by the chain's device functions, which every pose-graph kernel takes from the kernel header
+    kernel = open(os.path.join(ROOT, "ndt_2d_amd", "csrc", "posegraph", "ndt2d_posegraph_kernel.h")).read()
+    assert '#include "posegraph/ndt2d_posegraph_chain.h"' in kernel and "pg::chain::factor_node(" in kernel
+    assert os.path.join(ROOT, "ndt_2d_amd", "csrc", "posegraph", "ndt2d_posegraph_kernel.h") in build.HEADERS
     unit = open(os.path.join(ROOT, "ndt_2d_amd", "csrc", "posegraph", "ndt2d_posegraph.hip")).read()
-    assert '#include "posegraph/ndt2d_posegraph_chain.h"' in unit
+    assert '#include "posegraph/ndt2d_posegraph_kernel.h"' in unit
     # as tests/test_posegraph_host.py asks of the ten ndt2d_posegraph_* bodies: a multi-line body sits in the guard
     bodies = re.findall(r"\n(?:int|const char \*) ndt2d_pose_graph_\w+\([^)]*\)\n\{\n(.*?)\n\}\n", unit, flags=re.S)
     assert len(bodies) == 2

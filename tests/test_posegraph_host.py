@@ -57,16 +57,24 @@ def test_the_plugin_mirror_compiles():
 
 
 def test_the_unit_is_built_hashed_and_bound():
-    assert "posegraph/ndt2d_posegraph.hip" in build.SOURCES
-    assert os.path.join(ROOT, "ndt_2d_amd", "csrc", "posegraph", "ndt2d_posegraph_fn.h") in build.HEADERS
+    posegraph = os.path.join(ROOT, "ndt_2d_amd", "csrc", "posegraph")
+    for unit in ("ndt2d_posegraph.hip", "ndt2d_posegraph_robust.hip", "ndt2d_posegraph_marginals.hip"):
+        assert "posegraph/" + unit in build.SOURCES, unit
+    for name in ("ndt2d_posegraph_fn.h", "ndt2d_posegraph_kernel.h", "ndt2d_posegraph_state.h"):
+        assert os.path.join(posegraph, name) in build.HEADERS, name
     names = [n for n in _capi.SIGNATURES if n.startswith("ndt2d_posegraph_")]
     assert sorted(names) == sorted("ndt2d_posegraph_" + n for n in (
         "create", "destroy", "last_error", "set_graph", "set_weighting", "weighting", "evaluate", "solve", "set_timing", "last_ms"))
     header = open(os.path.join(ROOT, "include", "ndt2d_hip.h")).read()
     assert "#define NDT2D_ABI_VERSION 4" in header and "e^T L^T L e" in header
-    unit = open(os.path.join(ROOT, "ndt_2d_amd", "csrc", "posegraph", "ndt2d_posegraph.hip")).read()
-    code = re.sub(r"//[^\n]*", "", unit)
-    assert "atomic" not in code                                  # a result is bit-identical run to run
+    sources = sorted(n for n in os.listdir(posegraph) if n.endswith((".hip", ".h")))
+    assert len(sources) == 9, sources                            # three units, the kernel and state headers, four of plain C++
+    for name in sources:                                         # a result is bit-identical run to run
+        assert "atomic" not in re.sub(r"//[^\n]*", "", open(os.path.join(posegraph, name)).read()), name
+        assert len(open(os.path.join(posegraph, name)).read().splitlines()) <= 900, name
+    unit = open(os.path.join(posegraph, "ndt2d_posegraph.hip")).read()
+    assert '#include "posegraph/ndt2d_posegraph_fn.h"' in unit and '#include "posegraph/ndt2d_posegraph_kernel.h"' in unit
+    assert '#include "batch/ndt2d_batch_state.h"' in unit and "ndt2d_batch_host.h" not in unit and "ndt2d_batch_search.h" not in unit
     bodies = re.findall(r"\n(?:int|const char \*) ndt2d_posegraph_\w+\([^)]*\)\n\{\n(.*?)\n\}\n", unit, flags=re.S)
     assert len(bodies) == 10
     for body in bodies:

@@ -85,9 +85,14 @@ def test_the_entry_points_are_declared_bound_guarded_and_hashed():
     assert (_capi.MARGINALS_CONVERGED, _capi.MARGINALS_CG_CAP, _capi.MARGINALS_BREAKDOWN, _capi.MARGINALS_NOT_FREE) == (0, 1, 2, 3)
     assert _capi.MARGINALS_RECORD_DOUBLES == 5 and len(_capi.MARGINALS_STATUS_NAMES) == 4
     assert HEADER in build.HEADERS
-    unit = open(os.path.join(ROOT, "ndt_2d_amd", "csrc", "posegraph", "ndt2d_posegraph.hip")).read()
-    assert '#include "posegraph/ndt2d_posegraph_relative.h"' in unit
-    assert "atomic" not in re.sub(r"//[^\n]*", "", unit)
+    assert "posegraph/ndt2d_posegraph_marginals.hip" in build.SOURCES
+    posegraph = os.path.dirname(HEADER)
+    unit = open(os.path.join(posegraph, "ndt2d_posegraph_marginals.hip")).read()
+    assert '#include "posegraph/ndt2d_posegraph_relative.h"' in unit and '#include "posegraph/ndt2d_posegraph_kernel.h"' in unit
+    for name in sorted(n for n in os.listdir(posegraph) if n.endswith((".hip", ".h"))):
+        assert "atomic" not in re.sub(r"//[^\n]*", "", open(os.path.join(posegraph, name)).read()), name
+    solver = open(os.path.join(posegraph, "ndt2d_posegraph.hip")).read()
+    assert "marginals_" not in re.sub(r"//[^\n]*", "", solver)                        # the family and its kernels live in one unit
     bodies = re.findall(r"\nint ndt2d_marginals_\w+\([^)]*\)\n\{\n(.*?)\n\}\n", unit, flags=re.S)
     assert len(bodies) == 3
     for body in bodies:

@@ -131,8 +131,14 @@ def test_the_entry_points_are_declared_bound_guarded_and_hashed():
     assert names == ["ndt2d_robust_loss", "ndt2d_robust_rho", "ndt2d_robust_select", "ndt2d_robust_set_loss"]
     assert _capi.SIGNATURES["ndt2d_robust_loss"][0] is C.c_char_p
     assert os.path.join(ROOT, "ndt_2d_amd", "csrc", "posegraph", "ndt2d_posegraph_loss.h") in build.HEADERS
-    unit = open(os.path.join(ROOT, "ndt_2d_amd", "csrc", "posegraph", "ndt2d_posegraph.hip")).read()
-    assert '#include "posegraph/ndt2d_posegraph_loss.h"' in unit
+    assert "posegraph/ndt2d_posegraph_robust.hip" in build.SOURCES
+    # the losses are used by the kernels' device functions (the kernel header) and by the four entry points' unit
+    kernel = open(os.path.join(ROOT, "ndt_2d_amd", "csrc", "posegraph", "ndt2d_posegraph_kernel.h")).read()
+    assert '#include "posegraph/ndt2d_posegraph_loss.h"' in kernel and "pg::loss_weight<kLoss>(" in kernel
+    unit = open(os.path.join(ROOT, "ndt_2d_amd", "csrc", "posegraph", "ndt2d_posegraph_robust.hip")).read()
+    assert '#include "posegraph/ndt2d_posegraph_loss.h"' in unit and "__global__" not in unit and "hipLaunchKernelGGL" not in unit
+    solver = open(os.path.join(ROOT, "ndt_2d_amd", "csrc", "posegraph", "ndt2d_posegraph.hip")).read()
+    assert "ndt2d_robust_" not in re.sub(r"//[^\n]*", "", solver)              # the family lives in one unit
     bodies = re.findall(r"\n(?:int|const char \*) ndt2d_robust_\w+\([^)]*\)\n\{\n(.*?)\n\}\n", unit, flags=re.S)
     assert len(bodies) == 4
     for body in bodies:

@@ -66,16 +66,20 @@ def test_build_lists_and_the_unit_keeps_no_copy():
     code, kernel = re.sub(r"//[^\n]*", "", text), re.sub(r"//[^\n]*", "", kernel_text)
     # the shared device functions, the batch host and the stage layout are used, not copied: the
     # host's words in the unit, the kernel's in its header, which the unit includes
-    assert '#include "batch/ndt2d_batch_host.h"\n' in text and '#include "refine/ndt2d_refine_kernel.h"\n' in text
-    assert '#include "refine/ndt2d_refine_step.h"\n' in kernel_text and '#include "batch/ndt2d_batch_search.h"\n' in kernel_text
-    for used in ("BatchHost", "installed_grid(", "InstalledSource", "stage_layout("):
+    assert '#include "batch/ndt2d_batch_state.h"\n' in text and '#include "refine/ndt2d_refine_kernel.h"\n' in text
+    assert '#include "refine/ndt2d_refine_step.h"\n' in kernel_text and '#include "batch/ndt2d_installed_map.h"\n' in kernel_text
+    # neither takes the search kernels' header, directly or through the search engine's: the unit compiles its own kernel only
+    for header in ("ndt2d_batch_search.h", "ndt2d_batch_host.h"):
+        assert header not in code and header not in kernel, header
+    for used in ("BatchHost", "installed_grid(", "InstalledSource", "stage_layout(", "batch_round_trip("):
         assert used in code, used
     for used in ("cell_index<POW2>(", "record_exponent(", "exp_score(", "wave_sum_to_last_lane(", "refine::begin(", "refine::take("):
         assert used in kernel and used not in code, used
     # the installed grid's source is the shared one, beside InstalledMap, which it reads through
-    search = re.sub(r"//[^\n]*", "", open(os.path.join(csrc, "batch", "ndt2d_batch_search.h")).read())
-    assert search.count("struct InstalledSource") == 1 and "InstalledMap map(uint32_t) const" in search
-    for absent in ("hipHostMalloc", "hipEventCreate", "atomic", "__threadfence", "struct InstalledMap", "v_fma_f64",
+    installed = re.sub(r"//[^\n]*", "", open(os.path.join(csrc, "batch", "ndt2d_installed_map.h")).read())
+    assert installed.count("struct InstalledSource") == 1 and "InstalledMap map(uint32_t) const" in installed
+    assert "__global__" not in installed and "struct InstalledSource" not in open(os.path.join(csrc, "batch", "ndt2d_batch_search.h")).read()
+    for absent in ("hipHostMalloc", "hipEventCreate", "hipEventRecord", "atomic", "__threadfence", "struct InstalledMap", "v_fma_f64",
                    "struct InstalledSource"):
         assert absent not in code and absent not in kernel, absent
     # one kernel, in the header; launched from the unit: pow2 / divide

@@ -52,7 +52,8 @@ def test_shared_chunk_plan_gives_the_closure_plans_values(tmp_path):
     # scaffolding from csrc/batch/; none keeps a copy of any of it
     csrc = os.path.join(ROOT, "ndt_2d_amd", "csrc")
     shared = "".join(open(os.path.join(csrc, "batch", name)).read() for name in
-                     ("ndt2d_walk_fn.h", "ndt2d_sum_chunks.h", "ndt2d_batch_search.h", "ndt2d_batch_host.h"))
+                     ("ndt2d_walk_fn.h", "ndt2d_sum_chunks.h", "ndt2d_installed_map.h", "ndt2d_batch_search.h", "ndt2d_batch_state.h",
+                      "ndt2d_batch_host.h"))
     for once in ("uint32_t sum_chunks(", "void add_beam(", "void lane_take(", "void block_record(", "batch_search_kernel(",
                  "batch_reduce_kernel(", "switch (chunks)", "struct InstalledMap", "hipHostMalloc(", "hipEventCreate("):
         assert shared.count(once) == 1, once
