@@ -1,16 +1,20 @@
 # experiments/bin/<name>.so: the library with extra compiler flags for ONE translation unit
 #   bash experiments/build_variant_lib.sh <name> <file.hip> <flags...>
+# (<file.hip> relative to ndt_2d_amd/csrc; every other object is the one `python -m ndt_2d_amd.build`
+# left beside its source, the test-hooks objects excluded)
 set -e
 R=$(cd $(dirname $0)/.. && pwd)
 NAME=$1; FILE=$2; shift 2
+C=$R/ndt_2d_amd/csrc
 mkdir -p $R/experiments/bin/obj_$NAME
+OWN=$R/experiments/bin/obj_$NAME/$(basename ${FILE%.hip}).o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC "$@" -I $R/include -I $C -c $C/$FILE -o $OWN
 OBJS=""
-for f in ndt2d_kernels ndt2d_match_lane ndt2d_match_small ndt2d_poses_compact ndt2d_build ndt2d_motion ndt2d_scan ndt2d_occupancy ndt2d_exchange ndt2d_device; do
-  if [ $f.hip = $FILE ]; then
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC "$@" -I $R/include -I $R/ndt_2d_amd/csrc -c $R/ndt_2d_amd/csrc/$f.hip -o $R/experiments/bin/obj_$NAME/$f.o
-    OBJS="$OBJS $R/experiments/bin/obj_$NAME/$f.o"
-  else
-    OBJS="$OBJS $R/ndt_2d_amd/csrc/$f.o"
-  fi
+for o in $C/*.o $C/*/*.o; do
+  case $o in
+    *.hooks.o) ;;
+    $C/${FILE%.hip}.o) OBJS="$OBJS $OWN" ;;
+    *) OBJS="$OBJS $o" ;;
+  esac
 done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $OBJS $R/ndt_2d_amd/csrc/ndt2d_host.o $R/ndt_2d_amd/csrc/host/*.o $R/ndt_2d_amd/csrc/ndt2d_build_info.o -ldl -lpthread -o $R/experiments/bin/$NAME.so
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $OBJS -ldl -lpthread -o $R/experiments/bin/$NAME.so

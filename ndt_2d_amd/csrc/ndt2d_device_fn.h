@@ -282,6 +282,63 @@ __device__ __forceinline__ double wave_sum_to_last_lane(double v)
   return v;
 }
 
+// Ten sums of the wave at once, transposed: gfx950's lane swaps exchange the upper half (rows
+// 2, 3) of one register with the lower half (rows 0, 1) of another, or the odd rows of one with the
+// even rows of the other, so ONE add takes TWO sums down a level -- three instructions per pair of
+// sums and level where wave_sum_to_last_lane() spends six.  The tree is fixed by the lane numbers:
+//   32-lane level: (acc[2j], acc[2j+1]) -> p[j]: lanes 0..31 hold acc[2j]'s partial sums, 32..63 acc[2j+1]'s
+//   16-lane level: (p[0], p[1]) -> r[0], (p[2], p[3]) -> r[1]: row 0 of r[j] holds acc[4j], row 1 acc[4j+2],
+//                  row 2 acc[4j+1], row 3 acc[4j+3]
+//   inside a row:  the four DPP steps; every lane of a row ends with the row's sum
+// p[4] (acc[8], acc[9]) has no partner at the 16-lane level: it goes down its rows first, and
+// row_bcast15 then completes acc[8] in row 1 and acc[9] in row 3.
+// On return EVERY lane of row w (lanes 16 w .. 16 w + 15) holds
+//   r0 = acc[swap_sum_of_row(w)], r1 = acc[4 + swap_sum_of_row(w)], and for w = 1, 3: r2 = acc[8 + w / 2].
+// All 64 lanes must be active.  -DNDT2D_LANE_SWAP_EPILOGUE=0: the item epilogue keeps the ten
+// wave_sum_to_last_lane() calls.
+#ifndef NDT2D_LANE_SWAP_EPILOGUE
+#define NDT2D_LANE_SWAP_EPILOGUE 1
+#endif
+#if NDT2D_LANE_SWAP_EPILOGUE
+// a's upper 32 lanes (HALVES) or odd rows swapped with b's lower 32 lanes / even rows, then a + b
+template <bool HALVES>
+__device__ __forceinline__ double swap_add(double a, double b)
+{
+  typedef unsigned int uint2v __attribute__((ext_vector_type(2)));
+  const unsigned int a_lo = static_cast<unsigned int>(__double2loint(a)), a_hi = static_cast<unsigned int>(__double2hiint(a));
+  const unsigned int b_lo = static_cast<unsigned int>(__double2loint(b)), b_hi = static_cast<unsigned int>(__double2hiint(b));
+  const uint2v lo = HALVES ? __builtin_amdgcn_permlane32_swap(a_lo, b_lo, false, false)
+                           : __builtin_amdgcn_permlane16_swap(a_lo, b_lo, false, false);
+  const uint2v hi = HALVES ? __builtin_amdgcn_permlane32_swap(a_hi, b_hi, false, false)
+                           : __builtin_amdgcn_permlane16_swap(a_hi, b_hi, false, false);
+  return __hiloint2double(static_cast<int>(hi[0]), static_cast<int>(lo[0])) +
+         __hiloint2double(static_cast<int>(hi[1]), static_cast<int>(lo[1]));
+}
+
+__device__ __forceinline__ double row_sum_to_every_lane(double v)
+{
+  v += dpp_f64<kDppQuadXor1, 0xf>(v, 0.0);
+  v += dpp_f64<kDppQuadXor2, 0xf>(v, 0.0);
+  v += dpp_f64<kDppRowHalfMirror, 0xf>(v, 0.0);
+  v += dpp_f64<kDppRowMirror, 0xf>(v, 0.0);
+  return v;
+}
+
+__device__ __forceinline__ void wave_ten_sums_to_rows(const double (&acc)[10], double & r0, double & r1, double & r2)
+{
+  double p[5];
+#pragma unroll
+  for (int j = 0; j < 5; ++j) p[j] = swap_add<true>(acc[2 * j], acc[2 * j + 1]);
+  r0 = row_sum_to_every_lane(swap_add<false>(p[0], p[1]));
+  r1 = row_sum_to_every_lane(swap_add<false>(p[2], p[3]));
+  r2 = row_sum_to_every_lane(p[4]);
+  r2 += dpp_f64<kDppRowBcast15, 0xa>(r2, 0.0);
+}
+
+// acc index (of the first four) held by row w of r0 after wave_ten_sums_to_rows()
+__device__ __forceinline__ uint32_t swap_sum_of_row(uint32_t w) { return ((w & 1u) << 1) | (w >> 1); }
+#endif
+
 // angles::shortest_angular_distance(from, to) = normalize_angle(to - from),
 // normalize_angle(a) = fmod(a + pi, 2 pi) -/+ pi  (ROS `angles`, used at
 // reference src/particle_filter.cpp:215)

@@ -84,13 +84,39 @@ constexpr int kLaneThreadsCompact = NDT2D_LANE_THREADS_COMPACT; // compacted rec
 // The same launch builds the occupancy map of the window (one byte per map
 // cell, see the file header) once, in HBM; every search block then copies the
 // finished image into its LDS.
+//
+// Launch (NDT2D_LANE_TABLE_2D, the default): blockIdx.y < map_rows are the map's own blocks, 256
+// map bytes each; the others take the table, y - map_rows = theta step of the launch (strided by
+// the grid where a slab has more steps than the grid has rows), x = 256 beams -- no division, and
+// cos / sin of the step are one scalar load per block.  -DNDT2D_LANE_TABLE_2D=0 is the
+// one-dimensional launch: every thread builds its share of the map, then its table entries by
+// flat index.
+#ifndef NDT2D_LANE_TABLE_2D
+#define NDT2D_LANE_TABLE_2D 1
+#endif
+constexpr uint32_t kTableMaxRows = 65535;   // gridDim.y
+
 __global__ void __launch_bounds__(256) outer_table_kernel(const MatchArgs a, double4 * outer,
-                                                          uint8_t * map_out, const LaneGeom geo)
+                                                          uint8_t * map_out, const LaneGeom geo
+#if NDT2D_LANE_TABLE_2D
+                                                          , const uint32_t map_rows
+#endif
+                                                          )
 {
+#if NDT2D_LANE_TABLE_2D
+  if (blockIdx.y < map_rows)
+#endif
   {
     const GridDesc & g = a.grid;
     const uint32_t n_map = static_cast<uint32_t>(kMapStride) * geo.map_h;
-    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n_map; i += gridDim.x * 256)
+#if NDT2D_LANE_TABLE_2D
+    const uint32_t map_first = (blockIdx.y * gridDim.x + blockIdx.x) * 256 + threadIdx.x;
+    const uint32_t map_step = map_rows * gridDim.x * 256;
+#else
+    const uint32_t map_first = blockIdx.x * 256 + threadIdx.x;
+    const uint32_t map_step = gridDim.x * 256;
+#endif
+    for (uint32_t i = map_first; i < n_map; i += map_step)
     {
       // map sub-cell (mx, my): its box in the world, widened by kBoxMargin of a
       // sub-cell so that it holds every point whose rounded fixed-point coordinate
@@ -113,6 +139,15 @@ __global__ void __launch_bounds__(256) outer_table_kernel(const MatchArgs a, dou
   }
 
   // the work-item counter of the search kernel that follows on this stream
+#if NDT2D_LANE_TABLE_2D
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < kItemShards) a.next_item[threadIdx.x * kItemShardStride] = 0u;
+  if (blockIdx.y < map_rows) return;
+  const uint32_t b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= a.n_beams) return;
+  for (uint32_t t = blockIdx.y - map_rows; t < a.th_end - a.th_begin; t += gridDim.y - map_rows)
+  {
+    const uint64_t i = static_cast<uint64_t>(t) * a.n_beams + b;
+#else
   if (blockIdx.x == 0 && threadIdx.x < kItemShards) a.next_item[threadIdx.x * kItemShardStride] = 0u;
   const uint64_t n = static_cast<uint64_t>(a.th_end - a.th_begin) * a.n_beams;
   for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x; i < n;
@@ -120,6 +155,7 @@ __global__ void __launch_bounds__(256) outer_table_kernel(const MatchArgs a, dou
   {
     const uint32_t t = static_cast<uint32_t>(i / a.n_beams);
     const uint32_t b = static_cast<uint32_t>(i - static_cast<uint64_t>(t) * a.n_beams);
+#endif
     const uint32_t ith = a.th_begin + t * a.th_stride;
     const double ct = a.cos_th[ith];
     const double st = a.sin_th[ith];
@@ -220,6 +256,8 @@ __device__ __forceinline__ void match_lane_body(
   }
   {
     // the map image was built by the pre-kernel; kMapStride * map_h is a multiple of 16
+    // (the three copies run one 16-byte load per thread at a time; with eight in flight the
+    // launch was no shorter: experiments/README.md, "around the beam loop")
     const uint32_t n16 = static_cast<uint32_t>(kMapStride) * geo.map_h / 16;
     const uint4 * src = reinterpret_cast<const uint4 *>(map_image);
     uint4 * dst = reinterpret_cast<uint4 *>(lds_map);
@@ -404,6 +442,10 @@ __device__ __forceinline__ void match_lane_body(
     asm volatile("" : "+v"(lane_again));
     const uint32_t ix_e = x0 + (lane_again >> h_log2);
     const uint32_t iy_e = y0 + (lane_again & ((1u << h_log2) - 1u));
+#if NDT2D_LANE_SWAP_EPILOGUE
+    // (an item's record starts here, not across the beam loop: see no_index_here())
+    if (DYNAMIC_ITEMS) best_i = no_index_here();
+#endif
     if ((ix_e < x_end) & (iy_e < n_lin))
     {
       const uint32_t ix = ix_e, iy = iy_e;
@@ -451,6 +493,28 @@ __device__ __forceinline__ void match_lane_body(
     // (an item none of whose candidates reached a distribution: every lane holds the
     // record {0, no index, +0.0 x 10} already -- x * -0.0 added to +0.0 is +0.0 -- and so
     // would the reduction: skip it.  cfg-2 - 0.7 %, cfg-4 - 1.3 %)
+#if NDT2D_LANE_SWAP_EPILOGUE
+    // the ten sums go down transposed (wave_ten_sums_to_rows): the last lane of row w ends up
+    // with three of them and writes those words of the record
+    double sums_a = acc[0], sums_b = acc[4], sums_c = acc[8];
+    if (wave_any(sum != 0.0))
+    {
+      NDT2D_PATH(209, 1);
+      // (the sums first: their twenty registers are down to six when the best pair's steps want theirs)
+      wave_ten_sums_to_rows(acc, sums_a, sums_b, sums_c);
+      wave_best_to_last_lane(best_s, best_i);
+    }
+    uint32_t lane_out = lane;
+    asm volatile("" : "+v"(lane_out));
+    if ((lane_out & 15u) == 15u)
+    {
+      const uint32_t w = lane_out >> 4;
+      double * out = a.partials + static_cast<size_t>(item) * kRecord + 2;
+      out[swap_sum_of_row(w)] = sums_a;
+      out[4u + swap_sum_of_row(w)] = sums_b;
+      if ((w & 1u) != 0u) out[8u + (w >> 1)] = sums_c;
+    }
+#else
     if (wave_any(sum != 0.0))
     {
       NDT2D_PATH(209, 1);
@@ -458,6 +522,7 @@ __device__ __forceinline__ void match_lane_body(
 #pragma unroll
       for (int k = 0; k < 10; ++k) acc[k] = wave_sum_to_last_lane(acc[k]);
     }
+#endif
 
     uint32_t next = n_items;
     if (lane == kWave - 1)
@@ -465,8 +530,10 @@ __device__ __forceinline__ void match_lane_body(
       double * out = a.partials + static_cast<size_t>(item) * kRecord;
       out[0] = best_s;
       out[1] = best_i;
+#if !NDT2D_LANE_SWAP_EPILOGUE
 #pragma unroll
       for (int k = 0; k < 10; ++k) out[2 + k] = acc[k];
+#endif
       // Items beyond the first n_workers are dealt to kItemShards counters by
       // index; a wave draws from the shard of its block (blocks b, b + 8, ... are
       // observed to share an XCD) and, once that is empty, from the others.
@@ -480,7 +547,9 @@ __device__ __forceinline__ void match_lane_body(
     }
     item = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(next), kWave - 1));
     best_s = 0.0;
+#if !NDT2D_LANE_SWAP_EPILOGUE
     best_i = no_index_here();
+#endif
 #pragma unroll
     for (int k = 0; k < 10; ++k) acc[k] = 0.0;
   }
@@ -733,9 +802,11 @@ hipError_t launch_match_lane(const MatchArgs & args_in, double * outer, double *
   const uint64_t n_items = static_cast<uint64_t>(args.th_end - args.th_begin) * p1 * p1;
 
   const uint64_t n_outer = static_cast<uint64_t>(args.th_end - args.th_begin) * args.n_beams;
+#if !NDT2D_LANE_TABLE_2D
   uint32_t oblocks = static_cast<uint32_t>((n_outer + 255) / 256);
   if (oblocks > 4096) oblocks = 4096;
   if (oblocks < 64) oblocks = 64;  // the map build wants a few thousand threads as well
+#endif
   uint8_t * map_image = reinterpret_cast<uint8_t *>(outer + n_outer * 4);
   // mid-size lattices: a candidate's beams in parts (decided below, once the kernel form is known)
   uint32_t part_beams = 0;
@@ -811,8 +882,23 @@ hipError_t launch_match_lane(const MatchArgs & args_in, double * outer, double *
     if (blocks == 0) blocks = 1;
   }
   // the table pre-kernel (it also clears the item counters of the search that follows)
+#if NDT2D_LANE_TABLE_2D
+  {
+    // rows of 256-beam blocks: first the map's (a byte per thread), then one per theta step
+    const uint32_t beam_blocks = (args.n_beams + 255u) / 256u;
+    const uint32_t map_blocks = static_cast<uint32_t>(map_bytes + 255) / 256u;
+    uint32_t th_rows = args.th_end - args.th_begin;
+    if (beam_blocks == 0 || th_rows == 0) return hipErrorInvalidValue;
+    const uint32_t map_rows = (map_blocks + beam_blocks - 1u) / beam_blocks;
+    if (map_rows >= kTableMaxRows) return hipErrorInvalidValue;
+    if (th_rows > kTableMaxRows - map_rows) th_rows = kTableMaxRows - map_rows;
+    hipLaunchKernelGGL(outer_table_kernel, dim3(beam_blocks, map_rows + th_rows), dim3(256), 0, stream, args,
+                       reinterpret_cast<double4 *>(outer), map_image, geo, map_rows);
+  }
+#else
   hipLaunchKernelGGL(outer_table_kernel, dim3(oblocks), dim3(256), 0, stream, args,
                      reinterpret_cast<double4 *>(outer), map_image, geo);
+#endif
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   if (ev_after_pre_kernel != nullptr)
