@@ -908,6 +908,67 @@ int ndt2d_marginals_distance(const double * transform_pred, const double * covar
                              const double * transform_meas, const double * covariance_meas,
                              double * d2_out);
 
+/* Dense covariance (ndt2d_covariance_*: an object of its own beside an ndt2d_posegraph, which it
+ * refers to and is destroyed before).  For each job -- a mask over the pose graph's graph, as
+ * everywhere above -- the 3 x 3 diagonal block of EVERY node and the blocks of chosen (a, b) pairs of
+ *     Sigma = (H_FF + damping clamp(diag H_FF))^-1,
+ * the matrix of "Marginal covariances": the same H (sum rho'_c J_c^T J_c over the job's enabled
+ * constraints), the pose graph's weighting and loss as they are at the call, the same free set F
+ * and clamp [1e-6, 1e32], at the graph's poses (poses NULL) or at one [n][3] set per job.  The cost
+ * does not depend on the number of closures: A = H_FF + damping clamp(diag) is assembled densely
+ * (d = 3 n; a node not in F and the padding to whole panels of 48 keep the identity's rows and
+ * columns), factored A = L L^T by a blocked right-looking Cholesky without pivoting (panels of 48;
+ * the trailing update on the FP64 matrix cores, lower blocks only), T = L^-1 is formed by the same
+ * panels, and each asked block is Sigma_ab = sum over k >= 3 max(a, b) of T[k, a]^T T[k, b].
+ *     The outputs.  diagonal_out[K][n][9]: node i's block, row-major, symmetric bit for bit.
+ * pairs_out[K][P][9]: for pairs[P][2] = {a, b} the rows of node a in the columns of node b,
+ * row-major; duplicates and a == b are legal; pairs and pairs_out may be NULL with n_pairs == 0.
+ * Blocks are as computed, nothing is symmetrised afterwards: every block, whichever way round it is
+ * asked, is summed from the one lower-triangular factor T (only the lower triangle of A is
+ * assembled and factored), (a, b) and (b, a) by the same products in the same order, so they are
+ * transposes of each other bit for bit.  A block with a node not in F is zero.
+ * records_out[K][NDT2D_COVARIANCE_RECORD_DOUBLES] = {status, the first failing unknown (3 node + j)
+ * or -1, the pivot ratio}: the smallest, over the unknowns of F, of (the pivot before its square
+ * root) / (that unknown's diagonal entry of A); an unknown not in F has the ratio 1, which is also
+ * the largest a ratio can be.
+ *     Not positive definite.  A pivot <= 0 or not finite: NDT2D_COVARIANCE_NOT_POSITIVE_DEFINITE,
+ * the job's blocks are zero, the pivot ratio is the smallest up to that pivot, and the other jobs
+ * of the call are untouched.  A singular matrix (a component not joined to the fixed pose at
+ * damping = 0) is promised only: NOT_POSITIVE_DEFINITE, or OK with a pivot ratio at rounding level
+ * (about (d + 1) eps).
+ *     Determinism.  No atomics, no split sums: a block of A has one writer that walks the node's
+ * constraints in ascending constraint index, every element of the factorisation is summed over k in
+ * ascending order by one thread or one wave, a block of Sigma by a fixed tree.  A job's bits depend
+ * on the graph, the mask, the poses, the settings and the pair list -- not on the other jobs, the
+ * chunking, workspace_bytes or the run.
+ *     Memory.  Per job of a chunk two matrices of padded(d)^2 doubles (A then L; the identity then
+ * T), padded(d) = d rounded up to a multiple of 48, plus padded(d) + 3 n doubles.  The workspace is
+ * allocated at the first compute (what the call's largest chunk needs, never more than
+ * workspace_bytes) and freed by destroy.  The jobs of a chunk share every launch; a chunk holds
+ * min(the pose graph's max_jobs, workspace_bytes / bytes per job) jobs.
+ *   create    NDT2D_ERR_INVALID: a NULL posegraph or out, workspace_bytes == 0.
+ *   compute   NDT2D_ERR_INVALID before anything runs, the message names the item: a NULL object
+ *             (no message), NULL diagonal_out or records_out, NULL pairs or pairs_out with
+ *             n_pairs > 0, a pair index >= n ("pair q names node i"), a non-finite pose ("job k pose
+ *             i"), a negative or non-finite damping, more than 21,840 poses, a graph of which one
+ *             job does not fit workspace_bytes (the message gives the bytes a job needs).
+ *             n_jobs == 0: NDT2D_OK, nothing done.  Before set_graph: NDT2D_ERR_STATE.
+ *   set_timing / last_ms   HIP events around the launches and the read-back of the last chunk. */
+#define NDT2D_COVARIANCE_RECORD_DOUBLES 3
+#define NDT2D_COVARIANCE_OK 0
+#define NDT2D_COVARIANCE_NOT_POSITIVE_DEFINITE 1
+typedef struct ndt2d_covariance ndt2d_covariance;
+int ndt2d_covariance_create(ndt2d_posegraph * posegraph, size_t workspace_bytes,
+                            ndt2d_covariance ** out);
+int ndt2d_covariance_destroy(ndt2d_covariance * covariance);
+const char * ndt2d_covariance_last_error(ndt2d_covariance * covariance);
+int ndt2d_covariance_compute(ndt2d_covariance * covariance, const uint8_t * enabled, size_t n_jobs,
+                             const double * poses, double damping, const uint32_t * pairs,
+                             size_t n_pairs, double * diagonal_out, double * pairs_out,
+                             double * records_out);
+int ndt2d_covariance_set_timing(ndt2d_covariance * covariance, int enabled);
+int ndt2d_covariance_last_ms(ndt2d_covariance * covariance, float * kernel_ms, float * fetch_ms);
+
 /* Upload the beam endpoints of one scan, robot frame, already subsampled to
  * min(laser_max_beams, points.size()) points by the caller
  * (src/scan_matcher_ndt.cpp:95-96,110 / :165-166,171).  Beams are taken as given: finite,

@@ -36,6 +36,10 @@ POSEGRAPH_RECORD_DOUBLES = 6
 MARGINALS_CONVERGED, MARGINALS_CG_CAP, MARGINALS_BREAKDOWN, MARGINALS_NOT_FREE = range(4)
 MARGINALS_STATUS_NAMES = ("converged", "cg_cap", "breakdown", "not_free")
 MARGINALS_RECORD_DOUBLES = 5
+# NDT2D_COVARIANCE_*: how a job of the dense covariance ended; the doubles of its record
+COVARIANCE_OK, COVARIANCE_NOT_POSITIVE_DEFINITE = range(2)
+COVARIANCE_STATUS_NAMES = ("ok", "not_positive_definite")
+COVARIANCE_RECORD_DOUBLES = 3
 MATCH_RECORD_DOUBLES = 12
 POSE_STATS_DOUBLES = 8
 PF_RESULT_DOUBLES = 8
@@ -195,6 +199,12 @@ SIGNATURES = {
     "ndt2d_marginals_columns": (C.c_int, [_vp, C.POINTER(C.c_uint8), _sz, _dp, C.POINTER(_u32), _sz, _d, _d, _u32, _dp, _dp, _dp]),
     "ndt2d_marginals_relative": (C.c_int, [_dp, _dp, _dp, _dp, _dp]),
     "ndt2d_marginals_distance": (C.c_int, [_dp, _dp, _dp, _dp, _dp]),
+    "ndt2d_covariance_create": (C.c_int, [_vp, _sz, C.POINTER(_vp)]),
+    "ndt2d_covariance_destroy": (C.c_int, [_vp]),
+    "ndt2d_covariance_last_error": (C.c_char_p, [_vp]),
+    "ndt2d_covariance_compute": (C.c_int, [_vp, C.POINTER(C.c_uint8), _sz, _dp, _d, C.POINTER(_u32), _sz, _dp, _dp, _dp]),
+    "ndt2d_covariance_set_timing": (C.c_int, [_vp, C.c_int]),
+    "ndt2d_covariance_last_ms": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "ndt2d_set_eigenvalue_form": (C.c_int, [_vp, C.c_char_p]),
     "ndt2d_get_grid": (C.c_int, [_vp, _dp, _sz, C.POINTER(_u32), C.POINTER(_u32), _dp, _dp, _dp]),
     "ndt2d_clear_grid": (C.c_int, [_vp]),

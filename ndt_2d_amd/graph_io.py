@@ -320,20 +320,24 @@ class Graph:
             s.pose = pose.copy()
         return True
 
-    def closure_distances(self, matcher, constraints, weighting="information", preconditioner="jacobi", **kw):
+    def closure_distances(self, matcher, constraints, weighting="information", preconditioner="jacobi", method="cg", **kw):
         """For each proposed constraint the squared Mahalanobis distance of its transform (with its
         information inverted as its covariance) from what the graph as it stands predicts for
         (begin, end): the relative pose of the two scans with the covariance from their joint
         marginal (PoseGraph.marginals at the scans' poses, scans[0] held; one call covers the
         distinct end nodes).  kw: marginals' damping, tolerance and max_cg_iterations.  A verdict
         per constraint, no policy; nothing of the graph changes.  `last_closure_distances` keeps
-        the statuses and the predictions."""
+        the statuses and the predictions.  method="dense": the joint marginals from one
+        PoseGraph.covariances call instead (a dense Cholesky, whose cost does not depend on the
+        closures; kw: its damping and workspace_bytes), the status then the job's, once."""
         from .pose_graph import PoseGraph, _inverse3, closure_distance, relative_covariance
         constraints = list(constraints)
         self.last_closure_distances = None
         if not constraints:
             return []
         poses = np.array([s.pose for s in self.scans], dtype=np.float64)
+        if method not in ("cg", "dense"):
+            raise ValueError("closure_distances: method = %r (\"cg\" or \"dense\")" % (method,))
         nodes = sorted({int(c.begin) for c in constraints} | {int(c.end) for c in constraints})
         at = {v: i for i, v in enumerate(nodes)}
         pg = PoseGraph(matcher, max_nodes=len(self.scans), max_constraints=max(1, len(self.constraints)), max_jobs=max(1, len(nodes)))
@@ -341,7 +345,13 @@ class Graph:
             pg.set_weighting(weighting)
             pg.set_preconditioner(preconditioner)
             pg.set_graph(poses, self.constraints, fixed=0)
-            got = pg.marginals(nodes, **kw)[0]
+            if method == "dense":
+                grid = [(a, b) for a in nodes for b in nodes]
+                dense = pg.covariances(pairs=grid, **kw)
+                got = dict(blocks=dense["pairs"][0].reshape(len(nodes), len(nodes), 3, 3), status=dense["status"],
+                           cg_iterations=np.zeros(0, dtype=np.int64))
+            else:
+                got = pg.marginals(nodes, **kw)[0]
         finally:
             pg.close()
         out, predictions = [], []

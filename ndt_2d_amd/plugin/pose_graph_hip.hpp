@@ -46,6 +46,7 @@ public:
   PoseGraphHip & operator=(const PoseGraphHip &) = delete;
   ~PoseGraphHip()
   {
+    dropCovariance();
     if (pg_ != nullptr) ndt2d_posegraph_destroy(pg_);
   }
 
@@ -240,6 +241,65 @@ public:
     return ok(ndt2d_marginals_distance(t, cov, transform_meas, covariance_meas, &d2_out));
   }
 
+  // Every scan's 3 x 3 covariance and the blocks of chosen (a, b) pairs by a dense Cholesky on the
+  // device (include/ndt2d_hip.h, "Dense covariance"; the graph as marginals() takes it), at a cost
+  // that does not depend on the closures: diagonal_out[n][9], pairs_out[P][9] (the rows of scan a in
+  // the columns of scan b) for pairs = {a0, b0, a1, b1, ...}.  false: no scans, a refused graph or
+  // call, or a matrix that is not positive definite (a component not joined to scans[0] at
+  // damping = 0); last_error() says which, pivotRatio() how close the factorisation came.
+  // workspace_bytes: the device memory it may take, two 3 n x 3 n matrices of doubles.
+  template <class Constraints, class Scans>
+  bool covariances(const Constraints & constraints, const Scans & scans, const std::vector<std::uint32_t> & pairs,
+                   std::vector<double> & diagonal_out, std::vector<double> & pairs_out, double damping = 0.0,
+                   std::size_t workspace_bytes = std::size_t(1) << 30)
+  {
+    diagonal_out.clear();
+    pairs_out.clear();
+    poses_.clear();
+    for (const auto & scan : scans)
+    {
+      const auto pose = scan->getPose();
+      poses_.push_back(pose.x);
+      poses_.push_back(pose.y);
+      poses_.push_back(pose.theta);
+    }
+    gather(constraints);
+    const std::size_t n = poses_.size() / 3, m = begin_.size(), p = pairs.size() / 2;
+    if (n == 0) return false;
+    if (!upload(poses_.data(), n, begin_.data(), end_.data(), transform_.data(), information_.data(), m, 1)) return false;
+    if (m != 0 && !ok(ndt2d_robust_select(pg_, robust_.data(), m))) return false;
+    robust_.clear();
+    if (cov_ == nullptr || cov_bytes_ != workspace_bytes)
+    {
+      dropCovariance();
+      const int rc = ndt2d_covariance_create(pg_, workspace_bytes, &cov_);
+      if (rc != NDT2D_OK)
+      {
+        error_ = "ndt2d error " + std::to_string(rc) + ": ndt2d_covariance_create";
+        return false;
+      }
+      cov_bytes_ = workspace_bytes;
+    }
+    diagonal_out.assign(n * 9, 0.0);
+    pairs_out.assign(p * 9, 0.0);
+    double rec[NDT2D_COVARIANCE_RECORD_DOUBLES] = {0.0, -1.0, 0.0};
+    const int rc = ndt2d_covariance_compute(cov_, nullptr, 1, nullptr, damping, p != 0 ? pairs.data() : nullptr, p, diagonal_out.data(),
+                                            p != 0 ? pairs_out.data() : nullptr, rec);
+    if (rc != NDT2D_OK)
+    {
+      error_ = std::string("ndt2d error ") + std::to_string(rc) + ": " + ndt2d_covariance_last_error(cov_);
+      return false;
+    }
+    pivot_ratio_ = rec[2];
+    if (static_cast<int>(rec[0]) != NDT2D_COVARIANCE_OK)
+    {
+      error_ = "ndt2d_covariance_compute: not positive definite at unknown " + std::to_string(static_cast<long long>(rec[1]));
+      return false;
+    }
+    return true;
+  }
+
+  double pivotRatio() const { return pivot_ratio_; }            // of the last covariances()
   const PoseGraphRecord & record() const { return record_; }   // of the last optimize()
   const std::string & last_error() const { return error_; }
 
@@ -271,6 +331,7 @@ private:
   {
     if (pg_ == nullptr || n > max_nodes_ || m > max_constraints_ || jobs > max_jobs_)
     {
+      dropCovariance();   // (it refers to the object that goes)
       if (pg_ != nullptr) ndt2d_posegraph_destroy(pg_);
       pg_ = nullptr;
       max_nodes_ = n > 2 * max_nodes_ ? n : 2 * max_nodes_;
@@ -303,6 +364,12 @@ private:
     return r;
   }
 
+  void dropCovariance()
+  {
+    if (cov_ != nullptr) ndt2d_covariance_destroy(cov_);
+    cov_ = nullptr;
+  }
+
   bool ok(int rc)
   {
     if (rc == NDT2D_OK) return true;
@@ -312,6 +379,9 @@ private:
 
   ndt2d_matcher * m_;
   ndt2d_posegraph * pg_ = nullptr;
+  ndt2d_covariance * cov_ = nullptr;   // made at the first covariances(), destroyed before pg_
+  std::size_t cov_bytes_ = 0;
+  double pivot_ratio_ = 0.0;
   std::size_t max_nodes_ = 0, max_constraints_ = 0, max_jobs_ = 1;
   std::uint32_t max_iterations_ = 100;
   double gradient_tolerance_ = 1e-10, function_tolerance_ = 1e-6, parameter_tolerance_ = 1e-8;

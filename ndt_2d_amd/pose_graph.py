@@ -16,6 +16,7 @@ from . import _capi
 from ._capi import Ndt2dError, dptr
 from .graph_io import Constraint
 
+DEFAULT_COVARIANCE_WORKSPACE = 1 << 30   # bytes of the dense covariance's workspace: 2,700 poses a job
 DEFAULT_TOLERANCES = dict(max_iterations=100, gradient_tolerance=1e-10, function_tolerance=1e-6, parameter_tolerance=1e-8)
 
 
@@ -126,6 +127,8 @@ class PoseGraph:
         self._preconditioner = "jacobi"
         self._loss = ("trivial", 1.0, "all")   # kind, scale, on
         self._timing = False
+        self._cov = None           # the dense covariance's object (covariances), made at its first call
+        self._cov_bytes = 0
         self.n = self.m = 0
         self.switchable = np.zeros(0, dtype=bool)
         self._create(int(max_nodes), int(max_constraints), int(max_jobs))
@@ -134,6 +137,7 @@ class PoseGraph:
         p = C.c_void_p()
         self._matcher._dev_check(self._L.ndt2d_posegraph_create(self._matcher.device_handle, max_nodes, max_constraints, max_jobs, C.byref(p)),
                                  "ndt2d_posegraph_create")
+        self._close_covariance()   # (it refers to the object that goes)
         old, self._p = self._p, p
         if old:
             self._L.ndt2d_posegraph_destroy(old)
@@ -145,7 +149,13 @@ class PoseGraph:
         if self._timing:
             self.set_timing(True)
 
+    def _close_covariance(self):
+        if getattr(self, "_cov", None):
+            self._L.ndt2d_covariance_destroy(self._cov)
+        self._cov = None
+
     def close(self):
+        self._close_covariance()
         if getattr(self, "_p", None):
             self._L.ndt2d_posegraph_destroy(self._p)
             self._p = None
@@ -347,6 +357,75 @@ class PoseGraph:
         t, cov = relative_covariance(poses[int(a)], poses[int(b)], got["blocks"])
         return dict(transform=t, covariance=cov, status=got["status"], joint=got["blocks"])
 
+    def covariances(self, masks=None, poses=None, damping=0.0, pairs=None, workspace_bytes=DEFAULT_COVARIANCE_WORKSPACE):
+        """Every node's 3 x 3 block and the blocks of chosen (a, b) pairs of
+        (H_FF + damping clamp(diag H_FF))^-1 by a dense Cholesky on the device (include/ndt2d_hip.h,
+        "Dense covariance"): one job per mask (None: one job, every constraint on), at the graph's
+        poses or at poses [K, n, 3].  pairs [P, 2]: block = the rows of node a in the columns of
+        node b.  workspace_bytes: the device memory the jobs of a chunk may take (two 3n x 3n
+        matrices of doubles a job); the object is made at the first call and again when this changes.
+        Returns dict(diagonal [K, n, 3, 3], pairs [K, P, 3, 3], status [K], failed [K] (the first
+        failing unknown or -1), pivot_ratio [K])."""
+        en, K = self._masks(masks)
+        if poses is not None:
+            poses = np.ascontiguousarray(poses, dtype=np.float64)
+            if poses.size != K * self.n * 3:
+                raise ValueError("covariances: poses has %d values, %d jobs of %d poses need %d" % (poses.size, K, self.n, K * self.n * 3))
+        pr = np.zeros((0, 2), dtype=np.uint32) if pairs is None else np.asarray(pairs).reshape(-1, 2)
+        if pr.size and not (0 <= int(pr.min()) and int(pr.max()) < 2 ** 32):
+            raise ValueError("covariances: a pair names node %d" % int(pr.min() if pr.min() < 0 else pr.max()))
+        pr = np.ascontiguousarray(pr, dtype=np.uint32)
+        P = len(pr)
+        if self._cov is None or self._cov_bytes != int(workspace_bytes):
+            self._close_covariance()
+            c = C.c_void_p()
+            rc = self._L.ndt2d_covariance_create(self._p, int(workspace_bytes), C.byref(c))
+            if rc != _capi.OK:
+                raise Ndt2dError(rc, "ndt2d_covariance_create", "workspace_bytes = %d" % int(workspace_bytes))
+            self._cov, self._cov_bytes = c, int(workspace_bytes)
+            if self._timing:
+                self._L.ndt2d_covariance_set_timing(self._cov, 1)
+        diagonal = np.zeros((K, self.n, 3, 3))
+        blocks = np.zeros((K, P, 3, 3))
+        records = np.zeros((K, _capi.COVARIANCE_RECORD_DOUBLES))
+        rc = self._L.ndt2d_covariance_compute(self._cov, self._u8(en), K, None if poses is None else dptr(poses), float(damping),
+                                              pr.ctypes.data_as(C.POINTER(C.c_uint32)) if P else None, P, dptr(diagonal),
+                                              dptr(blocks) if P else None, dptr(records))
+        if rc != _capi.OK:
+            msg = self._L.ndt2d_covariance_last_error(self._cov)
+            raise Ndt2dError(rc, "ndt2d_covariance_compute", msg.decode() if msg else "")
+        return dict(diagonal=diagonal, pairs=blocks, status=records[:, 0].astype(np.int64), failed=records[:, 1].astype(np.int64),
+                    pivot_ratio=records[:, 2].copy())
+
+    def covariance_last_ms(self):
+        """(kernel_ms, fetch_ms) of the last covariances call's last chunk (set_timing(True))."""
+        a, b = C.c_float(0.0), C.c_float(0.0)
+        rc = self._L.ndt2d_covariance_last_ms(self._cov, C.byref(a), C.byref(b))
+        if rc != _capi.OK:
+            msg = self._L.ndt2d_covariance_last_error(self._cov)
+            raise Ndt2dError(rc, "ndt2d_covariance_last_ms", msg.decode() if msg else "")
+        return a.value, b.value
+
+    def relative_covariances(self, pairs, poses=None, mask=None, damping=0.0, workspace_bytes=DEFAULT_COVARIANCE_WORKSPACE):
+        """relative_covariance for every (a, b) of pairs [P, 2] from ONE covariances call: the joint
+        marginal of each pair is {diagonal[a], block (a, b), block (b, a), diagonal[b]}, then
+        ndt2d_marginals_relative per pair.  poses [n, 3]: where to linearise (required, as for
+        relative_covariance).  Returns a list of dict(transform [3], covariance [3, 3], joint
+        [2, 2, 3, 3], status: the job's)."""
+        if poses is None:
+            raise ValueError("relative_covariances: poses [n, 3] (the poses the graph was given, or optimize's)")
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(self.n, 3)
+        pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+        both = np.concatenate([pr, pr[:, ::-1]])
+        got = self.covariances(masks=None if mask is None else np.asarray(mask).reshape(1, -1), poses=poses[None], damping=damping, pairs=both,
+                               workspace_bytes=workspace_bytes)
+        out = []
+        for q, (a, b) in enumerate(pr):
+            joint = np.array([[got["diagonal"][0, a], got["pairs"][0, q]], [got["pairs"][0, len(pr) + q], got["diagonal"][0, b]]])
+            t, cov = relative_covariance(poses[a], poses[b], joint)
+            out.append(dict(transform=t, covariance=cov, joint=joint, status=int(got["status"][0])))
+        return out
+
     def _weights(self, chi2):
         """rho'(chi2) [K, m] (ndt2d_robust_rho's, by robust_weights), 1 where the loss does not apply."""
         kind, scale, on = self._loss
@@ -355,6 +434,8 @@ class PoseGraph:
 
     def set_timing(self, enabled):
         self._check(self._L.ndt2d_posegraph_set_timing(self._p, 1 if enabled else 0), "ndt2d_posegraph_set_timing")
+        if self._cov is not None:
+            self._L.ndt2d_covariance_set_timing(self._cov, 1 if enabled else 0)
         self._timing = bool(enabled)
 
     def last_ms(self):
