@@ -969,6 +969,68 @@ int ndt2d_covariance_compute(ndt2d_covariance * covariance, const uint8_t * enab
 int ndt2d_covariance_set_timing(ndt2d_covariance * covariance, int enabled);
 int ndt2d_covariance_last_ms(ndt2d_covariance * covariance, float * kernel_ms, float * fetch_ms);
 
+/* Direct solve (ndt2d_direct_*: an object of its own beside an ndt2d_posegraph, which it refers to
+ * and is destroyed before).  A second way to solve the problem of "Pose graph" and "Robust losses":
+ * the same residual, weighting, losses, cost F, Jacobians, H, g and D = clamp(diag H) to
+ * [1e-6, 1e32], by the same device functions, and the same Levenberg-Marquardt rules -- but the
+ * linear step is exact: A = H_FF + lambda D is assembled densely and factored A = L L^T by the blocked
+ * Cholesky of "Dense covariance" (the factor's launches only, no inverse), and delta solves
+ * L L^T delta = -g by two substitutions.  An iteration's cost does not depend on the number of
+ * closures, and its launches span the chip.  ndt2d_posegraph_solve stays the default solver.
+ *     ndt2d_direct_solve takes ndt2d_posegraph_solve's arguments with their meanings: enabled[K][m]
+ * or NULL, poses_out[K][n][3], an optional chi2_out[K][2][m] (at the start and at the end), the pose
+ * graph's weighting and loss as they are at the call, the same free set -- a node that cannot move
+ * (the fixed one, or without an enabled constraint) keeps its bits, -0.0 included.
+ *     The LM rules.  lambda_0 = 1e-4, nu = 2.  With dF = F - F_trial and the model's decrease
+ * predicted = 1/2 (lambda delta^T D delta - g^T delta) (an exact step leaves no residual term), a
+ * step is accepted when F_trial is finite, predicted > 0 and the gain ratio dF / predicted is above
+ * 1e-3 -- or, where |dF| <= 256 eps F, by the model alone.  Accepted: lambda *= max(1/3,
+ * 1 - (2 gain - 1)^3), under the noise rule 1/3, nu = 2.  Rejected: lambda *= nu, nu *= 2.  lambda
+ * stays within [1e-32, 1e32].  A factorisation that fails (a pivot <= 0 or not finite) counts as a
+ * rejected step: lambda and nu move as on a rejection and no trial point is evaluated.  The four
+ * stop rules and the status values are NDT2D_POSEGRAPH_*, evaluated where the CG solver evaluates
+ * them (the step rule before the trial's cost, the gradient and the cost rule behind an accepted
+ * step); an iteration is counted whether its step is accepted or not.
+ *     records_out[K][NDT2D_DIRECT_RECORD_DOUBLES] = {status, iterations, rejected steps (failed
+ * factorisations among them), factorisations that failed, initial_cost, final_cost, final |g|_inf,
+ * the smallest pivot ratio of the last successful factorisation in "Dense covariance"'s definition
+ * (1 before the first)}.  initial_cost is ndt2d_posegraph_evaluate's F bit for bit.  A start cost
+ * that is not finite: NDT2D_POSEGRAPH_FAILED and the start poses.  m = 0 or n = 1: nothing moves,
+ * NDT2D_POSEGRAPH_CONVERGED_GRADIENT.
+ *     An iteration of a chunk is a fixed list of launches -- the assembly at each job's own lambda,
+ * the factor's launches, one workgroup per job for the substitutions, one for the step -- after
+ * which the host reads the jobs' states back (one small read-back per LM iteration) and stops when
+ * no job is iterating or after max_iterations.  No waiting on the device.  The stream is the
+ * context's current one.  A job that has stopped is left alone: its poses and record do not change.
+ *     Determinism.  No atomics, every sum in a fixed order.  A job's bits depend on the graph, the
+ * mask, the settings and the tolerances -- not on the other jobs, the chunking, workspace_bytes,
+ * whether other jobs of the call have already stopped, or the run.
+ *     Memory.  Per job of a chunk ONE matrix of padded(d)^2 doubles (A, then L; d = 3 n, padded(d)
+ * = d rounded up to a multiple of 48), 2 padded(d) + 3 n doubles beside it (the diagonal, the
+ * substitutions' vector, cos / sin / free flag per node), the CG solver's node arrays (41 n
+ * doubles, m more under a loss) and 16 doubles of state: 8 (padded(d)^2 + 2 padded(d) + 44 n
+ * [+ m] + 16) bytes.  The workspace is allocated at the first solve (what the call's largest chunk
+ * needs, never more than workspace_bytes) and freed by destroy; a chunk holds min(the pose graph's
+ * max_jobs, workspace_bytes / bytes per job) jobs.
+ *   create    NDT2D_ERR_INVALID: a NULL posegraph or out, workspace_bytes == 0.
+ *   solve     NDT2D_ERR_INVALID before anything runs: a NULL object (no message), NULL poses_out or
+ *             records_out, a negative or non-finite tolerance, more than 21,840 poses, a graph of
+ *             which one job does not fit workspace_bytes (the message gives the bytes a job needs).
+ *             n_jobs == 0: NDT2D_OK, nothing done.  Before set_graph: NDT2D_ERR_STATE.
+ *   set_timing / last_ms   HIP events around the last chunk's iterations (the read-backs between
+ *             them included) and its final read-back. */
+#define NDT2D_DIRECT_RECORD_DOUBLES 8
+typedef struct ndt2d_direct ndt2d_direct;
+int ndt2d_direct_create(ndt2d_posegraph * posegraph, size_t workspace_bytes, ndt2d_direct ** out);
+int ndt2d_direct_destroy(ndt2d_direct * direct);
+const char * ndt2d_direct_last_error(ndt2d_direct * direct);
+int ndt2d_direct_solve(ndt2d_direct * direct, const uint8_t * enabled, size_t n_jobs,
+                       uint32_t max_iterations, double gradient_tolerance,
+                       double function_tolerance, double parameter_tolerance, double * poses_out,
+                       double * records_out, double * chi2_out);
+int ndt2d_direct_set_timing(ndt2d_direct * direct, int enabled);
+int ndt2d_direct_last_ms(ndt2d_direct * direct, float * kernel_ms, float * fetch_ms);
+
 /* Upload the beam endpoints of one scan, robot frame, already subsampled to
  * min(laser_max_beams, points.size()) points by the caller
  * (src/scan_matcher_ndt.cpp:95-96,110 / :165-166,171).  Beams are taken as given: finite,

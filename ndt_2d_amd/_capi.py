@@ -40,6 +40,8 @@ MARGINALS_RECORD_DOUBLES = 5
 COVARIANCE_OK, COVARIANCE_NOT_POSITIVE_DEFINITE = range(2)
 COVARIANCE_STATUS_NAMES = ("ok", "not_positive_definite")
 COVARIANCE_RECORD_DOUBLES = 3
+# the doubles of a direct solve's record (its status values are POSEGRAPH_*)
+DIRECT_RECORD_DOUBLES = 8
 MATCH_RECORD_DOUBLES = 12
 POSE_STATS_DOUBLES = 8
 PF_RESULT_DOUBLES = 8
@@ -205,6 +207,12 @@ SIGNATURES = {
     "ndt2d_covariance_compute": (C.c_int, [_vp, C.POINTER(C.c_uint8), _sz, _dp, _d, C.POINTER(_u32), _sz, _dp, _dp, _dp]),
     "ndt2d_covariance_set_timing": (C.c_int, [_vp, C.c_int]),
     "ndt2d_covariance_last_ms": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "ndt2d_direct_create": (C.c_int, [_vp, _sz, C.POINTER(_vp)]),
+    "ndt2d_direct_destroy": (C.c_int, [_vp]),
+    "ndt2d_direct_last_error": (C.c_char_p, [_vp]),
+    "ndt2d_direct_solve": (C.c_int, [_vp, C.POINTER(C.c_uint8), _sz, _u32, _d, _d, _d, _dp, _dp, _dp]),
+    "ndt2d_direct_set_timing": (C.c_int, [_vp, C.c_int]),
+    "ndt2d_direct_last_ms": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "ndt2d_set_eigenvalue_form": (C.c_int, [_vp, C.c_char_p]),
     "ndt2d_get_grid": (C.c_int, [_vp, _dp, _sz, C.POINTER(_u32), C.POINTER(_u32), _dp, _dp, _dp]),
     "ndt2d_clear_grid": (C.c_int, [_vp]),

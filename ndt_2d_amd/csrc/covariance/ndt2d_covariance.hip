@@ -62,12 +62,12 @@ void cov_launch(const ndt2d_covariance * s, hipStream_t stream, const PgGraph & 
 {
   const uint32_t ld = static_cast<uint32_t>(cov::padded(3 * static_cast<size_t>(a.n)));
   const dim3 per_node((a.n + kCovNodeThreads - 1) / kCovNodeThreads, 1, a.jobs);
-  hipLaunchKernelGGL(covariance_nodes_kernel, per_node, dim3(kCovNodeThreads), 0, stream, G, a.d_en, a.poses, a.pose_stride, a.workspace);
-  hipLaunchKernelGGL(covariance_fill_kernel, dim3((ld + kCovFillThreads - 1) / kCovFillThreads, ld, a.jobs), dim3(kCovFillThreads), 0, stream, a.n,
+  hipLaunchKernelGGL(covariance_nodes_kernel<>, per_node, dim3(kCovNodeThreads), 0, stream, G, a.d_en, a.poses, a.pose_stride, a.workspace);
+  hipLaunchKernelGGL(covariance_fill_kernel<>, dim3((ld + kCovFillThreads - 1) / kCovFillThreads, ld, a.jobs), dim3(kCovFillThreads), 0, stream, a.n,
                      a.workspace);
   pg_dispatch(s->graph, [&](auto, auto loss) {
     hipLaunchKernelGGL(covariance_assemble_kernel<decltype(loss)::value>, per_node, dim3(kCovNodeThreads), 0, stream, G, a.d_en, a.poses,
-                       a.pose_stride, a.damping, a.workspace);
+                       a.pose_stride, a.damping, nullptr, size_t(0), a.workspace);
   });
   for (const cov::Launch & l : s->launches)
   {
@@ -75,7 +75,7 @@ void cov_launch(const ndt2d_covariance * s, hipStream_t stream, const PgGraph & 
     switch (l.kind)
     {
       case cov::kFactor:
-        hipLaunchKernelGGL(covariance_factor_kernel, grid, dim3(kCovFactorThreads), 0, stream, a.n, l.panel, a.workspace, a.records);
+        hipLaunchKernelGGL(covariance_factor_kernel<>, grid, dim3(kCovFactorThreads), 0, stream, a.n, l.panel, a.workspace, a.records);
         break;
       case cov::kSolveBelow:
         hipLaunchKernelGGL(covariance_solve_kernel<false>, grid, dim3(kWave), 0, stream, a.n, l.panel, a.workspace);

@@ -52,9 +52,12 @@ constexpr size_t kCovRec = NDT2D_COVARIANCE_RECORD_DOUBLES;
 
 typedef double cov_d4 __attribute__((ext_vector_type(4)));
 
-// A job's part of the workspace.
+// A job's part of the workspace.  The kernels that walk a job's matrices take the layout as a template
+// argument, CovJob by default: the direct solve (direct/ndt2d_direct_kernel.h) runs the assembly and
+// the factorisation on a layout of its own, without T (kInverse = false).
 struct CovJob
 {
+  static constexpr bool kInverse = true;
   double * A, * T, * diag, * cs, * act;
   __device__ __forceinline__ CovJob(double * workspace, size_t n, size_t job)
   {
@@ -69,6 +72,7 @@ struct CovJob
 
 //   covariance_nodes_kernel   grid (nodes / 64, 1, job): cos and sin of each pose's heading (the
 //       device library's, as the solver's node cache) and whether the node is free.
+template <class Job = CovJob>
 __global__ void __launch_bounds__(kCovNodeThreads) covariance_nodes_kernel(const PgGraph G, const uint8_t * enabled, const double * poses,
                                                                            size_t pose_stride, double * workspace)
 {
@@ -76,7 +80,7 @@ __global__ void __launch_bounds__(kCovNodeThreads) covariance_nodes_kernel(const
   const uint32_t i = blockIdx.x * kCovNodeThreads + threadIdx.x;
   if (i >= G.n) return;
   const uint8_t * en = enabled != nullptr ? enabled + job * G.m : nullptr;
-  const CovJob w(workspace, n, job);
+  const Job w(workspace, n, job);
   const double * xs = poses + job * pose_stride;
   double sn, cs;
   sincos(xs[3 * static_cast<size_t>(i) + 2], &sn, &cs);
@@ -93,15 +97,16 @@ __global__ void __launch_bounds__(kCovNodeThreads) covariance_nodes_kernel(const
 }
 
 //   covariance_fill_kernel   grid (ld / 256, row, job): A = 0 but the padding's unit diagonal,
-//       T = the identity.
+//       T = the identity (where the layout has one).
+template <class Job = CovJob>
 __global__ void __launch_bounds__(kCovFillThreads) covariance_fill_kernel(uint32_t n, double * workspace)
 {
-  const CovJob w(workspace, n, blockIdx.z);
+  const Job w(workspace, n, blockIdx.z);
   const size_t d = 3 * static_cast<size_t>(n), ld = cov::padded(d);
   const size_t r = blockIdx.y, c = static_cast<size_t>(blockIdx.x) * kCovFillThreads + threadIdx.x;
   if (c >= ld) return;
   w.A[r * ld + c] = r == c && r >= d ? 1.0 : 0.0;
-  w.T[r * ld + c] = r == c ? 1.0 : 0.0;
+  if constexpr (Job::kInverse) w.T[r * ld + c] = r == c ? 1.0 : 0.0;
   if (r == 0 && c >= d) w.diag[c] = 1.0;
 }
 
@@ -110,16 +115,20 @@ __global__ void __launch_bounds__(kCovFillThreads) covariance_fill_kernel(uint32
 //       diagonal block as pg_linearize does (the same bits), block (i, j) for the free j < i as
 //       (W E_i)^T (W E_j), under a loss each weighted by the constraint's rho' taken from the node's
 //       own r -- duplicates and reversed edges included.  The diagonal block gets
-//       + damping clamp(diag).  A block has one writer: this thread.  Behind the node and fill kernels.
-template <int kLoss>
+//       + damping clamp(diag); job_damping: NULL, or the jobs' own dampings at
+//       job_damping[job x damping_stride] in place of `damping` (the direct solve's lambda).  A block
+//       has one writer: this thread.  Behind the node and fill kernels.
+template <int kLoss, class Job = CovJob>
 __global__ void __launch_bounds__(kCovNodeThreads) covariance_assemble_kernel(const PgGraph G, const uint8_t * enabled, const double * poses,
-                                                                              size_t pose_stride, double damping, double * workspace)
+                                                                              size_t pose_stride, double damping, const double * job_damping,
+                                                                              size_t damping_stride, double * workspace)
 {
   const size_t job = blockIdx.z, n = G.n, ld = cov::padded(3 * n);
+  if (job_damping != nullptr) damping = job_damping[job * damping_stride];
   const uint32_t i = blockIdx.x * kCovNodeThreads + threadIdx.x;
   if (i >= G.n) return;
   const uint8_t * en = enabled != nullptr ? enabled + job * G.m : nullptr;
-  const CovJob w(workspace, n, job);
+  const Job w(workspace, n, job);
   const double * xs = poses + job * pose_stride;
   const size_t at = cov::unknown(i, 0);
   double S[6] = {1.0, 0.0, 0.0, 1.0, 0.0, 1.0};
@@ -224,10 +233,11 @@ __device__ __forceinline__ void cov_load_block(const double * M, size_t ld, size
 //       the same order whatever the number of lanes.  Thread 0 owns the job's record {failed, the
 //       first failing unknown or -1, the smallest pivot / diagonal of A} with plain stores: panel 0
 //       starts it, every panel reads it back.  A pivot <= 0 or not finite fails.
+template <class Job = CovJob>
 __global__ void __launch_bounds__(kCovFactorThreads) covariance_factor_kernel(uint32_t n, uint32_t p, double * workspace, double * records)
 {
   __shared__ double S[cov::kPanel][kCovLds];
-  const CovJob w(workspace, n, blockIdx.z);
+  const Job w(workspace, n, blockIdx.z);
   const size_t d = 3 * static_cast<size_t>(n), ld = cov::padded(d), j0 = static_cast<size_t>(p) * cov::kPanel;
   const uint32_t t = threadIdx.x / kCovFactorLanes, lane = threadIdx.x % kCovFactorLanes;
   cov_load_block<false>(w.A, ld, j0, j0, S, kCovFactorThreads);
@@ -282,11 +292,11 @@ __global__ void __launch_bounds__(kCovFactorThreads) covariance_factor_kernel(ui
 //       kRow = false: a thread per row i below the panel, L[i, p] = A[i, p] L[p, p]^-T by
 //       substitution along the row.  kRow = true: a thread per column c < 48 (p + 1),
 //       T[p, c] = L[p, p]^-1 T[p, c] by substitution down the column.  The 48 values stay in registers.
-template <bool kRow>
+template <bool kRow, class Job = CovJob>
 __global__ void __launch_bounds__(kWave) covariance_solve_kernel(uint32_t n, uint32_t p, double * workspace)
 {
   __shared__ double L[cov::kPanel][kCovLds];
-  const CovJob w(workspace, n, blockIdx.z);
+  const Job w(workspace, n, blockIdx.z);
   const size_t ld = cov::padded(3 * static_cast<size_t>(n)), j0 = static_cast<size_t>(p) * cov::kPanel;
   cov_load_block<false>(w.A, ld, j0, j0, L, kWave);
   __syncthreads();
@@ -330,12 +340,12 @@ __global__ void __launch_bounds__(kWave) covariance_solve_kernel(uint32_t n, uin
 //       D[row (l >> 4) + 4 reg][col l & 15] in reg = 0 .. 3.  Wave v has the block's tile row v:
 //       three accumulators, each summed over the panel's 48 k in ascending order from zero, then
 //       subtracted from C once.
-template <bool kRect>
+template <bool kRect, class Job = CovJob>
 __global__ void __launch_bounds__(kCovUpdateThreads) covariance_update_kernel(uint32_t n, uint32_t p, double * workspace)
 {
   __shared__ double P[cov::kPanel][kCovLds];
   __shared__ double Q[cov::kPanel][kCovLds];
-  const CovJob w(workspace, n, blockIdx.z);
+  const Job w(workspace, n, blockIdx.z);
   const size_t ld = cov::padded(3 * static_cast<size_t>(n)), j0 = static_cast<size_t>(p) * cov::kPanel;
   uint32_t bi, bj;
   cov::update_block(kRect ? cov::kUpdateRect : cov::kUpdate, p, blockIdx.x, &bi, &bj);
@@ -360,7 +370,9 @@ __global__ void __launch_bounds__(kCovUpdateThreads) covariance_update_kernel(ui
       acc[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[tj], 0, 0, 0);
     }
   }
-  double * C = (kRect ? w.T : w.A) + (row0 + cov::kTile * wave) * ld + col0;
+  double * C;
+  if constexpr (kRect) C = w.T + (row0 + cov::kTile * wave) * ld + col0;
+  else C = w.A + (row0 + cov::kTile * wave) * ld + col0;
 #pragma unroll
   for (int tj = 0; tj < 3; ++tj)
   {
@@ -378,8 +390,9 @@ __global__ void __launch_bounds__(kCovUpdateThreads) covariance_update_kernel(ui
 //       for workgroup a < n, the asked pair behind.  Lane l takes the rows first + l, first + l + 64,
 //       ... in ascending order, the wave an xor butterfly.  (a, b) and (b, a) run the same products
 //       in the same order: transposes bit for bit, and (a, a) is symmetric.  Zero where a or b is
-//       not free, and everywhere in a job that failed.
-__global__ void __launch_bounds__(kWave) covariance_blocks_kernel(uint32_t n, const uint32_t * pairs, double * workspace, const double * records,
+//       not free, and everywhere in a job that failed.  ([[maybe_unused]]: the one kernel here that is
+//       not a template, in a header that the direct solve's unit takes for the factor alone.)
+[[maybe_unused]] __global__ void __launch_bounds__(kWave) covariance_blocks_kernel(uint32_t n, const uint32_t * pairs, double * workspace, const double * records,
                                                                   double * diagonal_out, double * pairs_out)
 {
   const size_t job = blockIdx.z;

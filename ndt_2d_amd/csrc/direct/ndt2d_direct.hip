@@ -1,0 +1,299 @@
+// The direct pose-graph solve on the device (include/ndt2d_hip.h, "Direct solve"): the CG solver's
+// problem and Levenberg-Marquardt rules with an exact linear step, L L^T delta = -g on the dense
+// covariance's blocked Cholesky of H_FF + lambda clamp(diag H_FF) -- a cost per iteration that does
+// not depend on the closures, in launches that span the chip (gfx950 / MI355X).  The object stands
+// beside an ndt2d_posegraph and reads its graph, weighting and loss; the kernels are
+// direct/ndt2d_direct_kernel.h and covariance/ndt2d_covariance_kernel.h, the decisions
+// direct/ndt2d_direct_step.h, a job's doubles direct/ndt2d_direct_plan.h, the panels and the factor's
+// launches covariance/ndt2d_covariance_plan.h.
+//
+// The host enqueues one iteration's launches for the chunk, reads the jobs' small states back and
+// stops when no job is iterating: one read-back per LM iteration, no waiting on the device.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "ndt2d_guard.h"
+#include "ndt2d_hip.h"
+#include "batch/ndt2d_batch_state.h"
+#include "covariance/ndt2d_covariance_kernel.h"
+#include "covariance/ndt2d_covariance_plan.h"
+#include "direct/ndt2d_direct_kernel.h"
+#include "direct/ndt2d_direct_plan.h"
+#include "direct/ndt2d_direct_step.h"
+#include "posegraph/ndt2d_posegraph_kernel.h"
+#include "posegraph/ndt2d_posegraph_state.h"
+
+struct ndt2d_direct : ndt2d::BatchHost
+{
+  ndt2d_posegraph * graph = nullptr;   // (the caller keeps it alive)
+  size_t workspace_bytes = 0;          // the budget
+  // from the first solve on: the chunk's jobs on the device, their states as read back (pinned)
+  void * d_workspace = nullptr;
+  size_t workspace_cap = 0;
+  double * h_state = nullptr;
+  size_t state_cap = 0;                // doubles
+  std::vector<ndt2d::covariance::Launch> launches;   // the factor's part of the plan's list
+};
+
+namespace ndt2d
+{
+
+namespace
+{
+
+int direct_from_graph(ndt2d_direct * s, int rc)
+{
+  if (rc != NDT2D_OK) s->err = s->graph->err;
+  return rc;
+}
+
+// One LM iteration of a chunk in stream order: the nodes, the fill, the assembly at each job's
+// lambda, the factor's launches, the substitutions, the step.
+void direct_iteration(const ndt2d_direct * s, hipStream_t stream, const PgGraph & G, const uint8_t * d_en, const DirectChunk & c, uint32_t jobs,
+                      const PgRules & rules)
+{
+  const uint32_t n = G.n, ld = static_cast<uint32_t>(cov::padded(3 * static_cast<size_t>(n)));
+  const dim3 per_node((n + kCovNodeThreads - 1) / kCovNodeThreads, 1, jobs);
+  const double * x = c.work + c.work_front;   // (PgWork's x leads a job's node arrays)
+  hipLaunchKernelGGL(covariance_nodes_kernel<DirectJob>, per_node, dim3(kCovNodeThreads), 0, stream, G, d_en, x, c.work_stride, c.dense);
+  hipLaunchKernelGGL(covariance_fill_kernel<DirectJob>, dim3((ld + kCovFillThreads - 1) / kCovFillThreads, ld, jobs), dim3(kCovFillThreads), 0,
+                     stream, n, c.dense);
+  const double * lambda = c.state + offsetof(direct::State, lambda) / sizeof(double);
+  pg_dispatch(s->graph, [&](auto, auto loss) {
+    hipLaunchKernelGGL((covariance_assemble_kernel<decltype(loss)::value, DirectJob>), per_node, dim3(kCovNodeThreads), 0, stream, G, d_en, x,
+                       c.work_stride, 0.0, lambda, kDirectLm, c.dense);
+  });
+  for (const cov::Launch & l : s->launches)
+  {
+    const dim3 grid(l.groups, 1, jobs);
+    switch (l.kind)
+    {
+      case cov::kFactor:
+        hipLaunchKernelGGL(covariance_factor_kernel<DirectJob>, grid, dim3(kCovFactorThreads), 0, stream, n, l.panel, c.dense, c.factor);
+        break;
+      case cov::kSolveBelow:
+        hipLaunchKernelGGL((covariance_solve_kernel<false, DirectJob>), grid, dim3(kWave), 0, stream, n, l.panel, c.dense);
+        break;
+      default:
+        hipLaunchKernelGGL((covariance_update_kernel<false, DirectJob>), grid, dim3(kCovUpdateThreads), 0, stream, n, l.panel, c.dense);
+        break;
+    }
+  }
+  hipLaunchKernelGGL(direct_substitute_kernel, dim3(jobs), dim3(kPgThreads), 0, stream, n, c, rules);
+  pg_dispatch(s->graph, [&](auto, auto loss) {
+    hipLaunchKernelGGL(direct_step_kernel<decltype(loss)::value>, dim3(jobs), dim3(kPgThreads), 0, stream, G, d_en, c, rules);
+  });
+}
+
+// The chunk's states to the host; *iterating: whether a job takes another iteration.
+int direct_fetch_states(ndt2d_direct * s, hipStream_t stream, const DirectChunk & c, size_t jobs, const direct::Rules & rules, bool * iterating)
+{
+  NDT2D_BATCH_HIP(s, hipGetLastError());
+  NDT2D_BATCH_HIP(s, hipMemcpyAsync(s->h_state, c.state, jobs * kDirectLm * sizeof(double), hipMemcpyDeviceToHost, stream));
+  NDT2D_BATCH_HIP(s, hipStreamSynchronize(stream));
+  *iterating = false;
+  for (size_t k = 0; k < jobs; ++k)
+  {
+    direct::State st;
+    std::memcpy(&st, s->h_state + k * kDirectLm, sizeof(st));
+    if (direct::iterating(st, rules)) *iterating = true;
+  }
+  return NDT2D_OK;
+}
+
+// The evaluate kernel's chi2 of the chunk's jobs at poses (posegraph/ndt2d_posegraph.hip's kernel is
+// that unit's own: the constraint's arithmetic is pg_constraint, one thread a constraint).
+__global__ void __launch_bounds__(kPgThreads) direct_chi2_kernel(const PgGraph G, const double * poses, size_t pose_stride, double * chi2,
+                                                                  size_t chi2_stride)
+{
+  const size_t job = blockIdx.x;
+  const double * xs = poses + job * pose_stride;
+  for (uint32_t c = pg_tid(); c < G.m; c += kPgThreads)
+  {
+    double e[3], r[3];
+    chi2[job * chi2_stride + c] = pg_constraint(G, c, xs, nullptr, e, r);
+  }
+}
+
+}  // namespace
+
+}  // namespace ndt2d
+
+using ndt2d::batch_fail;
+
+extern "C" {
+
+int ndt2d_direct_create(ndt2d_posegraph * posegraph, size_t workspace_bytes, ndt2d_direct ** out)
+{
+  NDT2D_C_TRY
+  if (out == nullptr) return NDT2D_ERR_INVALID;
+  *out = nullptr;
+  if (posegraph == nullptr || workspace_bytes == 0) return NDT2D_ERR_INVALID;
+  ndt2d_direct * s = new ndt2d_direct();
+  s->graph = posegraph;
+  s->h = posegraph->h;
+  s->device = posegraph->device;
+  s->workspace_bytes = workspace_bytes;
+  *out = s;
+  return NDT2D_OK;
+  NDT2D_C_CATCH(nullptr)
+}
+
+int ndt2d_direct_destroy(ndt2d_direct * s)
+{
+  NDT2D_C_TRY
+  if (s == nullptr) return NDT2D_ERR_INVALID;
+  ndt2d::batch_drain(s);
+  ndt2d::batch_release(s);
+  if (s->d_workspace != nullptr) (void)hipFree(s->d_workspace);
+  if (s->h_state != nullptr) (void)hipHostFree(s->h_state);
+  delete s;
+  return NDT2D_OK;
+  NDT2D_C_CATCH(nullptr)
+}
+
+const char * ndt2d_direct_last_error(ndt2d_direct * s)
+{
+  return s != nullptr ? s->err.c_str() : "null direct";
+}
+
+int ndt2d_direct_set_timing(ndt2d_direct * s, int enabled)
+{
+  NDT2D_C_TRY
+  return ndt2d::batch_set_timing(s, enabled);
+  NDT2D_C_CATCH(s)
+}
+
+int ndt2d_direct_last_ms(ndt2d_direct * s, float * kernel_ms, float * fetch_ms)
+{
+  NDT2D_C_TRY
+  return ndt2d::batch_last_ms(s, "direct", kernel_ms, fetch_ms);
+  NDT2D_C_CATCH(s)
+}
+
+int ndt2d_direct_solve(ndt2d_direct * s, const uint8_t * enabled, size_t n_jobs, uint32_t max_iterations, double gradient_tolerance,
+                       double function_tolerance, double parameter_tolerance, double * poses_out, double * records_out, double * chi2_out)
+{
+  NDT2D_C_TRY
+  namespace cov = ndt2d::covariance;
+  namespace direct = ndt2d::direct;
+  if (s == nullptr) return NDT2D_ERR_INVALID;
+  if (n_jobs == 0) return NDT2D_OK;
+  const std::string who = "ndt2d_direct_solve: ";
+  if (poses_out == nullptr || records_out == nullptr) return batch_fail(s, NDT2D_ERR_INVALID, who + "null argument");
+  if (!(gradient_tolerance >= 0.0) || !(function_tolerance >= 0.0) || !(parameter_tolerance >= 0.0) || !std::isfinite(gradient_tolerance) ||
+      !std::isfinite(function_tolerance) || !std::isfinite(parameter_tolerance))
+  {
+    return batch_fail(s, NDT2D_ERR_INVALID, who + "a tolerance is negative or not finite");
+  }
+  ndt2d_posegraph * g = s->graph;
+  int rc = ndt2d::direct_from_graph(s, ndt2d::pg_ready(g, "ndt2d_direct_solve"));
+  if (rc != NDT2D_OK) return rc;
+  const size_t n = g->n, m = g->m;
+  if (3 * n > cov::kMaxDim)
+  {
+    return batch_fail(s, NDT2D_ERR_INVALID, who + std::to_string(n) + " poses, a dense matrix holds " + std::to_string(cov::kMaxDim / 3));
+  }
+  const bool loss = g->loss != ndt2d::pg::kLossTrivial;
+  const size_t job_bytes = direct::job_doubles(n, m, loss) * sizeof(double);
+  const size_t chunk = cov::chunk_jobs(g->max_jobs, s->workspace_bytes, job_bytes);
+  if (chunk == 0)
+  {
+    return batch_fail(s, NDT2D_ERR_INVALID, who + "a job of " + std::to_string(n) + " poses needs " + std::to_string(job_bytes) +
+                                              " bytes, the workspace is " + std::to_string(s->workspace_bytes));
+  }
+  NDT2D_BATCH_HIP(s, hipSetDevice(s->device));
+  hipStream_t stream = static_cast<hipStream_t>(ndt2d_get_stream(s->h));
+  rc = ndt2d::direct_from_graph(s, ndt2d::pg_send_weights(g, stream));
+  if (rc != NDT2D_OK) return rc;
+  rc = ndt2d::direct_from_graph(s, ndt2d::pg_send_loss(g, stream));
+  if (rc != NDT2D_OK) return rc;
+  const ndt2d::PgGraph G = ndt2d::pg_device_graph(g);
+  const ndt2d::PgRules rules{max_iterations, gradient_tolerance, function_tolerance, parameter_tolerance};
+  const direct::Rules lm{max_iterations, gradient_tolerance, function_tolerance, parameter_tolerance};
+  // the workspace: what the call's largest chunk needs, never more than the budget
+  const size_t held = std::min(chunk, n_jobs), need = held * job_bytes;
+  if (need > s->workspace_cap)
+  {
+    if (s->d_workspace != nullptr) (void)hipFree(s->d_workspace);
+    s->d_workspace = nullptr;
+    s->workspace_cap = 0;
+    NDT2D_BATCH_HIP(s, hipMalloc(&s->d_workspace, need));
+    s->workspace_cap = need;
+  }
+  if (held * ndt2d::kDirectLm > s->state_cap)
+  {
+    if (s->h_state != nullptr) (void)hipHostFree(s->h_state);
+    s->h_state = nullptr;
+    s->state_cap = 0;
+    NDT2D_BATCH_HIP(s, hipHostMalloc(reinterpret_cast<void **>(&s->h_state), held * ndt2d::kDirectLm * sizeof(double), hipHostMallocDefault));
+    s->state_cap = held * ndt2d::kDirectLm;
+  }
+  // the factor's launches: those in front of the first of the inversion
+  s->launches.resize(cov::launch_list(3 * n, nullptr));
+  (void)cov::launch_list(3 * n, s->launches.data());
+  size_t factor_launches = 0;
+  while (factor_launches < s->launches.size() && s->launches[factor_launches].kind <= cov::kUpdate) ++factor_launches;
+  s->launches.resize(factor_launches);
+  // the regions of the workspace: [held] dense | work | state | the factor's records
+  ndt2d::DirectChunk c{};
+  c.dense = static_cast<double *>(s->d_workspace);
+  c.work = c.dense + held * direct::dense_doubles(n);
+  c.work_stride = direct::work_doubles(n, m, loss);
+  c.work_front = loss ? m : 0;
+  c.state = c.work + held * c.work_stride;
+  c.factor = c.state + held * ndt2d::kDirectLm;
+  for (size_t k0 = 0; k0 < n_jobs; k0 += chunk)
+  {
+    const size_t k1 = std::min(n_jobs, k0 + chunk), kc = k1 - k0;
+    const uint32_t jobs = static_cast<uint32_t>(kc);
+    const uint8_t * d_en = nullptr;
+    rc = ndt2d::direct_from_graph(s, ndt2d::pg_send_masks(g, stream, enabled, k0, k1, &d_en));
+    if (rc != NDT2D_OK) return rc;
+    // what comes back: [poses kc n 3 | records kc 8 | chi2 kc 2 m (start, end)]
+    const size_t at_rec = kc * n * 3, at_chi2 = at_rec + kc * ndt2d::kDirectRec;
+    const size_t total = at_chi2 + (chi2_out != nullptr ? kc * 2 * m : 0);
+    NDT2D_BATCH_HIP(s, ndt2d::grow_pair(&s->h_out, &s->d_out, &s->out_cap, total));
+    rc = ndt2d::batch_round_trip(s, stream, total, [&]() -> int {
+      if (chi2_out != nullptr)
+      {
+        hipLaunchKernelGGL(ndt2d::direct_chi2_kernel, dim3(jobs), dim3(ndt2d::kPgThreads), 0, stream, G, G.poses, size_t(0), s->d_out + at_chi2,
+                           2 * m);
+      }
+      ndt2d::pg_dispatch(g, [&](auto, auto loss_kind) {
+        hipLaunchKernelGGL(ndt2d::direct_begin_kernel<decltype(loss_kind)::value>, dim3(jobs), dim3(ndt2d::kPgThreads), 0, stream, G, d_en, c,
+                           rules);
+      });
+      bool iterating = false;
+      int rc_fetch = ndt2d::direct_fetch_states(s, stream, c, kc, lm, &iterating);
+      if (rc_fetch != NDT2D_OK) return rc_fetch;
+      for (uint32_t it = 0; it < max_iterations && iterating; ++it)
+      {
+        ndt2d::direct_iteration(s, stream, G, d_en, c, jobs, rules);
+        rc_fetch = ndt2d::direct_fetch_states(s, stream, c, kc, lm, &iterating);
+        if (rc_fetch != NDT2D_OK) return rc_fetch;
+      }
+      hipLaunchKernelGGL(ndt2d::direct_finish_kernel, dim3(jobs), dim3(ndt2d::kDirectFinishThreads), 0, stream, static_cast<uint32_t>(n), c,
+                         s->d_out, s->d_out + at_rec);
+      if (chi2_out != nullptr)
+      {
+        NDT2D_BATCH_HIP(s, hipGetLastError());
+        hipLaunchKernelGGL(ndt2d::direct_chi2_kernel, dim3(jobs), dim3(ndt2d::kPgThreads), 0, stream, G, s->d_out, 3 * n, s->d_out + at_chi2 + m,
+                           2 * m);
+      }
+      return NDT2D_OK;
+    });
+    if (rc != NDT2D_OK) return rc;
+    std::memcpy(poses_out + k0 * n * 3, s->h_out, kc * n * 3 * sizeof(double));
+    std::memcpy(records_out + k0 * ndt2d::kDirectRec, s->h_out + at_rec, kc * ndt2d::kDirectRec * sizeof(double));
+    if (chi2_out != nullptr && m != 0) std::memcpy(chi2_out + k0 * 2 * m, s->h_out + at_chi2, kc * 2 * m * sizeof(double));
+  }
+  return NDT2D_OK;
+  NDT2D_C_CATCH(s)
+}
+
+}  // extern "C"

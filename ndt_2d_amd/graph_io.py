@@ -288,17 +288,21 @@ class Graph:
         return [i for _, i in found]
 
     # src/ceres_solver.cpp:50-120
-    def optimize(self, matcher, loss=None, loss_scale=1.0, loss_on="switchable", **kw):
+    def optimize(self, matcher, loss=None, loss_scale=1.0, loss_on="switchable", method="cg", **kw):
         """CeresSolver::optimize(constraints, scans) on the device (pose_graph.PoseGraph): the
         poses are taken from the scans, scans[0] is held, one job with every constraint on is
         solved, and the poses are written back unless the solve FAILED.  kw: PoseGraph.optimize's
         tolerances, `weighting` and `preconditioner` ("jacobi", the default, or "chain").  loss: None (the reference passes no loss
         function), "huber" or "cauchy" at loss_scale, applied to the constraints loss_on says (PoseGraph.set_loss: "switchable", the
         closures, by default); `last_optimize` then has the weights rho' of the constraints at the solution.  Returns whether the solution is usable -- False for no scans,
-        as the reference; `last_optimize` keeps the job's record."""
+        as the reference; `last_optimize` keeps the job's record.
+        method: "cg" (the default: PoseGraph.optimize, LM with a preconditioned CG inside) or "direct" (PoseGraph.optimize_direct: the
+        same LM rules with an exact step on a dense Cholesky, whose cost does not depend on the closures; kw may carry workspace_bytes)."""
         from . import _capi
         from .pose_graph import PoseGraph
         self.last_optimize = None
+        if method not in ("cg", "direct"):
+            raise ValueError("optimize: method = %r (\"cg\" or \"direct\")" % (method,))
         if not self.scans:
             return False
         weighting = kw.pop("weighting", "reference")
@@ -310,7 +314,7 @@ class Graph:
             if loss is not None:
                 pg.set_loss(loss, loss_scale, loss_on)
             pg.set_graph(np.array([s.pose for s in self.scans], dtype=np.float64), self.constraints, fixed=0)
-            result = pg.optimize(**kw)[0]
+            result = (pg.optimize_direct(**kw) if method == "direct" else pg.optimize(**kw))[0]
         finally:
             pg.close()
         self.last_optimize = result

@@ -35,6 +35,10 @@ struct PoseGraphRecord
   int status = NDT2D_POSEGRAPH_FAILED;   // NDT2D_POSEGRAPH_*
   std::uint32_t iterations = 0, cg_iterations = 0;
   double initial_cost = 0.0, final_cost = 0.0, gradient = 0.0;
+  // of the "direct" solver (cg_iterations is then 0): steps not taken, factorisations that failed
+  // among them, the smallest pivot ratio of the last successful factorisation
+  std::uint32_t rejected = 0, not_positive_definite = 0;
+  double pivot_ratio = 0.0;
   bool usable() const { return status != NDT2D_POSEGRAPH_FAILED; }
 };
 
@@ -47,6 +51,7 @@ public:
   ~PoseGraphHip()
   {
     dropCovariance();
+    dropDirect();
     if (pg_ != nullptr) ndt2d_posegraph_destroy(pg_);
   }
 
@@ -64,6 +69,22 @@ public:
   // "jacobi" (the default) or "chain": the block-tridiagonal band of H + lambda D along the scans'
   // order, for the mapper's graphs (odometry between consecutive scans, a few closures).
   void setPreconditioner(const std::string & preconditioner) { preconditioner_ = preconditioner; }
+  // What optimize() solves with: "cg" (the default: ndt2d_posegraph_solve, LM with a preconditioned CG
+  // inside) or "direct" (ndt2d_direct_solve: the same LM rules with an exact step on a dense
+  // Cholesky, whose cost does not depend on the closures; workspace_bytes: the device memory a
+  // chunk's jobs may take, one 3n x 3n matrix of doubles a job).  false: another name (last_error()).
+  // consistency() keeps the CG solver.
+  bool setSolver(const std::string & solver, std::size_t workspace_bytes = std::size_t(1) << 30)
+  {
+    if (solver != "cg" && solver != "direct")
+    {
+      error_ = "setSolver: \"" + solver + "\" (\"cg\" or \"direct\")";
+      return false;
+    }
+    direct_solver_ = solver == "direct";
+    direct_workspace_ = workspace_bytes;
+    return true;
+  }
   // "trivial" (the default: the reference passes no loss function), "huber" or "cauchy" at `scale`,
   // applied to the switchable constraints (the closures): a gross outlier among them has almost no
   // pull on the poses.  The costs of the record are then the robust ones.
@@ -86,13 +107,20 @@ public:
     if (!upload(poses_xyt, n, begin, end, transform, information, m, 1)) return false;
     if (robust.size() == m && m != 0 && !ok(ndt2d_robust_select(pg_, robust.data(), m))) return false;
     out_.assign(3 * n, 0.0);
-    double rec[NDT2D_POSEGRAPH_RECORD_DOUBLES];
-    if (!ok(ndt2d_posegraph_solve(pg_, nullptr, 1, max_iterations_, gradient_tolerance_, function_tolerance_, parameter_tolerance_,
-                                  out_.data(), rec, nullptr)))
+    if (direct_solver_)
     {
-      return false;
+      if (!solveDirect()) return false;
     }
-    record_ = unpack(rec);
+    else
+    {
+      double rec[NDT2D_POSEGRAPH_RECORD_DOUBLES];
+      if (!ok(ndt2d_posegraph_solve(pg_, nullptr, 1, max_iterations_, gradient_tolerance_, function_tolerance_, parameter_tolerance_,
+                                    out_.data(), rec, nullptr)))
+      {
+        return false;
+      }
+      record_ = unpack(rec);
+    }
     if (!record_.usable()) return false;   // `if (!summary.IsSolutionUsable()) return false;`
     for (std::size_t i = 0; i < 3 * n; ++i) poses_xyt[i] = out_[i];
     return true;
@@ -331,7 +359,8 @@ private:
   {
     if (pg_ == nullptr || n > max_nodes_ || m > max_constraints_ || jobs > max_jobs_)
     {
-      dropCovariance();   // (it refers to the object that goes)
+      dropCovariance();   // (they refer to the object that goes)
+      dropDirect();
       if (pg_ != nullptr) ndt2d_posegraph_destroy(pg_);
       pg_ = nullptr;
       max_nodes_ = n > 2 * max_nodes_ ? n : 2 * max_nodes_;
@@ -364,6 +393,47 @@ private:
     return r;
   }
 
+  // One job, every constraint on, by ndt2d_direct_solve into out_ and record_.
+  bool solveDirect()
+  {
+    if (direct_ == nullptr || direct_bytes_ != direct_workspace_)
+    {
+      dropDirect();
+      const int rc = ndt2d_direct_create(pg_, direct_workspace_, &direct_);
+      if (rc != NDT2D_OK)
+      {
+        error_ = "ndt2d error " + std::to_string(rc) + ": ndt2d_direct_create";
+        return false;
+      }
+      direct_bytes_ = direct_workspace_;
+    }
+    double rec[NDT2D_DIRECT_RECORD_DOUBLES];
+    const int rc = ndt2d_direct_solve(direct_, nullptr, 1, max_iterations_, gradient_tolerance_, function_tolerance_, parameter_tolerance_,
+                                      out_.data(), rec, nullptr);
+    if (rc != NDT2D_OK)
+    {
+      error_ = std::string("ndt2d error ") + std::to_string(rc) + ": " + ndt2d_direct_last_error(direct_);
+      return false;
+    }
+    PoseGraphRecord r;
+    r.status = static_cast<int>(rec[0]);
+    r.iterations = static_cast<std::uint32_t>(rec[1]);
+    r.rejected = static_cast<std::uint32_t>(rec[2]);
+    r.not_positive_definite = static_cast<std::uint32_t>(rec[3]);
+    r.initial_cost = rec[4];
+    r.final_cost = rec[5];
+    r.gradient = rec[6];
+    r.pivot_ratio = rec[7];
+    record_ = r;
+    return true;
+  }
+
+  void dropDirect()
+  {
+    if (direct_ != nullptr) ndt2d_direct_destroy(direct_);
+    direct_ = nullptr;
+  }
+
   void dropCovariance()
   {
     if (cov_ != nullptr) ndt2d_covariance_destroy(cov_);
@@ -381,6 +451,9 @@ private:
   ndt2d_posegraph * pg_ = nullptr;
   ndt2d_covariance * cov_ = nullptr;   // made at the first covariances(), destroyed before pg_
   std::size_t cov_bytes_ = 0;
+  ndt2d_direct * direct_ = nullptr;    // made at the first optimize() under "direct", destroyed before pg_
+  std::size_t direct_bytes_ = 0, direct_workspace_ = std::size_t(1) << 30;
+  bool direct_solver_ = false;
   double pivot_ratio_ = 0.0;
   std::size_t max_nodes_ = 0, max_constraints_ = 0, max_jobs_ = 1;
   std::uint32_t max_iterations_ = 100;

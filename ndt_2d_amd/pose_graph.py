@@ -17,6 +17,7 @@ from ._capi import Ndt2dError, dptr
 from .graph_io import Constraint
 
 DEFAULT_COVARIANCE_WORKSPACE = 1 << 30   # bytes of the dense covariance's workspace: 2,700 poses a job
+DEFAULT_DIRECT_WORKSPACE = 1 << 30       # bytes of the direct solve's workspace: 3,800 poses a job
 DEFAULT_TOLERANCES = dict(max_iterations=100, gradient_tolerance=1e-10, function_tolerance=1e-6, parameter_tolerance=1e-8)
 
 
@@ -129,6 +130,8 @@ class PoseGraph:
         self._timing = False
         self._cov = None           # the dense covariance's object (covariances), made at its first call
         self._cov_bytes = 0
+        self._direct = None        # the direct solve's object (optimize_direct), made at its first call
+        self._direct_bytes = 0
         self.n = self.m = 0
         self.switchable = np.zeros(0, dtype=bool)
         self._create(int(max_nodes), int(max_constraints), int(max_jobs))
@@ -138,6 +141,7 @@ class PoseGraph:
         self._matcher._dev_check(self._L.ndt2d_posegraph_create(self._matcher.device_handle, max_nodes, max_constraints, max_jobs, C.byref(p)),
                                  "ndt2d_posegraph_create")
         self._close_covariance()   # (it refers to the object that goes)
+        self._close_direct()
         old, self._p = self._p, p
         if old:
             self._L.ndt2d_posegraph_destroy(old)
@@ -154,8 +158,14 @@ class PoseGraph:
             self._L.ndt2d_covariance_destroy(self._cov)
         self._cov = None
 
+    def _close_direct(self):
+        if getattr(self, "_direct", None):
+            self._L.ndt2d_direct_destroy(self._direct)
+        self._direct = None
+
     def close(self):
         self._close_covariance()
+        self._close_direct()
         if getattr(self, "_p", None):
             self._L.ndt2d_posegraph_destroy(self._p)
             self._p = None
@@ -312,6 +322,59 @@ class PoseGraph:
                 out[-1]["weights"] = weights[k]
         return out
 
+    def optimize_direct(self, masks=None, workspace_bytes=DEFAULT_DIRECT_WORKSPACE, **tolerances):
+        """optimize's problem, LM rules, arguments and tolerances with an exact linear step (include/ndt2d_hip.h,
+        "Direct solve"): H_FF + lambda D assembled densely, factored by the dense covariance's blocked Cholesky, and
+        L L^T delta = -g by substitution -- a cost per iteration that does not depend on the closures.  workspace_bytes:
+        the device memory the jobs of a chunk may take (one 3n x 3n matrix of doubles a job); the object is made at the
+        first call and again when this changes.  Returns optimize's dicts with rejected (steps not taken),
+        not_positive_definite (factorisations that failed, counted among them) and pivot_ratio (of the last successful
+        factorisation) in place of cg_iterations; weights [m] under a loss."""
+        unknown = set(tolerances) - set(DEFAULT_TOLERANCES)
+        if unknown:
+            raise TypeError("optimize_direct: unknown argument(s) %s" % sorted(unknown))
+        tol = dict(DEFAULT_TOLERANCES, **tolerances)
+        en, K = self._masks(masks)
+        if self._direct is None or self._direct_bytes != int(workspace_bytes):
+            self._close_direct()
+            p = C.c_void_p()
+            rc = self._L.ndt2d_direct_create(self._p, int(workspace_bytes), C.byref(p))
+            if rc != _capi.OK:
+                raise Ndt2dError(rc, "ndt2d_direct_create", "workspace_bytes = %d" % int(workspace_bytes))
+            self._direct, self._direct_bytes = p, int(workspace_bytes)
+            if self._timing:
+                self._L.ndt2d_direct_set_timing(self._direct, 1)
+        poses = np.zeros((K, self.n, 3))
+        records = np.zeros((K, _capi.DIRECT_RECORD_DOUBLES))
+        chi2 = np.zeros((K, 2, self.m))
+        rc = self._L.ndt2d_direct_solve(self._direct, self._u8(en), K, int(tol["max_iterations"]), float(tol["gradient_tolerance"]),
+                                        float(tol["function_tolerance"]), float(tol["parameter_tolerance"]), dptr(poses), dptr(records),
+                                        dptr(chi2))
+        if rc != _capi.OK:
+            msg = self._L.ndt2d_direct_last_error(self._direct)
+            raise Ndt2dError(rc, "ndt2d_direct_solve", msg.decode() if msg else "")
+        weights = self._weights(chi2[:, 1]) if self._loss[0] != "trivial" else None
+        out = []
+        for k in range(K):
+            status = int(records[k, 0])
+            out.append(dict(poses=poses[k].copy(), status=status, status_name=_capi.POSEGRAPH_STATUS_NAMES[status],
+                            iterations=int(records[k, 1]), rejected=int(records[k, 2]), not_positive_definite=int(records[k, 3]),
+                            initial_cost=float(records[k, 4]), final_cost=float(records[k, 5]), gradient=float(records[k, 6]),
+                            pivot_ratio=float(records[k, 7]), chi2_start=chi2[k, 0].copy(), chi2=chi2[k, 1].copy()))
+            if weights is not None:
+                out[-1]["weights"] = weights[k]
+        return out
+
+    def direct_last_ms(self):
+        """(kernel_ms, fetch_ms) of the last optimize_direct call's last chunk (set_timing(True)): its iterations with the
+        read-backs between them, and its final read-back."""
+        a, b = C.c_float(0.0), C.c_float(0.0)
+        rc = self._L.ndt2d_direct_last_ms(self._direct, C.byref(a), C.byref(b))
+        if rc != _capi.OK:
+            msg = self._L.ndt2d_direct_last_error(self._direct)
+            raise Ndt2dError(rc, "ndt2d_direct_last_ms", msg.decode() if msg else "")
+        return a.value, b.value
+
     def marginals(self, nodes, masks=None, poses=None, damping=0.0, tolerance=1e-10, max_cg_iterations=0, want_columns=False):
         """Block columns of (H_FF + damping clamp(diag H_FF))^-1 for the query `nodes` [Q]
         (include/ndt2d_hip.h, "Marginal covariances"): one job per mask (None: one job, every
@@ -436,6 +499,8 @@ class PoseGraph:
         self._check(self._L.ndt2d_posegraph_set_timing(self._p, 1 if enabled else 0), "ndt2d_posegraph_set_timing")
         if self._cov is not None:
             self._L.ndt2d_covariance_set_timing(self._cov, 1 if enabled else 0)
+        if self._direct is not None:
+            self._L.ndt2d_direct_set_timing(self._direct, 1 if enabled else 0)
         self._timing = bool(enabled)
 
     def last_ms(self):
