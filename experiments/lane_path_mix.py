@@ -31,8 +31,10 @@ P = {
                                     ("v_cmp_le_u32 vcc", 1)],
     # a group some lane of which is live: every beam's live test
     "live_group (8 live tests)": [("v_cmp_le_u32 vcc", 8)],
-    # a beam with a live lane: near-boundary tests (x, y), occupancy
-    "live_beam": [("v_cmp_gt_u16 vcc", 2), ("v_perm_b32", 1), ("v_and_b32", 1), ("v_cmp_le_u32 vcc", 1)],
+    # a beam with a live lane: the live test's mask, occupancy
+    "live_beam": [("v_and_b32", 1), ("v_cmp_le_u32 vcc", 1)],
+    # ... whose near-possible bit is set (the table's near_bits word): near-boundary tests (x, y)
+    "near_test": [("v_cmp_gt_u16 vcc", 2), ("v_perm_b32", 1)],
     # exact evaluation, interior of a cell: points_inner, look-up cell -> rank -> record, Cell::score's exponent, test
     "exact_evaluation": [("v_add_f64", 2),
                          ("v_lshrrev_b32_sdwa", 2), ("v_mul_u32_u24", 1), ("v_add3_u32", 1), ("v_cndmask_b32 sgpr", 1),
@@ -58,6 +60,7 @@ execs = {
     "lookup_group (per 8 beams)": n["beams_in_lookup_groups"] / 8.0,
     "live_group (8 live tests)": n["groups_with_a_live_lane"],
     "live_beam": n["beams_with_a_live_lane"],
+    "near_test": n["live_beams_near_possible"],
     "exact_evaluation": n["exact_evaluations"],
     "reference_index (extra)": n["evaluations_by_reference_index"],
     "exp_and_add": n["evaluations_with_exp"],

@@ -8,6 +8,7 @@
 #include <cmath>
 
 #include "ndt2d_device_fn.h"
+#include "ndt2d_near_bits.h"
 
 namespace ndt2d
 {
@@ -20,11 +21,15 @@ constexpr int kPatch = 8;            // patch is kPatch x kPatch candidates = on
 #define NDT2D_LANE_UNROLL 8
 #endif
 constexpr int kUnroll = NDT2D_LANE_UNROLL;  // beams per look-up group (a divisor of 64)
+// A/B switch of the beam table's near_bits word (profiles/near_bits_ab.json); =0 is
+// the code as it was: the near-boundary test of every live beam.
+#ifndef NDT2D_LANE_NEAR_BITS
+#define NDT2D_LANE_NEAR_BITS 1
+#endif
 // map coordinates are 8.16 fixed point
 constexpr double kFracScale = 65536.0;
 constexpr int kMapStride = 256;      // map row stride in bytes = 2^8 cells
 constexpr int kMaxMapCells = 256;    // cell coordinate is one byte
-constexpr uint32_t kNearUnits = 4;   // guard band around cell boundaries, in 2^-16 cells
 // widening of a map sub-cell's box (fraction of a sub-cell) when its exponent bound
 // is taken: 16 x the rounding of the fixed-point coordinate that selects it
 constexpr double kBoxMargin = 1.0 / 1024.0;
@@ -35,7 +40,7 @@ constexpr double kTwo52 = 4503599627370496.0;
 // box (widened by kBoxMargin = 64 units) holds the lane's point just as well, and such a
 // lane is "near" -- it takes the reference's own index arithmetic, not the look-up's cell.
 constexpr double kNearBias = kNearUnits * (kTwo24 + 1.0);
-static_assert(kNearUnits == 4, "near_boundary() tests the biased fraction against 2 * kNearUnits");
+static_assert(kNearUnits == 4 && kNearPatch == kPatch, "near_boundary() tests the biased fraction against 2 * kNearUnits");
 
 struct LaneGeom
 {
@@ -68,6 +73,16 @@ struct LaneGeom
   int32_t strips;
   int32_t strip_span_long, strip_span_short;
 };
+
+// Does the beam table's near_bits word (ndt2d_near_bits.h) say anything for this search?  Not
+// without a pre-test (nothing reads it), in the control mode or on a map coarser than the grid
+// (every lane counts as near), or for a lattice of more columns than the word has bits: the
+// pre-kernel then writes all ones and the launcher takes the kernels that do not read the word.
+__host__ __device__ inline bool lane_reads_near_bits(const LaneGeom & geo, uint32_t n_lin)
+{
+  return NDT2D_LANE_NEAR_BITS != 0 && geo.box_span >= 0 && geo.no_skip == 0 && geo.block_log2 == 0 && n_lin > 0u &&
+         n_lin <= kNearPatch * kNearColumns;
+}
 
 constexpr int kMaxBoxSpan = 3;   // the pre-test reads a 4 x 4 sub-cell box
 constexpr int kMaxStripSpan = 7; // ... and an 8 x 8 box for a strip tile
@@ -389,6 +404,7 @@ __device__ double * g_lane_hist = nullptr;   // set by the kernel from MatchArgs
 //   [205] exact evaluations      [206] ... through the reference's index arithmetic (a lane near a boundary)
 //   [207] evaluations that needed exp()   [208] skip-state refreshes   [209] items reduced (some sum != 0)
 //   [210] single beams through the U = 1 form
+//   [211] beams with a live lane whose near-possible bit is set (the per-lane near test runs)
 #ifdef NDT2D_LANE_PATHS
 #define NDT2D_PATH(slot, amount)                                                              \
   do {                                                                                        \
@@ -544,11 +560,14 @@ __device__ __forceinline__ SkipState skip_state(double sum, int32_t no_skip)
 // (the small search broadcasts them from LDS).
 // COMPACT (with LDS_RECORDS): the LDS records are the compacted ones, addressed through
 // the cell -> record table at c.rank_address (uint16 per grid cell, also in LDS).
+// near_possible: bit u says that beam u may have a lane near a cell boundary (near_bits() of
+// the large search's table, a wave-uniform value); a beam whose bit is clear has none, and its
+// per-lane near test is not run.  Callers without such a table pass all ones.
 template <int U, bool POW2, bool LDS_RECORDS, bool SCALAR_ROWS = true, bool COMPACT = false>
 __device__ __forceinline__ void lane_beams(const GridDesc & g, const LaneCtx & c,
                                            const double4 (&o)[U], double dx, double dy,
                                            double dxy, double & sum, SkipState & skip,
-                                           int32_t no_skip)
+                                           int32_t no_skip, uint32_t near_possible = ~0u)
 {
   const double skip_below = skip.skip_below;
   const uint32_t skip_level = skip.skip_level;
@@ -593,10 +612,17 @@ __device__ __forceinline__ void lane_beams(const GridDesc & g, const LaneCtx & c
         // come with both 16-bit fractions biased by kNearUnits (see kNearBias), so that is
         // (frac + 4) mod 2^16 < 8, a 16-bit compare per axis; the y fraction straddles
         // the two words (bytes 3, 4)
-        const uint32_t fy = __builtin_amdgcn_perm(hi[u], lo[u], 0x0c0c0403u);
+        // (a clear near-possible bit: no lane of the patch is; the control mode and the coarse
+        // maps, whose every lane counts as near, come with all bits set)
         const bool occ = (m[u] & 1u) != 0;
-        const uint64_t near_mask =
-          (near_boundary(lo[u]) | near_boundary(fy) | ((no_skip | c.exact_index) != 0 ? ~0ull : 0ull)) & live_mask;
+        uint64_t near_mask = 0ull;
+        if (!NDT2D_LANE_NEAR_BITS || ((near_possible >> u) & 1u) != 0u)
+        {
+          NDT2D_PATH(211, 1);
+          const uint32_t fy = __builtin_amdgcn_perm(hi[u], lo[u], 0x0c0c0403u);
+          near_mask =
+            (near_boundary(lo[u]) | near_boundary(fy) | ((no_skip | c.exact_index) != 0 ? ~0ull : 0ull)) & live_mask;
+        }
         const uint64_t occ_lanes = __builtin_amdgcn_ballot_w64(occ);
         const uint64_t occ_mask = occ_lanes & live_mask;
 #ifdef NDT2D_LANE_NO_EXACT

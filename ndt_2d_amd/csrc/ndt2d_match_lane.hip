@@ -45,7 +45,10 @@
 // change its sum (RN(s + exp(e)) == s); if every lane's byte is below its level
 // the beam is skipped.  Otherwise lanes within 4 fixed-point units of a boundary
 // are "near" (K carries a bias of 4 units on both fractions, so the test is a 16-bit
-// compare per axis); if any live lane is occupied or near, the wave runs the exact
+// compare per axis -- run only for a beam whose near_bits word in the table, made by the
+// pre-kernel from the integers K and D alone, says that a lane of the tile's column or row can
+// be near at all: one live beam in fifteen at cfg-2); if any live lane is occupied or near, the
+// wave runs the exact
 // reference arithmetic (points_inner :121-125, NDT::getIndex
 // src/ndt_model.cpp:203-218 for near lanes, Cell::score :105-116).  Every
 // skipped term is one that leaves the sum unchanged, so the sums are
@@ -75,7 +78,7 @@ constexpr int kLaneThreadsCompact = NDT2D_LANE_THREADS_COMPACT; // compacted rec
 
 // points_outer for the slab (reference :106-115) plus the packed fixed-point
 // map coordinate of each rotated beam:
-//   outer[t][b] = {ox, oy, K, 0},   K = 2^52 + ky * 2^24 + kx (+ kNearBias),
+//   outer[t][b] = {ox, oy, K, near_bits},   K = 2^52 + ky * 2^24 + kx (+ kNearBias),
 //   k = rint(((o - origin) * inv_cell - window_origin + pad) * 2^16) clamped to [k_min, k_max]
 // so that k + d stays inside the map for every lane offset d.  A clamped beam
 // is further outside the grid than any offset can bring back; it stays in the
@@ -142,13 +145,49 @@ __global__ void __launch_bounds__(256) outer_table_kernel(const MatchArgs a, dou
 #if NDT2D_LANE_TABLE_2D
   if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < kItemShards) a.next_item[threadIdx.x * kItemShardStride] = 0u;
   if (blockIdx.y < map_rows) return;
+#else
+  if (blockIdx.x == 0 && threadIdx.x < kItemShards) a.next_item[threadIdx.x * kItemShardStride] = 0u;
+#endif
+  // The table's fourth word: near_bits() of the beam (ndt2d_near_bits.h), from the 16-bit
+  // fractions of the lattice's offsets, which the block makes once.  Where no search reads the
+  // word (no pre-test) or every lane counts as near (the control mode, a map coarser than the
+  // grid), and for a lattice of more columns than the word has bits: all ones.
+  __shared__ uint16_t offset_fraction[kNearPatch * kNearColumns];
+  __shared__ int32_t offset_range[2];
+  const bool near_all = !lane_reads_near_bits(geo, a.n_lin);
+  if (!near_all)
+  {
+    if (threadIdx.x == 0)
+    {
+      offset_range[0] = INT32_MAX;
+      offset_range[1] = INT32_MIN;
+    }
+    __syncthreads();
+    // (256 threads, at most 256 steps; the steps behind n_lin repeat the last one, as shadow lanes do)
+    const uint32_t step = min(threadIdx.x, a.n_lin - 1u);
+    const int32_t units = static_cast<int32_t>(near_offset_units(a.dlin[step], geo.inv_scaled));
+    offset_fraction[threadIdx.x] = static_cast<uint16_t>(static_cast<uint32_t>(units));
+    int32_t least = units, greatest = units;
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1)
+    {
+      least = min(least, __shfl_xor(least, off));
+      greatest = max(greatest, __shfl_xor(greatest, off));
+    }
+    if ((threadIdx.x & (kWave - 1)) == 0)
+    {
+      atomicMin(&offset_range[0], least);
+      atomicMax(&offset_range[1], greatest);
+    }
+    __syncthreads();
+  }
+#if NDT2D_LANE_TABLE_2D
   const uint32_t b = blockIdx.x * 256 + threadIdx.x;
   if (b >= a.n_beams) return;
   for (uint32_t t = blockIdx.y - map_rows; t < a.th_end - a.th_begin; t += gridDim.y - map_rows)
   {
     const uint64_t i = static_cast<uint64_t>(t) * a.n_beams + b;
 #else
-  if (blockIdx.x == 0 && threadIdx.x < kItemShards) a.next_item[threadIdx.x * kItemShardStride] = 0u;
   const uint64_t n = static_cast<uint64_t>(a.th_end - a.th_begin) * a.n_beams;
   for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x; i < n;
        i += static_cast<uint64_t>(gridDim.x) * 256)
@@ -169,7 +208,11 @@ __global__ void __launch_bounds__(256) outer_table_kernel(const MatchArgs a, dou
     kx = !(kx >= geo.k_min) ? geo.k_min : (kx > geo.k_max_x ? geo.k_max_x : kx);
     ky = !(ky >= geo.k_min) ? geo.k_min : (ky > geo.k_max_y ? geo.k_max_y : ky);
     o.z = kTwo52 + (rint(ky) * kTwo24 + rint(kx)) + kNearBias;
-    o.w = 0.0;
+    const uint64_t k48 = static_cast<uint64_t>(__double_as_longlong(o.z)) & ((1ull << 48) - 1ull);
+    const uint64_t bits = near_all ? kNearAll
+                                   : near_bits(k48, static_cast<const uint16_t *>(offset_fraction), a.n_lin,
+                                               offset_range[0], offset_range[1]);
+    o.w = __longlong_as_double(static_cast<long long>(bits));
     outer[i] = o;
   }
 }
@@ -214,8 +257,10 @@ __device__ __forceinline__ double no_index_here()
   return __hiloint2double(static_cast<int>(hi), static_cast<int>(lo));
 }
 
+// NEAR: the search reads the table's near_bits word (lane_reads_near_bits(): the launcher picks
+// the instantiation); false is the search as it was, every live beam takes the per-lane near test.
 template <int THREADS, bool POW2, bool LDS_RECORDS, bool DYNAMIC_ITEMS, bool COMPACT, bool PARTS = false,
-          bool STRIPS = false>
+          bool STRIPS = false, bool NEAR = false>
 __device__ __forceinline__ void match_lane_body(
   const MatchArgs & a, const double4 * __restrict__ outer, const uint8_t * __restrict__ map_image,
   const LaneGeom & geo)
@@ -346,6 +391,11 @@ __device__ __forceinline__ void match_lane_body(
       x_end = n_lin;
     }
     const bool strip_tile = STRIPS && p >= tiling.core;
+    // the 8 x 8 tile's two bits of a beam's near_bits word: its patch column, its patch row
+    // (a strip tile has another shape and takes every beam as possibly near)
+    const uint64_t tile_near = !NEAR ? ~0ull
+                                     : (1ull << ((x0 / kPatch) & (kNearColumns - 1u))) |
+                                         (1ull << (kNearColumns + ((y0 / kPatch) & (kNearColumns - 1u))));
     // (lane -> tile position per item, two instructions, rather than two registers held for good)
     uint32_t lane_here = lane;
     asm volatile("" : "+v"(lane_here));
@@ -372,10 +422,24 @@ __device__ __forceinline__ void match_lane_body(
     const uint32_t beams_end = PARTS ? min(beams_begin + a.part_beams, a.n_beams) : a.n_beams;
     for (uint32_t b0 = beams_begin; b0 < beams_end; b0 += kWave)
     {
-      uint64_t can_score = ~0ull;
+      // near_chunk, beside it: the beams that may have a lane near a cell boundary, from the
+      // table's near_bits word and the tile's column and row (all of them without a pre-test)
+      uint64_t can_score = ~0ull, near_chunk = ~0ull;
       if (geo.box_span >= 0)
       {
-        const double k = row[min(b0 + lane, a.n_beams - 1u)].z;
+        // K and (NEAR) the near_bits word behind it: one 16-byte load
+        double k;
+        uint64_t near_word = ~0ull;
+        if (NEAR)
+        {
+          const ulonglong2 kw = *reinterpret_cast<const ulonglong2 *>(&row[min(b0 + lane, a.n_beams - 1u)].z);
+          k = __longlong_as_double(static_cast<long long>(kw.x));
+          near_word = kw.y;
+        }
+        else
+        {
+          k = row[min(b0 + lane, a.n_beams - 1u)].z;
+        }
         if (strip_tile)
         {
           // h < 8: the tile's long side lies along x
@@ -387,6 +451,7 @@ __device__ __forceinline__ void match_lane_body(
         else
         {
           can_score = __builtin_amdgcn_ballot_w64(patch_can_score(k + dxy_corner, geo.box_span));
+          if (NEAR) near_chunk = __builtin_amdgcn_ballot_w64((near_word & tile_near) != 0ull);
         }
         NDT2D_PATH(201, 1);
       }
@@ -395,7 +460,7 @@ __device__ __forceinline__ void match_lane_body(
 #endif
       const uint32_t chunk_end = min(b0 + static_cast<uint32_t>(kWave), beams_end);
       uint32_t b = b0;
-      for (; b + kUnroll <= chunk_end; b += kUnroll, can_score >>= kUnroll)
+      for (; b + kUnroll <= chunk_end; b += kUnroll, can_score >>= kUnroll, near_chunk >>= kUnroll)
       {
         if ((can_score & ((1ull << kUnroll) - 1ull)) == 0ull) continue;
         double4 o[kUnroll];
@@ -406,14 +471,16 @@ __device__ __forceinline__ void match_lane_body(
         // unflagged groups or reducing an item's records are not: issue priority while the
         // group is evaluated (cfg-2: - 3 %).
         __builtin_amdgcn_s_setprio(3);
-        lane_beams<kUnroll, POW2, LDS_RECORDS, true, COMPACT>(g, c, o, dx, dy, dxy, sum, skip, geo.no_skip);
+        lane_beams<kUnroll, POW2, LDS_RECORDS, true, COMPACT>(g, c, o, dx, dy, dxy, sum, skip, geo.no_skip,
+                                                              NEAR ? static_cast<uint32_t>(near_chunk) : ~0u);
         __builtin_amdgcn_s_setprio(0);
       }
-      for (; b < chunk_end; ++b, can_score >>= 1)
+      for (; b < chunk_end; ++b, can_score >>= 1, near_chunk >>= 1)
       {
         if ((can_score & 1ull) == 0ull) continue;
         const double4 one[1] = {row[b]};
-        lane_beams<1, POW2, LDS_RECORDS, true, COMPACT>(g, c, one, dx, dy, dxy, sum, skip, geo.no_skip);
+        lane_beams<1, POW2, LDS_RECORDS, true, COMPACT>(g, c, one, dx, dy, dxy, sum, skip, geo.no_skip,
+                                                        NEAR ? static_cast<uint32_t>(near_chunk) : ~0u);
       }
     }
 
@@ -595,39 +662,41 @@ __global__ void __launch_bounds__(THREADS) match_lane_kernel(
 // The compacted-records form: 768-thread blocks held to 80 VGPRs, two per CU = six waves
 // per SIMD (a block's waves must spread evenly over the four SIMDs: 640-thread blocks
 // would put six waves of two blocks on one SIMD, which its register file cannot hold).
-template <bool STRIPS>
+// NEAR (the six-wave kernels here and below): the near_bits word is read, see match_lane_body.
+template <bool STRIPS, bool NEAR>
 __global__ void __launch_bounds__(kLaneThreadsCompact) __attribute__((amdgpu_waves_per_eu(NDT2D_LANE_COMPACT_WAVES_PER_EU)))
 match_lane_compact_kernel(const MatchArgs a, const double4 * __restrict__ outer,
                           const uint8_t * __restrict__ map_image, const LaneGeom geo)
 {
-  match_lane_body<kLaneThreadsCompact, true, true, true, true, false, STRIPS>(a, outer, map_image, geo);
+  match_lane_body<kLaneThreadsCompact, true, true, true, true, false, STRIPS, NEAR>(a, outer, map_image, geo);
 }
 
 // Maps too large for LDS (records gathered from the 64-byte-stride HBM copy through L2):
 // the LDS image is the occupancy map alone, so two 768-thread blocks fit a CU as well --
 // six waves per SIMD to cover the gathers' latency instead of four.
-template <bool POW2, bool STRIPS>
+template <bool POW2, bool STRIPS, bool NEAR>
 __global__ void __launch_bounds__(kLaneThreadsCompact) __attribute__((amdgpu_waves_per_eu(NDT2D_LANE_COMPACT_WAVES_PER_EU)))
 match_lane_gather6_kernel(const MatchArgs a, const double4 * __restrict__ outer,
                           const uint8_t * __restrict__ map_image, const LaneGeom geo)
 {
-  match_lane_body<kLaneThreadsCompact, POW2, false, true, false, false, STRIPS>(a, outer, map_image, geo);
+  match_lane_body<kLaneThreadsCompact, POW2, false, true, false, false, STRIPS, NEAR>(a, outer, map_image, geo);
 }
 
 // The beam-part forms of the two six-wave kernels (mid-size lattices, MatchArgs::beam_parts).
+template <bool NEAR>
 __global__ void __launch_bounds__(kLaneThreadsCompact) __attribute__((amdgpu_waves_per_eu(NDT2D_LANE_COMPACT_WAVES_PER_EU)))
 match_lane_compact_parts_kernel(const MatchArgs a, const double4 * __restrict__ outer,
                                 const uint8_t * __restrict__ map_image, const LaneGeom geo)
 {
-  match_lane_body<kLaneThreadsCompact, true, true, true, true, true>(a, outer, map_image, geo);
+  match_lane_body<kLaneThreadsCompact, true, true, true, true, true, false, NEAR>(a, outer, map_image, geo);
 }
 
-template <bool POW2>
+template <bool POW2, bool NEAR>
 __global__ void __launch_bounds__(kLaneThreadsCompact) __attribute__((amdgpu_waves_per_eu(NDT2D_LANE_COMPACT_WAVES_PER_EU)))
 match_lane_gather6_parts_kernel(const MatchArgs a, const double4 * __restrict__ outer,
                                 const uint8_t * __restrict__ map_image, const LaneGeom geo)
 {
-  match_lane_body<kLaneThreadsCompact, POW2, false, true, false, true>(a, outer, map_image, geo);
+  match_lane_body<kLaneThreadsCompact, POW2, false, true, false, true, false, NEAR>(a, outer, map_image, geo);
 }
 
 // Second kernel of the beam-part form: a wave per (theta, patch) item, lane = candidate.
@@ -929,11 +998,30 @@ hipError_t launch_match_lane(const MatchArgs & args_in, double * outer, double *
     if (!dynamic_items) return with_items(std::false_type{}, std::false_type{});
     return strips ? with_items(std::true_type{}, std::true_type{}) : with_items(std::true_type{}, std::false_type{});
   };
+  // The six-wave kernels read the table's near_bits word where it says something: the rule the
+  // pre-kernel wrote it by.  Anywhere else they are the kernels they were.
+  auto six_wave = [&](auto near_tag) -> hipError_t {
+    constexpr bool N = decltype(near_tag)::value;
+    if (beam_parts > 1)
+    {
+      return compact ? launch(match_lane_compact_parts_kernel<N>, kLaneThreadsCompact)
+                     : (pow2 ? launch(match_lane_gather6_parts_kernel<true, N>, kLaneThreadsCompact)
+                             : launch(match_lane_gather6_parts_kernel<false, N>, kLaneThreadsCompact));
+    }
+    if (compact)
+    {
+      return strips ? launch(match_lane_compact_kernel<true, N>, kLaneThreadsCompact)
+                    : launch(match_lane_compact_kernel<false, N>, kLaneThreadsCompact);
+    }
+    return pow2 ? (strips ? launch(match_lane_gather6_kernel<true, true, N>, kLaneThreadsCompact)
+                          : launch(match_lane_gather6_kernel<true, false, N>, kLaneThreadsCompact))
+                : (strips ? launch(match_lane_gather6_kernel<false, true, N>, kLaneThreadsCompact)
+                          : launch(match_lane_gather6_kernel<false, false, N>, kLaneThreadsCompact));
+  };
+  const bool near = lane_reads_near_bits(geo, args.n_lin);
   if (beam_parts > 1)
   {
-    e = compact ? launch(match_lane_compact_parts_kernel, kLaneThreadsCompact)
-                : (pow2 ? launch(match_lane_gather6_parts_kernel<true>, kLaneThreadsCompact)
-                        : launch(match_lane_gather6_parts_kernel<false>, kLaneThreadsCompact));
+    e = near ? six_wave(std::true_type{}) : six_wave(std::false_type{});
     if (e == hipSuccess)
     {
       hipLaunchKernelGGL(match_lane_combine_kernel, dim3(static_cast<uint32_t>((n_items + 3) / 4)), dim3(256),
@@ -941,17 +1029,9 @@ hipError_t launch_match_lane(const MatchArgs & args_in, double * outer, double *
       e = hipGetLastError();
     }
   }
-  else if (compact)
+  else if (compact || gather6)
   {
-    e = strips ? launch(match_lane_compact_kernel<true>, kLaneThreadsCompact)
-               : launch(match_lane_compact_kernel<false>, kLaneThreadsCompact);
-  }
-  else if (gather6)
-  {
-    e = pow2 ? (strips ? launch(match_lane_gather6_kernel<true, true>, kLaneThreadsCompact)
-                       : launch(match_lane_gather6_kernel<true, false>, kLaneThreadsCompact))
-             : (strips ? launch(match_lane_gather6_kernel<false, true>, kLaneThreadsCompact)
-                       : launch(match_lane_gather6_kernel<false, false>, kLaneThreadsCompact));
+    e = near ? six_wave(std::true_type{}) : six_wave(std::false_type{});
   }
   else
   {
