@@ -5,7 +5,10 @@
 // beside an ndt2d_posegraph and reads its graph, weighting and loss; the kernels are
 // direct/ndt2d_direct_kernel.h and covariance/ndt2d_covariance_kernel.h, the decisions
 // direct/ndt2d_direct_step.h, a job's doubles direct/ndt2d_direct_plan.h, the panels and the factor's
-// launches covariance/ndt2d_covariance_plan.h.
+// launches covariance/ndt2d_covariance_plan.h, their launch path -- the dense covariance's, on this
+// unit's layout and without the inversion -- covariance/ndt2d_covariance_launch.h.  What an object
+// beside the graph is made of and the prelude of a call are posegraph/ndt2d_posegraph_state.h; what
+// the call refuses about its arguments is posegraph/ndt2d_posegraph_args.h.
 //
 // The host enqueues one iteration's launches for the chunk, reads the jobs' small states back and
 // stops when no job is iterating: one read-back per LM iteration, no waiting on the device.
@@ -20,20 +23,18 @@
 #include "ndt2d_hip.h"
 #include "batch/ndt2d_batch_state.h"
 #include "covariance/ndt2d_covariance_kernel.h"
+#include "covariance/ndt2d_covariance_launch.h"
 #include "covariance/ndt2d_covariance_plan.h"
 #include "direct/ndt2d_direct_kernel.h"
 #include "direct/ndt2d_direct_plan.h"
 #include "direct/ndt2d_direct_step.h"
+#include "posegraph/ndt2d_posegraph_args.h"
 #include "posegraph/ndt2d_posegraph_kernel.h"
 #include "posegraph/ndt2d_posegraph_state.h"
 
-struct ndt2d_direct : ndt2d::BatchHost
+struct ndt2d_direct : ndt2d::PgCompanion
 {
-  ndt2d_posegraph * graph = nullptr;   // (the caller keeps it alive)
-  size_t workspace_bytes = 0;          // the budget
-  // from the first solve on: the chunk's jobs on the device, their states as read back (pinned)
-  void * d_workspace = nullptr;
-  size_t workspace_cap = 0;
+  // from the first solve on: the states of the chunk's jobs as read back (pinned)
   double * h_state = nullptr;
   size_t state_cap = 0;                // doubles
   std::vector<ndt2d::covariance::Launch> launches;   // the factor's part of the plan's list
@@ -45,44 +46,22 @@ namespace ndt2d
 namespace
 {
 
-int direct_from_graph(ndt2d_direct * s, int rc)
-{
-  if (rc != NDT2D_OK) s->err = s->graph->err;
-  return rc;
-}
-
 // One LM iteration of a chunk in stream order: the nodes, the fill, the assembly at each job's
 // lambda, the factor's launches, the substitutions, the step.
 void direct_iteration(const ndt2d_direct * s, hipStream_t stream, const PgGraph & G, const uint8_t * d_en, const DirectChunk & c, uint32_t jobs,
                       const PgRules & rules)
 {
-  const uint32_t n = G.n, ld = static_cast<uint32_t>(cov::padded(3 * static_cast<size_t>(n)));
-  const dim3 per_node((n + kCovNodeThreads - 1) / kCovNodeThreads, 1, jobs);
-  const double * x = c.work + c.work_front;   // (PgWork's x leads a job's node arrays)
-  hipLaunchKernelGGL(covariance_nodes_kernel<DirectJob>, per_node, dim3(kCovNodeThreads), 0, stream, G, d_en, x, c.work_stride, c.dense);
-  hipLaunchKernelGGL(covariance_fill_kernel<DirectJob>, dim3((ld + kCovFillThreads - 1) / kCovFillThreads, ld, jobs), dim3(kCovFillThreads), 0,
-                     stream, n, c.dense);
-  const double * lambda = c.state + offsetof(direct::State, lambda) / sizeof(double);
-  pg_dispatch(s->graph, [&](auto, auto loss) {
-    hipLaunchKernelGGL((covariance_assemble_kernel<decltype(loss)::value, DirectJob>), per_node, dim3(kCovNodeThreads), 0, stream, G, d_en, x,
-                       c.work_stride, 0.0, lambda, kDirectLm, c.dense);
-  });
-  for (const cov::Launch & l : s->launches)
-  {
-    const dim3 grid(l.groups, 1, jobs);
-    switch (l.kind)
-    {
-      case cov::kFactor:
-        hipLaunchKernelGGL(covariance_factor_kernel<DirectJob>, grid, dim3(kCovFactorThreads), 0, stream, n, l.panel, c.dense, c.factor);
-        break;
-      case cov::kSolveBelow:
-        hipLaunchKernelGGL((covariance_solve_kernel<false, DirectJob>), grid, dim3(kWave), 0, stream, n, l.panel, c.dense);
-        break;
-      default:
-        hipLaunchKernelGGL((covariance_update_kernel<false, DirectJob>), grid, dim3(kCovUpdateThreads), 0, stream, n, l.panel, c.dense);
-        break;
-    }
-  }
+  const uint32_t n = G.n;
+  CovFactorLaunch a{};
+  a.jobs = jobs;
+  a.d_en = d_en;
+  a.poses = c.work + c.work_front;   // (PgWork's x leads a job's node arrays)
+  a.pose_stride = c.work_stride;
+  a.job_damping = c.state + offsetof(direct::State, lambda) / sizeof(double);
+  a.damping_stride = kDirectLm;
+  a.workspace = c.dense;
+  a.records = c.factor;
+  cov_enqueue_factor<DirectJob, false>(s->graph, stream, G, a, s->launches);
   hipLaunchKernelGGL(direct_substitute_kernel, dim3(jobs), dim3(kPgThreads), 0, stream, n, c, rules);
   pg_dispatch(s->graph, [&](auto, auto loss) {
     hipLaunchKernelGGL(direct_step_kernel<decltype(loss)::value>, dim3(jobs), dim3(kPgThreads), 0, stream, G, d_en, c, rules);
@@ -130,16 +109,7 @@ extern "C" {
 int ndt2d_direct_create(ndt2d_posegraph * posegraph, size_t workspace_bytes, ndt2d_direct ** out)
 {
   NDT2D_C_TRY
-  if (out == nullptr) return NDT2D_ERR_INVALID;
-  *out = nullptr;
-  if (posegraph == nullptr || workspace_bytes == 0) return NDT2D_ERR_INVALID;
-  ndt2d_direct * s = new ndt2d_direct();
-  s->graph = posegraph;
-  s->h = posegraph->h;
-  s->device = posegraph->device;
-  s->workspace_bytes = workspace_bytes;
-  *out = s;
-  return NDT2D_OK;
+  return ndt2d::pg_companion_create(posegraph, workspace_bytes, out);
   NDT2D_C_CATCH(nullptr)
 }
 
@@ -147,9 +117,7 @@ int ndt2d_direct_destroy(ndt2d_direct * s)
 {
   NDT2D_C_TRY
   if (s == nullptr) return NDT2D_ERR_INVALID;
-  ndt2d::batch_drain(s);
-  ndt2d::batch_release(s);
-  if (s->d_workspace != nullptr) (void)hipFree(s->d_workspace);
+  ndt2d::pg_companion_release(s);
   if (s->h_state != nullptr) (void)hipHostFree(s->h_state);
   delete s;
   return NDT2D_OK;
@@ -183,48 +151,31 @@ int ndt2d_direct_solve(ndt2d_direct * s, const uint8_t * enabled, size_t n_jobs,
   namespace direct = ndt2d::direct;
   if (s == nullptr) return NDT2D_ERR_INVALID;
   if (n_jobs == 0) return NDT2D_OK;
-  const std::string who = "ndt2d_direct_solve: ";
-  if (poses_out == nullptr || records_out == nullptr) return batch_fail(s, NDT2D_ERR_INVALID, who + "null argument");
-  if (!(gradient_tolerance >= 0.0) || !(function_tolerance >= 0.0) || !(parameter_tolerance >= 0.0) || !std::isfinite(gradient_tolerance) ||
-      !std::isfinite(function_tolerance) || !std::isfinite(parameter_tolerance))
-  {
-    return batch_fail(s, NDT2D_ERR_INVALID, who + "a tolerance is negative or not finite");
-  }
+  namespace args = ndt2d::pg_args;
+  const char * const entry = "ndt2d_direct_solve";
+  if (poses_out == nullptr || records_out == nullptr) return batch_fail(s, NDT2D_ERR_INVALID, std::string(entry) + ": null argument");
+  int rc = ndt2d::batch_refuse(s, args::tolerances_refusal(entry, gradient_tolerance, function_tolerance, parameter_tolerance));
+  if (rc != NDT2D_OK) return rc;
   ndt2d_posegraph * g = s->graph;
-  int rc = ndt2d::direct_from_graph(s, ndt2d::pg_ready(g, "ndt2d_direct_solve"));
+  bool loss = false;
+  size_t job_bytes = 0, chunk = 0;
+  ndt2d::PgCall call;
+  rc = ndt2d::pg_begin_call(s, g, entry, &call, [&] {
+    loss = g->loss != ndt2d::pg::kLossTrivial;
+    job_bytes = direct::job_doubles(g->n, g->m, loss) * sizeof(double);
+    chunk = cov::chunk_jobs(g->max_jobs, s->workspace_bytes, job_bytes);
+    return args::dense_refusal(entry, g->n, cov::kMaxDim, chunk, job_bytes, s->workspace_bytes);
+  });
   if (rc != NDT2D_OK) return rc;
+  const hipStream_t stream = call.stream;
+  const ndt2d::PgGraph & G = call.G;
   const size_t n = g->n, m = g->m;
-  if (3 * n > cov::kMaxDim)
-  {
-    return batch_fail(s, NDT2D_ERR_INVALID, who + std::to_string(n) + " poses, a dense matrix holds " + std::to_string(cov::kMaxDim / 3));
-  }
-  const bool loss = g->loss != ndt2d::pg::kLossTrivial;
-  const size_t job_bytes = direct::job_doubles(n, m, loss) * sizeof(double);
-  const size_t chunk = cov::chunk_jobs(g->max_jobs, s->workspace_bytes, job_bytes);
-  if (chunk == 0)
-  {
-    return batch_fail(s, NDT2D_ERR_INVALID, who + "a job of " + std::to_string(n) + " poses needs " + std::to_string(job_bytes) +
-                                              " bytes, the workspace is " + std::to_string(s->workspace_bytes));
-  }
-  NDT2D_BATCH_HIP(s, hipSetDevice(s->device));
-  hipStream_t stream = static_cast<hipStream_t>(ndt2d_get_stream(s->h));
-  rc = ndt2d::direct_from_graph(s, ndt2d::pg_send_weights(g, stream));
-  if (rc != NDT2D_OK) return rc;
-  rc = ndt2d::direct_from_graph(s, ndt2d::pg_send_loss(g, stream));
-  if (rc != NDT2D_OK) return rc;
-  const ndt2d::PgGraph G = ndt2d::pg_device_graph(g);
   const ndt2d::PgRules rules{max_iterations, gradient_tolerance, function_tolerance, parameter_tolerance};
   const direct::Rules lm{max_iterations, gradient_tolerance, function_tolerance, parameter_tolerance};
   // the workspace: what the call's largest chunk needs, never more than the budget
-  const size_t held = std::min(chunk, n_jobs), need = held * job_bytes;
-  if (need > s->workspace_cap)
-  {
-    if (s->d_workspace != nullptr) (void)hipFree(s->d_workspace);
-    s->d_workspace = nullptr;
-    s->workspace_cap = 0;
-    NDT2D_BATCH_HIP(s, hipMalloc(&s->d_workspace, need));
-    s->workspace_cap = need;
-  }
+  const size_t held = std::min(chunk, n_jobs);
+  rc = ndt2d::pg_companion_workspace(s, held * job_bytes);
+  if (rc != NDT2D_OK) return rc;
   if (held * ndt2d::kDirectLm > s->state_cap)
   {
     if (s->h_state != nullptr) (void)hipHostFree(s->h_state);
@@ -233,12 +184,7 @@ int ndt2d_direct_solve(ndt2d_direct * s, const uint8_t * enabled, size_t n_jobs,
     NDT2D_BATCH_HIP(s, hipHostMalloc(reinterpret_cast<void **>(&s->h_state), held * ndt2d::kDirectLm * sizeof(double), hipHostMallocDefault));
     s->state_cap = held * ndt2d::kDirectLm;
   }
-  // the factor's launches: those in front of the first of the inversion
-  s->launches.resize(cov::launch_list(3 * n, nullptr));
-  (void)cov::launch_list(3 * n, s->launches.data());
-  size_t factor_launches = 0;
-  while (factor_launches < s->launches.size() && s->launches[factor_launches].kind <= cov::kUpdate) ++factor_launches;
-  s->launches.resize(factor_launches);
+  ndt2d::cov_launch_list(3 * n, false, &s->launches);   // the factor's launches only
   // the regions of the workspace: [held] dense | work | state | the factor's records
   ndt2d::DirectChunk c{};
   c.dense = static_cast<double *>(s->d_workspace);
@@ -252,7 +198,7 @@ int ndt2d_direct_solve(ndt2d_direct * s, const uint8_t * enabled, size_t n_jobs,
     const size_t k1 = std::min(n_jobs, k0 + chunk), kc = k1 - k0;
     const uint32_t jobs = static_cast<uint32_t>(kc);
     const uint8_t * d_en = nullptr;
-    rc = ndt2d::direct_from_graph(s, ndt2d::pg_send_masks(g, stream, enabled, k0, k1, &d_en));
+    rc = ndt2d::pg_relay(s, g, ndt2d::pg_send_masks(g, stream, enabled, k0, k1, &d_en));
     if (rc != NDT2D_OK) return rc;
     // what comes back: [poses kc n 3 | records kc 8 | chi2 kc 2 m (start, end)]
     const size_t at_rec = kc * n * 3, at_chi2 = at_rec + kc * ndt2d::kDirectRec;

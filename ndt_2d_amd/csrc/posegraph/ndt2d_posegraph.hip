@@ -31,8 +31,10 @@
 // posegraph/ndt2d_posegraph_kernel.h, with the contract of determinism, bounds and LDS that holds for
 // every kernel built from it; the object and the host helpers shared with the units beside this one
 // (posegraph/ndt2d_posegraph_robust.hip: the losses' entry points; posegraph/ndt2d_posegraph_marginals.hip:
-// the marginal covariances) are posegraph/ndt2d_posegraph_state.h.  Here: the two kernels, the
-// object's life, the graph's upload, evaluate and solve.
+// the marginal covariances) are posegraph/ndt2d_posegraph_state.h, with the prelude a call begins
+// with (pg_begin_call); what the calls refuse about their arguments is
+// posegraph/ndt2d_posegraph_args.h.  Here: the two kernels, the object's life, the graph's upload,
+// evaluate and solve.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -43,6 +45,7 @@
 #include "ndt2d_guard.h"
 #include "ndt2d_hip.h"
 #include "batch/ndt2d_batch_state.h"
+#include "posegraph/ndt2d_posegraph_args.h"
 #include "posegraph/ndt2d_posegraph_fn.h"
 #include "posegraph/ndt2d_posegraph_loss.h"
 #include "posegraph/ndt2d_posegraph_kernel.h"
@@ -452,7 +455,7 @@ int ndt2d_posegraph_destroy(ndt2d_posegraph * s)
   if (s == nullptr) return NDT2D_ERR_INVALID;
   ndt2d::batch_drain(s);
   ndt2d::batch_release(s);
-  for (void * p : {s->d_graph, s->d_index, s->d_enabled, s->d_work, s->d_marginals, s->d_marginal_poses, s->d_marginal_nodes})
+  for (void * p : {s->d_graph, s->d_index, s->d_enabled, s->d_work, s->d_marginals, s->marginal_poses.d, s->d_marginal_nodes})
   {
     if (p != nullptr) (void)hipFree(p);
   }
@@ -618,15 +621,11 @@ int ndt2d_posegraph_evaluate(ndt2d_posegraph * s, const uint8_t * enabled, size_
   if (s == nullptr) return NDT2D_ERR_INVALID;
   if (n_jobs == 0) return NDT2D_OK;
   if (cost_out == nullptr) return batch_fail(s, NDT2D_ERR_INVALID, "ndt2d_posegraph_evaluate: null argument");
-  int rc = ndt2d::pg_ready(s, "ndt2d_posegraph_evaluate");
+  ndt2d::PgCall call;
+  int rc = ndt2d::pg_begin_call(s, s, "ndt2d_posegraph_evaluate", &call);
   if (rc != NDT2D_OK) return rc;
-  NDT2D_BATCH_HIP(s, hipSetDevice(s->device));
-  hipStream_t stream = static_cast<hipStream_t>(ndt2d_get_stream(s->h));
-  rc = ndt2d::pg_send_weights(s, stream);
-  if (rc != NDT2D_OK) return rc;
-  rc = ndt2d::pg_send_loss(s, stream);
-  if (rc != NDT2D_OK) return rc;
-  const ndt2d::PgGraph G = ndt2d::pg_device_graph(s);
+  const hipStream_t stream = call.stream;
+  const ndt2d::PgGraph & G = call.G;
   const size_t m = s->m;
   for (size_t k0 = 0; k0 < n_jobs; k0 += s->max_jobs)
   {
@@ -660,20 +659,14 @@ int ndt2d_posegraph_solve(ndt2d_posegraph * s, const uint8_t * enabled, size_t n
   if (s == nullptr) return NDT2D_ERR_INVALID;
   if (n_jobs == 0) return NDT2D_OK;
   if (poses_out == nullptr || records_out == nullptr) return batch_fail(s, NDT2D_ERR_INVALID, "ndt2d_posegraph_solve: null argument");
-  if (!(gradient_tolerance >= 0.0) || !(function_tolerance >= 0.0) || !(parameter_tolerance >= 0.0) || !std::isfinite(gradient_tolerance) ||
-      !std::isfinite(function_tolerance) || !std::isfinite(parameter_tolerance))
-  {
-    return batch_fail(s, NDT2D_ERR_INVALID, "ndt2d_posegraph_solve: a tolerance is negative or not finite");
-  }
-  int rc = ndt2d::pg_ready(s, "ndt2d_posegraph_solve");
+  int rc = ndt2d::batch_refuse(s, ndt2d::pg_args::tolerances_refusal("ndt2d_posegraph_solve", gradient_tolerance, function_tolerance,
+                                                                       parameter_tolerance));
   if (rc != NDT2D_OK) return rc;
-  NDT2D_BATCH_HIP(s, hipSetDevice(s->device));
-  hipStream_t stream = static_cast<hipStream_t>(ndt2d_get_stream(s->h));
-  rc = ndt2d::pg_send_weights(s, stream);
+  ndt2d::PgCall call;
+  rc = ndt2d::pg_begin_call(s, s, "ndt2d_posegraph_solve", &call);
   if (rc != NDT2D_OK) return rc;
-  rc = ndt2d::pg_send_loss(s, stream);
-  if (rc != NDT2D_OK) return rc;
-  const ndt2d::PgGraph G = ndt2d::pg_device_graph(s);
+  const hipStream_t stream = call.stream;
+  const ndt2d::PgGraph & G = call.G;
   const ndt2d::PgRules rules{max_iterations, gradient_tolerance, function_tolerance, parameter_tolerance};
   const size_t n = s->n, m = s->m;
   for (size_t k0 = 0; k0 < n_jobs; k0 += s->max_jobs)

@@ -9,9 +9,10 @@
 // Both are built from posegraph/ndt2d_posegraph_kernel.h -- the solver's pg_linearize, its chain
 // preconditioner and its reductions, under that header's contract of determinism, bounds and LDS
 // (1,280 bytes; registers and scratch: DESIGN.md 3.18.3) -- and pg_matvec3 here, the solver's
-// matrix-vector product with three vectors.  The object and the uploads a call makes first are
-// posegraph/ndt2d_posegraph_state.h; `relative` and `distance`, host only, are
-// posegraph/ndt2d_posegraph_relative.h.
+// matrix-vector product with three vectors.  The object, the prelude a call begins with and a
+// chunk's poses are posegraph/ndt2d_posegraph_state.h, what the call refuses about the damping, the
+// query nodes and the poses posegraph/ndt2d_posegraph_args.h; `relative` and `distance`, host only,
+// are posegraph/ndt2d_posegraph_relative.h.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -21,6 +22,7 @@
 #include "ndt2d_guard.h"
 #include "ndt2d_hip.h"
 #include "batch/ndt2d_batch_state.h"
+#include "posegraph/ndt2d_posegraph_args.h"
 #include "posegraph/ndt2d_posegraph_kernel.h"
 #include "posegraph/ndt2d_posegraph_relative.h"
 #include "posegraph/ndt2d_posegraph_state.h"
@@ -507,36 +509,24 @@ int ndt2d_marginals_columns(ndt2d_posegraph * s, const uint8_t * enabled, size_t
   NDT2D_C_TRY
   if (s == nullptr) return NDT2D_ERR_INVALID;
   if (n_jobs == 0 || n_nodes == 0) return NDT2D_OK;
-  const std::string who = "ndt2d_marginals_columns: ";
+  namespace args = ndt2d::pg_args;
+  const char * const entry = "ndt2d_marginals_columns";
+  const std::string who = std::string(entry) + ": ";
   if (nodes == nullptr || blocks_out == nullptr || records_out == nullptr) return batch_fail(s, NDT2D_ERR_INVALID, who + "null argument");
-  if (!(damping >= 0.0) || !std::isfinite(damping)) return batch_fail(s, NDT2D_ERR_INVALID, who + "the damping is negative or not finite");
+  int rc = ndt2d::batch_refuse(s, args::damping_refusal(entry, damping));
+  if (rc != NDT2D_OK) return rc;
   if (!(tolerance > 0.0) || !std::isfinite(tolerance)) return batch_fail(s, NDT2D_ERR_INVALID, who + "the tolerance is not finite and > 0");
-  int rc = ndt2d::pg_ready(s, "ndt2d_marginals_columns");
+  const size_t Q = n_nodes;
+  ndt2d::PgCall call;
+  rc = ndt2d::pg_begin_call(s, s, entry, &call, [&] {
+    if (Q > 0xFFFFFFFFu) return who + "more than 2^32 - 1 query nodes";
+    const std::string named = args::nodes_refusal(entry, "query", nodes, Q, 1, s->n);
+    return !named.empty() ? named : args::poses_refusal(entry, poses, n_jobs, s->n);
+  });
   if (rc != NDT2D_OK) return rc;
-  const size_t n = s->n, Q = n_nodes;
-  if (Q > 0xFFFFFFFFu) return batch_fail(s, NDT2D_ERR_INVALID, who + "more than 2^32 - 1 query nodes");
-  for (size_t q = 0; q < Q; ++q)
-  {
-    if (nodes[q] >= n) return batch_fail(s, NDT2D_ERR_INVALID, who + "query " + std::to_string(q) + " names node " + std::to_string(nodes[q]) +
-                                                                 " of " + std::to_string(n));
-  }
-  if (poses != nullptr)
-  {
-    for (size_t i = 0; i < n_jobs * n * 3; ++i)
-    {
-      if (!std::isfinite(poses[i]))
-      {
-        return batch_fail(s, NDT2D_ERR_INVALID, who + "job " + std::to_string(i / (3 * n)) + " pose " + std::to_string(i / 3 % n) + " is not finite");
-      }
-    }
-  }
-  NDT2D_BATCH_HIP(s, hipSetDevice(s->device));
-  hipStream_t stream = static_cast<hipStream_t>(ndt2d_get_stream(s->h));
-  rc = ndt2d::pg_send_weights(s, stream);
-  if (rc != NDT2D_OK) return rc;
-  rc = ndt2d::pg_send_loss(s, stream);
-  if (rc != NDT2D_OK) return rc;
-  const ndt2d::PgGraph G = ndt2d::pg_device_graph(s);
+  const hipStream_t stream = call.stream;
+  const ndt2d::PgGraph & G = call.G;
+  const size_t n = s->n;
   NDT2D_BATCH_HIP(s, ndt2d::grow_device(&s->d_marginal_nodes, &s->marginal_nodes_cap, Q * sizeof(uint32_t)));
   NDT2D_BATCH_HIP(s, hipMemcpyAsync(s->d_marginal_nodes, nodes, Q * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
   ndt2d::PgMarginalsLaunch a{};
@@ -562,18 +552,8 @@ int ndt2d_marginals_columns(ndt2d_posegraph * s, const uint8_t * enabled, size_t
     const size_t k0 = t0 / Q, k1 = (t1 - 1) / Q + 1, kc = k1 - k0;   // the jobs the chunk's pairs belong to
     rc = ndt2d::pg_send_masks(s, stream, enabled, k0, k1, &a.d_en);
     if (rc != NDT2D_OK) return rc;
-    if (poses != nullptr)
-    {
-      NDT2D_BATCH_HIP(s, ndt2d::grow_device(&s->d_marginal_poses, &s->marginal_poses_cap, kc * n * 3 * sizeof(double)));
-      NDT2D_BATCH_HIP(s, hipMemcpyAsync(s->d_marginal_poses, poses + k0 * n * 3, kc * n * 3 * sizeof(double), hipMemcpyHostToDevice, stream));
-      a.poses = static_cast<const double *>(s->d_marginal_poses);
-      a.pose_stride = 3 * n;
-    }
-    else
-    {
-      a.poses = G.poses;
-      a.pose_stride = 0;
-    }
+    rc = ndt2d::pg_chunk_poses(s, stream, &s->marginal_poses, poses, k0, kc, n, G, &a.poses, &a.pose_stride);
+    if (rc != NDT2D_OK) return rc;
     a.columns = ndt2d::pg_marginals_form(pc, s->compute_units);
     const size_t groups = a.columns == 1 ? 3 * pc : pc;   // workgroups, each with vectors of its own
     NDT2D_BATCH_HIP(s, ndt2d::grow_device(&s->d_marginals, &s->marginals_cap, (kc * a.block_doubles + groups * pair_doubles) * sizeof(double)));

@@ -101,46 +101,18 @@ public:
                 const double * information, std::size_t m)
   {
     record_ = PoseGraphRecord();
-    std::vector<std::uint8_t> robust;
-    robust.swap(robust_);       // (what the container overload gathered, for this call only)
     if (n == 0) return false;   // `if (scans.empty()) return false;`
     if (!upload(poses_xyt, n, begin, end, transform, information, m, 1)) return false;
-    if (robust.size() == m && m != 0 && !ok(ndt2d_robust_select(pg_, robust.data(), m))) return false;
-    out_.assign(3 * n, 0.0);
-    if (direct_solver_)
-    {
-      if (!solveDirect()) return false;
-    }
-    else
-    {
-      double rec[NDT2D_POSEGRAPH_RECORD_DOUBLES];
-      if (!ok(ndt2d_posegraph_solve(pg_, nullptr, 1, max_iterations_, gradient_tolerance_, function_tolerance_, parameter_tolerance_,
-                                    out_.data(), rec, nullptr)))
-      {
-        return false;
-      }
-      record_ = unpack(rec);
-    }
-    if (!record_.usable()) return false;   // `if (!summary.IsSolutionUsable()) return false;`
-    for (std::size_t i = 0; i < 3 * n; ++i) poses_xyt[i] = out_[i];
-    return true;
+    return solve(poses_xyt, n);
   }
 
   // CeresSolver::optimize(constraints, scans): containers of (smart) pointers to the node's types.
   template <class Constraints, class Scans>
   bool optimize(const Constraints & constraints, Scans & scans)
   {
-    poses_.clear();
-    for (const auto & scan : scans)
-    {
-      const auto pose = scan->getPose();
-      poses_.push_back(pose.x);
-      poses_.push_back(pose.y);
-      poses_.push_back(pose.theta);
-    }
-    gather(constraints);
-    const std::size_t n = poses_.size() / 3;
-    if (!optimize(poses_.data(), n, begin_.data(), end_.data(), transform_.data(), information_.data(), begin_.size())) return false;
+    record_ = PoseGraphRecord();
+    if (!stage(constraints, scans, 1)) return false;   // `if (scans.empty()) return false;`
+    if (!solve(poses_.data(), poses_.size() / 3)) return false;
     std::size_t i = 0;
     for (auto & scan : scans)
     {
@@ -163,27 +135,16 @@ public:
   {
     chi2_out.clear();
     records_out.clear();
-    poses_.clear();
     std::vector<std::size_t> switchable;
-    for (const auto & scan : scans)
-    {
-      const auto pose = scan->getPose();
-      poses_.push_back(pose.x);
-      poses_.push_back(pose.y);
-      poses_.push_back(pose.theta);
-    }
-    gather(constraints);
     std::size_t c = 0;
     for (const auto & constraint : constraints)
     {
       if (constraint->switchable) switchable.push_back(c);
       ++c;
     }
-    const std::size_t n = poses_.size() / 3, m = begin_.size(), jobs = 1 + switchable.size();
-    if (n == 0) return false;
-    if (!upload(poses_.data(), n, begin_.data(), end_.data(), transform_.data(), information_.data(), m, jobs)) return false;
-    if (m != 0 && !ok(ndt2d_robust_select(pg_, robust_.data(), m))) return false;
-    robust_.clear();
+    const std::size_t jobs = 1 + switchable.size();
+    if (!stage(constraints, scans, jobs)) return false;
+    const std::size_t n = poses_.size() / 3, m = begin_.size();
     std::vector<std::uint8_t> enabled(jobs * m, 1);
     for (std::size_t k = 0; k < switchable.size(); ++k) enabled[(1 + k) * m + switchable[k]] = 0;
     out_.assign(jobs * 3 * n, 0.0);
@@ -212,20 +173,8 @@ public:
   {
     blocks_out.clear();
     status_out.clear();
-    poses_.clear();
-    for (const auto & scan : scans)
-    {
-      const auto pose = scan->getPose();
-      poses_.push_back(pose.x);
-      poses_.push_back(pose.y);
-      poses_.push_back(pose.theta);
-    }
-    gather(constraints);
-    const std::size_t n = poses_.size() / 3, m = begin_.size(), q = nodes.size();
-    if (n == 0) return false;
-    if (!upload(poses_.data(), n, begin_.data(), end_.data(), transform_.data(), information_.data(), m, q > 0 ? q : 1)) return false;
-    if (m != 0 && !ok(ndt2d_robust_select(pg_, robust_.data(), m))) return false;
-    robust_.clear();
+    const std::size_t q = nodes.size();
+    if (!stage(constraints, scans, q > 0 ? q : 1)) return false;
     blocks_out.assign(q * q * 9, 0.0);
     std::vector<double> rec(q * NDT2D_MARGINALS_RECORD_DOUBLES, 0.0);
     if (!ok(ndt2d_marginals_columns(pg_, nullptr, 1, nullptr, nodes.data(), q, damping, tolerance, 0, blocks_out.data(), nullptr, rec.data())))
@@ -283,31 +232,13 @@ public:
   {
     diagonal_out.clear();
     pairs_out.clear();
-    poses_.clear();
-    for (const auto & scan : scans)
-    {
-      const auto pose = scan->getPose();
-      poses_.push_back(pose.x);
-      poses_.push_back(pose.y);
-      poses_.push_back(pose.theta);
-    }
-    gather(constraints);
-    const std::size_t n = poses_.size() / 3, m = begin_.size(), p = pairs.size() / 2;
-    if (n == 0) return false;
-    if (!upload(poses_.data(), n, begin_.data(), end_.data(), transform_.data(), information_.data(), m, 1)) return false;
-    if (m != 0 && !ok(ndt2d_robust_select(pg_, robust_.data(), m))) return false;
-    robust_.clear();
-    if (cov_ == nullptr || cov_bytes_ != workspace_bytes)
-    {
+    if (!stage(constraints, scans, 1)) return false;
+    const std::size_t n = poses_.size() / 3, p = pairs.size() / 2;
+    const auto make = [&] {
       dropCovariance();
-      const int rc = ndt2d_covariance_create(pg_, workspace_bytes, &cov_);
-      if (rc != NDT2D_OK)
-      {
-        error_ = "ndt2d error " + std::to_string(rc) + ": ndt2d_covariance_create";
-        return false;
-      }
-      cov_bytes_ = workspace_bytes;
-    }
+      return ndt2d_covariance_create(pg_, workspace_bytes, &cov_);
+    };
+    if (!companion(cov_, cov_bytes_, workspace_bytes, "ndt2d_covariance_create", make)) return false;
     diagonal_out.assign(n * 9, 0.0);
     pairs_out.assign(p * 9, 0.0);
     double rec[NDT2D_COVARIANCE_RECORD_DOUBLES] = {0.0, -1.0, 0.0};
@@ -353,6 +284,69 @@ private:
     }
   }
 
+  // What every call on the node's containers begins with: the scans' poses into poses_, the
+  // constraints into the arrays, the graph on the device with room for `jobs`, and the loss's
+  // selection (the switchable constraints).  false: no scans, or a refused graph (last_error()).
+  template <class Constraints, class Scans>
+  bool stage(const Constraints & constraints, const Scans & scans, std::size_t jobs)
+  {
+    poses_.clear();
+    for (const auto & scan : scans)
+    {
+      const auto pose = scan->getPose();
+      poses_.push_back(pose.x);
+      poses_.push_back(pose.y);
+      poses_.push_back(pose.theta);
+    }
+    gather(constraints);
+    const std::size_t n = poses_.size() / 3, m = begin_.size();
+    if (n == 0) return false;
+    if (!upload(poses_.data(), n, begin_.data(), end_.data(), transform_.data(), information_.data(), m, jobs)) return false;
+    if (m != 0 && !ok(ndt2d_robust_select(pg_, robust_.data(), m))) return false;
+    robust_.clear();
+    return true;
+  }
+
+  // One job, every constraint on, on the graph in place, by the solver chosen: record_, and the
+  // poses into poses_xyt[n][3] where the solution is usable.
+  bool solve(double * poses_xyt, std::size_t n)
+  {
+    out_.assign(3 * n, 0.0);
+    if (direct_solver_)
+    {
+      if (!solveDirect()) return false;
+    }
+    else
+    {
+      double rec[NDT2D_POSEGRAPH_RECORD_DOUBLES];
+      if (!ok(ndt2d_posegraph_solve(pg_, nullptr, 1, max_iterations_, gradient_tolerance_, function_tolerance_, parameter_tolerance_,
+                                    out_.data(), rec, nullptr)))
+      {
+        return false;
+      }
+      record_ = unpack(rec);
+    }
+    if (!record_.usable()) return false;   // `if (!summary.IsSolutionUsable()) return false;`
+    for (std::size_t i = 0; i < 3 * n; ++i) poses_xyt[i] = out_[i];
+    return true;
+  }
+
+  // An object beside pg_ at a budget of workspace_bytes: made at its first use and again when the
+  // budget changes, by make() -- the drop of the old one, then the ndt2d_<noun>_create named `create`.
+  template <class T, class Make>
+  bool companion(T * const & object, std::size_t & bytes, std::size_t workspace_bytes, const char * create, Make make)
+  {
+    if (object != nullptr && bytes == workspace_bytes) return true;
+    const int rc = make();
+    if (rc != NDT2D_OK)
+    {
+      error_ = "ndt2d error " + std::to_string(rc) + ": " + create;
+      return false;
+    }
+    bytes = workspace_bytes;
+    return true;
+  }
+
   // The object (made anew when a capacity is passed) holding the graph.
   bool upload(const double * poses_xyt, std::size_t n, const std::uint32_t * begin, const std::uint32_t * end, const double * transform,
               const double * information, std::size_t m, std::size_t jobs)
@@ -396,17 +390,11 @@ private:
   // One job, every constraint on, by ndt2d_direct_solve into out_ and record_.
   bool solveDirect()
   {
-    if (direct_ == nullptr || direct_bytes_ != direct_workspace_)
-    {
+    const auto make = [&] {
       dropDirect();
-      const int rc = ndt2d_direct_create(pg_, direct_workspace_, &direct_);
-      if (rc != NDT2D_OK)
-      {
-        error_ = "ndt2d error " + std::to_string(rc) + ": ndt2d_direct_create";
-        return false;
-      }
-      direct_bytes_ = direct_workspace_;
-    }
+      return ndt2d_direct_create(pg_, direct_workspace_, &direct_);
+    };
+    if (!companion(direct_, direct_bytes_, direct_workspace_, "ndt2d_direct_create", make)) return false;
     double rec[NDT2D_DIRECT_RECORD_DOUBLES];
     const int rc = ndt2d_direct_solve(direct_, nullptr, 1, max_iterations_, gradient_tolerance_, function_tolerance_, parameter_tolerance_,
                                       out_.data(), rec, nullptr);
@@ -462,7 +450,7 @@ private:
   double loss_scale_ = 1.0;
   std::vector<double> poses_, transform_, information_, out_;
   std::vector<std::uint32_t> begin_, end_;
-  std::vector<std::uint8_t> robust_;   // gather's: which constraints are switchable, until the call that uses it
+  std::vector<std::uint8_t> robust_;   // gather's: which constraints are switchable, until stage() has selected them
   PoseGraphRecord record_;
   std::string error_;
 };

@@ -19,6 +19,18 @@ from .graph_io import Constraint
 DEFAULT_COVARIANCE_WORKSPACE = 1 << 30   # bytes of the dense covariance's workspace: 2,700 poses a job
 DEFAULT_DIRECT_WORKSPACE = 1 << 30       # bytes of the direct solve's workspace: 3,800 poses a job
 DEFAULT_TOLERANCES = dict(max_iterations=100, gradient_tolerance=1e-10, function_tolerance=1e-6, parameter_tolerance=1e-8)
+# the objects that stand beside the pose graph's, by the noun of their ndt2d_<noun>_* functions: the attribute with the handle
+_COMPANIONS = dict(covariance="_cov", direct="_direct")
+
+
+def _tolerances(who, given):
+    """(max_iterations, gradient, function, parameter tolerance) as a solve takes them: DEFAULT_TOLERANCES under the
+    caller's keywords; TypeError names `who` and the keywords that are none of them."""
+    unknown = set(given) - set(DEFAULT_TOLERANCES)
+    if unknown:
+        raise TypeError("%s: unknown argument(s) %s" % (who, sorted(unknown)))
+    tol = dict(DEFAULT_TOLERANCES, **given)
+    return int(tol["max_iterations"]), float(tol["gradient_tolerance"]), float(tol["function_tolerance"]), float(tol["parameter_tolerance"])
 
 
 def _inverse3(m):
@@ -140,8 +152,7 @@ class PoseGraph:
         p = C.c_void_p()
         self._matcher._dev_check(self._L.ndt2d_posegraph_create(self._matcher.device_handle, max_nodes, max_constraints, max_jobs, C.byref(p)),
                                  "ndt2d_posegraph_create")
-        self._close_covariance()   # (it refers to the object that goes)
-        self._close_direct()
+        self._close_companions()   # (they refer to the object that goes)
         old, self._p = self._p, p
         if old:
             self._L.ndt2d_posegraph_destroy(old)
@@ -153,19 +164,45 @@ class PoseGraph:
         if self._timing:
             self.set_timing(True)
 
-    def _close_covariance(self):
-        if getattr(self, "_cov", None):
-            self._L.ndt2d_covariance_destroy(self._cov)
-        self._cov = None
+    def _companion(self, noun, workspace_bytes):
+        """The object ndt2d_<noun> beside the graph's: made at its first use and again when workspace_bytes changes,
+        with the timing flag passed on."""
+        attr, lib = _COMPANIONS[noun], self._L
+        if getattr(self, attr) is None or getattr(self, attr + "_bytes") != int(workspace_bytes):
+            self._close_companion(noun)
+            p = C.c_void_p()
+            rc = getattr(lib, "ndt2d_%s_create" % noun)(self._p, int(workspace_bytes), C.byref(p))
+            if rc != _capi.OK:
+                raise Ndt2dError(rc, "ndt2d_%s_create" % noun, "workspace_bytes = %d" % int(workspace_bytes))
+            setattr(self, attr, p)
+            setattr(self, attr + "_bytes", int(workspace_bytes))
+            if self._timing:
+                getattr(lib, "ndt2d_%s_set_timing" % noun)(p, 1)
+        return getattr(self, attr)
 
-    def _close_direct(self):
-        if getattr(self, "_direct", None):
-            self._L.ndt2d_direct_destroy(self._direct)
-        self._direct = None
+    def _companion_check(self, noun, rc, where):
+        """_check with the companion's own last error."""
+        if rc != _capi.OK:
+            msg = getattr(self._L, "ndt2d_%s_last_error" % noun)(getattr(self, _COMPANIONS[noun]))
+            raise Ndt2dError(rc, where, msg.decode() if msg else "")
+
+    def _companion_last_ms(self, noun):
+        a, b = C.c_float(0.0), C.c_float(0.0)
+        rc = getattr(self._L, "ndt2d_%s_last_ms" % noun)(getattr(self, _COMPANIONS[noun]), C.byref(a), C.byref(b))
+        self._companion_check(noun, rc, "ndt2d_%s_last_ms" % noun)
+        return a.value, b.value
+
+    def _close_companion(self, noun):
+        if getattr(self, _COMPANIONS[noun], None):
+            getattr(self._L, "ndt2d_%s_destroy" % noun)(getattr(self, _COMPANIONS[noun]))
+        setattr(self, _COMPANIONS[noun], None)
+
+    def _close_companions(self):
+        for noun in _COMPANIONS:
+            self._close_companion(noun)
 
     def close(self):
-        self._close_covariance()
-        self._close_direct()
+        self._close_companions()
         if getattr(self, "_p", None):
             self._L.ndt2d_posegraph_destroy(self._p)
             self._p = None
@@ -264,6 +301,20 @@ class PoseGraph:
         if self._loss[0] != "trivial" and not (isinstance(self._loss[2], str) and self._loss[2] == "all"):
             self._select()                                            # (set_graph has reset the selection to every constraint)
 
+    @staticmethod
+    def _solved(poses, records, chi2, fields, weights):
+        """A solve's records as its dicts: fields = (key, type) per double of a record behind the status."""
+        out = []
+        for k in range(len(records)):
+            status = int(records[k, 0])
+            d = dict(poses=poses[k].copy(), status=status, status_name=_capi.POSEGRAPH_STATUS_NAMES[status])
+            d.update((key, kind(records[k, 1 + i])) for i, (key, kind) in enumerate(fields))
+            d.update(chi2_start=chi2[k, 0].copy(), chi2=chi2[k, 1].copy())
+            if weights is not None:
+                d["weights"] = weights[k]
+            out.append(d)
+        return out
+
     def _masks(self, masks):
         """(bytes [K, m] or None, K); a mask may switch off switchable constraints only."""
         if masks is None:
@@ -299,28 +350,14 @@ class PoseGraph:
         cg_iterations, initial_cost, final_cost, gradient, chi2_start [m], chi2 [m]).  Under a loss
         (set_loss) the costs are the robust F, chi2 stays |r|^2, and a job's dict gains weights [m]:
         rho'(chi2) of each constraint at the job's final poses, 1 where the loss does not apply."""
-        unknown = set(tolerances) - set(DEFAULT_TOLERANCES)
-        if unknown:
-            raise TypeError("optimize: unknown argument(s) %s" % sorted(unknown))
-        tol = dict(DEFAULT_TOLERANCES, **tolerances)
+        tol = _tolerances("optimize", tolerances)
         en, K = self._masks(masks)
         poses = np.zeros((K, self.n, 3))
         records = np.zeros((K, _capi.POSEGRAPH_RECORD_DOUBLES))
         chi2 = np.zeros((K, 2, self.m))
-        self._check(self._L.ndt2d_posegraph_solve(self._p, self._u8(en), K, int(tol["max_iterations"]), float(tol["gradient_tolerance"]),
-                                                  float(tol["function_tolerance"]), float(tol["parameter_tolerance"]), dptr(poses),
-                                                  dptr(records), dptr(chi2)), "ndt2d_posegraph_solve")
-        weights = self._weights(chi2[:, 1]) if self._loss[0] != "trivial" else None
-        out = []
-        for k in range(K):
-            status = int(records[k, 0])
-            out.append(dict(poses=poses[k].copy(), status=status, status_name=_capi.POSEGRAPH_STATUS_NAMES[status],
-                            iterations=int(records[k, 1]), cg_iterations=int(records[k, 2]), initial_cost=float(records[k, 3]),
-                            final_cost=float(records[k, 4]), gradient=float(records[k, 5]), chi2_start=chi2[k, 0].copy(),
-                            chi2=chi2[k, 1].copy()))
-            if weights is not None:
-                out[-1]["weights"] = weights[k]
-        return out
+        self._check(self._L.ndt2d_posegraph_solve(self._p, self._u8(en), K, *tol, dptr(poses), dptr(records), dptr(chi2)), "ndt2d_posegraph_solve")
+        fields = (("iterations", int), ("cg_iterations", int), ("initial_cost", float), ("final_cost", float), ("gradient", float))
+        return self._solved(poses, records, chi2, fields, self._weights(chi2[:, 1]) if self._loss[0] != "trivial" else None)
 
     def optimize_direct(self, masks=None, workspace_bytes=DEFAULT_DIRECT_WORKSPACE, **tolerances):
         """optimize's problem, LM rules, arguments and tolerances with an exact linear step (include/ndt2d_hip.h,
@@ -330,50 +367,22 @@ class PoseGraph:
         first call and again when this changes.  Returns optimize's dicts with rejected (steps not taken),
         not_positive_definite (factorisations that failed, counted among them) and pivot_ratio (of the last successful
         factorisation) in place of cg_iterations; weights [m] under a loss."""
-        unknown = set(tolerances) - set(DEFAULT_TOLERANCES)
-        if unknown:
-            raise TypeError("optimize_direct: unknown argument(s) %s" % sorted(unknown))
-        tol = dict(DEFAULT_TOLERANCES, **tolerances)
+        tol = _tolerances("optimize_direct", tolerances)
         en, K = self._masks(masks)
-        if self._direct is None or self._direct_bytes != int(workspace_bytes):
-            self._close_direct()
-            p = C.c_void_p()
-            rc = self._L.ndt2d_direct_create(self._p, int(workspace_bytes), C.byref(p))
-            if rc != _capi.OK:
-                raise Ndt2dError(rc, "ndt2d_direct_create", "workspace_bytes = %d" % int(workspace_bytes))
-            self._direct, self._direct_bytes = p, int(workspace_bytes)
-            if self._timing:
-                self._L.ndt2d_direct_set_timing(self._direct, 1)
+        direct = self._companion("direct", workspace_bytes)
         poses = np.zeros((K, self.n, 3))
         records = np.zeros((K, _capi.DIRECT_RECORD_DOUBLES))
         chi2 = np.zeros((K, 2, self.m))
-        rc = self._L.ndt2d_direct_solve(self._direct, self._u8(en), K, int(tol["max_iterations"]), float(tol["gradient_tolerance"]),
-                                        float(tol["function_tolerance"]), float(tol["parameter_tolerance"]), dptr(poses), dptr(records),
-                                        dptr(chi2))
-        if rc != _capi.OK:
-            msg = self._L.ndt2d_direct_last_error(self._direct)
-            raise Ndt2dError(rc, "ndt2d_direct_solve", msg.decode() if msg else "")
-        weights = self._weights(chi2[:, 1]) if self._loss[0] != "trivial" else None
-        out = []
-        for k in range(K):
-            status = int(records[k, 0])
-            out.append(dict(poses=poses[k].copy(), status=status, status_name=_capi.POSEGRAPH_STATUS_NAMES[status],
-                            iterations=int(records[k, 1]), rejected=int(records[k, 2]), not_positive_definite=int(records[k, 3]),
-                            initial_cost=float(records[k, 4]), final_cost=float(records[k, 5]), gradient=float(records[k, 6]),
-                            pivot_ratio=float(records[k, 7]), chi2_start=chi2[k, 0].copy(), chi2=chi2[k, 1].copy()))
-            if weights is not None:
-                out[-1]["weights"] = weights[k]
-        return out
+        self._companion_check("direct", self._L.ndt2d_direct_solve(direct, self._u8(en), K, *tol, dptr(poses), dptr(records), dptr(chi2)),
+                              "ndt2d_direct_solve")
+        fields = (("iterations", int), ("rejected", int), ("not_positive_definite", int), ("initial_cost", float), ("final_cost", float),
+                  ("gradient", float), ("pivot_ratio", float))
+        return self._solved(poses, records, chi2, fields, self._weights(chi2[:, 1]) if self._loss[0] != "trivial" else None)
 
     def direct_last_ms(self):
         """(kernel_ms, fetch_ms) of the last optimize_direct call's last chunk (set_timing(True)): its iterations with the
         read-backs between them, and its final read-back."""
-        a, b = C.c_float(0.0), C.c_float(0.0)
-        rc = self._L.ndt2d_direct_last_ms(self._direct, C.byref(a), C.byref(b))
-        if rc != _capi.OK:
-            msg = self._L.ndt2d_direct_last_error(self._direct)
-            raise Ndt2dError(rc, "ndt2d_direct_last_ms", msg.decode() if msg else "")
-        return a.value, b.value
+        return self._companion_last_ms("direct")
 
     def marginals(self, nodes, masks=None, poses=None, damping=0.0, tolerance=1e-10, max_cg_iterations=0, want_columns=False):
         """Block columns of (H_FF + damping clamp(diag H_FF))^-1 for the query `nodes` [Q]
@@ -439,35 +448,20 @@ class PoseGraph:
             raise ValueError("covariances: a pair names node %d" % int(pr.min() if pr.min() < 0 else pr.max()))
         pr = np.ascontiguousarray(pr, dtype=np.uint32)
         P = len(pr)
-        if self._cov is None or self._cov_bytes != int(workspace_bytes):
-            self._close_covariance()
-            c = C.c_void_p()
-            rc = self._L.ndt2d_covariance_create(self._p, int(workspace_bytes), C.byref(c))
-            if rc != _capi.OK:
-                raise Ndt2dError(rc, "ndt2d_covariance_create", "workspace_bytes = %d" % int(workspace_bytes))
-            self._cov, self._cov_bytes = c, int(workspace_bytes)
-            if self._timing:
-                self._L.ndt2d_covariance_set_timing(self._cov, 1)
+        cov = self._companion("covariance", workspace_bytes)
         diagonal = np.zeros((K, self.n, 3, 3))
         blocks = np.zeros((K, P, 3, 3))
         records = np.zeros((K, _capi.COVARIANCE_RECORD_DOUBLES))
-        rc = self._L.ndt2d_covariance_compute(self._cov, self._u8(en), K, None if poses is None else dptr(poses), float(damping),
+        rc = self._L.ndt2d_covariance_compute(cov, self._u8(en), K, None if poses is None else dptr(poses), float(damping),
                                               pr.ctypes.data_as(C.POINTER(C.c_uint32)) if P else None, P, dptr(diagonal),
                                               dptr(blocks) if P else None, dptr(records))
-        if rc != _capi.OK:
-            msg = self._L.ndt2d_covariance_last_error(self._cov)
-            raise Ndt2dError(rc, "ndt2d_covariance_compute", msg.decode() if msg else "")
+        self._companion_check("covariance", rc, "ndt2d_covariance_compute")
         return dict(diagonal=diagonal, pairs=blocks, status=records[:, 0].astype(np.int64), failed=records[:, 1].astype(np.int64),
                     pivot_ratio=records[:, 2].copy())
 
     def covariance_last_ms(self):
         """(kernel_ms, fetch_ms) of the last covariances call's last chunk (set_timing(True))."""
-        a, b = C.c_float(0.0), C.c_float(0.0)
-        rc = self._L.ndt2d_covariance_last_ms(self._cov, C.byref(a), C.byref(b))
-        if rc != _capi.OK:
-            msg = self._L.ndt2d_covariance_last_error(self._cov)
-            raise Ndt2dError(rc, "ndt2d_covariance_last_ms", msg.decode() if msg else "")
-        return a.value, b.value
+        return self._companion_last_ms("covariance")
 
     def relative_covariances(self, pairs, poses=None, mask=None, damping=0.0, workspace_bytes=DEFAULT_COVARIANCE_WORKSPACE):
         """relative_covariance for every (a, b) of pairs [P, 2] from ONE covariances call: the joint
@@ -497,10 +491,9 @@ class PoseGraph:
 
     def set_timing(self, enabled):
         self._check(self._L.ndt2d_posegraph_set_timing(self._p, 1 if enabled else 0), "ndt2d_posegraph_set_timing")
-        if self._cov is not None:
-            self._L.ndt2d_covariance_set_timing(self._cov, 1 if enabled else 0)
-        if self._direct is not None:
-            self._L.ndt2d_direct_set_timing(self._direct, 1 if enabled else 0)
+        for noun, attr in _COMPANIONS.items():
+            if getattr(self, attr) is not None:
+                getattr(self._L, "ndt2d_%s_set_timing" % noun)(getattr(self, attr), 1 if enabled else 0)
         self._timing = bool(enabled)
 
     def last_ms(self):

@@ -63,16 +63,17 @@ def test_the_entry_points_are_declared_bound_guarded_and_built():
     assert (_capi.COVARIANCE_OK, _capi.COVARIANCE_NOT_POSITIVE_DEFINITE, _capi.COVARIANCE_RECORD_DOUBLES) == (0, 1, 3)
     assert len(_capi.COVARIANCE_STATUS_NAMES) == 2
     assert "covariance/ndt2d_covariance.hip" in build.SOURCES and PLAN in build.HEADERS and KERNELS in build.HEADERS
-    assert sorted(os.listdir(COVARIANCE)) == ["ndt2d_covariance.hip", "ndt2d_covariance_kernel.h", "ndt2d_covariance_plan.h"] or \
-        sorted(n for n in os.listdir(COVARIANCE) if n.endswith((".hip", ".h"))) == ["ndt2d_covariance.hip", "ndt2d_covariance_kernel.h",
-                                                                                  "ndt2d_covariance_plan.h"]
+    files = ["ndt2d_covariance.hip", "ndt2d_covariance_kernel.h", "ndt2d_covariance_launch.h", "ndt2d_covariance_plan.h"]
+    assert sorted(os.listdir(COVARIANCE)) == files or sorted(n for n in os.listdir(COVARIANCE) if n.endswith((".hip", ".h"))) == files
+    assert os.path.join(COVARIANCE, "ndt2d_covariance_launch.h") in build.HEADERS
     unit = open(os.path.join(COVARIANCE, "ndt2d_covariance.hip")).read()
-    for name in ("posegraph/ndt2d_posegraph_state.h", "covariance/ndt2d_covariance_kernel.h", "covariance/ndt2d_covariance_plan.h"):
+    for name in ("posegraph/ndt2d_posegraph_state.h", "covariance/ndt2d_covariance_kernel.h", "covariance/ndt2d_covariance_plan.h",
+                 "covariance/ndt2d_covariance_launch.h"):
         assert '#include "%s"' % name in unit
     kernels = open(KERNELS).read()
     for name in ("posegraph/ndt2d_posegraph_kernel.h", "posegraph/ndt2d_posegraph_fn.h", "posegraph/ndt2d_posegraph_loss.h"):
         assert '#include "%s"' % name in kernels
-    for name in ("ndt2d_covariance.hip", "ndt2d_covariance_kernel.h", "ndt2d_covariance_plan.h"):
+    for name in files:
         code = re.sub(r"//[^\n]*", "", open(os.path.join(COVARIANCE, name)).read())
         assert "atomic" not in code.lower(), name                                            # a block has one writer, no split sums
         assert not re.search(r'#include\s+"[^"]*\.hip"', code), name                         # no unit includes a .hip

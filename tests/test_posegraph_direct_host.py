@@ -74,11 +74,11 @@ def test_the_entry_points_are_declared_bound_guarded_and_built():
         assert os.path.join(DIRECT, name) in build.HEADERS, name
     assert sorted(n for n in os.listdir(DIRECT) if n.endswith((".hip", ".h"))) == FILES
     assert sorted(n for n in os.listdir(os.path.join(CSRC, "covariance")) if n.endswith((".hip", ".h"))) == \
-        ["ndt2d_covariance.hip", "ndt2d_covariance_kernel.h", "ndt2d_covariance_plan.h"]
-    assert len([n for n in os.listdir(os.path.join(CSRC, "posegraph")) if n.endswith((".hip", ".h"))]) == 9
+        ["ndt2d_covariance.hip", "ndt2d_covariance_kernel.h", "ndt2d_covariance_launch.h", "ndt2d_covariance_plan.h"]
+    assert len([n for n in os.listdir(os.path.join(CSRC, "posegraph")) if n.endswith((".hip", ".h"))]) == 10
     unit = open(os.path.join(DIRECT, "ndt2d_direct.hip")).read()
     for name in ("posegraph/ndt2d_posegraph_state.h", "posegraph/ndt2d_posegraph_kernel.h", "covariance/ndt2d_covariance_kernel.h",
-                 "covariance/ndt2d_covariance_plan.h", "direct/ndt2d_direct_step.h"):
+                 "covariance/ndt2d_covariance_plan.h", "covariance/ndt2d_covariance_launch.h", "direct/ndt2d_direct_step.h"):
         assert '#include "%s"' % name in unit, name
     kernels = open(os.path.join(DIRECT, "ndt2d_direct_kernel.h")).read()
     assert '#include "direct/ndt2d_direct_step.h"' in kernels and "direct::propose(" in kernels and "direct::take(" in kernels
@@ -93,11 +93,26 @@ def test_the_entry_points_are_declared_bound_guarded_and_built():
         assert body.lstrip().startswith("NDT2D_C_TRY") and "NDT2D_C_CATCH(" in body.splitlines()[-1], body[:80]
     for kernel in ("direct_begin_kernel", "direct_substitute_kernel", "direct_step_kernel", "direct_finish_kernel"):
         assert re.search(r"__global__ void __launch_bounds__\(\w+\) " + kernel + r"\(", kernels), kernel
-    # the factor is the covariance's: its kernels on this unit's layout, the inversion's launches not taken
-    for kernel in ("covariance_assemble_kernel", "covariance_factor_kernel", "covariance_solve_kernel<false, DirectJob>",
-                   "covariance_update_kernel<false, DirectJob>"):
-        assert kernel in unit, kernel
-    assert "covariance_blocks_kernel" not in unit and "<true" not in unit
+    # the factor is the covariance's: its kernels on this unit's layout, the inversion's launches not taken.  The launch
+    # header is the only file that names those kernels in a launch, on the layout it is instantiated with; this unit
+    # instantiates it with DirectJob and without the inversion, the covariance's unit includes it too
+    launch = _code(os.path.join(CSRC, "covariance", "ndt2d_covariance_launch.h"))
+    for kernel in ("covariance_nodes_kernel<Job>", "covariance_fill_kernel<Job>", "covariance_assemble_kernel<decltype(loss)::value, Job>",
+                   "covariance_factor_kernel<Job>", "covariance_solve_kernel<false, Job>", "covariance_update_kernel<false, Job>",
+                   "covariance_solve_kernel<true, Job>", "covariance_update_kernel<true, Job>"):
+        assert len(re.findall(r"hipLaunchKernelGGL\(\(?" + re.escape(kernel) + r"\)?,", launch)) == 1, kernel
+    inversion = launch[launch.index("if constexpr (kInverse)"):]
+    assert launch.count("<true, Job>") == 2 and inversion.count("<true, Job>") == 2            # the inversion's, behind the flag only
+    for root, _, names in os.walk(CSRC):
+        for name in names:
+            if name.endswith((".hip", ".h", ".cpp")) and name != "ndt2d_covariance_launch.h":
+                launches = re.findall(r"hipLaunchKernelGGL\(\(?\s*(?:ndt2d::)?(\w+)", _code(os.path.join(root, name)))
+                assert not [k for k in launches if re.fullmatch(r"covariance_(nodes|fill|assemble|factor|solve|update)_kernel", k)], name
+    assert unit.count("cov_enqueue_factor<DirectJob, false>(") == 1 and unit.count("cov_enqueue_factor<") == 1
+    assert "cov_launch_list(3 * n, false, " in unit                                            # the list cut to the factor's part
+    assert "covariance_blocks_kernel" not in unit and "<true" not in unit and ", true>" not in unit
+    cov_unit = open(os.path.join(CSRC, "covariance", "ndt2d_covariance.hip")).read()
+    assert '#include "covariance/ndt2d_covariance_launch.h"' in cov_unit and "cov_enqueue_factor<ndt2d::CovJob, true>(" in cov_unit
     # nothing of the pose graph's own units moved: the direct solve is not named there
     for name in os.listdir(os.path.join(CSRC, "posegraph")):
         if name.endswith((".hip", ".h")):

@@ -60,7 +60,7 @@ def test_the_unit_is_built_hashed_and_bound():
     posegraph = os.path.join(ROOT, "ndt_2d_amd", "csrc", "posegraph")
     for unit in ("ndt2d_posegraph.hip", "ndt2d_posegraph_robust.hip", "ndt2d_posegraph_marginals.hip"):
         assert "posegraph/" + unit in build.SOURCES, unit
-    for name in ("ndt2d_posegraph_fn.h", "ndt2d_posegraph_kernel.h", "ndt2d_posegraph_state.h"):
+    for name in ("ndt2d_posegraph_fn.h", "ndt2d_posegraph_kernel.h", "ndt2d_posegraph_state.h", "ndt2d_posegraph_args.h"):
         assert os.path.join(posegraph, name) in build.HEADERS, name
     names = [n for n in _capi.SIGNATURES if n.startswith("ndt2d_posegraph_")]
     assert sorted(names) == sorted("ndt2d_posegraph_" + n for n in (
@@ -68,7 +68,7 @@ def test_the_unit_is_built_hashed_and_bound():
     header = open(os.path.join(ROOT, "include", "ndt2d_hip.h")).read()
     assert "#define NDT2D_ABI_VERSION 4" in header and "e^T L^T L e" in header
     sources = sorted(n for n in os.listdir(posegraph) if n.endswith((".hip", ".h")))
-    assert len(sources) == 9, sources                            # three units, the kernel and state headers, four of plain C++
+    assert len(sources) == 10, sources                           # three units, the kernel and state headers, five of plain C++
     for name in sources:                                         # a result is bit-identical run to run
         assert "atomic" not in re.sub(r"//[^\n]*", "", open(os.path.join(posegraph, name)).read()), name
         assert len(open(os.path.join(posegraph, name)).read().splitlines()) <= 900, name
