@@ -1031,6 +1031,74 @@ int ndt2d_direct_solve(ndt2d_direct * direct, const uint8_t * enabled, size_t n_
 int ndt2d_direct_set_timing(ndt2d_direct * direct, int enabled);
 int ndt2d_direct_last_ms(ndt2d_direct * direct, float * kernel_ms, float * fetch_ms);
 
+/* Sparse solve (ndt2d_sparse_*: an object of its own beside an ndt2d_posegraph, which it refers to
+ * and is destroyed before).  A third way to solve the problem of "Pose graph" and "Robust losses",
+ * for the graphs a mapping session builds: a chain along the node order plus closures.  The problem
+ * is "Direct solve"'s term for term -- the residual, the weighting, the losses, F, the Jacobians,
+ * H = J^T J reweighted by rho', g, D = clamp(diag H_FF), A = H_FF + lambda D -- and so are the LM
+ * rules, bit for bit in their logic: lambda_0, nu, the gain ratio, the noise rule, the four stop
+ * rules, the statuses, predicted = 1/2 (lambda delta^T D delta - g^T delta), a failed factorisation
+ * counts as a rejected step.  Only the linear step A delta = -g is computed differently: its cost
+ * is O(n) for the chain plus O(s^3) for the s nodes closures touch, and no 3n x 3n matrix exists.
+ *     Separators.  A constraint is a chain edge when |begin - end| == 1, every other one a closure
+ * edge.  The separators are the nodes that are an end of at least one closure edge of the GRAPH,
+ * whatever the masks: the layout is one per graph, shared by the K jobs, and a job's bits do not
+ * depend on the other jobs' masks.  The fixed node and the nodes a job's mask leaves without a
+ * constraint are not unknowns, as in "Direct solve"; they only cut the chain.  The interior nodes
+ * are all the others, in node order.  ndt2d_sparse_layout reports the two counts.
+ *     The step.  The interior block A_ii is ONE block-tridiagonal SPD system over the interior
+ * nodes in node order (the coupling between two interior nodes that are not consecutive, or whose
+ * chain edge is off or absent, is zero; a principal submatrix of an SPD matrix is SPD, so block
+ * cyclic reduction without pivoting applies for any mask), factored by "Pose graph"'s chain
+ * reduction, all segments at once.  A_is has at most two 3 x 3 blocks per interior node -- to the
+ * separator directly before it and to the one directly after it -- so Z = A_ii^-1 A_is is six
+ * right-hand-side columns through the same reduction, and a seventh is y = A_ii^-1 (-g_i).  Then
+ * S = A_ss - A_si Z (a thread per separator writes its own block row; no atomics) in a dense
+ * padded(3 s)^2 matrix, factored S = L L^T by "Dense covariance"'s blocked Cholesky (the factor's
+ * launches only), S delta_s = -g_s - A_si y by "Direct solve"'s substitution, and
+ * delta_i = y_i - Z_left[i] delta_left(i) - Z_right[i] delta_right(i).  A non-positive pivot met
+ * by the reduction or by S's Cholesky is a failed factorisation.  With s = 0 nothing dense is
+ * launched.
+ *     ndt2d_sparse_solve takes ndt2d_direct_solve's arguments with their meanings, and
+ * records_out[K][NDT2D_DIRECT_RECORD_DOUBLES] has the direct solve's: the pivot ratio is S's (of the
+ * Schur complement against its own diagonal; 1 when s = 0), the failed factorisations count a
+ * failure of the reduction and a failure of S alike.  initial_cost is ndt2d_posegraph_evaluate's F
+ * bit for bit; a node that cannot move keeps its bits, -0.0 included.
+ *     An iteration of a chunk is a fixed list of launches -- S's fill, the band's assembly at each
+ * job's own lambda, one workgroup per job for the reduction, the Schur terms, S's factor, one
+ * workgroup per job for the substitution, the expansion, one for the step -- after which the host
+ * reads the jobs' states back (one small read-back per LM iteration) and stops when no job is
+ * iterating or after max_iterations.  No waiting on the device.  The stream is the context's
+ * current one.  A job that has stopped is left alone.
+ *     Determinism.  No atomics, every sum in a fixed ascending order, fixed reduction trees.  A
+ * job's bits depend on the graph, its mask, the settings and the tolerances -- not on the other
+ * jobs, the chunking, workspace_bytes or the run.
+ *     Memory.  Per job of a chunk 90 doubles per interior node (the reduction's D, U, L, P, the
+ * seven columns, Z and y, the couplings to the separators), padded(3 s)^2 + 2 padded(3 s) + 6 s for
+ * the separators, the CG solver's node arrays (41 n doubles, m more under a loss) and 17 doubles of
+ * state: 8 (90 n_i + padded(3 s)^2 + 2 padded(3 s) + 6 s + 41 n [+ m] + 17) bytes, 1 KiB a pose
+ * where closures are few.  The workspace is allocated at the first solve (what the call's largest
+ * chunk needs, never more than workspace_bytes) and freed by destroy.
+ *   create    NDT2D_ERR_INVALID: a NULL posegraph or out, workspace_bytes == 0.
+ *   solve     NDT2D_ERR_INVALID before anything runs: a NULL object (no message), NULL poses_out or
+ *             records_out, a negative or non-finite tolerance, more than 21,840 separators, a graph
+ *             of which one job does not fit workspace_bytes (the message gives the bytes a job
+ *             needs).  n_jobs == 0: NDT2D_OK, nothing done.  Before set_graph: NDT2D_ERR_STATE.
+ *   layout    the separators and the interior nodes of the graph in place.  NDT2D_ERR_INVALID: a
+ *             NULL object or output; before set_graph NDT2D_ERR_STATE.
+ *   set_timing / last_ms   as "Direct solve"'s. */
+typedef struct ndt2d_sparse ndt2d_sparse;
+int ndt2d_sparse_create(ndt2d_posegraph * posegraph, size_t workspace_bytes, ndt2d_sparse ** out);
+int ndt2d_sparse_destroy(ndt2d_sparse * sparse);
+const char * ndt2d_sparse_last_error(ndt2d_sparse * sparse);
+int ndt2d_sparse_solve(ndt2d_sparse * sparse, const uint8_t * enabled, size_t n_jobs,
+                       uint32_t max_iterations, double gradient_tolerance,
+                       double function_tolerance, double parameter_tolerance, double * poses_out,
+                       double * records_out, double * chi2_out);
+int ndt2d_sparse_layout(ndt2d_sparse * sparse, size_t * n_separators, size_t * n_interior);
+int ndt2d_sparse_set_timing(ndt2d_sparse * sparse, int enabled);
+int ndt2d_sparse_last_ms(ndt2d_sparse * sparse, float * kernel_ms, float * fetch_ms);
+
 /* Upload the beam endpoints of one scan, robot frame, already subsampled to
  * min(laser_max_beams, points.size()) points by the caller
  * (src/scan_matcher_ndt.cpp:95-96,110 / :165-166,171).  Beams are taken as given: finite,

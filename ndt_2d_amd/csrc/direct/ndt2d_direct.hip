@@ -62,7 +62,7 @@ void direct_iteration(const ndt2d_direct * s, hipStream_t stream, const PgGraph 
   a.workspace = c.dense;
   a.records = c.factor;
   cov_enqueue_factor<DirectJob, false>(s->graph, stream, G, a, s->launches);
-  hipLaunchKernelGGL(direct_substitute_kernel, dim3(jobs), dim3(kPgThreads), 0, stream, n, c, rules);
+  hipLaunchKernelGGL(direct_substitute_kernel<>, dim3(jobs), dim3(kPgThreads), 0, stream, n, c, rules);
   pg_dispatch(s->graph, [&](auto, auto loss) {
     hipLaunchKernelGGL(direct_step_kernel<decltype(loss)::value>, dim3(jobs), dim3(kPgThreads), 0, stream, G, d_en, c, rules);
   });
@@ -82,20 +82,6 @@ int direct_fetch_states(ndt2d_direct * s, hipStream_t stream, const DirectChunk 
     if (direct::iterating(st, rules)) *iterating = true;
   }
   return NDT2D_OK;
-}
-
-// The evaluate kernel's chi2 of the chunk's jobs at poses (posegraph/ndt2d_posegraph.hip's kernel is
-// that unit's own: the constraint's arithmetic is pg_constraint, one thread a constraint).
-__global__ void __launch_bounds__(kPgThreads) direct_chi2_kernel(const PgGraph G, const double * poses, size_t pose_stride, double * chi2,
-                                                                  size_t chi2_stride)
-{
-  const size_t job = blockIdx.x;
-  const double * xs = poses + job * pose_stride;
-  for (uint32_t c = pg_tid(); c < G.m; c += kPgThreads)
-  {
-    double e[3], r[3];
-    chi2[job * chi2_stride + c] = pg_constraint(G, c, xs, nullptr, e, r);
-  }
 }
 
 }  // namespace

@@ -72,7 +72,10 @@ struct DirectChunk
   double * factor;      // [job][kCovRec] the factor kernel's records
   size_t work_stride;
   size_t work_front;    // m under a loss, else 0
+  using Job = DirectJob;   // the layout of `dense`
   __device__ __forceinline__ double * work_of(size_t job) const { return work + job * work_stride + work_front; }
+  // where the substitution takes g from and leaves delta: the job's PgWork
+  __device__ __forceinline__ PgWork vectors_of(size_t job, size_t n) const { return PgWork(work_of(job), n); }
   __device__ __forceinline__ direct::State * state_of(size_t job) const { return reinterpret_cast<direct::State *>(state + job * kDirectLm); }
 };
 
@@ -135,8 +138,11 @@ __global__ void __launch_bounds__(kPgThreads) direct_begin_kernel(const PgGraph 
 //       the last panel: wave 0 eliminates in descending order; then thread j takes column j before
 //       the panel, rhs[j] -= sum_k L[j0 + k, j] delta[j0 + k], k ascending from zero (the threads
 //       of a wave read consecutive columns: coalesced).  delta goes to the solver's PgWork.  A job
-//       that is not iterating, or whose factorisation failed, is left alone.
-__global__ void __launch_bounds__(kPgThreads) direct_substitute_kernel(uint32_t n, const DirectChunk chunk, const PgRules rules)
+//       that is not iterating, or whose factorisation failed, is left alone.  Chunk: the chunk's layout,
+//       DirectChunk by default; the sparse solve (sparse/ndt2d_sparse_kernel.h) runs the substitution on
+//       the separators' matrix with a layout of its own (n is then the number of separators).
+template <class Chunk = DirectChunk>
+__global__ void __launch_bounds__(kPgThreads) direct_substitute_kernel(uint32_t n, const Chunk chunk, const PgRules rules)
 {
   __shared__ double T[cov::kPanel][kCovLds];
   __shared__ double solved[cov::kPanel];
@@ -144,8 +150,8 @@ __global__ void __launch_bounds__(kPgThreads) direct_substitute_kernel(uint32_t 
   const direct::State s = direct_load_state(chunk.state_of(job));
   if (!direct::iterating(s, direct_rules(rules))) return;
   if (pg_uniform(chunk.factor[job * kCovRec]) != 0.0) return;
-  const DirectJob w(chunk.dense, n, job);
-  const PgWork pw(chunk.work_of(job), n);
+  const typename Chunk::Job w(chunk.dense, n, job);
+  const auto pw = chunk.vectors_of(job, n);
   const size_t d = 3 * static_cast<size_t>(n), ld = cov::padded(d);
   const uint32_t np = static_cast<uint32_t>(ld / cov::kPanel), lane = threadIdx.x;
   for (size_t i = threadIdx.x; i < ld; i += kPgThreads) w.rhs[i] = i < d ? -pw.g[i] : 0.0;
@@ -293,6 +299,21 @@ __global__ void __launch_bounds__(kDirectFinishThreads) direct_finish_kernel(uin
   const PgWork w(chunk.work_of(job), n);
   for (size_t i = threadIdx.x; i < d; i += kDirectFinishThreads) poses_out[job * d + i] = w.x[i];
   if (threadIdx.x < kDirectRec) records[job * kDirectRec + threadIdx.x] = chunk.state[job * kDirectLm + threadIdx.x];
+}
+
+//   direct_chi2_kernel   grid (job), 1,024 threads: the evaluate kernel's chi2 of the chunk's jobs at
+//       poses (posegraph/ndt2d_posegraph.hip's kernel is that unit's own: the constraint's arithmetic is
+//       pg_constraint, one thread a constraint).
+[[maybe_unused]] __global__ void __launch_bounds__(kPgThreads) direct_chi2_kernel(const PgGraph G, const double * poses, size_t pose_stride, double * chi2,
+                                                                                   size_t chi2_stride)
+{
+  const size_t job = blockIdx.x;
+  const double * xs = poses + job * pose_stride;
+  for (uint32_t c = pg_tid(); c < G.m; c += kPgThreads)
+  {
+    double e[3], r[3];
+    chi2[job * chi2_stride + c] = pg_constraint(G, c, xs, nullptr, e, r);
+  }
 }
 
 }  // namespace

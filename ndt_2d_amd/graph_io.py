@@ -297,12 +297,14 @@ class Graph:
         closures, by default); `last_optimize` then has the weights rho' of the constraints at the solution.  Returns whether the solution is usable -- False for no scans,
         as the reference; `last_optimize` keeps the job's record.
         method: "cg" (the default: PoseGraph.optimize, LM with a preconditioned CG inside) or "direct" (PoseGraph.optimize_direct: the
-        same LM rules with an exact step on a dense Cholesky, whose cost does not depend on the closures; kw may carry workspace_bytes)."""
+        same LM rules with an exact step on a dense Cholesky, whose cost does not depend on the closures; kw may carry workspace_bytes)
+        or "schur" (PoseGraph.optimize_sparse: the same exact step by a block cyclic reduction of the chain and a Schur complement on
+        the nodes closures touch, for large maps; kw may carry workspace_bytes)."""
         from . import _capi
         from .pose_graph import PoseGraph
         self.last_optimize = None
-        if method not in ("cg", "direct"):
-            raise ValueError("optimize: method = %r (\"cg\" or \"direct\")" % (method,))
+        if method not in ("cg", "direct", "schur"):
+            raise ValueError("optimize: method = %r (\"cg\", \"direct\" or \"schur\")" % (method,))
         if not self.scans:
             return False
         weighting = kw.pop("weighting", "reference")
@@ -314,7 +316,8 @@ class Graph:
             if loss is not None:
                 pg.set_loss(loss, loss_scale, loss_on)
             pg.set_graph(np.array([s.pose for s in self.scans], dtype=np.float64), self.constraints, fixed=0)
-            result = (pg.optimize_direct(**kw) if method == "direct" else pg.optimize(**kw))[0]
+            solve = dict(cg=pg.optimize, direct=pg.optimize_direct, schur=pg.optimize_sparse)[method]
+            result = solve(**kw)[0]
         finally:
             pg.close()
         self.last_optimize = result

@@ -35,7 +35,7 @@ struct PoseGraphRecord
   int status = NDT2D_POSEGRAPH_FAILED;   // NDT2D_POSEGRAPH_*
   std::uint32_t iterations = 0, cg_iterations = 0;
   double initial_cost = 0.0, final_cost = 0.0, gradient = 0.0;
-  // of the "direct" solver (cg_iterations is then 0): steps not taken, factorisations that failed
+  // of the "direct" and "sparse" solvers (cg_iterations is then 0): steps not taken, factorisations that failed
   // among them, the smallest pivot ratio of the last successful factorisation
   std::uint32_t rejected = 0, not_positive_definite = 0;
   double pivot_ratio = 0.0;
@@ -52,6 +52,7 @@ public:
   {
     dropCovariance();
     dropDirect();
+    dropSparse();
     if (pg_ != nullptr) ndt2d_posegraph_destroy(pg_);
   }
 
@@ -72,16 +73,19 @@ public:
   // What optimize() solves with: "cg" (the default: ndt2d_posegraph_solve, LM with a preconditioned CG
   // inside) or "direct" (ndt2d_direct_solve: the same LM rules with an exact step on a dense
   // Cholesky, whose cost does not depend on the closures; workspace_bytes: the device memory a
-  // chunk's jobs may take, one 3n x 3n matrix of doubles a job).  false: another name (last_error()).
-  // consistency() keeps the CG solver.
+  // chunk's jobs may take, one 3n x 3n matrix of doubles a job) or "sparse" (ndt2d_sparse_solve: the
+  // same exact step by a block cyclic reduction of the scans' chain and a Schur complement on the
+  // scans closures touch, about 1 KiB a scan: for large maps with many closures).  false: another
+  // name (last_error()).  consistency() keeps the CG solver.
   bool setSolver(const std::string & solver, std::size_t workspace_bytes = std::size_t(1) << 30)
   {
-    if (solver != "cg" && solver != "direct")
+    if (solver != "cg" && solver != "direct" && solver != "sparse")
     {
-      error_ = "setSolver: \"" + solver + "\" (\"cg\" or \"direct\")";
+      error_ = "setSolver: \"" + solver + "\" (\"cg\", \"direct\" or \"sparse\")";
       return false;
     }
     direct_solver_ = solver == "direct";
+    sparse_solver_ = solver == "sparse";
     direct_workspace_ = workspace_bytes;
     return true;
   }
@@ -316,6 +320,10 @@ private:
     {
       if (!solveDirect()) return false;
     }
+    else if (sparse_solver_)
+    {
+      if (!solveSparse()) return false;
+    }
     else
     {
       double rec[NDT2D_POSEGRAPH_RECORD_DOUBLES];
@@ -355,6 +363,7 @@ private:
     {
       dropCovariance();   // (they refer to the object that goes)
       dropDirect();
+      dropSparse();
       if (pg_ != nullptr) ndt2d_posegraph_destroy(pg_);
       pg_ = nullptr;
       max_nodes_ = n > 2 * max_nodes_ ? n : 2 * max_nodes_;
@@ -403,6 +412,33 @@ private:
       error_ = std::string("ndt2d error ") + std::to_string(rc) + ": " + ndt2d_direct_last_error(direct_);
       return false;
     }
+    record_ = unpackDirect(rec);
+    return true;
+  }
+
+  // One job, every constraint on, by ndt2d_sparse_solve into out_ and record_.
+  bool solveSparse()
+  {
+    const auto make = [&] {
+      dropSparse();
+      return ndt2d_sparse_create(pg_, direct_workspace_, &sparse_);
+    };
+    if (!companion(sparse_, sparse_bytes_, direct_workspace_, "ndt2d_sparse_create", make)) return false;
+    double rec[NDT2D_DIRECT_RECORD_DOUBLES];
+    const int rc = ndt2d_sparse_solve(sparse_, nullptr, 1, max_iterations_, gradient_tolerance_, function_tolerance_, parameter_tolerance_,
+                                      out_.data(), rec, nullptr);
+    if (rc != NDT2D_OK)
+    {
+      error_ = std::string("ndt2d error ") + std::to_string(rc) + ": " + ndt2d_sparse_last_error(sparse_);
+      return false;
+    }
+    record_ = unpackDirect(rec);
+    return true;
+  }
+
+  // The record of the two exact solvers.
+  static PoseGraphRecord unpackDirect(const double * rec)
+  {
     PoseGraphRecord r;
     r.status = static_cast<int>(rec[0]);
     r.iterations = static_cast<std::uint32_t>(rec[1]);
@@ -412,14 +448,19 @@ private:
     r.final_cost = rec[5];
     r.gradient = rec[6];
     r.pivot_ratio = rec[7];
-    record_ = r;
-    return true;
+    return r;
   }
 
   void dropDirect()
   {
     if (direct_ != nullptr) ndt2d_direct_destroy(direct_);
     direct_ = nullptr;
+  }
+
+  void dropSparse()
+  {
+    if (sparse_ != nullptr) ndt2d_sparse_destroy(sparse_);
+    sparse_ = nullptr;
   }
 
   void dropCovariance()
@@ -442,6 +483,9 @@ private:
   ndt2d_direct * direct_ = nullptr;    // made at the first optimize() under "direct", destroyed before pg_
   std::size_t direct_bytes_ = 0, direct_workspace_ = std::size_t(1) << 30;
   bool direct_solver_ = false;
+  ndt2d_sparse * sparse_ = nullptr;    // made at the first optimize() under "sparse", destroyed before pg_
+  std::size_t sparse_bytes_ = 0;
+  bool sparse_solver_ = false;
   double pivot_ratio_ = 0.0;
   std::size_t max_nodes_ = 0, max_constraints_ = 0, max_jobs_ = 1;
   std::uint32_t max_iterations_ = 100;

@@ -20,7 +20,8 @@ DEFAULT_COVARIANCE_WORKSPACE = 1 << 30   # bytes of the dense covariance's works
 DEFAULT_DIRECT_WORKSPACE = 1 << 30       # bytes of the direct solve's workspace: 3,800 poses a job
 DEFAULT_TOLERANCES = dict(max_iterations=100, gradient_tolerance=1e-10, function_tolerance=1e-6, parameter_tolerance=1e-8)
 # the objects that stand beside the pose graph's, by the noun of their ndt2d_<noun>_* functions: the attribute with the handle
-_COMPANIONS = dict(covariance="_cov", direct="_direct")
+DEFAULT_SPARSE_WORKSPACE = 1 << 30       # bytes of the sparse solve's workspace: about 1 KiB a pose and 72 s^2 for s separators
+_COMPANIONS = dict(covariance="_cov", direct="_direct", sparse="_sparse")
 
 
 def _tolerances(who, given):
@@ -144,6 +145,8 @@ class PoseGraph:
         self._cov_bytes = 0
         self._direct = None        # the direct solve's object (optimize_direct), made at its first call
         self._direct_bytes = 0
+        self._sparse = None        # the sparse solve's object (optimize_sparse, sparse_layout), made at its first call
+        self._sparse_bytes = 0
         self.n = self.m = 0
         self.switchable = np.zeros(0, dtype=bool)
         self._create(int(max_nodes), int(max_constraints), int(max_jobs))
@@ -383,6 +386,37 @@ class PoseGraph:
         """(kernel_ms, fetch_ms) of the last optimize_direct call's last chunk (set_timing(True)): its iterations with the
         read-backs between them, and its final read-back."""
         return self._companion_last_ms("direct")
+
+    def optimize_sparse(self, masks=None, workspace_bytes=DEFAULT_SPARSE_WORKSPACE, **tolerances):
+        """optimize_direct's problem, LM rules, arguments, tolerances and result with the exact linear step taken sparsely
+        (include/ndt2d_hip.h, "Sparse solve"): the chain along the node order by one block cyclic reduction over the
+        interior nodes, the nodes closures touch (the separators) by a dense Cholesky of their Schur complement -- O(n) +
+        O(s^3) an iteration and no 3n x 3n matrix, for large maps with many closures.  workspace_bytes: the device memory
+        the jobs of a chunk may take; the object is made at the first call and again when this changes.  pivot_ratio is
+        the Schur complement's (1 without a closure); not_positive_definite counts the reduction's failures and its."""
+        tol = _tolerances("optimize_sparse", tolerances)
+        en, K = self._masks(masks)
+        sparse = self._companion("sparse", workspace_bytes)
+        poses = np.zeros((K, self.n, 3))
+        records = np.zeros((K, _capi.DIRECT_RECORD_DOUBLES))
+        chi2 = np.zeros((K, 2, self.m))
+        self._companion_check("sparse", self._L.ndt2d_sparse_solve(sparse, self._u8(en), K, *tol, dptr(poses), dptr(records), dptr(chi2)),
+                              "ndt2d_sparse_solve")
+        fields = (("iterations", int), ("rejected", int), ("not_positive_definite", int), ("initial_cost", float), ("final_cost", float),
+                  ("gradient", float), ("pivot_ratio", float))
+        return self._solved(poses, records, chi2, fields, self._weights(chi2[:, 1]) if self._loss[0] != "trivial" else None)
+
+    def sparse_layout(self, workspace_bytes=DEFAULT_SPARSE_WORKSPACE):
+        """dict(separators, interior): what the sparse solve's plan makes of the graph in place -- the nodes that are an
+        end of a constraint with |begin - end| != 1, and the others."""
+        sparse = self._companion("sparse", self._sparse_bytes if self._sparse is not None else workspace_bytes)
+        s, ni = C.c_size_t(0), C.c_size_t(0)
+        self._companion_check("sparse", self._L.ndt2d_sparse_layout(sparse, C.byref(s), C.byref(ni)), "ndt2d_sparse_layout")
+        return dict(separators=int(s.value), interior=int(ni.value))
+
+    def sparse_last_ms(self):
+        """(kernel_ms, fetch_ms) of the last optimize_sparse call's last chunk (set_timing(True))."""
+        return self._companion_last_ms("sparse")
 
     def marginals(self, nodes, masks=None, poses=None, damping=0.0, tolerance=1e-10, max_cg_iterations=0, want_columns=False):
         """Block columns of (H_FF + damping clamp(diag H_FF))^-1 for the query `nodes` [Q]
