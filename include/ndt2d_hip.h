@@ -1099,6 +1099,72 @@ int ndt2d_sparse_layout(ndt2d_sparse * sparse, size_t * n_separators, size_t * n
 int ndt2d_sparse_set_timing(ndt2d_sparse * sparse, int enabled);
 int ndt2d_sparse_last_ms(ndt2d_sparse * sparse, float * kernel_ms, float * fetch_ms);
 
+/* Sparse covariance (ndt2d_sparsecov_*: an object of its own beside an ndt2d_posegraph, which it
+ * refers to and is destroyed before).  "Dense covariance"'s call for the graphs "Sparse solve" is
+ * for: per job the 3 x 3 diagonal block of EVERY node and the blocks of chosen (a, b) pairs of
+ *     Sigma = (H_FF + damping clamp(diag H_FF))^-1,
+ * the matrix of "Dense covariance" -- the same H, weighting, loss, free set F and clamp, at the
+ * graph's poses (poses NULL) or at one [n][3] set per job -- in O(n) + O(s^3) for s separators and
+ * without a dense 3n x 3n matrix.  The arguments and the outputs are ndt2d_covariance_compute's, so
+ * that a caller can switch.
+ *     The factorisation is "Sparse solve"'s linear step at lambda = damping, launched as it is there:
+ * the interior block A_ii by the block cyclic reduction, Z = A_ii^-1 A_is by six columns through it,
+ * S = A_ss - A_si Z factored S = L L^T by "Dense covariance"'s blocked Cholesky, here followed by its
+ * inversion T = L^-1.  With i for interior and s for separator the blocks of the inverse are
+ *     Sigma_ss = S^-1,   Sigma_is = -Z Sigma_ss,   Sigma_ii = A_ii^-1 + Z Sigma_ss Z^T.
+ * An interior node k couples to the separator before it (u) and the one after it (w) only, so
+ *     Sigma_kk = G_kk + [Zl_k Zr_k] [Sigma_uu Sigma_uw; Sigma_wu Sigma_ww] [Zl_k Zr_k]^T,  G = A_ii^-1,
+ * a sum of two positive semidefinite terms.  The blocks of S^-1 are sums over T's rows, as the dense
+ * call's.  The diagonal blocks G_kk come from a selected inversion down the levels the reduction has
+ * factored: from the root's G_00 = P_0, for a node i eliminated at stride sigma into lo = i - sigma
+ * and hi = i + sigma, G_i,lo = -P_i (L_i^T G_lo,lo + U_i G_hi,lo), G_i,hi likewise, and
+ * G_i,i = P_i - (G_i,lo L_i + G_i,hi U_i^T) P_i: 24 doubles a node, one barrier a level.  A pair's
+ * block is Sigma_ab = C_a Sigma_{N(a), N(b)} C_b^T over the at most two separators each node reaches
+ * (C = the identity for a separator, -Zl and -Zr for an interior node), plus G_ab where both are
+ * interior nodes of one segment and a != b; G_ab is taken from a three-column solve A_ii^-1 E_b
+ * through the reduction, one pass per distinct such b.
+ *     The outputs.  diagonal_out[K][n][9] and pairs_out[K][P][9] with the dense call's meaning and
+ * layout: row-major, pairs[P][2] = {a, b} the rows of node a in the columns of node b, duplicates and
+ * a == b legal ((a, a) is the diagonal block), pairs and pairs_out may be NULL with n_pairs == 0.  A
+ * diagonal block is symmetric bit for bit (its upper triangle is computed and mirrored).  The block
+ * of (a, b) with a > b is returned as the transpose of the block computed for (b, a): the two are
+ * transposes bit for bit.  A block with a node not in F is zero.
+ * records_out[K][NDT2D_COVARIANCE_RECORD_DOUBLES] = {status, stage, the pivot ratio}: status is
+ * NDT2D_COVARIANCE_OK or NDT2D_COVARIANCE_NOT_POSITIVE_DEFINITE; stage is 0 for none, 1 for a pivot
+ * of the reduction, 2 for a pivot of S; the pivot ratio is S's, 1 when s = 0, as in "Sparse solve".
+ *     Not positive definite.  A job that fails has zero blocks; the other jobs of the call are
+ * untouched.  The reduction keeps no pivot ratio: for a singular matrix (a component not joined to
+ * the fixed pose at damping = 0) nothing is promised beyond a clean return with either status.
+ *     Determinism.  No atomics, every sum in a fixed order.  A job's diagonal does not depend on the
+ * pair list, the other jobs, the chunking, workspace_bytes or the run; a pair's block does not
+ * depend on the other pairs.
+ *     Memory.  Per job of a chunk "Sparse solve"'s doubles, 24 more per interior node, a second
+ * padded(3 s)^2 matrix (T), and 9 doubles per block of S^-1 that is wanted (2 s - 1, and at most four
+ * more per pair) and per pair: 8 (114 n_i + 2 padded(3 s)^2 + 2 padded(3 s) + 6 s + 9 blocks +
+ * 9 P + 41 n [+ m] + 17) bytes.  The workspace is allocated at the first compute (what the call's
+ * largest chunk needs, never more than workspace_bytes) and freed by destroy.  The jobs of a chunk
+ * share every launch.
+ *   create    NDT2D_ERR_INVALID: a NULL posegraph or out, workspace_bytes == 0.
+ *   compute   NDT2D_ERR_INVALID before anything runs, the message names the item: a NULL object
+ *             (no message), NULL diagonal_out or records_out, NULL pairs or pairs_out with
+ *             n_pairs > 0, a pair index >= n ("pair q names node i"), a non-finite pose ("job k pose
+ *             i"), a negative or non-finite damping, more than 21,840 separators, a graph of which
+ *             one job does not fit workspace_bytes (the message gives the bytes a job needs).
+ *             n_jobs == 0: NDT2D_OK, nothing done.  Before set_graph: NDT2D_ERR_STATE.
+ *   last_error   of a NULL object: "null sparsecov".
+ *   set_timing / last_ms   HIP events around the launches and the read-back of the last chunk. */
+typedef struct ndt2d_sparsecov ndt2d_sparsecov;
+int ndt2d_sparsecov_create(ndt2d_posegraph * posegraph, size_t workspace_bytes,
+                           ndt2d_sparsecov ** out);
+int ndt2d_sparsecov_destroy(ndt2d_sparsecov * sparsecov);
+const char * ndt2d_sparsecov_last_error(ndt2d_sparsecov * sparsecov);
+int ndt2d_sparsecov_compute(ndt2d_sparsecov * sparsecov, const uint8_t * enabled, size_t n_jobs,
+                            const double * poses, double damping, const uint32_t * pairs,
+                            size_t n_pairs, double * diagonal_out, double * pairs_out,
+                            double * records_out);
+int ndt2d_sparsecov_set_timing(ndt2d_sparsecov * sparsecov, int enabled);
+int ndt2d_sparsecov_last_ms(ndt2d_sparsecov * sparsecov, float * kernel_ms, float * fetch_ms);
+
 /* Upload the beam endpoints of one scan, robot frame, already subsampled to
  * min(laser_max_beams, points.size()) points by the caller
  * (src/scan_matcher_ndt.cpp:95-96,110 / :165-166,171).  Beams are taken as given: finite,

@@ -220,6 +220,12 @@ SIGNATURES = {
     "ndt2d_sparse_layout": (C.c_int, [_vp, C.POINTER(_sz), C.POINTER(_sz)]),
     "ndt2d_sparse_set_timing": (C.c_int, [_vp, C.c_int]),
     "ndt2d_sparse_last_ms": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "ndt2d_sparsecov_create": (C.c_int, [_vp, _sz, C.POINTER(_vp)]),
+    "ndt2d_sparsecov_destroy": (C.c_int, [_vp]),
+    "ndt2d_sparsecov_last_error": (C.c_char_p, [_vp]),
+    "ndt2d_sparsecov_compute": (C.c_int, [_vp, C.POINTER(C.c_uint8), _sz, _dp, _d, C.POINTER(_u32), _sz, _dp, _dp, _dp]),
+    "ndt2d_sparsecov_set_timing": (C.c_int, [_vp, C.c_int]),
+    "ndt2d_sparsecov_last_ms": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "ndt2d_set_eigenvalue_form": (C.c_int, [_vp, C.c_char_p]),
     "ndt2d_get_grid": (C.c_int, [_vp, _dp, _sz, C.POINTER(_u32), C.POINTER(_u32), _dp, _dp, _dp]),
     "ndt2d_clear_grid": (C.c_int, [_vp]),

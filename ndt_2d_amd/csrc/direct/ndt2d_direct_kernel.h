@@ -291,8 +291,9 @@ __global__ void __launch_bounds__(kPgThreads) direct_step_kernel(const PgGraph G
   if (threadIdx.x == 0) *chunk.state_of(job) = s;
 }
 
-//   direct_finish_kernel   grid (job), 256 threads: the job's poses and its record.
-__global__ void __launch_bounds__(kDirectFinishThreads) direct_finish_kernel(uint32_t n, const DirectChunk chunk, double * poses_out,
+//   direct_finish_kernel   grid (job), 256 threads: the job's poses and its record.  ([[maybe_unused]]:
+//       the sparse covariance's unit takes this header with the sparse solve's kernels and has no poses to return.)
+[[maybe_unused]] __global__ void __launch_bounds__(kDirectFinishThreads) direct_finish_kernel(uint32_t n, const DirectChunk chunk, double * poses_out,
                                                                              double * records)
 {
   const size_t job = blockIdx.x, d = 3 * static_cast<size_t>(n);

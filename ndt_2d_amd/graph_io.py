@@ -336,15 +336,17 @@ class Graph:
         per constraint, no policy; nothing of the graph changes.  `last_closure_distances` keeps
         the statuses and the predictions.  method="dense": the joint marginals from one
         PoseGraph.covariances call instead (a dense Cholesky, whose cost does not depend on the
-        closures; kw: its damping and workspace_bytes), the status then the job's, once."""
+        closures; kw: its damping and workspace_bytes), the status then the job's, once.
+        method="schur": the same from one PoseGraph.covariances_sparse call (the sparse solve's
+        factorisation: O(n) + O(s^3) for s nodes that closures touch, for maps the dense call cannot hold)."""
         from .pose_graph import PoseGraph, _inverse3, closure_distance, relative_covariance
         constraints = list(constraints)
         self.last_closure_distances = None
         if not constraints:
             return []
         poses = np.array([s.pose for s in self.scans], dtype=np.float64)
-        if method not in ("cg", "dense"):
-            raise ValueError("closure_distances: method = %r (\"cg\" or \"dense\")" % (method,))
+        if method not in ("cg", "dense", "schur"):
+            raise ValueError("closure_distances: method = %r (\"cg\", \"dense\" or \"schur\")" % (method,))
         nodes = sorted({int(c.begin) for c in constraints} | {int(c.end) for c in constraints})
         at = {v: i for i, v in enumerate(nodes)}
         pg = PoseGraph(matcher, max_nodes=len(self.scans), max_constraints=max(1, len(self.constraints)), max_jobs=max(1, len(nodes)))
@@ -352,9 +354,9 @@ class Graph:
             pg.set_weighting(weighting)
             pg.set_preconditioner(preconditioner)
             pg.set_graph(poses, self.constraints, fixed=0)
-            if method == "dense":
+            if method != "cg":
                 grid = [(a, b) for a in nodes for b in nodes]
-                dense = pg.covariances(pairs=grid, **kw)
+                dense = (pg.covariances if method == "dense" else pg.covariances_sparse)(pairs=grid, **kw)
                 got = dict(blocks=dense["pairs"][0].reshape(len(nodes), len(nodes), 3, 3), status=dense["status"],
                            cg_iterations=np.zeros(0, dtype=np.int64))
             else:

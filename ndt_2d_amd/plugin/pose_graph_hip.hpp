@@ -53,6 +53,7 @@ public:
     dropCovariance();
     dropDirect();
     dropSparse();
+    dropSparsecov();
     if (pg_ != nullptr) ndt2d_posegraph_destroy(pg_);
   }
 
@@ -262,7 +263,46 @@ public:
     return true;
   }
 
-  double pivotRatio() const { return pivot_ratio_; }            // of the last covariances()
+  // covariances() from the sparse solve's factorisation (include/ndt2d_hip.h, "Sparse covariance"): the
+  // same arguments and outputs at O(n) + O(s^3) for s scans that closures touch, without a 3 n x 3 n
+  // matrix -- for maps the dense call cannot hold.  false as covariances(); last_error() names the
+  // stage (a pivot of the reduction, or of the Schur complement), pivotRatio() is the Schur
+  // complement's (1 without a closure).
+  template <class Constraints, class Scans>
+  bool covariancesSparse(const Constraints & constraints, const Scans & scans, const std::vector<std::uint32_t> & pairs,
+                         std::vector<double> & diagonal_out, std::vector<double> & pairs_out, double damping = 0.0,
+                         std::size_t workspace_bytes = std::size_t(1) << 30)
+  {
+    diagonal_out.clear();
+    pairs_out.clear();
+    if (!stage(constraints, scans, 1)) return false;
+    const std::size_t n = poses_.size() / 3, p = pairs.size() / 2;
+    const auto make = [&] {
+      dropSparsecov();
+      return ndt2d_sparsecov_create(pg_, workspace_bytes, &sparsecov_);
+    };
+    if (!companion(sparsecov_, sparsecov_bytes_, workspace_bytes, "ndt2d_sparsecov_create", make)) return false;
+    diagonal_out.assign(n * 9, 0.0);
+    pairs_out.assign(p * 9, 0.0);
+    double rec[NDT2D_COVARIANCE_RECORD_DOUBLES] = {0.0, 0.0, 0.0};
+    const int rc = ndt2d_sparsecov_compute(sparsecov_, nullptr, 1, nullptr, damping, p != 0 ? pairs.data() : nullptr, p, diagonal_out.data(),
+                                           p != 0 ? pairs_out.data() : nullptr, rec);
+    if (rc != NDT2D_OK)
+    {
+      error_ = std::string("ndt2d error ") + std::to_string(rc) + ": " + ndt2d_sparsecov_last_error(sparsecov_);
+      return false;
+    }
+    pivot_ratio_ = rec[2];
+    if (static_cast<int>(rec[0]) != NDT2D_COVARIANCE_OK)
+    {
+      error_ = std::string("ndt2d_sparsecov_compute: not positive definite in a pivot of ") +
+               (static_cast<int>(rec[1]) == 1 ? "the reduction" : "the Schur complement");
+      return false;
+    }
+    return true;
+  }
+
+  double pivotRatio() const { return pivot_ratio_; }            // of the last covariances() or covariancesSparse()
   const PoseGraphRecord & record() const { return record_; }   // of the last optimize()
   const std::string & last_error() const { return error_; }
 
@@ -364,6 +404,7 @@ private:
       dropCovariance();   // (they refer to the object that goes)
       dropDirect();
       dropSparse();
+      dropSparsecov();
       if (pg_ != nullptr) ndt2d_posegraph_destroy(pg_);
       pg_ = nullptr;
       max_nodes_ = n > 2 * max_nodes_ ? n : 2 * max_nodes_;
@@ -463,6 +504,12 @@ private:
     sparse_ = nullptr;
   }
 
+  void dropSparsecov()
+  {
+    if (sparsecov_ != nullptr) ndt2d_sparsecov_destroy(sparsecov_);
+    sparsecov_ = nullptr;
+  }
+
   void dropCovariance()
   {
     if (cov_ != nullptr) ndt2d_covariance_destroy(cov_);
@@ -486,6 +533,8 @@ private:
   ndt2d_sparse * sparse_ = nullptr;    // made at the first optimize() under "sparse", destroyed before pg_
   std::size_t sparse_bytes_ = 0;
   bool sparse_solver_ = false;
+  ndt2d_sparsecov * sparsecov_ = nullptr;   // made at the first covariancesSparse(), destroyed before pg_
+  std::size_t sparsecov_bytes_ = 0;
   double pivot_ratio_ = 0.0;
   std::size_t max_nodes_ = 0, max_constraints_ = 0, max_jobs_ = 1;
   std::uint32_t max_iterations_ = 100;

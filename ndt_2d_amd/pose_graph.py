@@ -21,7 +21,8 @@ DEFAULT_DIRECT_WORKSPACE = 1 << 30       # bytes of the direct solve's workspace
 DEFAULT_TOLERANCES = dict(max_iterations=100, gradient_tolerance=1e-10, function_tolerance=1e-6, parameter_tolerance=1e-8)
 # the objects that stand beside the pose graph's, by the noun of their ndt2d_<noun>_* functions: the attribute with the handle
 DEFAULT_SPARSE_WORKSPACE = 1 << 30       # bytes of the sparse solve's workspace: about 1 KiB a pose and 72 s^2 for s separators
-_COMPANIONS = dict(covariance="_cov", direct="_direct", sparse="_sparse")
+DEFAULT_SPARSECOV_WORKSPACE = 1 << 30     # bytes of the sparse covariance's workspace: about 1.3 KiB a pose and 144 s^2 for s separators
+_COMPANIONS = dict(covariance="_cov", direct="_direct", sparse="_sparse", sparsecov="_sparsecov")
 
 
 def _tolerances(who, given):
@@ -147,6 +148,8 @@ class PoseGraph:
         self._direct_bytes = 0
         self._sparse = None        # the sparse solve's object (optimize_sparse, sparse_layout), made at its first call
         self._sparse_bytes = 0
+        self._sparsecov = None     # the sparse covariance's object (covariances_sparse), made at its first call
+        self._sparsecov_bytes = 0
         self.n = self.m = 0
         self.switchable = np.zeros(0, dtype=bool)
         self._create(int(max_nodes), int(max_constraints), int(max_jobs))
@@ -497,19 +500,60 @@ class PoseGraph:
         """(kernel_ms, fetch_ms) of the last covariances call's last chunk (set_timing(True))."""
         return self._companion_last_ms("covariance")
 
-    def relative_covariances(self, pairs, poses=None, mask=None, damping=0.0, workspace_bytes=DEFAULT_COVARIANCE_WORKSPACE):
+    def _covariance_call(self, noun, who, masks, poses, damping, pairs, workspace_bytes):
+        """The arguments and the outputs the dense and the sparse covariance share: (diagonal [K, n, 3, 3],
+        pairs [K, P, 3, 3], records [K, 3]) of ndt2d_<noun>_compute."""
+        en, K = self._masks(masks)
+        if poses is not None:
+            poses = np.ascontiguousarray(poses, dtype=np.float64)
+            if poses.size != K * self.n * 3:
+                raise ValueError("%s: poses has %d values, %d jobs of %d poses need %d" % (who, poses.size, K, self.n, K * self.n * 3))
+        pr = np.zeros((0, 2), dtype=np.uint32) if pairs is None else np.asarray(pairs).reshape(-1, 2)
+        if pr.size and not (0 <= int(pr.min()) and int(pr.max()) < 2 ** 32):
+            raise ValueError("%s: a pair names node %d" % (who, int(pr.min() if pr.min() < 0 else pr.max())))
+        pr = np.ascontiguousarray(pr, dtype=np.uint32)
+        P = len(pr)
+        obj = self._companion(noun, workspace_bytes)
+        diagonal = np.zeros((K, self.n, 3, 3))
+        blocks = np.zeros((K, P, 3, 3))
+        records = np.zeros((K, _capi.COVARIANCE_RECORD_DOUBLES))
+        rc = getattr(self._L, "ndt2d_%s_compute" % noun)(obj, self._u8(en), K, None if poses is None else dptr(poses), float(damping),
+                                                         pr.ctypes.data_as(C.POINTER(C.c_uint32)) if P else None, P, dptr(diagonal),
+                                                         dptr(blocks) if P else None, dptr(records))
+        self._companion_check(noun, rc, "ndt2d_%s_compute" % noun)
+        return diagonal, blocks, records
+
+    def covariances_sparse(self, masks=None, poses=None, damping=0.0, pairs=None, workspace_bytes=DEFAULT_SPARSECOV_WORKSPACE):
+        """covariances' blocks, arguments and layout from the sparse solve's factorisation (include/ndt2d_hip.h, "Sparse
+        covariance"): the chain by the block cyclic reduction and a selected inversion down its levels, the nodes closures
+        touch (the separators) by a dense Cholesky of their Schur complement and its inverse -- O(n) + O(s^3) and no
+        3n x 3n matrix, for large maps.  Returns dict(diagonal [K, n, 3, 3], pairs [K, P, 3, 3], status [K], stage [K]
+        (0: none, 1: a pivot of the reduction, 2: a pivot of the Schur complement), pivot_ratio [K] (the Schur
+        complement's, 1 without a closure))."""
+        diagonal, blocks, records = self._covariance_call("sparsecov", "covariances_sparse", masks, poses, damping, pairs, workspace_bytes)
+        return dict(diagonal=diagonal, pairs=blocks, status=records[:, 0].astype(np.int64), stage=records[:, 1].astype(np.int64),
+                    pivot_ratio=records[:, 2].copy())
+
+    def sparsecov_last_ms(self):
+        """(kernel_ms, fetch_ms) of the last covariances_sparse call's last chunk (set_timing(True))."""
+        return self._companion_last_ms("sparsecov")
+
+    def relative_covariances(self, pairs, poses=None, mask=None, damping=0.0, workspace_bytes=DEFAULT_COVARIANCE_WORKSPACE, method="dense"):
         """relative_covariance for every (a, b) of pairs [P, 2] from ONE covariances call: the joint
         marginal of each pair is {diagonal[a], block (a, b), block (b, a), diagonal[b]}, then
         ndt2d_marginals_relative per pair.  poses [n, 3]: where to linearise (required, as for
-        relative_covariance).  Returns a list of dict(transform [3], covariance [3, 3], joint
-        [2, 2, 3, 3], status: the job's)."""
+        relative_covariance).  method: "dense" (covariances) or "schur" (covariances_sparse).  Returns a
+        list of dict(transform [3], covariance [3, 3], joint [2, 2, 3, 3], status: the job's)."""
+        if method not in ("dense", "schur"):
+            raise ValueError("relative_covariances: method = %r (\"dense\" or \"schur\")" % (method,))
         if poses is None:
             raise ValueError("relative_covariances: poses [n, 3] (the poses the graph was given, or optimize's)")
         poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(self.n, 3)
         pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
         both = np.concatenate([pr, pr[:, ::-1]])
-        got = self.covariances(masks=None if mask is None else np.asarray(mask).reshape(1, -1), poses=poses[None], damping=damping, pairs=both,
-                               workspace_bytes=workspace_bytes)
+        call = self.covariances if method == "dense" else self.covariances_sparse
+        got = call(masks=None if mask is None else np.asarray(mask).reshape(1, -1), poses=poses[None], damping=damping, pairs=both,
+                   workspace_bytes=workspace_bytes)
         out = []
         for q, (a, b) in enumerate(pr):
             joint = np.array([[got["diagonal"][0, a], got["pairs"][0, q]], [got["pairs"][0, len(pr) + q], got["diagonal"][0, b]]])
