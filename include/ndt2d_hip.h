@@ -1569,6 +1569,77 @@ int ndt2d_occmap_read(ndt2d_occupancy_map * map, uint32_t x0, uint32_t y0, uint3
                       uint32_t h, signed char * out, size_t out_row_stride);
 /* bounds4_out = {min_x_, max_x_, min_y_, max_y_}, *num_scans_out = num_scans_. */
 int ndt2d_occmap_bounds(ndt2d_occupancy_map * map, double * bounds4_out, size_t * num_scans_out);
+/* Read-only: *d_map = the DEVICE row-major map of the last update and *info its geometry, once
+ * that update's trace is complete (the call waits for it).  The pointer is the object's own:
+ * valid until the next ndt2d_occmap_update, _reset or _destroy, never written through.  Before
+ * the first update NDT2D_ERR_STATE. */
+int ndt2d_occmap_device_map(ndt2d_occupancy_map * map, const signed char ** d_map,
+                            ndt2d_occupancy_info * info);
+
+/* ---- Global localisation: particles seeded over the map's free space ----
+ *
+ * The first step of a filter that does not know where it is (particles uniform over the free
+ * cells of an occupancy map, heading uniform) and the recovery step of augmented MCL (a share of
+ * a set replaced by fresh such particles).  An ndt2d_seeder is an object of its own beside the
+ * context: it owns the free table and a pinned word, launches on the context's current stream
+ * (ndt2d_set_stream) and must be destroyed before ndt2d_destroy(h).  Nothing here reads or writes
+ * weights, and nothing is a policy: when to inject, and how much, is the caller's.
+ *
+ * The free table.  A cell is free when its byte is exactly 0 (-1 unknown, 100 occupied and any
+ * stray value are not).  free_cells[F] holds the row-major indices y * width + x of the free
+ * cells of region4 = {x0, y0, w, h} (in cells; NULL = the whole map) in ascending order, as
+ * uint32, F = ndt2d_seed_free_count.  ndt2d_seed_set_map takes a HOST map as ndt2d_occmap_read
+ * gives it, ndt2d_seed_set_map_device a DEVICE one (ndt2d_occmap_device_map: nothing is
+ * uploaded); both return when the table is complete, so the map may change afterwards, and both
+ * replace the table of an earlier call.  Refused before anything runs, NDT2D_ERR_INVALID with a
+ * message naming the item, the seeder left as it was: a NULL seeder or map; width * height zero
+ * or >= 2^31; a resolution that is not finite and positive; an origin that is not finite; a
+ * region that leaves the map.  F == 0 is not an error here.
+ *
+ * A sample is a function of (seed, step, global particle index, table, geometry) and nothing
+ * else, so shards of a set draw what the whole set would (first_index, as in the noise calls).
+ * Particle i takes two Philox4x32-10 blocks with key = seed (the convention of
+ * ndt2d_pf_noise_launch): A = counter (first_index + i, step), B = counter (first_index + i,
+ * step + 1); a call consumes TWO steps.  With a0..a3 and b0..b3 their words:
+ *   u     = ((a0 >> 5) * 2^26 + (a1 >> 6)) * 2^-53          in [0, 1), the resampler's uniform
+ *   k     = min(F - 1, (uint64) (u * F))                    one double multiply, truncation
+ *   cell  = free_cells[k],  cx = cell mod width,  cy = cell / width
+ *   ux    = ((a2 >> 8) + 0.5) * 2^-24,  uy likewise from a3   exact, in (0, 1)
+ *   x     = origin_x + ((double) cx + ux) * resolution      add, multiply, add: three roundings,
+ *   y     = origin_y + ((double) cy + uy) * resolution      never contracted to a fused multiply-add
+ *   theta = -pi + (2 pi) * ((b0 >> 8) + 0.5) * 2^-24        pi the double M_PI, 2 pi = 2.0 * pi; one
+ *                                                           multiply, one add: in (-pi, pi)
+ *   v     = ((b1 >> 5) * 2^26 + (b2 >> 6)) * 2^-53          the inject draw
+ * ndt2d_seed_launch writes d_poses_xyt[n][3] (DEVICE), asynchronously.  ndt2d_seed_inject_launch
+ * writes particle i's sample exactly where v < probability and leaves every other particle's
+ * bits alone: probability in [0, 1] (anything else, NaN included, NDT2D_ERR_INVALID); 0 writes
+ * nothing; at 1 the poses are bit for bit ndt2d_seed_launch's.  *d_count (DEVICE, or NULL)
+ * receives the number replaced, reduced without atomics.  Both calls: n == 0 is NDT2D_OK;
+ * without a table NDT2D_ERR_STATE; with F == 0 NDT2D_ERR_STATE ("no free cell").
+ *
+ * ndt2d_seed_read_table copies the table to HOST out[capacity] (for tests and tools);
+ * *n_out = F also when out is too small (NDT2D_ERR_INVALID then).  ndt2d_seed_set_timing /
+ * _last_ms: HIP events round the three launches of the last set_map and round the last sample
+ * or inject launch (0 for the one that has not been timed; neither: NDT2D_ERR_STATE). */
+typedef struct ndt2d_seeder ndt2d_seeder;
+int ndt2d_seed_create(ndt2d_handle h, ndt2d_seeder ** out);
+int ndt2d_seed_destroy(ndt2d_seeder * seeder);
+const char * ndt2d_seed_last_error(ndt2d_seeder * seeder);
+int ndt2d_seed_set_map(ndt2d_seeder * seeder, const signed char * map, uint32_t width,
+                       uint32_t height, double origin_x, double origin_y, double resolution,
+                       const uint32_t * region4);
+int ndt2d_seed_set_map_device(ndt2d_seeder * seeder, const signed char * d_map, uint32_t width,
+                              uint32_t height, double origin_x, double origin_y,
+                              double resolution, const uint32_t * region4);
+int ndt2d_seed_free_count(ndt2d_seeder * seeder, size_t * n_out);
+int ndt2d_seed_read_table(ndt2d_seeder * seeder, uint32_t * out, size_t capacity, size_t * n_out);
+int ndt2d_seed_launch(ndt2d_seeder * seeder, double * d_poses_xyt, size_t n, uint64_t seed,
+                      uint64_t step, uint64_t first_index);
+int ndt2d_seed_inject_launch(ndt2d_seeder * seeder, double * d_poses_xyt, size_t n,
+                             double probability, uint64_t seed, uint64_t step,
+                             uint64_t first_index, uint64_t * d_count);
+int ndt2d_seed_set_timing(ndt2d_seeder * seeder, int enabled);
+int ndt2d_seed_last_ms(ndt2d_seeder * seeder, float * table_ms, float * sample_ms);
 
 /* ---- device memory for hosts without a GPU runtime of their own ----
  *

@@ -286,6 +286,18 @@ SIGNATURES = {
     "ndt2d_occmap_update": (C.c_int, [_vp, _dp, _sz, C.POINTER(OccmapResult)]),
     "ndt2d_occmap_read": (C.c_int, [_vp, _u32, _u32, _u32, _u32, _vp, _sz]),
     "ndt2d_occmap_bounds": (C.c_int, [_vp, _dp, _szp]),
+    "ndt2d_occmap_device_map": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(OccupancyInfo)]),
+    "ndt2d_seed_create": (C.c_int, [_vp, C.POINTER(_vp)]),
+    "ndt2d_seed_destroy": (C.c_int, [_vp]),
+    "ndt2d_seed_last_error": (C.c_char_p, [_vp]),
+    "ndt2d_seed_set_map": (C.c_int, [_vp, _vp, _u32, _u32, _d, _d, _d, C.POINTER(_u32)]),
+    "ndt2d_seed_set_map_device": (C.c_int, [_vp, _vp, _u32, _u32, _d, _d, _d, C.POINTER(_u32)]),
+    "ndt2d_seed_free_count": (C.c_int, [_vp, _szp]),
+    "ndt2d_seed_read_table": (C.c_int, [_vp, C.POINTER(_u32), _sz, _szp]),
+    "ndt2d_seed_launch": (C.c_int, [_vp, _vp, _sz, _u64, _u64, _u64]),
+    "ndt2d_seed_inject_launch": (C.c_int, [_vp, _vp, _sz, _d, _u64, _u64, _u64, _vp]),
+    "ndt2d_seed_set_timing": (C.c_int, [_vp, C.c_int]),
+    "ndt2d_seed_last_ms": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "ndt2d_device_alloc": (C.c_int, [_vp, _sz, C.POINTER(_vp)]),
     "ndt2d_device_free": (C.c_int, [_vp, _vp]),
     "ndt2d_copy_to_device": (C.c_int, [_vp, _vp, _vp, _sz]),

@@ -864,6 +864,23 @@ int ndt2d_occmap_read(ndt2d_occupancy_map * m, uint32_t x0, uint32_t y0, uint32_
   NDT2D_C_CATCH(m)
 }
 
+int ndt2d_occmap_device_map(ndt2d_occupancy_map * m, const signed char ** d_map, ndt2d_occupancy_info * info)
+{
+  NDT2D_C_TRY
+  if (m == nullptr) return NDT2D_ERR_INVALID;
+  if (d_map == nullptr || info == nullptr) return mfail(m, NDT2D_ERR_INVALID, "ndt2d_occmap_device_map: null argument");
+  *d_map = nullptr;
+  if (!m->have_map) return mfail(m, NDT2D_ERR_STATE, "ndt2d_occmap_device_map: no map (no update yet, or the last one failed)");
+  hipStream_t stream;
+  const int rc = current_stream(m, &stream);
+  if (rc != NDT2D_OK) return rc;
+  NDT2D_MHIP(m, hipStreamSynchronize(stream));   // the last update's trace and finalize are complete
+  *d_map = m->d_data;
+  *info = m->geo;
+  return NDT2D_OK;
+  NDT2D_C_CATCH(m)
+}
+
 int ndt2d_occmap_bounds(ndt2d_occupancy_map * m, double * bounds4_out, size_t * num_scans_out)
 {
   NDT2D_C_TRY

@@ -82,6 +82,16 @@ class OccupancyMap:
     def num_scans(self):
         return self._state()[1]
 
+    def device_map(self):
+        """(DEVICE address of the int8 map of the last getMsg, its _capi.OccupancyInfo): the resident
+        map for a consumer on the same GPU (Seeder.set_occupancy_map), valid until the next getMsg,
+        reset or close."""
+        ptr = C.c_void_p()
+        info = _capi.OccupancyInfo()
+        self._check(self._L.ndt2d_occmap_device_map(self._map, C.byref(ptr), C.byref(info)),
+                    "ndt2d_occmap_device_map")
+        return ptr.value, info
+
     def reset(self):
         """A new generator: scans, counters and bounds are forgotten."""
         self._check(self._L.ndt2d_occmap_reset(self._map), "ndt2d_occmap_reset")

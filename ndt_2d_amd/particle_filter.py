@@ -93,6 +93,40 @@ def kld_resample_native(particles, weights, min_particles, max_particles, kld_er
     return out[:n_out.value].copy()
 
 
+class RecoveryAverages:
+    """The short- and long-term averages of augmented MCL (Thrun, Burgard, Fox, Probabilistic
+    Robotics, table 8.3) from the mean unnormalised weight of each `measure`
+    (ParticleFilter.mean_measure_weight()):
+
+        w_slow += alpha_slow (w_avg - w_slow),   w_fast += alpha_fast (w_avg - w_fast),
+
+    both started at the first w_avg.  update(w_avg) returns max(0, 1 - w_fast / w_slow), the share
+    of the set to hand to ParticleFilter.inject.  The reference's score is the NEGATED mean
+    likelihood (src/scan_matcher_ndt.cpp:174), so its w_avg is <= 0; the ratio is the same for
+    either sign, as long as every w_avg has the same one.  Host arithmetic only.  This class is the
+    only policy in the package; it is optional and nothing calls it by default."""
+
+    def __init__(self, alpha_slow, alpha_fast):
+        if not 0.0 <= alpha_slow <= alpha_fast <= 1.0:
+            raise ValueError("0 <= alpha_slow <= alpha_fast <= 1 is required")
+        self.alpha_slow = float(alpha_slow)
+        self.alpha_fast = float(alpha_fast)
+        self.w_slow = None
+        self.w_fast = None
+
+    def update(self, w_avg):
+        w_avg = float(w_avg)
+        if self.w_slow is None:
+            self.w_slow = self.w_fast = w_avg
+        else:
+            self.w_slow += self.alpha_slow * (w_avg - self.w_slow)
+            self.w_fast += self.alpha_fast * (w_avg - self.w_fast)
+        if self.w_slow == 0.0:
+            return 0.0
+        share = 1.0 - self.w_fast / self.w_slow
+        return max(0.0, share) if share == share else 0.0
+
+
 class ParticleFilter:
     """ndt_2d::ParticleFilter over the MI355X kernels.  `matcher` supplies the device
     context (an ndt_2d_amd.ScanMatcherNDT); `seed` keys the Philox noise stream
@@ -142,6 +176,8 @@ class ParticleFilter:
                                       dtype=torch.float64, device=self.device)
         self._mean = np.zeros(3)
         self._cov = np.zeros((3, 3))
+        self._seeder = None
+        self._measure_total = None
         self._update_statistics(have_moments=False)
 
     # -- reference interface ------------------------------------------------------------
@@ -212,6 +248,64 @@ class ParticleFilter:
             self.weights = out_w[:n_keep]
         self._update_statistics(have_moments=False)
 
+    # -- global localisation (not in the reference) -----------------------------------------
+
+    def _seeder_for(self, map_source, region):
+        """The filter's Seeder with its table made from `map_source`."""
+        from .occupancy_map import OccupancyMap
+        from .seeder import Seeder
+        if self._seeder is None:
+            self._seeder = Seeder(self._matcher)
+        if isinstance(map_source, OccupancyMap):
+            self._seeder.set_occupancy_map(map_source, region)
+        else:
+            grid, origin_x, origin_y, resolution = map_source
+            self._seeder.set_map(grid, origin_x, origin_y, resolution, region)
+        return self._seeder
+
+    def init_global(self, map_source, n=None, region=None):
+        """The set becomes `n` (default max_particles) particles uniform over the free cells (byte
+        0) of the map, heading uniform in (-pi, pi), weights 1/n.  map_source: an OccupancyMap (its
+        resident map, nothing uploaded) or (int8 array [h, w], origin_x, origin_y, resolution);
+        region = (x0, y0, w, h) in cells restricts the cells.  Consumes two steps of the counter.
+        The map is kept as this filter's free table for inject()."""
+        torch = self._torch
+        n = self.max_particles if n is None else int(n)
+        if n <= 0:
+            raise ValueError("init_global needs at least one particle")
+        seeder = self._seeder_for(map_source, region)
+        step = self._next_step()
+        self._next_step()
+        with torch.cuda.stream(self._stream):
+            particles = torch.empty((n, 3), dtype=torch.float64, device=self.device)
+            seeder.launch(particles.data_ptr(), n, self.seed, step, 0)
+            self.particles = particles
+            self.weights = torch.full((n,), 1.0 / n, dtype=torch.float64, device=self.device)
+        self._update_statistics(have_moments=False)
+
+    def inject(self, probability):
+        """Augmented MCL's recovery step: every particle is replaced, with `probability`, by a fresh
+        sample over the free table of the last init_global.  Weights are not touched (the next
+        measure overwrites them).  Consumes two steps; returns the number replaced."""
+        torch = self._torch
+        if self._seeder is None:
+            raise _capi.Ndt2dError(_capi.ERR_STATE, "ParticleFilter.inject", "no free table: call init_global first")
+        step = self._next_step()
+        self._next_step()
+        with torch.cuda.stream(self._stream):
+            count = torch.zeros((1,), dtype=torch.int64, device=self.device)
+            self._seeder.inject_launch(self.particles.data_ptr(), len(self.particles), probability, self.seed,
+                                       step, 0, count.data_ptr())
+            replaced = int(count.cpu().item())
+        self._update_statistics(have_moments=False)
+        return replaced
+
+    def mean_measure_weight(self):
+        """The mean unnormalised weight of the last measure (the total pf_finalize reduces, over n):
+        the w_avg of RecoveryAverages.  It has the sign of the reference's scores (<= 0: the negated
+        mean likelihood).  None before the first measure."""
+        return self._measure_total
+
     def getMean(self):
         return self._mean.copy()
 
@@ -244,6 +338,8 @@ class ParticleFilter:
         with self._torch.cuda.stream(self._stream):
             out = st[_capi.POSE_STATS_DOUBLES:].cpu().numpy()
         self._stream.synchronize()
+        if have_moments:
+            self._measure_total = float(out[0]) / n
         self._mean = out[1:4].copy()
         c = self._cov
         c[0, 0] = out[4]

@@ -62,6 +62,8 @@ public:
 
   ~ParticleFilterHip()
   {
+    if (seeder_ != nullptr) ndt2d_seed_destroy(seeder_);
+    ndt2d_device_free(dev_, d_count_);
     ndt2d_device_free(dev_, d_particles_);
     ndt2d_device_free(dev_, d_weights_);
     ndt2d_device_free(dev_, d_stats_);
@@ -142,6 +144,58 @@ public:
     updateStatistics(false);
   }
 
+  // Global localisation (not in the reference; include/ndt2d_hip.h "Global localisation"): the set
+  // becomes n particles (0 = max_particles) uniform over the free cells (byte 0) of a HOST
+  // row-major int8 map, heading uniform, weights 1 / n.  region4 = {x0, y0, w, h} in cells or
+  // nullptr.  Consumes two steps of the counter; the map stays this filter's free table for inject.
+  void initGlobal(const signed char * map, std::uint32_t width, std::uint32_t height, double origin_x,
+                  double origin_y, double resolution, std::size_t n = 0,
+                  const std::uint32_t * region4 = nullptr)
+  {
+    if (!seeder()) return;
+    seedCheck(ndt2d_seed_set_map(seeder_, map, width, height, origin_x, origin_y, resolution, region4));
+    seedFrom(n);
+  }
+  // The same from the resident map of an ndt2d_occupancy_map's last update: nothing is uploaded.
+  void initGlobal(ndt2d_occupancy_map * resident, std::size_t n = 0, const std::uint32_t * region4 = nullptr)
+  {
+    if (!seeder()) return;
+    const signed char * d_map = nullptr;
+    ndt2d_occupancy_info info;
+    check(ndt2d_occmap_device_map(resident, &d_map, &info));
+    if (!ok_) return;
+    seedCheck(ndt2d_seed_set_map_device(seeder_, d_map, info.width, info.height, info.origin_x, info.origin_y,
+                                        info.resolution, region4));
+    seedFrom(n);
+  }
+
+  // Augmented MCL's recovery step: every particle is replaced, with `probability`, by a fresh sample
+  // over the free table of the last initGlobal.  Weights are not touched.  Consumes two steps;
+  // returns the number replaced.
+  std::size_t inject(double probability)
+  {
+    if (seeder_ == nullptr && ok_)
+    {
+      ok_ = false;
+      error_ = "inject: no free table, call initGlobal first";
+    }
+    if (!ok_) return 0;
+    if (d_count_ == nullptr)
+    {
+      void * p = nullptr;
+      check(ndt2d_device_alloc(dev_, sizeof(std::uint64_t), &p));
+      d_count_ = static_cast<std::uint64_t *>(p);
+    }
+    if (!ok_) return 0;
+    const std::uint64_t step = step_ + 1;
+    step_ += 2;
+    seedCheck(ndt2d_seed_inject_launch(seeder_, d_particles_, n_, probability, seed_, step, 0, d_count_));
+    std::uint64_t replaced = 0;
+    check(ndt2d_copy_to_host(dev_, &replaced, d_count_, sizeof(replaced)));
+    updateStatistics(false);
+    return ok_ ? static_cast<std::size_t>(replaced) : 0;
+  }
+
   void getMean(double * mean3) const { std::copy(mean_, mean_ + 3, mean3); }
   void getCovariance(double * cov9) const { std::copy(cov_, cov_ + 9, cov9); }
 
@@ -172,6 +226,36 @@ private:
       ok_ = false;
       error_ = std::string("ndt2d error ") + std::to_string(rc) + ": " + ndt2d_last_error(dev_);
     }
+  }
+
+  bool seeder()
+  {
+    if (seeder_ == nullptr && ok_) check(ndt2d_seed_create(dev_, &seeder_));
+    return ok_;
+  }
+
+  void seedCheck(int rc)
+  {
+    if (rc != NDT2D_OK && ok_)
+    {
+      ok_ = false;
+      error_ = std::string("ndt2d error ") + std::to_string(rc) + ": " + ndt2d_seed_last_error(seeder_);
+    }
+  }
+
+  // n fresh particles from the seeder's table, weights 1 / n, statistics
+  void seedFrom(std::size_t n)
+  {
+    if (!ok_) return;
+    if (n == 0) n = max_particles_;
+    resize(n);
+    if (!ok_ || n_ == 0) return;
+    const std::uint64_t step = step_ + 1;
+    step_ += 2;
+    seedCheck(ndt2d_seed_launch(seeder_, d_particles_, n_, seed_, step, 0));
+    std::vector<double> w(n_, 1.0 / static_cast<double>(n_));
+    check(ndt2d_copy_to_device(dev_, d_weights_, w.data(), w.size() * sizeof(double)));
+    updateStatistics(false);
   }
 
   void resize(std::size_t n)
@@ -224,6 +308,8 @@ private:
   std::uint64_t seed_, step_ = 0;
   std::mt19937 gen_;
   double * d_particles_ = nullptr, * d_weights_ = nullptr, * d_stats_ = nullptr;
+  ndt2d_seeder * seeder_ = nullptr;
+  std::uint64_t * d_count_ = nullptr;
   std::size_t n_ = 0, capacity_ = 0;
   double mean_[3] = {0.0, 0.0, 0.0};
   double cov_[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};

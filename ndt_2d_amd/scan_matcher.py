@@ -177,6 +177,8 @@ class ScanMatcherNDT:
                 r.close()
             for o in list(getattr(self, "_occupancy_maps", ())):
                 o.close()
+            for o in list(getattr(self, "_seeders", ())):
+                o.close()
             self._L.ndt2d_matcher_destroy(self._m)
             self._m = None
 
