@@ -306,6 +306,80 @@ int ndt2d_starts_match(ndt2d_starts * starts, const double * starts_xyt, size_t 
 int ndt2d_starts_set_timing(ndt2d_starts * starts, int enabled);
 int ndt2d_starts_last_ms(ndt2d_starts * starts, float * search_ms, float * reduce_ms);
 
+/* ---- wide search: the exhaustive lattice's winner by tile bounds (csrc/wide/) ----
+ *
+ * One scan, the grid INSTALLED in the context, one pose, a lattice too large to score whole (a
+ * window of metres and radians for relocalisation or a loop closure after drift).  The record is
+ * the one ndt2d_starts_match gives for this start on the same beams, dth and dlin -- best_score bit
+ * for bit, the same best_index, the same near-tie mark -- but most candidates are never scored:
+ *   image    pixel (i, j) of an image with origin grid origin - (W + P) and pitch P holds an upper
+ *            bound on Cell::score(p) over the box [x_i - g, x_i + P + W + g] x [y_j - g, y_j + P + W + g],
+ *            g = 1e-9 m: over the cells with n >= 5 the box touches, exp of the exact maximum of the
+ *            cell's exponent over box and cell (each inflated by g), times 1 + 2^-40, plus 2^-1000
+ *            (for values exp() leaves subnormal, where a relative inflation does nothing); 0
+ *            where the box touches none.  A cell with a non-finite record is left out: a candidate that touches
+ *            one scores NaN and cannot win.  FP64 in device memory.
+ *   tiles    with tile_steps T the translation lattice of a theta step is cut into the index windows
+ *            [ix0, min(ix0 + T, n_lin)) x [iy0, min(iy0 + T, n_lin)); a tile job is (theta step,
+ *            tile), job = (ith * n_tiles + ix0 / T) * n_tiles + iy0 / T.  W is the widest
+ *            dlin[last] - dlin[first] over the windows, P = max(W, cell_size / 4) / pixels_per_tile.
+ *   bounds   a job's bound: every beam rotated as the searches rotate it, moved by (dlin[ix0],
+ *            dlin[iy0]), looked up in the image (off the image, or NaN: 0), summed in FP64 in a
+ *            fixed order.  It is never below the raw likelihood sum of a candidate of the tile.
+ *   order    the jobs sorted by bound, descending; equal bounds in ascending job order.
+ *   rounds   the sorted jobs are scored exactly in chunks (64, 128, ... up to max_tiles), a block
+ *            per tile job; after each chunk one small read-back.  The call ends when the next
+ *            bound is strictly below best_sum * (1 - 2^-35): every candidate within the near-tie
+ *            tolerance (NDT2D_NEAR_TIE_REL) of the winner has been scored by then.  No winner yet
+ *            (a map without cells): every tile is scored, the index is -1.
+ * The covariance sums acc[10] need every candidate and are NOT made: a covariance for the winner
+ * comes from ndt2d_refine (neighbourhood 9).  A near tie is marked, not settled.
+ * An object of its own beside the context, as ndt2d_starts: it reads the grid installed at the
+ * time of the call, installs nothing, launches on the context's current stream, and must be
+ * destroyed before ndt2d_destroy(h).
+ *
+ *   create   max_tiles (1 .. 2^24): tile jobs of one exact launch at most.
+ *   set_tile / tile   tile_steps 1 .. 32 (default NDT2D_WIDE_DEFAULT_TILE_STEPS), pixels_per_tile
+ *            1 .. 8 (default NDT2D_WIDE_DEFAULT_PIXELS_PER_TILE); anything else: NDT2D_ERR_INVALID,
+ *            the values stay.
+ *   match    pose_xyt[3]; beams_xy: the subsampled robot-frame beams; dth[n_th] / dlin[n_lin] as
+ *            for ndt2d_starts_match, dlin strictly ascending.  record_out[2] = {best_score,
+ *            best_index (-1: none; + 0.5: near tie)} with the flat index of the FULL lattice
+ *            (ith * n_lin^2 + ix * n_lin + iy); stats_out[2] (optional) = {tile jobs scored, tile
+ *            jobs in all}; bounds_out[n_th * n_tiles^2] (optional) every job's bound;
+ *            evaluated_out (optional) a byte per job, 1 = scored.  reuse_image = 1 is the caller's
+ *            statement that the installed grid is that of this object's previous call: the image
+ *            is kept when W and P are the same too.  Otherwise it is made inside the call: one more
+ *            launch, no synchronisation.  Two calls give the same bits and score the same tiles.
+ *            Refused before anything is launched (NDT2D_ERR_INVALID unless said otherwise), the
+ *            message names the remedy: a non-finite pose; no grid (NDT2D_ERR_NO_GRID); a lattice or
+ *            beam count ndt2d_set_search / ndt2d_set_beams refuse; dlin not strictly ascending; an
+ *            image of more than 2^26 pixels; a box that spans more than 8 x 8 cells (the tile is then
+ *            too coarse to prune anything); 2^31 tile jobs or more.
+ *   read_image   info_out[8] = {nx, ny, origin_x, origin_y, P, W, g, 0} of the last image made and,
+ *            data_out != NULL, its nx * ny values, row j after row j - 1 (capacity in doubles; too
+ *            small: NDT2D_ERR_INVALID).  Before the first match: NDT2D_ERR_STATE.
+ *   set_timing / last_ms   HIP events round the image, the bounds, the sort and the exact rounds
+ *            (with their read-backs) of the last match, off by default. */
+/* (measured: experiments/wide_search_timing.py; at linear resolutions coarser than 0.05 m fewer tile
+ * steps keep a box within 8 x 8 cells of 0.25 m) */
+#define NDT2D_WIDE_DEFAULT_TILE_STEPS 16
+#define NDT2D_WIDE_DEFAULT_PIXELS_PER_TILE 4
+typedef struct ndt2d_wide ndt2d_wide;
+int ndt2d_wide_create(ndt2d_handle h, size_t max_tiles, ndt2d_wide ** out);
+int ndt2d_wide_destroy(ndt2d_wide * wide);
+const char * ndt2d_wide_last_error(ndt2d_wide * wide);
+int ndt2d_wide_set_tile(ndt2d_wide * wide, uint32_t tile_steps, uint32_t pixels_per_tile);
+int ndt2d_wide_tile(ndt2d_wide * wide, uint32_t * tile_steps, uint32_t * pixels_per_tile);
+int ndt2d_wide_match(ndt2d_wide * wide, const double * pose_xyt, const double * beams_xy, size_t n_beams,
+                     const double * dth, size_t n_th, const double * dlin, size_t n_lin, int reuse_image,
+                     double * record_out, uint64_t * stats_out, double * bounds_out,
+                     uint8_t * evaluated_out);
+int ndt2d_wide_read_image(ndt2d_wide * wide, double * info_out, double * data_out, size_t capacity);
+int ndt2d_wide_set_timing(ndt2d_wide * wide, int enabled);
+int ndt2d_wide_last_ms(ndt2d_wide * wide, float * image_ms, float * bounds_ms, float * sort_ms,
+                       float * exact_ms);
+
 /* ---- batched scan tracking: K scans, each from its own pose (csrc/scans/) ----
  *
  * A job is a (scan, pose) pair; a call takes S scans and K jobs against the grid INSTALLED in the
@@ -1895,6 +1969,29 @@ int ndt2d_matcher_match_starts(ndt2d_matcher * m, const double * starts_xyt, siz
 /* The batched call's object (made by the first match_starts with an NDT in place; NULL before), for
  * ndt2d_starts_set_timing / _last_ms. */
 ndt2d_starts * ndt2d_matcher_starts(ndt2d_matcher * m);
+/* matchScan over a lattice of the CALL's sizes -- linear_size / linear_res, angular_size /
+ * angular_res, the offsets of ndt2d_search_offsets -- against the NDT in place, by the wide search
+ * (ndt2d_wide_match on the first device): what replaces matchScan where the window is metres wide.
+ * The scan is subsampled with the matcher's laser_max_beams as matchScan subsamples it; the
+ * matcher's own lattice is not touched.  tile_steps == 0 keeps the object's tile steps.
+ * pose_out[3] = the winner's (dx, dy, dtheta) correction (written only with a winner), *score_out =
+ * best / N (:148), *best_index_out = its flat index in the call's lattice (NDT2D_NO_INDEX: none),
+ * *near_tie_out = 1 when another candidate lies within the near-tie tolerance (marked, not
+ * settled), stats_out[2] = {tile jobs scored, tile jobs in all}; all optional but score_out.  No
+ * covariance: the sums need every candidate (ndt2d_matcher_refine_scans with neighbourhood 9 on
+ * the winner gives one).  The bound image is kept between calls while the matcher has not built,
+ * installed or dropped an NDT in between.  No NDT in place: score 0.0, nothing else written.
+ * A search launched ahead by score_scan is waited out and dropped first.  NDT2D_ERR_INVALID,
+ * nothing launched: a non-finite pose, sizes or resolutions ndt2d_search_offsets refuses, what
+ * ndt2d_wide_match refuses (its message follows "match_wide: "). */
+int ndt2d_matcher_match_wide(ndt2d_matcher * m, const double * scan_pose_xyt, const double * points_xy,
+                             size_t n_points, double linear_size, double linear_res,
+                             double angular_size, double angular_res, uint32_t tile_steps,
+                             double * pose_out, double * score_out, uint64_t * best_index_out,
+                             int * near_tie_out, uint64_t * stats_out);
+/* The wide search's object (made by the first match_wide with an NDT in place; NULL before), for
+ * ndt2d_wide_set_tile / _set_timing / _last_ms. */
+ndt2d_wide * ndt2d_matcher_wide(ndt2d_matcher * m);
 /* matchScan of K jobs -- (scan, pose) pairs -- against the NDT in place, in one call
  * (ndt2d_scans_match with the matcher's own parameters, on the first device): the localisation
  * branch (src/ndt_mapper.cpp:547-566) for a fleet on one map, a replayed bag, a graph's scans

@@ -154,6 +154,17 @@ SIGNATURES = {
     "ndt2d_starts_match": (C.c_int, [_vp, _dp, _sz, _dp, _sz, _dp, _sz, _dp, _sz, _dp, _dp]),
     "ndt2d_starts_set_timing": (C.c_int, [_vp, C.c_int]),
     "ndt2d_starts_last_ms": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "ndt2d_wide_create": (C.c_int, [_vp, _sz, C.POINTER(_vp)]),
+    "ndt2d_wide_destroy": (C.c_int, [_vp]),
+    "ndt2d_wide_last_error": (C.c_char_p, [_vp]),
+    "ndt2d_wide_set_tile": (C.c_int, [_vp, _u32, _u32]),
+    "ndt2d_wide_tile": (C.c_int, [_vp, C.POINTER(_u32), C.POINTER(_u32)]),
+    "ndt2d_wide_match": (C.c_int, [_vp, _dp, _dp, _sz, _dp, _sz, _dp, _sz, C.c_int, _dp, C.POINTER(_u64), _dp,
+                                   C.POINTER(C.c_uint8)]),
+    "ndt2d_wide_read_image": (C.c_int, [_vp, _dp, _dp, _sz]),
+    "ndt2d_wide_set_timing": (C.c_int, [_vp, C.c_int]),
+    "ndt2d_wide_last_ms": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                     C.POINTER(C.c_float)]),
     "ndt2d_scans_create": (C.c_int, [_vp, _sz, C.POINTER(_vp)]),
     "ndt2d_scans_destroy": (C.c_int, [_vp]),
     "ndt2d_scans_last_error": (C.c_char_p, [_vp]),
@@ -348,6 +359,9 @@ SIGNATURES = {
     "ndt2d_matcher_match_starts": (C.c_int, [_vp, _dp, _sz, _dp, _sz, _dp, _dp, _dp, C.POINTER(C.c_uint64), _dp, _sz,
                                              _szp]),
     "ndt2d_matcher_starts": (_vp, [_vp]),
+    "ndt2d_matcher_match_wide": (C.c_int, [_vp, _dp, _dp, _sz, _d, _d, _d, _d, _u32, _dp, _dp, C.POINTER(_u64),
+                                           C.POINTER(C.c_int), C.POINTER(_u64)]),
+    "ndt2d_matcher_wide": (_vp, [_vp]),
     "ndt2d_matcher_match_scans": (C.c_int, [_vp, _dp, C.POINTER(_u32), _sz, _dp, _szp, _sz, _dp, _dp, _dp,
                                             C.POINTER(C.c_uint64), _dp, _sz, _szp]),
     "ndt2d_matcher_scans": (_vp, [_vp]),

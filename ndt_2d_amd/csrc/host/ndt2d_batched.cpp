@@ -353,6 +353,81 @@ int ndt2d_matcher_match_starts(ndt2d_matcher * m, const double * starts_xyt, siz
 
 ndt2d_starts * ndt2d_matcher_starts(ndt2d_matcher * m) { return m != nullptr ? m->starts : nullptr; }
 
+// Tile jobs the wide search scores in one launch at most (its chunks double up to this).
+static constexpr size_t kWideMaxTiles = size_t(1) << 16;
+
+int ndt2d_matcher_match_wide(ndt2d_matcher * m, const double * scan_pose_xyt, const double * points_xy, size_t n_points,
+                             double linear_size, double linear_res, double angular_size, double angular_res,
+                             uint32_t tile_steps, double * pose_out, double * score_out, uint64_t * best_index_out,
+                             int * near_tie_out, uint64_t * stats_out)
+{
+  NDT2D_C_TRY
+  if (m == nullptr) return NDT2D_ERR_INVALID;
+  if (scan_pose_xyt == nullptr || score_out == nullptr || (n_points > 0 && points_xy == nullptr))
+  {
+    return mfail(m, NDT2D_ERR_INVALID, "match_wide: null input");
+  }
+  *score_out = 0.0;
+  if (best_index_out != nullptr) *best_index_out = NDT2D_NO_INDEX;
+  if (near_tie_out != nullptr) *near_tie_out = 0;
+  if (stats_out != nullptr) stats_out[0] = stats_out[1] = 0;
+  // `if (!ndt_) return 0.0;` (reference src/scan_matcher_ndt.cpp:80)
+  if (!m->ndt.have()) return NDT2D_OK;
+  if (!std::isfinite(scan_pose_xyt[0]) || !std::isfinite(scan_pose_xyt[1]) || !std::isfinite(scan_pose_xyt[2]))
+  {
+    return mfail(m, NDT2D_ERR_INVALID, "match_wide: a non-finite scan pose");
+  }
+  if (!offsets_fit(linear_size, linear_res, 46340) || !offsets_fit(angular_size, angular_res, 1u << 24))
+  {
+    return mfail(m, NDT2D_ERR_INVALID, "match_wide: the sizes and resolutions give no lattice ndt2d_set_search takes");
+  }
+  const std::vector<double> dlin = search_offsets(linear_size, linear_res), dth = search_offsets(angular_size, angular_res);
+  discard_ahead(m);   // a search launched ahead by scoreScan is waited out and dropped
+  // the scan as matchScan takes it: subsampled beams (:95-96,110)
+  const size_t use = adopt_scan(m, points_xy, n_points);
+  if (use == 0 || dlin.empty() || dth.empty()) return NDT2D_OK;   // (the loops do not run: no candidate, best = 0)
+  if (m->wide == nullptr)
+  {
+    const int rc = ndt2d_wide_create(m->dev, kWideMaxTiles, &m->wide);
+    if (rc != NDT2D_OK) return dev_fail(m, rc, "ndt2d_wide_create");
+  }
+  if (tile_steps != 0)
+  {
+    uint32_t pixels = 0;
+    (void)ndt2d_wide_tile(m->wide, nullptr, &pixels);
+    const int rc = ndt2d_wide_set_tile(m->wide, tile_steps, pixels);
+    if (rc != NDT2D_OK) return mfail(m, rc, std::string("match_wide: ") + ndt2d_wide_last_error(m->wide));
+  }
+  // the image of the last call is of this NDT when the matcher has not built or dropped one since
+  const int reuse = m->wide_installs == m->ndt.installs() ? 1 : 0;
+  m->wide_installs = ~0ull;
+  double record[2] = {0.0, -1.0};
+  const int rc = ndt2d_wide_match(m->wide, scan_pose_xyt, m->beams.host.data(), use, dth.data(), dth.size(), dlin.data(),
+                                  dlin.size(), reuse, record, stats_out, nullptr, nullptr);
+  if (rc != NDT2D_OK) return mfail(m, rc, std::string("match_wide: ") + ndt2d_wide_last_error(m->wide));
+  m->wide_installs = m->ndt.installs();
+  m->last_multi = false;
+  if (record[1] >= 0.0)
+  {
+    const uint64_t best = static_cast<uint64_t>(record[1]);   // (truncates a near-tie mark, index + 0.5)
+    const uint64_t n_lin = dlin.size(), per_th = n_lin * n_lin;
+    if (best_index_out != nullptr) *best_index_out = best;
+    if (near_tie_out != nullptr) *near_tie_out = marked_winner(record) ? 1 : 0;
+    if (pose_out != nullptr)
+    {
+      // :128-134: the accumulated offsets of the winning candidate
+      pose_out[0] = dlin[(best % per_th) / n_lin];
+      pose_out[1] = dlin[best % n_lin];
+      pose_out[2] = dth[best / per_th];
+    }
+  }
+  *score_out = record[0] / use;   // :148
+  return NDT2D_OK;
+  NDT2D_C_CATCH(m)
+}
+
+ndt2d_wide * ndt2d_matcher_wide(ndt2d_matcher * m) { return m != nullptr ? m->wide : nullptr; }
+
 // Jobs the batched scan tracking launches at a time: the object's limit (a fleet is tens, a
 // replayed bag or a graph's scans hundreds to a few thousand).
 static constexpr size_t kScansSlots = 4096;

@@ -85,6 +85,8 @@ struct ndt2d_matcher
   std::vector<double> closure_records;     // its records, [K][NDT2D_MATCH_RECORD_DOUBLES]
   ndt2d_starts * starts = nullptr;         // batched match from K start poses on the first device (made by the first match_starts)
   std::vector<double> starts_records;      // its records, [K][NDT2D_MATCH_RECORD_DOUBLES]
+  ndt2d_wide * wide = nullptr;             // wide search on the first device (made by the first match_wide)
+  uint64_t wide_installs = ~0ull;          // ndt.installs() at its last call: the same, and its bound image is of this NDT
   ndt2d_scans * scans = nullptr;           // batched scan tracking on the first device (made by the first match_scans)
   std::vector<double> scans_records;       // its records, [K][NDT2D_MATCH_RECORD_DOUBLES]
   ndt2d_refine * refine = nullptr;         // Newton registration on the first device (made by the first refine_scans)
@@ -108,6 +110,8 @@ struct ndt2d_matcher
     // back for the host path would cost the cycle more than the build saved)
     bool fused() const { return fused_; }
     const char * last_build() const { return have_ ? build_ : ""; }   // ndt2d_matcher_last_build
+    // counts the builds and drops: what was derived from the grid on the devices is stale once it moved
+    uint64_t installs() const { return installs_; }
     const HostNdt * built() const { return host_.get(); }             // the host build's own NDT; none after a device build
     // ... or else the copy fetched back from the device, if one was (host_ndt())
     const HostNdt * host_copy() const { return host_ ? host_.get() : fetched_.get(); }
@@ -145,7 +149,9 @@ struct ndt2d_matcher
       fetched_.reset();
       have_ = fused_ = false;
       build_ = "";
+      ++installs_;
     }
+    uint64_t installs_ = 0;
     std::unique_ptr<HostNdt> host_, spare_, fetched_;
     bool have_ = false, fused_ = false;
     const char * build_ = "";

@@ -392,6 +392,7 @@ void destroy_matcher(ndt2d_matcher * m)
   }
   if (m->closure != nullptr) (void)ndt2d_closure_destroy(m->closure);         // (before its store)
   if (m->starts != nullptr) (void)ndt2d_starts_destroy(m->starts);            // (before its context)
+  if (m->wide != nullptr) (void)ndt2d_wide_destroy(m->wide);                  // (before its context)
   if (m->scans != nullptr) (void)ndt2d_scans_destroy(m->scans);               // (before its context)
   if (m->refine != nullptr) (void)ndt2d_refine_destroy(m->refine);            // (before its context)
   if (m->verify != nullptr) (void)ndt2d_verify_destroy(m->verify);            // (before its context)

@@ -460,6 +460,28 @@ class ScanMatcherNDT:
             self._m, dptr(sp), K, dptr(pts), len(pts), *out.args), "matchStarts")
         return out.dicts(has_ndt=bool(self._L.ndt2d_matcher_has_ndt(self._m)))
 
+    def matchWide(self, scan_pose, points, linear_size, linear_resolution, angular_size, angular_resolution,
+                  tile_steps=None):
+        """matchScan over a lattice of the CALL's sizes by the wide search (ndt2d_matcher_match_wide):
+        the exhaustive lattice's winner, found by scoring only the tiles whose upper bound can
+        still hold it.  Returns dict(score, pose, best_index, near_tie, tiles_scored, tiles_total):
+        score is per beam used and pose the correction, as matchScan gives them; pose stays (0, 0, 0)
+        and best_index is NO_INDEX without a winner.  No covariance: refineScans(neighbourhood=9) on
+        the winner gives one."""
+        sp = _f64(scan_pose, (3,))
+        pts = _f64(points, (-1, 2))
+        pose = np.zeros(3)
+        score = C.c_double(0.0)
+        best = C.c_uint64(_capi.NO_INDEX)
+        near = C.c_int(0)
+        stats = (C.c_uint64 * 2)(0, 0)
+        self._check(self._L.ndt2d_matcher_match_wide(
+            self._m, dptr(sp), dptr(pts), len(pts), float(linear_size), float(linear_resolution), float(angular_size),
+            float(angular_resolution), 0 if tile_steps is None else int(tile_steps), dptr(pose), C.byref(score),
+            C.byref(best), C.byref(near), stats), "matchWide")
+        return dict(score=score.value, pose=pose, best_index=best.value, near_tie=bool(near.value),
+                    tiles_scored=int(stats[0]), tiles_total=int(stats[1]))
+
     def starts_set_timing(self, enabled):
         """HIP events around the batched match's search and reduce launches on / off (after the
         first matchStarts with an NDT in place: the object is made by it)."""
