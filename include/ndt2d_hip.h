@@ -781,8 +781,13 @@ int ndt2d_closure_verify_rays(ndt2d_closure * closure, int * out);
  * accepted when the gain ratio (F(x) - F(x + delta)) / (model decrease) is above 1e-3 -- or when
  * |F(x) - F(x + delta)| is below 256 eps F, where the ratio is the rounding of the cost's own sum
  * and the (positive) model decrease decides.  The damping update, the CG forcing term and the CG
- * cap are the implementation's (the kernel's head says which).  Stop rules, each evaluated in the
- * kernel, a tolerance of 0 disables its rule:
+ * cap are the implementation's (the kernel's head says which).  What follows from the cap,
+ * min(3 n + 16, 8192) CG iterations per LM iteration: on a small ill-conditioned graph (24 poses with
+ * kappa(H) ~ 1e7: anisotropic information) a "jacobi" solve needs more, the steps are then truncated
+ * CG steps, and the LM iterations are many -- 129 where the direct solve takes 11, and 266 under Huber,
+ * beyond Ceres's default max_iterations of 100, where the status is then
+ * NDT2D_POSEGRAPH_MAX_ITERATIONS.  "chain", the direct and the sparse solve do not have it.
+ * Stop rules, each evaluated in the kernel, a tolerance of 0 disables its rule:
  *     max_iterations          iterations made, accepted or not      NDT2D_POSEGRAPH_MAX_ITERATIONS
  *     gradient_tolerance      |g|_inf <= it, at the start or after an accepted step
  *                                                                    NDT2D_POSEGRAPH_CONVERGED_GRADIENT

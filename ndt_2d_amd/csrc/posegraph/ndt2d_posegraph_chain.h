@@ -18,7 +18,8 @@
 //   U [9]  row-major, the block (i, i + s) at the node's current stride; in: the block (i, i + 1).
 //          After the node's elimination at stride s it stays as it was: its coupling to i + s
 //   L [9]  kept at the node's elimination: the block (i - s, i)
-//   P [6]  kept at the node's elimination (the root's: at the end): the inverse of its pivot D[i]
+//   P [6]  kept at the node's elimination (the root's: at the end): its pivot D[i] factored, M = L^-1 of
+//          D[i] = L L^T (factor_spd); D[i]^-1 v is apply_pivot's M^T (M v), D[i]^-1 itself pivot_inverse's M^T M
 // and for a solve b [3], the right-hand side reduced in place, and x [3].
 #ifndef NDT2D_POSEGRAPH_CHAIN_H_
 #define NDT2D_POSEGRAPH_CHAIN_H_
@@ -92,19 +93,21 @@ NDT2D_PG_HD inline void sub_sym(const double * X, double * S)
   S[3] -= X[4]; S[4] -= X[5]; S[5] -= X[8];
 }
 
-// The inverse of a symmetric 3 x 3 that must be positive definite: false (out zeroed, nothing
-// inverted) unless its three leading minors are positive finite numbers.
+// A node's pivot is kept factored (factor_spd, apply_pivot and pivot_inverse of ndt2d_posegraph_fn.h): a product with
+// the explicit inverse D^-1 leaves a residual kappa(D) times a solve's, which the reduction carried from level to
+// level.
+using posegraph::apply_pivot;
+using posegraph::factor_spd;
+using posegraph::pivot_inverse;
+
+// The inverse itself, D^-1 = M^T M; false (out zeroed) where factor_spd refuses.  No kernel calls it: kept for the
+// host checks (tests/cpp/posegraph_chain_check.cpp, posegraph_fn_check.cpp), which hold its refusals.
 NDT2D_PG_HD inline bool invert_spd(const double * S, double * out)
 {
-  const double big = 1.7976931348623157e308;
-  const double minor2 = S[0] * S[3] - S[1] * S[1];
-  const bool ok = S[0] > 0.0 && S[0] <= big && minor2 > 0.0 && minor2 <= big;
-  if (!ok)
-  {
-    for (int i = 0; i < 6; ++i) out[i] = 0.0;
-    return false;
-  }
-  return invert_sym(S, out);   // (the third minor is the determinant it tests)
+  double M[6];
+  const bool ok = factor_spd(S, M);
+  pivot_inverse(M, out);
+  return ok;
 }
 
 // ---- the per-node steps ----
@@ -120,13 +123,13 @@ NDT2D_PG_HD inline bool factor_node(const System & m, size_t n, size_t j, size_t
   if (j >= s)
   {
     const size_t lo = j - s;
-    ok = invert_spd(m.D + 6 * lo, inv) && ok;   // (lo's own P is written by the node at lo - s)
+    ok = factor_spd(m.D + 6 * lo, inv) && ok;   // (lo's own P is written by the node at lo - s)
     const double * C = m.U + 9 * lo;            // the block (lo, j)
     for (int b = 0; b < 3; ++b)                 // T = P C, column by column
     {
       const double c[3] = {C[b], C[3 + b], C[6 + b]};
       double t[3];
-      mul_sym(inv, c, t);
+      apply_pivot(inv, c, t);
       T[b] = t[0];
       T[3 + b] = t[1];
       T[6 + b] = t[2];
@@ -137,7 +140,7 @@ NDT2D_PG_HD inline bool factor_node(const System & m, size_t n, size_t j, size_t
   const size_t hi = j + s;
   if (hi < n)
   {
-    ok = invert_spd(m.D + 6 * hi, inv) && ok;
+    ok = factor_spd(m.D + 6 * hi, inv) && ok;
     for (int k = 0; k < 6; ++k) m.P[6 * hi + k] = inv[k];
     double C[9];                                // the block (j, hi)
     for (int k = 0; k < 9; ++k)
@@ -145,7 +148,7 @@ NDT2D_PG_HD inline bool factor_node(const System & m, size_t n, size_t j, size_t
       C[k] = m.U[9 * j + k];
       m.L[9 * hi + k] = C[k];
     }
-    for (int a = 0; a < 3; ++a) mul_sym(inv, C + 3 * a, T + 3 * a);   // T = C P, row by row (P is symmetric)
+    for (int a = 0; a < 3; ++a) apply_pivot(inv, C + 3 * a, T + 3 * a);   // T = C P, row by row (P is symmetric)
     mmt(T, C, X);                               // C P C^T
     sub_sym(X, Dj);
     if (hi + s < n)
@@ -163,7 +166,7 @@ NDT2D_PG_HD inline bool factor_node(const System & m, size_t n, size_t j, size_t
 }
 
 // Behind the last level: the root's pivot.
-NDT2D_PG_HD inline bool factor_root(const System & m) { return invert_spd(m.D, m.P); }
+NDT2D_PG_HD inline bool factor_root(const System & m) { return factor_spd(m.D, m.P); }
 
 // The right-hand side, stride s, the staying node j: b_j -= (j, lo) P_lo b_lo + (j, hi) P_hi b_hi.
 NDT2D_PG_HD inline void forward_node(const System & m, double * b, size_t n, size_t j, size_t s)
@@ -172,7 +175,7 @@ NDT2D_PG_HD inline void forward_node(const System & m, double * b, size_t n, siz
   if (j >= s)
   {
     const size_t lo = j - s;
-    mul_sym(m.P + 6 * lo, b + 3 * lo, t);
+    apply_pivot(m.P + 6 * lo, b + 3 * lo, t);
     mul_t(m.U + 9 * lo, t, y);
     bj[0] -= y[0];
     bj[1] -= y[1];
@@ -181,7 +184,7 @@ NDT2D_PG_HD inline void forward_node(const System & m, double * b, size_t n, siz
   const size_t hi = j + s;
   if (hi < n)
   {
-    mul_sym(m.P + 6 * hi, b + 3 * hi, t);
+    apply_pivot(m.P + 6 * hi, b + 3 * hi, t);
     mul(m.L + 9 * hi, t, y);
     bj[0] -= y[0];
     bj[1] -= y[1];
@@ -192,7 +195,7 @@ NDT2D_PG_HD inline void forward_node(const System & m, double * b, size_t n, siz
   b[3 * j + 2] = bj[2];
 }
 
-NDT2D_PG_HD inline void back_root(const System & m, const double * b, double * x) { mul_sym(m.P, b, x); }
+NDT2D_PG_HD inline void back_root(const System & m, const double * b, double * x) { apply_pivot(m.P, b, x); }
 
 // Back-substitution, stride s, the eliminated node i: x_i = P_i (b_i - (i, i - s) x_{i-s} - (i, i + s) x_{i+s}).
 NDT2D_PG_HD inline void back_node(const System & m, const double * b, double * x, size_t n, size_t i, size_t s)
@@ -209,7 +212,7 @@ NDT2D_PG_HD inline void back_node(const System & m, const double * b, double * x
     t[1] -= y[1];
     t[2] -= y[2];
   }
-  mul_sym(m.P + 6 * i, t, y);
+  apply_pivot(m.P + 6 * i, t, y);
   x[3 * i] = y[0];
   x[3 * i + 1] = y[1];
   x[3 * i + 2] = y[2];

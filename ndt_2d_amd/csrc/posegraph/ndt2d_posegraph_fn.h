@@ -144,27 +144,70 @@ NDT2D_PG_HD inline void mul_sym(const double * S, const double * v, double * y)
   y[2] = S[2] * v[0] + S[4] * v[1] + S[5] * v[2];
 }
 
-// The inverse of a symmetric 3 x 3 by cofactors, in the same storage; false (out zeroed) when the
-// determinant is not a positive finite number.
+// A symmetric positive definite 3 x 3 D (00, 01, 02, 11, 12, 22) factored: M = L^-1 of D = L L^T, the lower triangle
+// as (00, 10, 11, 20, 21, 22).  D^-1 v is applied as M^T (M v), two triangular products (apply_pivot); D^-1 itself is
+// M^T M (pivot_inverse).  false (M zeroed: every product with it is zero) unless the three Cholesky pivots are
+// positive finite numbers and M is finite.
+NDT2D_PG_HD inline bool factor_spd(const double * S, double * M)
+{
+  const double big = 1.7976931348623157e308;
+  const double p0 = S[0];
+  const double l00 = sqrt(p0);
+  const double l10 = S[1] / l00;
+  const double l20 = S[2] / l00;
+  const double p1 = S[3] - l10 * l10;
+  const double l11 = sqrt(p1);
+  const double l21 = (S[4] - l20 * l10) / l11;
+  const double p2 = (S[5] - l20 * l20) - l21 * l21;
+  const double l22 = sqrt(p2);
+  const double m00 = 1.0 / l00, m11 = 1.0 / l11, m22 = 1.0 / l22;
+  const double m10 = -(l10 * m00) / l11;
+  const double m21 = -(l21 * m11) / l22;
+  const double m20 = -(l20 * m00 + l21 * m10) / l22;
+  const double c[6] = {m00, m10, m11, m20, m21, m22};
+  bool ok = p0 > 0.0 && p0 <= big && p1 > 0.0 && p1 <= big && p2 > 0.0 && p2 <= big;
+  for (int i = 0; i < 6; ++i) ok = ok && fabs(c[i]) <= big;
+  for (int i = 0; i < 6; ++i) M[i] = ok ? c[i] : 0.0;
+  return ok;
+}
+
+// y = D^-1 v = M^T (M v).
+NDT2D_PG_HD inline void apply_pivot(const double * M, const double * v, double * y)
+{
+  const double t0 = M[0] * v[0];
+  const double t1 = M[1] * v[0] + M[2] * v[1];
+  const double t2 = (M[3] * v[0] + M[4] * v[1]) + M[5] * v[2];
+  y[0] = (M[0] * t0 + M[1] * t1) + M[3] * t2;
+  y[1] = M[2] * t1 + M[4] * t2;
+  y[2] = M[5] * t2;
+}
+
+// D^-1 = M^T M itself, symmetric storage (00, 01, 02, 11, 12, 22).
+NDT2D_PG_HD inline void pivot_inverse(const double * M, double * P)
+{
+  P[0] = (M[0] * M[0] + M[1] * M[1]) + M[3] * M[3];
+  P[1] = M[1] * M[2] + M[3] * M[4];
+  P[2] = M[3] * M[5];
+  P[3] = M[2] * M[2] + M[4] * M[4];
+  P[4] = M[4] * M[5];
+  P[5] = M[5] * M[5];
+}
+
+// The inverse of a symmetric positive definite 3 x 3, in the same storage: M^T M of factor_spd (the form of refine's
+// covariance).  false (out zeroed) when a pivot is not a positive finite number or an entry of the inverse is not
+// finite.  Its error grows with kappa(S), where the cofactor form's grew with kappa^1.5 (the determinant is summed
+// from products kappa^1.5 times its size).
 NDT2D_PG_HD inline bool invert_sym(const double * S, double * out)
 {
-  const double c00 = S[3] * S[5] - S[4] * S[4];
-  const double c01 = S[2] * S[4] - S[1] * S[5];
-  const double c02 = S[1] * S[4] - S[2] * S[3];
-  const double det = S[0] * c00 + S[1] * c01 + S[2] * c02;
-  if (!(det > 0.0) || !(det <= 1.7976931348623157e308))
+  double M[6];
+  bool ok = factor_spd(S, M);
+  pivot_inverse(M, out);
+  for (int i = 0; i < 6; ++i) ok = ok && fabs(out[i]) <= 1.7976931348623157e308;
+  if (!ok)
   {
     for (int i = 0; i < 6; ++i) out[i] = 0.0;
-    return false;
   }
-  const double inv = 1.0 / det;
-  out[0] = c00 * inv;
-  out[1] = c01 * inv;
-  out[2] = c02 * inv;
-  out[3] = (S[0] * S[5] - S[2] * S[2]) * inv;
-  out[4] = (S[1] * S[2] - S[0] * S[4]) * inv;
-  out[5] = (S[0] * S[3] - S[1] * S[1]) * inv;
-  return true;
+  return ok;
 }
 
 // The lower Cholesky factor L (row-major, zeros above the diagonal) of the lower triangle of a

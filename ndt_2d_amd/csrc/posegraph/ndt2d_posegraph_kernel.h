@@ -56,7 +56,7 @@ constexpr size_t kPgNodeDoubles = 8 * 3 + 2 * 6 + 2 * 2 + 1;
 // the preconditioner, the solve kernel's template argument
 constexpr int kPgJacobi = 0, kPgChain = 1;
 // what "chain" adds per node: H's block (i, i + 1) (9), the reduction's working diagonal (6) and
-// coupling (9), the coupling (9) and the inverse pivot (6) kept at the node's elimination, the
+// coupling (9), the coupling (9) and the factored pivot (6) kept at the node's elimination, the
 // reduced right-hand side (3)
 constexpr size_t kPgChainDoubles = 9 + 6 + 9 + 9 + 6 + 3;
 

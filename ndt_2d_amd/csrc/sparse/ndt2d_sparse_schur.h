@@ -92,7 +92,7 @@ NDT2D_PG_HD inline void forward_columns(const chain::System & m, double * b, siz
     for (int c = 0; c < K; ++c)
     {
       double t[3], y[3];
-      posegraph::mul_sym(P, bl + 3 * c, t);
+      chain::apply_pivot(P, bl + 3 * c, t);
       posegraph::mul_t(U, t, y);
       bj[3 * c] -= y[0];
       bj[3 * c + 1] -= y[1];
@@ -109,7 +109,7 @@ NDT2D_PG_HD inline void forward_columns(const chain::System & m, double * b, siz
     for (int c = 0; c < K; ++c)
     {
       double t[3], y[3];
-      posegraph::mul_sym(P, bh + 3 * c, t);
+      chain::apply_pivot(P, bh + 3 * c, t);
       posegraph::mul(L, t, y);
       bj[3 * c] -= y[0];
       bj[3 * c + 1] -= y[1];
@@ -121,7 +121,7 @@ NDT2D_PG_HD inline void forward_columns(const chain::System & m, double * b, siz
 template <int K>
 NDT2D_PG_HD inline void root_columns(const chain::System & m, const double * b, double * x)
 {
-  for (int c = 0; c < K; ++c) posegraph::mul_sym(m.P, b + 3 * c, x + 3 * c);
+  for (int c = 0; c < K; ++c) chain::apply_pivot(m.P, b + 3 * c, x + 3 * c);
 }
 
 template <int K>
@@ -149,7 +149,7 @@ NDT2D_PG_HD inline void back_columns(const chain::System & m, const double * b, 
       t[1] -= y[1];
       t[2] -= y[2];
     }
-    posegraph::mul_sym(P, t, y);
+    chain::apply_pivot(P, t, y);
     xi[3 * c] = y[0];
     xi[3 * c + 1] = y[1];
     xi[3 * c + 2] = y[2];

@@ -64,7 +64,7 @@ NDT2D_PG_HD inline void transposed(const double * A, double * M)
 
 NDT2D_PG_HD inline void select_root(const chain::System & m, double * sel)
 {
-  for (int k = 0; k < 6; ++k) sel[k] = m.P[k];
+  chain::pivot_inverse(m.P, sel);
   for (int k = 6; k < 24; ++k) sel[k] = 0.0;
 }
 
@@ -117,7 +117,9 @@ NDT2D_PG_HD inline void select_node(const chain::System & m, double * sel, size_
   }
   NDT2D_SPARSECOV_PHASE();
   double P[9], Gl[9], Gh[9];
-  full(m.P + 6 * i, P);
+  double Pi[6];
+  chain::pivot_inverse(m.P + 6 * i, Pi);
+  full(Pi, P);
   chain::mm(P, T1, Gl);
   chain::mm(P, T2, Gh);
   for (int k = 0; k < 9; ++k)
