@@ -1720,6 +1720,94 @@ int ndt2d_seed_inject_launch(ndt2d_seeder * seeder, double * d_poses_xyt, size_t
 int ndt2d_seed_set_timing(ndt2d_seeder * seeder, int enabled);
 int ndt2d_seed_last_ms(ndt2d_seeder * seeder, float * table_ms, float * sample_ms);
 
+/* ---- Pose clusters: the pose of the heaviest cluster of a particle set ----
+ *
+ * While a globally seeded set settles, its belief has several modes; the mean over all particles
+ * lies in none of them.  An ndt2d_clusterer groups the particles d_poses_xyt[n][3] with weights
+ * d_weights[n] (both DEVICE; d_weights NULL = every weight 1.0 / (double) n) into connected
+ * clusters of occupied pose bins and returns the max_clusters heaviest with updateStatistics'
+ * quantities of each.  The particles never leave the device; one small block is read back.  It is
+ * an object of its own beside the context (as the seeder and the resampler): it launches on the
+ * context's current stream and must be destroyed before ndt2d_destroy(h).  Nothing calls it by
+ * default and nothing here is a policy: what share makes a filter "localised" is the caller's.
+ * (ndt_2d_amd/csrc/cluster/ndt2d_cluster_fn.h holds this arithmetic as plain C++.)
+ *
+ * Bins.  kx = floor(x / cell_x), ky = floor(y / cell_y): floor, not the KLD tree's truncation,
+ * which makes the bin at 0 twice as wide.  ktheta = min(n_theta - 1, (int) ((t + pi) / (2 pi) *
+ * n_theta)) with t = theta normalised into [-pi, pi): r = fmod(theta, 2 pi); r += 2 pi where
+ * r < -pi; then r -= 2 pi where r >= pi (pi the double M_PI, 2 pi = 2.0 * pi; the add, the
+ * quotient and the product each rounded on their own).  Defaults cell_x = cell_y = 0.5,
+ * n_theta = 24; ndt2d_cluster_set_bins changes them (cells finite and positive, n_theta >= 1).
+ *
+ * Left out.  A particle is left out, counted in n_left_out and labelled 0xFFFFFFFF when its pose is
+ * not finite, when |x / cell_x| or |y / cell_y| is 2^30 or more, or when its weight is not in
+ * [0, 1] (a NaN is not).
+ *
+ * Adjacency.  Two occupied bins are neighbours when their keys differ by at most 1 in each
+ * coordinate, ktheta taken modulo n_theta (the 26-neighbourhood; a blob at heading +-pi is one
+ * cluster; with n_theta of 1 or 2 a bin is its own or its twin's heading neighbour).  A cluster is
+ * a connected component; its LABEL is the smallest particle index in it.
+ *
+ * Mass.  q_i = (uint64) (w_i * 2^40), Q = sum q_i: integer adds, the same Q in any order.  Clusters
+ * are ranked by (Q descending, label ascending).  A weight below 2^-40 has q = 0 and does not count
+ * towards the rank; it does count towards W and the statistics.  No floating-point atomic is used
+ * anywhere.  (max_particles <= 2^23 keeps Q below 2^63 for any weights in [0, 1].)
+ *
+ * Statistics of each of the first max_clusters clusters of that order (1 .. 16, default 8),
+ * restricted to the cluster and renormalised by its own W = sum w_i: the means of x and y, the
+ * circular mean atan2(sum w sin theta, sum w cos theta), the CENTRED second moments
+ * sum w (x - mean_x)(y - mean_y) / W for xx, xy and yy, sum w d^2 / W with d = theta_i - mean_theta
+ * normalised as above, and the particle count.  Every double sum is a fixed tree over fixed chunks
+ * of the index order: two calls on the same input give the same bits.  (A cluster whose weights are
+ * all 0 has W = 0 and statistics that are not numbers; it ranks behind every cluster with mass.)
+ *
+ * ndt2d_cluster_launch is asynchronous: it queues the keys, the bin table, the bin list, the
+ * neighbour table and the first label rounds, and keeps the two pointers until the fetch, which
+ * reads them again.  ndt2d_cluster_fetch waits, queues further label rounds while the last one
+ * still lowered a label (more than B + 2 rounds: NDT2D_ERR_INTERNAL), then the masses, the
+ * selection and the statistics, and copies the header and *n_records = min(max_clusters, C) records,
+ * heaviest first, to HOST records_out[capacity] (capacity below that: NDT2D_ERR_INVALID, *n_records
+ * still set).  A second fetch returns the same block.  n == 0 is legal and gives zeros.  Refused
+ * before anything is allocated or queued, NDT2D_ERR_INVALID with a message, the object left as it
+ * was: a cell that is not finite and positive, n_theta < 1, max_clusters outside 1 .. 16,
+ * n > max_particles, NULL poses with n > 0.  ndt2d_cluster_read_labels copies every particle's
+ * label of the last fetched call to HOST out[n] (for tests and tools).  ndt2d_cluster_set_timing /
+ * _last_ms: HIP events round five phases of the last fetched call, in ms: {keys and table, bin
+ * list and neighbours, label rounds (with the host's reads between them), masses and selection,
+ * statistics and read-back}. */
+#define NDT2D_CLUSTER_MAX_RECORDS 16
+typedef struct ndt2d_cluster_header
+{
+  uint64_t n;            /* particles of the call */
+  uint64_t n_left_out;
+  uint64_t n_bins;       /* B: occupied bins */
+  uint64_t n_clusters;   /* C: all of them, also beyond max_clusters */
+  uint64_t rounds;       /* label rounds run, the one that changed nothing included */
+  double w_total;        /* sum of the weights of the particles that are not left out */
+} ndt2d_cluster_header;
+typedef struct ndt2d_cluster_record
+{
+  uint32_t label;        /* the smallest particle index of the cluster */
+  uint32_t count;        /* its particles */
+  double mass;           /* Q * 2^-40 */
+  double weight;         /* W */
+  double mean_x, mean_y, mean_theta;
+  double cxx, cxy, cyy, var_theta;
+} ndt2d_cluster_record;
+typedef struct ndt2d_clusterer ndt2d_clusterer;
+int ndt2d_cluster_create(ndt2d_handle h, size_t max_particles, ndt2d_clusterer ** out);
+int ndt2d_cluster_destroy(ndt2d_clusterer * clusterer);
+const char * ndt2d_cluster_last_error(ndt2d_clusterer * clusterer);
+int ndt2d_cluster_set_bins(ndt2d_clusterer * clusterer, double cell_x, double cell_y, int n_theta);
+int ndt2d_cluster_set_max_clusters(ndt2d_clusterer * clusterer, int max_clusters);
+int ndt2d_cluster_launch(ndt2d_clusterer * clusterer, const double * d_poses_xyt,
+                         const double * d_weights, size_t n);
+int ndt2d_cluster_fetch(ndt2d_clusterer * clusterer, ndt2d_cluster_header * header_out,
+                        ndt2d_cluster_record * records_out, size_t capacity, size_t * n_records);
+int ndt2d_cluster_read_labels(ndt2d_clusterer * clusterer, uint32_t * out, size_t n);
+int ndt2d_cluster_set_timing(ndt2d_clusterer * clusterer, int enabled);
+int ndt2d_cluster_last_ms(ndt2d_clusterer * clusterer, float * ms5);
+
 /* ---- device memory for hosts without a GPU runtime of their own ----
  *
  * The *_launch entry points take device pointers.  A host that already manages

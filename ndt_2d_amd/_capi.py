@@ -88,6 +88,22 @@ OCCMAP_INCREMENTAL = 1
 OCCMAP_UNCHANGED = 2
 
 
+class ClusterHeader(C.Structure):
+    """ndt2d_cluster_header"""
+    _fields_ = [("n", C.c_uint64), ("n_left_out", C.c_uint64), ("n_bins", C.c_uint64),
+                ("n_clusters", C.c_uint64), ("rounds", C.c_uint64), ("w_total", C.c_double)]
+
+
+class ClusterRecord(C.Structure):
+    """ndt2d_cluster_record"""
+    _fields_ = [("label", C.c_uint32), ("count", C.c_uint32), ("mass", C.c_double), ("weight", C.c_double),
+                ("mean_x", C.c_double), ("mean_y", C.c_double), ("mean_theta", C.c_double),
+                ("cxx", C.c_double), ("cxy", C.c_double), ("cyy", C.c_double), ("var_theta", C.c_double)]
+
+
+CLUSTER_MAX_RECORDS = 16
+
+
 class World(C.Structure):
     _fields_ = [("room_half", C.c_double), ("pillar_pitch", C.c_double),
                 ("pillar_half", C.c_double)]
@@ -309,6 +325,16 @@ SIGNATURES = {
     "ndt2d_seed_inject_launch": (C.c_int, [_vp, _vp, _sz, _d, _u64, _u64, _u64, _vp]),
     "ndt2d_seed_set_timing": (C.c_int, [_vp, C.c_int]),
     "ndt2d_seed_last_ms": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "ndt2d_cluster_create": (C.c_int, [_vp, _sz, C.POINTER(_vp)]),
+    "ndt2d_cluster_destroy": (C.c_int, [_vp]),
+    "ndt2d_cluster_last_error": (C.c_char_p, [_vp]),
+    "ndt2d_cluster_set_bins": (C.c_int, [_vp, _d, _d, C.c_int]),
+    "ndt2d_cluster_set_max_clusters": (C.c_int, [_vp, C.c_int]),
+    "ndt2d_cluster_launch": (C.c_int, [_vp, _vp, _vp, _sz]),
+    "ndt2d_cluster_fetch": (C.c_int, [_vp, C.POINTER(ClusterHeader), C.POINTER(ClusterRecord), _sz, _szp]),
+    "ndt2d_cluster_read_labels": (C.c_int, [_vp, C.POINTER(_u32), _sz]),
+    "ndt2d_cluster_set_timing": (C.c_int, [_vp, C.c_int]),
+    "ndt2d_cluster_last_ms": (C.c_int, [_vp, C.POINTER(C.c_float)]),
     "ndt2d_device_alloc": (C.c_int, [_vp, _sz, C.POINTER(_vp)]),
     "ndt2d_device_free": (C.c_int, [_vp, _vp]),
     "ndt2d_copy_to_device": (C.c_int, [_vp, _vp, _vp, _sz]),

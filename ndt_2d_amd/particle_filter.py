@@ -177,6 +177,7 @@ class ParticleFilter:
         self._mean = np.zeros(3)
         self._cov = np.zeros((3, 3))
         self._seeder = None
+        self._clusterer = None
         self._measure_total = None
         self._update_statistics(have_moments=False)
 
@@ -305,6 +306,35 @@ class ParticleFilter:
         the w_avg of RecoveryAverages.  It has the sign of the reference's scores (<= 0: the negated
         mean likelihood).  None before the first measure."""
         return self._measure_total
+
+    # -- pose clusters (not in the reference) ------------------------------------------------
+
+    def clusters(self, max_clusters=8):
+        """The set as it stands grouped into connected clusters of occupied pose bins (include/
+        ndt2d_hip.h, "Pose clusters"; clusters.py): the `max_clusters` heaviest as PoseCluster
+        records, heaviest first.  The particles stay on the device; getMean / getCovariance are not
+        touched.  `cluster_header` holds the call's header (n, n_left_out, n_bins, n_clusters,
+        rounds, w_total)."""
+        from .clusters import Clusterer
+        n = len(self.particles)
+        if self._clusterer is None or self._clusterer.max_particles < n:
+            if self._clusterer is not None:
+                self._clusterer.close()
+            self._clusterer = Clusterer(self._matcher, max(n, self.min_particles, self.max_particles, 1))
+        self._clusterer.set_max_clusters(max_clusters)
+        self._clusterer.launch(self.particles.data_ptr(), self.weights.data_ptr(), n)
+        self.cluster_header, found = self._clusterer.fetch()
+        return found
+
+    def estimate(self):
+        """(mean, covariance, share) of the heaviest cluster: getMean()- and getCovariance()-shaped
+        values from that cluster's particles only, and its share W / W_total of the set's weight
+        (1.0 once the set has collapsed into one cluster)."""
+        found = self.clusters(max_clusters=1)
+        if not found:
+            raise _capi.Ndt2dError(_capi.ERR_STATE, "ParticleFilter.estimate", "no particle belongs to a cluster")
+        best = found[0]
+        return best.mean.copy(), best.covariance.copy(), best.share
 
     def getMean(self):
         return self._mean.copy()

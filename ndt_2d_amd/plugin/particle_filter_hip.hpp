@@ -38,6 +38,17 @@
 namespace ndt_2d_hip
 {
 
+// One pose cluster as bestCluster() reports it: getMean()- and getCovariance()-shaped values from
+// the cluster's particles only (row-major 3 x 3; only [8] is filled for theta, as the filter fills
+// it), and its share W / W_total of the set's weight.
+struct PoseClusterHip
+{
+  double mean[3] = {0.0, 0.0, 0.0};
+  double covariance[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  double share = 0.0;
+  std::uint32_t label = 0, count = 0;
+};
+
 class ParticleFilterHip
 {
 public:
@@ -63,6 +74,7 @@ public:
   ~ParticleFilterHip()
   {
     if (seeder_ != nullptr) ndt2d_seed_destroy(seeder_);
+    if (clusterer_ != nullptr) ndt2d_cluster_destroy(clusterer_);
     ndt2d_device_free(dev_, d_count_);
     ndt2d_device_free(dev_, d_particles_);
     ndt2d_device_free(dev_, d_weights_);
@@ -196,6 +208,47 @@ public:
     return ok_ ? static_cast<std::size_t>(replaced) : 0;
   }
 
+  // Pose clusters (not in the reference; include/ndt2d_hip.h "Pose clusters"): the set as it stands
+  // grouped on the device into connected clusters of occupied pose bins; the max_clusters (1 .. 16)
+  // heaviest, heaviest first.  getMean / getCovariance are not touched.  The records are this
+  // object's until the next call; clusterHeader() is that call's header.
+  const std::vector<ndt2d_cluster_record> & clusters(int max_clusters = 8)
+  {
+    records_.clear();
+    cluster_header_ = ndt2d_cluster_header();
+    if (!clusterer()) return records_;
+    clusterCheck(ndt2d_cluster_set_max_clusters(clusterer_, max_clusters));
+    if (ok_) clusterCheck(ndt2d_cluster_launch(clusterer_, d_particles_, d_weights_, n_));
+    if (!ok_) return records_;
+    records_.resize(NDT2D_CLUSTER_MAX_RECORDS);
+    std::size_t found = 0;
+    clusterCheck(ndt2d_cluster_fetch(clusterer_, &cluster_header_, records_.data(), records_.size(), &found));
+    records_.resize(ok_ ? found : 0);
+    return records_;
+  }
+  const ndt2d_cluster_header & clusterHeader() const { return cluster_header_; }
+
+  // The heaviest cluster: where a node that started with initGlobal reads its pose instead of
+  // getMean() while the set still has several modes.  false when no particle belongs to a cluster.
+  bool bestCluster(PoseClusterHip * out)
+  {
+    const std::vector<ndt2d_cluster_record> & found = clusters(1);
+    if (!ok_ || found.empty() || out == nullptr) return false;
+    const ndt2d_cluster_record & r = found.front();
+    *out = PoseClusterHip();
+    out->mean[0] = r.mean_x;
+    out->mean[1] = r.mean_y;
+    out->mean[2] = r.mean_theta;
+    out->covariance[0] = r.cxx;
+    out->covariance[1] = out->covariance[3] = r.cxy;
+    out->covariance[4] = r.cyy;
+    out->covariance[8] = r.var_theta;
+    out->share = cluster_header_.w_total > 0.0 ? r.weight / cluster_header_.w_total : 0.0;
+    out->label = r.label;
+    out->count = r.count;
+    return true;
+  }
+
   void getMean(double * mean3) const { std::copy(mean_, mean_ + 3, mean3); }
   void getCovariance(double * cov9) const { std::copy(cov_, cov_ + 9, cov9); }
 
@@ -232,6 +285,31 @@ private:
   {
     if (seeder_ == nullptr && ok_) check(ndt2d_seed_create(dev_, &seeder_));
     return ok_;
+  }
+
+  // created on first use, for the largest set this filter can hold
+  bool clusterer()
+  {
+    if (clusterer_ != nullptr && cluster_capacity_ < n_ && ok_)
+    {
+      ndt2d_cluster_destroy(clusterer_);
+      clusterer_ = nullptr;
+    }
+    if (clusterer_ == nullptr && ok_)
+    {
+      cluster_capacity_ = std::max<std::size_t>(std::max(capacity_, n_), 1);
+      check(ndt2d_cluster_create(dev_, cluster_capacity_, &clusterer_));
+    }
+    return ok_;
+  }
+
+  void clusterCheck(int rc)
+  {
+    if (rc != NDT2D_OK && ok_)
+    {
+      ok_ = false;
+      error_ = std::string("ndt2d error ") + std::to_string(rc) + ": " + ndt2d_cluster_last_error(clusterer_);
+    }
   }
 
   void seedCheck(int rc)
@@ -309,6 +387,10 @@ private:
   std::mt19937 gen_;
   double * d_particles_ = nullptr, * d_weights_ = nullptr, * d_stats_ = nullptr;
   ndt2d_seeder * seeder_ = nullptr;
+  ndt2d_clusterer * clusterer_ = nullptr;
+  std::size_t cluster_capacity_ = 0;
+  ndt2d_cluster_header cluster_header_ = ndt2d_cluster_header();
+  std::vector<ndt2d_cluster_record> records_;
   std::uint64_t * d_count_ = nullptr;
   std::size_t n_ = 0, capacity_ = 0;
   double mean_[3] = {0.0, 0.0, 0.0};
