@@ -3,7 +3,7 @@
 // updateStatistics' quantities of each of them.  The arithmetic of a key is cluster/ndt2d_cluster_fn.h.
 //
 //   keys_kernel       one thread a particle: its key (or "left out") and its integer mass q
-//   insert_kernel     open addressing over the keys as the resampler's table (a power of two >= 2 n,
+//   insert_kernel     the key table of particles/ndt2d_key_table.h over the keys (a power of two >= 2 n,
 //                     linear probing; a slot's owner is the SMALLEST particle index with its key).
 //                     The lanes of a wave that hold one key are combined first (a loop over the
 //                     distinct keys: the first lane's key, a ballot of the lanes that match, a
@@ -13,8 +13,8 @@
 //                     and sends each staged slot ONE atomicMin and two integer atomicAdds when it
 //                     ends, so a converged set does not queue on one address
 //   count_kernel, scan_kernel, scatter_kernel
-//                     the bins in ascending owner index: the seeder's compaction (ballots,
-//                     popcounts, one fixed scan) over the flags "particle i owns its slot"; B to a
+//                     the bins in ascending owner index: the compaction of
+//                     particles/ndt2d_compact.h over the flags "particle i owns its slot"; B to a
 //                     device word and to the pinned block
 //   neighbours_kernel one thread a bin: its 26 neighbour keys looked up in the table, their bin
 //                     ranks (or -1), neighbour j of bin b at nbr[j * n + b] (a wave's loads coalesce)
@@ -44,8 +44,8 @@
 // label rounds; ndt2d_cluster_fetch reads the rounds' words, queues more rounds while the last one
 // still lowered a label, then the masses, the selection and the statistics, and reads the block back.
 //
-// The clusterer is an object of its own on the public device-layer calls (ndt2d_get_stream,
-// ndt2d_device_alloc, ndt2d_host_alloc): the device context has no field for it.
+// The clusterer is an object of its own on the public device-layer calls
+// (particles/ndt2d_device_object.h): the device context has no field for it.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -57,17 +57,23 @@
 #include "cluster/ndt2d_cluster_fn.h"
 #include "ndt2d_guard.h"
 #include "ndt2d_hip.h"
+#include "particles/ndt2d_compact.h"
+#include "particles/ndt2d_device_object.h"
+#include "particles/ndt2d_key_table.h"
+
+using namespace ndt2d::object;
 
 namespace
 {
 
 namespace fn = ndt2d::cluster;
+namespace pt = ndt2d::particles;
+using pt::kEmpty;
+using pt::load_key;
 
-constexpr uint32_t kEmpty = 0xffffffffu;
 constexpr int kWave = 64;
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / kWave;
-constexpr uint32_t kMaxBlocks = 4096;   // grid-stride kernels
 constexpr int kMaxClusters = NDT2D_CLUSTER_MAX_RECORDS;
 constexpr int kChunk = 4096;            // particles per block of the statistics
 constexpr int kPerThread = kChunk / kBlock;
@@ -83,15 +89,6 @@ constexpr int kCtrlBins = 0, kCtrlLeftOut = 1, kCtrlClusters = 2, kCtrlFull = 3,
 __device__ __forceinline__ uint32_t load_u32(const uint32_t * p)
 {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ fn::Key load_key(const int32_t * __restrict__ keys, uint64_t i)
-{
-  fn::Key k;
-  k.kx = keys[3 * i];
-  k.ky = keys[3 * i + 1];
-  k.kt = keys[3 * i + 2];
-  return k;
 }
 
 // ---- 1. keys ----
@@ -199,27 +196,8 @@ __global__ void __launch_bounds__(kBlock) insert_kernel(const int32_t * __restri
     uint32_t found = kEmpty;
     if (leader)
     {
-      uint32_t slot = fn::key_hash(k) & mask;
-      for (uint32_t probe = 0; probe <= mask; ++probe)
-      {
-        uint32_t o = load_u32(owner + slot);
-        if (o == kEmpty)
-        {
-          o = atomicCAS(owner + slot, kEmpty, me);
-          if (o == kEmpty)
-          {
-            found = slot;
-            break;
-          }
-        }
-        // whoever owns the slot, now or later, has the key of its first owner
-        if (fn::same_key(load_key(keys, o), k))
-        {
-          found = slot;
-          break;
-        }
-        slot = (slot + 1) & mask;
-      }
+      uint32_t seen;   // (the owner is lowered once, from the staging table)
+      found = pt::probe_claim(keys, owner, mask, me, k, &seen);
       if (found == kEmpty) atomicOr(ctrl + kCtrlFull, 1u);   // (a table at most half full cannot run out)
     }
     found = __shfl(found, leader_lane, kWave);
@@ -272,47 +250,19 @@ __global__ void __launch_bounds__(kBlock) count_kernel(const uint32_t * __restri
                                                        const uint32_t * __restrict__ bin_of, uint64_t n,
                                                        uint32_t * __restrict__ sums)
 {
-  __shared__ uint32_t sh[kWaves];
-  const bool flag = owns_bin(owner, bin_of, n, static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x);
-  const uint32_t c = static_cast<uint32_t>(__popcll(__ballot(flag)));
-  if ((threadIdx.x & (kWave - 1)) == 0) sh[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) sums[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+  pt::tile_count(owns_bin(owner, bin_of, n, static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x), sums);
 }
 
 // sums[b] -> bins in the tiles before b; the total B to ctrl and to the pinned block
 __global__ void __launch_bounds__(kBlock) scan_kernel(uint32_t * sums, uint32_t n_tiles, uint32_t * ctrl,
                                                       uint32_t * host_bins)
 {
-  __shared__ uint32_t sh[kBlock];
-  const uint32_t t = threadIdx.x;
-  const uint32_t chunk = (n_tiles + kBlock - 1) / kBlock;
-  const uint64_t lo64 = static_cast<uint64_t>(t) * chunk;
-  const uint32_t lo = lo64 < n_tiles ? static_cast<uint32_t>(lo64) : n_tiles;
-  const uint32_t hi = n_tiles - lo > chunk ? lo + chunk : n_tiles;
-  uint32_t mine = 0;
-  for (uint32_t b = lo; b < hi; ++b) mine += sums[b];
-  sh[t] = mine;
-  __syncthreads();
-  for (uint32_t d = 1; d < kBlock; d <<= 1)
+  const uint32_t total = pt::scan_tile_sums(sums, n_tiles);
+  if (threadIdx.x == kBlock - 1)
   {
-    const uint32_t add = t >= d ? sh[t - d] : 0;
-    __syncthreads();
-    sh[t] += add;
-    __syncthreads();
-  }
-  uint32_t run = sh[t] - mine;
-  for (uint32_t b = lo; b < hi; ++b)
-  {
-    const uint32_t s = sums[b];
-    sums[b] = run;
-    run += s;
-  }
-  if (t == kBlock - 1)
-  {
-    ctrl[kCtrlBins] = sh[t];
-    // the pinned word, written through at system scope (a vector store), as the seeder's count
-    __hip_atomic_store(host_bins, sh[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    ctrl[kCtrlBins] = total;
+    // the pinned word, written through at system scope (a vector store)
+    __hip_atomic_store(host_bins, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
 
@@ -326,17 +276,10 @@ __global__ void __launch_bounds__(kBlock) scatter_kernel(const uint32_t * __rest
                                                          unsigned long long * __restrict__ root_q,
                                                          uint32_t * __restrict__ root_count)
 {
-  __shared__ uint32_t sh[kWaves];
-  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & (kWave - 1);
   const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
   const bool flag = owns_bin(owner, bin_of, n, i);
-  const unsigned long long ballot = __ballot(flag);
-  if (lane == 0) sh[wave] = static_cast<uint32_t>(__popcll(ballot));
-  __syncthreads();
+  const uint32_t rank = pt::tile_rank(flag, sums);
   if (!flag) return;
-  uint32_t rank = sums[blockIdx.x];
-  for (uint32_t w = 0; w < wave; ++w) rank += sh[w];
-  rank += static_cast<uint32_t>(__popcll(ballot & ((1ull << lane) - 1ull)));
   if (rank >= n) return;   // (a bin has an owner: B <= n; the test keeps a stray count inside the arrays)
   const uint32_t s = bin_of[i];
   bin_slot[rank] = s;
@@ -806,16 +749,8 @@ __global__ void __launch_bounds__(kWave) pack_kernel(const uint32_t * __restrict
   out->records[c] = r;
 }
 
-uint32_t stride_blocks(uint64_t n)
-{
-  const uint64_t need = (n + kBlock - 1) / kBlock;
-  return static_cast<uint32_t>(need < kMaxBlocks ? (need > 0 ? need : 1) : kMaxBlocks);
-}
-
-size_t align_up(size_t v) { return (v + 255) & ~static_cast<size_t>(255); }
-
 // the pinned block: the bins, the label rounds' words, the results
-struct Pinned
+struct HostBlock
 {
   uint32_t bins;
   uint32_t changed[kRoundsPerRead];
@@ -826,12 +761,9 @@ enum Phase { kPhaseTable = 0, kPhaseBins, kPhaseLabels, kPhaseSelect, kPhaseStat
 
 }  // namespace
 
-struct ndt2d_clusterer
+struct ndt2d_clusterer : DeviceObject
 {
-  ndt2d_handle h = nullptr;
-  int device = 0;
   size_t n_cap = 0;
-  std::string err;
 
   fn::Bins bins{0.5, 0.5, 24};
   int max_clusters = 8;
@@ -859,8 +791,7 @@ struct ndt2d_clusterer
   Selected * selected = nullptr;
   Packed * packed = nullptr;
   uint32_t * ctrl = nullptr;             // [kCtrlWords]
-  Pinned * pinned = nullptr;
-  Pinned * pinned_dev = nullptr;
+  Pinned<HostBlock> pinned;
 
   // the launch a fetch completes
   bool launched = false, fetched = false;
@@ -877,45 +808,6 @@ struct ndt2d_clusterer
 namespace
 {
 
-void guard_note(ndt2d_clusterer * c, const char * what) noexcept
-{
-  if (c == nullptr) return;
-  try
-  {
-    c->err = what;
-  }
-  catch (...)
-  {
-  }
-}
-void guard_note(std::nullptr_t, const char *) noexcept {}
-
-int cfail(ndt2d_clusterer * c, int code, const char * what)
-{
-  guard_note(c, what);
-  return code;
-}
-
-int cfail_hip(ndt2d_clusterer * c, hipError_t e, const char * where)
-{
-  try
-  {
-    c->err = std::string(where) + ": " + hipGetErrorString(e);
-  }
-  catch (...)
-  {
-  }
-  (void)hipGetLastError();
-  return NDT2D_ERR_HIP;
-}
-
-#define NDT2D_CHIP(c, call)                                          \
-  do                                                                 \
-  {                                                                  \
-    const hipError_t hip_status_ = (call);                           \
-    if (hip_status_ != hipSuccess) return cfail_hip(c, hip_status_, #call); \
-  } while (0)
-
 void release(ndt2d_clusterer * c)
 {
   for (hipEvent_t e : c->ev)
@@ -923,16 +815,8 @@ void release(ndt2d_clusterer * c)
     if (e != nullptr) (void)hipEventDestroy(e);
   }
   if (c->workspace != nullptr) (void)ndt2d_device_free(c->h, c->workspace);
-  if (c->pinned != nullptr) (void)ndt2d_host_free(c->h, c->pinned);
+  pinned_free(c, &c->pinned);
   delete c;
-}
-
-template <typename T>
-T * carve(char ** p, size_t count)
-{
-  T * out = reinterpret_cast<T *>(*p);
-  *p += align_up(count * sizeof(T));
-  return out;
 }
 
 uint32_t chunks_of(uint64_t n) { return static_cast<uint32_t>((n + kChunk - 1) / kChunk); }
@@ -940,12 +824,12 @@ uint32_t chunks_of(uint64_t n) { return static_cast<uint32_t>((n + kChunk - 1) /
 // kRoundsPerRead more label rounds, each with its own word of the pinned block
 int queue_rounds(ndt2d_clusterer * c)
 {
-  for (int r = 0; r < kRoundsPerRead; ++r) __atomic_store_n(&c->pinned->changed[r], 0u, __ATOMIC_RELEASE);
+  for (int r = 0; r < kRoundsPerRead; ++r) __atomic_store_n(&c->pinned.host->changed[r], 0u, __ATOMIC_RELEASE);
   for (int r = 0; r < kRoundsPerRead; ++r)
   {
-    hipLaunchKernelGGL(round_kernel, dim3(stride_blocks(c->n)), dim3(kBlock), 0, c->stream, c->nbr, c->lab,
-                       c->ctrl, c->n, &c->pinned_dev->changed[r]);
-    NDT2D_CHIP(c, hipGetLastError());
+    hipLaunchKernelGGL(round_kernel, dim3(stride_blocks(c->n, kBlock)), dim3(kBlock), 0, c->stream, c->nbr, c->lab,
+                       c->ctrl, c->n, &c->pinned.dev->changed[r]);
+    NDT2D_OBJ_HIP(c, hipGetLastError());
   }
   return NDT2D_OK;
 }
@@ -955,38 +839,38 @@ int queue_rest(ndt2d_clusterer * c)
 {
   hipStream_t s = c->stream;
   const uint64_t n = c->n;
-  const uint32_t blocks = stride_blocks(n), chunks = chunks_of(n);
+  const uint32_t blocks = stride_blocks(n, kBlock), chunks = chunks_of(n);
   const double uniform_w = 1.0 / static_cast<double>(n);
   hipLaunchKernelGGL(mass_kernel, dim3(blocks), dim3(kBlock), 0, s, c->lab, c->bin_slot, c->slot_q,
                      c->slot_count, c->root_q, c->root_count, c->root_list, c->ctrl, n);
-  NDT2D_CHIP(c, hipGetLastError());
+  NDT2D_OBJ_HIP(c, hipGetLastError());
   hipLaunchKernelGGL(labels_kernel, dim3(blocks), dim3(kBlock), 0, s, c->bin_of, c->rank_of_slot, c->lab,
                      c->bin_owner, n, c->labels);
-  NDT2D_CHIP(c, hipGetLastError());
+  NDT2D_OBJ_HIP(c, hipGetLastError());
   hipLaunchKernelGGL(select_kernel, dim3(1), dim3(kBlock), 0, s, c->root_list, c->bin_owner, c->root_q,
                      c->root_count, c->ctrl, n, c->max_clusters, c->selected);
-  NDT2D_CHIP(c, hipGetLastError());
-  if (c->timing) NDT2D_CHIP(c, hipEventRecord(c->ev[kPhaseStats], s));
+  NDT2D_OBJ_HIP(c, hipGetLastError());
+  if (c->timing) NDT2D_OBJ_HIP(c, hipEventRecord(c->ev[kPhaseStats], s));
   hipLaunchKernelGGL(sums_kernel, dim3(chunks), dim3(kBlock), 0, s, c->d_poses, c->d_weights, n, uniform_w,
                      c->labels, c->selected, c->ctrl, c->partials);
-  NDT2D_CHIP(c, hipGetLastError());
+  NDT2D_OBJ_HIP(c, hipGetLastError());
   hipLaunchKernelGGL(fold_kernel, dim3((kMaxClusters + 1) * kSums), dim3(kBlock), 0, s, c->partials, chunks,
                      static_cast<uint32_t>((kMaxClusters + 1) * kSums), c->folded);
-  NDT2D_CHIP(c, hipGetLastError());
+  NDT2D_OBJ_HIP(c, hipGetLastError());
   hipLaunchKernelGGL(means_kernel, dim3(1), dim3(kWave), 0, s, c->folded, c->ctrl, c->means);
-  NDT2D_CHIP(c, hipGetLastError());
+  NDT2D_OBJ_HIP(c, hipGetLastError());
   hipLaunchKernelGGL(centred_kernel, dim3(chunks), dim3(kBlock), 0, s, c->d_poses, c->d_weights, n, uniform_w,
                      c->labels, c->selected, c->ctrl, c->means, c->partials);
-  NDT2D_CHIP(c, hipGetLastError());
+  NDT2D_OBJ_HIP(c, hipGetLastError());
   double * centred = c->folded + (kMaxClusters + 1) * kSums;
   hipLaunchKernelGGL(fold_kernel, dim3(kMaxClusters * kCentred), dim3(kBlock), 0, s, c->partials, chunks,
                      static_cast<uint32_t>(kMaxClusters * kCentred), centred);
-  NDT2D_CHIP(c, hipGetLastError());
+  NDT2D_OBJ_HIP(c, hipGetLastError());
   hipLaunchKernelGGL(pack_kernel, dim3(1), dim3(kWave), 0, s, c->ctrl, n, c->selected, c->means, centred,
                      c->packed);
-  NDT2D_CHIP(c, hipGetLastError());
-  NDT2D_CHIP(c, hipMemcpyAsync(&c->pinned->packed, c->packed, sizeof(Packed), hipMemcpyDeviceToHost, s));
-  if (c->timing) NDT2D_CHIP(c, hipEventRecord(c->ev[kPhases], s));
+  NDT2D_OBJ_HIP(c, hipGetLastError());
+  NDT2D_OBJ_HIP(c, hipMemcpyAsync(&c->pinned.host->packed, c->packed, sizeof(Packed), hipMemcpyDeviceToHost, s));
+  if (c->timing) NDT2D_OBJ_HIP(c, hipEventRecord(c->ev[kPhases], s));
   return NDT2D_OK;
 }
 
@@ -1018,7 +902,7 @@ int ndt2d_cluster_create(ndt2d_handle h, size_t max_particles, ndt2d_clusterer *
     align_up(n_folded * sizeof(double)) + align_up(sizeof(Means)) + align_up(sizeof(Selected)) +
     align_up(sizeof(Packed)) + align_up(kCtrlWords * sizeof(uint32_t));
   int rc = ndt2d_device_alloc(h, bytes, &c->workspace);
-  if (rc == NDT2D_OK) rc = ndt2d_host_alloc(h, sizeof(Pinned), reinterpret_cast<void **>(&c->pinned));
+  if (rc == NDT2D_OK) rc = pinned_alloc(c, &c->pinned);
   if (rc != NDT2D_OK)
   {
     release(c);
@@ -1047,10 +931,9 @@ int ndt2d_cluster_create(ndt2d_handle h, size_t max_particles, ndt2d_clusterer *
   c->selected = carve<Selected>(&p, 1);
   c->packed = carve<Packed>(&p, 1);
   c->ctrl = carve<uint32_t>(&p, kCtrlWords);
-  std::memset(c->pinned, 0, sizeof(Pinned));
+  std::memset(c->pinned.host, 0, sizeof(HostBlock));
   std::memset(&c->result, 0, sizeof(Packed));
-  hipError_t e = hipSetDevice(c->device);
-  if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void **>(&c->pinned_dev), c->pinned, 0);
+  hipError_t e = hipSuccess;
   for (hipEvent_t & ev : c->ev)
   {
     if (e == hipSuccess) e = hipEventCreate(&ev);
@@ -1085,9 +968,9 @@ int ndt2d_cluster_set_bins(ndt2d_clusterer * c, double cell_x, double cell_y, in
   if (c == nullptr) return NDT2D_ERR_INVALID;
   if (!std::isfinite(cell_x) || !std::isfinite(cell_y) || !(cell_x > 0.0) || !(cell_y > 0.0))
   {
-    return cfail(c, NDT2D_ERR_INVALID, "ndt2d_cluster_set_bins: a cell size is not finite and positive");
+    return fail(c, NDT2D_ERR_INVALID, "ndt2d_cluster_set_bins: a cell size is not finite and positive");
   }
-  if (n_theta < 1) return cfail(c, NDT2D_ERR_INVALID, "ndt2d_cluster_set_bins: n_theta is below 1");
+  if (n_theta < 1) return fail(c, NDT2D_ERR_INVALID, "ndt2d_cluster_set_bins: n_theta is below 1");
   c->bins = fn::Bins{cell_x, cell_y, n_theta};
   return NDT2D_OK;
   NDT2D_C_CATCH(c)
@@ -1099,7 +982,7 @@ int ndt2d_cluster_set_max_clusters(ndt2d_clusterer * c, int max_clusters)
   if (c == nullptr) return NDT2D_ERR_INVALID;
   if (max_clusters < 1 || max_clusters > kMaxClusters)
   {
-    return cfail(c, NDT2D_ERR_INVALID, "ndt2d_cluster_set_max_clusters: not in 1 .. 16");
+    return fail(c, NDT2D_ERR_INVALID, "ndt2d_cluster_set_max_clusters: not in 1 .. 16");
   }
   c->max_clusters = max_clusters;
   return NDT2D_OK;
@@ -1120,10 +1003,10 @@ int ndt2d_cluster_last_ms(ndt2d_clusterer * c, float * ms5)
 {
   NDT2D_C_TRY
   if (c == nullptr) return NDT2D_ERR_INVALID;
-  if (ms5 == nullptr) return cfail(c, NDT2D_ERR_INVALID, "ndt2d_cluster_last_ms: null argument");
-  if (!c->timed) return cfail(c, NDT2D_ERR_STATE, "ndt2d_cluster_last_ms: no timed call has been fetched");
-  NDT2D_CHIP(c, hipSetDevice(c->device));
-  for (int p = 0; p < kPhases; ++p) NDT2D_CHIP(c, hipEventElapsedTime(ms5 + p, c->ev[p], c->ev[p + 1]));
+  if (ms5 == nullptr) return fail(c, NDT2D_ERR_INVALID, "ndt2d_cluster_last_ms: null argument");
+  if (!c->timed) return fail(c, NDT2D_ERR_STATE, "ndt2d_cluster_last_ms: no timed call has been fetched");
+  NDT2D_OBJ_HIP(c, hipSetDevice(c->device));
+  for (int p = 0; p < kPhases; ++p) NDT2D_OBJ_HIP(c, hipEventElapsedTime(ms5 + p, c->ev[p], c->ev[p + 1]));
   return NDT2D_OK;
   NDT2D_C_CATCH(c)
 }
@@ -1132,12 +1015,12 @@ int ndt2d_cluster_launch(ndt2d_clusterer * c, const double * d_poses_xyt, const 
 {
   NDT2D_C_TRY
   if (c == nullptr) return NDT2D_ERR_INVALID;
-  if (n > c->n_cap) return cfail(c, NDT2D_ERR_INVALID, "ndt2d_cluster_launch: more particles than the clusterer was made for");
-  if (n > 0 && d_poses_xyt == nullptr) return cfail(c, NDT2D_ERR_INVALID, "ndt2d_cluster_launch: null poses");
-  NDT2D_CHIP(c, hipSetDevice(c->device));
+  if (n > c->n_cap) return fail(c, NDT2D_ERR_INVALID, "ndt2d_cluster_launch: more particles than the clusterer was made for");
+  if (n > 0 && d_poses_xyt == nullptr) return fail(c, NDT2D_ERR_INVALID, "ndt2d_cluster_launch: null poses");
+  NDT2D_OBJ_HIP(c, hipSetDevice(c->device));
   hipStream_t s = static_cast<hipStream_t>(ndt2d_get_stream(c->h));
   // work queued on a stream the caller has since replaced finishes first
-  if (c->stream != nullptr && c->stream != s) NDT2D_CHIP(c, hipStreamSynchronize(c->stream));
+  if (c->stream != nullptr && c->stream != s) NDT2D_OBJ_HIP(c, hipStreamSynchronize(c->stream));
   c->stream = s;
   c->launched = false;
   c->fetched = false;
@@ -1153,31 +1036,31 @@ int ndt2d_cluster_launch(ndt2d_clusterer * c, const double * d_poses_xyt, const 
   const uint64_t n64 = n;
   const uint64_t table = fn::table_size(n64);
   const uint32_t mask = static_cast<uint32_t>(table - 1);
-  const uint32_t blocks = stride_blocks(n64);
+  const uint32_t blocks = stride_blocks(n64, kBlock);
   const uint32_t tiles = static_cast<uint32_t>((n64 + kBlock - 1) / kBlock);
-  NDT2D_CHIP(c, hipMemsetAsync(c->owner, 0xff, table * sizeof(uint32_t), s));
-  NDT2D_CHIP(c, hipMemsetAsync(c->slot_count, 0, table * sizeof(uint32_t), s));
-  NDT2D_CHIP(c, hipMemsetAsync(c->slot_q, 0, table * sizeof(unsigned long long), s));
-  NDT2D_CHIP(c, hipMemsetAsync(c->ctrl, 0, kCtrlWords * sizeof(uint32_t), s));
-  if (c->timing) NDT2D_CHIP(c, hipEventRecord(c->ev[kPhaseTable], s));
+  NDT2D_OBJ_HIP(c, hipMemsetAsync(c->owner, 0xff, table * sizeof(uint32_t), s));
+  NDT2D_OBJ_HIP(c, hipMemsetAsync(c->slot_count, 0, table * sizeof(uint32_t), s));
+  NDT2D_OBJ_HIP(c, hipMemsetAsync(c->slot_q, 0, table * sizeof(unsigned long long), s));
+  NDT2D_OBJ_HIP(c, hipMemsetAsync(c->ctrl, 0, kCtrlWords * sizeof(uint32_t), s));
+  if (c->timing) NDT2D_OBJ_HIP(c, hipEventRecord(c->ev[kPhaseTable], s));
   hipLaunchKernelGGL(keys_kernel, dim3(blocks), dim3(kBlock), 0, s, d_poses_xyt, d_weights, n64,
                      1.0 / static_cast<double>(n64), c->bins, c->keys, c->q, c->ctrl);
-  NDT2D_CHIP(c, hipGetLastError());
+  NDT2D_OBJ_HIP(c, hipGetLastError());
   hipLaunchKernelGGL(insert_kernel, dim3(blocks < kInsertBlocks ? blocks : kInsertBlocks), dim3(kBlock), 0, s, c->keys, c->q, n64, c->owner, c->slot_q,
                      c->slot_count, mask, c->bin_of, c->ctrl);
-  NDT2D_CHIP(c, hipGetLastError());
-  if (c->timing) NDT2D_CHIP(c, hipEventRecord(c->ev[kPhaseBins], s));
+  NDT2D_OBJ_HIP(c, hipGetLastError());
+  if (c->timing) NDT2D_OBJ_HIP(c, hipEventRecord(c->ev[kPhaseBins], s));
   hipLaunchKernelGGL(count_kernel, dim3(tiles), dim3(kBlock), 0, s, c->owner, c->bin_of, n64, c->sums);
-  NDT2D_CHIP(c, hipGetLastError());
-  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(kBlock), 0, s, c->sums, tiles, c->ctrl, &c->pinned_dev->bins);
-  NDT2D_CHIP(c, hipGetLastError());
+  NDT2D_OBJ_HIP(c, hipGetLastError());
+  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(kBlock), 0, s, c->sums, tiles, c->ctrl, &c->pinned.dev->bins);
+  NDT2D_OBJ_HIP(c, hipGetLastError());
   hipLaunchKernelGGL(scatter_kernel, dim3(tiles), dim3(kBlock), 0, s, c->owner, c->bin_of, n64, c->sums,
                      c->bin_slot, c->bin_owner, c->rank_of_slot, c->lab, c->root_q, c->root_count);
-  NDT2D_CHIP(c, hipGetLastError());
+  NDT2D_OBJ_HIP(c, hipGetLastError());
   hipLaunchKernelGGL(neighbours_kernel, dim3(blocks), dim3(kBlock), 0, s, c->keys, c->owner, c->rank_of_slot,
                      c->bin_owner, c->ctrl, mask, c->bins.n_theta, n64, c->nbr);
-  NDT2D_CHIP(c, hipGetLastError());
-  if (c->timing) NDT2D_CHIP(c, hipEventRecord(c->ev[kPhaseLabels], s));
+  NDT2D_OBJ_HIP(c, hipGetLastError());
+  if (c->timing) NDT2D_OBJ_HIP(c, hipEventRecord(c->ev[kPhaseLabels], s));
   const int rc = queue_rounds(c);
   if (rc != NDT2D_OK) return rc;
   c->launched = true;
@@ -1193,41 +1076,41 @@ int ndt2d_cluster_fetch(ndt2d_clusterer * c, ndt2d_cluster_header * header_out,
   if (n_records != nullptr) *n_records = 0;
   if (header_out == nullptr || n_records == nullptr || (records_out == nullptr && capacity > 0))
   {
-    return cfail(c, NDT2D_ERR_INVALID, "ndt2d_cluster_fetch: null argument");
+    return fail(c, NDT2D_ERR_INVALID, "ndt2d_cluster_fetch: null argument");
   }
-  if (!c->launched && !c->fetched) return cfail(c, NDT2D_ERR_STATE, "ndt2d_cluster_fetch: nothing launched");
+  if (!c->launched && !c->fetched) return fail(c, NDT2D_ERR_STATE, "ndt2d_cluster_fetch: nothing launched");
   if (c->launched)
   {
     c->launched = false;
     std::memset(&c->result, 0, sizeof(Packed));
     if (c->n > 0)
     {
-      NDT2D_CHIP(c, hipSetDevice(c->device));
+      NDT2D_OBJ_HIP(c, hipSetDevice(c->device));
       uint64_t rounds = 0;
       bool standing = false;
       uint64_t n_bins = 0;
       while (!standing)
       {
-        NDT2D_CHIP(c, hipStreamSynchronize(c->stream));
-        n_bins = __atomic_load_n(&c->pinned->bins, __ATOMIC_ACQUIRE);
-        if (n_bins > c->n) return cfail(c, NDT2D_ERR_INTERNAL, "ndt2d_cluster_fetch: more bins than particles");
+        NDT2D_OBJ_HIP(c, hipStreamSynchronize(c->stream));
+        n_bins = __atomic_load_n(&c->pinned.host->bins, __ATOMIC_ACQUIRE);
+        if (n_bins > c->n) return fail(c, NDT2D_ERR_INTERNAL, "ndt2d_cluster_fetch: more bins than particles");
         for (int r = 0; r < kRoundsPerRead && !standing; ++r)
         {
           ++rounds;
-          standing = __atomic_load_n(&c->pinned->changed[r], __ATOMIC_ACQUIRE) == 0;
+          standing = __atomic_load_n(&c->pinned.host->changed[r], __ATOMIC_ACQUIRE) == 0;
         }
         if (standing) break;
         // (plain propagation alone ends within B rounds)
-        if (rounds > n_bins + 2) return cfail(c, NDT2D_ERR_INTERNAL, "ndt2d_cluster_fetch: the labels did not stand still within B + 2 rounds");
+        if (rounds > n_bins + 2) return fail(c, NDT2D_ERR_INTERNAL, "ndt2d_cluster_fetch: the labels did not stand still within B + 2 rounds");
         const int rc = queue_rounds(c);
         if (rc != NDT2D_OK) return rc;
       }
-      if (c->timing) NDT2D_CHIP(c, hipEventRecord(c->ev[kPhaseSelect], c->stream));
+      if (c->timing) NDT2D_OBJ_HIP(c, hipEventRecord(c->ev[kPhaseSelect], c->stream));
       const int rc = queue_rest(c);
       if (rc != NDT2D_OK) return rc;
-      NDT2D_CHIP(c, hipStreamSynchronize(c->stream));
-      if (c->pinned->packed.table_full != 0) return cfail(c, NDT2D_ERR_INTERNAL, "ndt2d_cluster_fetch: the bin table ran out of slots");
-      std::memcpy(&c->result, &c->pinned->packed, sizeof(Packed));
+      NDT2D_OBJ_HIP(c, hipStreamSynchronize(c->stream));
+      if (c->pinned.host->packed.table_full != 0) return fail(c, NDT2D_ERR_INTERNAL, "ndt2d_cluster_fetch: the bin table ran out of slots");
+      std::memcpy(&c->result, &c->pinned.host->packed, sizeof(Packed));
       c->result.header.rounds = rounds;
       c->timed = c->timing;
     }
@@ -1241,7 +1124,7 @@ int ndt2d_cluster_fetch(ndt2d_clusterer * c, ndt2d_cluster_header * header_out,
     ++live;
   }
   *n_records = live;
-  if (capacity < live) return cfail(c, NDT2D_ERR_INVALID, "ndt2d_cluster_fetch: a capacity below the number of records");
+  if (capacity < live) return fail(c, NDT2D_ERR_INVALID, "ndt2d_cluster_fetch: a capacity below the number of records");
   for (size_t k = 0; k < live; ++k) records_out[k] = c->result.records[k];
   return NDT2D_OK;
   NDT2D_C_CATCH(c)
@@ -1251,10 +1134,10 @@ int ndt2d_cluster_read_labels(ndt2d_clusterer * c, uint32_t * out, size_t n)
 {
   NDT2D_C_TRY
   if (c == nullptr) return NDT2D_ERR_INVALID;
-  if (!c->fetched) return cfail(c, NDT2D_ERR_STATE, "ndt2d_cluster_read_labels: no fetched call");
-  if (n != c->n) return cfail(c, NDT2D_ERR_INVALID, "ndt2d_cluster_read_labels: n is not the last call's");
+  if (!c->fetched) return fail(c, NDT2D_ERR_STATE, "ndt2d_cluster_read_labels: no fetched call");
+  if (n != c->n) return fail(c, NDT2D_ERR_INVALID, "ndt2d_cluster_read_labels: n is not the last call's");
   if (n == 0) return NDT2D_OK;
-  if (out == nullptr) return cfail(c, NDT2D_ERR_INVALID, "ndt2d_cluster_read_labels: null output");
+  if (out == nullptr) return fail(c, NDT2D_ERR_INVALID, "ndt2d_cluster_read_labels: null output");
   return ndt2d_copy_to_host(c->h, out, c->labels, n * sizeof(uint32_t));
   NDT2D_C_CATCH(c)
 }

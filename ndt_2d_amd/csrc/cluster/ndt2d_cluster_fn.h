@@ -12,6 +12,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "../particles/ndt2d_key_table.h"   // (relative: a stand-alone check needs this directory alone on its path)
+
 #if defined(__HIPCC__)
 #define NDT2D_CLUSTER_HD __host__ __device__
 #else
@@ -44,10 +46,11 @@ struct Bins
   int32_t n_theta;   // >= 1
 };
 
-struct Key
-{
-  int32_t kx, ky, kt;   // kt < 0: left out
-};
+// The key of a bin, its hash and the size of the table over it: particles/ndt2d_key_table.h.
+using Key = particles::Key3;   // kt < 0: left out
+using particles::key_hash;
+using particles::same_key;
+using particles::table_size;
 
 // theta into [-pi, pi): the remainder of theta / 2 pi (fmod is exact), then at most one turn either
 // way.  pi itself goes to -pi; a remainder that the added turn rounds up to pi goes there too.
@@ -100,18 +103,6 @@ NDT2D_CLUSTER_HD inline Key key_of(double x, double y, double theta, double w, c
   return k;
 }
 
-NDT2D_CLUSTER_HD inline bool same_key(const Key & a, const Key & b)
-{
-  return a.kx == b.kx && a.ky == b.ky && a.kt == b.kt;
-}
-
-// The resampler's hash; the slot is its low bits (the table is a power of two), linear probing.
-NDT2D_CLUSTER_HD inline uint32_t key_hash(const Key & k)
-{
-  return static_cast<uint32_t>(k.kx) * 0x9E3779B1u + static_cast<uint32_t>(k.ky) * 0x85EBCA77u +
-         static_cast<uint32_t>(k.kt) * 0xC2B2AE3Du;
-}
-
 // Neighbour j (0 .. 25) of a key: the offsets (dx, dy, dt) in {-1, 0, 1}^3 without (0, 0, 0), dt
 // slowest and dx fastest, the heading bin taken modulo n_theta.  With n_theta of 1 or 2 some
 // entries name the key itself or one twin more than once; a reader takes them as they come.
@@ -132,14 +123,6 @@ NDT2D_CLUSTER_HD inline Key neighbour(const Key & k, int j, int32_t n_theta)
 NDT2D_CLUSTER_HD inline bool ranks_before(uint64_t q_a, uint32_t label_a, uint64_t q_b, uint32_t label_b)
 {
   return q_a > q_b || (q_a == q_b && label_a < label_b);
-}
-
-// The size of the table for n particles: a power of two, at least 64 and at least 2 n.
-NDT2D_CLUSTER_HD inline uint64_t table_size(uint64_t n)
-{
-  uint64_t t = 64;
-  while (t < 2 * n) t <<= 1;
-  return t;
 }
 
 }  // namespace cluster

@@ -27,6 +27,7 @@
 #include "ndt2d_kernels.h"
 
 #include "ndt2d_device_fn.h"
+#include "particles/ndt2d_philox.h"
 
 namespace ndt2d
 {
@@ -48,31 +49,7 @@ struct Normals3
   float z0, z1, z2;
 };
 
-// Philox4x32-10 (Salmon et al., SC'11), key = seed, counter = {index, step}.
-__device__ __forceinline__ void philox4x32_10(uint64_t seed, uint64_t index, uint64_t step,
-                                              uint32_t out[4])
-{
-  uint32_t c0 = static_cast<uint32_t>(index), c1 = static_cast<uint32_t>(index >> 32);
-  uint32_t c2 = static_cast<uint32_t>(step), c3 = static_cast<uint32_t>(step >> 32);
-  uint32_t k0 = static_cast<uint32_t>(seed), k1 = static_cast<uint32_t>(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r)
-  {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0;
-    c1 = lo1;
-    c2 = hi0 ^ c3 ^ k1;
-    c3 = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  out[0] = c0;
-  out[1] = c1;
-  out[2] = c2;
-  out[3] = c3;
-}
-
+// The words are particles/ndt2d_philox.h's; their conversion to float is this unit's own.
 // 24 random bits k -> (0, 1]: float round-to-nearest-even of k + 0.5, times 2^-24.  The sum is
 // exact only below k = 2^23; from there it needs 25 significand bits and is rounded to even
 // (k even: k, k odd: k + 1), so k = 2^24 - 1 gives 1.0f.  Never 0: the logarithm stays finite.
@@ -84,7 +61,7 @@ __device__ __forceinline__ float unit_open(uint32_t bits)
 __device__ __forceinline__ Normals3 standard_normals(uint64_t seed, uint64_t index, uint64_t step)
 {
   uint32_t w[4];
-  philox4x32_10(seed, index, step, w);
+  particles::philox4x32_10(seed, index, step, w);
   const float r0 = sqrtf(-2.0f * logf(unit_open(w[0])));
   const float r1 = sqrtf(-2.0f * logf(unit_open(w[2])));
   const float a0 = 6.28318530717958647692f * unit_open(w[1]);

@@ -27,8 +27,8 @@
 // step on).  One new scan is 720 rays: its trace is a few waves and is bounded by the longest ray,
 // not by atomic throughput.
 //
-// The object is beside the device context, not in it: it reaches the context through
-// ndt2d_get_stream and ndt2d_device_id only.
+// The object is beside the device context, not in it (particles/ndt2d_device_object.h): it reaches
+// the context through ndt2d_get_stream and ndt2d_device_id only.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -42,6 +42,9 @@
 #include "ndt2d_guard.h"
 #include "ndt2d_hip.h"
 #include "ndt2d_kernels.h"
+#include "particles/ndt2d_device_object.h"
+
+using namespace ndt2d::object;
 
 namespace
 {
@@ -269,12 +272,9 @@ __global__ void __launch_bounds__(256) map_finalize_kernel(const unsigned long l
 
 }  // namespace
 
-struct ndt2d_occupancy_map
+struct ndt2d_occupancy_map : DeviceObject
 {
-  ndt2d_handle h = nullptr;
-  int device = 0;
   double resolution = 0.0, occ_thresh = 0.0;
-  std::string err;
 
   // resident scans
   double * d_points = nullptr;      // [points_cap][2]
@@ -306,55 +306,20 @@ struct ndt2d_occupancy_map
   bool table_stale = false;         // the device scan table is not the one made from `poses`
   std::vector<ScanRec> stage;
 
-  hipStream_t last_stream = nullptr;
-  bool used = false;
+  StreamUse use;
 };
 
 namespace
 {
 
-void guard_note(ndt2d_occupancy_map * m, const char * what) noexcept
+// after a failed HIP call (DeviceObject::hip_failed): whatever was in flight may not have happened
+void invalidate(DeviceObject * o)
 {
-  if (m == nullptr) return;
-  try
-  {
-    m->err = what;
-  }
-  catch (...)
-  {
-  }
-}
-void guard_note(std::nullptr_t, const char *) noexcept {}
-
-int mfail(ndt2d_occupancy_map * m, int code, const char * what)
-{
-  guard_note(m, what);
-  return code;
-}
-
-int mfail_hip(ndt2d_occupancy_map * m, hipError_t e, const char * where)
-{
-  try
-  {
-    m->err = std::string(where) + ": " + hipGetErrorString(e);
-  }
-  catch (...)
-  {
-  }
-  (void)hipGetLastError();
-  // whatever was in flight may not have happened
+  ndt2d_occupancy_map * m = static_cast<ndt2d_occupancy_map *>(o);
   m->counts_valid = false;
   m->have_map = false;
   m->table_stale = true;
-  return NDT2D_ERR_HIP;
 }
-
-#define NDT2D_MHIP(m, call)                                          \
-  do                                                                 \
-  {                                                                  \
-    const hipError_t hip_status_ = (call);                           \
-    if (hip_status_ != hipSuccess) return mfail_hip(m, hip_status_, #call); \
-  } while (0)
 
 void release(ndt2d_occupancy_map * m)
 {
@@ -369,19 +334,6 @@ void release(ndt2d_occupancy_map * m)
   delete m;
 }
 
-// The context's current stream.  A caller that rebinds the context (ndt2d_set_stream) between
-// two calls gets the work of the earlier stream finished first.
-int current_stream(ndt2d_occupancy_map * m, hipStream_t * out)
-{
-  NDT2D_MHIP(m, hipSetDevice(m->device));
-  hipStream_t s = static_cast<hipStream_t>(ndt2d_get_stream(m->h));
-  if (m->used && s != m->last_stream) NDT2D_MHIP(m, hipStreamSynchronize(m->last_stream));
-  m->last_stream = s;
-  m->used = true;
-  *out = s;
-  return NDT2D_OK;
-}
-
 // room for `need` points / scans: double, copy device to device, release the old block
 template <typename T>
 int grow(ndt2d_occupancy_map * m, T ** buf, size_t * cap, size_t need, size_t keep, size_t extra,
@@ -391,14 +343,14 @@ int grow(ndt2d_occupancy_map * m, T ** buf, size_t * cap, size_t need, size_t ke
   size_t cap_new = *cap;
   while (cap_new < need) cap_new *= 2;
   T * fresh = nullptr;
-  NDT2D_MHIP(m, hipMalloc(reinterpret_cast<void **>(&fresh), (cap_new + extra) * sizeof(T)));
+  NDT2D_OBJ_HIP(m, hipMalloc(reinterpret_cast<void **>(&fresh), (cap_new + extra) * sizeof(T)));
   hipError_t e = hipSuccess;
   if (keep > 0) e = hipMemcpyAsync(fresh, *buf, keep * sizeof(T), hipMemcpyDeviceToDevice, stream);
   if (e == hipSuccess) e = hipStreamSynchronize(stream);   // nothing in flight reads the old block
   if (e != hipSuccess)
   {
     (void)hipFree(fresh);
-    return mfail_hip(m, e, "growing a resident buffer");
+    return fail_hip(m, e, "growing a resident buffer");
   }
   (void)hipFree(*buf);
   *buf = fresh;
@@ -455,6 +407,7 @@ int ndt2d_occmap_create(ndt2d_handle h, double resolution, double occ_thresh,
   ndt2d_occupancy_map * m = new ndt2d_occupancy_map();
   m->h = h;
   m->device = ndt2d_device_id(h);
+  m->hip_failed = invalidate;
   m->resolution = resolution;
   m->occ_thresh = occ_thresh;
   hipError_t e = hipSetDevice(m->device);
@@ -484,7 +437,7 @@ int ndt2d_occmap_destroy(ndt2d_occupancy_map * m)
   NDT2D_C_TRY
   if (m == nullptr) return NDT2D_ERR_INVALID;
   (void)hipSetDevice(m->device);
-  if (m->used) (void)hipStreamSynchronize(m->last_stream);
+  if (m->use.used) (void)hipStreamSynchronize(m->use.last_stream);
   release(m);
   return NDT2D_OK;
   NDT2D_C_CATCH(nullptr)
@@ -497,16 +450,16 @@ int ndt2d_occmap_append_scan(ndt2d_occupancy_map * m, const double * points_xy, 
 {
   NDT2D_C_TRY
   if (m == nullptr) return NDT2D_ERR_INVALID;
-  if (n_points > 0 && points_xy == nullptr) return mfail(m, NDT2D_ERR_INVALID, "ndt2d_occmap_append_scan: null points");
+  if (n_points > 0 && points_xy == nullptr) return fail(m, NDT2D_ERR_INVALID, "ndt2d_occmap_append_scan: null points");
   const size_t n_scans = m->offsets.size() - 1;
   const size_t first = m->offsets.back();
   // point indices are 32-bit words on the device (as in ndt2d_occupancy_grid)
   if (n_points >= (1ull << 31) || first + n_points >= (1ull << 31) || n_scans >= (1u << 30))
   {
-    return mfail(m, NDT2D_ERR_INVALID, "ndt2d_occmap_append_scan: too many points or scans");
+    return fail(m, NDT2D_ERR_INVALID, "ndt2d_occmap_append_scan: too many points or scans");
   }
   hipStream_t stream;
-  int rc = current_stream(m, &stream);
+  int rc = current_stream(m, &m->use, &stream);
   if (rc != NDT2D_OK) return rc;
   // (the doubled blocks hold [cap][2] doubles and [cap + 1] offsets)
   {
@@ -525,12 +478,12 @@ int ndt2d_occmap_append_scan(ndt2d_occupancy_map * m, const double * points_xy, 
   const uint32_t end = static_cast<uint32_t>(first + n_points);
   if (n_points > 0)
   {
-    NDT2D_MHIP(m, hipMemcpyAsync(m->d_points + 2 * first, points_xy, 2 * n_points * sizeof(double),
+    NDT2D_OBJ_HIP(m, hipMemcpyAsync(m->d_points + 2 * first, points_xy, 2 * n_points * sizeof(double),
                                  hipMemcpyHostToDevice, stream));
   }
-  NDT2D_MHIP(m, hipMemcpyAsync(m->d_offsets + n_scans + 1, &end, sizeof(uint32_t), hipMemcpyHostToDevice,
+  NDT2D_OBJ_HIP(m, hipMemcpyAsync(m->d_offsets + n_scans + 1, &end, sizeof(uint32_t), hipMemcpyHostToDevice,
                                stream));
-  NDT2D_MHIP(m, hipStreamSynchronize(stream));   // the caller's array is free again
+  NDT2D_OBJ_HIP(m, hipStreamSynchronize(stream));   // the caller's array is free again
   m->offsets.push_back(end);
   m->scan_nonfinite.push_back(nonfinite ? 1 : 0);
   m->nonfinite_points = m->nonfinite_points || nonfinite;
@@ -543,7 +496,7 @@ int ndt2d_occmap_scan_count(ndt2d_occupancy_map * m, size_t * n_out)
 {
   NDT2D_C_TRY
   if (m == nullptr) return NDT2D_ERR_INVALID;
-  if (n_out == nullptr) return mfail(m, NDT2D_ERR_INVALID, "ndt2d_occmap_scan_count: null argument");
+  if (n_out == nullptr) return fail(m, NDT2D_ERR_INVALID, "ndt2d_occmap_scan_count: null argument");
   *n_out = m->offsets.size() - 1;
   return NDT2D_OK;
   NDT2D_C_CATCH(m)
@@ -553,10 +506,10 @@ int ndt2d_occmap_reset(ndt2d_occupancy_map * m)
 {
   NDT2D_C_TRY
   if (m == nullptr) return NDT2D_ERR_INVALID;
-  if (m->used)
+  if (m->use.used)
   {
-    NDT2D_MHIP(m, hipSetDevice(m->device));
-    NDT2D_MHIP(m, hipStreamSynchronize(m->last_stream));
+    NDT2D_OBJ_HIP(m, hipSetDevice(m->device));
+    NDT2D_OBJ_HIP(m, hipStreamSynchronize(m->use.last_stream));
   }
   forget(m);
   return NDT2D_OK;
@@ -570,20 +523,20 @@ int ndt2d_occmap_update(ndt2d_occupancy_map * m, const double * poses_xyt, size_
   if (m == nullptr) return NDT2D_ERR_INVALID;
   if (result == nullptr || (n_scans > 0 && poses_xyt == nullptr))
   {
-    return mfail(m, NDT2D_ERR_INVALID, "ndt2d_occmap_update: null argument");
+    return fail(m, NDT2D_ERR_INVALID, "ndt2d_occmap_update: null argument");
   }
   // 1.
   if (n_scans > m->offsets.size() - 1)
   {
-    return mfail(m, NDT2D_ERR_INVALID, "ndt2d_occmap_update: more scans than were appended");
+    return fail(m, NDT2D_ERR_INVALID, "ndt2d_occmap_update: more scans than were appended");
   }
   if (n_scans < m->num_scans)
   {
-    return mfail(m, NDT2D_ERR_INVALID,
+    return fail(m, NDT2D_ERR_INVALID,
                  "ndt2d_occmap_update: fewer scans than the last update rendered (ndt2d_occmap_reset drops scans)");
   }
   hipStream_t stream;
-  int rc = current_stream(m, &stream);
+  int rc = current_stream(m, &m->use, &stream);
   if (rc != NDT2D_OK) return rc;
 
   const size_t n_old = m->num_scans;
@@ -608,7 +561,7 @@ int ndt2d_occmap_update(ndt2d_occupancy_map * m, const double * poses_xyt, size_
     }
     if (n_scans > first_rec)
     {
-      NDT2D_MHIP(m, hipMemcpyAsync(m->d_scans + first_rec, m->stage.data(),
+      NDT2D_OBJ_HIP(m, hipMemcpyAsync(m->d_scans + first_rec, m->stage.data(),
                                    (n_scans - first_rec) * sizeof(ScanRec), hipMemcpyHostToDevice, stream));
       uploaded = true;
     }
@@ -649,7 +602,7 @@ int ndt2d_occmap_update(ndt2d_occupancy_map * m, const double * poses_xyt, size_
         e = hipGetLastError();
       }
       if (e == hipSuccess) e = hipStreamSynchronize(stream);
-      if (e != hipSuccess) return mfail_hip(m, e, "ndt2d_occmap_update: bounds");
+      if (e != hipSuccess) return fail_hip(m, e, "ndt2d_occmap_update: bounds");
       uploaded = false;   // (the staged records have arrived)
       for (int k = 0; k < 4; ++k) found[k] = static_cast<const volatile double *>(m->pinned)[k];
     }
@@ -692,7 +645,7 @@ int ndt2d_occmap_update(ndt2d_occupancy_map * m, const double * poses_xyt, size_
     // refused: bounds, count, poses, counters and map stay as they were (a scan table written
     // over with the refused poses is marked stale above)
     if (uploaded) (void)hipStreamSynchronize(stream);
-    return mfail(m, status, refusal);
+    return fail(m, status, refusal);
   }
 
   // 4.
@@ -711,7 +664,7 @@ int ndt2d_occmap_update(ndt2d_occupancy_map * m, const double * poses_xyt, size_
   args.origin_x = geo.origin_x;
   args.origin_y = geo.origin_y;
 
-  // from here on the object describes the new state; a failing launch invalidates it (mfail_hip)
+  // from here on the object describes the new state; a failing launch invalidates it (invalidate)
   m->bounds[0] = bounds[0];
   m->bounds[1] = bounds[1];
   m->bounds[2] = bounds[2];
@@ -727,35 +680,35 @@ int ndt2d_occmap_update(ndt2d_occupancy_map * m, const double * poses_xyt, size_
     m->have_map = false;
     if (n_cells > m->cells_cap)
     {
-      NDT2D_MHIP(m, hipStreamSynchronize(stream));
+      NDT2D_OBJ_HIP(m, hipStreamSynchronize(stream));
       (void)hipFree(m->d_counts);
       (void)hipFree(m->d_data);
       m->d_counts = nullptr;
       m->d_data = nullptr;
       m->cells_cap = 0;
       const size_t cap = n_cells + n_cells / 4;   // some room for a map that keeps growing
-      NDT2D_MHIP(m, hipMalloc(reinterpret_cast<void **>(&m->d_counts), cap * sizeof(unsigned long long)));
-      NDT2D_MHIP(m, hipMalloc(reinterpret_cast<void **>(&m->d_data), cap));
+      NDT2D_OBJ_HIP(m, hipMalloc(reinterpret_cast<void **>(&m->d_counts), cap * sizeof(unsigned long long)));
+      NDT2D_OBJ_HIP(m, hipMalloc(reinterpret_cast<void **>(&m->d_data), cap));
       m->cells_cap = cap;
     }
     if (n_cells > 0)
     {
-      NDT2D_MHIP(m, hipMemsetAsync(m->d_counts, 0, n_cells * sizeof(unsigned long long), stream));
+      NDT2D_OBJ_HIP(m, hipMemsetAsync(m->d_counts, 0, n_cells * sizeof(unsigned long long), stream));
       if (args.n_points > 0)
       {
         args.first_scan = 0;
         args.first_point = 0;
         hipLaunchKernelGGL(map_trace_kernel, dim3((args.n_points + 255) / 256), dim3(256), 0, stream, args,
                            m->d_counts);
-        NDT2D_MHIP(m, hipGetLastError());
+        NDT2D_OBJ_HIP(m, hipGetLastError());
       }
       rect = CellRect{0, 0, geo.width, geo.height};
       launch_finalize(m, rect, stream);
-      NDT2D_MHIP(m, hipGetLastError());
+      NDT2D_OBJ_HIP(m, hipGetLastError());
     }
     beams = args.n_points;
     // the staged scan records must have left the host before the next update writes them
-    NDT2D_MHIP(m, hipStreamSynchronize(stream));
+    NDT2D_OBJ_HIP(m, hipStreamSynchronize(stream));
   }
   else if (mode == NDT2D_OCCMAP_INCREMENTAL && n_new_points > 0)
   {
@@ -803,11 +756,11 @@ int ndt2d_occmap_update(ndt2d_occupancy_map * m, const double * poses_xyt, size_
       args.first_point = first_new_point;
       hipLaunchKernelGGL(map_trace_kernel, dim3((n_new_points + 255) / 256), dim3(256), 0, stream, args,
                          m->d_counts);
-      NDT2D_MHIP(m, hipGetLastError());
+      NDT2D_OBJ_HIP(m, hipGetLastError());
       if (rect.w > 0 && rect.h > 0)
       {
         launch_finalize(m, rect, stream);
-        NDT2D_MHIP(m, hipGetLastError());
+        NDT2D_OBJ_HIP(m, hipGetLastError());
       }
     }
     beams = n_new_points;
@@ -815,7 +768,7 @@ int ndt2d_occmap_update(ndt2d_occupancy_map * m, const double * poses_xyt, size_
   else if (uploaded)
   {
     // new scans without a point: their records were staged and nothing waited for them yet
-    NDT2D_MHIP(m, hipStreamSynchronize(stream));
+    NDT2D_OBJ_HIP(m, hipStreamSynchronize(stream));
   }
   m->counts_valid = true;
   m->have_map = true;
@@ -836,30 +789,30 @@ int ndt2d_occmap_read(ndt2d_occupancy_map * m, uint32_t x0, uint32_t y0, uint32_
 {
   NDT2D_C_TRY
   if (m == nullptr) return NDT2D_ERR_INVALID;
-  if (!m->have_map) return mfail(m, NDT2D_ERR_STATE, "ndt2d_occmap_read: no map (no update yet, or the last one failed)");
+  if (!m->have_map) return fail(m, NDT2D_ERR_STATE, "ndt2d_occmap_read: no map (no update yet, or the last one failed)");
   if (static_cast<uint64_t>(x0) + w > m->geo.width || static_cast<uint64_t>(y0) + h > m->geo.height)
   {
-    return mfail(m, NDT2D_ERR_INVALID, "ndt2d_occmap_read: the rectangle leaves the map");
+    return fail(m, NDT2D_ERR_INVALID, "ndt2d_occmap_read: the rectangle leaves the map");
   }
   if (w == 0 || h == 0) return NDT2D_OK;
   if (out == nullptr || out_row_stride < w)
   {
-    return mfail(m, NDT2D_ERR_INVALID, "ndt2d_occmap_read: null output or a row stride below w");
+    return fail(m, NDT2D_ERR_INVALID, "ndt2d_occmap_read: null output or a row stride below w");
   }
   hipStream_t stream;
-  int rc = current_stream(m, &stream);
+  int rc = current_stream(m, &m->use, &stream);
   if (rc != NDT2D_OK) return rc;
   const signed char * src = m->d_data + static_cast<size_t>(y0) * m->geo.width + x0;
   if (w == m->geo.width && out_row_stride == w)
   {
-    NDT2D_MHIP(m, hipMemcpyAsync(out, src, static_cast<size_t>(w) * h, hipMemcpyDeviceToHost, stream));
+    NDT2D_OBJ_HIP(m, hipMemcpyAsync(out, src, static_cast<size_t>(w) * h, hipMemcpyDeviceToHost, stream));
   }
   else
   {
-    NDT2D_MHIP(m, hipMemcpy2DAsync(out, out_row_stride, src, m->geo.width, w, h, hipMemcpyDeviceToHost,
+    NDT2D_OBJ_HIP(m, hipMemcpy2DAsync(out, out_row_stride, src, m->geo.width, w, h, hipMemcpyDeviceToHost,
                                    stream));
   }
-  NDT2D_MHIP(m, hipStreamSynchronize(stream));
+  NDT2D_OBJ_HIP(m, hipStreamSynchronize(stream));
   return NDT2D_OK;
   NDT2D_C_CATCH(m)
 }
@@ -868,13 +821,13 @@ int ndt2d_occmap_device_map(ndt2d_occupancy_map * m, const signed char ** d_map,
 {
   NDT2D_C_TRY
   if (m == nullptr) return NDT2D_ERR_INVALID;
-  if (d_map == nullptr || info == nullptr) return mfail(m, NDT2D_ERR_INVALID, "ndt2d_occmap_device_map: null argument");
+  if (d_map == nullptr || info == nullptr) return fail(m, NDT2D_ERR_INVALID, "ndt2d_occmap_device_map: null argument");
   *d_map = nullptr;
-  if (!m->have_map) return mfail(m, NDT2D_ERR_STATE, "ndt2d_occmap_device_map: no map (no update yet, or the last one failed)");
+  if (!m->have_map) return fail(m, NDT2D_ERR_STATE, "ndt2d_occmap_device_map: no map (no update yet, or the last one failed)");
   hipStream_t stream;
-  const int rc = current_stream(m, &stream);
+  const int rc = current_stream(m, &m->use, &stream);
   if (rc != NDT2D_OK) return rc;
-  NDT2D_MHIP(m, hipStreamSynchronize(stream));   // the last update's trace and finalize are complete
+  NDT2D_OBJ_HIP(m, hipStreamSynchronize(stream));   // the last update's trace and finalize are complete
   *d_map = m->d_data;
   *info = m->geo;
   return NDT2D_OK;
@@ -887,7 +840,7 @@ int ndt2d_occmap_bounds(ndt2d_occupancy_map * m, double * bounds4_out, size_t * 
   if (m == nullptr) return NDT2D_ERR_INVALID;
   if (bounds4_out == nullptr || num_scans_out == nullptr)
   {
-    return mfail(m, NDT2D_ERR_INVALID, "ndt2d_occmap_bounds: null argument");
+    return fail(m, NDT2D_ERR_INVALID, "ndt2d_occmap_bounds: null argument");
   }
   for (int k = 0; k < 4; ++k) bounds4_out[k] = m->bounds[k];
   *num_scans_out = m->num_scans;

@@ -11,16 +11,17 @@
 //                   compare against these bits, so no reassociated scan): one wave, lane 0 walks
 //                   the chain through LDS while all 64 lanes move the tiles in and out
 //   draw_kernel     one draw per thread: libstdc++'s upper_bound bisection, the pinned key
-//   insert_kernel   open-addressing table over the draws' 96-bit keys; a slot holds the SMALLEST
-//                   draw index that has its key (claimed by CAS, lowered by atomicMin), so
-//                   "draw i met a new leaf" == (slot owner == i), whatever the schedule
+//   insert_kernel   the key table of particles/ndt2d_key_table.h over the draws' 96-bit keys; a slot
+//                   holds the SMALLEST draw index that has its key (claimed by CAS, lowered by
+//                   atomicMin), so "draw i met a new leaf" == (slot owner == i), whatever the schedule
 //   count_kernel, scan_sums_kernel, stop_kernel
-//                   inclusive scan of the new-leaf flags, Mx, stop test, min-reduction
+//                   inclusive scan of the new-leaf flags (particles/ndt2d_compact.h), Mx, stop test,
+//                   min-reduction
 //   gather_kernel   out[j] = in[p_j] for j < count (count read from device memory), and the
 //                   count to the resampler's pinned word with a system-scope vector store
 //
-// The resampler is an object of its own on the public device-layer calls (ndt2d_get_stream,
-// ndt2d_device_alloc, ndt2d_host_alloc): the device context has no field for it.
+// The resampler is an object of its own on the public device-layer calls
+// (particles/ndt2d_device_object.h): the device context has no field for it.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -30,49 +31,29 @@
 
 #include "ndt2d_guard.h"
 #include "ndt2d_hip.h"
+#include "particles/ndt2d_compact.h"
+#include "particles/ndt2d_device_object.h"
+#include "particles/ndt2d_key_table.h"
+#include "particles/ndt2d_philox.h"
+
+using namespace ndt2d::object;
 
 namespace
 {
 
-constexpr uint32_t kEmpty = 0xffffffffu;
+namespace pt = ndt2d::particles;
+using pt::kEmpty;
+
 constexpr int kWave = 64;
 constexpr int kTile = 1024;          // doubles per LDS tile of the cdf chain
 constexpr int kTileRegs = kTile / kWave;
-constexpr uint32_t kMaxBlocks = 4096;  // grid-stride kernels
 
-// ---- Philox4x32-10 (Salmon et al., SC'11): key = seed, counter = {index, step}: the convention of
-// ndt2d_pf_noise_launch (ndt2d_motion.hip keeps its own copy in an unnamed namespace) ----
-__device__ __forceinline__ void philox4x32_10(uint64_t seed, uint64_t index, uint64_t step,
-                                              uint32_t out[4])
-{
-  uint32_t c0 = static_cast<uint32_t>(index), c1 = static_cast<uint32_t>(index >> 32);
-  uint32_t c2 = static_cast<uint32_t>(step), c3 = static_cast<uint32_t>(step >> 32);
-  uint32_t k0 = static_cast<uint32_t>(seed), k1 = static_cast<uint32_t>(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r)
-  {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0;
-    c1 = lo1;
-    c2 = hi0 ^ c3 ^ k1;
-    c3 = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  out[0] = c0;
-  out[1] = c1;
-  out[2] = c2;
-  out[3] = c3;
-}
-
-// 53 random bits -> [0, 1) on the 2^-53 grid (27 bits of word 0 above 26 bits of word 1)
+// the uniform of draw `index`: words 0 and 1 of its Philox block (key = seed, counter = {index, step})
 __device__ __forceinline__ double philox_uniform(uint64_t seed, uint64_t index, uint64_t step)
 {
   uint32_t w[4];
-  philox4x32_10(seed, index, step, w);
-  const uint64_t bits = (static_cast<uint64_t>(w[0] >> 5) << 26) + static_cast<uint64_t>(w[1] >> 6);
-  return static_cast<double>(bits) * 1.1102230246251565e-16;   // 2^-53, exact
+  pt::philox4x32_10(seed, index, step, w);
+  return pt::uniform53(w[0], w[1]);
 }
 
 __global__ void __launch_bounds__(256) uniforms_kernel(double * out, uint64_t n, uint64_t seed,
@@ -237,15 +218,8 @@ __global__ void __launch_bounds__(256) draw_kernel(const double * __restrict__ p
 }
 
 // ---- 3. the leaf count ----
-// slot = (kx * 0x9E3779B1 + ky * 0x85EBCA77 + kz * 0xC2B2AE3D) mod table size (a power of two, at
-// least 2 * max_particles), linear probing.  A slot is never emptied during a launch, so every
-// draw with one key walks the same chain to the same slot.
-__device__ __forceinline__ uint32_t key_hash(int32_t kx, int32_t ky, int32_t kz)
-{
-  return static_cast<uint32_t>(kx) * 0x9E3779B1u + static_cast<uint32_t>(ky) * 0x85EBCA77u +
-         static_cast<uint32_t>(kz) * 0xC2B2AE3Du;
-}
-
+// The table (a power of two, at least 2 * max_particles) and the probe are
+// particles/ndt2d_key_table.h; the keys were written by draw_kernel.
 __global__ void __launch_bounds__(256) insert_kernel(const int32_t * __restrict__ keys,
                                                      uint64_t max_particles, uint32_t * table,
                                                      uint32_t mask, uint32_t * __restrict__ slots,
@@ -255,32 +229,16 @@ __global__ void __launch_bounds__(256) insert_kernel(const int32_t * __restrict_
        i += static_cast<uint64_t>(gridDim.x) * 256)
   {
     const uint32_t me = static_cast<uint32_t>(i);
-    const int32_t kx = keys[3 * i], ky = keys[3 * i + 1], kz = keys[3 * i + 2];
-    uint32_t slot = key_hash(kx, ky, kz) & mask;
-    uint32_t found = kEmpty;
-    for (uint32_t probe = 0; probe <= mask; ++probe)
+    uint32_t owner;
+    const uint32_t found = pt::probe_claim(keys, table, mask, me, pt::load_key(keys, i), &owner);
+    if (found == kEmpty)
     {
-      uint32_t owner = __hip_atomic_load(table + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (owner == kEmpty)
-      {
-        owner = atomicCAS(table + slot, kEmpty, me);
-        if (owner == kEmpty)
-        {
-          found = slot;
-          break;
-        }
-      }
-      // whoever owns the slot, now or later, has the key of its first owner (written by draw_kernel)
-      const uint64_t o = owner;
-      if (keys[3 * o] == kx && keys[3 * o + 1] == ky && keys[3 * o + 2] == kz)
-      {
-        if (me < owner) atomicMin(table + slot, me);
-        found = slot;
-        break;
-      }
-      slot = (slot + 1) & mask;
+      atomicOr(ctrl + 2, 1u);   // (a table at most half full cannot run out)
     }
-    if (found == kEmpty) atomicOr(ctrl + 2, 1u);   // (a table at most half full cannot run out)
+    else if (me < owner)
+    {
+      atomicMin(table + found, me);
+    }
     slots[i] = found;
   }
 }
@@ -296,41 +254,14 @@ __global__ void __launch_bounds__(256) count_kernel(const uint32_t * __restrict_
                                                     const uint32_t * __restrict__ slots,
                                                     uint64_t max_particles, uint32_t * __restrict__ sums)
 {
-  __shared__ uint32_t sh[4];
   const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
-  const bool flag = i < max_particles && is_new_leaf(table, slots, i);
-  const uint32_t c = static_cast<uint32_t>(__popcll(__ballot(flag)));
-  if ((threadIdx.x & (kWave - 1)) == 0) sh[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) sums[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+  pt::tile_count(i < max_particles && is_new_leaf(table, slots, i), sums);
 }
 
-// sums[b] -> new leaves in the blocks before b (one block; integer sums, any order)
+// sums[b] -> new leaves in the blocks before b (one block)
 __global__ void __launch_bounds__(256) scan_sums_kernel(uint32_t * sums, uint32_t n_blocks)
 {
-  __shared__ uint32_t sh[256];
-  const uint32_t t = threadIdx.x;
-  const uint32_t chunk = (n_blocks + 255) / 256;
-  const uint32_t lo = t * chunk < n_blocks ? t * chunk : n_blocks;
-  const uint32_t hi = lo + chunk < n_blocks ? lo + chunk : n_blocks;
-  uint32_t mine = 0;
-  for (uint32_t b = lo; b < hi; ++b) mine += sums[b];
-  sh[t] = mine;
-  __syncthreads();
-  for (uint32_t d = 1; d < 256; d <<= 1)
-  {
-    const uint32_t add = t >= d ? sh[t - d] : 0;
-    __syncthreads();
-    sh[t] += add;
-    __syncthreads();
-  }
-  uint32_t run = sh[t] - mine;
-  for (uint32_t b = lo; b < hi; ++b)
-  {
-    const uint32_t s = sums[b];
-    sums[b] = run;
-    run += s;
-  }
+  (void)pt::scan_tile_sums(sums, n_blocks);
 }
 
 // Mx after each draw and the stop test (particle_filter.cpp:107,117-132); ctrl[0] = the smallest
@@ -341,18 +272,11 @@ __global__ void __launch_bounds__(256) stop_kernel(const uint32_t * __restrict__
                                                    uint64_t min_particles, uint64_t max_particles,
                                                    double kld_err, double kld_z, uint32_t * ctrl)
 {
-  __shared__ uint32_t wave_count[4];
   __shared__ uint32_t block_min;
   const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & (kWave - 1);
-  const bool flag = i < max_particles && is_new_leaf(table, slots, i);
-  const unsigned long long ballot = __ballot(flag);
-  if (lane == 0) wave_count[wave] = static_cast<uint32_t>(__popcll(ballot));
   if (threadIdx.x == 0) block_min = kEmpty;
-  __syncthreads();
-  uint64_t k = sums[blockIdx.x];
-  for (int w = 0; w < wave; ++w) k += wave_count[w];
-  k += static_cast<uint64_t>(__popcll(ballot & (~0ull >> (kWave - 1 - lane))));   // inclusive
+  // the leaves after draw i (the rank's barrier orders block_min's store as well)
+  const uint64_t k = pt::tile_rank_inclusive(i < max_particles && is_new_leaf(table, slots, i), sums);
   if (i < max_particles)
   {
     uint64_t mx_pinned = max_particles;
@@ -406,23 +330,12 @@ __global__ void __launch_bounds__(256) gather_kernel(const double * __restrict__
   }
 }
 
-uint32_t stride_blocks(uint64_t n)
-{
-  const uint64_t need = (n + 255) / 256;
-  return static_cast<uint32_t>(need < kMaxBlocks ? need : kMaxBlocks);
-}
-
-size_t align_up(size_t v) { return (v + 255) & ~static_cast<size_t>(255); }
-
 }  // namespace
 
-struct ndt2d_resampler
+struct ndt2d_resampler : DeviceObject
 {
-  ndt2d_handle h = nullptr;
-  int device = 0;
   size_t n_cap = 0;
   size_t max_cap = 0;
-  std::string err;
 
   void * workspace = nullptr;
   double * cdf = nullptr;        // [n_cap]
@@ -432,8 +345,7 @@ struct ndt2d_resampler
   uint32_t * table = nullptr;    // [table_cap]
   uint32_t * sums = nullptr;     // [ceil(max_cap / 256)]
   uint32_t * ctrl = nullptr;     // {stop index, -, table-full flag, -}
-  unsigned long long * host_count = nullptr;   // pinned
-  unsigned long long * host_count_dev = nullptr;
+  Pinned<unsigned long long> count;   // the particles kept, as the gather wrote it
 
   hipStream_t stream = nullptr;  // of the launch a fetch waits for
   bool launched = false;
@@ -447,58 +359,12 @@ struct ndt2d_resampler
 namespace
 {
 
-void guard_note(ndt2d_resampler * r, const char * what) noexcept
-{
-  if (r == nullptr) return;
-  try
-  {
-    r->err = what;
-  }
-  catch (...)
-  {
-  }
-}
-void guard_note(std::nullptr_t, const char *) noexcept {}
-
-int rfail(ndt2d_resampler * r, int code, const char * what)
-{
-  guard_note(r, what);
-  return code;
-}
-
-int rfail_hip(ndt2d_resampler * r, hipError_t e, const char * where)
-{
-  try
-  {
-    r->err = std::string(where) + ": " + hipGetErrorString(e);
-  }
-  catch (...)
-  {
-  }
-  (void)hipGetLastError();
-  return NDT2D_ERR_HIP;
-}
-
-#define NDT2D_RHIP(r, call)                                         \
-  do                                                                \
-  {                                                                 \
-    const hipError_t hip_status_ = (call);                          \
-    if (hip_status_ != hipSuccess) return rfail_hip(r, hip_status_, #call); \
-  } while (0)
-
-uint64_t table_size(uint64_t max_particles)
-{
-  uint64_t t = 64;
-  while (t < 2 * max_particles) t <<= 1;
-  return t;
-}
-
 void release(ndt2d_resampler * r)
 {
   if (r->ev0 != nullptr) (void)hipEventDestroy(r->ev0);
   if (r->ev1 != nullptr) (void)hipEventDestroy(r->ev1);
   if (r->workspace != nullptr) (void)ndt2d_device_free(r->h, r->workspace);
-  if (r->host_count != nullptr) (void)ndt2d_host_free(r->h, r->host_count);
+  pinned_free(r, &r->count);
   delete r;
 }
 
@@ -527,34 +393,27 @@ int ndt2d_resampler_create(ndt2d_handle h, size_t n_capacity, size_t max_particl
   const size_t b_cdf = align_up(n_capacity * sizeof(double));
   const size_t b_draws = align_up(m * sizeof(uint32_t));
   const size_t b_keys = align_up(3 * m * sizeof(int32_t));
-  const size_t b_table = align_up(static_cast<size_t>(table_size(m)) * sizeof(uint32_t));
-  const size_t b_sums = align_up(((m + 255) / 256) * sizeof(uint32_t));
+  const size_t n_table = static_cast<size_t>(pt::table_size(m)), n_sums = (m + 255) / 256;
+  const size_t b_table = align_up(n_table * sizeof(uint32_t));
+  const size_t b_sums = align_up(n_sums * sizeof(uint32_t));
   const size_t b_ctrl = 256;
   int rc = ndt2d_device_alloc(h, b_cdf + 2 * b_draws + b_keys + b_table + b_sums + b_ctrl, &r->workspace);
-  if (rc == NDT2D_OK) rc = ndt2d_host_alloc(h, sizeof(unsigned long long), reinterpret_cast<void **>(&r->host_count));
+  if (rc == NDT2D_OK) rc = pinned_alloc(r, &r->count);
   if (rc != NDT2D_OK)
   {
     release(r);
     return rc;
   }
   char * p = static_cast<char *>(r->workspace);
-  r->cdf = reinterpret_cast<double *>(p);
-  p += b_cdf;
-  r->draws = reinterpret_cast<uint32_t *>(p);
-  p += b_draws;
-  r->slots = reinterpret_cast<uint32_t *>(p);
-  p += b_draws;
-  r->keys = reinterpret_cast<int32_t *>(p);
-  p += b_keys;
-  r->table = reinterpret_cast<uint32_t *>(p);
-  p += b_table;
-  r->sums = reinterpret_cast<uint32_t *>(p);
-  p += b_sums;
-  r->ctrl = reinterpret_cast<uint32_t *>(p);
-  *r->host_count = 0;
-  hipError_t e = hipSetDevice(r->device);
-  if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void **>(&r->host_count_dev), r->host_count, 0);
-  if (e == hipSuccess) e = hipEventCreate(&r->ev0);
+  r->cdf = carve<double>(&p, n_capacity);
+  r->draws = carve<uint32_t>(&p, m);
+  r->slots = carve<uint32_t>(&p, m);
+  r->keys = carve<int32_t>(&p, 3 * m);
+  r->table = carve<uint32_t>(&p, n_table);
+  r->sums = carve<uint32_t>(&p, n_sums);
+  r->ctrl = carve<uint32_t>(&p, 4);
+  *r->count.host = 0;
+  hipError_t e = hipEventCreate(&r->ev0);
   if (e == hipSuccess) e = hipEventCreate(&r->ev1);
   if (e != hipSuccess)
   {
@@ -594,10 +453,10 @@ int ndt2d_resampler_cdf_ms(ndt2d_resampler * r, float * ms)
 {
   NDT2D_C_TRY
   if (r == nullptr || ms == nullptr) return NDT2D_ERR_INVALID;
-  if (!r->cdf_timed) return rfail(r, NDT2D_ERR_STATE, "ndt2d_resampler_cdf_ms: no timed launch");
-  NDT2D_RHIP(r, hipSetDevice(r->device));
-  NDT2D_RHIP(r, hipEventSynchronize(r->ev1));
-  NDT2D_RHIP(r, hipEventElapsedTime(ms, r->ev0, r->ev1));
+  if (!r->cdf_timed) return fail(r, NDT2D_ERR_STATE, "ndt2d_resampler_cdf_ms: no timed launch");
+  NDT2D_OBJ_HIP(r, hipSetDevice(r->device));
+  NDT2D_OBJ_HIP(r, hipEventSynchronize(r->ev1));
+  NDT2D_OBJ_HIP(r, hipEventElapsedTime(ms, r->ev0, r->ev1));
   return NDT2D_OK;
   NDT2D_C_CATCH(r)
 }
@@ -607,12 +466,12 @@ int ndt2d_resample_uniforms_launch(ndt2d_resampler * r, uint64_t seed, uint64_t 
 {
   NDT2D_C_TRY
   if (r == nullptr) return NDT2D_ERR_INVALID;
-  if (n == 0 || d_out == nullptr) return rfail(r, NDT2D_ERR_INVALID, "ndt2d_resample_uniforms_launch: nothing to write");
-  NDT2D_RHIP(r, hipSetDevice(r->device));
+  if (n == 0 || d_out == nullptr) return fail(r, NDT2D_ERR_INVALID, "ndt2d_resample_uniforms_launch: nothing to write");
+  NDT2D_OBJ_HIP(r, hipSetDevice(r->device));
   hipStream_t stream = static_cast<hipStream_t>(ndt2d_get_stream(r->h));
-  hipLaunchKernelGGL(uniforms_kernel, dim3(stride_blocks(n)), dim3(256), 0, stream, d_out,
+  hipLaunchKernelGGL(uniforms_kernel, dim3(stride_blocks(n, 256)), dim3(256), 0, stream, d_out,
                      static_cast<uint64_t>(n), seed, first_index, step);
-  NDT2D_RHIP(r, hipGetLastError());
+  NDT2D_OBJ_HIP(r, hipGetLastError());
   return NDT2D_OK;
   NDT2D_C_CATCH(r)
 }
@@ -635,53 +494,53 @@ int ndt2d_resample_launch(ndt2d_resampler * r, const double * d_particles_xyt,
   if (n == 0 || n > 0xffffffffull || d_particles_xyt == nullptr || d_weights == nullptr ||
       leaf_size3 == nullptr || d_particles_out == nullptr || d_weights_out == nullptr)
   {
-    return rfail(r, NDT2D_ERR_INVALID, "ndt2d_resample_launch: null pointer or bad particle count");
+    return fail(r, NDT2D_ERR_INVALID, "ndt2d_resample_launch: null pointer or bad particle count");
   }
   if (n > r->n_cap || max_particles > r->max_cap)
   {
-    return rfail(r, NDT2D_ERR_INVALID, "ndt2d_resample_launch: beyond the resampler's capacity");
+    return fail(r, NDT2D_ERR_INVALID, "ndt2d_resample_launch: beyond the resampler's capacity");
   }
   if (d_particles_out == d_particles_xyt || d_weights_out == d_weights)
   {
-    return rfail(r, NDT2D_ERR_INVALID, "ndt2d_resample_launch: the gather cannot run in place");
+    return fail(r, NDT2D_ERR_INVALID, "ndt2d_resample_launch: the gather cannot run in place");
   }
-  NDT2D_RHIP(r, hipSetDevice(r->device));
+  NDT2D_OBJ_HIP(r, hipSetDevice(r->device));
   hipStream_t stream = static_cast<hipStream_t>(ndt2d_get_stream(r->h));
   const uint64_t n64 = n, max64 = max_particles;
-  const uint64_t tsize = table_size(max64);
+  const uint64_t tsize = pt::table_size(max64);
   const uint32_t item_blocks = static_cast<uint32_t>((max64 + 255) / 256);
   Leaf3 leaf;
   for (int d = 0; d < 3; ++d) leaf.v[d] = leaf_size3[d];
 
-  NDT2D_RHIP(r, hipMemsetAsync(r->table, 0xff, tsize * sizeof(uint32_t), stream));
-  NDT2D_RHIP(r, hipMemsetAsync(r->ctrl, 0xff, sizeof(uint32_t), stream));
-  NDT2D_RHIP(r, hipMemsetAsync(r->ctrl + 1, 0, 3 * sizeof(uint32_t), stream));
-  if (r->timing) NDT2D_RHIP(r, hipEventRecord(r->ev0, stream));
+  NDT2D_OBJ_HIP(r, hipMemsetAsync(r->table, 0xff, tsize * sizeof(uint32_t), stream));
+  NDT2D_OBJ_HIP(r, hipMemsetAsync(r->ctrl, 0xff, sizeof(uint32_t), stream));
+  NDT2D_OBJ_HIP(r, hipMemsetAsync(r->ctrl + 1, 0, 3 * sizeof(uint32_t), stream));
+  if (r->timing) NDT2D_OBJ_HIP(r, hipEventRecord(r->ev0, stream));
   hipLaunchKernelGGL(cdf_kernel, dim3(1), dim3(kWave), 0, stream, d_weights, n64, r->cdf);
-  NDT2D_RHIP(r, hipGetLastError());
+  NDT2D_OBJ_HIP(r, hipGetLastError());
   if (r->timing)
   {
-    NDT2D_RHIP(r, hipEventRecord(r->ev1, stream));
+    NDT2D_OBJ_HIP(r, hipEventRecord(r->ev1, stream));
     r->cdf_timed = true;
   }
-  hipLaunchKernelGGL(draw_kernel, dim3(stride_blocks(max64)), dim3(256), 0, stream, d_particles_xyt,
+  hipLaunchKernelGGL(draw_kernel, dim3(stride_blocks(max64, 256)), dim3(256), 0, stream, d_particles_xyt,
                      r->cdf, n64, d_uniforms, seed, step, max64, leaf, r->draws, r->keys);
-  NDT2D_RHIP(r, hipGetLastError());
-  hipLaunchKernelGGL(insert_kernel, dim3(stride_blocks(max64)), dim3(256), 0, stream, r->keys, max64,
+  NDT2D_OBJ_HIP(r, hipGetLastError());
+  hipLaunchKernelGGL(insert_kernel, dim3(stride_blocks(max64, 256)), dim3(256), 0, stream, r->keys, max64,
                      r->table, static_cast<uint32_t>(tsize - 1), r->slots, r->ctrl);
-  NDT2D_RHIP(r, hipGetLastError());
+  NDT2D_OBJ_HIP(r, hipGetLastError());
   hipLaunchKernelGGL(count_kernel, dim3(item_blocks), dim3(256), 0, stream, r->table, r->slots, max64,
                      r->sums);
-  NDT2D_RHIP(r, hipGetLastError());
+  NDT2D_OBJ_HIP(r, hipGetLastError());
   hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(256), 0, stream, r->sums, item_blocks);
-  NDT2D_RHIP(r, hipGetLastError());
+  NDT2D_OBJ_HIP(r, hipGetLastError());
   hipLaunchKernelGGL(stop_kernel, dim3(item_blocks), dim3(256), 0, stream, r->table, r->slots, r->sums,
                      static_cast<uint64_t>(min_particles), max64, kld_err, kld_z, r->ctrl);
-  NDT2D_RHIP(r, hipGetLastError());
-  hipLaunchKernelGGL(gather_kernel, dim3(stride_blocks(max64)), dim3(256), 0, stream, d_particles_xyt,
+  NDT2D_OBJ_HIP(r, hipGetLastError());
+  hipLaunchKernelGGL(gather_kernel, dim3(stride_blocks(max64, 256)), dim3(256), 0, stream, d_particles_xyt,
                      d_weights, r->draws, r->ctrl, max64, d_particles_out, d_weights_out, d_indices_out,
-                     r->host_count_dev);
-  NDT2D_RHIP(r, hipGetLastError());
+                     r->count.dev);
+  NDT2D_OBJ_HIP(r, hipGetLastError());
   r->stream = stream;
   r->launched = true;
   r->launched_empty = false;
@@ -694,12 +553,12 @@ int ndt2d_resample_fetch(ndt2d_resampler * r, size_t * n_out)
   NDT2D_C_TRY
   if (r == nullptr || n_out == nullptr) return NDT2D_ERR_INVALID;
   *n_out = 0;
-  if (!r->launched) return rfail(r, NDT2D_ERR_STATE, "ndt2d_resample_fetch: nothing launched");
+  if (!r->launched) return fail(r, NDT2D_ERR_STATE, "ndt2d_resample_fetch: nothing launched");
   r->launched = false;
   if (r->launched_empty) return NDT2D_OK;
-  NDT2D_RHIP(r, hipSetDevice(r->device));
-  NDT2D_RHIP(r, hipStreamSynchronize(r->stream));
-  *n_out = static_cast<size_t>(__atomic_load_n(r->host_count, __ATOMIC_ACQUIRE));
+  NDT2D_OBJ_HIP(r, hipSetDevice(r->device));
+  NDT2D_OBJ_HIP(r, hipStreamSynchronize(r->stream));
+  *n_out = static_cast<size_t>(__atomic_load_n(r->count.host, __ATOMIC_ACQUIRE));
   return NDT2D_OK;
   NDT2D_C_CATCH(r)
 }

@@ -2,15 +2,13 @@
 // the free cells of an occupancy map with a uniform heading, and the replacement of a share of a set
 // by fresh such particles.  The arithmetic of a sample is seed/ndt2d_seed_fn.h.
 //
-// The free table free_cells[F] (the row-major indices of the cells whose byte is 0, ascending) is an
-// order-preserving compaction without atomics, a tile being the 256 cells of one block:
+// The free table free_cells[F] (the row-major indices of the cells whose byte is 0, ascending) is the
+// order-preserving compaction of particles/ndt2d_compact.h over the flags "cell i is free":
 //
-//   count_kernel    free cells per tile: one ballot and one popcount per wave
-//   scan_kernel     exclusive scan of the tile counts in ONE block: a chunk of tiles per thread, a
-//                   fixed doubling tree over the 256 chunk sums in LDS; the total F goes to the
+//   count_kernel    free cells per tile
+//   scan_kernel     exclusive scan of the tile counts in one block; the total F goes to the
 //                   seeder's pinned word by a system-scope vector store
-//   scatter_kernel  the same ballots again: a lane's rank is its tile's offset plus its waves'
-//                   counts before it plus the popcount of the ballot bits below it
+//   scatter_kernel  a free cell to its rank
 //
 // The host reads F between the scan and the scatter, so the table is allocated at its size.
 //
@@ -20,8 +18,8 @@
 //                   particles are counted per block by ballots
 //   fold_kernel     the block counts added by one block: a strided share per thread, fixed trees
 //
-// The seeder is an object of its own on the public device-layer calls (ndt2d_get_stream,
-// ndt2d_device_alloc, ndt2d_host_alloc): the device context has no field for it.
+// The seeder is an object of its own on the public device-layer calls
+// (particles/ndt2d_device_object.h): the device context has no field for it.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -31,17 +29,21 @@
 
 #include "ndt2d_guard.h"
 #include "ndt2d_hip.h"
+#include "particles/ndt2d_compact.h"
+#include "particles/ndt2d_device_object.h"
 #include "seed/ndt2d_seed_fn.h"
+
+using namespace ndt2d::object;
 
 namespace
 {
 
 namespace fn = ndt2d::seed;
+namespace compact = ndt2d::particles;
 
 constexpr int kWave = 64;
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / kWave;
-constexpr uint32_t kMaxBlocks = 4096;   // grid-stride kernels
 
 struct Region
 {
@@ -61,47 +63,19 @@ __global__ void __launch_bounds__(kBlock) count_kernel(const signed char * __res
                                                        uint32_t width, Region r, uint32_t n,
                                                        uint32_t * __restrict__ sums)
 {
-  __shared__ uint32_t sh[kWaves];
   uint32_t cell = 0;
-  const bool flag = item_free(map, width, r, n, blockIdx.x * kBlock + threadIdx.x, &cell);
-  const uint32_t c = static_cast<uint32_t>(__popcll(__ballot(flag)));
-  if ((threadIdx.x & (kWave - 1)) == 0) sh[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) sums[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+  compact::tile_count(item_free(map, width, r, n, blockIdx.x * kBlock + threadIdx.x, &cell), sums);
 }
 
 // sums[b] -> free cells in the tiles before b; the total to host_total (pinned)
 __global__ void __launch_bounds__(kBlock) scan_kernel(uint32_t * sums, uint32_t n_tiles,
                                                       unsigned long long * host_total)
 {
-  __shared__ uint32_t sh[kBlock];
-  const uint32_t t = threadIdx.x;
-  const uint32_t chunk = (n_tiles + kBlock - 1) / kBlock;
-  const uint64_t lo64 = static_cast<uint64_t>(t) * chunk;
-  const uint32_t lo = lo64 < n_tiles ? static_cast<uint32_t>(lo64) : n_tiles;
-  const uint32_t hi = n_tiles - lo > chunk ? lo + chunk : n_tiles;
-  uint32_t mine = 0;
-  for (uint32_t b = lo; b < hi; ++b) mine += sums[b];
-  sh[t] = mine;
-  __syncthreads();
-  for (uint32_t d = 1; d < kBlock; d <<= 1)
+  const uint32_t total = compact::scan_tile_sums(sums, n_tiles);
+  if (threadIdx.x == kBlock - 1)
   {
-    const uint32_t add = t >= d ? sh[t - d] : 0;
-    __syncthreads();
-    sh[t] += add;
-    __syncthreads();
-  }
-  uint32_t run = sh[t] - mine;
-  for (uint32_t b = lo; b < hi; ++b)
-  {
-    const uint32_t s = sums[b];
-    sums[b] = run;
-    run += s;
-  }
-  if (t == kBlock - 1)
-  {
-    // the pinned word, written through at system scope (a vector store), as the resampler's count
-    __hip_atomic_store(host_total, static_cast<unsigned long long>(sh[t]), __ATOMIC_RELAXED,
+    // the pinned word, written through at system scope (a vector store)
+    __hip_atomic_store(host_total, static_cast<unsigned long long>(total), __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
@@ -112,17 +86,10 @@ __global__ void __launch_bounds__(kBlock) scatter_kernel(const signed char * __r
                                                          uint32_t n_free,
                                                          uint32_t * __restrict__ free_cells)
 {
-  __shared__ uint32_t sh[kWaves];
-  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & (kWave - 1);
   uint32_t cell = 0;
   const bool flag = item_free(map, width, r, n, blockIdx.x * kBlock + threadIdx.x, &cell);
-  const unsigned long long ballot = __ballot(flag);
-  if (lane == 0) sh[wave] = static_cast<uint32_t>(__popcll(ballot));
-  __syncthreads();
+  const uint32_t rank = compact::tile_rank(flag, sums);
   if (!flag) return;
-  uint32_t rank = sums[blockIdx.x];
-  for (uint32_t w = 0; w < wave; ++w) rank += sh[w];
-  rank += fn::rank_in_wave(ballot, lane);
   // (the map the count saw is the map read here: rank < n_free; the test keeps a map that changed
   // in between from writing past the table)
   if (rank < n_free) free_cells[rank] = cell;
@@ -194,20 +161,10 @@ __global__ void __launch_bounds__(kBlock) fold_kernel(const unsigned long long *
   if (threadIdx.x == 0) *out = sh[0] + sh[1] + sh[2] + sh[3];
 }
 
-uint32_t stride_blocks(uint64_t n)
-{
-  const uint64_t need = (n + kBlock - 1) / kBlock;
-  return static_cast<uint32_t>(need < kMaxBlocks ? need : kMaxBlocks);
-}
-
 }  // namespace
 
-struct ndt2d_seeder
+struct ndt2d_seeder : DeviceObject
 {
-  ndt2d_handle h = nullptr;
-  int device = 0;
-  std::string err;
-
   // the table and what it was made from
   bool have_table = false;
   uint64_t n_free = 0;
@@ -219,11 +176,9 @@ struct ndt2d_seeder
   signed char * d_stage = nullptr; // [stage_cap] a host map's copy
   size_t stage_cap = 0;
   unsigned long long * d_blocks = nullptr;       // [kMaxBlocks] inject's block counts
-  unsigned long long * host_total = nullptr;     // pinned
-  unsigned long long * host_total_dev = nullptr;
+  Pinned<unsigned long long> total;              // F, as the scan wrote it
 
-  hipStream_t last_stream = nullptr;   // of the last launch
-  bool used = false;
+  StreamUse use;
 
   bool timing = false;
   bool table_timed = false, sample_timed = false;
@@ -232,45 +187,6 @@ struct ndt2d_seeder
 
 namespace
 {
-
-void guard_note(ndt2d_seeder * s, const char * what) noexcept
-{
-  if (s == nullptr) return;
-  try
-  {
-    s->err = what;
-  }
-  catch (...)
-  {
-  }
-}
-void guard_note(std::nullptr_t, const char *) noexcept {}
-
-int sfail(ndt2d_seeder * s, int code, const char * what)
-{
-  guard_note(s, what);
-  return code;
-}
-
-int sfail_hip(ndt2d_seeder * s, hipError_t e, const char * where)
-{
-  try
-  {
-    s->err = std::string(where) + ": " + hipGetErrorString(e);
-  }
-  catch (...)
-  {
-  }
-  (void)hipGetLastError();
-  return NDT2D_ERR_HIP;
-}
-
-#define NDT2D_SHIP(s, call)                                          \
-  do                                                                 \
-  {                                                                  \
-    const hipError_t hip_status_ = (call);                           \
-    if (hip_status_ != hipSuccess) return sfail_hip(s, hip_status_, #call); \
-  } while (0)
 
 void release(ndt2d_seeder * s)
 {
@@ -282,37 +198,11 @@ void release(ndt2d_seeder * s)
   if (s->d_sums != nullptr) (void)ndt2d_device_free(s->h, s->d_sums);
   if (s->d_stage != nullptr) (void)ndt2d_device_free(s->h, s->d_stage);
   if (s->d_blocks != nullptr) (void)ndt2d_device_free(s->h, s->d_blocks);
-  if (s->host_total != nullptr) (void)ndt2d_host_free(s->h, s->host_total);
+  pinned_free(s, &s->total);
   delete s;
 }
 
-// The context's current stream; work queued on a stream the caller has since replaced finishes first.
-int current_stream(ndt2d_seeder * s, hipStream_t * out)
-{
-  NDT2D_SHIP(s, hipSetDevice(s->device));
-  hipStream_t stream = static_cast<hipStream_t>(ndt2d_get_stream(s->h));
-  if (s->used && stream != s->last_stream) NDT2D_SHIP(s, hipStreamSynchronize(s->last_stream));
-  s->last_stream = stream;
-  s->used = true;
-  *out = stream;
-  return NDT2D_OK;
-}
-
-// room for `need` items; nothing in flight reads the old block (the caller has synchronised)
-template <typename T>
-int reserve(ndt2d_seeder * s, T ** buf, size_t * cap, size_t need)
-{
-  if (need <= *cap) return NDT2D_OK;
-  if (*buf != nullptr) (void)ndt2d_device_free(s->h, *buf);
-  *buf = nullptr;
-  *cap = 0;
-  void * p = nullptr;
-  const int rc = ndt2d_device_alloc(s->h, need * sizeof(T), &p);
-  if (rc != NDT2D_OK) return sfail(s, rc, "ndt2d_seed_set_map: device allocation failed");
-  *buf = static_cast<T *>(p);
-  *cap = need;
-  return NDT2D_OK;
-}
+constexpr const char * kNoRoom = "ndt2d_seed_set_map: device allocation failed";
 
 // what both forms of set_map refuse, before anything runs
 const char * refusal(const signed char * map, uint32_t width, uint32_t height, double origin_x,
@@ -348,27 +238,27 @@ int build_table(ndt2d_seeder * s, const signed char * d_map, uint32_t width, uin
   uint64_t n_free = 0;
   if (n > 0)
   {
-    int rc = reserve(s, &s->d_sums, &s->sums_cap, n_tiles);
+    int rc = reserve(s, &s->d_sums, &s->sums_cap, n_tiles, kNoRoom);
     if (rc != NDT2D_OK) return rc;
-    if (s->timing) NDT2D_SHIP(s, hipEventRecord(s->t0, stream));
+    if (s->timing) NDT2D_OBJ_HIP(s, hipEventRecord(s->t0, stream));
     hipLaunchKernelGGL(count_kernel, dim3(n_tiles), dim3(kBlock), 0, stream, d_map, width, r, n, s->d_sums);
-    NDT2D_SHIP(s, hipGetLastError());
-    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(kBlock), 0, stream, s->d_sums, n_tiles, s->host_total_dev);
-    NDT2D_SHIP(s, hipGetLastError());
-    NDT2D_SHIP(s, hipStreamSynchronize(stream));
-    n_free = static_cast<uint64_t>(__atomic_load_n(s->host_total, __ATOMIC_ACQUIRE));
-    if (n_free > n) return sfail(s, NDT2D_ERR_INTERNAL, "ndt2d_seed_set_map: a count above the region's cells");
+    NDT2D_OBJ_HIP(s, hipGetLastError());
+    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(kBlock), 0, stream, s->d_sums, n_tiles, s->total.dev);
+    NDT2D_OBJ_HIP(s, hipGetLastError());
+    NDT2D_OBJ_HIP(s, hipStreamSynchronize(stream));
+    n_free = static_cast<uint64_t>(__atomic_load_n(s->total.host, __ATOMIC_ACQUIRE));
+    if (n_free > n) return fail(s, NDT2D_ERR_INTERNAL, "ndt2d_seed_set_map: a count above the region's cells");
     if (n_free > 0)
     {
-      rc = reserve(s, &s->d_free, &s->free_cap, static_cast<size_t>(n_free));
+      rc = reserve(s, &s->d_free, &s->free_cap, static_cast<size_t>(n_free), kNoRoom);
       if (rc != NDT2D_OK) return rc;
       hipLaunchKernelGGL(scatter_kernel, dim3(n_tiles), dim3(kBlock), 0, stream, d_map, width, r, n,
                          s->d_sums, static_cast<uint32_t>(n_free), s->d_free);
-      NDT2D_SHIP(s, hipGetLastError());
+      NDT2D_OBJ_HIP(s, hipGetLastError());
     }
-    if (s->timing) NDT2D_SHIP(s, hipEventRecord(s->t1, stream));
+    if (s->timing) NDT2D_OBJ_HIP(s, hipEventRecord(s->t1, stream));
     // the caller's map (a staged copy or a resident one) is free again when this returns
-    NDT2D_SHIP(s, hipStreamSynchronize(stream));
+    NDT2D_OBJ_HIP(s, hipStreamSynchronize(stream));
     s->table_timed = s->timing;
   }
   s->n_free = n_free;
@@ -381,9 +271,9 @@ int build_table(ndt2d_seeder * s, const signed char * d_map, uint32_t width, uin
 int sample_prelude(ndt2d_seeder * s, const double * d_poses, size_t n, const char * null_text,
                    const char * state_text, const char * empty_text)
 {
-  if (n > 0 && d_poses == nullptr) return sfail(s, NDT2D_ERR_INVALID, null_text);
-  if (!s->have_table) return sfail(s, NDT2D_ERR_STATE, state_text);
-  if (s->n_free == 0) return sfail(s, NDT2D_ERR_STATE, empty_text);
+  if (n > 0 && d_poses == nullptr) return fail(s, NDT2D_ERR_INVALID, null_text);
+  if (!s->have_table) return fail(s, NDT2D_ERR_STATE, state_text);
+  if (s->n_free == 0) return fail(s, NDT2D_ERR_STATE, empty_text);
   return NDT2D_OK;
 }
 
@@ -403,16 +293,14 @@ int ndt2d_seed_create(ndt2d_handle h, ndt2d_seeder ** out)
   void * p = nullptr;
   int rc = ndt2d_device_alloc(h, kMaxBlocks * sizeof(unsigned long long), &p);
   s->d_blocks = static_cast<unsigned long long *>(p);
-  if (rc == NDT2D_OK) rc = ndt2d_host_alloc(h, sizeof(unsigned long long), reinterpret_cast<void **>(&s->host_total));
+  if (rc == NDT2D_OK) rc = pinned_alloc(s, &s->total);
   if (rc != NDT2D_OK)
   {
     release(s);
     return rc;
   }
-  *s->host_total = 0;
-  hipError_t e = hipSetDevice(s->device);
-  if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void **>(&s->host_total_dev), s->host_total, 0);
-  if (e == hipSuccess) e = hipEventCreate(&s->t0);
+  *s->total.host = 0;
+  hipError_t e = hipEventCreate(&s->t0);
   if (e == hipSuccess) e = hipEventCreate(&s->t1);
   if (e == hipSuccess) e = hipEventCreate(&s->s0);
   if (e == hipSuccess) e = hipEventCreate(&s->s1);
@@ -432,7 +320,7 @@ int ndt2d_seed_destroy(ndt2d_seeder * s)
   NDT2D_C_TRY
   if (s == nullptr) return NDT2D_ERR_INVALID;
   (void)hipSetDevice(s->device);
-  if (s->used) (void)hipStreamSynchronize(s->last_stream);
+  if (s->use.used) (void)hipStreamSynchronize(s->use.last_stream);
   release(s);
   return NDT2D_OK;
   NDT2D_C_CATCH(nullptr)
@@ -454,16 +342,16 @@ int ndt2d_seed_last_ms(ndt2d_seeder * s, float * table_ms, float * sample_ms)
 {
   NDT2D_C_TRY
   if (s == nullptr) return NDT2D_ERR_INVALID;
-  if (table_ms == nullptr || sample_ms == nullptr) return sfail(s, NDT2D_ERR_INVALID, "ndt2d_seed_last_ms: null argument");
-  if (!s->table_timed && !s->sample_timed) return sfail(s, NDT2D_ERR_STATE, "ndt2d_seed_last_ms: no timed launch");
+  if (table_ms == nullptr || sample_ms == nullptr) return fail(s, NDT2D_ERR_INVALID, "ndt2d_seed_last_ms: null argument");
+  if (!s->table_timed && !s->sample_timed) return fail(s, NDT2D_ERR_STATE, "ndt2d_seed_last_ms: no timed launch");
   *table_ms = 0.0f;
   *sample_ms = 0.0f;
-  NDT2D_SHIP(s, hipSetDevice(s->device));
-  if (s->table_timed) NDT2D_SHIP(s, hipEventElapsedTime(table_ms, s->t0, s->t1));
+  NDT2D_OBJ_HIP(s, hipSetDevice(s->device));
+  if (s->table_timed) NDT2D_OBJ_HIP(s, hipEventElapsedTime(table_ms, s->t0, s->t1));
   if (s->sample_timed)
   {
-    NDT2D_SHIP(s, hipEventSynchronize(s->s1));
-    NDT2D_SHIP(s, hipEventElapsedTime(sample_ms, s->s0, s->s1));
+    NDT2D_OBJ_HIP(s, hipEventSynchronize(s->s1));
+    NDT2D_OBJ_HIP(s, hipEventElapsedTime(sample_ms, s->s0, s->s1));
   }
   return NDT2D_OK;
   NDT2D_C_CATCH(s)
@@ -475,15 +363,15 @@ int ndt2d_seed_set_map(ndt2d_seeder * s, const signed char * map, uint32_t width
   NDT2D_C_TRY
   if (s == nullptr) return NDT2D_ERR_INVALID;
   const char * why = refusal(map, width, height, origin_x, origin_y, resolution, region4);
-  if (why != nullptr) return sfail(s, NDT2D_ERR_INVALID, why);
+  if (why != nullptr) return fail(s, NDT2D_ERR_INVALID, why);
   hipStream_t stream;
-  int rc = current_stream(s, &stream);
+  int rc = current_stream(s, &s->use, &stream);
   if (rc != NDT2D_OK) return rc;
-  NDT2D_SHIP(s, hipStreamSynchronize(stream));   // no sample in flight reads the table
+  NDT2D_OBJ_HIP(s, hipStreamSynchronize(stream));   // no sample in flight reads the table
   const size_t cells = static_cast<size_t>(width) * height;
   s->have_table = false;
-  if ((rc = reserve(s, &s->d_stage, &s->stage_cap, cells)) != NDT2D_OK) return rc;
-  NDT2D_SHIP(s, hipMemcpyAsync(s->d_stage, map, cells, hipMemcpyHostToDevice, stream));
+  if ((rc = reserve(s, &s->d_stage, &s->stage_cap, cells, kNoRoom)) != NDT2D_OK) return rc;
+  NDT2D_OBJ_HIP(s, hipMemcpyAsync(s->d_stage, map, cells, hipMemcpyHostToDevice, stream));
   return build_table(s, s->d_stage, width, height, origin_x, origin_y, resolution, region4, stream);
   NDT2D_C_CATCH(s)
 }
@@ -495,11 +383,11 @@ int ndt2d_seed_set_map_device(ndt2d_seeder * s, const signed char * d_map, uint3
   NDT2D_C_TRY
   if (s == nullptr) return NDT2D_ERR_INVALID;
   const char * why = refusal(d_map, width, height, origin_x, origin_y, resolution, region4);
-  if (why != nullptr) return sfail(s, NDT2D_ERR_INVALID, why);
+  if (why != nullptr) return fail(s, NDT2D_ERR_INVALID, why);
   hipStream_t stream;
-  const int rc = current_stream(s, &stream);
+  const int rc = current_stream(s, &s->use, &stream);
   if (rc != NDT2D_OK) return rc;
-  NDT2D_SHIP(s, hipStreamSynchronize(stream));
+  NDT2D_OBJ_HIP(s, hipStreamSynchronize(stream));
   return build_table(s, d_map, width, height, origin_x, origin_y, resolution, region4, stream);
   NDT2D_C_CATCH(s)
 }
@@ -508,8 +396,8 @@ int ndt2d_seed_free_count(ndt2d_seeder * s, size_t * n_out)
 {
   NDT2D_C_TRY
   if (s == nullptr) return NDT2D_ERR_INVALID;
-  if (n_out == nullptr) return sfail(s, NDT2D_ERR_INVALID, "ndt2d_seed_free_count: null argument");
-  if (!s->have_table) return sfail(s, NDT2D_ERR_STATE, "ndt2d_seed_free_count: no map (none set, or the last one failed)");
+  if (n_out == nullptr) return fail(s, NDT2D_ERR_INVALID, "ndt2d_seed_free_count: null argument");
+  if (!s->have_table) return fail(s, NDT2D_ERR_STATE, "ndt2d_seed_free_count: no map (none set, or the last one failed)");
   *n_out = static_cast<size_t>(s->n_free);
   return NDT2D_OK;
   NDT2D_C_CATCH(s)
@@ -519,13 +407,13 @@ int ndt2d_seed_read_table(ndt2d_seeder * s, uint32_t * out, size_t capacity, siz
 {
   NDT2D_C_TRY
   if (s == nullptr) return NDT2D_ERR_INVALID;
-  if (n_out == nullptr) return sfail(s, NDT2D_ERR_INVALID, "ndt2d_seed_read_table: null argument");
+  if (n_out == nullptr) return fail(s, NDT2D_ERR_INVALID, "ndt2d_seed_read_table: null argument");
   *n_out = 0;
-  if (!s->have_table) return sfail(s, NDT2D_ERR_STATE, "ndt2d_seed_read_table: no map (none set, or the last one failed)");
+  if (!s->have_table) return fail(s, NDT2D_ERR_STATE, "ndt2d_seed_read_table: no map (none set, or the last one failed)");
   const size_t count = static_cast<size_t>(s->n_free);
   *n_out = count;
   if (count == 0) return NDT2D_OK;
-  if (out == nullptr || capacity < count) return sfail(s, NDT2D_ERR_INVALID, "ndt2d_seed_read_table: null output or a capacity below the count");
+  if (out == nullptr || capacity < count) return fail(s, NDT2D_ERR_INVALID, "ndt2d_seed_read_table: null output or a capacity below the count");
   return ndt2d_copy_to_host(s->h, out, s->d_free, count * sizeof(uint32_t));
   NDT2D_C_CATCH(s)
 }
@@ -541,15 +429,15 @@ int ndt2d_seed_launch(ndt2d_seeder * s, double * d_poses_xyt, size_t n, uint64_t
   if (refused != NDT2D_OK) return refused;
   if (n == 0) return NDT2D_OK;
   hipStream_t stream;
-  const int rc = current_stream(s, &stream);
+  const int rc = current_stream(s, &s->use, &stream);
   if (rc != NDT2D_OK) return rc;
-  if (s->timing) NDT2D_SHIP(s, hipEventRecord(s->s0, stream));
-  hipLaunchKernelGGL(sample_kernel, dim3(stride_blocks(n)), dim3(kBlock), 0, stream, d_poses_xyt,
+  if (s->timing) NDT2D_OBJ_HIP(s, hipEventRecord(s->s0, stream));
+  hipLaunchKernelGGL(sample_kernel, dim3(stride_blocks(n, kBlock)), dim3(kBlock), 0, stream, d_poses_xyt,
                      static_cast<uint64_t>(n), seed, step, first_index, s->d_free, s->n_free, s->geo);
-  NDT2D_SHIP(s, hipGetLastError());
+  NDT2D_OBJ_HIP(s, hipGetLastError());
   if (s->timing)
   {
-    NDT2D_SHIP(s, hipEventRecord(s->s1, stream));
+    NDT2D_OBJ_HIP(s, hipEventRecord(s->s1, stream));
     s->sample_timed = true;
   }
   return NDT2D_OK;
@@ -563,7 +451,7 @@ int ndt2d_seed_inject_launch(ndt2d_seeder * s, double * d_poses_xyt, size_t n, d
   if (s == nullptr) return NDT2D_ERR_INVALID;
   if (!(probability >= 0.0 && probability <= 1.0))
   {
-    return sfail(s, NDT2D_ERR_INVALID, "ndt2d_seed_inject_launch: the probability is not in [0, 1]");
+    return fail(s, NDT2D_ERR_INVALID, "ndt2d_seed_inject_launch: the probability is not in [0, 1]");
   }
   const int refused = sample_prelude(s, d_poses_xyt, n, "ndt2d_seed_inject_launch: null poses",
                                      "ndt2d_seed_inject_launch: no map (none set, or the last one failed)",
@@ -571,29 +459,29 @@ int ndt2d_seed_inject_launch(ndt2d_seeder * s, double * d_poses_xyt, size_t n, d
   if (refused != NDT2D_OK) return refused;
   if (n == 0 && d_count == nullptr) return NDT2D_OK;
   hipStream_t stream;
-  const int rc = current_stream(s, &stream);
+  const int rc = current_stream(s, &s->use, &stream);
   if (rc != NDT2D_OK) return rc;
   if (n == 0 || probability == 0.0)
   {
     // no draw lies below 0: nothing is written
-    if (d_count != nullptr) NDT2D_SHIP(s, hipMemsetAsync(d_count, 0, sizeof(uint64_t), stream));
+    if (d_count != nullptr) NDT2D_OBJ_HIP(s, hipMemsetAsync(d_count, 0, sizeof(uint64_t), stream));
     return NDT2D_OK;
   }
-  const uint32_t blocks = stride_blocks(n);
-  if (s->timing) NDT2D_SHIP(s, hipEventRecord(s->s0, stream));
+  const uint32_t blocks = stride_blocks(n, kBlock);
+  if (s->timing) NDT2D_OBJ_HIP(s, hipEventRecord(s->s0, stream));
   hipLaunchKernelGGL(inject_kernel, dim3(blocks), dim3(kBlock), 0, stream, d_poses_xyt,
                      static_cast<uint64_t>(n), probability, seed, step, first_index, s->d_free,
                      s->n_free, s->geo, d_count != nullptr ? s->d_blocks : nullptr);
-  NDT2D_SHIP(s, hipGetLastError());
+  NDT2D_OBJ_HIP(s, hipGetLastError());
   if (d_count != nullptr)
   {
     hipLaunchKernelGGL(fold_kernel, dim3(1), dim3(kBlock), 0, stream, s->d_blocks, blocks,
                        reinterpret_cast<unsigned long long *>(d_count));
-    NDT2D_SHIP(s, hipGetLastError());
+    NDT2D_OBJ_HIP(s, hipGetLastError());
   }
   if (s->timing)
   {
-    NDT2D_SHIP(s, hipEventRecord(s->s1, stream));
+    NDT2D_OBJ_HIP(s, hipEventRecord(s->s1, stream));
     s->sample_timed = true;
   }
   return NDT2D_OK;

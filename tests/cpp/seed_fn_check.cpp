@@ -1,10 +1,10 @@
-// Stand-alone check of ndt_2d_amd/csrc/seed/ndt2d_seed_fn.h: Philox against Random123's known
-// answers, the uniforms and the pick of a free cell against integer arithmetic (the double product
-// of the pick restated as a round-to-nearest-even of a 128-bit integer), the cell -> pose arithmetic
-// against long double and the occupancy grid's own cell rule, and the order-preserving compaction
-// (tile counts, exclusive scan, ranks from ballots) run serially over random maps against a plain
-// loop.  Built with the host compiler (once more with -fsanitize=address,undefined) and run
-// directly; no device, no library.  Prints one line per designed sample
+// Stand-alone check of ndt_2d_amd/csrc/seed/ndt2d_seed_fn.h and of particles/ndt2d_philox.h under
+// it: Philox against Random123's known answers, the uniforms and the pick of a free cell against
+// integer arithmetic (the double product of the pick restated as a round-to-nearest-even of a
+// 128-bit integer), the cell -> pose arithmetic against long double and the occupancy grid's own
+// cell rule.  (The table's compaction: tests/cpp/compact_fn_check.cpp.)  Built with the host
+// compiler (once more with -fsanitize=address,undefined) and run directly; no device, no library.
+// Prints one line per designed sample
 // ("P <seed> <step> <index> <x hex> <y hex> <theta hex> <inject hex>") for
 // tests/test_seed_restatement.py to compare with the restatement bit for bit; exits non-zero when a
 // check fails.
@@ -16,6 +16,7 @@
 
 #include "ndt2d_seed_fn.h"
 
+namespace P = ndt2d::particles;
 namespace S = ndt2d::seed;
 
 namespace
@@ -74,43 +75,6 @@ uint64_t pick_in_integers(uint64_t bits, uint64_t n_free)
   return k < n_free - 1 ? k : n_free - 1;
 }
 
-// The three launches of the table build, serially: 256 cells a tile, 64 lanes a wave.
-std::vector<uint32_t> compact_as_launched(const std::vector<signed char> & map, uint32_t width,
-                                          uint32_t x0, uint32_t y0, uint32_t w, uint32_t h)
-{
-  const uint32_t n = w * h, n_tiles = (n + 255) / 256;
-  std::vector<uint64_t> ballots(static_cast<size_t>(n_tiles) * 4, 0);
-  std::vector<uint32_t> sums(n_tiles, 0);
-  for (uint32_t i = 0; i < n; ++i)
-  {
-    if (S::is_free(map[S::region_cell(i, x0, y0, w, width)])) ballots[i / 64] |= 1ull << (i % 64);
-  }
-  for (uint32_t t = 0; t < n_tiles; ++t)
-  {
-    for (int wv = 0; wv < 4; ++wv) sums[t] += S::popcount64(ballots[4 * t + wv]);
-  }
-  uint32_t run = 0;
-  for (uint32_t t = 0; t < n_tiles; ++t)
-  {
-    const uint32_t c = sums[t];
-    sums[t] = run;
-    run += c;
-  }
-  std::vector<uint32_t> out(run, 0xffffffffu);
-  for (uint32_t i = 0; i < n; ++i)
-  {
-    const uint32_t tile = i / 256, wave = (i % 256) / 64, lane = i % 64;
-    const uint64_t ballot = ballots[4 * tile + wave];
-    if (((ballot >> lane) & 1) == 0) continue;
-    uint32_t rank = sums[tile];
-    for (uint32_t wv = 0; wv < wave; ++wv) rank += S::popcount64(ballots[4 * tile + wv]);
-    rank += S::rank_in_wave(ballot, lane);
-    check(rank < out.size() && out[rank] == 0xffffffffu, "compaction: a rank outside the table or taken twice");
-    if (rank < out.size()) out[rank] = S::region_cell(i, x0, y0, w, width);
-  }
-  return out;
-}
-
 }  // namespace
 
 int main()
@@ -129,26 +93,26 @@ int main()
     for (const Kat & k : kat)
     {
       uint32_t w[4];
-      S::philox4x32_10(k.seed, k.index, k.step, w);
+      P::philox4x32_10(k.seed, k.index, k.step, w);
       check(w[0] == k.out[0] && w[1] == k.out[1] && w[2] == k.out[2] && w[3] == k.out[3], "philox: known answer");
     }
   }
 
   // ---- the uniforms: designed words at both ends, random words, against integers ----
   SplitMix64 rng{2024};
-  check(S::uniform53(0u, 0u) == 0.0, "uniform53: all-zero words");
-  check(S::uniform53(31u, 63u) == 0.0, "uniform53: the dropped low bits");
-  check(S::uniform53(~0u, ~0u) == 1.0 - std::ldexp(1.0, -53) && S::uniform53(~0u, ~0u) < 1.0, "uniform53: all-one words");
-  check(S::uniform24(0u) == std::ldexp(1.0, -25) && S::uniform24(255u) == std::ldexp(1.0, -25), "uniform24: the smallest value");
-  check(S::uniform24(~0u) == 1.0 - std::ldexp(1.0, -25) && S::uniform24(~0u) < 1.0, "uniform24: the largest value");
+  check(P::uniform53(0u, 0u) == 0.0, "uniform53: all-zero words");
+  check(P::uniform53(31u, 63u) == 0.0, "uniform53: the dropped low bits");
+  check(P::uniform53(~0u, ~0u) == 1.0 - std::ldexp(1.0, -53) && P::uniform53(~0u, ~0u) < 1.0, "uniform53: all-one words");
+  check(P::uniform24(0u) == std::ldexp(1.0, -25) && P::uniform24(255u) == std::ldexp(1.0, -25), "uniform24: the smallest value");
+  check(P::uniform24(~0u) == 1.0 - std::ldexp(1.0, -25) && P::uniform24(~0u) < 1.0, "uniform24: the largest value");
   for (int it = 0; it < 200000; ++it)
   {
     const uint32_t a = static_cast<uint32_t>(rng.next()), b = static_cast<uint32_t>(rng.next());
     const uint64_t bits = (static_cast<uint64_t>(a >> 5) << 26) + (b >> 6);
-    const double u = S::uniform53(a, b);
+    const double u = P::uniform53(a, b);
     check(u >= 0.0 && u < 1.0 && static_cast<uint64_t>(std::ldexp(u, 53)) == bits && std::ldexp(u, 53) == std::floor(std::ldexp(u, 53)),
           "uniform53: the 53 bits");
-    const double v = S::uniform24(a);
+    const double v = P::uniform24(a);
     check(v > 0.0 && v < 1.0 && static_cast<long>(std::ldexp(v, 25)) == 2 * static_cast<long>(a >> 8) + 1, "uniform24: (2 k + 1) 2^-25");
   }
 
@@ -158,14 +122,14 @@ int main()
     for (uint64_t f : sizes)
     {
       check(S::pick(0.0, f) == 0, "pick: u = 0");
-      check(S::pick(S::uniform53(~0u, ~0u), f) == f - 1, "pick: all-one words take the last cell");
+      check(S::pick(P::uniform53(~0u, ~0u), f) == f - 1, "pick: all-one words take the last cell");
       check(S::pick(1.0, f) == f - 1, "pick: the clamp to F - 1");
-      check(S::pick(S::uniform53(~0u, ~0u), f) == pick_in_integers((1ull << 53) - 1, f), "pick: all-one words in integers");
+      check(S::pick(P::uniform53(~0u, ~0u), f) == pick_in_integers((1ull << 53) - 1, f), "pick: all-one words in integers");
       for (int it = 0; it < 20000; ++it)
       {
         const uint32_t a = static_cast<uint32_t>(rng.next()), b = static_cast<uint32_t>(rng.next());
         const uint64_t bits = (static_cast<uint64_t>(a >> 5) << 26) + (b >> 6);
-        const uint64_t k = S::pick(S::uniform53(a, b), f);
+        const uint64_t k = S::pick(P::uniform53(a, b), f);
         check(k < f && k == pick_in_integers(bits, f), "pick: against integers");
       }
       // products next to an integer: bits = ceil(j 2^53 / f) and its neighbour below
@@ -176,7 +140,7 @@ int main()
         for (uint64_t bb : {bits - 1, bits})
         {
           if (bb >= (1ull << 53)) continue;
-          const double u = static_cast<double>(bb) * S::kInv53;
+          const double u = static_cast<double>(bb) * P::kInv53;
           check(S::pick(u, f) == pick_in_integers(bb, f), "pick: next to an integer");
         }
       }
@@ -199,7 +163,7 @@ int main()
         for (int it = 0; it < 2000; ++it)
         {
           const uint32_t w = it < 7 ? designed[it] : static_cast<uint32_t>(rng.next());
-          const double u = S::uniform24(w);
+          const double u = P::uniform24(w);
           const double p = S::coordinate(g.origin, c, u, g.resolution);
           const long double exact = static_cast<long double>(g.origin) +
                                     (static_cast<long double>(c) + static_cast<long double>(u)) * static_cast<long double>(g.resolution);
@@ -211,12 +175,12 @@ int main()
         }
       }
     }
-    check(S::heading(S::uniform24(0u)) > -S::kPi && S::heading(S::uniform24(~0u)) < S::kPi, "heading: in (-pi, pi)");
+    check(S::heading(P::uniform24(0u)) > -S::kPi && S::heading(P::uniform24(~0u)) < S::kPi, "heading: in (-pi, pi)");
     check(S::heading(0.5) == 0.0, "heading: the middle");
     double last = -4.0;
     for (uint32_t k = 0; k < (1u << 24); k += 4099)
     {
-      const double t = S::heading(S::uniform24(k << 8));
+      const double t = S::heading(P::uniform24(k << 8));
       check(t > last && t >= -S::kPi && t < S::kPi, "heading: monotone, in range");
       last = t;
     }
@@ -245,65 +209,17 @@ int main()
     {
       const S::Sample s = S::sample(c.seed, c.step, c.index, table.data(), table.size(), g);
       uint32_t a[4], b[4];
-      S::philox4x32_10(c.seed, c.index, c.step, a);
-      S::philox4x32_10(c.seed, c.index, c.step + 1, b);
-      const uint32_t cell = table[S::pick(S::uniform53(a[0], a[1]), table.size())];
-      check(s.x == S::coordinate(g.origin_x, cell % W, S::uniform24(a[2]), g.resolution) &&
-              s.y == S::coordinate(g.origin_y, cell / W, S::uniform24(a[3]), g.resolution) &&
-              s.theta == S::heading(S::uniform24(b[0])) && s.inject == S::uniform53(b[1], b[2]),
+      P::philox4x32_10(c.seed, c.index, c.step, a);
+      P::philox4x32_10(c.seed, c.index, c.step + 1, b);
+      const uint32_t cell = table[S::pick(P::uniform53(a[0], a[1]), table.size())];
+      check(s.x == S::coordinate(g.origin_x, cell % W, P::uniform24(a[2]), g.resolution) &&
+              s.y == S::coordinate(g.origin_y, cell / W, P::uniform24(a[3]), g.resolution) &&
+              s.theta == S::heading(P::uniform24(b[0])) && s.inject == P::uniform53(b[1], b[2]),
             "sample: the composition of its parts");
       check(static_cast<long>((s.x - g.origin_x) / g.resolution) == static_cast<long>(cell % W) &&
               static_cast<long>((s.y - g.origin_y) / g.resolution) == static_cast<long>(cell / W),
             "sample: in its cell");
       std::printf("P %" PRIu64 " %" PRIu64 " %" PRIu64 " %a %a %a %a\n", c.seed, c.step, c.index, s.x, s.y, s.theta, s.inject);
-    }
-  }
-
-  // ---- the compaction over random maps ----
-  {
-    for (uint64_t v = 0; v < 4096; ++v)
-    {
-      const uint64_t r = rng.next();
-      check(S::popcount64(r) == static_cast<uint32_t>(__builtin_popcountll(r)), "popcount64");
-      check(S::rank_in_wave(r, static_cast<uint32_t>(v % 64)) ==
-              static_cast<uint32_t>(__builtin_popcountll(r & ((1ull << (v % 64)) - 1))), "rank_in_wave");
-    }
-    check(S::rank_in_wave(~0ull, 0) == 0 && S::rank_in_wave(~0ull, 63) == 63, "rank_in_wave: the end lanes");
-    const signed char values[] = {0, 0, 0, -1, 100, 1, -128, 127};
-    const uint32_t dims[][2] = {{1, 1}, {63, 5}, {64, 4}, {65, 9}, {255, 3}, {257, 7}, {300, 300}, {16, 16}, {1, 700}, {700, 1}};
-    for (const auto & d : dims)
-    {
-      const uint32_t W = d[0], H = d[1];
-      for (int density = 0; density < 4; ++density)
-      {
-        std::vector<signed char> map(static_cast<size_t>(W) * H);
-        for (signed char & c : map)
-        {
-          const uint64_t r = rng.next();
-          c = density == 0 ? static_cast<signed char>(0)
-                           : (density == 1 ? static_cast<signed char>(100) : values[(r >> 8) % (density == 2 ? 8 : 4)]);
-        }
-        for (int reg = 0; reg < 4; ++reg)
-        {
-          uint32_t x0 = 0, y0 = 0, w = W, h = H;
-          if (reg > 0)
-          {
-            w = 1 + static_cast<uint32_t>(rng.next() % W);
-            h = 1 + static_cast<uint32_t>(rng.next() % H);
-            x0 = reg == 1 ? 0 : (reg == 2 ? W - w : static_cast<uint32_t>(rng.next() % (W - w + 1)));
-            y0 = reg == 1 ? 0 : (reg == 2 ? H - h : static_cast<uint32_t>(rng.next() % (H - h + 1)));
-          }
-          std::vector<uint32_t> want;
-          for (uint32_t y = y0; y < y0 + h; ++y)
-          {
-            for (uint32_t x = x0; x < x0 + w; ++x)
-            {
-              if (map[static_cast<size_t>(y) * W + x] == 0) want.push_back(y * W + x);
-            }
-          }
-          check(compact_as_launched(map, W, x0, y0, w, h) == want, "compaction: the table of a plain loop");
-        }
-      }
     }
   }
 

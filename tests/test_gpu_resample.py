@@ -212,8 +212,29 @@ def random_case(n, seed):
     return p, w, min_p, max_p, kld_err, kld_z, u, sk
 
 
-@pytest.mark.parametrize("n", SIZES)
+SCAN_N = 1200                 # leaves of scan_case
+SCAN_MAX = 65536 + 256 + 1    # 258 tiles of 256 draws: two a thread of the scan, the last one ragged
+
+
+def scan_case():
+    """A stop that only the inclusive rank of a late draw decides: 1,200 particles, each in a leaf of
+    its own, so that after the first few thousand draws every draw has k = 1,200 leaves before it
+    and Mx(1,200) = 65,724 for (0.01, 2.3).  The host loop keeps 65,724 draws: beyond the scan's
+    first chunk of tiles and beyond draw 65,536, inside the last whole tile, below max."""
+    rng = np.random.default_rng(SCAN_N)
+    p = np.zeros((SCAN_N, 3))
+    p[:, 0] = (np.arange(SCAN_N) % 40 + 0.5) * KD_LEAF[0]
+    p[:, 1] = (np.arange(SCAN_N) // 40 + 0.5) * KD_LEAF[1]
+    p[:, 2] = rng.uniform(-0.1, 0.1, size=SCAN_N)
+    return p, rng.uniform(0.5, 1.0, size=SCAN_N), 3, SCAN_MAX, 0.01, 2.3, rng.random(SCAN_MAX)
+
+
+@pytest.mark.parametrize("n", SIZES + (pytest.param(None, id="scan-two-tiles-a-thread"),))
 def test_random_sets_match_the_host_loop(torch, ctx, n):
+    if n is None:          # the designed set of scan_case, not a size of random sets
+        want = check_case(torch, ctx, *scan_case(), statistics=True)
+        assert len(want) == 65724 and len(set(want.tolist())) == SCAN_N
+        return
     ended = set()
     for seed in range(SEEDS_PER_SIZE):
         p, w, min_p, max_p, kld_err, kld_z, u, sk = random_case(n, seed)

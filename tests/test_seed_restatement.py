@@ -15,7 +15,8 @@ import noise_restatement as N
 import seed_restatement as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SEED_DIR = os.path.join(ROOT, "ndt_2d_amd", "csrc", "seed")
+CSRC = os.path.join(ROOT, "ndt_2d_amd", "csrc")
+SEED_DIR = os.path.join(CSRC, "seed")
 
 ZERO = np.zeros((1, 4), dtype=np.uint64)
 ONES = np.full((1, 4), 0xffffffff, dtype=np.uint64)
@@ -141,15 +142,14 @@ def test_free_table_regions():
     assert S.free_table(grid, (3, 0, 1, 2)).tolist() == []
 
 
-def test_plain_cpp_header_in_a_program_of_its_own_and_under_the_sanitizers(tmp_path):
-    """tests/cpp/seed_fn_check.cpp over csrc/seed/ndt2d_seed_fn.h: built with the host compiler,
-    plainly and with -fsanitize=address,undefined (the runtime linked into the program), run
-    directly.  Its own checks: Philox's known answers, the uniforms and the pick against integers,
-    the coordinates against long double and the cell rule, the compaction against a plain loop.
-    Here: every printed sample equals the restatement's bit for bit."""
-    src = os.path.join(ROOT, "tests", "cpp", "seed_fn_check.cpp")
-    common = ["g++", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off", "-I", SEED_DIR, src]
-    plain, sanitized = os.path.join(str(tmp_path), "seed_check"), os.path.join(str(tmp_path), "seed_check_san")
+def _check_outputs(tmp_path, name):
+    """tests/cpp/<name> built with the host compiler, plainly and with -fsanitize=address,undefined
+    (the runtime linked into the program), and run directly: both end with "ok", write nothing to
+    stderr and print the same."""
+    src = os.path.join(ROOT, "tests", "cpp", name)
+    common = ["g++", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off", "-I", SEED_DIR, "-I", CSRC, src]
+    stem = os.path.join(str(tmp_path), os.path.splitext(name)[0])
+    plain, sanitized = stem, stem + "_san"
     subprocess.check_call(common + ["-O2", "-o", plain])
     subprocess.check_call(common + ["-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-o", sanitized])
     outputs = []
@@ -159,6 +159,22 @@ def test_plain_cpp_header_in_a_program_of_its_own_and_under_the_sanitizers(tmp_p
         assert done.stdout.splitlines()[-1] == "ok"
         outputs.append(done.stdout)
     assert outputs[0] == outputs[1]
+    return outputs
+
+
+def test_the_compaction_in_a_program_of_its_own_and_under_the_sanitizers(tmp_path):
+    """tests/cpp/compact_fn_check.cpp over csrc/particles/ndt2d_compact_fn.h: the ranks of a lane
+    against the builtin popcount, the scan's chunks (they tile [0, n_tiles) up to 2^32 - 1), the
+    compaction against a plain loop."""
+    _check_outputs(tmp_path, "compact_fn_check.cpp")
+
+
+def test_plain_cpp_header_in_a_program_of_its_own_and_under_the_sanitizers(tmp_path):
+    """tests/cpp/seed_fn_check.cpp over csrc/seed/ndt2d_seed_fn.h: built with the host compiler,
+    plainly and with -fsanitize=address,undefined (the runtime linked into the program), run
+    directly.  Its own checks: Philox's known answers, the uniforms and the pick against integers,
+    the coordinates against long double and the cell rule.  Here: every printed sample equals the restatement's bit for bit."""
+    outputs = _check_outputs(tmp_path, "seed_fn_check.cpp")
     rows = [line.split() for line in outputs[0].splitlines() if line.startswith("P ")]
     assert len(rows) == 32
     width, height = 37, 23
