@@ -38,7 +38,7 @@ m.synchronize()
 h = hist.cpu().numpy()
 names = ["items", "chunks_pretested", "beams_in_lookup_groups", "groups_with_a_live_lane", "beams_with_a_live_lane",
          "exact_evaluations", "evaluations_by_reference_index", "evaluations_with_exp", "skip_refreshes",
-         "items_reduced", "single_beams", "live_beams_near_possible"]
+         "items_reduced", "single_beams", "live_beams_near_possible", "chunks_refined_by_level", "level_retakes"]
 items = float(h[200])   # (theta, tile) work items: the edge of the lattice may be cut into strip tiles
 out = {"what": "path counts of one search, wave-level events (experiments/lane_paths.py, -DNDT2D_LANE_PATHS build)",
        "cfg": cfg, "variant": m.last_variant(), "n_theta_run": n_th_run, "n_lin": n_lin, "beams": n_b,

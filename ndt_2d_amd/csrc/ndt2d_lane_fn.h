@@ -9,6 +9,7 @@
 
 #include "ndt2d_device_fn.h"
 #include "ndt2d_near_bits.h"
+#include "ndt2d_pretest_level.h"
 
 namespace ndt2d
 {
@@ -405,6 +406,8 @@ __device__ double * g_lane_hist = nullptr;   // set by the kernel from MatchArgs
 //   [207] evaluations that needed exp()   [208] skip-state refreshes   [209] items reduced (some sum != 0)
 //   [210] single beams through the U = 1 form
 //   [211] beams with a live lane whose near-possible bit is set (the per-lane near test runs)
+//   [212] 64-beam chunks whose pre-test was refined by the wave's lowest skip level
+//   [213] re-takes of that level (the DPP min-reduction)
 #ifdef NDT2D_LANE_PATHS
 #define NDT2D_PATH(slot, amount)                                                              \
   do {                                                                                        \
@@ -468,7 +471,10 @@ __device__ __forceinline__ uint2 lds_two_dwords_at(uint32_t address)
 // the beam whatever its threshold.  Rows beyond `span` are not read; the columns beyond
 // it are masked.  (Reads past the last map row, possible only for rows the candidates
 // cannot reach, land in the block's own LDS behind the map or return 0.)
-__device__ __forceinline__ bool patch_can_score(double s, int32_t span)
+// patch_box_word: the OR of the box's rows, its level bits of columns 0 .. span; non-zero is
+// the test above, and pretest_level_bound() of it bounds the box's highest level for the
+// test against the wave's lowest skip level (ndt2d_pretest_level.h).
+__device__ __forceinline__ uint32_t patch_box_word(double s, int32_t span)
 {
   const uint32_t lo = static_cast<uint32_t>(__double2loint(s));
   const uint32_t hi = static_cast<uint32_t>(__double2hiint(s));
@@ -486,13 +492,16 @@ __device__ __forceinline__ bool patch_can_score(double s, int32_t span)
     }
   }
   // levels live in bits 2..7 of a byte; keep columns 0 .. span
-  const uint32_t columns = span >= 3 ? 0xfcfcfcfcu : (0xfcfcfcfcu >> (8 * (3 - span)));
-  return (any & columns) != 0u;
+  const uint32_t columns = span >= 3 ? kLevelColumns : (kLevelColumns >> (8 * (3 - span)));
+  return any & columns;
 }
+
+__device__ __forceinline__ bool patch_can_score(double s, int32_t span) { return patch_box_word(s, span) != 0u; }
 
 // The same for a strip tile (lane_tiling), whose candidates lie within span_x / span_y sub-cells
 // (each at most kMaxStripSpan) of the corner: up to eight rows of eight bytes, three dwords a row.
-__device__ __forceinline__ bool strip_can_score(double s, int32_t span_x, int32_t span_y)
+// The two words of columns 0..3 and 4..7 come back ORed into one: column c stands for c and c + 4.
+__device__ __forceinline__ uint32_t strip_box_word(double s, int32_t span_x, int32_t span_y)
 {
   typedef const __attribute__((address_space(3), aligned(4))) uint32_t * lds_u32_ptr;
   const uint32_t lo = static_cast<uint32_t>(__double2loint(s));
@@ -514,7 +523,26 @@ __device__ __forceinline__ bool strip_can_score(double s, int32_t span_x, int32_
   }
   // levels live in bits 2..7 of a byte; keep columns 0 .. span_x
   const uint64_t columns = 0xfcfcfcfcfcfcfcfcull >> (8 * (kMaxStripSpan - span_x));
-  return ((any_lo & static_cast<uint32_t>(columns)) | (any_hi & static_cast<uint32_t>(columns >> 32))) != 0u;
+  return (any_lo & static_cast<uint32_t>(columns)) | (any_hi & static_cast<uint32_t>(columns >> 32));
+}
+
+__device__ __forceinline__ bool strip_can_score(double s, int32_t span_x, int32_t span_y)
+{
+  return strip_box_word(s, span_x, span_y) != 0u;
+}
+
+// The least skip level of the wave's lanes (all 64 active), wave-uniform: the DPP steps of
+// wave_sum_to_last_lane() with a minimum, complete in lane 63.
+__device__ __forceinline__ uint32_t wave_min_skip_level(uint32_t level)
+{
+  int v = static_cast<int>(level);   // levels are small and non-negative
+  v = min(v, __builtin_amdgcn_update_dpp(v, v, kDppQuadXor1, 0xf, 0xf, false));
+  v = min(v, __builtin_amdgcn_update_dpp(v, v, kDppQuadXor2, 0xf, 0xf, false));
+  v = min(v, __builtin_amdgcn_update_dpp(v, v, kDppRowHalfMirror, 0xf, 0xf, false));
+  v = min(v, __builtin_amdgcn_update_dpp(v, v, kDppRowMirror, 0xf, 0xf, false));
+  v = min(v, __builtin_amdgcn_update_dpp(v, v, kDppRowBcast15, 0xa, 0xf, false));
+  v = min(v, __builtin_amdgcn_update_dpp(v, v, kDppRowBcast31, 0xc, 0xf, false));
+  return static_cast<uint32_t>(__builtin_amdgcn_readlane(v, kWave - 1));
 }
 
 // Cell::score's exponent against packed record idx of the LDS copy, addressed with
@@ -563,8 +591,10 @@ __device__ __forceinline__ SkipState skip_state(double sum, int32_t no_skip)
 // near_possible: bit u says that beam u may have a lane near a cell boundary (near_bits() of
 // the large search's table, a wave-uniform value); a beam whose bit is clear has none, and its
 // per-lane near test is not run.  Callers without such a table pass all ones.
+// Returns whether the group added a term to some lane's sum (the skip state was refreshed): a
+// wave-uniform flag.
 template <int U, bool POW2, bool LDS_RECORDS, bool SCALAR_ROWS = true, bool COMPACT = false>
-__device__ __forceinline__ void lane_beams(const GridDesc & g, const LaneCtx & c,
+__device__ __forceinline__ bool lane_beams(const GridDesc & g, const LaneCtx & c,
                                            const double4 (&o)[U], double dx, double dy,
                                            double dxy, double & sum, SkipState & skip,
                                            int32_t no_skip, uint32_t near_possible = ~0u)
@@ -584,10 +614,10 @@ __device__ __forceinline__ void lane_beams(const GridDesc & g, const LaneCtx & c
     top = max(top, m[u]);
   }
   NDT2D_PATH(U == 1 ? 210 : 202, U);
+  bool added = false;
   if (wave_any(top >= skip_level))
   {
     NDT2D_PATH(203, 1);
-    bool added = false;
     // have the beams' end points on their way before the first exact evaluation needs
     // them (left to itself the compiler loads each pair inside its own branch)
     if (SCALAR_ROWS)
@@ -693,6 +723,7 @@ __device__ __forceinline__ void lane_beams(const GridDesc & g, const LaneCtx & c
     if (added) NDT2D_PATH(208, 1);
     if (added) skip = skip_state(sum, no_skip);
   }
+  return added;
 }
 
 // Window of grid cells [lo, hi] reachable along one axis, clipped to the grid.

@@ -33,7 +33,11 @@
 // within a few sub-cells of the patch's first lane, and if the 4 x 4 box of map bytes
 // there holds level 0 only, every lane would skip the beam (patch_can_score, four LDS
 // reads for 64 beams).  Groups of eight consecutive beams none of which passes are
-// stepped over by a scalar test -- four beams out of five at cfg-2.
+// stepped over by a scalar test -- four beams out of five at cfg-2.  Once every lane of the wave
+// has scored, the flagged beams are tested again, against the least of the 64 lanes' skip levels
+// (taken at a chunk start by one DPP reduction, and again only after a group added a term): the OR
+// of the box's bytes bounds its highest level, and a beam whose bound is below that level has no
+// live lane in the chunk (ndt2d_pretest_level.h) -- three look-up groups in ten at cfg-2.
 //
 // The map is padded by more cells than any offset reaches and beams are
 // pre-clamped, so no per-lane range check exists.  The map is kept at up to
@@ -409,6 +413,8 @@ __device__ __forceinline__ void match_lane_body(
 
     double sum = 0.0;
     SkipState skip = skip_state(0.0, geo.no_skip);
+    // the least skip level of the wave's lanes as last taken (see the pre-test below): no lane has scored
+    uint32_t level_min = kLowestSkipLevel;
     NDT2D_PATH(200, 1);
     // Beams go by in chunks of 64.  First the wave asks, one beam per lane, whether the
     // patch as a whole can reach a distribution with that beam (patch_can_score: four LDS
@@ -440,20 +446,40 @@ __device__ __forceinline__ void match_lane_body(
         {
           k = row[min(b0 + lane, a.n_beams - 1u)].z;
         }
+        uint32_t box_word;
         if (strip_tile)
         {
           // h < 8: the tile's long side lies along x
           const bool along_x = h_log2 < 3u;
-          can_score = __builtin_amdgcn_ballot_w64(
-            strip_can_score(k + dxy_corner, along_x ? geo.strip_span_long : geo.strip_span_short,
-                            along_x ? geo.strip_span_short : geo.strip_span_long));
+          box_word = strip_box_word(k + dxy_corner, along_x ? geo.strip_span_long : geo.strip_span_short,
+                                    along_x ? geo.strip_span_short : geo.strip_span_long);
         }
         else
         {
-          can_score = __builtin_amdgcn_ballot_w64(patch_can_score(k + dxy_corner, geo.box_span));
+          box_word = patch_box_word(k + dxy_corner, geo.box_span);
           if (NEAR) near_chunk = __builtin_amdgcn_ballot_w64((near_word & tile_near) != 0ull);
         }
+        can_score = __builtin_amdgcn_ballot_w64(box_word != 0u);
         NDT2D_PATH(201, 1);
+        // The flagged beams again, against the least skip level of the wave's lanes: a beam whose
+        // box holds no byte of that level has no live lane in any group of this chunk (levels
+        // only rise), and a group none of whose beams stays flagged is not looked up.  Only
+        // where that can say more than the test above: something is flagged and every lane has
+        // scored (level_min: bits 2..7 the level, taken at a chunk start; bit 0: a group has
+        // added a term since -- the one value this keeps across the group loop).
+        if (can_score != 0ull && level_min != kLowestSkipLevel)
+        {
+          if ((level_min & 1u) != 0u)
+          {
+            NDT2D_PATH(213, 1);
+            level_min = wave_min_skip_level(skip.skip_level);
+          }
+          if (level_min != kLowestSkipLevel)
+          {
+            NDT2D_PATH(212, 1);
+            can_score = __builtin_amdgcn_ballot_w64(pretest_level_passes(pretest_level_bound(box_word), level_min));
+          }
+        }
       }
 #ifdef NDT2D_LANE_TRACE
       trace_flagged += static_cast<uint32_t>(__popcll(can_score));
@@ -471,16 +497,22 @@ __device__ __forceinline__ void match_lane_body(
         // unflagged groups or reducing an item's records are not: issue priority while the
         // group is evaluated (cfg-2: - 3 %).
         __builtin_amdgcn_s_setprio(3);
-        lane_beams<kUnroll, POW2, LDS_RECORDS, true, COMPACT>(g, c, o, dx, dy, dxy, sum, skip, geo.no_skip,
-                                                              NEAR ? static_cast<uint32_t>(near_chunk) : ~0u);
+        if (lane_beams<kUnroll, POW2, LDS_RECORDS, true, COMPACT>(g, c, o, dx, dy, dxy, sum, skip, geo.no_skip,
+                                                                  NEAR ? static_cast<uint32_t>(near_chunk) : ~0u))
+        {
+          level_min |= 1u;
+        }
         __builtin_amdgcn_s_setprio(0);
       }
       for (; b < chunk_end; ++b, can_score >>= 1, near_chunk >>= 1)
       {
         if ((can_score & 1ull) == 0ull) continue;
         const double4 one[1] = {row[b]};
-        lane_beams<1, POW2, LDS_RECORDS, true, COMPACT>(g, c, one, dx, dy, dxy, sum, skip, geo.no_skip,
-                                                        NEAR ? static_cast<uint32_t>(near_chunk) : ~0u);
+        if (lane_beams<1, POW2, LDS_RECORDS, true, COMPACT>(g, c, one, dx, dy, dxy, sum, skip, geo.no_skip,
+                                                            NEAR ? static_cast<uint32_t>(near_chunk) : ~0u))
+        {
+          level_min |= 1u;
+        }
       }
     }
 
