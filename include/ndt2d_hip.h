@@ -1720,6 +1720,71 @@ int ndt2d_seed_inject_launch(ndt2d_seeder * seeder, double * d_poses_xyt, size_t
 int ndt2d_seed_set_timing(ndt2d_seeder * seeder, int enabled);
 int ndt2d_seed_last_ms(ndt2d_seeder * seeder, float * table_ms, float * sample_ms);
 
+/* ---- Clearance map: the exact distance of every cell to the nearest wall ----
+ *
+ * A robot's centre cannot be nearer to a wall than the robot's radius, so a seeder that keeps off
+ * walls, and a planner that wants an inflated map, both need the distance from every cell to the
+ * nearest obstacle.  An ndt2d_clearance is an object of its own beside the context, like the
+ * seeder: it launches on the context's current stream and must be destroyed before ndt2d_destroy(h).
+ *
+ * The quantity.  For an int8 map [height][width] a cell is an OBSTACLE when its byte is neither 0
+ * nor -1 (100 and every stray value); with unknown_is_obstacle != 0, when its byte is not 0.
+ * d2[y][x] (uint32) is the exact squared Euclidean distance in cells, centre to centre, to the
+ * nearest obstacle cell; an obstacle cell has d2 = 0.  Outside the map there is nothing: the border
+ * is no obstacle.  A map without any obstacle has NDT2D_CLEARANCE_FAR everywhere.  With a cap
+ * max_cells = R > 0 every cell whose exact d2 > R * R is reported as NDT2D_CLEARANCE_FAR and every
+ * other cell is exact; R = 0 is no cap.  width and height are at most 32,768 each, so d2 <=
+ * 2 * 32767^2 < 2^31.  Integer arithmetic throughout, no atomics: two calls give the same bits.
+ *
+ * Metres enter in one place, on the host: ndt2d_clearance_min_d2 gives *min_d2 = ceil(q * q) with
+ * q = clearance_m / resolution, one double divide (0.25 / 0.05 -> 25, 0.3 / 0.05 -> 36,
+ * 0.3 / 0.1 -> 9).  NDT2D_ERR_INVALID: a clearance that is negative or not finite, a resolution
+ * that is not finite and positive, a negative max_cells, a min_d2 above 2^31, or a cap R > 0 with
+ * min_d2 > R * R (the capped transform could not tell such cells apart).  A cell HAS THE CLEARANCE
+ * exactly when d2 >= min_d2, so NDT2D_CLEARANCE_FAR always has it.  A caller who wants an integer
+ * radius r passes min_d2 = r * r itself.
+ *
+ * ndt2d_clearance_compute takes a HOST map, ndt2d_clearance_compute_device a DEVICE one
+ * (ndt2d_occmap_device_map: nothing is uploaded).  The transform always covers the whole map.
+ * ndt2d_clearance_mask makes the object's own copy of that map in which every free cell (byte 0)
+ * with d2 < min_d2 is byte 99 (the "inscribed" value of the nav2 costmap convention) and every
+ * other byte is unchanged: given to ndt2d_seed_set_map_device, whose rule "byte exactly 0" drops
+ * the 99s, it seeds only cells that have the clearance.  compute* and mask return when complete,
+ * so the source map may change afterwards.  *d_d2 (ndt2d_clearance_device) and *d_masked_map are
+ * the object's own, read-only, valid until the next compute*, mask or destroy.
+ * ndt2d_clearance_read / _read_mask copy a rectangle to HOST out[h][out_row_stride] (in elements,
+ * >= w), as ndt2d_occmap_read does.
+ *
+ * Refused before anything is allocated or launched, NDT2D_ERR_INVALID with a message naming the
+ * item, the object (and its earlier result) left as it was: NULL arguments, a zero width or
+ * height, a side above 32,768, a negative max_cells, a rectangle that leaves the map.  read,
+ * device and mask before the first compute, and read_mask before a mask of the last compute, are
+ * NDT2D_ERR_STATE.  ndt2d_clearance_set_timing / _last_ms: HIP events round the four launches of
+ * the last compute and round the last mask launch (0 for the one not timed; neither:
+ * NDT2D_ERR_STATE). */
+#define NDT2D_CLEARANCE_FAR 0xFFFFFFFFu
+typedef struct ndt2d_clearance ndt2d_clearance;
+int ndt2d_clearance_create(ndt2d_handle h, ndt2d_clearance ** out);
+int ndt2d_clearance_destroy(ndt2d_clearance * clearance);
+const char * ndt2d_clearance_last_error(ndt2d_clearance * clearance);
+int ndt2d_clearance_compute(ndt2d_clearance * clearance, const signed char * map, uint32_t width,
+                            uint32_t height, int unknown_is_obstacle, int64_t max_cells);
+int ndt2d_clearance_compute_device(ndt2d_clearance * clearance, const signed char * d_map,
+                                   uint32_t width, uint32_t height, int unknown_is_obstacle,
+                                   int64_t max_cells);
+int ndt2d_clearance_min_d2(double clearance_m, double resolution, int64_t max_cells,
+                           uint32_t * min_d2);
+int ndt2d_clearance_read(ndt2d_clearance * clearance, uint32_t x0, uint32_t y0, uint32_t w,
+                         uint32_t h, uint32_t * out, size_t out_row_stride);
+int ndt2d_clearance_device(ndt2d_clearance * clearance, const uint32_t ** d_d2, uint32_t * width,
+                           uint32_t * height);
+int ndt2d_clearance_mask(ndt2d_clearance * clearance, uint32_t min_d2,
+                         const signed char ** d_masked_map);
+int ndt2d_clearance_read_mask(ndt2d_clearance * clearance, uint32_t x0, uint32_t y0, uint32_t w,
+                              uint32_t h, signed char * out, size_t out_row_stride);
+int ndt2d_clearance_set_timing(ndt2d_clearance * clearance, int enabled);
+int ndt2d_clearance_last_ms(ndt2d_clearance * clearance, float * transform_ms, float * mask_ms);
+
 /* ---- Pose clusters: the pose of the heaviest cluster of a particle set ----
  *
  * While a globally seeded set settles, its belief has several modes; the mean over all particles

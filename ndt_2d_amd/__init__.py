@@ -10,6 +10,7 @@ from .occupancy_map import OccupancyMap  # noqa: F401
 from .particle_filter import MotionModel, ParticleFilter, RecoveryAverages  # noqa: F401
 from .pose_graph import PoseGraph, closure_constraints, closure_distance, make_constraint, relative_covariance  # noqa: F401
 from .seeder import Seeder  # noqa: F401
+from .clearance import ClearanceMap  # noqa: F401
 from .clusters import Clusterer, PoseCluster  # noqa: F401
 from .wide_search import WideSearch  # noqa: F401
 from .scan_matcher import (DEFAULT_PARAMS, Resampler, ScanMatcherNDT, close_loops, heading_fan,  # noqa: F401
@@ -20,4 +21,4 @@ __all__ = ["ScanMatcherNDT", "Resampler", "ParticleFilter", "MotionModel", "pf_m
            "search_offsets", "host_build_grid", "DEFAULT_PARAMS", "Ndt2dError", "LIB_PATH", "OccupancyMap",
            "close_loops", "loop_closure_window", "relocalize", "heading_fan", "track_scans", "refine_matches", "refine_covariance", "explained_mask",
            "PoseGraph", "make_constraint", "closure_constraints", "relative_covariance", "closure_distance",
-           "Seeder", "RecoveryAverages", "Clusterer", "PoseCluster"]
+           "Seeder", "ClearanceMap", "RecoveryAverages", "Clusterer", "PoseCluster"]

@@ -102,6 +102,7 @@ class ClusterRecord(C.Structure):
 
 
 CLUSTER_MAX_RECORDS = 16
+CLEARANCE_FAR = 0xFFFFFFFF      # NDT2D_CLEARANCE_FAR
 
 
 class World(C.Structure):
@@ -325,6 +326,18 @@ SIGNATURES = {
     "ndt2d_seed_inject_launch": (C.c_int, [_vp, _vp, _sz, _d, _u64, _u64, _u64, _vp]),
     "ndt2d_seed_set_timing": (C.c_int, [_vp, C.c_int]),
     "ndt2d_seed_last_ms": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "ndt2d_clearance_create": (C.c_int, [_vp, C.POINTER(_vp)]),
+    "ndt2d_clearance_destroy": (C.c_int, [_vp]),
+    "ndt2d_clearance_last_error": (C.c_char_p, [_vp]),
+    "ndt2d_clearance_compute": (C.c_int, [_vp, _vp, _u32, _u32, C.c_int, C.c_int64]),
+    "ndt2d_clearance_compute_device": (C.c_int, [_vp, _vp, _u32, _u32, C.c_int, C.c_int64]),
+    "ndt2d_clearance_min_d2": (C.c_int, [_d, _d, C.c_int64, C.POINTER(_u32)]),
+    "ndt2d_clearance_read": (C.c_int, [_vp, _u32, _u32, _u32, _u32, _vp, _sz]),
+    "ndt2d_clearance_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_u32), C.POINTER(_u32)]),
+    "ndt2d_clearance_mask": (C.c_int, [_vp, _u32, C.POINTER(_vp)]),
+    "ndt2d_clearance_read_mask": (C.c_int, [_vp, _u32, _u32, _u32, _u32, _vp, _sz]),
+    "ndt2d_clearance_set_timing": (C.c_int, [_vp, C.c_int]),
+    "ndt2d_clearance_last_ms": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "ndt2d_cluster_create": (C.c_int, [_vp, _sz, C.POINTER(_vp)]),
     "ndt2d_cluster_destroy": (C.c_int, [_vp]),
     "ndt2d_cluster_last_error": (C.c_char_p, [_vp]),

@@ -251,30 +251,33 @@ class ParticleFilter:
 
     # -- global localisation (not in the reference) -----------------------------------------
 
-    def _seeder_for(self, map_source, region):
+    def _seeder_for(self, map_source, region, min_clearance=0.0, unknown_is_obstacle=False):
         """The filter's Seeder with its table made from `map_source`."""
         from .occupancy_map import OccupancyMap
         from .seeder import Seeder
         if self._seeder is None:
             self._seeder = Seeder(self._matcher)
         if isinstance(map_source, OccupancyMap):
-            self._seeder.set_occupancy_map(map_source, region)
+            self._seeder.set_occupancy_map(map_source, region, min_clearance, unknown_is_obstacle)
         else:
             grid, origin_x, origin_y, resolution = map_source
-            self._seeder.set_map(grid, origin_x, origin_y, resolution, region)
+            self._seeder.set_map(grid, origin_x, origin_y, resolution, region, min_clearance, unknown_is_obstacle)
         return self._seeder
 
-    def init_global(self, map_source, n=None, region=None):
+    def init_global(self, map_source, n=None, region=None, min_clearance=0.0, unknown_is_obstacle=False):
         """The set becomes `n` (default max_particles) particles uniform over the free cells (byte
         0) of the map, heading uniform in (-pi, pi), weights 1/n.  map_source: an OccupancyMap (its
         resident map, nothing uploaded) or (int8 array [h, w], origin_x, origin_y, resolution);
-        region = (x0, y0, w, h) in cells restricts the cells.  Consumes two steps of the counter.
-        The map is kept as this filter's free table for inject()."""
+        region = (x0, y0, w, h) in cells restricts the cells.  min_clearance > 0 (metres) keeps only
+        the free cells at least that far from every obstacle of the whole map (the robot's radius:
+        include/ndt2d_hip.h, "Clearance map"); unknown_is_obstacle counts -1 cells as obstacles too.
+        Consumes two steps of the counter.  The table is kept as this filter's free table for
+        inject(), which so inherits the clearance."""
         torch = self._torch
         n = self.max_particles if n is None else int(n)
         if n <= 0:
             raise ValueError("init_global needs at least one particle")
-        seeder = self._seeder_for(map_source, region)
+        seeder = self._seeder_for(map_source, region, min_clearance, unknown_is_obstacle)
         step = self._next_step()
         self._next_step()
         with torch.cuda.stream(self._stream):

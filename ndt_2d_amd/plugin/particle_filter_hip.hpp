@@ -29,10 +29,12 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <memory>
 #include <random>
 #include <string>
 #include <vector>
 
+#include "clearance_hip.hpp"
 #include "ndt2d_hip.h"
 
 namespace ndt_2d_hip
@@ -74,6 +76,7 @@ public:
   ~ParticleFilterHip()
   {
     if (seeder_ != nullptr) ndt2d_seed_destroy(seeder_);
+    clearance_.reset();
     if (clusterer_ != nullptr) ndt2d_cluster_destroy(clusterer_);
     ndt2d_device_free(dev_, d_count_);
     ndt2d_device_free(dev_, d_particles_);
@@ -160,21 +163,36 @@ public:
   // becomes n particles (0 = max_particles) uniform over the free cells (byte 0) of a HOST
   // row-major int8 map, heading uniform, weights 1 / n.  region4 = {x0, y0, w, h} in cells or
   // nullptr.  Consumes two steps of the counter; the map stays this filter's free table for inject.
+  // min_clearance > 0 (metres, the robot's radius) keeps only the free cells at least that far from
+  // every obstacle of the whole map ("Clearance map": bytes that are neither 0 nor -1); 0.0 is the
+  // call without it.
   void initGlobal(const signed char * map, std::uint32_t width, std::uint32_t height, double origin_x,
                   double origin_y, double resolution, std::size_t n = 0,
-                  const std::uint32_t * region4 = nullptr)
+                  const std::uint32_t * region4 = nullptr, double min_clearance = 0.0)
   {
     if (!seeder()) return;
-    seedCheck(ndt2d_seed_set_map(seeder_, map, width, height, origin_x, origin_y, resolution, region4));
+    if (min_clearance != 0.0)
+    {
+      const signed char * d_masked = cleared(map, false, width, height, resolution, min_clearance);
+      if (!ok_) return;
+      seedCheck(ndt2d_seed_set_map_device(seeder_, d_masked, width, height, origin_x, origin_y, resolution, region4));
+    }
+    else
+    {
+      seedCheck(ndt2d_seed_set_map(seeder_, map, width, height, origin_x, origin_y, resolution, region4));
+    }
     seedFrom(n);
   }
   // The same from the resident map of an ndt2d_occupancy_map's last update: nothing is uploaded.
-  void initGlobal(ndt2d_occupancy_map * resident, std::size_t n = 0, const std::uint32_t * region4 = nullptr)
+  void initGlobal(ndt2d_occupancy_map * resident, std::size_t n = 0, const std::uint32_t * region4 = nullptr,
+                  double min_clearance = 0.0)
   {
     if (!seeder()) return;
     const signed char * d_map = nullptr;
     ndt2d_occupancy_info info;
     check(ndt2d_occmap_device_map(resident, &d_map, &info));
+    if (!ok_) return;
+    if (min_clearance != 0.0) d_map = cleared(d_map, true, info.width, info.height, info.resolution, min_clearance);
     if (!ok_) return;
     seedCheck(ndt2d_seed_set_map_device(seeder_, d_map, info.width, info.height, info.origin_x, info.origin_y,
                                         info.resolution, region4));
@@ -287,6 +305,35 @@ private:
     return ok_;
   }
 
+  // This filter's masked DEVICE copy of a map: the free cells nearer than min_clearance to an obstacle
+  // are 99 in it.  The transform is capped at the radius the clearance needs, so it costs at most that
+  // many steps a cell however open the map is.
+  const signed char * cleared(const signed char * map, bool on_device, std::uint32_t width, std::uint32_t height,
+                              double resolution, double min_clearance)
+  {
+    std::uint32_t min_d2 = 0;
+    if (!ClearanceMapHip::minD2(min_clearance, resolution, 0, &min_d2))
+    {
+      ok_ = false;
+      error_ = "initGlobal: min_clearance and the resolution do not give a clearance in cells";
+      return nullptr;
+    }
+    const std::int64_t cap = static_cast<std::int64_t>(std::ceil(min_clearance / resolution));   // cap^2 >= min_d2
+    if (!clearance_) clearance_.reset(new ClearanceMapHip(dev_));
+    const signed char * d_masked = nullptr;
+    if (clearance_->valid() && (on_device ? clearance_->computeDevice(map, width, height, false, cap)
+                                          : clearance_->compute(map, width, height, false, cap)))
+    {
+      d_masked = clearance_->mask(min_d2);
+    }
+    if (d_masked == nullptr && ok_)
+    {
+      ok_ = false;
+      error_ = clearance_->last_error();
+    }
+    return d_masked;
+  }
+
   // created on first use, for the largest set this filter can hold
   bool clusterer()
   {
@@ -387,6 +434,7 @@ private:
   std::mt19937 gen_;
   double * d_particles_ = nullptr, * d_weights_ = nullptr, * d_stats_ = nullptr;
   ndt2d_seeder * seeder_ = nullptr;
+  std::unique_ptr<ClearanceMapHip> clearance_;   // made by the first initGlobal with a clearance
   ndt2d_clusterer * clusterer_ = nullptr;
   std::size_t cluster_capacity_ = 0;
   ndt2d_cluster_header cluster_header_ = ndt2d_cluster_header();

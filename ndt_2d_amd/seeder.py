@@ -39,8 +39,12 @@ class Seeder:
         device._seeders.add(self)     # closed before the context is destroyed
         self.width = self.height = 0
         self.origin_x = self.origin_y = self.resolution = 0.0
+        self._clearance = None        # a ClearanceMap, made by the first call with min_clearance > 0
 
     def close(self):
+        if getattr(self, "_clearance", None) is not None:
+            self._clearance.close()
+            self._clearance = None
         if getattr(self, "_s", None):
             self._L.ndt2d_seed_destroy(self._s)
             self._s = None
@@ -61,9 +65,31 @@ class Seeder:
         self.width, self.height = int(width), int(height)
         self.origin_x, self.origin_y, self.resolution = float(origin_x), float(origin_y), float(resolution)
 
-    def set_map(self, grid, origin_x, origin_y, resolution, region=None):
+    def _masked(self, compute, resolution, min_clearance, unknown_is_obstacle):
+        """The DEVICE map of this seeder's ClearanceMap in which the free cells nearer than
+        min_clearance (metres) to an obstacle are no longer byte 0.  compute(clearance_map,
+        unknown_is_obstacle, max_cells) runs the transform, capped at the radius the clearance needs:
+        the transform then costs at most that many steps a cell, however open the map is."""
+        from .clearance import ClearanceMap, min_d2_of
+        min_d2 = min_d2_of(min_clearance, resolution)                  # (refuses what is not a clearance)
+        cap = int(np.ceil(np.float64(min_clearance) / np.float64(resolution)))   # cap^2 >= min_d2
+        if self._clearance is None:
+            self._clearance = ClearanceMap(self._device)
+        compute(self._clearance, unknown_is_obstacle, cap)
+        return self._clearance.mask(min_d2=min_d2)
+
+    def set_map(self, grid, origin_x, origin_y, resolution, region=None, min_clearance=0.0,
+                unknown_is_obstacle=False):
         """grid: HOST int8 [height, width], as OccupancyMap.getMsg()["data"]; region = (x0, y0, w, h)
-        in cells or None.  Returns the number of free cells."""
+        in cells or None.  Returns the number of free cells.  With min_clearance > 0 (metres) only
+        the free cells at least that far from every obstacle of the WHOLE map are kept (obstacles:
+        bytes that are neither 0 nor -1, or with unknown_is_obstacle every byte but 0); with 0.0 the
+        call is what it was without the argument."""
+        if min_clearance != 0.0:
+            ptr = self._masked(lambda c, unknown, cap: c.compute(grid, unknown, cap), resolution, min_clearance,
+                               unknown_is_obstacle)
+            h, w = np.shape(grid)
+            return self.set_map_device(ptr, w, h, origin_x, origin_y, resolution, region)
         g = np.ascontiguousarray(grid, dtype=np.int8)
         if g.ndim != 2 or not np.array_equal(g, grid):     # (a value that does not fit int8 could wrap to 0)
             raise ValueError("the map must be a 2-D array [height, width] of int8 values")
@@ -82,9 +108,14 @@ class Seeder:
         self._took(width, height, origin_x, origin_y, resolution)
         return self.free_count()
 
-    def set_occupancy_map(self, occupancy_map, region=None):
-        """The resident map of an OccupancyMap's last getMsg: nothing is uploaded."""
+    def set_occupancy_map(self, occupancy_map, region=None, min_clearance=0.0, unknown_is_obstacle=False):
+        """The resident map of an OccupancyMap's last getMsg: nothing is uploaded.  min_clearance as
+        in set_map."""
         ptr, info = occupancy_map.device_map()
+        if min_clearance != 0.0:
+            source = ptr
+            ptr = self._masked(lambda c, unknown, cap: c.compute_device(source, info.width, info.height, unknown, cap),
+                               info.resolution, min_clearance, unknown_is_obstacle)
         return self.set_map_device(ptr, info.width, info.height, info.origin_x, info.origin_y, info.resolution,
                                    region)
 
