@@ -26,8 +26,8 @@ import tempfile
 
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNELS = [
-    ("ndt2d_match_lane.hip", "match_lane_compact_kernel", r"25match_lane_compact_kernelILb1ELb1EEE"),
-    ("ndt2d_match_lane.hip", "match_lane_compact_parts_kernel", r"31match_lane_compact_parts_kernelILb1EEE"),
+    ("ndt2d_match_lane.hip", "match_lane_compact_kernel", r"25match_lane_compact_kernelILb1ELb1ELj1EEE"),
+    ("ndt2d_match_lane.hip", "match_lane_compact_parts_kernel", r"31match_lane_compact_parts_kernelILb1ELj1EEE"),
     ("ndt2d_match_small.hip", "match_small_kernel", r"18match_small_kernelILb1ELb1ELb1EEE"),
     ("ndt2d_poses_compact.hip", "score_poses_compact_kernel", r"26score_poses_compact_kernelILi256ELb1ELb1ELb0EEE"),
 ]

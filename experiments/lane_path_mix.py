@@ -35,16 +35,18 @@ P = {
     "live_beam": [("v_and_b32", 1), ("v_cmp_le_u32 vcc", 1)],
     # ... whose near-possible bit is set (the table's near_bits word): near-boundary tests (x, y)
     "near_test": [("v_cmp_gt_u16 vcc", 2), ("v_perm_b32", 1)],
-    # exact evaluation, interior of a cell: points_inner, look-up cell -> rank -> record, Cell::score's exponent, test
+    # exact evaluation, interior of a cell: points_inner, the look-up's cell bytes -> entry of the window table
+    # (csrc/ndt2d_address_table.h; at cfg-2 its entries are ranks in a byte) -> rank -> record, Cell::score's
+    # exponent, test
     "exact_evaluation": [("v_add_f64", 2),
-                         ("v_lshrrev_b32_sdwa", 2), ("v_mul_u32_u24", 1), ("v_add3_u32", 1), ("v_cndmask_b32 sgpr", 1),
-                         ("v_lshl_add_u32", 1), ("v_mad_u32_u24", 1),
+                         ("v_lshrrev_b32_sdwa", 2), ("v_lshl_add_u32", 1), ("v_add_u32", 1), ("v_mad_u32_u24", 1),
                          ("v_add_f64", 5), ("v_mul_f64", 6), ("v_cmp_lt_f64 vcc", 1)],
-    # ... a lane near a boundary: the reference's own index arithmetic instead of the look-up cell (replaces 5)
+    # ... a lane near a boundary: the reference's own index arithmetic and the cell's place in the window instead of
+    # the look-up cell (replaces 3)
     "reference_index (extra)": [("v_add_f64", 2), ("v_mul_f64", 2), ("v_cmp_lt_f64 vcc", 4), ("v_cvt_u32_f64", 2),
-                                ("v_mad_u64_u32", 1), ("v_mov_b32 from sgpr", 1), ("v_cndmask_b32 vcc", 1),
-                                ("v_lshrrev_b32_sdwa", -2), ("v_mul_u32_u24", -1), ("v_add3_u32", -1),
-                                ("v_cndmask_b32 sgpr", -1)],
+                                ("v_add_u32", 2), ("v_cmp_le_u32 vcc", 2), ("v_lshl_add_u32", 1),
+                                ("v_mov_b32 from sgpr", 1), ("v_cndmask_b32 vcc", 1),
+                                ("v_lshrrev_b32_sdwa", -2), ("v_lshl_add_u32", -1)],
     # exp() and the sum
     "exp_and_add": [("v_max_f64", 1), ("v_mul_f64", 1), ("v_rndne_f64", 1), ("v_fmac_f64", 2), ("v_fma_f64", 11),
                     ("v_cvt_i32_f64", 1), ("v_cmp_lt_f64 vcc", 1), ("v_ldexp_f64", 1), ("v_add_f64", 1)],

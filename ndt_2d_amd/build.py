@@ -25,7 +25,7 @@ SOURCES = ["ndt2d_kernels.hip", "ndt2d_match_lane.hip", "ndt2d_match_small.hip",
            "device/ndt2d_context.hip", "device/ndt2d_context_grid.hip", "device/ndt2d_context_search.hip", "device/ndt2d_context_poses.hip", "device/ndt2d_context_scan.hip",
            "resample/ndt2d_resample.hip", "occupancy_map/ndt2d_occupancy_map.hip", "seed/ndt2d_seed.hip", "clearance/ndt2d_clearance.hip", "cluster/ndt2d_cluster.hip", "build_small/ndt2d_build_small.hip", "closure/ndt2d_closure.hip", "starts/ndt2d_starts.hip", "wide/ndt2d_wide.hip", "scans/ndt2d_scans.hip", "refine/ndt2d_refine.hip", "verify/ndt2d_verify.hip", "posegraph/ndt2d_posegraph.hip", "posegraph/ndt2d_posegraph_robust.hip", "posegraph/ndt2d_posegraph_marginals.hip", "covariance/ndt2d_covariance.hip", "direct/ndt2d_direct.hip", "sparse/ndt2d_sparse.hip", "sparsecov/ndt2d_sparsecov.hip", "ndt2d_host.cpp",
            "host/ndt2d_host_ndt.cpp", "host/ndt2d_multi.cpp", "host/ndt2d_batched.cpp", "host/ndt2d_kld.cpp", "host/ndt2d_synth.cpp"]
-HEADERS = [os.path.join(_CSRC, "ndt2d_kernels.h"), os.path.join(_CSRC, "ndt2d_device_fn.h"), os.path.join(_CSRC, "ndt2d_lane_fn.h"), os.path.join(_CSRC, "ndt2d_near_bits.h"), os.path.join(_CSRC, "ndt2d_pretest_level.h"), os.path.join(_CSRC, "ndt2d_poses_fn.h"), os.path.join(_CSRC, "ndt2d_exchange.h"), os.path.join(_CSRC, "ndt2d_eigen2.h"), os.path.join(_CSRC, "build_small", "ndt2d_build_fn.h"), os.path.join(_CSRC, "build_small", "ndt2d_build_small_fn.h"), os.path.join(_CSRC, "ndt2d_workers.h"), os.path.join(_CSRC, "ndt2d_guard.h"), os.path.join(_CSRC, "batch", "ndt2d_sum_chunks.h"), os.path.join(_CSRC, "batch", "ndt2d_walk_fn.h"), os.path.join(_CSRC, "batch", "ndt2d_job_groups.h"), os.path.join(_CSRC, "batch", "ndt2d_stage_layout.h"), os.path.join(_CSRC, "batch", "ndt2d_batch_search.h"), os.path.join(_CSRC, "batch", "ndt2d_installed_map.h"), os.path.join(_CSRC, "batch", "ndt2d_batch_state.h"), os.path.join(_CSRC, "batch", "ndt2d_batch_host.h"), os.path.join(_CSRC, "batch", "ndt2d_refine_jobs.h"), os.path.join(_CSRC, "refine", "ndt2d_refine_step.h"), os.path.join(_CSRC, "verify", "ndt2d_verify_ray.h"), os.path.join(_CSRC, "posegraph", "ndt2d_posegraph_fn.h"), os.path.join(_CSRC, "posegraph", "ndt2d_posegraph_chain.h"), os.path.join(_CSRC, "posegraph", "ndt2d_posegraph_loss.h"), os.path.join(_CSRC, "posegraph", "ndt2d_posegraph_relative.h"), os.path.join(_CSRC, "posegraph", "ndt2d_posegraph_kernel.h"), os.path.join(_CSRC, "posegraph", "ndt2d_posegraph_state.h"), os.path.join(_CSRC, "posegraph", "ndt2d_posegraph_args.h"), os.path.join(_CSRC, "covariance", "ndt2d_covariance_plan.h"), os.path.join(_CSRC, "covariance", "ndt2d_covariance_kernel.h"), os.path.join(_CSRC, "covariance", "ndt2d_covariance_launch.h"), os.path.join(_CSRC, "direct", "ndt2d_direct_step.h"), os.path.join(_CSRC, "direct", "ndt2d_direct_plan.h"), os.path.join(_CSRC, "direct", "ndt2d_direct_kernel.h"), os.path.join(_CSRC, "sparse", "ndt2d_sparse_plan.h"), os.path.join(_CSRC, "sparse", "ndt2d_sparse_schur.h"), os.path.join(_CSRC, "sparse", "ndt2d_sparse_kernel.h"), os.path.join(_CSRC, "sparsecov", "ndt2d_sparsecov_plan.h"), os.path.join(_CSRC, "sparsecov", "ndt2d_sparsecov_select.h"), os.path.join(_CSRC, "sparsecov", "ndt2d_sparsecov_kernel.h"), os.path.join(_CSRC, "seed", "ndt2d_seed_fn.h"), os.path.join(_CSRC, "clearance", "ndt2d_clearance_fn.h"), os.path.join(_CSRC, "cluster", "ndt2d_cluster_fn.h"), os.path.join(_CSRC, "wide", "ndt2d_wide_fn.h"), os.path.join(_CSRC, "closure", "ndt2d_closure_jobs.h"), os.path.join(_CSRC, "host", "ndt2d_host_ndt.h"), os.path.join(_CSRC, "host", "ndt2d_matcher_state.h"), os.path.join(_CSRC, "host", "ndt2d_job_batch.h"), os.path.join(_CSRC, "device", "ndt2d_context.h"), os.path.join(_CSRC, "refine", "ndt2d_refine_kernel.h"), os.path.join(_CSRC, "verify", "ndt2d_verify_kernel.h"), os.path.join(_CSRC, "particles", "ndt2d_philox.h"), os.path.join(_CSRC, "particles", "ndt2d_compact_fn.h"), os.path.join(_CSRC, "particles", "ndt2d_compact.h"), os.path.join(_CSRC, "particles", "ndt2d_key_table.h"), os.path.join(_CSRC, "particles", "ndt2d_device_object.h"), os.path.join(_ROOT, "include", "ndt2d_hip.h")]
+HEADERS = [os.path.join(_CSRC, "ndt2d_kernels.h"), os.path.join(_CSRC, "ndt2d_device_fn.h"), os.path.join(_CSRC, "ndt2d_lane_fn.h"), os.path.join(_CSRC, "ndt2d_near_bits.h"), os.path.join(_CSRC, "ndt2d_address_table.h"), os.path.join(_CSRC, "ndt2d_pretest_level.h"), os.path.join(_CSRC, "ndt2d_poses_fn.h"), os.path.join(_CSRC, "ndt2d_exchange.h"), os.path.join(_CSRC, "ndt2d_eigen2.h"), os.path.join(_CSRC, "build_small", "ndt2d_build_fn.h"), os.path.join(_CSRC, "build_small", "ndt2d_build_small_fn.h"), os.path.join(_CSRC, "ndt2d_workers.h"), os.path.join(_CSRC, "ndt2d_guard.h"), os.path.join(_CSRC, "batch", "ndt2d_sum_chunks.h"), os.path.join(_CSRC, "batch", "ndt2d_walk_fn.h"), os.path.join(_CSRC, "batch", "ndt2d_job_groups.h"), os.path.join(_CSRC, "batch", "ndt2d_stage_layout.h"), os.path.join(_CSRC, "batch", "ndt2d_batch_search.h"), os.path.join(_CSRC, "batch", "ndt2d_installed_map.h"), os.path.join(_CSRC, "batch", "ndt2d_batch_state.h"), os.path.join(_CSRC, "batch", "ndt2d_batch_host.h"), os.path.join(_CSRC, "batch", "ndt2d_refine_jobs.h"), os.path.join(_CSRC, "refine", "ndt2d_refine_step.h"), os.path.join(_CSRC, "verify", "ndt2d_verify_ray.h"), os.path.join(_CSRC, "posegraph", "ndt2d_posegraph_fn.h"), os.path.join(_CSRC, "posegraph", "ndt2d_posegraph_chain.h"), os.path.join(_CSRC, "posegraph", "ndt2d_posegraph_loss.h"), os.path.join(_CSRC, "posegraph", "ndt2d_posegraph_relative.h"), os.path.join(_CSRC, "posegraph", "ndt2d_posegraph_kernel.h"), os.path.join(_CSRC, "posegraph", "ndt2d_posegraph_state.h"), os.path.join(_CSRC, "posegraph", "ndt2d_posegraph_args.h"), os.path.join(_CSRC, "covariance", "ndt2d_covariance_plan.h"), os.path.join(_CSRC, "covariance", "ndt2d_covariance_kernel.h"), os.path.join(_CSRC, "covariance", "ndt2d_covariance_launch.h"), os.path.join(_CSRC, "direct", "ndt2d_direct_step.h"), os.path.join(_CSRC, "direct", "ndt2d_direct_plan.h"), os.path.join(_CSRC, "direct", "ndt2d_direct_kernel.h"), os.path.join(_CSRC, "sparse", "ndt2d_sparse_plan.h"), os.path.join(_CSRC, "sparse", "ndt2d_sparse_schur.h"), os.path.join(_CSRC, "sparse", "ndt2d_sparse_kernel.h"), os.path.join(_CSRC, "sparsecov", "ndt2d_sparsecov_plan.h"), os.path.join(_CSRC, "sparsecov", "ndt2d_sparsecov_select.h"), os.path.join(_CSRC, "sparsecov", "ndt2d_sparsecov_kernel.h"), os.path.join(_CSRC, "seed", "ndt2d_seed_fn.h"), os.path.join(_CSRC, "clearance", "ndt2d_clearance_fn.h"), os.path.join(_CSRC, "cluster", "ndt2d_cluster_fn.h"), os.path.join(_CSRC, "wide", "ndt2d_wide_fn.h"), os.path.join(_CSRC, "closure", "ndt2d_closure_jobs.h"), os.path.join(_CSRC, "host", "ndt2d_host_ndt.h"), os.path.join(_CSRC, "host", "ndt2d_matcher_state.h"), os.path.join(_CSRC, "host", "ndt2d_job_batch.h"), os.path.join(_CSRC, "device", "ndt2d_context.h"), os.path.join(_CSRC, "refine", "ndt2d_refine_kernel.h"), os.path.join(_CSRC, "verify", "ndt2d_verify_kernel.h"), os.path.join(_CSRC, "particles", "ndt2d_philox.h"), os.path.join(_CSRC, "particles", "ndt2d_compact_fn.h"), os.path.join(_CSRC, "particles", "ndt2d_compact.h"), os.path.join(_CSRC, "particles", "ndt2d_key_table.h"), os.path.join(_CSRC, "particles", "ndt2d_device_object.h"), os.path.join(_ROOT, "include", "ndt2d_hip.h")]
 ARCH = "gfx950"
 # -ffp-contract=off: the reference's x86-64 build has no fused multiply-add; the
 # kernels keep its separate roundings (see DESIGN.md "Numerics").

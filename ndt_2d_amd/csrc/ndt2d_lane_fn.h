@@ -7,6 +7,7 @@
 
 #include <cmath>
 
+#include "ndt2d_address_table.h"
 #include "ndt2d_device_fn.h"
 #include "ndt2d_near_bits.h"
 #include "ndt2d_pretest_level.h"
@@ -22,6 +23,12 @@ constexpr int kPatch = 8;            // patch is kPatch x kPatch candidates = on
 #define NDT2D_LANE_UNROLL 8
 #endif
 constexpr int kUnroll = NDT2D_LANE_UNROLL;  // beams per look-up group (a divisor of 64)
+// A/B switch of the window table of record addresses (ndt2d_address_table.h, DESIGN.md 3.1,
+// profiles/address_table_ab.json); =0 is the code as it was: the compacted-records forms of the large
+// search go from the look-up cell to its record through the grid's cell -> rank table.
+#ifndef NDT2D_LANE_ADDRESS_TABLE
+#define NDT2D_LANE_ADDRESS_TABLE 1
+#endif
 // A/B switch of the beam table's near_bits word (profiles/near_bits_ab.json); =0 is
 // the code as it was: the near-boundary test of every live beam.
 #ifndef NDT2D_LANE_NEAR_BITS
@@ -427,6 +434,12 @@ struct LaneCtx
   // idx_bias = (pad - win_y0) * size_x + (pad - win_x0), modulo 2^32
   uint32_t idx_bias;
   uint32_t size_x;
+  // TABLE: the window table of record addresses (ndt2d_address_table.h) instead of the rank
+  // table -- its LDS byte address, its shape, and pad - win_x0, pad - win_y0 (modulo 2^32) for the
+  // near-boundary path
+  uint32_t table_address;
+  AddressTableShape table;
+  uint32_t win_off_x, win_off_y;
 };
 
 // U consecutive beams of one patch; o[] holds their table rows, dxy the lane's
@@ -445,6 +458,12 @@ __device__ __forceinline__ uint32_t lds_u16_at(uint32_t address)
 {
   typedef const __attribute__((address_space(3))) uint16_t * lds_u16_ptr;
   return *reinterpret_cast<lds_u16_ptr>(address);
+}
+
+__device__ __forceinline__ uint32_t lds_u32_at(uint32_t address)
+{
+  typedef const __attribute__((address_space(3), aligned(4))) uint32_t * lds_u32_ptr;
+  return *reinterpret_cast<lds_u32_ptr>(address);
 }
 
 // Lanes whose 16-bit fraction (the low half of v), biased by kNearUnits, is below
@@ -556,6 +575,38 @@ __device__ __forceinline__ double lds_record_exponent(uint32_t cells_address, ui
   return record_exponent(rec[0], rec[1], rec[2], rec[3], rec[4], px, py);
 }
 
+// ... against the packed record AT an LDS byte address (an entry of the window table of record addresses).
+__device__ __forceinline__ double lds_record_exponent_at(uint32_t record_address, double px, double py)
+{
+  typedef const __attribute__((address_space(3), aligned(16))) double * lds_double_ptr;
+  const lds_double_ptr rec = reinterpret_cast<lds_double_ptr>(record_address);
+  return record_exponent(rec[0], rec[1], rec[2], rec[3], rec[4], px, py);
+}
+
+// cell_index() (NDT::getIndex, the same lines) for the window table: the entry of the point's cell,
+// or of "outside" where cell_index gives ncell.
+template <bool POW2>
+__device__ __forceinline__ uint32_t window_table_entry(const GridDesc & g, const LaneCtx & c, double px, double py)
+{
+  const double tx = px - g.origin_x;
+  const double ty = py - g.origin_y;
+  double fx, fy;
+  if (POW2)
+  {
+    fx = tx * g.inv_cell_size;
+    fy = ty * g.inv_cell_size;
+  }
+  else
+  {
+    fx = tx / g.cell_size;
+    fy = ty / g.cell_size;
+  }
+  const bool inside = (tx >= 0.0) & (ty >= 0.0) & (fx < static_cast<double>(g.size_x)) &
+                      (fy < static_cast<double>(g.size_y));
+  return address_table_entry_of_cell(c.table, c.win_off_x, c.win_off_y, inside, static_cast<uint32_t>(fx),
+                                     static_cast<uint32_t>(fy));
+}
+
 // Per-lane skip state.  Terms whose exponent is below skip_below cannot change
 // the lane's sum (bit-exact skip); skip_level is the same threshold on the map's
 // scale, pre-shifted to the byte's layout: a map byte below it promises an
@@ -588,12 +639,15 @@ __device__ __forceinline__ SkipState skip_state(double sum, int32_t no_skip)
 // (the small search broadcasts them from LDS).
 // COMPACT (with LDS_RECORDS): the LDS records are the compacted ones, addressed through
 // the cell -> record table at c.rank_address (uint16 per grid cell, also in LDS).
+// TABLE (with COMPACT; the bytes of an entry, 0: none): ... through the window table at c.table_address
+// instead (ndt2d_address_table.h): the look-up's cell bytes select the entry, the entry is the record's
+// address (kAddressEntryBytes) or its rank (kRankEntryBytes).
 // near_possible: bit u says that beam u may have a lane near a cell boundary (near_bits() of
 // the large search's table, a wave-uniform value); a beam whose bit is clear has none, and its
 // per-lane near test is not run.  Callers without such a table pass all ones.
 // Returns whether the group added a term to some lane's sum (the skip state was refreshed): a
 // wave-uniform flag.
-template <int U, bool POW2, bool LDS_RECORDS, bool SCALAR_ROWS = true, bool COMPACT = false>
+template <int U, bool POW2, bool LDS_RECORDS, bool SCALAR_ROWS = true, bool COMPACT = false, uint32_t TABLE = 0>
 __device__ __forceinline__ bool lane_beams(const GridDesc & g, const LaneCtx & c,
                                            const double4 (&o)[U], double dx, double dy,
                                            double dxy, double & sum, SkipState & skip,
@@ -668,7 +722,17 @@ __device__ __forceinline__ bool lane_beams(const GridDesc & g, const LaneCtx & c
           const double px = o[u].x + dx;
           const double py = o[u].y + dy;
           uint32_t idx;
-          if (near_mask != 0ull)
+          if (TABLE != 0)
+          {
+            static_assert(TABLE == 0 || (COMPACT && LDS_RECORDS), "the window table addresses the compacted LDS records");
+            static_assert(TABLE == 0 || TABLE == kAddressEntryBytes || TABLE == kRankEntryBytes, "entries of four bytes or one");
+            // interior of a cell: the look-up cell is the reference's cell, and its two bytes are
+            // the window's column and row
+            idx = near_mask != 0ull
+                    ? window_table_entry<POW2>(g, c, px, py)
+                    : address_table_entry(c.table, ((lo[u] >> 16) & 0xffu) >> c.sub_log2, ((hi[u] >> 8) & 0xffu) >> c.sub_log2);
+          }
+          else if (near_mask != 0ull)
           {
             idx = cell_index<POW2>(g, px, py);
           }
@@ -690,9 +754,12 @@ __device__ __forceinline__ bool lane_beams(const GridDesc & g, const LaneCtx & c
               idx = occ ? cell : g.ncell;
             }
           }
-          if (COMPACT) idx = lds_u16_at(c.rank_address + 2u * idx);
-          const double e = LDS_RECORDS ? lds_record_exponent(c.lds_cells_address, idx, px, py)
-                                       : indexed_exponent<false>(g, nullptr, idx, px, py);
+          if (COMPACT && TABLE == 0) idx = lds_u16_at(c.rank_address + 2u * idx);
+          if (TABLE == kRankEntryBytes) idx = lds_byte_at(c.table_address + idx);
+          const double e = TABLE == kAddressEntryBytes
+                             ? lds_record_exponent_at(lds_u32_at(c.table_address + 4u * idx), px, py)
+                             : LDS_RECORDS ? lds_record_exponent(c.lds_cells_address, idx, px, py)
+                                           : indexed_exponent<false>(g, nullptr, idx, px, py);
 #ifdef NDT2D_LANE_HIST
           // experiments/lane_useful_hist.py: how many lanes of an exact evaluation matter.
           // hist[k]: evaluations with k lanes flagged (live and occupied or near a boundary);

@@ -263,8 +263,12 @@ __device__ __forceinline__ double no_index_here()
 
 // NEAR: the search reads the table's near_bits word (lane_reads_near_bits(): the launcher picks
 // the instantiation); false is the search as it was, every live beam takes the per-lane near test.
+// TABLE (the compacted six-wave forms; the bytes of an entry): the block stages the window table of record
+// addresses, or of ranks in a byte (ndt2d_address_table.h), where the others copy the grid's cell -> rank
+// table, and an exact evaluation reads its record's address (rank) from it; 0 is the search as it was (the
+// launcher picks the instantiation: the widest entry with which two blocks' images still fit a CU).
 template <int THREADS, bool POW2, bool LDS_RECORDS, bool DYNAMIC_ITEMS, bool COMPACT, bool PARTS = false,
-          bool STRIPS = false, bool NEAR = false>
+          bool STRIPS = false, bool NEAR = false, uint32_t TABLE = 0>
 __device__ __forceinline__ void match_lane_body(
   const MatchArgs & a, const double4 * __restrict__ outer, const uint8_t * __restrict__ map_image,
   const LaneGeom & geo)
@@ -282,17 +286,42 @@ __device__ __forceinline__ void match_lane_body(
   // lds_byte_at() addresses the map absolutely: it must start at LDS offset 0 -- no static
   // __shared__ in this kernel (the launcher checks: prepare_absolute_lds_kernel)
   const uint32_t map_bytes = static_cast<uint32_t>(geo.map_h) * kMapStride;
-  const uint32_t rank_bytes = COMPACT ? compact_rank_bytes(g.ncell) : 0u;
+  static_assert(TABLE == 0 || COMPACT, "the window table of record addresses: the compacted-records forms only");
+  const AddressTableShape table = address_table_shape(geo.win_w, geo.win_h, geo.pad);
+  const uint32_t rank_bytes = TABLE != 0 ? address_table_bytes(table, TABLE) : (COMPACT ? compact_rank_bytes(g.ncell) : 0u);
   double * lds_cells = lds + (map_bytes + rank_bytes) / sizeof(double);
 
   if (COMPACT)
   {
-    const uint4 * src_rank = reinterpret_cast<const uint4 *>(g.cell_rank);
-    uint4 * dst_rank = reinterpret_cast<uint4 *>(lds_map + map_bytes + kRankLead);
-    for (uint32_t i = threadIdx.x; i < (rank_bytes - kRankLead) / 16; i += THREADS) dst_rank[i] = src_rank[i];
-    if (threadIdx.x == 0)
+    if (TABLE != 0)
     {
-      reinterpret_cast<uint16_t *>(lds_map + map_bytes + kRankLead)[-1] = static_cast<uint16_t>(g.n_occ);
+      // an entry per cell of the padded window (and "outside"): the LDS address of the cell's record, or
+      // its rank, from the grid's own cell -> rank table
+      const uint32_t n_entries = address_table_entries(table);
+      for (uint32_t i = threadIdx.x; i < n_entries; i += THREADS)
+      {
+        const uint32_t rank =
+          address_table_rank(g.cell_rank, g.size_x, g.size_y, g.n_occ, geo.win_x0, geo.win_y0, geo.pad, table, i);
+        if (TABLE == kRankEntryBytes)
+        {
+          lds_map[map_bytes + i] = static_cast<uint8_t>(rank);
+        }
+        else
+        {
+          reinterpret_cast<uint32_t *>(lds_map + map_bytes)[i] =
+            address_table_value(map_bytes + rank_bytes, rank, static_cast<uint32_t>(kCellDoubles * sizeof(double)));
+        }
+      }
+    }
+    else
+    {
+      const uint4 * src_rank = reinterpret_cast<const uint4 *>(g.cell_rank);
+      uint4 * dst_rank = reinterpret_cast<uint4 *>(lds_map + map_bytes + kRankLead);
+      for (uint32_t i = threadIdx.x; i < (rank_bytes - kRankLead) / 16; i += THREADS) dst_rank[i] = src_rank[i];
+      if (threadIdx.x == 0)
+      {
+        reinterpret_cast<uint16_t *>(lds_map + map_bytes + kRankLead)[-1] = static_cast<uint16_t>(g.n_occ);
+      }
     }
     const uint32_t n2 = (g.n_occ + 1) * kCellDoubles / 2;
     const double2 * src = reinterpret_cast<const double2 *>(g.compact_records);
@@ -328,6 +357,10 @@ __device__ __forceinline__ void match_lane_body(
   c.idx_bias = static_cast<uint32_t>(geo.pad - geo.win_y0) * g.size_x +
                static_cast<uint32_t>(geo.pad - geo.win_x0);
   c.size_x = g.size_x;
+  c.table_address = map_bytes;
+  c.table = table;
+  c.win_off_x = static_cast<uint32_t>(geo.pad - geo.win_x0);
+  c.win_off_y = static_cast<uint32_t>(geo.pad - geo.win_y0);
 
   const uint32_t lane = threadIdx.x & (kWave - 1);
   const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -497,8 +530,8 @@ __device__ __forceinline__ void match_lane_body(
         // unflagged groups or reducing an item's records are not: issue priority while the
         // group is evaluated (cfg-2: - 3 %).
         __builtin_amdgcn_s_setprio(3);
-        if (lane_beams<kUnroll, POW2, LDS_RECORDS, true, COMPACT>(g, c, o, dx, dy, dxy, sum, skip, geo.no_skip,
-                                                                  NEAR ? static_cast<uint32_t>(near_chunk) : ~0u))
+        if (lane_beams<kUnroll, POW2, LDS_RECORDS, true, COMPACT, TABLE>(
+              g, c, o, dx, dy, dxy, sum, skip, geo.no_skip, NEAR ? static_cast<uint32_t>(near_chunk) : ~0u))
         {
           level_min |= 1u;
         }
@@ -508,8 +541,8 @@ __device__ __forceinline__ void match_lane_body(
       {
         if ((can_score & 1ull) == 0ull) continue;
         const double4 one[1] = {row[b]};
-        if (lane_beams<1, POW2, LDS_RECORDS, true, COMPACT>(g, c, one, dx, dy, dxy, sum, skip, geo.no_skip,
-                                                            NEAR ? static_cast<uint32_t>(near_chunk) : ~0u))
+        if (lane_beams<1, POW2, LDS_RECORDS, true, COMPACT, TABLE>(
+              g, c, one, dx, dy, dxy, sum, skip, geo.no_skip, NEAR ? static_cast<uint32_t>(near_chunk) : ~0u))
         {
           level_min |= 1u;
         }
@@ -695,12 +728,13 @@ __global__ void __launch_bounds__(THREADS) match_lane_kernel(
 // per SIMD (a block's waves must spread evenly over the four SIMDs: 640-thread blocks
 // would put six waves of two blocks on one SIMD, which its register file cannot hold).
 // NEAR (the six-wave kernels here and below): the near_bits word is read, see match_lane_body.
-template <bool STRIPS, bool NEAR>
+// TABLE (this kernel and its beam-part form): the window table of record addresses, see match_lane_body.
+template <bool STRIPS, bool NEAR, uint32_t TABLE>
 __global__ void __launch_bounds__(kLaneThreadsCompact) __attribute__((amdgpu_waves_per_eu(NDT2D_LANE_COMPACT_WAVES_PER_EU)))
 match_lane_compact_kernel(const MatchArgs a, const double4 * __restrict__ outer,
                           const uint8_t * __restrict__ map_image, const LaneGeom geo)
 {
-  match_lane_body<kLaneThreadsCompact, true, true, true, true, false, STRIPS, NEAR>(a, outer, map_image, geo);
+  match_lane_body<kLaneThreadsCompact, true, true, true, true, false, STRIPS, NEAR, TABLE>(a, outer, map_image, geo);
 }
 
 // Maps too large for LDS (records gathered from the 64-byte-stride HBM copy through L2):
@@ -715,12 +749,12 @@ match_lane_gather6_kernel(const MatchArgs a, const double4 * __restrict__ outer,
 }
 
 // The beam-part forms of the two six-wave kernels (mid-size lattices, MatchArgs::beam_parts).
-template <bool NEAR>
+template <bool NEAR, uint32_t TABLE>
 __global__ void __launch_bounds__(kLaneThreadsCompact) __attribute__((amdgpu_waves_per_eu(NDT2D_LANE_COMPACT_WAVES_PER_EU)))
 match_lane_compact_parts_kernel(const MatchArgs a, const double4 * __restrict__ outer,
                                 const uint8_t * __restrict__ map_image, const LaneGeom geo)
 {
-  match_lane_body<kLaneThreadsCompact, true, true, true, true, true, false, NEAR>(a, outer, map_image, geo);
+  match_lane_body<kLaneThreadsCompact, true, true, true, true, true, false, NEAR, TABLE>(a, outer, map_image, geo);
 }
 
 template <bool POW2, bool NEAR>
@@ -965,6 +999,32 @@ hipError_t launch_match_lane(const MatchArgs & args_in, double * outer, double *
   if (blocks > max_blocks) blocks = max_blocks;
   if (blocks == 0) blocks = 1;
   const bool compact = !small && compact_possible;
+  // The compacted forms with the window table of record addresses in the rank table's place
+  // (ndt2d_address_table.h), where the image still fits two blocks per CU with it and the map is no
+  // coarser than the grid (a window of blocks of cells has no byte per cell); otherwise, and with
+  // NDT2D_LANE_ADDRESS_TABLE=0 (the A/B knob), the rank table's instantiation.  Both read the same
+  // record for every point: no score bit depends on which one runs.
+  // Entries of four bytes (the address) where that fits, else of one (the rank, fewer than 256 records).
+  const AddressTableShape table_shape = address_table_shape(geo.win_w, geo.win_h, geo.pad);
+  const size_t records_bytes = (static_cast<size_t>(args.grid.n_occ) + 1) * kCellDoubles * sizeof(double);
+  const char * knob_table = std::getenv("NDT2D_LANE_ADDRESS_TABLE");
+  uint32_t table_entry_bytes = 0;
+  if (NDT2D_LANE_ADDRESS_TABLE != 0 && compact && geo.block_log2 == 0 && !(knob_table != nullptr && knob_table[0] == '0'))
+  {
+    if (2 * (map_bytes + address_table_bytes(table_shape, kAddressEntryBytes) + records_bytes) <= lds_per_block &&
+        !(knob_table != nullptr && knob_table[0] == '1'))   // (=1: one-byte entries although four would fit, for A/B runs)
+    {
+      table_entry_bytes = kAddressEntryBytes;
+    }
+    else if (args.grid.n_occ + 1u <= kRankEntryMaxRecords &&
+             2 * (map_bytes + address_table_bytes(table_shape, kRankEntryBytes) + records_bytes) <= lds_per_block)
+    {
+      table_entry_bytes = kRankEntryBytes;
+    }
+  }
+  const bool address_table = table_entry_bytes != 0;
+  const size_t table_image_bytes =
+    map_bytes + (address_table ? address_table_bytes(table_shape, table_entry_bytes) : 0) + records_bytes;
   const bool gather6 = !compact && !small && gather6_possible;
   // 0: records gathered from HBM, 1: the whole grid's records in LDS, 2: compacted records in LDS
   // (+4: the map is one byte per block of grid cells)
@@ -974,7 +1034,7 @@ hipError_t launch_match_lane(const MatchArgs & args_in, double * outer, double *
   }
   if (compact || gather6)
   {
-    lds_bytes = compact ? map_bytes + compact_bytes : map_bytes;
+    lds_bytes = compact ? (address_table ? table_image_bytes : map_bytes + compact_bytes) : map_bytes;
     const uint32_t wpb = kLaneThreadsCompact / kWave;
     blocks = static_cast<uint32_t>((n_sub_items + wpb - 1) / wpb);
     uint32_t cap = 2 * static_cast<uint32_t>(cus);
@@ -1034,16 +1094,31 @@ hipError_t launch_match_lane(const MatchArgs & args_in, double * outer, double *
   // pre-kernel wrote it by.  Anywhere else they are the kernels they were.
   auto six_wave = [&](auto near_tag) -> hipError_t {
     constexpr bool N = decltype(near_tag)::value;
+    // (NDT2D_LANE_ADDRESS_TABLE=0: the table's instantiations are not built)
+    constexpr uint32_t A4 = NDT2D_LANE_ADDRESS_TABLE != 0 ? kAddressEntryBytes : 0u;
+    constexpr uint32_t A1 = NDT2D_LANE_ADDRESS_TABLE != 0 ? kRankEntryBytes : 0u;
+    if (compact && address_table && table_entry_bytes == kAddressEntryBytes)
+    {
+      if (beam_parts > 1) return launch(match_lane_compact_parts_kernel<N, A4>, kLaneThreadsCompact);
+      return strips ? launch(match_lane_compact_kernel<true, N, A4>, kLaneThreadsCompact)
+                    : launch(match_lane_compact_kernel<false, N, A4>, kLaneThreadsCompact);
+    }
+    if (compact && address_table)
+    {
+      if (beam_parts > 1) return launch(match_lane_compact_parts_kernel<N, A1>, kLaneThreadsCompact);
+      return strips ? launch(match_lane_compact_kernel<true, N, A1>, kLaneThreadsCompact)
+                    : launch(match_lane_compact_kernel<false, N, A1>, kLaneThreadsCompact);
+    }
     if (beam_parts > 1)
     {
-      return compact ? launch(match_lane_compact_parts_kernel<N>, kLaneThreadsCompact)
+      return compact ? launch(match_lane_compact_parts_kernel<N, 0u>, kLaneThreadsCompact)
                      : (pow2 ? launch(match_lane_gather6_parts_kernel<true, N>, kLaneThreadsCompact)
                              : launch(match_lane_gather6_parts_kernel<false, N>, kLaneThreadsCompact));
     }
     if (compact)
     {
-      return strips ? launch(match_lane_compact_kernel<true, N>, kLaneThreadsCompact)
-                    : launch(match_lane_compact_kernel<false, N>, kLaneThreadsCompact);
+      return strips ? launch(match_lane_compact_kernel<true, N, 0u>, kLaneThreadsCompact)
+                    : launch(match_lane_compact_kernel<false, N, 0u>, kLaneThreadsCompact);
     }
     return pow2 ? (strips ? launch(match_lane_gather6_kernel<true, true, N>, kLaneThreadsCompact)
                           : launch(match_lane_gather6_kernel<true, false, N>, kLaneThreadsCompact))
